@@ -435,8 +435,53 @@ def resident_thermo_rows(E, steps):
     return rows
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_SAMPLE_ATOMS = 262144   # x, v, f and tag of this many atoms in float64: 21 MB, under the 64 MB limit
+DUMP_SEED = 5081931
+
+
+def dump_outputs(dom, s, out_dir, last_step, energy_tallied, par):
+    """--dump-outputs: what the timed path hands its caller after its last step -- positions, velocities and forces of
+    the owned atoms (all of them, or a fixed seeded sample of DUMP_SAMPLE_ATOMS, in tag order: the device keeps its own
+    atom order) and, when that step tallied them, the potential energy and the virial.  Collective over the ranks;
+    rank 0 writes DIR/<name>.npy (float64).  Returns the description for the result line (rank 0) or None."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    k = min(s.n, DUMP_SAMPLE_ATOMS)
+    want = np.sort(s.tag if k == s.n else s.tag[rng.choice(s.n, size=k, replace=False)]).astype(np.int64)
+    tags = dom.tags_local.astype(np.int64)
+    got = dom.ctx.md_download(dom.nlocal, want=("x", "v", "f"))
+    keep = np.isin(tags, want)
+    part = (tags[keep], got["x"][keep], got["v"][keep], got["f"][keep])
+    th = dom.thermo()                       # (collective: energy and virial summed over the ranks)
+    parts = [part]
+    if par["dist"] is not None:
+        parts = [None] * par["world"]
+        par["dist"].all_gather_object(parts, part)
+    if par["rank"] != 0:
+        return None
+    tag = np.concatenate([p[0] for p in parts])
+    order = np.argsort(tag, kind="stable")
+    if not np.array_equal(tag[order], want):
+        raise RuntimeError("--dump-outputs: the owned atoms of the ranks are not the sampled atoms, each once")
+    arrays = {"tags": tag[order].astype(np.float64),
+              "positions": np.concatenate([p[1] for p in parts])[order],
+              "velocities": np.concatenate([p[2] for p in parts])[order],
+              "forces": np.concatenate([p[3] for p in parts])[order]}
+    if energy_tallied:
+        arrays["energy_virial"] = np.array([th["pe"], *th["virial"]], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "step": last_step, "atoms": s.n, "atoms_dumped": k, "sample_seed": DUMP_SEED if k < s.n else None,
+            "arrays": {name: list(a.shape) for name, a in arrays.items()}, "dtype": "float64",
+            "note": "owned atoms in tag order after the last timed step (`step`: MD steps since the start, overlap-policy "
+                    "trial and warm-up included); energy_virial = [pe, virial xx yy zz xy xz yz] "
+                    "when that step tallied them (thermo step)"}
+
+
 # ------------------------------------------------------------------------------------------------ one measured job
-def run_job(E, job, par):
+def run_job(E, job, par, dump_dir=None):
     """job: workload, replicate, temp, steps, warmup, thermo_every, check_every, inner_skin
     par: world, rank, local_rank, dist, dev, stage_host, native.  Returns (result dict, pieces for the host-mode leg)."""
     import numpy as np
@@ -543,6 +588,12 @@ def run_job(E, job, par):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if stage_host else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if dump_dir is not None:       # (outside the timed region, before the steps below move the atoms on)
+        # (the overlap-policy trial of the library transport moves the atoms too: its steps count)
+        last = job["warmup"] + job["steps"]
+        dumped = dump_outputs(dom, s, dump_dir, (overlap or {}).get("trial_steps", 0) + last,
+                              bool(thermo_every and last % thermo_every == 0), par)
 
     # ---- per-kernel time of the hot path: HIP events on the compute stream, force-only steps of the SAME Verlet loop
     # (same rebuild policy; steps that reneighbored are left out of the average) ----
@@ -705,6 +756,8 @@ def run_job(E, job, par):
         out["config"].update(nlocal_per_rank=m[:, 0].tolist(), self_ghosts_per_rank=m[:, 1].tolist(),
                              remote_ghosts_per_rank=m[:, 2].tolist(), halo_bytes_sent_per_step_per_rank=(m[:, 3] * 24).tolist(),
                              procgrid=list(dom.grid))
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     ctx.close()
     # (keep: the AEAM tables point into the potential-file object `af`, so it must outlive every user of `pot`)
     return out, dict(s=s, pot=pot, skin=skin, cutghost=cutghost, keep=getattr(ctx, "_af", None))
@@ -731,9 +784,17 @@ def main():
     ap.add_argument("--inner-skin", type=float, default=None,
                     help="skin of the style's own device-built lists in A (default: library default 1.0, capped by "
                          "the host skin); they are rebuilt on the device when an atom has moved half of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (positions, velocities, forces of "
+                         "a fixed seeded sample of the atoms in tag order; energy and virial on a thermo step) as "
+                         "DIR/<name>.npy, float64")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))      # the parent has made no GPU call; the children are fresh processes
     # stdout carries ONE line, the result.  Libraries print there too (RCCL writes a version banner to stdout when a
@@ -810,7 +871,7 @@ def main():
         job["disorder"] = dict(scale=args.strain[0], jitter=args.strain[1], seed=1234)
     if args.frac2 is not None and args.workload == "aeam":
         job["disorder"] = dict(frac2=args.frac2)
-    out, pieces = run_job(E, job, par)
+    out, pieces = run_job(E, job, par, dump_dir=args.dump_outputs)
     out["config"]["rccl_ranks"] = rccl_ranks
     if os.environ.get("MDP_BENCH_FALLBACK_REASON"):
         out["transport_fallback"] = os.environ["MDP_BENCH_FALLBACK_REASON"]

@@ -27,14 +27,11 @@ def _env(timeout="30"):
 
 @pytest.fixture(scope="module")
 def results(tmp_path_factory):
-    out = tmp_path_factory.mktemp("native_ranks") / "results.json"
-    log = os.path.join(ROOT, "gpurun_out", "native_ranks_child.log")
-    os.makedirs(os.path.dirname(log), exist_ok=True)
+    d = tmp_path_factory.mktemp("native_ranks")
+    out, log = d / "results.json", d / "child.log"
     with open(log, "w") as fh:
         p = subprocess.run([sys.executable, CHILD, str(out)], env=_env(), stdout=fh, stderr=subprocess.STDOUT, timeout=1500)
-    assert out.exists(), f"the child wrote nothing (exit {p.returncode}); see {log}"
-    import shutil
-    shutil.copy(out, os.path.join(ROOT, "gpurun_out", "native_ranks_results.json"))
+    assert out.exists(), f"the child wrote nothing (exit {p.returncode}); see {log}:\n{log.read_text()[-3000:]}"
     return json.load(open(out))
 
 
