@@ -455,6 +455,36 @@ int mdp_hnve_initial(mdp_ctx *ctx, int *moved, int *dangerous);
 int mdp_hnve_final(mdp_ctx *ctx);
 int mdp_hnve_download(mdp_ctx *ctx, double *x, double *v, double *f /* [nlocal][3] each, or NULL */);
 
+/* ---- Nose-Hoover chain thermostat on the device (LAMMPS fix nvt, thermostat only; the plugin style `fix nvt/mdp`) -----
+ * Once set, the integrate calls of this context apply it: the resident ones (initial / final / final_initial /
+ * integrate_check) and the host-mode ones (hnve initial / final).  Without it they run exactly the NVE code.  The chain
+ * (eta, eta_dot, eta_dotdot, masses) lives on the device; the temperature is a fixed-order reduction of per-block partial
+ * sums (bitwise reproducible) and the scale factor travels to the integrate kernel in device memory, so a step adds no
+ * host wait.  One rank only: a brick of several ranks refuses it (and refuses to become one while it is set).
+ *   setup: Tstart Tstop Tdamp, tchain (1..8) tloop drag, nf = degrees of freedom (3N - 3), boltz, mvv2e
+ *   run(first, last): the ramp of the next run (target T at step n: Tstart + (n-first)/(last-first) (Tstop-Tstart));
+ *                     the step counter starts at `first` and advances with every initial half; the chain masses and
+ *                     the temperature are set up again at the next initial half (LAMMPS FixNH::setup)
+ *   A final half deferred by the host (mdp_md_defer_final) completes inside mdp_nhc_run and mdp_nhc_off, at the target
+ *   of its own step.
+ *   state: out[MDP_NHC_STATE_LEN] = T, Tt, thermostat energy (ecouple), eta[8], eta_dot[9], eta_dotdot[8]
+ *          (the temperature / target / energy of the last half-update)
+ *   set_state: the same layout (T, Tt and the energy are ignored): seeds the chain, e.g. from an earlier run */
+#define MDP_NHC_STATE_LEN 28
+#define MDP_NHC_MAXCHAIN 8
+typedef struct {
+  double t_start, t_stop, t_period; /* temp Tstart Tstop Tdamp                                          */
+  int tchain, tloop;                /* chain length (1..8), sub-steps of each half-update               */
+  double drag;                      /* 0: none                                                          */
+  double nf;                        /* degrees of freedom of the group (3N - 3 for all atoms)           */
+  double boltz, mvv2e;              /* force->boltz, force->mvv2e                                       */
+} mdp_nhc_config;
+int mdp_nhc_setup(mdp_ctx *ctx, const mdp_nhc_config *cfg);
+int mdp_nhc_run(mdp_ctx *ctx, long long first, long long last);
+int mdp_nhc_state(mdp_ctx *ctx, double *out);
+int mdp_nhc_set_state(mdp_ctx *ctx, const double *in);
+int mdp_nhc_off(mdp_ctx *ctx);
+
 /* per-phase device time of the last compute in ms (HIP events on the compute stream):
  * rebomos: [0]=REBO centre kernels of the lane-group classes, [1]=the general kernel (centres that outgrew their lane
  * group since the list build), [2]=row pruning (0 unless one was due), [3]=LJ+gather kernel;

@@ -223,12 +223,15 @@ __global__ __launch_bounds__(256) void ang_select_kernel(const int nlocal, const
 // check yes` of the new positions against the positions of the last reneighboring in the same pass (what
 // dd_moved_kernel does in a pass of its own): flag[0] = some atom beyond the trigger, flag[1] = beyond half the skin.
 // SC: the style-level checks and the accumulator reset of the compute that follows, in the same pass (MdpStyleCheck).
-template <bool FINAL, bool CHECK>
+// SCALE: the thermostat's velocity factor *vscale between the two half-kicks (nhc.hip); the NVE instantiations
+// (SCALE = false) never read it, so their code is what it was without a thermostat.
+template <bool FINAL, bool CHECK, bool SCALE = false>
 __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const double *__restrict__ rmass,
                                    double *__restrict__ f, double *__restrict__ v, double4 *__restrict__ xq,
                                    const mdp_hold_t *__restrict__ xhold, const double trigsq, const double hardsq,
                                    int *__restrict__ flag, const MdpStyleCheck SC, const int zero_f,
-                                   double *__restrict__ dflag_set = nullptr, double *__restrict__ dflag_clear = nullptr)
+                                   double *__restrict__ dflag_set = nullptr, double *__restrict__ dflag_clear = nullptr,
+                                   const double *__restrict__ vscale = nullptr)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (CHECK && dflag_clear && i == 0) *dflag_clear = 0.0; // (the word of the next step; this step's was cleared a step ago)
@@ -257,6 +260,12 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
       vx += s * fx;
       vy += s * fy;
       vz += s * fz;
+    }
+    if (SCALE) { // the thermostat's factor (nhc.hip): final half of step n (if FINAL) times initial half of step n+1
+      const double S = *vscale;
+      vx *= S;
+      vy *= S;
+      vz *= S;
     }
     vx = vx + s * fx; // initial_integrate (step n+1)
     vy = vy + s * fy;
@@ -890,6 +899,8 @@ int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double
   if (c->final_deferred_seen && with_final && !c->final_pending) with_final = false;
   if (with_final) c->final_pending = false;
   const double dtf = 0.5 * c->cfg.dt * c->cfg.ftm2v;
+  const double *vscale = nullptr;
+  if (c->nhc.on) MDP_TRY(mdp_nhc_open(c, c->nlocal, dtf, c->cfg.dt, &with_final, &vscale));
   // aeam accumulates into f (three-body atomics, tile kernels): its force_clear rides in this kernel and in the refresh
   // of the images when every ghost is a periodic self-image (one GPU).  The flag is dropped by whatever rebuilds or
   // re-orders the atom arrays before the compute (mdp_aeam_prepare) -- the compute then clears f itself.
@@ -909,9 +920,15 @@ int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double
     const int g = nblk(c->nlocal);
     MdpStyleCheck sc;
     mdp_sflag_arm(c, sc);
+#define MDP_ADV1(FV, CV, SV)                                                                                          \
+  nve_advance_kernel<FV, CV, SV><<<g, 256, 0, c->stream>>>(c->nlocal, dtf, c->cfg.dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, \
+                                                      c->xhold.p, trigsq, hardsq, flag, sc, zero_f ? 1 : 0, dset, dclr, \
+                                                      vscale)
 #define MDP_ADV(FV, CV)                                                                                               \
-  nve_advance_kernel<FV, CV><<<g, 256, 0, c->stream>>>(c->nlocal, dtf, c->cfg.dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, \
-                                                      c->xhold.p, trigsq, hardsq, flag, sc, zero_f ? 1 : 0, dset, dclr)
+  do {                                                                                                                \
+    if (vscale) MDP_ADV1(FV, CV, true);                                                                               \
+    else MDP_ADV1(FV, CV, false);                                                                                     \
+  } while (0)
     if (with_final) {
       if (flag) MDP_ADV(true, true);
       else MDP_ADV(true, false);
@@ -920,6 +937,7 @@ int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double
       else MDP_ADV(false, false);
     }
 #undef MDP_ADV
+#undef MDP_ADV1
     c->acc_prezeroed = sc.acc != nullptr;
     // the flag words are complete behind this kernel unless remote ghosts arrive later in the step (mdp_md_unpack_x)
     if (!(c->remote_start < c->nall)) MDP_TRY(mdp_sflag_commit(c));
@@ -965,6 +983,7 @@ int mdp_md_final_integrate(mdp_ctx *c)
   if (!c->md) return mdp_fail(c, MDP_ESTATE, "mdp_md_setup not called");
   c->final_pending = false;
   const double dtf = 0.5 * c->cfg.dt * c->cfg.ftm2v;
+  if (c->nhc.on) return mdp_nhc_final(c, c->nlocal, dtf, c->cfg.dt);
   if (c->nlocal) nve_final_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, dtf, c->rmass.p, c->f.p, c->v.p);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
@@ -1149,8 +1168,16 @@ int mdp_hnve_initial(mdp_ctx *c, int *moved, int *dangerous)
     MdpStyleCheck sc;
     c->hn_deferred_check = !c->md && c->have_rebomos && !c->have_aeam && c->host_ghosts_derived;
     if (c->hn_deferred_check) mdp_sflag_arm(c, sc);
-    nve_advance_kernel<false, true><<<nblk(n), 256, 0, c->stream>>>(n, c->hn_dtf, c->hn_dt, c->rmass.p, c->f.p, c->v.p, c->xq.p,
-                                                                    c->xhold.p, trig * trig, hard * hard, h, sc, 0);
+    const double *vscale = nullptr;
+    bool with_final = false;
+    if (c->nhc.on) MDP_TRY(mdp_nhc_open(c, n, c->hn_dtf, c->hn_dt, &with_final, &vscale));
+    if (vscale)
+      nve_advance_kernel<false, true, true><<<nblk(n), 256, 0, c->stream>>>(n, c->hn_dtf, c->hn_dt, c->rmass.p, c->f.p, c->v.p,
+                                                                            c->xq.p, c->xhold.p, trig * trig, hard * hard, h,
+                                                                            sc, 0, nullptr, nullptr, vscale);
+    else
+      nve_advance_kernel<false, true><<<nblk(n), 256, 0, c->stream>>>(n, c->hn_dtf, c->hn_dt, c->rmass.p, c->f.p, c->v.p, c->xq.p,
+                                                                      c->xhold.p, trig * trig, hard * hard, h, sc, 0);
     MDP_HIP(c, hipGetLastError());
     if (c->hn_deferred_check && c->sflag_armed) { // one event behind the kernel serves both readers of its words
       MDP_TRY(mdp_sflag_commit(c));
@@ -1174,6 +1201,7 @@ int mdp_hnve_final(mdp_ctx *c)
   if (!c) return MDP_EINVAL;
   if (!c->hn_on || !c->hn_v_current) return mdp_fail(c, MDP_ESTATE, "mdp_hnve_upload_v not called for the current atoms");
   MDP_HIP(c, hipSetDevice(c->device));
+  if (c->nhc.on) return mdp_nhc_final(c, c->nlocal, c->hn_dtf, c->hn_dt);
   if (c->nlocal)
     nve_final_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, c->hn_dtf, c->rmass.p, c->f.p, c->v.p);
   MDP_HIP(c, hipGetLastError());

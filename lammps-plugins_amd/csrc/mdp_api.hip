@@ -934,6 +934,8 @@ int mdp_destroy(mdp_ctx *c)
       (void) hipEventDestroy(c->ev_sb[i]);
       (void) hipEventDestroy(c->ev_se[i]);
     }
+  c->nhc.st.release();
+  c->nhc.part.release();
   if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
   delete c;
   return MDP_OK;

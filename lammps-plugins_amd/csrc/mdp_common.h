@@ -253,6 +253,19 @@ struct MdpDomain {
 
 constexpr int MDP_UP_RING = 2;      // host-mode upload: pinned staging chunks in flight
 constexpr int MDP_DOWN_CHUNKS = 8;  // host-mode download: pieces of the force array
+// Nose-Hoover chain thermostat (nhc.hip): the chain lives in st on the device; the host keeps the step counter and the
+// ramp of the current run
+struct MdpNhc {
+  bool on = false;
+  bool need_setup = false;  // the next initial half sets the masses up again from the velocities (FixNH::setup)
+  mdp_nhc_config cfg;
+  long long first = 0, last = 0, step = 0;
+  double tt = 0.0;          // target temperature of the current step
+  DevBuf<double> st;        // [MDP_NHC_STATE_LEN] state (mdp_nhc_state layout), then Q[8], then the scale factor S
+  DevBuf<double> part;      // per-block partial sums of m v^2 (fixed slots: the reduction is bitwise reproducible)
+};
+static constexpr int kNhcQ = MDP_NHC_STATE_LEN, kNhcS = MDP_NHC_STATE_LEN + MDP_NHC_MAXCHAIN, kNhcWords = kNhcS + 1;
+
 struct mdp_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -416,6 +429,7 @@ struct mdp_ctx {
   MdpStyleCheck sflag_chk;
   MdpStyleCheckMeta sflag_meta[2];
   hipEvent_t ev_sflag[2] = {nullptr, nullptr};
+  MdpNhc nhc;                      // thermostat of the integrate calls (mdp_nhc_setup)
   bool final_pending = false;      // the host deferred the final half-kick of the finished step (mdp_md_defer_final)
   bool final_deferred_seen = false; // the host uses mdp_md_defer_final at all (older hosts: with_final is authoritative)
   bool acc_prezeroed = false; // the integrate kernel reset the accumulators: the next mdp_acc_begin launches nothing
@@ -540,6 +554,12 @@ int mdp_host_pinned_reserve(mdp_ctx *c, size_t ndoubles); // c->h_down: pinned d
 int mdp_host_upload(mdp_ctx *c, void *d_dst, const void *h_src, size_t bytes); // pageable host array -> device, pipelined through pinned staging
 int mdp_host_refresh_ghosts(mdp_ctx *c);                  // host mode, images kept by the library: owner + count * h of this step
 int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double hardsq); // integrate kernel (+ displacement check)
+// thermostat (nhc.hip), around the integrate kernels when c->nhc.on.  _open: before the kernel of an initial half (after
+// the pending final half if *with_final): the chain update(s) of the step; *vscale = the device word the integrate kernel
+// scales the velocities by.  (*with_final comes back false when the final half had to run on its own first.)
+// _final: a final half on its own (kick, chain update, velocity scaling).
+int mdp_nhc_open(mdp_ctx *c, int n, double dtf, double dt, bool *with_final, const double **vscale);
+int mdp_nhc_final(mdp_ctx *c, int n, double dtf, double dt);
 void mdp_host_add(double *dst, const double *src, size_t n); // dst += src, threaded for large arrays
 int mdp_host_download_add(mdp_ctx *c, double *h_dst, double *h_stage, const double *d_src, size_t n); // chunked D2H + add
 int mdp_to_host_order(mdp_ctx *c, int n, int w, const double *d_src, double *d_dst);   // per-atom arrays, device -> host order

@@ -45,6 +45,17 @@ class DdConfig(C.Structure):
                 ("cutghost", C.c_double), ("self_remote", C.c_int), ("nonperiodic", C.c_int * 3)]
 
 
+class NhcConfig(C.Structure):
+    """mirror of mdp_nhc_config"""
+    _fields_ = [("t_start", C.c_double), ("t_stop", C.c_double), ("t_period", C.c_double), ("tchain", C.c_int),
+                ("tloop", C.c_int), ("drag", C.c_double), ("nf", C.c_double), ("boltz", C.c_double),
+                ("mvv2e", C.c_double)]
+
+
+NHC_STATE_LEN, NHC_MAXCHAIN = 28, 8
+BOLTZ_METAL = 8.617343e-5    # force->boltz, metal units
+
+
 STYLE_REBOMOS, STYLE_AEAM = 1, 2
 EXPORTS = [
     "mdp_abi_version", "mdp_device_count", "mdp_create", "mdp_destroy", "mdp_last_error", "mdp_set_stream",
@@ -67,6 +78,7 @@ EXPORTS = [
     "mdp_dd_comm_forward_begin", "mdp_dd_comm_forward_end", "mdp_dd_comm_forward_scalar", "mdp_dd_comm_reverse",
     "mdp_dd_comm_allreduce", "mdp_dd_comm_step_begin", "mdp_dd_comm_step_end", "mdp_dd_comm_step_info", "mdp_aeam_device_lists", "mdp_rebomos_host_list", "mdp_aeam_check_host_list",
     "mdp_md_defer_final", "mdp_md_list_state", "mdp_md_aeam_force_begin", "mdp_md_aeam_state", "mdp_dd_comm_aeam_exchange_begin", "mdp_dd_comm_aeam_exchange_end",
+    "mdp_nhc_setup", "mdp_nhc_run", "mdp_nhc_state", "mdp_nhc_set_state", "mdp_nhc_off",
 ]
 
 
@@ -465,6 +477,29 @@ class Context:
         out = {k: np.zeros((nlocal, 3)) for k in want}
         self._ck(self.L.mdp_hnve_download(self.h, _dp(out.get("x")), _dp(out.get("v")), _dp(out.get("f"))))
         return out
+
+    # ---------------- Nose-Hoover chain thermostat of the integrate calls (fix nvt/mdp)
+    def nhc_setup(self, t_start, t_stop, t_period, nf, tchain=3, tloop=1, drag=0.0, boltz=BOLTZ_METAL, mvv2e=1.0364269e-4):
+        cfg = NhcConfig(t_start, t_stop, t_period, tchain, tloop, drag, nf, boltz, mvv2e)
+        self._ck(self.L.mdp_nhc_setup(self.h, C.byref(cfg)))
+
+    def nhc_run(self, first, last):
+        self._ck(self.L.mdp_nhc_run(self.h, C.c_longlong(first), C.c_longlong(last)))
+
+    def nhc_state(self):
+        """{"temp", "target", "energy", "eta"[8], "eta_dot"[9], "eta_dotdot"[8], "raw"} of the last half-update"""
+        out = np.zeros(NHC_STATE_LEN)
+        self._ck(self.L.mdp_nhc_state(self.h, _dp(out)))
+        return {"temp": out[0], "target": out[1], "energy": out[2], "eta": out[3:11].copy(), "eta_dot": out[11:20].copy(),
+                "eta_dotdot": out[20:28].copy(), "raw": out}
+
+    def nhc_set_state(self, raw):
+        raw = np.ascontiguousarray(raw, dtype=np.float64)
+        assert raw.shape == (NHC_STATE_LEN,)
+        self._ck(self.L.mdp_nhc_set_state(self.h, _dp(raw)))
+
+    def nhc_off(self):
+        self._ck(self.L.mdp_nhc_off(self.h))
 
     def md_class_stats(self):
         """how the last compute's work was spread over the kernel classes (see mdpair_hip.h)"""

@@ -387,6 +387,25 @@ class DeviceDomain:
         else:
             ctx.md_final_integrate()
 
+    def thermostat(self, t_start, t_stop, t_period, tchain=3, tloop=1, drag=0.0, first=0, last=0):
+        """Nose-Hoover chain thermostat (LAMMPS fix nvt on group all) in the integrate calls of this domain, from the
+        chain at rest; one GPU only.  first / last: the ramp of the run that follows (nhc_run)."""
+        if self.world > 1:
+            raise ValueError("the thermostat runs on one GPU only (multi-rank NVT would need a per-step all-reduce)")
+        self.ctx.nhc_setup(t_start, t_stop, t_period, 3.0 * self.natoms_total - 3.0, tchain=tchain, tloop=tloop,
+                           drag=drag, boltz=S.BOLTZ, mvv2e=S.MVV2E)
+        self.ctx.nhc_run(first, last)
+
+    def thermostat_off(self):
+        """back to NVE; a deferred final half completes inside mdp_nhc_off, with its chain update"""
+        self.ctx.nhc_off()
+        self._final_pending = False
+
+    def thermostat_state(self):
+        """the chain after the last half-update (completes a deferred final half first)"""
+        self.flush()
+        return self.ctx.nhc_state()
+
     def tune_overlap(self, max_steps=80):
         """library transport: force-only steps until the library's overlap-policy trial has chosen (comm_rccl.hip); returns
         the step info.  Collective: every rank runs the same steps."""

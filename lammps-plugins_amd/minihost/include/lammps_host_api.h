@@ -143,12 +143,14 @@ class Force {
   int newton_pair = 1;
   double ftm2v = 1.0 / 1.0364269e-4; // metal units
   double mvv2e = 1.0364269e-4;
+  double boltz = 8.617343e-5;
   Pair *pair = nullptr;
 };
 
 class Update { // the members of LAMMPS' Update a fix style reads
  public:
   bigint ntimestep = 0, laststep = 0;
+  bigint firststep = 0, beginstep = 0, endstep = 0; // the run's first / last step (`run N start/stop`: the ramp's ends)
   double dt = 0.001;
 };
 
@@ -280,6 +282,7 @@ class Fix : protected Pointers {
   int igroup = 0, groupbit = 1;
   int time_integrate = 0;
   int force_reneighbor = 0;     // 1: Neighbor::decide() reneighbors on the step next_reneighbor names
+  int ecouple_flag = 0;         // 1: compute_scalar() is energy the fix exchanges with a reservoir (thermo `ecouple`)
   bigint next_reneighbor = -1;
 
   Fix(LAMMPS *lmp, int narg, char **arg) : Pointers(lmp)
@@ -299,6 +302,7 @@ class Fix : protected Pointers {
   virtual void final_integrate() {}
   virtual void post_run() {}    // Modify::post_run(): behind the last step of every run
   virtual void reset_dt() {}
+  virtual double compute_scalar() { return 0.0; } // thermo f_ID
 };
 
 } // namespace LAMMPS_NS

@@ -890,6 +890,8 @@ struct Host {
           : c == "cellgamma"                                                                       ? "CellGamma"
           : c == "epair"                                                                           ? "E_pair"
           : c == "emol"                                                                            ? "E_mol"
+          : c == "ecouple"                                                                         ? "Ecouple"
+          : c == "econserve"                                                                       ? "Econserve"
                                                                                                    : c;
       char buf[32];
       snprintf(buf, sizeof buf, c == "step" ? "%6s    " : " %-14s", n.c_str());
@@ -897,6 +899,9 @@ struct Host {
     }
     printf("%s\n", s.c_str());
   }
+
+  // Modify::energy_couple(): what the fixes with ecouple_flag exchanged with their reservoirs
+  double ecouple() { return fix && fix->ecouple_flag ? fix->compute_scalar() : 0.0; }
 
   void print_thermo()
   {
@@ -917,6 +922,12 @@ struct Host {
         else if (c == "pe" || c == "epair") v = pe;
         else if (c == "ke") v = ke;
         else if (c == "etotal") v = pe + ke;
+        else if (c == "ecouple") v = ecouple();
+        else if (c == "econserve") v = pe + ke + ecouple();
+        else if (c.compare(0, 2, "f_") == 0) {
+          if (!fix || c.substr(2) != fix->id) error.all(FLERR, "Could not find thermo custom fix ID: " + c.substr(2));
+          v = fix->compute_scalar();
+        }
         else if (c == "vol") v = volume();
         else if (c == "cellgamma") {
           // angle between a and b edge vectors
@@ -965,6 +976,8 @@ struct Host {
     update.dt = dt;
     update.ntimestep = step;
     update.laststep = step + nsteps;
+    update.firststep = update.beginstep = step;
+    update.endstep = step + nsteps;
     skin = neighbor.skin;
     wrap_owned();
     if (np > 1 && !decomposed) decompose();
