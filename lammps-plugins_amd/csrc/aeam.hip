@@ -29,13 +29,6 @@ constexpr int AE_L = 8;      // lanes per atom in the list-streaming kernels
 constexpr int ANG_CAP = 160; // LDS slots per angular centre
 constexpr double kCutDec = 1.5; // pair_aeam.cpp:188
 
-template <int W> __device__ __forceinline__ double lane_sum(double v)
-{
-#pragma unroll
-  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // spline row + fractional coordinate (pair_aeam.cpp:195-201)
 __device__ __forceinline__ const double *spline_row(const double *__restrict__ tab, int table, int nmax1, double r,
                                                     double rdr, int nr, double &p)
@@ -168,7 +161,7 @@ __global__ __launch_bounds__(256) void aeam_density_kernel(const AeamDev A, cons
       }
     }
   }
-  acc = lane_sum<L>(acc);
+  acc = group_sum<L>(acc);
   if (have && metal && s == 0) rho[i] = acc;
 }
 
@@ -372,7 +365,7 @@ __global__ __launch_bounds__(256) void aeam_tile_density_kernel(
   segment(std::integral_constant<int, 0>{});
   segment(std::integral_constant<int, 1>{});
 #pragma unroll
-  for (int c = 0; c < CL; c++) acc[c] = lane_sum<L>(acc[c]);
+  for (int c = 0; c < CL; c++) acc[c] = group_sum<L>(acc[c]);
   if (s < CL) {
 #pragma unroll
     for (int c = 0; c < CL; c++)
@@ -561,16 +554,16 @@ __global__ __launch_bounds__(256) void aeam_tile_force_kernel(
   segment(std::integral_constant<int, 1>{});
 #pragma unroll
   for (int c = 0; c < CL; c++) {
-    fx[c] = lane_sum<L>(fx[c]);
-    fy[c] = lane_sum<L>(fy[c]);
-    fz[c] = lane_sum<L>(fz[c]);
+    fx[c] = group_sum<L>(fx[c]);
+    fy[c] = group_sum<L>(fy[c]);
+    fz[c] = group_sum<L>(fz[c]);
   }
   double ev_e = 0.0;
   if (EV) {
 #pragma unroll
     for (int c = 0; c < CL; c++) {
       ev_e += ea[c];
-      ea[c] = lane_sum<L>(ea[c]);
+      ea[c] = group_sum<L>(ea[c]);
     }
   }
   if (s < CL) {
@@ -587,16 +580,16 @@ __global__ __launch_bounds__(256) void aeam_tile_force_kernel(
   if (EV) {
     double *slot = acc + MDP_ACC_STRIDE * (1 + (blockIdx.x & (MDP_ACC_SLOTS - 1)));
     if (eflag & MDP_EFLAG_GLOBAL) {
-      ev_e = lane_sum<64>(ev_e);
+      ev_e = group_sum<64>(ev_e);
       if (lane == 0) atomicAdd(&slot[0], ev_e);
     }
     if (vflag & MDP_VFLAG_GLOBAL) {
-      v0 = lane_sum<64>(v0);
-      v1 = lane_sum<64>(v1);
-      v2 = lane_sum<64>(v2);
-      v3 = lane_sum<64>(v3);
-      v4 = lane_sum<64>(v4);
-      v5 = lane_sum<64>(v5);
+      v0 = group_sum<64>(v0);
+      v1 = group_sum<64>(v1);
+      v2 = group_sum<64>(v2);
+      v3 = group_sum<64>(v3);
+      v4 = group_sum<64>(v4);
+      v5 = group_sum<64>(v5);
       if (lane == 0) {
         atomicAdd(&slot[1], v0);
         atomicAdd(&slot[2], v1);
@@ -906,7 +899,7 @@ __global__ __launch_bounds__(NSUB * 256) void aeam_ptile_kernel(const AeamDev A,
     }
     // ---- results of the tile ----
 #pragma unroll
-    for (int c = 0; c < CL; c++) ac0[c] = lane_sum<L>(ac0[c]);
+    for (int c = 0; c < CL; c++) ac0[c] = group_sum<L>(ac0[c]);
     if (s < CL) {
 #pragma unroll
       for (int c = 0; c < CL; c++)
@@ -1015,7 +1008,7 @@ __global__ __launch_bounds__(256) void aeam_density_ang_kernel(const AeamDev A, 
       acc += 2 * qa[5] * qb[5] * (delcs * delcs);
     }
   }
-  acc = lane_sum<64>(acc);
+  acc = group_sum<64>(acc);
   if (lane == 0) rho[i] = acc;
 }
 
@@ -1084,7 +1077,7 @@ __global__ __launch_bounds__(256) void aeam_embed_kernel(const AeamDev A, const 
     }
   }
   if (eflag & MDP_EFLAG_GLOBAL) {
-    e = lane_sum<64>(e);
+    e = group_sum<64>(e);
     if ((threadIdx.x & 63) == 0) atomicAdd(&acc[MDP_ACC_STRIDE * (1 + (blockIdx.x & (MDP_ACC_SLOTS - 1)))], e);
   }
 }
@@ -1187,9 +1180,9 @@ __global__ __launch_bounds__(256) void aeam_force_kernel(const AeamDev A, const 
       }
     }
   }
-  fx = lane_sum<L>(fx);
-  fy = lane_sum<L>(fy);
-  fz = lane_sum<L>(fz);
+  fx = group_sum<L>(fx);
+  fy = group_sum<L>(fy);
+  fz = group_sum<L>(fz);
   if (have && s == 0) {
     // plain += : this kernel is the only writer of owned f at this point (stream order); the angular
     // kernel that follows uses atomics
@@ -1200,16 +1193,16 @@ __global__ __launch_bounds__(256) void aeam_force_kernel(const AeamDev A, const 
   }
   if (EV) {
     if (eflag & MDP_EFLAG_ATOM) {
-      const double ea = lane_sum<L>(e);
+      const double ea = group_sum<L>(e);
       if (have && s == 0) eatom[a] += ea;
     }
     if (vflag & MDP_VFLAG_ATOM) {
-      a0 = lane_sum<L>(a0);
-      a1 = lane_sum<L>(a1);
-      a2 = lane_sum<L>(a2);
-      a3 = lane_sum<L>(a3);
-      a4 = lane_sum<L>(a4);
-      a5 = lane_sum<L>(a5);
+      a0 = group_sum<L>(a0);
+      a1 = group_sum<L>(a1);
+      a2 = group_sum<L>(a2);
+      a3 = group_sum<L>(a3);
+      a4 = group_sum<L>(a4);
+      a5 = group_sum<L>(a5);
       if (have && s == 0) { // plain stores: the angular kernel (atomics) runs after this one
         double *va = vatom + 6 * (size_t) a;
         va[0] += a0;
@@ -1222,16 +1215,16 @@ __global__ __launch_bounds__(256) void aeam_force_kernel(const AeamDev A, const 
     }
     double *slot = acc + MDP_ACC_STRIDE * (1 + (blockIdx.x & (MDP_ACC_SLOTS - 1)));
     if (eflag & MDP_EFLAG_GLOBAL) {
-      const double et = lane_sum<64>(e);
+      const double et = group_sum<64>(e);
       if (lane == 0) atomicAdd(&slot[0], et);
     }
     if (vflag & MDP_VFLAG_GLOBAL) {
-      v0 = lane_sum<64>(v0);
-      v1 = lane_sum<64>(v1);
-      v2 = lane_sum<64>(v2);
-      v3 = lane_sum<64>(v3);
-      v4 = lane_sum<64>(v4);
-      v5 = lane_sum<64>(v5);
+      v0 = group_sum<64>(v0);
+      v1 = group_sum<64>(v1);
+      v2 = group_sum<64>(v2);
+      v3 = group_sum<64>(v3);
+      v4 = group_sum<64>(v4);
+      v5 = group_sum<64>(v5);
       if (lane == 0) {
         atomicAdd(&slot[1], v0);
         atomicAdd(&slot[2], v1);
@@ -1350,21 +1343,21 @@ __global__ __launch_bounds__(256) void aeam_force_ang_kernel(const AeamDev A, co
       atomicAdd(&f[3 * (size_t) jj + 2], qa[9]);
     }
   }
-  fix = lane_sum<64>(fix);
-  fiy = lane_sum<64>(fiy);
-  fiz = lane_sum<64>(fiz);
+  fix = group_sum<64>(fix);
+  fiy = group_sum<64>(fiy);
+  fiz = group_sum<64>(fiz);
   if (lane == 0) {
     atomicAdd(&f[3 * (size_t) i], fix);
     atomicAdd(&f[3 * (size_t) i + 1], fiy);
     atomicAdd(&f[3 * (size_t) i + 2], fiz);
   }
   if (vflag & MDP_VFLAG_GLOBAL) {
-    v0 = lane_sum<64>(v0);
-    v1 = lane_sum<64>(v1);
-    v2 = lane_sum<64>(v2);
-    v3 = lane_sum<64>(v3);
-    v4 = lane_sum<64>(v4);
-    v5 = lane_sum<64>(v5);
+    v0 = group_sum<64>(v0);
+    v1 = group_sum<64>(v1);
+    v2 = group_sum<64>(v2);
+    v3 = group_sum<64>(v3);
+    v4 = group_sum<64>(v4);
+    v5 = group_sum<64>(v5);
     if (lane == 0) {
       double *slot = acc + MDP_ACC_STRIDE * (1 + (blockIdx.x & (MDP_ACC_SLOTS - 1)));
       atomicAdd(&slot[1], v0);
@@ -1478,8 +1471,6 @@ __global__ __launch_bounds__(256) void tile_first_remote_kernel(const int ntile,
   }
 }
 
-inline int nblk(long long n, int per) { return (int) ((n + per - 1) / per); }
-
 } // namespace
 
 // largest cutoff between the two classes of the tile lists (type 0 | every other type), either visit of a pair
@@ -1539,10 +1530,10 @@ int mdp_aeam_prepare(mdp_ctx *c)
                                                                   c->tu.p, c->lj_off.p, c->ang_count.p);
     if (have_list) {
       if (init[0] && remote && c->aeam_tiled)
-        ang_reach_kernel<<<nblk(init[0], 256), 256, 0, st>>>(init[0], c->ang_list.p, c->ang_count.p, kTile * c->aeam_cl);
+        ang_reach_kernel<<<nblk(init[0]), 256, 0, st>>>(init[0], c->ang_list.p, c->ang_count.p, kTile * c->aeam_cl);
     } else if (c->nlocal)
-      ang_list_kernel<<<nblk(c->nlocal, 256), 256, 0, st>>>(c->aeam.nnonangular, c->nlocal, c->xq.p, c->ang_list.p, c->ang_count.p,
-                                                            remote && c->aeam_tiled ? kTile * c->aeam_cl : 0);
+      ang_list_kernel<<<nblk(c->nlocal), 256, 0, st>>>(c->aeam.nnonangular, c->nlocal, c->xq.p, c->ang_list.p, c->ang_count.p,
+                                                       remote && c->aeam_tiled ? kTile * c->aeam_cl : 0);
     MDP_HIP(c, hipGetLastError());
     int h[5] = {0, 0, 0, 0, 0};
     MDP_TRY(mdp_read_one(c, c->ang_count.p, sizeof h, h));
@@ -1858,8 +1849,8 @@ int mdp_aeam_run_density(mdp_ctx *c, int eflag)
   // resident runs: the periodic self-images [nlocal, remote_start) get their fp in the same launch
   const int nimg = c->md && c->ghost_owner.p ? (c->remote_start >= nlocal && c->remote_start <= c->nall ? c->remote_start - nlocal : c->nghost) : 0;
   if (nlocal)
-    aeam_embed_kernel<<<nblk(nlocal + nimg, 256), 256, 0, st>>>(c->aeam, nlocal, c->xq.p, c->rho.p, c->fp.p, c->eatom.p,
-                                                                c->acc.p, eflag, /*accumulate=*/0, nimg, c->ghost_owner.p);
+    aeam_embed_kernel<<<nblk(nlocal + nimg), 256, 0, st>>>(c->aeam, nlocal, c->xq.p, c->rho.p, c->fp.p, c->eatom.p,
+                                                           c->acc.p, eflag, /*accumulate=*/0, nimg, c->ghost_owner.p);
   c->aeam_img_fp = nlocal > 0 && nimg > 0;
   MDP_HIP(c, hipGetLastError());
   mdp_span_end(c, 2);
@@ -2014,14 +2005,14 @@ int mdp_aeam_set_tables(mdp_ctx *c, const mdp_aeam_tables *t)
     MDP_HIP(c, c->aeam_rhor_d4.reserve(rr));
     MDP_HIP(c, c->aeam_z2r_v4.reserve(zr));
     MDP_HIP(c, c->aeam_z2r_d4.reserve(zr));
-    relay_kernel<<<(int) ((rr + 255) / 256), 256, 0, c->stream>>>(rr, c->aeam_rhor.p, c->aeam_rhor_v4.p, c->aeam_rhor_d4.p);
-    relay_kernel<<<(int) ((zr + 255) / 256), 256, 0, c->stream>>>(zr, c->aeam_z2r.p, c->aeam_z2r_v4.p, c->aeam_z2r_d4.p);
+    relay_kernel<<<nblk(rr), 256, 0, c->stream>>>(rr, c->aeam_rhor.p, c->aeam_rhor_v4.p, c->aeam_rhor_d4.p);
+    relay_kernel<<<nblk(zr), 256, 0, c->stream>>>(zr, c->aeam_z2r.p, c->aeam_z2r_v4.p, c->aeam_z2r_d4.p);
     MDP_HIP(c, hipGetLastError());
     MDP_HIP(c, hipStreamSynchronize(c->stream));
     MDP_HIP(c, c->aeam_rhor_ys.reserve(rr + 1));
     MDP_HIP(c, c->aeam_z2r_ys.reserve(zr + 1));
-    ys_kernel<<<(int) ((rr + 255) / 256), 256, 0, c->stream>>>(rr, c->aeam_rhor.p, c->aeam_rhor_ys.p);
-    ys_kernel<<<(int) ((zr + 255) / 256), 256, 0, c->stream>>>(zr, c->aeam_z2r.p, c->aeam_z2r_ys.p);
+    ys_kernel<<<nblk(rr), 256, 0, c->stream>>>(rr, c->aeam_rhor.p, c->aeam_rhor_ys.p);
+    ys_kernel<<<nblk(zr), 256, 0, c->stream>>>(zr, c->aeam_z2r.p, c->aeam_z2r_ys.p);
     MDP_HIP(c, hipGetLastError());
     MDP_HIP(c, hipStreamSynchronize(c->stream));
     A.rhor_ys = c->aeam_rhor_ys.p;
@@ -2033,7 +2024,7 @@ int mdp_aeam_set_tables(mdp_ctx *c, const mdp_aeam_tables *t)
     // per pair type: {rho' coefficients | phi' coefficients} in one 64-byte record (tile force kernel)
     const int npair = A.ntypes * A.ntypes, nm1 = A.nrmax + 1;
     MDP_HIP(c, c->aeam_pair_d8.reserve((size_t) npair * nm1 * 6 + 8));
-    pair_der_kernel<<<(int) (((size_t) npair * nm1 + 255) / 256), 256, 0, c->stream>>>(
+    pair_der_kernel<<<nblk((long long) npair * nm1), 256, 0, c->stream>>>(
         npair, nm1, A.g_t2rhor, A.g_t2z2r, c->aeam_rhor.p, c->aeam_z2r.p, c->aeam_pair_d8.p);
     MDP_HIP(c, hipGetLastError());
     MDP_HIP(c, hipStreamSynchronize(c->stream));

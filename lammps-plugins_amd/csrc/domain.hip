@@ -22,8 +22,6 @@
 
 namespace {
 
-inline int nblk(long long n) { return (int) ((n + 255) / 256); }
-
 __device__ __forceinline__ void dd_x2lamda(const DdGeom &G, const double x, const double y, const double z, double lam[3])
 {
   const double d0 = x - G.lo[0], d1 = y - G.lo[1], d2 = z - G.lo[2];
@@ -355,24 +353,6 @@ __global__ __launch_bounds__(256) void dd_self_ghost_kernel(const int nself, con
   xq[nlocal + g] = make_double4(x.x + shift[3 * (size_t) g], x.y + shift[3 * (size_t) g + 1], x.z + shift[3 * (size_t) g + 2], x.w);
   type[nlocal + g] = type[o];
   tag[nlocal + g] = tag[o];
-}
-
-// `neigh_modify check yes` on the host-level skin, owned atoms (Neighbor::check_distance): flag[0] = some atom is
-// beyond the trigger distance, flag[1] = some atom is beyond half the skin itself (a build that came too late)
-__global__ __launch_bounds__(256) void dd_moved_kernel(const int n, const double trigsq, const double hardsq,
-                                                       const double4 *__restrict__ xq, const mdp_hold_t *__restrict__ xhold,
-                                                       int *__restrict__ flag)
-{
-  bool t = false, h = false;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const double4 x = xq[i];
-    const double dx = x.x - xhold[3 * (size_t) i], dy = x.y - xhold[3 * (size_t) i + 1], dz = x.z - xhold[3 * (size_t) i + 2];
-    const double d2 = dx * dx + dy * dy + dz * dz;
-    t = t || d2 > trigsq;
-    h = h || d2 > hardsq;
-  }
-  if (__ballot(t) && (threadIdx.x & 63) == 0) flag[0] = 1;
-  if (__ballot(h) && (threadIdx.x & 63) == 0) flag[1] = 1;
 }
 
 template <typename T> void swap_buf(DevBuf<T> &a, DevBuf<T> &b)
@@ -859,9 +839,7 @@ int mdp_md_moved_async(mdp_ctx *c, int *moved, int *dangerous)
   const double hard = 0.5 * c->cfg.skin;
   double trig = hard - 0.1 * mdp_margin_scale(c);
   if (trig < 0.5 * hard) trig = 0.5 * hard;
-  const int grid = nblk(c->nlocal) < 1024 ? nblk(c->nlocal) : 1024;
-  dd_moved_kernel<<<grid, 256, 0, st>>>(c->nlocal, trig * trig, hard * hard, c->xq.p, c->xhold.p, h);
-  MDP_HIP(c, hipGetLastError());
+  MDP_TRY(mdp_moved(c, c->nlocal, 1024, trig * trig, hard * hard, c->xhold.p, h));
   MDP_HIP(c, hipEventRecord(D.ev_moved, st));
   D.ev_moved_ref = D.ev_moved;
   D.moved_pending = true;

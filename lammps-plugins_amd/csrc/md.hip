@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256) void ang_select_kernel(const int nlocal, const
 // one in one pass (both half-kicks use the same forces) -- saves reading f, v, rmass and writing v once per step; the
 // same operations in the same order as the two kernels, so the trajectory is bit-identical.  CHECK: `neigh_modify
 // check yes` of the new positions against the positions of the last reneighboring in the same pass (what
-// dd_moved_kernel does in a pass of its own): flag[0] = some atom beyond the trigger, flag[1] = beyond half the skin.
+// moved_kernel does in a pass of its own): flag[0] = some atom beyond the trigger, flag[1] = beyond half the skin.
 // SC: the style-level checks and the accumulator reset of the compute that follows, in the same pass (MdpStyleCheck).
 // SCALE: the thermostat's velocity factor *vscale between the two half-kicks (nhc.hip); the NVE instantiations
 // (SCALE = false) never read it, so their code is what it was without a thermostat.
@@ -364,8 +364,10 @@ __global__ void ghost_refresh_kernel(int nlocal, int nghost, const int *__restri
   xq[nlocal + g] = x;
 }
 
-__global__ void ghost_scalar_refresh_kernel(int nlocal, int nghost, const int *__restrict__ owner,
-                                            double *__restrict__ a)
+// forward comm of a per-atom scalar on one rank: a periodic self-image takes its owner's value (owner < 0: a remote
+// ghost, left alone)
+__global__ void ghost_scalar_kernel(const int nlocal, const int nghost, const int *__restrict__ owner,
+                                    double *__restrict__ a)
 {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= nghost) return;
@@ -373,29 +375,70 @@ __global__ void ghost_scalar_refresh_kernel(int nlocal, int nghost, const int *_
   if (o >= 0) a[nlocal + g] = a[o];
 }
 
-__global__ void fold_self_ghost_f_kernel(int nlocal, int nghost, const int *__restrict__ owner, double *__restrict__ f)
+// Comm::reverse_comm on one rank: what the periodic self-images collected (w doubles per atom) goes to their owners and
+// the images are zeroed (owner < 0: a remote ghost, left alone).  Several images share an owner, hence the atomics:
+// the order of the additions is not fixed, the sum is to the last bit or two.
+__global__ void ghost_fold_kernel(const int nlocal, const int nghost, const int w, const int *__restrict__ owner,
+                                  double *__restrict__ a)
 {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= nghost) return;
   const int o = owner[g];
   if (o < 0) return;
-  double *fg = f + 3 * (size_t) (nlocal + g);
-  if (fg[0] != 0.0 || fg[1] != 0.0 || fg[2] != 0.0) {
-    atomicAdd(&f[3 * (size_t) o], fg[0]);
-    atomicAdd(&f[3 * (size_t) o + 1], fg[1]);
-    atomicAdd(&f[3 * (size_t) o + 2], fg[2]);
-    fg[0] = fg[1] = fg[2] = 0.0;
-  }
+  double *ag = a + (size_t) w * (nlocal + g);
+  for (int k = 0; k < w; k++)
+    if (ag[k] != 0.0) {
+      atomicAdd(&a[(size_t) w * o + k], ag[k]);
+      ag[k] = 0.0;
+    }
 }
 
-__global__ void hold_kernel(int nlocal, const double4 *__restrict__ xq, mdp_hold_t *__restrict__ xhold)
+// positions of the first n atoms as the reference of a displacement check
+__global__ void hold_kernel(const int n, const double4 *__restrict__ xq, mdp_hold_t *__restrict__ xhold)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nlocal) return;
+  if (i >= n) return;
   const double4 x = xq[i];
   xhold[3 * (size_t) i] = (mdp_hold_t) x.x;
   xhold[3 * (size_t) i + 1] = (mdp_hold_t) x.y;
   xhold[3 * (size_t) i + 2] = (mdp_hold_t) x.z;
+}
+
+// `neigh_modify check yes` in a pass of its own (Neighbor::check_distance), grid-stride over the first n atoms:
+// flag[0] = some atom is beyond the trigger, flag[1] = beyond the hard limit (a build that came too late);
+// PRUNE: flag[2], flag[3] the same against the positions of the last pruning of the rows (xprune).
+// Every lane reaches the votes: a lane that returned early would drop out of __any.
+template <bool PRUNE>
+__global__ __launch_bounds__(256) void moved_kernel(const int n, const double trigsq, const double hardsq,
+                                                    const double4 *__restrict__ xq,
+                                                    const mdp_hold_t *__restrict__ xhold, int *__restrict__ flag,
+                                                    const mdp_hold_t *__restrict__ xprune, const double ptrigsq,
+                                                    const double phardsq)
+{
+  bool far = false, toofar = false, pfar = false, ptoofar = false;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const double4 x = xq[i];
+    const double dx = x.x - xhold[3 * (size_t) i], dy = x.y - xhold[3 * (size_t) i + 1],
+                 dz = x.z - xhold[3 * (size_t) i + 2];
+    const double d2 = dx * dx + dy * dy + dz * dz;
+    far = far || d2 > trigsq;
+    toofar = toofar || d2 > hardsq;
+    if (PRUNE) {
+      const double px = x.x - xprune[3 * (size_t) i], py = x.y - xprune[3 * (size_t) i + 1],
+                   pz = x.z - xprune[3 * (size_t) i + 2];
+      const double p2 = px * px + py * py + pz * pz;
+      pfar = pfar || p2 > ptrigsq;
+      ptoofar = ptoofar || p2 > phardsq;
+    }
+  }
+  // `flag` is pinned HOST memory (zeroed by the host before the launch): plain idempotent stores, visible when the
+  // kernel has completed -- no memset and no copy engine in the per-step path
+  if (PRUNE) {
+    if (__any(pfar) && (threadIdx.x & 63) == 0) flag[2] = 1;
+    if (__any(ptoofar) && (threadIdx.x & 63) == 0) flag[3] = 1;
+  }
+  if (__any(far) && (threadIdx.x & 63) == 0) flag[0] = 1;
+  if (__any(toofar) && (threadIdx.x & 63) == 0) flag[1] = 1;
 }
 
 // out[7] += KE, out[8] = max(out[8], disp^2)   (acc[7], acc[8])
@@ -531,9 +574,44 @@ __global__ void x3_to_xq_kernel(int n, const double *__restrict__ x3, double4 *_
   xq[i] = x;
 }
 
-inline int nblk(long long n) { return (int) ((n + 255) / 256); }
-
 } // namespace
+
+// ---- the per-atom helpers other translation units launch -----------------------------------------
+
+int mdp_hold(mdp_ctx *c, int n, mdp_hold_t *d_hold)
+{
+  if (n > 0) hold_kernel<<<nblk(n), 256, 0, c->stream>>>(n, c->xq.p, d_hold);
+  MDP_HIP(c, hipGetLastError());
+  return MDP_OK;
+}
+
+int mdp_moved(mdp_ctx *c, int n, int max_grid, double trigsq, double hardsq, const mdp_hold_t *d_hold, int *flag,
+              const mdp_hold_t *d_prune, double ptrigsq, double phardsq)
+{
+  const int grid = nblk(n) < max_grid ? nblk(n) : max_grid;
+  if (d_prune)
+    moved_kernel<true><<<grid, 256, 0, c->stream>>>(n, trigsq, hardsq, c->xq.p, d_hold, flag, d_prune, ptrigsq, phardsq);
+  else
+    moved_kernel<false><<<grid, 256, 0, c->stream>>>(n, trigsq, hardsq, c->xq.p, d_hold, flag, nullptr, 0.0, 0.0);
+  MDP_HIP(c, hipGetLastError());
+  return MDP_OK;
+}
+
+int mdp_host_ghost_scalar(mdp_ctx *c, double *d_a)
+{
+  if (!c->host_ghosts_derived || c->nghost <= 0) return MDP_OK;
+  ghost_scalar_kernel<<<nblk(c->nghost), 256, 0, c->stream>>>(c->nlocal, c->nghost, c->ghost_owner.p, d_a);
+  MDP_HIP(c, hipGetLastError());
+  return MDP_OK;
+}
+
+int mdp_host_ghost_fold(mdp_ctx *c, int w, double *d_a)
+{
+  if (!c->host_ghosts_derived || c->nghost <= 0) return MDP_OK;
+  ghost_fold_kernel<<<nblk(c->nghost), 256, 0, c->stream>>>(c->nlocal, c->nghost, w, c->ghost_owner.p, d_a);
+  MDP_HIP(c, hipGetLastError());
+  return MDP_OK;
+}
 
 // ---- neighbor-list cutoffs the style's init_one() would hand the host ----------------------------
 // aeam: squared list cutoffs (cut[ti][tj] + skin)^2 per type pair (pair_aeam.cpp:618-620), in the kernel arguments up
@@ -998,8 +1076,7 @@ int mdp_md_aeam_density(mdp_ctx *c, int eflag)
   // forward comm of fp on one rank: periodic self-images copy their owner's value -- normally done by the embedding
   // kernel itself (aeam_img_fp)
   if (c->nghost && !c->aeam_img_fp && !(c->dd.on && c->dd.nself == 0)) // (a brick without periodic self-images: nothing to copy)
-    ghost_scalar_refresh_kernel<<<nblk(c->nghost), 256, 0, c->stream>>>(c->nlocal, c->nghost, c->ghost_owner.p,
-                                                                        c->fp.p);
+    ghost_scalar_kernel<<<nblk(c->nghost), 256, 0, c->stream>>>(c->nlocal, c->nghost, c->ghost_owner.p, c->fp.p);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }
@@ -1020,7 +1097,7 @@ int mdp_md_fold_self_ghost_f(mdp_ctx *c)
   // nothing is left on the images; rebomos writes nothing to ghosts at all
   if (c->cfg.style == 2) return MDP_OK;
   if (c->nghost)
-    fold_self_ghost_f_kernel<<<nblk(c->nghost), 256, 0, c->stream>>>(c->nlocal, c->nghost, c->ghost_owner.p, c->f.p);
+    ghost_fold_kernel<<<nblk(c->nghost), 256, 0, c->stream>>>(c->nlocal, c->nghost, 3, c->ghost_owner.p, c->f.p);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }

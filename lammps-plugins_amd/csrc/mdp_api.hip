@@ -275,29 +275,6 @@ __global__ void host_ghost_refresh_kernel(const int nlocal, const int nghost, co
   xq[nlocal + g] = x;
 }
 
-__global__ void host_ghost_scalar_kernel(const int nlocal, const int nghost, const int *__restrict__ owner,
-                                         double *__restrict__ a)
-{
-  const int g = blockIdx.x * 256 + threadIdx.x;
-  if (g < nghost) a[nlocal + g] = a[owner[g]];
-}
-
-// Comm::reverse_comm on one periodic rank: what the images collected goes to their owners (several images per owner:
-// atomics; the order of the additions is not fixed, the sum is to the last bit or two)
-__global__ void host_ghost_fold_kernel(const int nlocal, const int nghost, const int w, const int *__restrict__ owner,
-                                       double *__restrict__ a)
-{
-  const int g = blockIdx.x * 256 + threadIdx.x;
-  if (g >= nghost) return;
-  const int o = owner[g];
-  double *ag = a + (size_t) w * (nlocal + g);
-  for (int k = 0; k < w; k++)
-    if (ag[k] != 0.0) {
-      atomicAdd(&a[(size_t) w * o + k], ag[k]);
-      ag[k] = 0.0;
-    }
-}
-
 // start of every compute: energy/virial accumulators (+ their slots), the four flag words, the overflow counter.
 // flags[0] (overflow bits of the compute just finished) is folded into the STICKY word flags[4] first: force-only
 // steps of a resident run never read the flags, and a truncated neighbour set must still stop the run at the next
@@ -340,7 +317,7 @@ __global__ void acc_reduce_kernel(double *__restrict__ acc)
 int mdp_to_host_order(mdp_ctx *c, int n, int w, const double *d_src, double *d_dst)
 {
   if (n <= 0) return MDP_OK;
-  unpermute_kernel<<<(unsigned) (((long long) n * w + 255) / 256), 256, 0, c->stream>>>(n, w, c->host_perm.p, d_src, d_dst);
+  unpermute_kernel<<<nblk((long long) n * w), 256, 0, c->stream>>>(n, w, c->host_perm.p, d_src, d_dst);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }
@@ -348,7 +325,7 @@ int mdp_to_host_order(mdp_ctx *c, int n, int w, const double *d_src, double *d_d
 int mdp_to_device_order(mdp_ctx *c, int n, int w, const double *d_src, double *d_dst)
 {
   if (n <= 0) return MDP_OK;
-  permute_kernel<<<(unsigned) (((long long) n * w + 255) / 256), 256, 0, c->stream>>>(n, w, c->host_perm.p, d_src, d_dst);
+  permute_kernel<<<nblk((long long) n * w), 256, 0, c->stream>>>(n, w, c->host_perm.p, d_src, d_dst);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }
@@ -362,7 +339,7 @@ int mdp_acc_begin(mdp_ctx *c, bool any)
     return MDP_OK;
   }
   const int n = any ? MDP_ACC_STRIDE * (1 + MDP_ACC_SLOTS) : MDP_ACC_STRIDE;
-  acc_zero_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(c->acc.p, n, c->flags.p, c->ovf.p, c->ovf_stride);
+  acc_zero_kernel<<<nblk(n), 256, 0, c->stream>>>(c->acc.p, n, c->flags.p, c->ovf.p, c->ovf_stride);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }
@@ -664,9 +641,9 @@ int mdp_pack_xq(mdp_ctx *c, const double *d_x3, const int *d_type, int count)
     d_map = c->type.p + c->nall;
   }
   if (c->host_sort)
-    pack_xq_perm_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(n, d_x3, d_type, d_map, c->host_perm.p, c->xq.p);
+    pack_xq_perm_kernel<<<nblk(n), 256, 0, c->stream>>>(n, d_x3, d_type, d_map, c->host_perm.p, c->xq.p);
   else
-    pack_xq_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(n, d_x3, d_type, d_map, c->xq.p);
+    pack_xq_kernel<<<nblk(n), 256, 0, c->stream>>>(n, d_x3, d_type, d_map, c->xq.p);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }
@@ -688,9 +665,9 @@ static int host_sort_atoms(mdp_ctx *c)
   MDP_HIP(c, c->host_perm.reserve(nall + 1));
   double sc[3];
   for (int d = 0; d < 3; d++) sc[d] = 1024.0 / (c->bbox_hi[d] - c->bbox_lo[d]);
-  hilbert_key_kernel<<<(nall + 255) / 256, 256, 0, st>>>(nall, c->nlocal, c->xraw.p, c->bbox_lo[0], c->bbox_lo[1],
-                                                         c->bbox_lo[2], sc[0], sc[1], sc[2], c->sort_keys_a.p,
-                                                         c->cell_of.p);
+  hilbert_key_kernel<<<nblk(nall), 256, 0, st>>>(nall, c->nlocal, c->xraw.p, c->bbox_lo[0], c->bbox_lo[1],
+                                                 c->bbox_lo[2], sc[0], sc[1], sc[2], c->sort_keys_a.p,
+                                                 c->cell_of.p);
   MDP_HIP(c, hipGetLastError());
   size_t tmp = 0;
   MDP_HIP(c, rocprim::radix_sort_pairs(nullptr, tmp, c->sort_keys_a.p, c->sort_keys_b.p, c->cell_of.p, c->host_perm.p,
@@ -743,7 +720,7 @@ int mdp_chunk_by_element(mdp_ctx *c, int n, int n_owned, const int *d_idx_in, in
   if (n <= 0) return MDP_OK;
   MDP_HIP(c, c->sort_keys_a.reserve((size_t) n + 1));
   MDP_HIP(c, c->sort_keys_b.reserve((size_t) n + 1));
-  chunk_key_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(n, n_owned, d_idx_in, d_xq, d_type, d_map, c->sort_keys_a.p);
+  chunk_key_kernel<<<nblk(n), 256, 0, c->stream>>>(n, n_owned, d_idx_in, d_xq, d_type, d_map, c->sort_keys_a.p);
   MDP_HIP(c, hipGetLastError());
   int bits = 2;
   while ((1ull << bits) <= ((((unsigned long long) n_owned >> 5) + 2ull) << 1)) bits++;
@@ -1073,20 +1050,20 @@ static int host_derive_ghosts(mdp_ctx *c, const int *h_tag)
   int *flag = c->host_tagmap.p + maxtag + 1;
   MDP_HIP(c, hipMemsetAsync(c->host_tagmap.p, 0xff, sizeof(int) * ((size_t) maxtag + 1), st));
   MDP_HIP(c, hipMemsetAsync(flag, 0, sizeof(int), st));
-  host_tagmap_kernel<<<(nlocal + 255) / 256, 256, 0, st>>>(nlocal, c->tag.p, maxtag, c->host_tagmap.p, flag);
+  host_tagmap_kernel<<<nblk(nlocal), 256, 0, st>>>(nlocal, c->tag.p, maxtag, c->host_tagmap.p, flag);
   const int *perm = nullptr, *inv = nullptr;
   if (c->host_sort) {
     MDP_HIP(c, c->host_inv.reserve((size_t) nall + 1));
-    host_inv_kernel<<<(nall + 255) / 256, 256, 0, st>>>(nall, c->host_perm.p, c->host_inv.p);
+    host_inv_kernel<<<nblk(nall), 256, 0, st>>>(nall, c->host_perm.p, c->host_inv.p);
     perm = c->host_perm.p;
     inv = c->host_inv.p;
   }
   const double *h = c->host_h;
-  host_ghost_owner_kernel<<<(nghost + 255) / 256, 256, 0, st>>>(nlocal, nall, perm, inv, c->tag.p, c->type.p, maxtag,
-                                                                c->host_tagmap.p, c->xraw.p, h[0], h[1], h[2], h[3], h[4],
-                                                                h[5], c->ghost_owner.p, c->host_img.p, c->ghost_shift.p,
-                                                                flag);
-  host_tag_dev_kernel<<<(nall + 255) / 256, 256, 0, st>>>(nall, perm, c->tag.p, c->host_tag_dev.p);
+  host_ghost_owner_kernel<<<nblk(nghost), 256, 0, st>>>(nlocal, nall, perm, inv, c->tag.p, c->type.p, maxtag,
+                                                        c->host_tagmap.p, c->xraw.p, h[0], h[1], h[2], h[3], h[4],
+                                                        h[5], c->ghost_owner.p, c->host_img.p, c->ghost_shift.p,
+                                                        flag);
+  host_tag_dev_kernel<<<nblk(nall), 256, 0, st>>>(nall, perm, c->tag.p, c->host_tag_dev.p);
   MDP_HIP(c, hipGetLastError());
   int hflag = 1;
   MDP_TRY(mdp_read_one(c, flag, sizeof(int), &hflag));
@@ -1098,9 +1075,9 @@ static int host_derive_ghosts(mdp_ctx *c, const int *h_tag)
 static int host_refresh_ghosts(mdp_ctx *c)
 {
   const double *h = c->host_h;
-  host_ghost_refresh_kernel<<<(c->nghost + 255) / 256, 256, 0, c->stream>>>(c->nlocal, c->nghost, c->ghost_owner.p,
-                                                                            c->host_img.p, h[0], h[1], h[2], h[3], h[4],
-                                                                            h[5], c->xq.p);
+  host_ghost_refresh_kernel<<<nblk(c->nghost), 256, 0, c->stream>>>(c->nlocal, c->nghost, c->ghost_owner.p,
+                                                                    c->host_img.p, h[0], h[1], h[2], h[3], h[4],
+                                                                    h[5], c->xq.p);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }
@@ -1109,22 +1086,6 @@ extern "C++" int mdp_host_refresh_ghosts(mdp_ctx *c)
 {
   if (!c->host_ghosts_derived || c->nghost <= 0) return MDP_OK;
   return host_refresh_ghosts(c);
-}
-
-extern "C++" int mdp_host_ghost_scalar(mdp_ctx *c, double *d_a)
-{
-  if (!c->host_ghosts_derived || c->nghost <= 0) return MDP_OK;
-  host_ghost_scalar_kernel<<<(c->nghost + 255) / 256, 256, 0, c->stream>>>(c->nlocal, c->nghost, c->ghost_owner.p, d_a);
-  MDP_HIP(c, hipGetLastError());
-  return MDP_OK;
-}
-
-extern "C++" int mdp_host_ghost_fold(mdp_ctx *c, int w, double *d_a)
-{
-  if (!c->host_ghosts_derived || c->nghost <= 0) return MDP_OK;
-  host_ghost_fold_kernel<<<(c->nghost + 255) / 256, 256, 0, c->stream>>>(c->nlocal, c->nghost, w, c->ghost_owner.p, d_a);
-  MDP_HIP(c, hipGetLastError());
-  return MDP_OK;
 }
 
 // ---- host-mode atoms ----------------------------------------------------------------------------
@@ -1370,15 +1331,14 @@ int mdp_rebomos_compute_host(mdp_ctx *c, int eflag, int vflag, double *f, double
   if (c->host_sort && nlocal > 0) { // back to the host's atom order (owned atoms permute among themselves)
     MDP_HIP(c, c->host_stage.reserve((size_t) 10 * nlocal + 10));
     double *sf = c->host_stage.p, *se = sf + (size_t) 3 * nlocal, *sv = se + nlocal;
-    const auto blocks = [](long long n) { return (unsigned) ((n + 255) / 256); };
-    unpermute_kernel<<<blocks(3ll * nlocal), 256, 0, st>>>(nlocal, 3, c->host_perm.p, c->f.p, sf);
+    unpermute_kernel<<<nblk(3ll * nlocal), 256, 0, st>>>(nlocal, 3, c->host_perm.p, c->f.p, sf);
     df = sf;
     if (eflag & MDP_EFLAG_ATOM) {
-      unpermute_kernel<<<blocks(nlocal), 256, 0, st>>>(nlocal, 1, c->host_perm.p, c->eatom.p, se);
+      unpermute_kernel<<<nblk(nlocal), 256, 0, st>>>(nlocal, 1, c->host_perm.p, c->eatom.p, se);
       de = se;
     }
     if (vflag & MDP_VFLAG_ATOM) {
-      unpermute_kernel<<<blocks(6ll * nlocal), 256, 0, st>>>(nlocal, 6, c->host_perm.p, c->vatom.p, sv);
+      unpermute_kernel<<<nblk(6ll * nlocal), 256, 0, st>>>(nlocal, 6, c->host_perm.p, c->vatom.p, sv);
       dv = sv;
     }
     MDP_HIP(c, hipGetLastError());

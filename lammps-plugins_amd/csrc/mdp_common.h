@@ -18,6 +18,7 @@
 // global energy/virial accumulators: acc[0..15] final values (0 eng, 1..6 virial, 7 KE, 8 maxdisp2),
 // followed by MDP_ACC_SLOTS partial slots of MDP_ACC_STRIDE doubles each
 #define MDP_CLUSTER 2
+static_assert(MDP_CLUSTER == 1 || MDP_CLUSTER == 2, "the Lennard-Jones kernels are instantiated for 1- and 2-atom clusters only");
 #define MDP_ACC_SLOTS 512
 #define MDP_ACC_STRIDE 16
 // REBO centre classes: lane-group size (4, 8, 12, 16, 32) x element, x {interior, boundary}: classes 10..19 hold the
@@ -144,6 +145,17 @@ struct AeamDev {
   const double2 *rhor_ys, *z2r_ys; // [table][nrmax+1] (value, slope) = columns 6 and 5 of a row: the persistent tile kernels' tables
   const double2 *pair_d6; // [ntypes*ntypes][nrmax+1][3]: {rho' c0 c1 | rho' c2, phi' c0 | phi' c1 c2} of the pair type, 48 B per row
 };
+
+// blocks of `per` threads (or work items) that cover n
+inline int nblk(long long n, int per = 256) { return (int) ((n + per - 1) / per); }
+
+// butterfly sum over W consecutive lanes (W a power of two <= 64): every lane of the group ends with the total
+template <int W> __device__ __forceinline__ double group_sum(double v)
+{
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 // 30-bit key of a cell (10 bits per axis) along a 3-D Hilbert curve (Skilling, "Programming the Hilbert curve":
 // axes -> transposed index).  A Hilbert curve has no jumps: any run of consecutive keys is a compact blob, which
@@ -526,6 +538,11 @@ int mdp_pack_xq(mdp_ctx *c, const double *d_x3, const int *d_type_or_null, int c
 int mdp_rebomos_host_precheck(mdp_ctx *c);                 // host mode: displacement check behind the position upload
 int mdp_host_ghost_scalar(mdp_ctx *c, double *d_a);        // host mode, derived images: a[image] = a[owner]
 int mdp_host_ghost_fold(mdp_ctx *c, int w, double *d_a);   // a[owner] += a[image], a[image] = 0 (w doubles per atom)
+int mdp_hold(mdp_ctx *c, int n, mdp_hold_t *d_hold);        // d_hold = positions of the first n atoms (reference of a displacement check)
+// displacement check of the first n atoms on at most max_grid blocks: flag[0] / flag[1] = some atom is beyond sqrt(trigsq) /
+// sqrt(hardsq) from d_hold; with d_prune, flag[2] / flag[3] the same against d_prune.  flag: pinned host memory, zeroed by the caller
+int mdp_moved(mdp_ctx *c, int n, int max_grid, double trigsq, double hardsq, const mdp_hold_t *d_hold, int *flag,
+              const mdp_hold_t *d_prune = nullptr, double ptrigsq = 0.0, double phardsq = 0.0);
 int mdp_scan_exclusive_int(mdp_ctx *c, const int *d_in, int *d_out, int n);  // d_out[n] = total (n+1 entries)
 int mdp_chunk_by_element(mdp_ctx *c, int n, int n_owned, const int *d_idx_in, int *d_idx_out, const double4 *d_xq,
                          const int *d_type, const int *d_map); // element-sorted runs of 32 owned atoms (stable)

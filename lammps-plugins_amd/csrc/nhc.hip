@@ -13,8 +13,6 @@
 
 namespace {
 
-inline int nblk(long long n) { return (int) ((n + 255) / 256); }
-
 // w_i = v_i (+ dtf / m_i f_i if KICK; stored if STORE); part[block] = sum over the block of m_i |w_i|^2 in a fixed order
 template <bool KICK, bool STORE>
 __global__ __launch_bounds__(256) void nhc_ke_kernel(const int n, const double dtf, const double *__restrict__ rmass,

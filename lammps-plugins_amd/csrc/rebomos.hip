@@ -57,13 +57,6 @@ __device__ __forceinline__ int xcd_contiguous(const int b, const int n)
   return xcd * q + (xcd < r ? xcd : r) + idx;
 }
 
-template <int W> __device__ __forceinline__ double group_sum(double v)
-{
-#pragma unroll
-  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <int G> __device__ __forceinline__ double group_sum_any(double v, const int s, const int lane)
 {
   if constexpr ((G & (G - 1)) == 0) {
@@ -1010,7 +1003,7 @@ __global__ __launch_bounds__(256) void rebo_centre_general_kernel(
 // ------------------------------------------------------------------------------------------------
 // The per-atom gather x[j] is what bounds this loop (one 32-byte gather feeds ~25 flops and the L1
 // tag rate saturates), so MDP_CLUSTER consecutive (Morton-ordered, hence adjacent) atoms share ONE
-// union neighbour list: every gathered x[j] is tested against all four cluster atoms from registers.
+// union neighbour list: every gathered x[j] is tested against all the cluster's atoms from registers.
 
 // loop-invariant Lennard-Jones parameters of one (cluster atom, neighbour element) pair type
 struct LJPar {
@@ -3063,51 +3056,6 @@ __global__ __launch_bounds__(256) void tile_scan_csr_kernel(const RebomosDev P, 
   }
 }
 
-// positions at list-build time (all atoms, ghosts included) and the displacement trigger
-__global__ void hold_all_kernel(const int nall, const double4 *__restrict__ xq, mdp_hold_t *__restrict__ xhold)
-{
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nall) return;
-  const double4 x = xq[i];
-  xhold[3 * (size_t) i] = (mdp_hold_t) x.x;
-  xhold[3 * (size_t) i + 1] = (mdp_hold_t) x.y;
-  xhold[3 * (size_t) i + 2] = (mdp_hold_t) x.z;
-}
-
-// flag[0]: someone moved beyond the trigger; flag[1]: beyond the hard limit (half the inner skin)
-// flag[2], flag[3]: the same against the positions of the last pruning of the rows (xprune, may be null)
-__global__ __launch_bounds__(256) void moved_kernel(const int nall, const double trigsq, const double hardsq,
-                                                    const double4 *__restrict__ xq,
-                                                    const mdp_hold_t *__restrict__ xhold, int *__restrict__ flag,
-                                                    const mdp_hold_t *__restrict__ xprune, const double ptrigsq,
-                                                    const double phardsq)
-{
-  bool far = false, toofar = false, pfar = false, ptoofar = false;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < nall; i += gridDim.x * 256) {
-    const double4 x = xq[i];
-    const double dx = x.x - xhold[3 * (size_t) i], dy = x.y - xhold[3 * (size_t) i + 1],
-                 dz = x.z - xhold[3 * (size_t) i + 2];
-    const double d2 = dx * dx + dy * dy + dz * dz;
-    far = far || d2 > trigsq;
-    toofar = toofar || d2 > hardsq;
-    if (xprune) {
-      const double px = x.x - xprune[3 * (size_t) i], py = x.y - xprune[3 * (size_t) i + 1],
-                   pz = x.z - xprune[3 * (size_t) i + 2];
-      const double p2 = px * px + py * py + pz * pz;
-      pfar = pfar || p2 > ptrigsq;
-      ptoofar = ptoofar || p2 > phardsq;
-    }
-  }
-  if (xprune) {
-    if (__any(pfar) && (threadIdx.x & 63) == 0) flag[2] = 1;
-    if (__any(ptoofar) && (threadIdx.x & 63) == 0) flag[3] = 1;
-  }
-  // `flag` is pinned HOST memory (zeroed by the host before the launch): plain idempotent stores, visible when the
-  // kernel has completed -- no memset and no copy engine in the per-step path
-  if (__any(far) && (threadIdx.x & 63) == 0) flag[0] = 1;
-  if (__any(toofar) && (threadIdx.x & 63) == 0) flag[1] = 1;
-}
-
 // rev[slot of j in cand(a)] = absolute slot of a in cand(j), for owned a (static between list builds)
 // rev16: the first 16 reverse slots of every owned atom at a fixed stride (-1 beyond the row), so that the
 // gather reaches a slot record in two dependent loads instead of three (no row offset to fetch first)
@@ -3579,8 +3527,7 @@ int mdp_rebomos_repack(mdp_ctx *c)
   cluster_build_kernel<CLV, FILLV><<<gb, 256, 0, st>>>(c->grid, c->rebomos, nclus, nlocal, c->xq.p, c->cell_perm.p, \
                                                        c->cell_start.p, c->lj_cnt.p, c->lj_split.p, OFFP, OUTP)
     if (cl == 1) MDP_CB(1, false, nullptr, nullptr);
-    else if (cl == 2) MDP_CB(2, false, nullptr, nullptr);
-    else MDP_CB(4, false, nullptr, nullptr);
+    else MDP_CB(2, false, nullptr, nullptr);
   }
   MDP_HIP(c, hipGetLastError());
   const int nrow = tiled ? ntile * MDP_TILE : nclus;
@@ -3622,8 +3569,7 @@ int mdp_rebomos_repack(mdp_ctx *c)
   if (nclus && !tiled) {
     const int gb = (nclus + 15) / 16;
     if (cl == 1) MDP_CB(1, true, c->lj_off.p, c->lj.p);
-    else if (cl == 2) MDP_CB(2, true, c->lj_off.p, c->lj.p);
-    else MDP_CB(4, true, c->lj_off.p, c->lj.p);
+    else MDP_CB(2, true, c->lj_off.p, c->lj.p);
   }
 #undef MDP_CB
   MDP_HIP(c, hipGetLastError());
@@ -3642,8 +3588,8 @@ int mdp_rebomos_repack(mdp_ctx *c)
     MDP_HIP(c, c->cl_pos.reserve((size_t) 4 * (nunit + 2)));
     MDP_HIP(c, c->cl_order.reserve(nunit + 1));
     int *flag4 = c->cl_flag.p;
-    unit_class_kernel<<<(nunit + 255) / 256, 256, 0, st>>>(nunit, nullptr,
-                                                           tiled ? c->tile_nu.p : nullptr, kSmallUnion, flag4);
+    unit_class_kernel<<<nblk(nunit), 256, 0, st>>>(nunit, nullptr,
+                                                   tiled ? c->tile_nu.p : nullptr, kSmallUnion, flag4);
     MDP_HIP(c, hipGetLastError());
     int total[4] = {0, 0, 0, 0};
     MdpRead rd[4];
@@ -3654,22 +3600,22 @@ int mdp_rebomos_repack(mdp_ctx *c)
     }
     MDP_TRY(mdp_read_small(c, rd, 4));
     for (int q = 0; q < 4; q++) c->lj_class_base[q + 1] = c->lj_class_base[q] + total[q];
-    unit_order_kernel<<<(nunit + 255) / 256, 256, 0, st>>>(nunit, flag4, c->cl_pos.p, c->lj_class_base[1],
-                                                           c->lj_class_base[2], c->lj_class_base[3], c->cl_order.p);
+    unit_order_kernel<<<nblk(nunit), 256, 0, st>>>(nunit, flag4, c->cl_pos.p, c->lj_class_base[1],
+                                                   c->lj_class_base[2], c->lj_class_base[3], c->cl_order.p);
     MDP_HIP(c, hipGetLastError());
     c->lj_ordered = true;
   }
   if (nall)
-    classify_kernel<<<(nall + 255) / 256, 256, 0, st>>>(c->rebomos, nall, nlocal, c->xq.p, c->cand_off.p, c->cand.p,
-                                                        c->is_center.p, c->class_list.p, c->class_count.p,
-                                                        centre_split ? c->remote_start : 0x7fffffff);
+    classify_kernel<<<nblk(nall), 256, 0, st>>>(c->rebomos, nall, nlocal, c->xq.p, c->cand_off.p, c->cand.p,
+                                                c->is_center.p, c->class_list.p, c->class_count.p,
+                                                centre_split ? c->remote_start : 0x7fffffff);
   MDP_HIP(c, hipGetLastError());
   if (nlocal)
     rev_kernel<<<(nlocal + per_block - 1) / per_block, 256, 0, st>>>(nlocal, c->cand_off.p, c->cand.p, c->rev.p,
                                                                      c->rev16.p, c->flags.p, self_end, c->xq.p, tag_dev,
                                                                      c->ghost_owner.p, c->rebomos);
-  if (nall) hold_all_kernel<<<(nall + 255) / 256, 256, 0, st>>>(nall, c->xq.p, c->xhold_all.p);
   MDP_HIP(c, hipGetLastError());
+  MDP_TRY(mdp_hold(c, nall, c->xhold_all.p));
   int hflags[4] = {0, 0, 0, 0};
   {
     const MdpRead rd[2] = {{c->class_count.p, sizeof(int) * MDP_NCLASS, c->h_class_count}, {c->flags.p, sizeof(int) * 4, hflags}};
@@ -3730,10 +3676,10 @@ int mdp_rebomos_repack(mdp_ctx *c)
       const int w = width[(k % MDP_NCLASS_HALF) / 2];
       const long long n = (long long) c->h_class_count[k] * w;
       if (n > 0)
-        pack_cand_kernel<<<(unsigned) ((n + 255) / 256), 256, 0, st>>>(c->h_class_count[k], w,
-                                                                       c->class_list.p + (size_t) k * nall,
-                                                                       c->cand_off.p, c->cand.p,
-                                                                       c->pk_cand.p + c->pk_base[k]);
+        pack_cand_kernel<<<nblk(n), 256, 0, st>>>(c->h_class_count[k], w,
+                                                  c->class_list.p + (size_t) k * nall,
+                                                  c->cand_off.p, c->cand.p,
+                                                  c->pk_cand.p + c->pk_base[k]);
     }
     MDP_HIP(c, hipGetLastError());
   }
@@ -3830,9 +3776,7 @@ int mdp_tile_lists_build(mdp_ctx *c, const double cutsq[4], int cl, bool *ok)
 
 static int rebomos_check_launch(mdp_ctx *c, const double trig)
 {
-  hipStream_t st = c->stream;
   const int nall = c->nall;
-  const int grid = (nall + 255) / 256 < 2048 ? (nall + 255) / 256 : 2048;
   const double hard = 0.5 * c->skin_inner;
   int *h = (int *) (c->h_pinned + 24); // no check is in flight here: the caller has waited for the previous one
   h[0] = h[1] = h[2] = h[3] = 0;
@@ -3841,10 +3785,8 @@ static int rebomos_check_launch(mdp_ctx *c, const double trig)
   double ptrig = 0.5 * c->prune_buf - kPruneMargin * mdp_margin_scale(c);
   if (ptrig < 0.25 * c->prune_buf) ptrig = 0.25 * c->prune_buf;
   const double phard = 0.5 * c->prune_buf;
-  moved_kernel<<<grid, 256, 0, st>>>(nall, trig * trig, hard * hard, c->xq.p, c->xhold_all.p, h,
-                                     pr ? c->xhold_prune.p : nullptr, ptrig * ptrig, phard * phard);
-  MDP_HIP(c, hipGetLastError());
-  return MDP_OK;
+  return mdp_moved(c, nall, 2048, trig * trig, hard * hard, c->xhold_all.p, h, pr ? c->xhold_prune.p : nullptr,
+                   ptrig * ptrig, phard * phard);
 }
 
 // host mode: the displacement check of the compute that follows, launched where the stream is waited for anyway
@@ -3983,8 +3925,8 @@ int mdp_tile_prune(mdp_ctx *c, const double lim_rsq[4])
   else
     MDP_TP(2);
 #undef MDP_TP
-  if (c->nall) hold_all_kernel<<<(c->nall + 255) / 256, 256, 0, st>>>(c->nall, c->xq.p, c->xhold_prune.p);
   MDP_HIP(c, hipGetLastError());
+  MDP_TRY(mdp_hold(c, c->nall, c->xhold_prune.p));
   c->prune_valid = true;
   c->prune_stale = false;
   c->prune_epoch++; // (a displacement check launched before this says nothing about the new reference)
@@ -4141,7 +4083,6 @@ static int launch_lj(mdp_ctx *c, int klass, bool gather, int eflag, int vflag, b
     else MDP_LJ(CLV, false, false);                                                                                 \
   } while (0)
   if (c->cluster == 1) MDP_LJ2(1);
-  else if (c->cluster == 4) MDP_LJ2(4);
   else MDP_LJ2(2);
 #undef MDP_LJ2
 #undef MDP_LJ
@@ -4327,7 +4268,6 @@ int mdp_rebomos_run_end(mdp_ctx *c, int eflag, int vflag)
         const int grid = (c->nlocal + 31) / 32;
         const unsigned short *lj16 = c->lj_tiled ? c->lj16.p : nullptr;
         if (c->cluster == 1) rebo_lj_vatom_kernel<1><<<grid, 256, 0, st>>>(c->rebomos, c->nlocal, c->xq.p, c->lj_off.p, c->lj.p, lj16, c->tu.p, c->tile_cap, c->tile_nu.p, c->vatom.p, MDP_TILE);
-        else if (c->cluster == 4) rebo_lj_vatom_kernel<4><<<grid, 256, 0, st>>>(c->rebomos, c->nlocal, c->xq.p, c->lj_off.p, c->lj.p, lj16, c->tu.p, c->tile_cap, c->tile_nu.p, c->vatom.p, MDP_TILE);
         else rebo_lj_vatom_kernel<2><<<grid, 256, 0, st>>>(c->rebomos, c->nlocal, c->xq.p, c->lj_off.p, c->lj.p, lj16, c->tu.p, c->tile_cap, c->tile_nu.p, c->vatom.p, MDP_TILE);
       }
     }

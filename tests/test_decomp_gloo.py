@@ -71,7 +71,7 @@ def _worker(rank, world, port, q):
         o = orc.rebomos_compute(P, nloc, x_all, type_all - 1, tag_all, nn, off, nb, eflag=1, vflag=1)
         f = o["f"][:nloc].copy()
         fg = o["f"][nloc:]
-        np.add.at(f, plan.ghost_owner_local[selfm], fg[selfm])             # fold_self_ghost_f_kernel
+        np.add.at(f, plan.ghost_owner_local[selfm], fg[selfm])             # ghost_fold_kernel
         halo.recv3[:halo.nrecv * 3] = torch.from_numpy(fg[plan.nself:].ravel())   # pack_ghost_f
         halo.reverse3()
         np.add.at(f, plan.send_local, halo.send3[:halo.nsend * 3].numpy().reshape(-1, 3))  # unpack_add_f
