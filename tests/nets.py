@@ -1,0 +1,747 @@
+"""The randomised parity nets: one home for what profiles/*_fuzz.py run by hand and tests/test_gpu_nets.py runs at fixed
+seeds.  A helper module like fixture_cases.py, not a test module.
+
+For each net NAME of NETS:
+  draw_NAME(rng) -> spec      pure Python (no GPU, no oracle): one case drawn from a random.Random, the draws consumed in
+                              the order the command-line nets have always used, so `profiles/NAME_fuzz.py <cases> <seed>`
+                              still draws the cases recorded under profiles/r06_NAME/;
+  run_NAME(spec) -> (errors, limits)
+                              builds and runs the case on the GPU; the case passes when errors[q] < limits[q] for every
+                              q of limits (a condition that must hold counts 0 when it does, 1 when it does not; errors
+                              may carry more keys, which only the report prints);
+  line_NAME(spec, errors)     the report line of the case.
+
+spec["env"] holds the library's environment knobs of the case (MDP_INNER_SKIN, MDP_PRUNE, MDP_LJ_QUEUE,
+MDP_PRUNE_BUFFER).  A case runs with exactly these set and the others unset: the caller applies them (knobs() here,
+monkeypatch under pytest); run_NAME never writes os.environ.  spec["id"] is the short text of a test id."""
+from __future__ import annotations
+
+import atexit
+import contextlib
+import os
+import random
+import tempfile
+
+import numpy as np
+
+from lammps_plugins_amd.host import system as S
+
+KNOBS = ("MDP_INNER_SKIN", "MDP_PRUNE", "MDP_LJ_QUEUE", "MDP_PRUNE_BUFFER")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "lammps-plugins_amd")
+
+# The fixed seeds of the GPU suite: net -> [(seed, cases)].  tests/test_net_draws.py asserts that they reach the corners
+# the nets exist for.
+SUITE = {
+    "force": [(1, 60)],
+    "hostmode_walk": [(1, 30)],
+    "aeam_types": [(1, 30)],
+    "prune": [(1, 10)],
+    "dd": [(1, 10)],
+    "hnve": [(1, 8)],
+    "minilmp": [(2, 6)],
+    "trajectory": [(1, 12)],
+    "block": [(1, 8)],
+}
+
+
+def cases(net, seed, ncase):
+    """the first ncase specs of `net` at `seed`, as the command-line net draws them"""
+    rng = random.Random(seed)
+    return [NETS[net][0](rng) for _ in range(ncase)]
+
+
+@contextlib.contextmanager
+def knobs(env):
+    """the library's knobs of one case set (and the others unset) for the duration of the block; restored after"""
+    old = {k: os.environ.get(k) for k in KNOBS}
+    try:
+        for k in KNOBS:
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def passed(errors, limits):
+    return all(errors[q] < limits[q] for q in limits)
+
+
+_R = {}
+
+
+def _res():
+    """oracle, parameters and tables, loaded once per process"""
+    if not _R:
+        from conftest import POT_AEAM, POT_REBOMOS
+        from lammps_plugins_amd.host import capi
+        import oracle_bindings as ob
+        orc = ob.load()
+        af = capi.AeamFile(POT_AEAM)
+        _R.update(orc=orc, P=orc.rebomos_params(POT_REBOMOS), T=orc.aeam_pot(POT_AEAM), rp=capi.read_rebomos_file(POT_REBOMOS),
+                  af=af, tabs=af.build(), pot_aeam=POT_AEAM)
+    return _R
+
+
+def close_shared():
+    """close the context the REBO-MoS force cases share (tests/test_gpu_nets.py: at the end of its module; the command
+    line: at exit)"""
+    ctx = _R.pop("rctx", None)
+    if ctx is not None:
+        ctx.close()
+
+
+def _fold(a, owner, n):
+    out = a[:n].copy()
+    np.add.at(out, owner, a[n:])
+    return out
+
+
+def _inner(rng, choices):
+    """the nets' draw of MDP_INNER_SKIN: set (one of choices) in half of the cases"""
+    return {"MDP_INNER_SKIN": str(rng.choice(choices))} if rng.random() < 0.5 else {}
+
+
+def _fmt(v):
+    return f"{v:.1e}" if isinstance(v, float) or hasattr(v, "dtype") else f"{v}"
+
+
+REBO_CELL_N = 288     # atoms of S.rebomos_bulk_cell()
+
+
+def _rebo_n(rep):
+    return REBO_CELL_N * (1 if rep is None else rep[0] * rep[1] * rep[2])
+
+
+# ---------------------------------------------------------------------------------------------------------------- force
+# Random MoS2 cells (scale 0.92-1.16, jitter up to 0.25 A, small replicas) and random Al-Si alloys (4-7 fcc cells,
+# 0-50 % Si, jitter up to 0.3 A, half of them in a sheared box) through the host-mode HIP path (device-built or host
+# CSR lists, every tally on, then a force-only call) against a LIVE oracle compute on the same inputs.
+def draw_force(rng):
+    style = rng.choice(["rebomos", "aeam"])
+    if style == "rebomos":
+        fac, amp, sd = rng.uniform(0.92, 1.16), rng.uniform(0.0, 0.25), rng.randrange(10**6)
+        rep = rng.choice([None, (2, 1, 1), (1, 2, 1), (2, 2, 1), (1, 1, 2)])
+        spec = dict(style=style, fac=fac, amp=amp, seed=sd, rep=rep, n=_rebo_n(rep))
+        desc = f"fac {fac:.3f} amp {amp:.3f} seed {sd} rep {rep}"
+    else:
+        nc, frac, amp, sd = rng.choice([4, 5, 6, 7]), rng.choice([0.0, 0.0075, 0.03, 0.08, 0.2, 0.5]), rng.uniform(0.0, 0.3), rng.randrange(10**6)
+        spec = dict(style=style, cells=nc, frac=frac, amp=amp, seed=sd, tilt=None, n=4 * nc ** 3)
+        desc = f"cells {nc} frac {frac} amp {amp:.3f} seed {sd}"
+        if rng.random() < 0.5:   # a sheared (triclinic) box: same lamda coordinates in a tilted cell
+            L = 4.045 * nc
+            spec["tilt"] = [rng.uniform(-0.12, 0.12) * L for _ in range(3)]
+            desc += f" tilt {np.round(np.array(spec['tilt']), 2).tolist()}"
+    spec["lists"] = rng.choice(["device", "host_csr"])
+    spec.update(desc=desc + f" lists {spec['lists']}", env={}, id=f"{style}-{spec['lists']}-n{spec['n']}")
+    return spec
+
+
+def run_force(spec):
+    import fixture_cases as FC
+    import oracle_bindings as ob
+    from lammps_plugins_amd.host import capi
+    R = _res()
+    if spec["style"] == "rebomos":
+        if "rctx" not in R:   # (one context for every REBO-MoS case, as the command-line net has always run them)
+            R["rctx"] = capi.Context(0)
+            atexit.register(close_shared)
+            R["rctx"].rebomos_set_params(R["rp"])
+        rctx = R["rctx"]
+        s = FC._rebomos(spec["fac"], spec["amp"], spec["seed"], spec["rep"])
+        eng = FC.engine("rebomos", s, R["orc"], P=R["P"])
+        want = FC.oracle_outputs("rebomos", eng, s.x)
+        xa = eng.all_positions(s.x)
+        rctx.set_atoms_host(eng.nlocal, xa, eng.type_all, eng.tag_all, 2, map_=[0, 0, 1])
+        if spec["lists"] == "device":
+            rctx.set_skin(2.0)
+        else:
+            rctx.set_neighbors_csr_host(eng.nn, eng.off, eng.nb, 2.0)
+        g = rctx.rebomos_compute_host(eng.nlocal, eflag=3, vflag=5)
+        g0 = rctx.rebomos_compute_host(eng.nlocal, eflag=0, vflag=0)
+        fs = max(1.0, float(np.abs(want["f"]).max()))
+        err = dict(f=np.abs(g["f"] - want["f"]).max() / fs, f0=np.abs(g0["f"] - want["f"]).max() / fs,
+                   e=abs(g["eng"] - float(want["eng"])) / abs(float(want["eng"])), ea=np.abs(g["eatom"] - want["eatom"]).max(),
+                   va=np.abs(g["vatom"] - want["vatom"]).max() / max(1.0, np.abs(want["vatom"]).max()))
+        return err, dict(f=1e-9, f0=1e-9, e=1e-10, ea=1e-9, va=1e-9)
+    s = FC._aeam_cell(spec["cells"], spec["frac"], spec["amp"], spec["seed"])
+    if spec["tilt"] is not None:
+        nb = S.Box(s.box.lo.copy(), s.box.prd.copy(), np.array(spec["tilt"]))
+        s = S.System(nb, nb.lamda2x(s.box.x2lamda(s.x)), s.type, s.tag, s.mass)
+    eng = FC.engine("aeam", s, R["orc"], T=R["T"])
+    want = FC.oracle_outputs("aeam", eng, s.x)
+    ctx = capi.Context(0)
+    try:
+        ctx.aeam_set_tables(R["tabs"])
+        if spec["lists"] == "device":
+            cut = float(R["af"].cut_table(R["tabs"]).max()) + 1.0
+            xa, type_all, tag_all, owner, _, nloc, _ = S.with_ghosts(s, cut)
+            ctx.aeam_device_lists(True)
+            ctx.set_atoms_host(nloc, xa, type_all, tag_all, 2, map_=None)
+            ctx.set_skin(1.0)
+        else:
+            xa, owner, nloc = eng.all_positions(s.x), eng.owner, eng.nlocal
+            ctx.set_atoms_host(nloc, xa, eng.type_all, eng.tag_all, 2, map_=None)
+            ctx.set_neighbors_csr_host(eng.nn, eng.off, eng.nb, 1.0)
+        d = ctx.aeam_density_host(nloc, eflag=3)
+        r = ctx.aeam_force_host(len(xa), nloc, np.concatenate([d["fp"], d["fp"][owner]]), eflag=3, vflag=5)
+        d0 = ctx.aeam_density_host(nloc, eflag=0)
+        r0 = ctx.aeam_force_host(len(xa), nloc, np.concatenate([d0["fp"], d0["fp"][owner]]), eflag=0, vflag=0)
+    finally:
+        ctx.close()
+    fs = max(1.0, float(np.abs(want["f"]).max()))
+    err = dict(f=np.abs(ob.fold_ghost_forces(r["f"], owner, nloc) - want["f"]).max() / fs,
+               f0=np.abs(ob.fold_ghost_forces(r0["f"], owner, nloc) - want["f"]).max() / fs,
+               e=abs(d["eng"] + r["eng"] - float(want["eng"])) / abs(float(want["eng"])),
+               ea=np.abs(d["eatom"] + r["eatom"] - want["eatom"]).max(),
+               va=np.abs(_fold(r["vatom"], owner, nloc) - want["vatom"]).max() / max(1.0, np.abs(want["vatom"]).max()),
+               rho=np.abs(d["rho"] - want["rho"]).max() / max(1.0, np.abs(want["rho"]).max()))
+    return err, dict(f=1e-9, f0=1e-9, e=1e-10, ea=1e-9, va=1e-9, rho=1e-11)
+
+
+def line_force(spec, err):
+    return f"{spec['style']} {spec['desc']} n {spec['n']} " + " ".join(f"{q} {_fmt(v)}" for q, v in err.items())
+
+
+# ---------------------------------------------------------------------------------------------------------- aeam_types
+# AEAM runs with 3 - 12 atom types (relabelled copies of the bundled two-element file, tests/aeam_five.py: every new
+# element behaves as Al or as Si, so the oracle on the relabelled file is the reference): tile kernels with per-entry
+# types for up to 8 types, the generic kernels beyond.  30 device-resident steps, then forces and energy against the
+# oracle on the final positions.
+def draw_aeam_types(rng):
+    nmet, nang = rng.choice([(2, 1), (3, 2), (4, 2), (5, 3), (7, 5), (1, 3), (6, 2)])
+    n = rng.choice([6, 8, 10, 12]); frac = rng.choice([0.01, 0.06, 0.25]); temp = rng.choice([300, 863, 2000]); sd = rng.randrange(1, 10**6)
+    return dict(nmet=nmet, nang=nang, cells=n, frac=frac, temp=temp, seed=sd, ntypes=nmet + nang, env={},
+                id=f"types{nmet}+{nang}-cells{n}-T{temp}")
+
+
+def run_aeam_types(spec):
+    import aeam_five
+    import mdref
+    from lammps_plugins_amd.host import capi, resident
+    R = _res()
+    nmet, nang, sd = spec["nmet"], spec["nang"], spec["seed"]
+    if "tmp" not in R:
+        R["tmp"] = tempfile.mkdtemp()
+    path = os.path.join(R["tmp"], f"p{nmet}_{nang}.aeam")
+    if not os.path.exists(path):
+        aeam_five.write_relabelled_file(path, R["pot_aeam"], [0] * nmet + [1] * nang, ["M%d" % i for i in range(nmet)] + ["X%d" % i for i in range(nang)])
+    af = capi.AeamFile(path); T = R["orc"].aeam_pot(path); tabs = af.build()
+    s2 = S.jitter(S.fcc_cell(4.045, spec["cells"], frac_type2=spec["frac"], seed=sd), 0.05, seed=sd + 1)
+    r = np.random.default_rng(sd)
+    ty = np.where(s2.type == 1, r.integers(1, nmet + 1, s2.n), r.integers(nmet + 1, nmet + nang + 1, s2.n)).astype(np.int32)
+    s = S.System(s2.box, s2.x.copy(), ty, s2.tag.copy(), np.array([0.0] + list(af.mass)))
+    v0 = S.gaussian_velocities(s, float(spec["temp"]), seed=sd + 2)
+    ctx = capi.Context(0)
+    try:
+        ctx.aeam_set_tables(tabs)
+        d = resident.DeviceDomain(ctx, capi.STYLE_AEAM, s, float(af.cut_table(tabs).max()) + 1.0, 1.0, None, v0=v0)
+        d.compute(0, 0)
+        for _ in range(30):
+            d.step(0, 0, rebuild="auto")
+        d.compute(1, 0)
+        th = d.thermo(); got = ctx.md_download(d.nlocal, want=("x", "f")); tags = d.tags_local; builds = d.builds
+    finally:
+        ctx.close()
+    x = np.zeros((s.n, 3)); f = np.zeros((s.n, 3)); x[tags - 1] = got["x"]; f[tags - 1] = got["f"]
+    xw = S.wrap(s.box, x)
+    o = mdref.AeamCPU(R["orc"], T, S.System(s.box, xw, s.type, s.tag, s.mass)).compute(xw, eflag=1, vflag=0)
+    df = float(np.abs(f - o["f_owned"]).max()) / max(1.0, float(np.abs(o["f_owned"]).max())); de = abs(th["pe"] - o["eng"]) / abs(o["eng"])
+    return dict(dF=df, dE=de, builds=builds), dict(dF=1e-9, dE=1e-10)
+
+
+def line_aeam_types(spec, err):
+    return (f"types {spec['nmet']}+{spec['nang']} cells {spec['cells']} frac {spec['frac']} T {spec['temp']} seed {spec['seed']} "
+            f"dF {err['dF']:.1e} dE {err['dE']:.1e} builds {err['builds']}")
+
+
+# --------------------------------------------------------------------------------------------------------------- prune
+# Dynamic row pruning and the pair queues (one GPU, minihost/ddhost.cpp): random hot / drifting runs with the kernels
+# walking PRUNED rows (default) against the same run with MDP_PRUNE=0 (rows as built), against MDP_LJ_QUEUE=1 / 0
+# (cubic-branch pairs queued / found by a second walk) and against other inner skins of the style's own lists.  A pair
+# missed by the one-step-late displacement trigger shows as a trajectory that leaves its twin.
+PRUNE_VARIANTS = (("pruned", {}), ("as_built", {"MDP_PRUNE": "0"}), ("queued", {"MDP_LJ_QUEUE": "1"}), ("walked", {"MDP_LJ_QUEUE": "0"}),
+                  ("inner_skin_0.3", {"MDP_INNER_SKIN": "0.3"}), ("inner_skin_1.2", {"MDP_INNER_SKIN": "1.2"}))
+
+
+def draw_prune(rng):
+    style = rng.choice(["rebomos", "aeam"])
+    if style == "rebomos":
+        rep = rng.choice([(3, 3, 2), (4, 4, 2), (5, 3, 2)]); temp = rng.choice([300, 1500, 3000, 5000]); extra = []
+    else:
+        n = rng.choice([12, 16, 20]); rep = (n, n, n); temp = rng.choice([300, 863, 2000]); extra = ["-frac2", rng.choice([0.0075, 0.08])]
+    drift = [rng.choice([-60, 0, 40, 90]) for _ in range(3)]
+    steps = rng.choice([80, 150, 250]); sd = rng.randrange(1, 10**7)
+    variants = [(name, env) for name, env in PRUNE_VARIANTS if style == "rebomos" or name in ("pruned", "as_built")]
+    return dict(style=style, rep=rep, temp=temp, extra=extra, drift=drift, steps=steps, seed=sd, variants=variants, env={},
+                id=f"{style}-T{temp}-steps{steps}")
+
+
+def run_prune(spec):
+    import test_gpu_ddhost as T
+    common = ["-style", spec["style"], "-ranks", 1, "-replicate", *spec["rep"], "-steps", spec["steps"], "-thermo", spec["steps"],
+              "-temp", spec["temp"], "-seed", spec["seed"], "-drift", *spec["drift"]] + spec["extra"]
+    res = {}
+    with tempfile.TemporaryDirectory() as d:
+        for name, env in spec["variants"]:
+            out, _ = T._ddhost(common + ["-dump", os.path.join(d, name)], env=env)
+            res[name] = T._dump(os.path.join(d, name), 1) + (out.split("Neighbor list builds = ")[1].split()[0],)
+    ref = res["as_built"]
+    err, lim = {"builds": res["pruned"][2]}, {}
+    for n, r in res.items():
+        if n != "as_built":
+            err[n + " dx"], err[n + " dv"] = float(np.abs(r[0] - ref[0]).max()), float(np.abs(r[1] - ref[1]).max())
+            lim[n + " dx"], lim[n + " dv"] = 1e-9, 1e-8
+    return err, lim
+
+
+def line_prune(spec, err):
+    return (f"{spec['style']} rep {spec['rep']} T {spec['temp']} drift {spec['drift']} steps {spec['steps']} seed {spec['seed']} "
+            f"{spec['extra']} builds {err.get('builds', '?')} " + " ".join(f"{q} {_fmt(v)}" for q, v in err.items() if q != "builds"))
+
+
+# ------------------------------------------------------------------------------------------------------------------ dd
+# Multi-rank consistency of the C++ resident host (minihost/ddhost.cpp) on one GPU through the RCCL test double: the
+# N-rank run must end where the one-rank run ends (positions 1e-8 A, velocities 1e-7 A/ps, thermo rows as printed).
+def draw_dd(rng, only=None):
+    style = only or rng.choice(["rebomos", "aeam"])
+    ranks = rng.choice([2, 3, 4, 6, 8])
+    if style == "rebomos":
+        rep = rng.choice([(3, 3, 2), (4, 2, 2), (2, 4, 3), (5, 3, 2), (3, 2, 4)])
+        temp = rng.choice([300, 900, 1500, 3000, 5000])
+        extra = []
+    else:
+        n = rng.choice([12, 14, 16, 18])
+        rep = (n, n, n)
+        temp = rng.choice([300, 863, 1200, 3000])
+        extra = ["-frac2", rng.choice([0.0, 0.0075, 0.03, 0.08])]
+    drift = [rng.choice([-60, -30, 0, 25, 40, 70]) for _ in range(3)]
+    steps = rng.choice([40, 60, 90])
+    sd = rng.randrange(1, 10**7)
+    thermo = rng.choice([steps, 10, 7])     # (energy / virial steps in mid-run: the other kernel variants, sums over ranks)
+    return dict(style=style, ranks=ranks, rep=rep, temp=temp, extra=extra, drift=drift, steps=steps, seed=sd, thermo=thermo,
+                env={}, id=f"{style}-ranks{ranks}-T{temp}")
+
+
+def run_dd(spec):
+    import test_gpu_ddhost as T
+    box = (S.replicate(S.rebomos_bulk_cell(), spec["rep"]) if spec["style"] == "rebomos" else S.fcc_cell(4.045, spec["rep"][0])).box
+    common = ["-style", spec["style"], "-replicate", *spec["rep"], "-steps", spec["steps"], "-thermo", spec["thermo"],
+              "-temp", spec["temp"], "-seed", spec["seed"], "-drift", *spec["drift"]] + spec["extra"]
+    with tempfile.TemporaryDirectory() as d:
+        _, rows1 = T._ddhost(["-ranks", 1, "-dump", os.path.join(d, "one")] + common)
+        out, rowsn = T._ddhost(["-ranks", spec["ranks"], "-dump", os.path.join(d, "many")] + common, double=True)
+        x1, v1 = T._dump(os.path.join(d, "one"), 1)
+        xn, vn = T._dump(os.path.join(d, "many"), spec["ranks"])
+    dx = xn - x1
+    dx -= np.round(box.x2lamda(dx + box.lo)) @ box.h.T
+    rows_ok = len(rows1) == len(rowsn) and len(rows1) >= 2
+    for a, b in zip(rowsn, rows1):       # step temp press pe ke as printed (%.8g or better)
+        rows_ok = rows_ok and all(abs(u - v) <= 2e-7 * max(abs(v), 1.0) for u, v in zip(a, b))
+    err = dict(dx=float(np.abs(dx).max()), dv=float(np.abs(vn - v1).max()), rows=0 if rows_ok else 1,
+               builds=out.split("Neighbor list builds = ")[1].split()[0])
+    return err, dict(dx=1e-8, dv=1e-7, rows=1)
+
+
+def line_dd(spec, err):
+    return (f"{spec['style']} ranks {spec['ranks']} rep {spec['rep']} T {spec['temp']} drift {spec['drift']} steps {spec['steps']} "
+            f"seed {spec['seed']} {spec['extra']} dx {err['dx']:.2e} dv {err['dv']:.2e} builds {err['builds']}")
+
+
+# ------------------------------------------------------------------------------------------------------- hostmode_walk
+# HOST-MODE walks (the plain plugin path: atoms uploaded once, then positions every step, the library deciding by itself
+# when its own lists and pruned rows are stale): random cells, then 40 steps of a random walk (every atom a little, one
+# atom a lot, some steps nobody) inside the host's skin, forces against the oracle at EVERY step.
+def draw_hostmode_walk(rng):
+    style = rng.choice(["rebomos", "aeam"]); sd = rng.randrange(1, 10**6)
+    images = rng.random() < 0.5     # one periodic rank: the library keeps the images itself, the host's ghost positions are poison
+    if style == "rebomos":
+        fac, amp, rep = rng.uniform(0.95, 1.12), rng.uniform(0.0, 0.15), rng.choice([None, (2, 1, 1), (1, 2, 1)])
+        spec = dict(fac=fac, amp=amp, rep=rep, skin=2.0, n=_rebo_n(rep), env=_inner(rng, [0.3, 0.6]))
+    else:
+        cells, frac, amp = rng.choice([4, 5, 6]), rng.choice([0.0075, 0.08, 0.3]), rng.uniform(0.0, 0.15)
+        spec = dict(cells=cells, frac=frac, amp=amp, skin=1.0, n=4 * cells ** 3, env={})
+    walk = []
+    for _ in range(40):
+        mode = rng.choice(["all", "all", "one", "none", "few"])
+        arg = rng.choice([0.002, 0.01, 0.03]) if mode == "all" else (rng.randrange(spec["n"]) if mode == "one" else None)
+        walk.append((mode, arg))
+    spec.update(style=style, seed=sd, images=images, walk=walk, id=f"{style}-n{spec['n']}-images{int(images)}")
+    return spec
+
+
+def run_hostmode_walk(spec):
+    import fixture_cases as FC
+    import oracle_bindings as ob
+    from lammps_plugins_amd.host import capi
+    R = _res()
+    style, sd, images, skin = spec["style"], spec["seed"], spec["images"], spec["skin"]
+    nr = np.random.default_rng(sd)
+    if style == "rebomos":
+        s = FC._rebomos(spec["fac"], spec["amp"], sd, spec["rep"])
+        eng = FC.engine(style, s, R["orc"], P=R["P"])
+    else:
+        s = FC._aeam_cell(spec["cells"], spec["frac"], spec["amp"], sd)
+        eng = FC.engine(style, s, R["orc"], T=R["T"])
+    assert s.n == spec["n"]
+    worst, at = 0.0, ""
+    ctx = capi.Context(0)
+    try:
+        if style == "rebomos":
+            ctx.rebomos_set_params(R["rp"])
+        else:
+            ctx.aeam_set_tables(R["tabs"]); ctx.aeam_device_lists(True)
+        if images: ctx.set_box_host(s.box)
+        ctx.set_atoms_host(eng.nlocal, eng.all_positions(s.x), eng.type_all, eng.tag_all, 2, map_=[0, 0, 1] if style == "rebomos" else None)
+        ctx.set_skin(skin)
+        x = s.x.copy(); x0 = x.copy(); n = s.n; owner = eng.owner
+        for step, (mode, arg) in enumerate(spec["walk"]):
+            dxs = np.zeros((n, 3))
+            if mode == "all": dxs = nr.normal(0.0, arg, (n, 3))
+            elif mode == "one": dxs[arg] = nr.normal(0.0, 0.15, 3)
+            elif mode == "few": dxs[nr.integers(0, n, 5)] = nr.normal(0.0, 0.08, (5, 3))
+            xn = x + dxs
+            # stay inside the host's list: no atom further than 0.45 skin from where the lists were built
+            far = np.linalg.norm(xn - x0, axis=1) > 0.45 * skin
+            xn[far] = x[far]
+            x = xn
+            xa = eng.all_positions(x)
+            if images:
+                xa = xa.copy(); xa[eng.nlocal:] = np.nan
+            ctx.set_positions_host(xa)
+            o = eng.compute(x, eflag=1, vflag=0)
+            if style == "rebomos":
+                f = ctx.rebomos_compute_host(eng.nlocal, eflag=0 if step % 3 else 1, vflag=0)["f"]
+            elif images:   # fp and the images' share of the three-body forces stay on the device
+                ctx.aeam_density_host(eng.nlocal, eflag=0, keep_fp=True)
+                f = ctx.aeam_force_host(len(xa), eng.nlocal, None, eflag=0, vflag=0)["f"][:eng.nlocal]
+            else:
+                d = ctx.aeam_density_host(eng.nlocal, eflag=0)
+                r = ctx.aeam_force_host(len(xa), eng.nlocal, np.concatenate([d["fp"], d["fp"][owner]]), eflag=0, vflag=0)
+                f = ob.fold_ghost_forces(r["f"], owner, eng.nlocal)
+            err = float(np.abs(f - o["f_owned"]).max()) / max(1.0, float(np.abs(o["f_owned"]).max()))
+            if err > worst: worst, at = err, f"worst at step {step} ({mode})"
+    finally:
+        ctx.close()
+    return dict(dF=worst, at=at), dict(dF=1e-9)
+
+
+def line_hostmode_walk(spec, err):
+    return (f"{spec['style']} n {spec['n']} images {spec['images']} seed {spec['seed']} inner {spec['env'].get('MDP_INNER_SKIN')} "
+            f"dF {err['dF']:.1e} {err['at']}")
+
+
+# ---------------------------------------------------------------------------------------------------------------- hnve
+# What `fix nve/mdp` does on one rank in its default mode (mdp_hnve_initial / compute with f == NULL / mdp_hnve_final,
+# the images kept by the library, the device's displacement check read one step late and a HOST reneighboring when it
+# fires): random MoS2 cells up to 3 000 K, a projectile in some, against velocity Verlet around the ORACLE.
+def draw_hnve(rng):
+    sd = rng.randrange(1, 10**6)
+    rep = rng.choice([None, (2, 1, 1), (1, 2, 1)]); temp = rng.choice([300, 1200, 3000]); skin = rng.choice([1.0, 2.0])
+    n = _rebo_n(rep)
+    shot = rng.random() < 0.4
+    shot_atom = rng.randrange(n) if shot else None
+    return dict(seed=sd, rep=rep, temp=temp, skin=skin, n=n, shot=shot, shot_atom=shot_atom, nsteps=90, env=_inner(rng, [0.3, 0.5]),
+                id=f"n{n}-T{temp}-skin{skin}-shot{int(shot)}")
+
+
+def run_hnve(spec):
+    import mdref
+    import oracle_bindings as ob
+    import test_gpu_trajectory as TT
+    from lammps_plugins_amd.host import capi
+    R = _res(); orc, P = R["orc"], R["P"]
+    sd, rep, skin, nsteps = spec["seed"], spec["rep"], spec["skin"], spec["nsteps"]
+    s = S.rebomos_bulk_cell() if rep is None else S.replicate(S.rebomos_bulk_cell(), rep)
+    v0 = S.gaussian_velocities(s, float(spec["temp"]), seed=sd)
+    if spec["shot"]: v0[spec["shot_atom"]] += np.array([20.0, -22.0, 18.0])
+    host = TT._host_run(lambda sy: mdref.RebomosCPU(orc, P, sy, skin=skin), s, v0, nsteps, nsteps, skin, rebuild_every=10)
+    x = S.wrap(s.box, s.x); v = v0.copy(); rebuilds = 0
+    c = capi.Context(0)
+
+    def upload(x, v):
+        eng = mdref.RebomosCPU(None, P, S.System(s.box, x.copy(), s.type, s.tag, s.mass), skin=skin)   # ghosts only
+        c.set_box_host(s.box)
+        c.set_atoms_host(eng.nlocal, eng.all_positions(x), eng.type_all, eng.tag_all, 2, map_=[0, 0, 1])
+        c.set_skin(skin)
+        c.hnve_upload_v(v)
+    try:
+        c.rebomos_set_params(ob.product_rebomos_params(P))
+        c.hnve_setup(0.001, S.FTM2V, s.mass)
+        upload(x, v)
+        c.rebomos_compute_host(s.n, eflag=0, vflag=0)
+        late_any = False
+        for step in range(nsteps):
+            moved, late = c.hnve_initial()
+            late_any |= late
+            if moved:   # the host reneighbors: what Verlet::run does when Neighbor::decide() says so
+                got = c.hnve_download(s.n, want=("x", "v"))
+                upload(S.wrap(s.box, got["x"]), got["v"]); rebuilds += 1
+            c._ck(c.L.mdp_rebomos_compute_host(c.h, 0, 0, None, None, None, None, None))
+            c.hnve_final()
+        got = c.hnve_download(s.n, want=("x", "v"))
+    finally:
+        c.close()
+    xh = host[nsteps][0]
+    dx = got["x"] - xh; dx -= np.round(s.box.x2lamda(dx + s.box.lo)) @ s.box.h.T
+    hot = spec["temp"] >= 3000 or spec["shot"]
+    return dict(dx=float(np.abs(dx).max()), late=int(late_any), rebuilds=rebuilds), dict(dx=1e-6 if hot else 1e-8, late=1)
+
+
+def line_hnve(spec, err):
+    return (f"n {spec['n']} T {spec['temp']} skin {spec['skin']} shot {spec['shot']} seed {spec['seed']} inner {spec['env'].get('MDP_INNER_SKIN')} "
+            f"dx {err['dx']:.1e} host rebuilds {err['rebuilds']} late {bool(err['late'])}")
+
+
+# ------------------------------------------------------------------------------------------------------------- minilmp
+# The plugins on N ranks of the mini-host: the thermo rows of `minilmp -np N` -- in host mode and under `fix nve/mdp` on
+# the library's bricks; on one rank: the fix in its default mode and with `bricks yes` -- must be the rows of the
+# one-rank run with the host's own `fix nve` (printed digits: rel 5e-7).
+def draw_minilmp(rng):
+    np_ = rng.choice([1, 1, 2, 3, 4, 6, 8])
+    if rng.random() < 0.5:
+        rep = rng.choice(["2 2 1", "2 2 2", "3 2 1", "1 2 2", "3 3 1"]); T = rng.choice([300, 900, 1500, 4000]); skin = rng.choice([0.4, 0.8, 2.0])
+        steps = rng.choice([60, 120, 200]); sd = rng.randrange(1, 10**7)
+        spec = dict(style="rebomos", rep=rep, T=T, skin=skin, steps=steps, seed=sd,
+                    desc=f"rebomos rep {rep} T {T} skin {skin} steps {steps} seed {sd}")
+    else:
+        n = rng.choice([8, 10, 12, 14]); T = rng.choice([300, 863, 1400, 3000]); steps = rng.choice([60, 100, 160]); sd = rng.randrange(1, 10**7)
+        frac = rng.choice([0.0075, 0.03, 0.08])
+        spec = dict(style="aeam", cells=n, frac=frac, T=T, steps=steps, seed=sd,
+                    desc=f"aeam cells {n} frac {frac} T {T} steps {steps} seed {sd}")
+    spec.update(np=np_, env={}, id=f"{spec['style']}-np{np_}-T{spec['T']}-steps{spec['steps']}")
+    return spec
+
+
+def minilmp_input(spec):
+    if spec["style"] == "rebomos":
+        text = open(os.path.join(PKG, "examples", "in.rebomos-bulk.mi355x")).read()
+        text = text.replace("create_atoms 2 box basis 1 1 basis 2 1 basis 3 2 basis 4 2 basis 5 2 basis 6 2",
+                            "create_atoms 2 box basis 1 1 basis 2 1 basis 3 2 basis 4 2 basis 5 2 basis 6 2\nreplicate " + spec["rep"])
+        text = text.replace("thermo 10", f"velocity all create {spec['T']}.0 {spec['seed']}\nneighbor {spec['skin']} bin\nthermo {spec['steps'] // 4}").replace("run 20", f"run {spec['steps']}")
+    else:
+        n = spec["cells"]
+        text = open(os.path.join(PKG, "examples", "in.aeam-alsi.mi355x")).read()
+        text = text.replace("region MeSi block 0 20 0 20 0 20", f"region MeSi block 0 {n} 0 {n} 0 {n}").replace("type/fraction 2 0.0075 7683797", f"type/fraction 2 {spec['frac']} {spec['seed']}")
+        text = text.replace("velocity all create 863.0 1082337", f"velocity all create {spec['T']}.0 {spec['seed']}").replace("thermo 100", f"thermo {spec['steps'] // 4}").replace("run 400", f"run {spec['steps']}")
+    assert "fix integrate all nve" in text
+    return text
+
+
+def _rows_equal(a, b):
+    if len(a) != len(b) or not a: return False
+    for r, q in zip(a, b):
+        for u, v in zip(r, q):
+            if abs(u - v) > 5e-7 * max(abs(v), 1.0) + 1e-5: return False
+    return True
+
+
+def run_minilmp(spec):
+    from test_plugin_boundary import _run, _thermo_rows
+    from lammps_plugins_amd.host import capi
+    env = dict(MDP_RCCL_LIBRARY=capi.FAKE_RCCL, MDP_FAKE_RCCL_TIMEOUT_S="60", MDP_FIX_STATS="1")
+    text, np_ = minilmp_input(spec), spec["np"]
+    rc0, out0, _ = _run(text)
+    if np_ == 1:   # one rank: the fix in its default mode (the host reneighbors) and with one brick of the library's
+        rc1, out1, err1 = _run(text.replace("fix integrate all nve", "fix integrate all nve/mdp"), env=env)
+        rc2, out2, err2 = _run(text.replace("fix integrate all nve", "fix integrate all nve/mdp bricks yes"), env=env)
+    else:
+        rc1, out1, err1 = _run(text, np=np_)
+        rc2, out2, err2 = _run(text.replace("fix integrate all nve", "fix integrate all nve/mdp"), np=np_, env=env)
+    r0, r1, r2 = _thermo_rows(out0), _thermo_rows(out1), _thermo_rows(out2)
+    err = dict(rc=0 if rc0 == rc1 == rc2 == 0 else 1, rows_host=0 if _rows_equal(r1, r0) else 1, rows_fix=0 if _rows_equal(r2, r0) else 1,
+               nrows=len(r0), host_builds=out0.split("Neighbor list builds = ")[-1].split()[0],
+               reneighborings=out2.split("reneighborings on the device")[0].split()[-1] if "reneighborings on the device" in out2 else "?",
+               rcs=f"{rc0} {rc1} {rc2}", stderr=f"{err1[-200:]} {err2[-200:]}")
+    return err, dict(rc=1, rows_host=1, rows_fix=1)
+
+
+def line_minilmp(spec, err):
+    ok = not (err["rc"] or err["rows_host"] or err["rows_fix"])
+    return (f"np {spec['np']} {spec['desc']} rows {err['nrows']} host builds {err['host_builds']} device reneighborings {err['reneighborings']}"
+            + ("" if ok else f" rc {err['rcs']} {err['stderr']}"))
+
+
+# ---------------------------------------------------------------------------------------------------------- trajectory
+# Device-resident trajectories against the same trajectories driven on the host with ORACLE forces: small MoS2 cells and
+# Al-Si alloys (half of them sheared), up to 4 000 K, a fast projectile in some, 120 steps with the device's own deferred
+# checks, row prunings, list rebuilds and reneighborings.  Positions 1e-8 A (hot cases 1e-6: the trajectories are
+# chaotic), energy 1e-9 eV per atom, no late pruning.
+def draw_trajectory(rng):
+    style = rng.choice(["rebomos", "aeam"]); sd = rng.randrange(1, 10**6)
+    if style == "rebomos":
+        rep = rng.choice([None, (2, 1, 1), (1, 2, 1)]); temp = rng.choice([300, 1500, 4000])
+        spec = dict(rep=rep, temp=temp, skin=2.0, n=_rebo_n(rep), env=_inner(rng, [0.3, 0.5, 1.0]), tilt=None)
+    else:
+        n = rng.choice([4, 5, 6]); temp = rng.choice([300, 863, 2500]); frac = rng.choice([0.0, 0.03, 0.2])
+        spec = dict(cells=n, temp=temp, frac=frac, skin=1.0, n=4 * n ** 3, env={}, tilt=None)
+        if rng.random() < 0.5:   # a sheared (triclinic) box
+            L = 4.045 * n
+            spec["tilt"] = [rng.uniform(-0.06, 0.06) * L for _ in range(3)]
+    shot = rng.random() < 0.4
+    spec["shot"] = (rng.randrange(spec["n"]), rng.choice([-1, 1])) if shot else None
+    spec.update(style=style, seed=sd, nsteps=120, id=f"{style}-n{spec['n']}-T{spec['temp']}-shot{int(shot)}")
+    return spec
+
+
+def run_trajectory(spec):
+    import mdref
+    import test_gpu_trajectory as TT
+    from lammps_plugins_amd.host import capi
+    R = _res(); orc, P, T, rp, af, tabs = R["orc"], R["P"], R["T"], R["rp"], R["af"], R["tabs"]
+    style, sd, skin, nsteps = spec["style"], spec["seed"], spec["skin"], spec["nsteps"]
+    if style == "rebomos":
+        s = S.rebomos_bulk_cell() if spec["rep"] is None else S.replicate(S.rebomos_bulk_cell(), spec["rep"])
+    else:
+        s = S.fcc_cell(4.045, spec["cells"], frac_type2=spec["frac"], seed=sd); s.mass[1:3] = af.mass[:2]
+        if spec["tilt"] is not None:
+            nb = S.Box(s.box.lo.copy(), s.box.prd.copy(), np.array(spec["tilt"]))
+            s = S.System(nb, nb.lamda2x(s.box.x2lamda(s.x)), s.type, s.tag, s.mass)
+    v0 = S.gaussian_velocities(s, float(spec["temp"]), seed=sd + 1)
+    if spec["shot"]: v0[spec["shot"][0]] += np.array([spec["shot"][1] * 22.0, 20.0, 18.0])   # a projectile at ~35 A/ps
+    ctx = capi.Context(0)
+    try:
+        if style == "rebomos":
+            host = TT._host_run(lambda sy: mdref.RebomosCPU(orc, P, sy, skin=skin), s, v0, nsteps, 30, skin, rebuild_every=10)
+            ctx.rebomos_set_params(rp)
+            dev, d = TT._device_run(ctx, capi.STYLE_REBOMOS, s, v0, nsteps, 30, skin, 3.0 * rp.rcmax[0][0] + skin, [0, 0, 1])
+        else:
+            host = TT._host_run(lambda sy: mdref.AeamCPU(orc, T, sy, skin=skin), s, v0, nsteps, 30, skin, rebuild_every=5)
+            ctx.aeam_set_tables(tabs)
+            dev, d = TT._device_run(ctx, capi.STYLE_AEAM, s, v0, nsteps, 30, skin, float(af.cut_table(tabs).max()) + skin, None)
+        pr = ctx.md_prune_stats()
+    finally:
+        ctx.close()
+    hot = spec["temp"] >= 2500 or spec["shot"] is not None
+    xtol, etol = (1e-6, 1e-8) if hot else (1e-8, 1e-9)
+    wx, we = TT._compare(s, host, dev, xtol=np.inf, etol=np.inf)   # (worst values; the limits are applied below)
+    return (dict(dx=wx, dE_atom=we, late=pr["late"], prunings=pr["prunings"], builds=d.builds, tilt=np.round(s.box.tilt, 1).tolist()),
+            dict(dx=xtol, dE_atom=etol, late=1))
+
+
+def line_trajectory(spec, err):
+    return (f"{spec['style']} n {spec['n']} tilt {err.get('tilt', '?')} T {spec['temp']} shot {spec['shot'] is not None} seed {spec['seed']} "
+            f"inner {spec['env'].get('MDP_INNER_SKIN')} dx {err['dx']:.1e} dE/atom {err['dE_atom']:.1e} prunings {err['prunings']} "
+            f"late {err['late']} builds {err['builds']}")
+
+
+# --------------------------------------------------------------------------------------------------------------- block
+# Parity at scale: systems of 70 000 - 390 000 atoms (MoS2 replicas scaled by 0.97 - 1.12 with jitter, or Al-Si alloys
+# with 0 - 20 % Si) run device-resident for 20 - 60 steps from 300 - 3 000 K (lists rebuilt and rows pruned on the
+# device's own triggers), then the forces of ~400-atom blocks at the box corners, the brick seams, the last tile and
+# random places against the ORACLE's for the same atoms (tests/blockcheck.py), 1e-9 eV/A; no late pruning.
+def draw_block(rng):
+    style = rng.choice(["rebomos", "aeam"]); sd = rng.randrange(1, 10**6); steps = rng.choice([20, 40, 60])
+    if style == "rebomos":
+        rep = rng.choice([(6, 5, 8), (7, 6, 8), (8, 7, 9), (10, 9, 10), (12, 10, 10)])
+        fac, amp, temp = rng.choice([0.97, 1.0, 1.0, 1.05, 1.12]), rng.choice([0.0, 0.05, 0.15]), rng.choice([300, 1000, 3000])
+        spec = dict(rep=rep, fac=fac, amp=amp, temp=temp, n=_rebo_n(rep), env=_inner(rng, [0.4, 0.6, 1.0]),
+                    desc=f"rep {rep} fac {fac} amp {amp}")
+    else:
+        n = rng.choice([28, 32, 36, 40, 46]); frac, temp = rng.choice([0.0, 0.0075, 0.08, 0.2]), rng.choice([300, 863, 2500])
+        spec = dict(cells=n, frac=frac, temp=temp, n=4 * n ** 3, env={}, desc=f"cells {n} frac {frac}")
+    spec.update(style=style, seed=sd, steps=steps, id=f"{style}-n{spec['n']}-T{spec['temp']}-steps{steps}")
+    return spec
+
+
+def run_block(spec):
+    import blockcheck
+    import mdref
+    from lammps_plugins_amd.host import capi, resident
+    R = _res(); orc, P, T, rp, af, tabs = R["orc"], R["P"], R["T"], R["rp"], R["af"], R["tabs"]
+    sd = spec["seed"]
+    ctx = capi.Context(0)
+    try:
+        if spec["style"] == "rebomos":
+            s = S.replicate(S.rebomos_bulk_cell(), spec["rep"])
+            if spec["fac"] != 1.0: s = S.scale(s, spec["fac"])
+            if spec["amp"]: s = S.jitter(s, spec["amp"], seed=sd)
+            ctx.rebomos_set_params(rp)
+            skin, cutghost, map_, st = 2.0, 3.0 * rp.rcmax[0][0] + 2.0, [0, 0, 1], capi.STYLE_REBOMOS
+            factory, shell, margin = (lambda cs: mdref.RebomosCPU(orc, P, cs)), 11.0, 16.0
+        else:
+            s = S.fcc_cell(4.045, spec["cells"], frac_type2=spec["frac"], seed=sd); s.mass[1:3] = af.mass[:2]
+            ctx.aeam_set_tables(tabs)
+            skin, cutghost, map_, st = 1.0, float(af.cut_table(tabs).max()) + 1.0, None, capi.STYLE_AEAM
+            factory, shell, margin = (lambda cs: mdref.AeamCPU(orc, T, cs)), 13.5, 10.0
+        v0 = S.gaussian_velocities(s, float(spec["temp"]), seed=sd + 1)
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        d.compute(0, 0)
+        for _ in range(spec["steps"]): d.step(0, 0, rebuild="auto")
+        pr = ctx.md_prune_stats()
+        got = ctx.md_download(d.nlocal, want=("x", "f"))
+        tags, types = d.tags_local, ctx.md_download_int("type", d.nlocal)
+        builds = d.builds
+    finally:
+        ctx.close()
+    pts = blockcheck.seeds(s.box, got["x"], n_random=3, seed=sd)
+    worst, rows = blockcheck.check_blocks(s.box, got["x"], got["f"], types, tags, s.mass, pts, factory, n_interior=400,
+                                          shell=shell, margin=margin, tol=1e-9)
+    return dict(dF=worst, late=pr["late"], blocks=len(rows), prunings=pr["prunings"], builds=builds), dict(dF=1e-9, late=1)
+
+
+def line_block(spec, err):
+    return (f"{spec['style']} n {spec['n']} {spec['desc']} T {spec['temp']} steps {spec['steps']} seed {spec['seed']} "
+            f"inner {spec['env'].get('MDP_INNER_SKIN')} worst dF {err['dF']:.1e} over {err['blocks']} blocks "
+            f"prunings {err['prunings']} late {err['late']} builds {err['builds']}")
+
+
+# ---------------------------------------------------------------------------------------------------------------- nvt
+# The Nose-Hoover chain thermostat (tests/test_gpu_nvt_net.py): chains of 1-8, 1-3 loops, drag, flat or ramped targets,
+# both styles, the resident path and (REBO-MoS) the host-linked one, atom counts whose last 256-atom block varies.
+NVT_SUITE = (25, 10)     # (seed, cases); tests/test_net_draws.py asserts the corners
+
+
+def draw_nvt(rng):
+    style = rng.choice(["rebomos", "aeam"])
+    tchain, tloop, drag = rng.randint(1, 8), rng.randint(1, 3), rng.choice([0.0, 0.2, 0.5])
+    t0 = rng.choice([300.0, 600.0])
+    t1 = rng.choice([t0, 900.0])
+    if style == "rebomos":
+        size = rng.choice([(1, 1, 1), (2, 1, 1), (3, 1, 1)])
+        n = REBO_CELL_N * size[0] * size[1] * size[2]
+        path = rng.choice(["resident", "hostlinked"])
+    else:
+        size = rng.choice([4, 5, 6, 7])
+        n = 4 * size ** 3
+        path = "resident"
+    return dict(style=style, path=path, tchain=tchain, tloop=tloop, drag=drag, t0=t0, t1=t1, size=size, n=n,
+                seed=rng.randrange(1, 10**6))
+
+
+def nvt_cases(seed, ncase):
+    rng = random.Random(seed)
+    return [draw_nvt(rng) for _ in range(ncase)]
+
+
+NETS = {name: (globals()["draw_" + name], globals()["run_" + name], globals()["line_" + name])
+        for name in ("force", "hostmode_walk", "aeam_types", "prune", "dd", "hnve", "minilmp", "trajectory", "block")}
+
+
+def main(net, argv):
+    """the command line of profiles/<net>_fuzz.py: <cases> <seed> [dd: style]; one line per case, exit status 1 if any
+    case failed"""
+    import sys
+    import time
+    ncase, seed = int(argv[0]), int(argv[1])
+    draw, run, line = NETS[net]
+    rng = random.Random(seed)
+    only = argv[2] if net == "dd" and len(argv) > 2 else None
+    bad = 0; t0 = time.time()
+    for k in range(ncase):
+        spec = draw_dd(rng, only) if net == "dd" else draw(rng)
+        try:
+            with knobs(spec["env"]):
+                err, lim = run(spec)
+            ok, text = passed(err, lim), line(spec, err)
+        except Exception as e:  # noqa: BLE001
+            ok, text = False, f"{spec['id']} exception {type(e).__name__} {str(e)[-300:]}"
+        bad += 0 if ok else 1
+        print(f"{'ok ' if ok else 'BAD'} case {k} {text}", flush=True)
+    print(f"{ncase} cases, {bad} bad, {time.time() - t0:.0f} s")
+    sys.exit(1 if bad else 0)

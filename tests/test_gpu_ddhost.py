@@ -20,11 +20,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "lammps-plugins_amd")
 
 
-def _ddhost(args, double=False, timeout=600):
+def _ddhost(args, double=False, timeout=600, env=None):
     exe = os.path.join(PKG, "ddhost")
     if not os.path.exists(exe):
         subprocess.run(["make", "-C", PKG, "ddhost"], check=True)
-    env = dict(os.environ)
+    env = dict(os.environ, **(env or {}))
     if double:
         if not os.path.exists(capi.FAKE_RCCL):
             subprocess.run(["make", "-C", PKG, "rccl-double"], check=True)

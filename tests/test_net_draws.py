@@ -1,0 +1,108 @@
+"""CPU: the fixed seeds of the GPU nets (tests/nets.py SUITE, run by tests/test_gpu_nets.py) reach the corners the nets
+exist for.  A later trim of the seeds or of the case counts that loses a corner fails here, not silently."""
+import random
+
+import pytest
+
+import nets
+
+SPECS = {net: [s for seed, n in nets.SUITE[net] for s in nets.cases(net, seed, n)] for net in nets.NETS}
+
+CORNERS = {
+    "force": {
+        "both styles": lambda c: {s["style"] for s in c} == {"rebomos", "aeam"},
+        "device lists, both styles": lambda c: {s["style"] for s in c if s["lists"] == "device"} == {"rebomos", "aeam"},
+        "host CSR lists, both styles": lambda c: {s["style"] for s in c if s["lists"] == "host_csr"} == {"rebomos", "aeam"},
+        "a sheared alloy box": lambda c: any(s["style"] == "aeam" and s["tilt"] is not None for s in c),
+        "every REBO replica": lambda c: {s["rep"] for s in c if s["style"] == "rebomos"} == {None, (2, 1, 1), (1, 2, 1), (2, 2, 1), (1, 1, 2)},
+        "Si fraction 0": lambda c: any(s["style"] == "aeam" and s["frac"] == 0.0 for s in c),
+        "Si fraction 0.5": lambda c: any(s["style"] == "aeam" and s["frac"] == 0.5 for s in c),
+    },
+    "hostmode_walk": {
+        "both styles with library-kept images": lambda c: {s["style"] for s in c if s["images"]} == {"rebomos", "aeam"},
+        "both styles with host ghosts": lambda c: {s["style"] for s in c if not s["images"]} == {"rebomos", "aeam"},
+        "one atom moved far": lambda c: any(m == "one" for s in c for m, _ in s["walk"]),
+        "a set inner skin": lambda c: any(s["env"] for s in c),
+    },
+    "aeam_types": {
+        "at most 8 types (tile kernels)": lambda c: any(s["ntypes"] <= 8 for s in c),
+        "more than 8 types (generic kernels)": lambda c: any(s["ntypes"] > 8 for s in c),
+    },
+    "prune": {
+        "both styles": lambda c: {s["style"] for s in c} == {"rebomos", "aeam"},
+        "5 000 K with a drift": lambda c: any(s["temp"] == 5000 and any(s["drift"]) for s in c),
+        "MDP_LJ_QUEUE queued and walked": lambda c: any({"queued", "walked"} <= {n for n, _ in s["variants"]} for s in c),
+        "other inner skins": lambda c: any({"inner_skin_0.3", "inner_skin_1.2"} <= {n for n, _ in s["variants"]} for s in c),
+    },
+    "dd": {
+        "both styles": lambda c: {s["style"] for s in c} == {"rebomos", "aeam"},
+        "an odd rank count": lambda c: any(s["ranks"] % 2 for s in c),
+        "mid-run thermo steps": lambda c: any(s["thermo"] != s["steps"] for s in c),
+    },
+    "hnve": {
+        "a projectile": lambda c: any(s["shot"] for s in c),
+        "no projectile": lambda c: any(not s["shot"] for s in c),
+        "both skins": lambda c: {s["skin"] for s in c} == {1.0, 2.0},
+    },
+    "minilmp": {
+        "both styles": lambda c: {s["style"] for s in c} == {"rebomos", "aeam"},
+        "host mode on several ranks": lambda c: any(s["np"] > 1 for s in c),
+        "fix nve/mdp in its one-rank modes": lambda c: any(s["np"] == 1 for s in c),
+    },
+    "trajectory": {
+        "both styles": lambda c: {s["style"] for s in c} == {"rebomos", "aeam"},
+        "a projectile": lambda c: any(s["shot"] for s in c),
+        "a sheared alloy box": lambda c: any(s["style"] == "aeam" and s["tilt"] is not None for s in c),
+    },
+    "block": {
+        "both styles": lambda c: {s["style"] for s in c} == {"rebomos", "aeam"},
+    },
+}
+
+
+@pytest.mark.parametrize("net,corner", [(n, k) for n in CORNERS for k in CORNERS[n]])
+def test_fixed_seeds_reach_the_corner(net, corner):
+    assert CORNERS[net][corner](SPECS[net]), f"{net}: no case of {nets.SUITE[net]} reaches '{corner}'"
+
+
+def test_every_net_has_its_corners_and_at_most_8_ranks():
+    assert set(CORNERS) == set(nets.NETS) == set(nets.SUITE)
+    assert all(s["ranks"] <= 8 for s in SPECS["dd"]) and all(s["np"] <= 8 for s in SPECS["minilmp"])
+
+
+def test_draws_are_pure_and_repeatable():
+    for net in nets.NETS:
+        seed, n = nets.SUITE[net][0]
+        assert nets.cases(net, seed, n) == nets.cases(net, seed, n)
+        assert all(set(s["env"]) <= set(nets.KNOBS) for s in SPECS[net])
+
+
+def test_draws_reproduce_recorded_cases():
+    """first cases of recorded runs of the command-line nets (profiles/r06_*_fuzz/): `profiles/<net>_fuzz.py <cases>
+    <seed>` still draws the cases it drew when they were recorded"""
+    s = nets.cases("dd", 6, 3)
+    assert [(c["style"], c["ranks"], c["rep"], c["temp"], c["drift"], c["steps"], c["seed"]) for c in s] == [
+        ("rebomos", 6, (2, 4, 3), 300, [-60, -30, 70], 90, 7889558), ("aeam", 4, (12, 12, 12), 1200, [-30, 70, 25], 90, 9047122),
+        ("rebomos", 3, (3, 2, 4), 5000, [70, 70, 0], 90, 1478225)]
+    f = nets.cases("force", 11, 1)[0]
+    assert f["desc"] == "cells 7 frac 0.08 amp 0.152 seed 615917 tilt [2.07, -0.16, 0.77] lists device"
+    m = nets.cases("minilmp", 7, 1)[0]
+    assert (m["np"], m["desc"]) == (2, "aeam cells 14 frac 0.0075 T 300 steps 60 seed 8990609")
+    h = nets.cases("hnve", 1, 1)[0]
+    assert (h["n"], h["temp"], h["skin"], h["shot"], h["seed"], h["env"]) == (576, 300, 2.0, True, 140892, {"MDP_INNER_SKIN": "0.5"})
+    t = nets.cases("trajectory", 5, 1)[0]
+    assert (t["style"], t["n"], t["temp"], t["shot"], t["seed"]) == ("aeam", 500, 2500, None, 777821)
+
+
+def test_nvt_seed_reaches_its_corners():
+    """the thermostat net of tests/test_gpu_nvt_net.py (nets.NVT_SUITE)"""
+    c = nets.nvt_cases(*nets.NVT_SUITE)
+    for path in ("resident", "hostlinked"):
+        assert any(s["tchain"] == 8 and s["path"] == path for s in c), f"no chain of 8 on the {path} path"
+    host = [s for s in c if s["path"] == "hostlinked"]
+    assert {s["tloop"] for s in host} >= {2, 3} and any(s["drag"] > 0 for s in host)
+    assert {s["tloop"] for s in c} == {1, 2, 3} and {s["drag"] for s in c} == {0.0, 0.2, 0.5}
+    assert {s["style"] for s in c} == {"rebomos", "aeam"} and all(s["style"] == "rebomos" for s in host)
+    assert any(s["t0"] != s["t1"] for s in c) and any(s["t0"] == s["t1"] for s in c)
+    # the last 256-atom block: several fill levels, a full one among them (n % 256 == 1 no cell of either style allows)
+    assert len({s["n"] % 256 for s in c}) >= 4 and any(s["n"] % 256 == 0 for s in c)
