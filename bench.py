@@ -17,9 +17,12 @@ all-to-all per step on RCCL, overlapped with the interior REBO centres.
 it exits non-zero -- never falls back to fewer ranks -- when a rank does not come up, when the box has fewer
 GPUs than ranks, or when RCCL reports another rank count.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  The default one-GPU run adds a `secondary`
-block: the same REBO-MoS system from 300 K (list builds and row prunings inside the timed region) and the AEAM
-configuration #3 (1,000,188 atoms, 863 K, 1000 steps, check every step), each with its own roofline / CPU baseline."""
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's headline
+needs: set-up, the W warm-up and N timed steps, --dump-outputs if asked for, the line.  `--full` also measures what
+takes runs of its own: per-kernel times and the roofline, one forced reneighboring, the host-mode rate, the CPU
+baseline and, on one GPU, a `secondary` block: the same REBO-MoS system from 300 K (list builds and row prunings
+inside the timed region), the AEAM configuration #3 (1,000,188 atoms, 863 K, 1000 steps, check every step), two
+off-lattice variants, each with its own roofline / CPU baseline, and the drop-in path on the mini-host."""
 from __future__ import annotations
 
 import argparse
@@ -480,10 +483,71 @@ def dump_outputs(dom, s, out_dir, last_step, energy_tallied, par):
                     "when that step tallied them (thermo step)"}
 
 
+# ------------------------------------------------------------------------------------------------ roofline (--full)
+def roofline_block(wl, dis, rep, world, nlocal, natoms, ms_per_step, kms, nmeas, dens, multi):
+    """the `roofline` entry: kms = mean per-phase kernel ms of nmeas force-only steps (ctx.get_timing order)"""
+    if wl == "rebomos":
+        lj = "rebo_lj_gather_kernel" if os.environ.get("MDP_LJ_TILE", "1") == "0" else "rebo_lj_tile_kernel"
+        phases = {"rebo_centre3_kernel + rebo_centre_kernel<8|12|16|32> (all launches)": kms[0],
+                  "rebo_centre_general_kernel (centres that outgrew their lane group)": kms[1],
+                  "tile_prune_kernel (when due)": kms[2], lj + " (one launch)": kms[3]}
+        single = {lj: kms[3]}                       # phases that are ONE launch: candidates for `dominant_kernel`
+    else:
+        # (each phase is timed between its own pair of events: no exchange and no host gap lies inside one)
+        phases = {dens + " (one launch)": kms[0], "aeam_density_ang_kernel": kms[1], "aeam_embed_kernel": kms[2],
+                  "aeam_tile_force_kernel (one launch)": kms[3], "aeam_force_ang_kernel": kms[4]}
+        single = {dens: kms[0], "aeam_density_ang_kernel": kms[1], "aeam_embed_kernel": kms[2],
+                  "aeam_tile_force_kernel": kms[3], "aeam_force_ang_kernel": kms[4]}
+        if multi:   # several GPUs: the tiles that reach no remote ghost run behind the exchanges
+            phases[dens + ", interior tiles (position exchange in flight)"] = kms[5]
+            phases["aeam_tile_force_kernel, interior tiles (fp / ghost-force exchange in flight)"] = kms[6]
+            single[dens + " (interior tiles)"] = kms[5]
+            single["aeam_tile_force_kernel (interior tiles)"] = kms[6]
+    # algorithmic bytes of ONE pass of the path over this rank's atoms: SURVEY 8(d) per-atom figure x atoms.
+    # `achieved` / `frac` use the time of ALL kernels of the path (the contract figure is per atom-step of the
+    # whole compute(), not of its longest kernel); the largest single launch is reported beside it with ITS counter bytes.
+    alg_bytes = B_ALG[wl] * nlocal
+    kall = float(sum(phases.values()))
+    path_achieved = alg_bytes / (kall * 1e-3) / 1e9 if kall > 0 else 0.0
+    step_achieved = B_ALG[wl] * natoms / world / (ms_per_step * 1e-3) / 1e9
+    flops_path = FLOP_ALG[wl] * nlocal / (kall * 1e-3) / 1e12 if kall > 0 else 0.0
+    flops_step = FLOP_ALG[wl] * natoms / world / (ms_per_step * 1e-3) / 1e12
+    # (counter traffic is stored per lattice configuration: an off-lattice variant of the same size has no entry of its own)
+    ent, traffic_note = pmc_entry(wl + ("_" + "_".join(sorted(dis)) if dis else ""), rep, world)
+    traffic = ent.get("bytes_per_step") if ent else None
+    dname = max(single, key=lambda k: single[k])
+    dms = float(single[dname])
+    dom_k = {"name": dname, "ms": round(dms, 4), "launches_per_step": 1}
+    if ent:
+        mine = [(k, v) for k, v in ent.get("per_kernel", {}).items() if k.startswith(dname)]
+        if mine and dms > 0:
+            kb = max(v["hbm_bytes"] for _, v in mine)     # (the force-only variant is the one measured per step)
+            dom_k.update(counter_name=max(mine, key=lambda kv: kv[1]["hbm_bytes"])[0], counter_bytes=kb,
+                         counter_GBps=round(kb / (dms * 1e-3) / 1e9, 1),
+                         counter_frac=round(kb / (dms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4))
+    return {"bound": "hbm", "achieved": round(path_achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "frac": round(path_achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_note": traffic_note,
+            "basis": "algorithmic bytes of one compute() pass of rank 0 / time of ALL kernels of the path "
+                     f"(force-only steps, HIP events on the compute stream, mean of {nmeas} steps)",
+            "algorithmic_bytes_per_pass": alg_bytes, "path_ms": round(kall, 4),
+            "phase_ms": {n: round(float(m), 4) for n, m in phases.items()},
+            "dominant_kernel": dom_k,
+            "binding": binding_block(wl + ("_" + "_".join(sorted(dis)) if dis else ""), rep, world,
+                                     {"rebo_lj_tile_kernel": "lj_tile", "rebo_lj_gather_kernel": "lj_gather",
+                                      "aeam_tile_force_kernel": "aeam_tile_force", "aeam_ptile_kernel": "aeam_ptile",
+                                      "aeam_tile_density_kernel": "aeam_tile_density"}.get(dname.split(" ")[0], dname)),
+            "whole_step": {"achieved": round(step_achieved, 2), "frac": round(step_achieved / HBM_PEAK_GBPS, 5)},
+            "fp64": {"bound": "fp64-valu", "flop_per_atom_step": FLOP_ALG[wl],
+                     "achieved": round(flops_path, 3), "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                     "frac": round(flops_path / FP64_PEAK_TFLOPS, 5),
+                     "whole_step_frac": round(flops_step / FP64_PEAK_TFLOPS, 5)}}
+
+
 # ------------------------------------------------------------------------------------------------ one measured job
-def run_job(E, job, par, dump_dir=None):
+def run_job(E, job, par, dump_dir=None, full=False):
     """job: workload, replicate, temp, steps, warmup, thermo_every, check_every, inner_skin
-    par: world, rank, local_rank, dist, dev, stage_host, native.  Returns (result dict, pieces for the host-mode leg)."""
+    par: world, rank, local_rank, dist, dev, stage_host, native.  full: after the timed steps also the per-kernel
+    times, the roofline and one forced reneighboring.  Returns (result dict, pieces for the host-mode leg)."""
     import numpy as np
     import torch
     capi, resident, S = E["capi"], E["resident"], E["S"]
@@ -595,73 +659,9 @@ def run_job(E, job, par, dump_dir=None):
         dumped = dump_outputs(dom, s, dump_dir, (overlap or {}).get("trial_steps", 0) + last,
                               bool(thermo_every and last % thermo_every == 0), par)
 
-    # ---- per-kernel time of the hot path: HIP events on the compute stream, force-only steps of the SAME Verlet loop
-    # (same rebuild policy; steps that reneighbored are left out of the average) ----
-    ctx.set_timing(True)
-    kms, kcount = np.zeros(8), [0]
-
-    def collect(rebuilt, ev):
-        if not rebuilt and not ev:
-            kms[:] += np.array(ctx.get_timing())
-            kcount[0] += 1
-
-    nmeas = 20  # (long enough for a row pruning to weigh what it weighs in the run)
-    run(nmeas, job["warmup"] + job["steps"], on_step=collect)   # (thermo steps fall where they fall and are left out)
-    kms /= max(kcount[0], 1)
-    ctx.set_timing(False)
-
-    # ---- one forced reneighboring (remap, migration, ghosts, lists; collective), wall time incl. its host syncs ----
-    sync_all()
-    t0 = time.perf_counter()
-    dom.reneighbor()
-    sync_all()
-    reneighbor_ms = (time.perf_counter() - t0) * 1e3
-
-    dom.compute(1, 1)
-    th1 = dom.thermo()
-
     value = s.n * job["steps"] / elapsed / 1e6
     ms_per_step = elapsed / job["steps"] * 1e3
-    if wl == "rebomos":
-        lj = "rebo_lj_gather_kernel" if os.environ.get("MDP_LJ_TILE", "1") == "0" else "rebo_lj_tile_kernel"
-        phases = {"rebo_centre3_kernel + rebo_centre_kernel<8|12|16|32> (all launches)": kms[0],
-                  "rebo_centre_general_kernel (centres that outgrew their lane group)": kms[1],
-                  "tile_prune_kernel (when due)": kms[2], lj + " (one launch)": kms[3]}
-        single = {lj: kms[3]}                       # phases that are ONE launch: candidates for `dominant_kernel`
-    else:
-        dens = "aeam_tile_density_kernel" if os.environ.get("MDP_AEAM_PERSIST", "") == "0" else "aeam_ptile_kernel"
-        # (each phase is timed between its own pair of events: no exchange and no host gap lies inside one)
-        phases = {dens + " (one launch)": kms[0], "aeam_density_ang_kernel": kms[1], "aeam_embed_kernel": kms[2],
-                  "aeam_tile_force_kernel (one launch)": kms[3], "aeam_force_ang_kernel": kms[4]}
-        single = {dens: kms[0], "aeam_density_ang_kernel": kms[1], "aeam_embed_kernel": kms[2],
-                  "aeam_tile_force_kernel": kms[3], "aeam_force_ang_kernel": kms[4]}
-        if dist is not None:   # several GPUs: the tiles that reach no remote ghost run behind the exchanges
-            phases[dens + ", interior tiles (position exchange in flight)"] = kms[5]
-            phases["aeam_tile_force_kernel, interior tiles (fp / ghost-force exchange in flight)"] = kms[6]
-            single[dens + " (interior tiles)"] = kms[5]
-            single["aeam_tile_force_kernel (interior tiles)"] = kms[6]
-    # algorithmic bytes of ONE pass of the path over this rank's atoms: SURVEY 8(d) per-atom figure x atoms.
-    # `achieved` / `frac` use the time of ALL kernels of the path (the contract figure is per atom-step of the
-    # whole compute(), not of its longest kernel); the largest single launch is reported beside it with ITS counter bytes.
-    alg_bytes = B_ALG[wl] * dom.nlocal
-    kall = float(sum(phases.values()))
-    path_achieved = alg_bytes / (kall * 1e-3) / 1e9 if kall > 0 else 0.0
-    step_achieved = B_ALG[wl] * s.n / world / (ms_per_step * 1e-3) / 1e9
-    flops_path = FLOP_ALG[wl] * dom.nlocal / (kall * 1e-3) / 1e12 if kall > 0 else 0.0
-    flops_step = FLOP_ALG[wl] * s.n / world / (ms_per_step * 1e-3) / 1e12
-    # (counter traffic is stored per lattice configuration: an off-lattice variant of the same size has no entry of its own)
-    ent, traffic_note = pmc_entry(wl + ("_" + "_".join(sorted(dis)) if dis else ""), rep, world)
-    traffic = ent.get("bytes_per_step") if ent else None
-    dname = max(single, key=lambda k: single[k])
-    dms = float(single[dname])
-    dom_k = {"name": dname, "ms": round(dms, 4), "launches_per_step": 1}
-    if ent:
-        mine = [(k, v) for k, v in ent.get("per_kernel", {}).items() if k.startswith(dname)]
-        if mine and dms > 0:
-            kb = max(v["hbm_bytes"] for _, v in mine)     # (the force-only variant is the one measured per step)
-            dom_k.update(counter_name=max(mine, key=lambda kv: kv[1]["hbm_bytes"])[0], counter_bytes=kb,
-                         counter_GBps=round(kb / (dms * 1e-3) / 1e9, 1),
-                         counter_frac=round(kb / (dms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4))
+    dens = "aeam_tile_density_kernel" if os.environ.get("MDP_AEAM_PERSIST", "") == "0" else "aeam_ptile_kernel"
     out = {
         "metric": "Matom-steps/sec",
         "value": round(value, 4),
@@ -692,7 +692,7 @@ def run_job(E, job, par, dump_dir=None):
                    "displacement_check": "every step, deferred on-device flag" if dist is None
                    else ("every step, every rank's flag gathered behind the position exchange (no blocking collective)"
                          if native else f"every {check_every} steps, collective"),
-                   "reneighborings_in_timed_region": rebuilds, "reneighbor_wall_ms": round(reneighbor_ms, 3),
+                   "reneighborings_in_timed_region": rebuilds,
                    "dangerous_builds": int(dom.dangerous),
                    "inner_skin": (float(os.environ["MDP_INNER_SKIN"]) if "MDP_INNER_SKIN" in os.environ
                                   else "adaptive from 1.0") if wl == "rebomos" else None,
@@ -704,25 +704,37 @@ def run_job(E, job, par, dump_dir=None):
                    "row_prunings_late_rank0": prune1["late"] - prune0["late"],
                    "row_pruning": (f"tile rows re-filtered to window + {prune1['buffer']:.2f} A from the current positions, "
                                    "own displacement trigger") if prune1["active"] else "off",
-                   "pe_per_atom_start_eV": round(pe0 / s.n, 6), "pe_per_atom_end_eV": round(th1["pe"] / s.n, 6),
-                   "temp_end_K": round(th1["temp"], 2)},
-        "roofline": {"bound": "hbm", "achieved": round(path_achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(path_achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_note": traffic_note,
-                     "basis": "algorithmic bytes of one compute() pass of rank 0 / time of ALL kernels of the path "
-                              f"(force-only steps, HIP events on the compute stream, mean of {kcount[0]} steps)",
-                     "algorithmic_bytes_per_pass": alg_bytes, "path_ms": round(kall, 4),
-                     "phase_ms": {n: round(float(m), 4) for n, m in phases.items()},
-                     "dominant_kernel": dom_k,
-                     "binding": binding_block(wl + ("_" + "_".join(sorted(dis)) if dis else ""), rep, world,
-                                              {"rebo_lj_tile_kernel": "lj_tile", "rebo_lj_gather_kernel": "lj_gather",
-                                               "aeam_tile_force_kernel": "aeam_tile_force", "aeam_ptile_kernel": "aeam_ptile",
-                                               "aeam_tile_density_kernel": "aeam_tile_density"}.get(dname.split(" ")[0], dname)),
-                     "whole_step": {"achieved": round(step_achieved, 2), "frac": round(step_achieved / HBM_PEAK_GBPS, 5)},
-                     "fp64": {"bound": "fp64-valu", "flop_per_atom_step": FLOP_ALG[wl],
-                              "achieved": round(flops_path, 3), "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                              "frac": round(flops_path / FP64_PEAK_TFLOPS, 5),
-                              "whole_step_frac": round(flops_step / FP64_PEAK_TFLOPS, 5)}},
+                   "pe_per_atom_start_eV": round(pe0 / s.n, 6)},
     }
+    if full:
+        # ---- per-kernel time of the hot path: HIP events on the compute stream, force-only steps of the SAME Verlet
+        # loop (same rebuild policy; steps that reneighbored are left out of the average) ----
+        ctx.set_timing(True)
+        kms, kcount = np.zeros(8), [0]
+
+        def collect(rebuilt, ev):
+            if not rebuilt and not ev:
+                kms[:] += np.array(ctx.get_timing())
+                kcount[0] += 1
+
+        nmeas = 20  # (long enough for a row pruning to weigh what it weighs in the run)
+        run(nmeas, job["warmup"] + job["steps"], on_step=collect)   # (thermo steps fall where they fall and are left out)
+        kms /= max(kcount[0], 1)
+        ctx.set_timing(False)
+
+        # ---- one forced reneighboring (remap, migration, ghosts, lists; collective), wall time incl. its host syncs ----
+        sync_all()
+        t0 = time.perf_counter()
+        dom.reneighbor()
+        sync_all()
+        reneighbor_ms = (time.perf_counter() - t0) * 1e3
+
+        dom.compute(1, 1)
+        th1 = dom.thermo()
+        out["config"].update(reneighbor_wall_ms=round(reneighbor_ms, 3), pe_per_atom_end_eV=round(th1["pe"] / s.n, 6),
+                             temp_end_K=round(th1["temp"], 2))
+        out["roofline"] = roofline_block(wl, dis, rep, world, dom.nlocal, s.n, ms_per_step, kms, kcount[0], dens,
+                                         dist is not None)
     # how the work was spread over the kernel classes (the lattice-tuned fast paths against their fallbacks)
     try:
         cs = ctx.md_class_stats()
@@ -777,10 +789,15 @@ def main():
     ap.add_argument("--strain", type=float, nargs=2, default=None, metavar=("SCALE", "JITTER"),
                     help="rebomos: box and coordinates x SCALE, uniform jitter +-JITTER A (R-strain-112: 1.12 0.15)")
     ap.add_argument("--frac2", type=float, default=None, help="aeam: fraction of atoms of type 2 (sample.in: 0.0075)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-mode", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure what it does not need: per-kernel times and roofline, one forced "
+                         "reneighboring, the host-mode rate, the CPU baseline and the secondary block (--no-* below leave "
+                         "parts of it out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--no-host-mode", action="store_true", help="--full: no host-mode rate, no mini-host runs")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary block (REBO-MoS from 300 K, AEAM configuration #3) of the default one-GPU run")
+                    help="--full: skip the secondary block (REBO-MoS from 300 K, AEAM configuration #3, ...) of a one-GPU "
+                         "run and the C++ hosts of an N-rank run")
     ap.add_argument("--inner-skin", type=float, default=None,
                     help="skin of the style's own device-built lists in A (default: library default 1.0, capped by "
                          "the host skin); they are rebuilt on the device when an atom has moved half of it")
@@ -871,11 +888,11 @@ def main():
         job["disorder"] = dict(scale=args.strain[0], jitter=args.strain[1], seed=1234)
     if args.frac2 is not None and args.workload == "aeam":
         job["disorder"] = dict(frac2=args.frac2)
-    out, pieces = run_job(E, job, par, dump_dir=args.dump_outputs)
+    out, pieces = run_job(E, job, par, dump_dir=args.dump_outputs, full=args.full)
     out["config"]["rccl_ranks"] = rccl_ranks
     if os.environ.get("MDP_BENCH_FALLBACK_REASON"):
         out["transport_fallback"] = os.environ["MDP_BENCH_FALLBACK_REASON"]
-    if rank == 0 and world == 1 and dist is None and not args.no_host_mode:
+    if args.full and rank == 0 and world == 1 and dist is None and not args.no_host_mode:
         try:
             hm, img = host_mode_rate(E, pieces["s"], args.workload, pieces["pot"], pieces["skin"], pieces["cutghost"])
             out["host_mode_ms_per_step"] = round(hm, 3)
@@ -885,12 +902,12 @@ def main():
             log(f"[bench] host-mode measurement failed: {e}")
     pieces = None
 
-    # ---- secondary block of the default one-GPU run: what the cold-start headline does not show ----
-    if world == 1 and dist is None and not custom and not args.no_secondary:
+    # ---- secondary block of a --full one-GPU run: what the cold-start headline does not show ----
+    if args.full and world == 1 and dist is None and not custom and not args.no_secondary:
         sec = {}
         try:
             hot = dict(job, temp=300.0, steps=max(200, args.steps), warmup=20)
-            o, _ = run_job(E, hot, par)
+            o, _ = run_job(E, hot, par, full=True)
             sec["rebomos_300K"] = {k: o[k] for k in ("value", "unit", "steps", "warmup", "ms_per_step", "config", "roofline")}
             sec["rebomos_300K"]["note"] = ("the headline system started at 300 K (SURVEY 8d config #4 variant): style-list "
                                            "builds and row prunings happen inside the timed region")
@@ -899,7 +916,7 @@ def main():
         try:
             aj = dict(workload="aeam", replicate=DEFAULT_REPLICATE["aeam"], temp=863.0, steps=1000, warmup=20,
                       thermo_every=THERMO_EVERY["aeam"], check_every=args.check_every)
-            o, pieces = run_job(E, aj, par)
+            o, pieces = run_job(E, aj, par, full=True)
             o["note"] = "BASELINE.json configs[2] / SURVEY 8d config #3 as written: 1,000,188 atoms, 863 K, 1000 NVE steps, check every step"
             if not args.no_host_mode:
                 try:
@@ -923,7 +940,7 @@ def main():
         try:
             sj = dict(job, temp=300.0, steps=max(200, args.steps), warmup=20,
                       disorder=dict(scale=1.12, jitter=0.15, seed=1234))
-            o, _ = run_job(E, sj, par)
+            o, _ = run_job(E, sj, par, full=True)
             sec["rebomos_strained_112_jitter_300K"] = {k: o[k] for k in ("value", "unit", "steps", "warmup", "ms_per_step", "config", "roofline")}
             sec["rebomos_strained_112_jitter_300K"]["note"] = (
                 "R-strain-112 of SURVEY Appendix C replicated 24x24x24 (3 981 312 atoms), 300 K: switching interior, LJ cubic "
@@ -933,7 +950,7 @@ def main():
         try:
             aj = dict(workload="aeam", replicate=DEFAULT_REPLICATE["aeam"], temp=863.0, steps=300, warmup=20,
                       thermo_every=THERMO_EVERY["aeam"], check_every=args.check_every, disorder=dict(frac2=0.08))
-            o, _ = run_job(E, aj, par)
+            o, _ = run_job(E, aj, par, full=True)
             sec["aeam_8pct_si"] = {k: o[k] for k in ("value", "unit", "steps", "warmup", "ms_per_step", "config", "roofline")}
             sec["aeam_8pct_si"]["note"] = ("A-6-8pct of SURVEY Appendix C at the size of config #3: 1 000 188 atoms, 8 % Si "
                                            "(80 000 angular centres with their O(n^2) triplet loops), 863 K")
@@ -1011,7 +1028,7 @@ def main():
     # at the barrier below).  One thread per GPU in ONE process each: `ddhost -ranks N` through the C-ABI alone, and
     # `minilmp -np N` through the plugin surface with fix nve/mdp on the library's bricks.  Informational; a failure is logged.
     plain_rebomos = args.workload == "rebomos" and args.temp == 0.0 and args.strain is None   # (any --replicate: the children take it)
-    if world > 1 and rank == 0 and plain_rebomos and not args.no_secondary and native:
+    if args.full and world > 1 and rank == 0 and plain_rebomos and not args.no_secondary and native:
         sec = {}
         pkg = os.path.join(ROOT, "lammps-plugins_amd")
         import re
@@ -1042,7 +1059,7 @@ def main():
         if sec:
             out["secondary"] = sec
     # the CPU baseline runs on rank 0 AFTER every timed region (the other ranks wait at the barrier below)
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         attach_cpu_baseline(out, args.workload, 8.0)
     if rank == 0:
         sys.stdout.flush()

@@ -9,7 +9,7 @@ i=0
 for v in "$@"; do
   i=$((i+1))
   ( [ "$v" != "-" ] && export $v
-    timeout -k 10 400 python3 bench.py --workload aeam --temp 863 --steps $STEPS --warmup 20 --no-cpu-baseline --no-host-mode --no-secondary \
+    timeout -k 10 400 python3 bench.py --workload aeam --temp 863 --steps $STEPS --warmup 20 --full --no-cpu-baseline --no-host-mode --no-secondary \
        > $OUT/run$i.json 2> $OUT/run$i.err ) || echo "run $i failed"
   echo "== $v"
   python3 - $OUT/run$i.json <<'PY'

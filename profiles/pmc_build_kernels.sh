@@ -2,11 +2,12 @@
 # counters of the LIST-BUILD kernels (tile_scan, cand_build, tile_sort, classify, rev, tile_fill ...) of one forced
 # reneighboring of the bench workload.  usage: profiles/pmc_build_kernels.sh <outdir-under-gpurun_out> [bench args...]
 set -u
+BENCH=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1; shift
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 run() { name=$1; shift
-  rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --no-host-mode $BENCH_ARGS > $OUT/$name.json 2> $OUT/$name.err || echo "pass $name failed"; }
+  rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 $BENCH --steps 2 --warmup 1 --full --no-cpu-baseline --no-secondary --no-host-mode $BENCH_ARGS > $OUT/$name.json 2> $OUT/$name.err || echo "pass $name failed"; }
 BENCH_ARGS="$*"
 run sq1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU
 run sq2 SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS

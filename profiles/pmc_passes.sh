@@ -2,12 +2,13 @@
 # PMC passes over the bench workload (one counter group per run; never combined with tracing).
 # usage: profiles/pmc_passes.sh <outdir-under-gpurun_out> [bench args...]
 set -u
+BENCH=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1; shift
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 run() { # name counters...
   name=$1; shift
-  rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 $GRAFT_REPO_ROOT/bench.py --steps 4 --warmup 1 --no-cpu-baseline $BENCH_ARGS > $OUT/$name.json 2> $OUT/$name.err || echo "pass $name failed"
+  rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 $BENCH --steps 4 --warmup 1 --full --no-cpu-baseline $BENCH_ARGS > $OUT/$name.json 2> $OUT/$name.err || echo "pass $name failed"
 }
 BENCH_ARGS="$*"
 run fetch FETCH_SIZE

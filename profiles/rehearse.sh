@@ -5,7 +5,7 @@
 set -u
 cd $GRAFT_REPO_ROOT; O=gpurun_out/${1:-rehearse}; mkdir -p $O
 run() { tag=$1; n=$2; shift 2
-  MDP_BENCH_BACKEND=gloo timeout -k 10 400 python3 bench.py --gpus $n "$@" --no-host-mode > $O/$tag.json 2> $O/$tag.err
+  MDP_BENCH_BACKEND=gloo timeout -k 10 400 python3 bench.py --gpus $n "$@" --full --no-host-mode > $O/$tag.json 2> $O/$tag.err
   echo "$tag rc=$?"; grep '^{' $O/$tag.json | python3 -c "
 import json,sys
 for l in sys.stdin:
@@ -30,12 +30,12 @@ timeout -k 10 200 python3 bench.py --gpus 2 --replicate 4 4 4 --steps 2 --warmup
 # the N>1 code path of bench.py over RCCL itself with ONE rank: every periodic self-image travels through the transport
 # to the rank itself (torch.distributed all_to_all on the "nccl" backend, then the library's ncclSend/ncclRecv)
 for tr in torch native; do
-  MDP_BENCH_SELF_REMOTE=1 MDP_BENCH_TRANSPORT=$tr timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --replicate 12 12 12 --temp 300 --steps 200 --warmup 10 --no-cpu-baseline > $O/self_$tr.json 2> $O/self_$tr.err
+  MDP_BENCH_SELF_REMOTE=1 MDP_BENCH_TRANSPORT=$tr timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --replicate 12 12 12 --temp 300 --steps 200 --warmup 10 --full --no-cpu-baseline > $O/self_$tr.json 2> $O/self_$tr.err
   echo "self_$tr rc=$? stdout lines: $(wc -l < $O/self_$tr.json)"; python3 -c "
 import json;d=json.load(open('$O/self_$tr.json'));c=d['config'];print('  ', d['value'], d['ms_per_step'], c['transport'], c['pe_per_atom_end_eV'], c['temp_end_K'])"
   # aeam: position exchange, fp forward and ghost-force reverse exchanges through RCCL to the rank itself, against the
   # plain one-GPU run of the same system (aeam_plain below)
-  MDP_BENCH_SELF_REMOTE=1 MDP_BENCH_TRANSPORT=$tr timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29542 bench.py --gpus 1 --workload aeam --replicate 63 63 63 --temp 863 --steps 200 --warmup 10 --no-cpu-baseline > $O/self_aeam_$tr.json 2> $O/self_aeam_$tr.err
+  MDP_BENCH_SELF_REMOTE=1 MDP_BENCH_TRANSPORT=$tr timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29542 bench.py --gpus 1 --workload aeam --replicate 63 63 63 --temp 863 --steps 200 --warmup 10 --full --no-cpu-baseline > $O/self_aeam_$tr.json 2> $O/self_aeam_$tr.err
   echo "self_aeam_$tr rc=$? stdout lines: $(wc -l < $O/self_aeam_$tr.json)"; python3 -c "
 import json;d=json.load(open('$O/self_aeam_$tr.json'));c=d['config'];print('  ', d['value'], d['ms_per_step'], c['transport'], c['pe_per_atom_end_eV'], c['temp_end_K'], 'phased steps', c.get('aeam_steps_with_exchanges_behind_interior_tiles_rank0'), 'interior', c.get('aeam_interior_tiles_rank0'), 'of', c.get('aeam_tiles_rank0'))"
 done

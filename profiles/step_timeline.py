@@ -2,7 +2,7 @@
 """timeline of one MD step from a rocprofv3 kernel trace (start, duration and the gap before each kernel, us) and the
 mean over the last steps of the trace.  profiles/subdomain_step.py ends with rank 0 stepping alone, so the last steps
 are that loop.  usage: step_timeline.py <dir with trace/> [steps to average, default 30] [which step to print, from the end]
-(bench.py ends with 20 steps that carry timing events between the kernels and one forced reneighboring: pass e.g.
+(bench.py --full ends with 20 steps that carry timing events between the kernels and one forced reneighboring: pass e.g.
 `60 45` to print a step of the timed region and `60`... the mean then still spans those 20 steps)"""
 import csv, glob, sys
 f = sorted(glob.glob(sys.argv[1] + "/trace/*/*kernel_trace.csv"))[-1]

@@ -44,7 +44,7 @@ def test_n_rank_code_path_over_rccl_prints_one_line():
     """MDP_BENCH_SELF_REMOTE=1 under torch.distributed.run with one rank: bench.py takes its N>1 code path (process
     group on RCCL, collective checks, per-rank gathers; periodic images travel through the all-to-all to the rank
     itself).  stdout must hold the result line and nothing else -- RCCL prints a version banner to stdout when a
-    communicator comes up -- and the line must describe the decomposition."""
+    communicator comes up -- and the line must describe the decomposition (and, with --full, its roofline)."""
     import json
     import socket
     with socket.socket() as sk:
@@ -54,7 +54,7 @@ def test_n_rank_code_path_over_rccl_prints_one_line():
     env.update(MDP_BENCH_SELF_REMOTE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--replicate",
-                        "6", "6", "6", "--temp", "300", "--steps", "20", "--warmup", "3", "--no-cpu-baseline"],
+                        "6", "6", "6", "--temp", "300", "--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=500)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

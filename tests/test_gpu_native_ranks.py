@@ -140,10 +140,10 @@ def test_failing_library_transport_falls_back_to_torch_and_says_so():
 
 @pytest.mark.timeout(900)
 def test_bench_on_n_ranks_also_runs_the_two_cpp_hosts_on_the_same_ranks():
-    """a plain REBO-MoS line on N ranks carries `secondary`: `ddhost -ranks N` (the C-ABI alone) and `minilmp -np N` with
-    fix nve/mdp on the library's bricks (the plugin surface), started by rank 0 behind the timed region"""
+    """a --full REBO-MoS line from rest on N ranks carries `secondary`: `ddhost -ranks N` (the C-ABI alone) and
+    `minilmp -np N` with fix nve/mdp on the library's bricks (the plugin surface), started by rank 0 behind the timed region"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-           "--replicate", "6", "6", "4", "--no-cpu-baseline"]
+           "--replicate", "6", "6", "4", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, env=_env("60"), capture_output=True, text=True, timeout=800)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
