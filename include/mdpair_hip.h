@@ -485,6 +485,42 @@ int mdp_nhc_state(mdp_ctx *ctx, double *out);
 int mdp_nhc_set_state(mdp_ctx *ctx, const double *in);
 int mdp_nhc_off(mdp_ctx *ctx);
 
+/* ---- Langevin thermostat on the device (LAMMPS fix langevin without gjf / angmom / omega; the plugin style
+ * `fix langevin/mdp`) -----
+ * Once set, the kernel that first consumes a compute's forces adds the Langevin force of that step in registers
+ * (FixLangevin::post_force): f_L = gfactor1[t] v + gfactor2[t] sqrt(T(n)) (u - 0.5) per component, with
+ *   gfactor1[t] = -mass[t] / damp / ftm2v / ratio[t],  gfactor2[t] = sqrt(mass[t]) sqrt(24 boltz / damp / dt / mvv2e)
+ *   / ftm2v / sqrt(ratio[t]),  T(n) = Tstart + (n - first) / (last - first) (Tstop - Tstart)
+ * and v the velocities after the initial half of step n.  The kernels are those of the integrate calls: the resident
+ * ones (initial / final / final_initial / integrate_check, and so the bricks step) and the host-mode ones (hnve initial
+ * / final).  A final half on its own writes f + f_L back, so the next initial half uses LAMMPS' modified forces.
+ * Noise: Philox4x32-10, key {seed, 0}, counter {tag, (uint32) n, (uint32) (n >> 32), phase} (phase 0: the post_force of
+ * step n, 1: the setup force of the run's first step); words 0..2 give x, y, z as u = (r + 0.5) 2^-32.  The noise of
+ * an atom depends on its tag and the step alone, so the trajectory does not depend on the atom order or on the number
+ * of ranks.  Needs the atoms' tags.
+ *   setup: see mdp_langevin_config.  zero: the mean of the random parts (over natoms) is taken out of every force.
+ *          tally: the energy the thermostat has taken out (FixLangevin::compute_scalar with tally yes).  zero and tally
+ *          need the whole system on one rank: a brick of several ranks refuses them (in either call order).  The
+ *          Nose-Hoover chain and the Langevin thermostat refuse each other on one context.
+ *   run(first, last): the ramp of the next run (steps beyond `last` hold Tstop); the step counter starts at `first`
+ *          and advances with every initial half.  The next initial half applies the setup force (phase 1, at step `first`) first.
+ *   tally: *out = the thermostat energy (0 without tally yes); completes a deferred final half first.
+ *   A final half deferred by the host (mdp_md_defer_final) completes inside mdp_langevin_run and mdp_langevin_off.
+ *   After mdp_langevin_off the forces on the device still hold the last Langevin force (LAMMPS' atom->f does too)
+ *   until the next compute: a new run computes them first (Verlet::setup). */
+typedef struct {
+  double t_start, t_stop, t_period; /* Tstart Tstop damp (T >= 0, damp > 0)                              */
+  int seed;                         /* > 0                                                               */
+  int zero, tally;                  /* zero yes / tally yes                                              */
+  double boltz, mvv2e;              /* force->boltz, force->mvv2e                                        */
+  double ratio[16];                 /* scale: per type 1..15 (> 0; 1 when not scaled)                    */
+  long long natoms;                 /* atoms in the system (zero yes divides by it)                      */
+} mdp_langevin_config;
+int mdp_langevin_setup(mdp_ctx *ctx, const mdp_langevin_config *cfg);
+int mdp_langevin_run(mdp_ctx *ctx, long long first, long long last);
+int mdp_langevin_tally(mdp_ctx *ctx, double *out);
+int mdp_langevin_off(mdp_ctx *ctx);
+
 /* per-phase device time of the last compute in ms (HIP events on the compute stream):
  * rebomos: [0]=REBO centre kernels of the lane-group classes, [1]=the general kernel (centres that outgrew their lane
  * group since the list build), [2]=row pruning (0 unless one was due), [3]=LJ+gather kernel;

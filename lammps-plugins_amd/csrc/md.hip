@@ -225,14 +225,18 @@ __global__ __launch_bounds__(256) void ang_select_kernel(const int nlocal, const
 // SC: the style-level checks and the accumulator reset of the compute that follows, in the same pass (MdpStyleCheck).
 // SCALE: the thermostat's velocity factor *vscale between the two half-kicks (nhc.hip); the NVE instantiations
 // (SCALE = false) never read it, so their code is what it was without a thermostat.
-template <bool FINAL, bool CHECK, bool SCALE = false>
+// LANGEVIN: this kernel is the first reader of the compute's forces and adds the Langevin force of the step (L,
+// langevin.hip) to them in registers, from the velocities it reads; L.part: the per-block sums of f_L . v for the tally
+// (v after the final half; with FINAL = false the setup force, and v as read).  LANGEVIN = false never reads L.
+template <bool FINAL, bool CHECK, bool SCALE = false, bool LANGEVIN = false>
 __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const double *__restrict__ rmass,
                                    double *__restrict__ f, double *__restrict__ v, double4 *__restrict__ xq,
                                    const mdp_hold_t *__restrict__ xhold, const double trigsq, const double hardsq,
                                    int *__restrict__ flag, const MdpStyleCheck SC, const int zero_f,
                                    double *__restrict__ dflag_set = nullptr, double *__restrict__ dflag_clear = nullptr,
-                                   const double *__restrict__ vscale = nullptr)
+                                   const double *__restrict__ vscale = nullptr, const MdpLgvArgs L = MdpLgvArgs())
 {
+  double lgv_e = 0.0; // (LANGEVIN, tally: f_L . v of this atom)
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (CHECK && dflag_clear && i == 0) *dflag_clear = 0.0; // (the word of the next step; this step's was cleared a step ago)
   bool t = false, h = false, sa = false, sah = false, sp = false, sph = false;
@@ -249,18 +253,26 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
   }
   if (i < nlocal) {
     const double s = dtf / rmass[i];
-    const double fx = f[3 * (size_t) i], fy = f[3 * (size_t) i + 1], fz = f[3 * (size_t) i + 2];
+    double fx = f[3 * (size_t) i], fy = f[3 * (size_t) i + 1], fz = f[3 * (size_t) i + 2];
     if (zero_f) { // the forces have had their last reader: force_clear of the next compute (a style that accumulates)
       f[3 * (size_t) i] = 0.0;
       f[3 * (size_t) i + 1] = 0.0;
       f[3 * (size_t) i + 2] = 0.0;
     }
     double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
+    double lx = 0.0, ly = 0.0, lz = 0.0;
+    if (LANGEVIN) { // post_force of step n (or the setup force): f += f_L, kept for both half-kicks
+      mdp_lgv_force(L, i, vx, vy, vz, lx, ly, lz);
+      fx = fx + lx;
+      fy = fy + ly;
+      fz = fz + lz;
+    }
     if (FINAL) { // final_integrate (step n)
       vx += s * fx;
       vy += s * fy;
       vz += s * fz;
     }
+    if (LANGEVIN && L.part) lgv_e = lx * vx + ly * vy + lz * vz; // (end_of_step of step n: v after the final half)
     if (SCALE) { // the thermostat's factor (nhc.hip): final half of step n (if FINAL) times initial half of step n+1
       const double S = *vscale;
       vx *= S;
@@ -306,6 +318,8 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
       sph = d2 > SC.hard_p;
     }
   }
+  if constexpr (LANGEVIN)
+    if (L.part) mdp_block_sum_256(lgv_e, L.part);
   if (CHECK) { // (pinned host words zeroed by the host before the launch: plain idempotent stores)
     if (__ballot(t) && (threadIdx.x & 63) == 0) {
       flag[0] = 1;
@@ -341,6 +355,37 @@ __global__ void nve_final_kernel(int nlocal, double dtf, const double *__restric
   v[3 * (size_t) i] += s * f[3 * (size_t) i];
   v[3 * (size_t) i + 1] += s * f[3 * (size_t) i + 1];
   v[3 * (size_t) i + 2] += s * f[3 * (size_t) i + 2];
+}
+
+// a final half on its own with the Langevin force (langevin.hip): f += f_L is written back (writeback), so that the
+// initial half of the next step kicks with the same modified forces (LAMMPS keeps them in atom->f); L.part: the
+// tally's partials
+__global__ __launch_bounds__(256) void lgv_final_kernel(int nlocal, double dtf, const double *__restrict__ rmass,
+                                                        double *__restrict__ f, double *__restrict__ v, const MdpLgvArgs L,
+                                                        const int writeback)
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double e = 0.0;
+  if (i < nlocal) {
+    const double s = dtf / rmass[i];
+    double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
+    double lx, ly, lz;
+    mdp_lgv_force(L, i, vx, vy, vz, lx, ly, lz);
+    const double fx = f[3 * (size_t) i] + lx, fy = f[3 * (size_t) i + 1] + ly, fz = f[3 * (size_t) i + 2] + lz;
+    if (writeback) {
+      f[3 * (size_t) i] = fx;
+      f[3 * (size_t) i + 1] = fy;
+      f[3 * (size_t) i + 2] = fz;
+    }
+    vx += s * fx;
+    vy += s * fy;
+    vz += s * fz;
+    v[3 * (size_t) i] = vx;
+    v[3 * (size_t) i + 1] = vy;
+    v[3 * (size_t) i + 2] = vz;
+    e = lx * vx + ly * vy + lz * vz;
+  }
+  if (L.part) mdp_block_sum_256(e, L.part);
 }
 
 __global__ void ghost_refresh_kernel(int nlocal, int nghost, const int *__restrict__ owner,
@@ -572,6 +617,19 @@ __global__ void x3_to_xq_kernel(int n, const double *__restrict__ x3, double4 *_
   x.y = x3[3 * (size_t) i + 1];
   x.z = x3[3 * (size_t) i + 2];
   xq[i] = x;
+}
+
+// a final half on its own with the Langevin thermostat on (mdp_md_final_integrate, mdp_hnve_final).  writeback: the
+// initial half that follows kicks with these forces (false: the forces of a new run's setup come next instead)
+int lgv_final(mdp_ctx *c, double dtf, double dt, double ftm2v, bool writeback = true)
+{
+  bool apply = false;
+  MdpLgvArgs L;
+  MDP_TRY(mdp_lgv_open(c, c->nlocal, dt, ftm2v, false, false, &apply, &L));
+  if (c->nlocal)
+    lgv_final_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, dtf, c->rmass.p, c->f.p, c->v.p, L, writeback ? 1 : 0);
+  MDP_HIP(c, hipGetLastError());
+  return mdp_lgv_close(c, c->nlocal, dt, L);
 }
 
 } // namespace
@@ -979,6 +1037,17 @@ int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double
   const double dtf = 0.5 * c->cfg.dt * c->cfg.ftm2v;
   const double *vscale = nullptr;
   if (c->nhc.on) MDP_TRY(mdp_nhc_open(c, c->nlocal, dtf, c->cfg.dt, &with_final, &vscale));
+  bool lgv = false;
+  MdpLgvArgs L;
+  if (c->lgv.on) {
+    // a final half pending across mdp_langevin_run (a host that does not defer it) goes first, on its own, and leaves f
+    // as it was: the setup force of the new run is added to the compute's forces alone, as after Verlet::setup
+    if (with_final && c->lgv.need_setup) {
+      MDP_TRY(lgv_final(c, dtf, c->cfg.dt, c->cfg.ftm2v, false));
+      with_final = false;
+    }
+    MDP_TRY(mdp_lgv_open(c, c->nlocal, c->cfg.dt, c->cfg.ftm2v, with_final, true, &lgv, &L));
+  }
   // aeam accumulates into f (three-body atomics, tile kernels): its force_clear rides in this kernel and in the refresh
   // of the images when every ghost is a periodic self-image (one GPU).  The flag is dropped by whatever rebuilds or
   // re-orders the atom arrays before the compute (mdp_aeam_prepare) -- the compute then clears f itself.
@@ -998,14 +1067,15 @@ int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double
     const int g = nblk(c->nlocal);
     MdpStyleCheck sc;
     mdp_sflag_arm(c, sc);
-#define MDP_ADV1(FV, CV, SV)                                                                                          \
-  nve_advance_kernel<FV, CV, SV><<<g, 256, 0, c->stream>>>(c->nlocal, dtf, c->cfg.dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, \
-                                                      c->xhold.p, trigsq, hardsq, flag, sc, zero_f ? 1 : 0, dset, dclr, \
-                                                      vscale)
+#define MDP_ADV1(FV, CV, SV, LV)                                                                                      \
+  nve_advance_kernel<FV, CV, SV, LV><<<g, 256, 0, c->stream>>>(c->nlocal, dtf, c->cfg.dt, c->rmass.p, c->f.p, c->v.p,   \
+                                                               c->xq.p, c->xhold.p, trigsq, hardsq, flag, sc,           \
+                                                               zero_f ? 1 : 0, dset, dclr, vscale, L)
 #define MDP_ADV(FV, CV)                                                                                               \
   do {                                                                                                                \
-    if (vscale) MDP_ADV1(FV, CV, true);                                                                               \
-    else MDP_ADV1(FV, CV, false);                                                                                     \
+    if (vscale) MDP_ADV1(FV, CV, true, false);                                                                        \
+    else if (lgv) MDP_ADV1(FV, CV, false, true);                                                                      \
+    else MDP_ADV1(FV, CV, false, false);                                                                              \
   } while (0)
     if (with_final) {
       if (flag) MDP_ADV(true, true);
@@ -1017,6 +1087,7 @@ int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double
 #undef MDP_ADV
 #undef MDP_ADV1
     c->acc_prezeroed = sc.acc != nullptr;
+    if (lgv) MDP_TRY(mdp_lgv_close(c, c->nlocal, c->cfg.dt, L));
     // the flag words are complete behind this kernel unless remote ghosts arrive later in the step (mdp_md_unpack_x)
     if (!(c->remote_start < c->nall)) MDP_TRY(mdp_sflag_commit(c));
   }
@@ -1062,6 +1133,7 @@ int mdp_md_final_integrate(mdp_ctx *c)
   c->final_pending = false;
   const double dtf = 0.5 * c->cfg.dt * c->cfg.ftm2v;
   if (c->nhc.on) return mdp_nhc_final(c, c->nlocal, dtf, c->cfg.dt);
+  if (c->lgv.on) return lgv_final(c, dtf, c->cfg.dt, c->cfg.ftm2v);
   if (c->nlocal) nve_final_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, dtf, c->rmass.p, c->f.p, c->v.p);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
@@ -1165,6 +1237,7 @@ int mdp_hnve_setup(mdp_ctx *c, double dt, double ftm2v, const double *mass_type,
   if (c->md) return mdp_fail(c, MDP_ESTATE, "mdp_hnve_setup: a resident-mode context integrates through mdp_md_*");
   c->hn_dt = dt;
   c->hn_dtf = 0.5 * dt * ftm2v;
+  c->hn_ftm2v = ftm2v;
   for (int t = 0; t < 16; t++) c->hn_mass[t] = t >= 1 && t <= ntypes ? mass_type[t] : 1.0;
   MDP_HIP(c, hipSetDevice(c->device));
   MDP_HIP(c, c->hn_mass_dev.reserve(16));
@@ -1248,7 +1321,14 @@ int mdp_hnve_initial(mdp_ctx *c, int *moved, int *dangerous)
     const double *vscale = nullptr;
     bool with_final = false;
     if (c->nhc.on) MDP_TRY(mdp_nhc_open(c, n, c->hn_dtf, c->hn_dt, &with_final, &vscale));
-    if (vscale)
+    bool lgv = false;
+    MdpLgvArgs L;
+    if (c->lgv.on) MDP_TRY(mdp_lgv_open(c, n, c->hn_dt, c->hn_ftm2v, false, true, &lgv, &L));
+    if (lgv) // the setup force of a run (the later steps' forces were completed by mdp_hnve_final)
+      nve_advance_kernel<false, true, false, true><<<nblk(n), 256, 0, c->stream>>>(
+          n, c->hn_dtf, c->hn_dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p, trig * trig, hard * hard, h, sc, 0,
+          nullptr, nullptr, nullptr, L);
+    else if (vscale)
       nve_advance_kernel<false, true, true><<<nblk(n), 256, 0, c->stream>>>(n, c->hn_dtf, c->hn_dt, c->rmass.p, c->f.p, c->v.p,
                                                                             c->xq.p, c->xhold.p, trig * trig, hard * hard, h,
                                                                             sc, 0, nullptr, nullptr, vscale);
@@ -1256,6 +1336,7 @@ int mdp_hnve_initial(mdp_ctx *c, int *moved, int *dangerous)
       nve_advance_kernel<false, true><<<nblk(n), 256, 0, c->stream>>>(n, c->hn_dtf, c->hn_dt, c->rmass.p, c->f.p, c->v.p, c->xq.p,
                                                                       c->xhold.p, trig * trig, hard * hard, h, sc, 0);
     MDP_HIP(c, hipGetLastError());
+    if (lgv) MDP_TRY(mdp_lgv_close(c, n, c->hn_dt, L));
     if (c->hn_deferred_check && c->sflag_armed) { // one event behind the kernel serves both readers of its words
       MDP_TRY(mdp_sflag_commit(c));
       D.ev_moved_ref = c->ev_sflag[c->sflag_set];
@@ -1279,6 +1360,7 @@ int mdp_hnve_final(mdp_ctx *c)
   if (!c->hn_on || !c->hn_v_current) return mdp_fail(c, MDP_ESTATE, "mdp_hnve_upload_v not called for the current atoms");
   MDP_HIP(c, hipSetDevice(c->device));
   if (c->nhc.on) return mdp_nhc_final(c, c->nlocal, c->hn_dtf, c->hn_dt);
+  if (c->lgv.on) return lgv_final(c, c->hn_dtf, c->hn_dt, c->hn_ftm2v);
   if (c->nlocal)
     nve_final_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, c->hn_dtf, c->rmass.p, c->f.p, c->v.p);
   MDP_HIP(c, hipGetLastError());

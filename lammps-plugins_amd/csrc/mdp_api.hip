@@ -913,6 +913,8 @@ int mdp_destroy(mdp_ctx *c)
     }
   c->nhc.st.release();
   c->nhc.part.release();
+  c->lgv.st.release();
+  c->lgv.part.release();
   if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
   delete c;
   return MDP_OK;

@@ -277,6 +277,85 @@ struct MdpNhc {
   DevBuf<double> part;      // per-block partial sums of m v^2 (fixed slots: the reduction is bitwise reproducible)
 };
 static constexpr int kNhcQ = MDP_NHC_STATE_LEN, kNhcS = MDP_NHC_STATE_LEN + MDP_NHC_MAXCHAIN, kNhcWords = kNhcS + 1;
+// Langevin thermostat (langevin.hip): the host keeps the step counter and the ramp; the per-type factors, the mean of
+// the random parts (zero yes) and the tally live on the device
+struct MdpLangevin {
+  bool on = false;
+  bool need_setup = false;  // the next initial half applies the setup force of the run first (Fix::setup)
+  mdp_langevin_config cfg;
+  long long first = 0, last = 0, step = 0; // step: the step of the forces the next post_force is applied to
+  double tab_dt = 0.0, tab_ftm2v = 0.0;    // what the factors in st were computed for
+  DevBuf<double> st;        // [0..16) gfactor1, [16..32) gfactor2, [32..35) mean, [35] energy, [36] E of the last step
+  DevBuf<double> part;      // per-block partial sums (zero: 3 per block; tally: 1 per block)
+};
+static constexpr int kLgvG2 = 16, kLgvMean = 32, kLgvE = 35, kLgvElast = 36, kLgvWords = 37;
+// what the integrate kernels need to add the Langevin force of one step (md.hip nve_advance_kernel / nve_final_kernel)
+struct MdpLgvArgs {
+  const int *tag = nullptr, *type = nullptr, *perm = nullptr; // owned atom i: tag[perm ? perm[i] : i], same for type
+  const double *st = nullptr;   // MdpLangevin::st
+  const double *mean = nullptr; // zero yes: the mean of the random parts, [3]
+  double *part = nullptr;       // tally yes: per-block partial sums of f_L . v
+  double tsqrt = 0.0;           // sqrt(T(n))
+  unsigned seed = 0, lo = 0, hi = 0, phase = 0; // the Philox key and counter words of the step
+};
+
+// Philox4x32-10 (Salmon et al., SC11; the Random123 constants), in place on the counter c
+__device__ __forceinline__ void mdp_philox4x32_10(unsigned c[4], unsigned k0, unsigned k1)
+{
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    if (r) {
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    const unsigned hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+  }
+}
+
+// owned atom i: the random part gamma2 (u - 0.5) of its Langevin force (FixLangevin::post_force, fran)
+__device__ __forceinline__ void mdp_lgv_random(const MdpLgvArgs &L, int i, double &rx, double &ry, double &rz)
+{
+  const int a = L.perm ? L.perm[i] : i;
+  const int t = L.type[a] & 15;
+  unsigned c[4] = {(unsigned) L.tag[a], L.lo, L.hi, L.phase};
+  mdp_philox4x32_10(c, L.seed, 0u);
+  const double g2 = L.st[kLgvG2 + t] * L.tsqrt;
+  rx = g2 * (((double) c[0] + 0.5) * 0x1p-32 - 0.5);
+  ry = g2 * (((double) c[1] + 0.5) * 0x1p-32 - 0.5);
+  rz = g2 * (((double) c[2] + 0.5) * 0x1p-32 - 0.5);
+}
+
+// owned atom i with velocity v: its Langevin force f_L = gamma1 v + fran (- the mean of fran with zero yes)
+__device__ __forceinline__ void mdp_lgv_force(const MdpLgvArgs &L, int i, double vx, double vy, double vz, double &lx,
+                                              double &ly, double &lz)
+{
+  double rx, ry, rz;
+  mdp_lgv_random(L, i, rx, ry, rz);
+  const double g1 = L.st[L.type[L.perm ? L.perm[i] : i] & 15];
+  lx = g1 * vx + rx;
+  ly = g1 * vy + ry;
+  lz = g1 * vz + rz;
+  if (L.mean) {
+    lx -= L.mean[0];
+    ly -= L.mean[1];
+    lz -= L.mean[2];
+  }
+}
+
+// the per-block sum of e over a 256-lane workgroup into part[blockIdx.x] (fixed order; every lane must call it)
+__device__ __forceinline__ void mdp_block_sum_256(double e, double *part)
+{
+  __shared__ double wsum[4];
+  for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = e;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
 
 struct mdp_ctx {
   int device = 0;
@@ -392,7 +471,7 @@ struct mdp_ctx {
   DevBuf<int> is_center;          // [nall]
   // fix nve on the device for a host-mode context (mdp_hnve_*, the plugins' `fix nve/mdp`)
   bool hn_on = false;
-  double hn_dt = 0.0, hn_dtf = 0.0;
+  double hn_dt = 0.0, hn_dtf = 0.0, hn_ftm2v = 0.0;
   double hn_mass[16] = {};
   DevBuf<double> hn_mass_dev;
   bool hn_v_current = false;      // c->v / c->rmass match the atoms of the last mdp_set_atoms_host
@@ -442,6 +521,7 @@ struct mdp_ctx {
   MdpStyleCheckMeta sflag_meta[2];
   hipEvent_t ev_sflag[2] = {nullptr, nullptr};
   MdpNhc nhc;                      // thermostat of the integrate calls (mdp_nhc_setup)
+  MdpLangevin lgv;                 // Langevin thermostat of the integrate calls (mdp_langevin_setup)
   bool final_pending = false;      // the host deferred the final half-kick of the finished step (mdp_md_defer_final)
   bool final_deferred_seen = false; // the host uses mdp_md_defer_final at all (older hosts: with_final is authoritative)
   bool acc_prezeroed = false; // the integrate kernel reset the accumulators: the next mdp_acc_begin launches nothing
@@ -577,6 +657,12 @@ int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double
 // _final: a final half on its own (kick, chain update, velocity scaling).
 int mdp_nhc_open(mdp_ctx *c, int n, double dtf, double dt, bool *with_final, const double **vscale);
 int mdp_nhc_final(mdp_ctx *c, int n, double dtf, double dt);
+// Langevin thermostat (langevin.hip), around the integrate kernels when c->lgv.on.  _open: before a kernel that
+// first consumes a compute's forces (the fused final + initial, the setup step's initial half, a final half on its own):
+// *apply = whether this kernel adds the force; if so *L is filled (and the zero pre-pass queued).  Advances the step
+// counter when `initial`.  _close: behind that kernel (the tally of the step).
+int mdp_lgv_open(mdp_ctx *c, int n, double dt, double ftm2v, bool with_final, bool initial, bool *apply, MdpLgvArgs *L);
+int mdp_lgv_close(mdp_ctx *c, int n, double dt, const MdpLgvArgs &L);
 void mdp_host_add(double *dst, const double *src, size_t n); // dst += src, threaded for large arrays
 int mdp_host_download_add(mdp_ctx *c, double *h_dst, double *h_stage, const double *d_src, size_t n); // chunked D2H + add
 int mdp_to_host_order(mdp_ctx *c, int n, int w, const double *d_src, double *d_dst);   // per-atom arrays, device -> host order

@@ -53,6 +53,13 @@ class NhcConfig(C.Structure):
 
 
 NHC_STATE_LEN, NHC_MAXCHAIN = 28, 8
+
+
+class LangevinConfig(C.Structure):
+    """mirror of mdp_langevin_config"""
+    _fields_ = [("t_start", C.c_double), ("t_stop", C.c_double), ("t_period", C.c_double), ("seed", C.c_int),
+                ("zero", C.c_int), ("tally", C.c_int), ("boltz", C.c_double), ("mvv2e", C.c_double),
+                ("ratio", C.c_double * 16), ("natoms", C.c_longlong)]
 BOLTZ_METAL = 8.617343e-5    # force->boltz, metal units
 
 
@@ -79,6 +86,7 @@ EXPORTS = [
     "mdp_dd_comm_allreduce", "mdp_dd_comm_step_begin", "mdp_dd_comm_step_end", "mdp_dd_comm_step_info", "mdp_aeam_device_lists", "mdp_rebomos_host_list", "mdp_aeam_check_host_list",
     "mdp_md_defer_final", "mdp_md_list_state", "mdp_md_aeam_force_begin", "mdp_md_aeam_state", "mdp_dd_comm_aeam_exchange_begin", "mdp_dd_comm_aeam_exchange_end",
     "mdp_nhc_setup", "mdp_nhc_run", "mdp_nhc_state", "mdp_nhc_set_state", "mdp_nhc_off",
+    "mdp_langevin_setup", "mdp_langevin_run", "mdp_langevin_tally", "mdp_langevin_off",
 ]
 
 
@@ -500,6 +508,31 @@ class Context:
 
     def nhc_off(self):
         self._ck(self.L.mdp_nhc_off(self.h))
+
+    # ---------------- Langevin thermostat of the integrate calls (fix langevin/mdp)
+    def langevin_setup(self, t_start, t_stop, t_period, seed, natoms, ratio=None, zero=False, tally=False,
+                       boltz=BOLTZ_METAL, mvv2e=1.0364269e-4):
+        """ratio: {type: ratio} of `scale` (1 for the other types)"""
+        cfg = LangevinConfig()
+        cfg.t_start, cfg.t_stop, cfg.t_period, cfg.seed = t_start, t_stop, t_period, seed
+        cfg.zero, cfg.tally, cfg.boltz, cfg.mvv2e, cfg.natoms = int(zero), int(tally), boltz, mvv2e, natoms
+        for t in range(16):
+            cfg.ratio[t] = 1.0
+        for t, r in (ratio or {}).items():
+            cfg.ratio[t] = r
+        self._ck(self.L.mdp_langevin_setup(self.h, C.byref(cfg)))
+
+    def langevin_run(self, first, last):
+        self._ck(self.L.mdp_langevin_run(self.h, C.c_longlong(first), C.c_longlong(last)))
+
+    def langevin_tally(self):
+        """the thermostat energy (FixLangevin::compute_scalar; 0 without tally)"""
+        out = C.c_double(0.0)
+        self._ck(self.L.mdp_langevin_tally(self.h, C.byref(out)))
+        return out.value
+
+    def langevin_off(self):
+        self._ck(self.L.mdp_langevin_off(self.h))
 
     def md_class_stats(self):
         """how the last compute's work was spread over the kernel classes (see mdpair_hip.h)"""

@@ -406,6 +406,25 @@ class DeviceDomain:
         self.flush()
         return self.ctx.nhc_state()
 
+    def langevin(self, t_start, t_stop, damp, seed, ratio=None, zero=False, tally=False, first=0, last=0):
+        """Langevin thermostat (LAMMPS fix langevin on group all, noise keyed by tag and step) in the integrate calls of
+        this domain.  zero / tally need one GPU.  first / last: the ramp of the run that follows (langevin_run)."""
+        if self.world > 1 and (zero or tally):
+            raise ValueError("Langevin zero and tally run on one GPU only (they sum over all atoms every step)")
+        self.ctx.langevin_setup(t_start, t_stop, damp, seed, self.natoms_total, ratio=ratio, zero=zero, tally=tally,
+                                boltz=S.BOLTZ, mvv2e=S.MVV2E)
+        self.ctx.langevin_run(first, last)
+
+    def langevin_off(self):
+        """back to NVE; a deferred final half completes inside mdp_langevin_off, with its Langevin force"""
+        self.ctx.langevin_off()
+        self._final_pending = False
+
+    def langevin_tally(self):
+        """the thermostat energy of the last full step (completes a deferred final half first)"""
+        self.flush()
+        return self.ctx.langevin_tally()
+
     def tune_overlap(self, max_steps=80):
         """library transport: force-only steps until the library's overlap-policy trial has chosen (comm_rccl.hip); returns
         the step info.  Collective: every rank runs the same steps."""

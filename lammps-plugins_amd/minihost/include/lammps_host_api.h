@@ -16,7 +16,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <regex>
 #include <string>
+#include <vector>
 
 #define FLERR __FILE__, __LINE__
 #ifndef MIN
@@ -52,6 +54,7 @@ class Pair;
 class Update;
 class Output;
 class Fix;
+class Modify;
 
 namespace NeighConst {
   enum { REQ_DEFAULT = 0, REQ_FULL = 1 << 0, REQ_GHOST = 1 << 1 };
@@ -192,6 +195,7 @@ class LAMMPS {
   Neighbor *neighbor = nullptr;
   Update *update = nullptr;
   Output *output = nullptr;
+  Modify *modify = nullptr;
   MPI_Comm world = 0;
 };
 
@@ -199,7 +203,7 @@ class Pointers {
  public:
   explicit Pointers(LAMMPS *ptr) :
       lmp(ptr), memory(ptr->memory), error(ptr->error), atom(ptr->atom), comm(ptr->comm), domain(ptr->domain), force(ptr->force),
-      neighbor(ptr->neighbor), update(ptr->update), output(ptr->output), world(ptr->world)
+      neighbor(ptr->neighbor), update(ptr->update), output(ptr->output), modify(ptr->modify), world(ptr->world)
   {
   }
   virtual ~Pointers() = default;
@@ -215,6 +219,7 @@ class Pointers {
   Neighbor *&neighbor;
   Update *&update;
   Output *&output;
+  Modify *&modify;
   MPI_Comm &world;
 };
 
@@ -303,6 +308,23 @@ class Fix : protected Pointers {
   virtual void post_run() {}    // Modify::post_run(): behind the last step of every run
   virtual void reset_dt() {}
   virtual double compute_scalar() { return 0.0; } // thermo f_ID
+  virtual void *extract(const char *, int &) { return nullptr; } // what a fix hands another one (Fix::extract)
+};
+
+// the part of LAMMPS' Modify a fix style reads: the fixes in the order of their definition
+class Modify {
+ public:
+  int nfix = 0;
+  Fix **fix = nullptr;
+  // Modify::get_fix_by_style: the fixes whose style matches the pattern (utils::strmatch: a regular expression search)
+  const std::vector<Fix *> get_fix_by_style(const std::string &style) const
+  {
+    std::vector<Fix *> out;
+    const std::regex re(style);
+    for (int i = 0; i < nfix; i++)
+      if (std::regex_search(fix[i]->style, re)) out.push_back(fix[i]);
+    return out;
+  }
 };
 
 } // namespace LAMMPS_NS

@@ -250,6 +250,26 @@ struct Host {
   Output output;
   Pair *pair = nullptr;
   Fix *fix = nullptr; // a time-integration fix style from a plugin (fix nve/mdp); built-in nve / nvt: fix_style
+  std::vector<Fix *> fixes; // every fix style from a plugin, in the order of definition (Modify::fix), fix among them
+  Modify modify;
+  void sync_modify()
+  {
+    modify.nfix = (int) fixes.size();
+    modify.fix = fixes.data();
+  }
+  Fix *fix_by_id(const std::string &id)
+  {
+    for (Fix *f : fixes)
+      if (id == f->id) return f;
+    return nullptr;
+  }
+  void remove_fix(Fix *f) // (delete it and take it out of the list)
+  {
+    fixes.erase(std::find(fixes.begin(), fixes.end(), f));
+    if (f == fix) fix = nullptr;
+    delete f;
+    sync_modify();
+  }
 
   // registry of plugin styles
   std::map<std::string, lammpsplugin_factory1 *> pair_styles;
@@ -469,6 +489,7 @@ struct Host {
     lmp.neighbor = &neighbor;
     lmp.update = &update;
     lmp.output = &output;
+    lmp.modify = &modify;
     comm.h = this;
     avec.h = this;
     atom.avec = &avec;
@@ -901,7 +922,13 @@ struct Host {
   }
 
   // Modify::energy_couple(): what the fixes with ecouple_flag exchanged with their reservoirs
-  double ecouple() { return fix && fix->ecouple_flag ? fix->compute_scalar() : 0.0; }
+  double ecouple()
+  {
+    double e = 0.0;
+    for (Fix *f : fixes)
+      if (f->ecouple_flag) e += f->compute_scalar();
+    return e;
+  }
 
   void print_thermo()
   {
@@ -925,8 +952,9 @@ struct Host {
         else if (c == "ecouple") v = ecouple();
         else if (c == "econserve") v = pe + ke + ecouple();
         else if (c.compare(0, 2, "f_") == 0) {
-          if (!fix || c.substr(2) != fix->id) error.all(FLERR, "Could not find thermo custom fix ID: " + c.substr(2));
-          v = fix->compute_scalar();
+          Fix *f = fix_by_id(c.substr(2));
+          if (!f) error.all(FLERR, "Could not find thermo custom fix ID: " + c.substr(2));
+          v = f->compute_scalar();
         }
         else if (c == "vol") v = volume();
         else if (c == "cellgamma") {
@@ -985,7 +1013,7 @@ struct Host {
     build_ghosts();
     build_neighbor_lists();
     if (!multi()) set_vviews();
-    if (fix) fix->init(); // (LAMMPS::init: force->init() before modify->init())
+    for (Fix *f : fixes) f->init(); // (LAMMPS::init: force->init() before modify->init())
     // Neighbor::init(), behind Modify::init() in LAMMPS::init(): its check of the settings a fix may have touched
     if (neighbor.delay > 0 && neighbor.delay % neighbor.every != 0)
       error.all(FLERR, "Neighbor delay must be 0 or multiple of every setting");
@@ -997,7 +1025,7 @@ struct Host {
     const int every = thermo_every;
     output.next = output.next_thermo = step; // (setup: thermo of the initial state)
     compute_forces(1, 2);
-    if (fix) fix->setup(2);
+    for (Fix *f : fixes) f->setup(2);
     print_thermo_header();
     print_thermo();
     const double dtf = 0.5 * dt * FTM2V;
@@ -1080,7 +1108,7 @@ struct Host {
       if (out || last) print_thermo();
     }
     const double loop = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (fix) fix->post_run(); // (Modify::post_run, behind Verlet::run in Run::command)
+    for (Fix *f : fixes) f->post_run(); // (Modify::post_run, behind Verlet::run in Run::command)
     const long nat = multi() ? natoms_all : (long) atom.nlocal;
     printf("Loop time of %g on %d procs for %ld steps with %ld atoms\n\n", loop, np, nsteps, nat);
     if (nsteps > 0 && loop > 0) {
@@ -1635,6 +1663,12 @@ struct Script {
       const double t = H.temperature();
       if (t > 0)
         for (int i = 0; i < 3 * n; i++) H.vs[i] *= sqrt(T / t);
+    } else if (c == "unfix") { // unfix ID: the fix is deleted (Modify::delete_fix)
+      need(2);
+      Fix *f = H.fix_by_id(w[1]);
+      if (!f) H.error.all(FLERR, "Could not find fix ID " + w[1] + " to delete");
+      if (f == H.fix) H.fix_style = "";
+      H.remove_fix(f);
     } else if (c == "fix") {
       need(4);
       if (w[3] == "nve")
@@ -1647,13 +1681,20 @@ struct Script {
         H.nvt_damp = std::stod(w[7]);
         H.nvt_eta_dot = 0.0;
       } else if (H.fix_styles.count(w[3])) { // a fix style from a plugin: fix ID group style args
-        delete H.fix;
         std::vector<char *> args;
         for (size_t k = 1; k < w.size(); k++) args.push_back(const_cast<char *>(w[k].c_str()));
-        H.fix = static_cast<Fix *>(H.fix_styles[w[3]](&H.lmp, (int) args.size(), args.data()));
-        if (!(H.fix->setmask() & (FixConst::INITIAL_INTEGRATE | FixConst::FINAL_INTEGRATE)) || !H.fix->time_integrate)
-          H.error.all(FLERR, "minilmp hosts time-integration fix styles only");
-        H.fix_style = "plugin";
+        Fix *f = static_cast<Fix *>(H.fix_styles[w[3]](&H.lmp, (int) args.size(), args.data()));
+        if (f->time_integrate) { // the one time integrator: a new one takes the place of the last
+          if (!(f->setmask() & (FixConst::INITIAL_INTEGRATE | FixConst::FINAL_INTEGRATE)))
+            H.error.all(FLERR, "minilmp hosts time-integration fix styles only");
+          if (H.fix) H.remove_fix(H.fix);
+          H.fix = f;
+          H.fix_style = "plugin";
+        } else if (f->setmask() != 0)
+          H.error.all(FLERR, "minilmp hosts time-integration fix styles and fixes without per-step hooks only");
+        if (Fix *old = H.fix_by_id(f->id)) H.remove_fix(old); // (a fix with the ID of an existing one replaces it)
+        H.fixes.push_back(f);
+        H.sync_modify();
       } else
         H.error.all(FLERR, "minilmp supports fix nve|nvt and time-integration fix styles of loaded plugins only");
     } else if (c == "timestep") {
@@ -1762,7 +1803,9 @@ int main(int argc, char **argv)
       delete H.pair;
       H.pair = nullptr;
       H.force.pair = nullptr;
-      delete H.fix;
+      for (Fix *f : H.fixes) delete f;
+      H.fixes.clear();
+      H.sync_modify();
       H.fix = nullptr;
     } catch (const HostAbort &e) {
       if (e.what()[0]) fprintf(stderr, "%s\n", e.what());

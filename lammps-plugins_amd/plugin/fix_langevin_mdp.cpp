@@ -1,0 +1,133 @@
+/* ------------------------------------------------------------------------------------------------
+   fix langevin/mdp -- see fix_langevin_mdp.h.  What runs where:
+     constructor        the arguments (refused here: group, variables, gjf / angmom / omega, bad numbers)
+     init()             the one fix nve/mdp found through modify; a copy of the settings (with natoms, boltz, mvv2e)
+                        handed to it through Fix::extract("mdp_langevin") -- virtual dispatch, since fix nve/mdp is
+                        compiled into several plugin files
+     the steps          fix nve/mdp's: its setup() switches the thermostat on (mdp_langevin_setup / _run over
+                        beginstep .. endstep) in the context the steps run on, its post_run() switches it off
+     compute_scalar()   the tally, read through the context fix nve/mdp exposes (Fix::extract("mdp_run_ctx"))
+-------------------------------------------------------------------------------------------------- */
+#include "fix_langevin_mdp.h"
+
+#include "atom.h"
+#include "comm.h"
+#include "error.h"
+#include "force.h"
+#include "modify.h"
+
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+using namespace LAMMPS_NS;
+
+namespace {
+double number(LAMMPS *lmp, const char *s, const char *what)
+{
+  if (strncmp(s, "v_", 2) == 0)
+    lmp->error->all(FLERR, std::string("Fix langevin/mdp: variables are not supported (") + what + " " + s + ")");
+  char *end = nullptr;
+  const double v = strtod(s, &end);
+  if (!end || end == s || *end) lmp->error->all(FLERR, std::string("Illegal fix langevin/mdp command: bad ") + what + " value " + s);
+  return v;
+}
+
+bool yesno(LAMMPS *lmp, const std::string &key, const char *s)
+{
+  if (strcmp(s, "yes") == 0) return true;
+  if (strcmp(s, "no") == 0) return false;
+  lmp->error->all(FLERR, "Illegal fix langevin/mdp command: " + key + " takes yes or no, not " + s);
+  return false;
+}
+} // namespace
+
+FixLangevinMDP::FixLangevinMDP(LAMMPS *lmp, int narg, char **arg) : Fix(lmp, narg, arg)
+{
+  memset(&cfg, 0, sizeof cfg);
+  for (int t = 0; t < 16; t++) cfg.ratio[t] = 1.0;
+  if (narg < 7) error->all(FLERR, "Illegal fix langevin/mdp command: fix ID all langevin/mdp Tstart Tstop damp seed [keywords]");
+  if (strcmp(arg[1], "all") != 0) error->all(FLERR, "Fix langevin/mdp requires group all");
+  cfg.t_start = number(lmp, arg[3], "Tstart");
+  cfg.t_stop = number(lmp, arg[4], "Tstop");
+  cfg.t_period = number(lmp, arg[5], "damp");
+  const double seed = number(lmp, arg[6], "seed");
+  if (!(cfg.t_start >= 0.0) || !(cfg.t_stop >= 0.0)) error->all(FLERR, "Fix langevin/mdp: Tstart and Tstop must be >= 0.0");
+  if (!(cfg.t_period > 0.0)) error->all(FLERR, "Fix langevin/mdp: damp must be > 0.0");
+  if (!(seed >= 1.0) || seed > 2147483647.0 || seed != (double) (int) seed)
+    error->all(FLERR, "Fix langevin/mdp: the seed must be an integer > 0");
+  cfg.seed = (int) seed;
+  for (int k = 7; k < narg;) {
+    const std::string key = arg[k];
+    if (key == "gjf" || key == "angmom" || key == "omega")
+      error->all(FLERR, "Fix langevin/mdp: keyword " + key + " is not supported");
+    if (key == "scale") {
+      if (k + 2 >= narg) error->all(FLERR, "Illegal fix langevin/mdp command: scale needs a type and a ratio");
+      const double t = number(lmp, arg[k + 1], "scale type");
+      if (t < 1.0 || t > 15.0 || t != (double) (int) t || (atom && (int) t > atom->ntypes))
+        error->all(FLERR, std::string("Fix langevin/mdp: scale type ") + arg[k + 1] + " out of range");
+      const double r = number(lmp, arg[k + 2], "scale ratio");
+      if (!(r > 0.0)) error->all(FLERR, "Fix langevin/mdp: the scale ratio must be > 0.0");
+      cfg.ratio[(int) t] = r;
+      k += 3;
+      continue;
+    }
+    if (k + 1 >= narg) error->all(FLERR, "Illegal fix langevin/mdp command: " + key + " needs a value");
+    if (key == "tally") cfg.tally = yesno(lmp, key, arg[k + 1]);
+    else if (key == "zero") cfg.zero = yesno(lmp, key, arg[k + 1]);
+    else error->all(FLERR, "Illegal fix langevin/mdp command: unknown keyword " + key);
+    k += 2;
+  }
+  ecouple_flag = cfg.tally ? 1 : 0;
+}
+
+int FixLangevinMDP::setmask() { return 0; } // (the force is applied inside fix nve/mdp's device steps)
+
+Fix *FixLangevinMDP::integrator() const
+{
+  for (int i = 0; i < modify->nfix; i++)
+    if (strcmp(modify->fix[i]->style, "nve/mdp") == 0) return modify->fix[i];
+  return nullptr;
+}
+
+void FixLangevinMDP::init()
+{
+  if ((cfg.zero || cfg.tally) && comm->nprocs > 1)
+    error->all(FLERR, "Fix langevin/mdp: zero yes and tally yes run on one MPI rank only");
+  Fix *nve = nullptr;
+  for (int i = 0; i < modify->nfix; i++) {
+    Fix *f = modify->fix[i];
+    if (f == this) continue;
+    if (strcmp(f->style, "nvt/mdp") == 0)
+      error->all(FLERR, std::string("Fix langevin/mdp: fix ") + f->id + " (nvt/mdp) is a thermostat too; use one thermostat");
+    if (strcmp(f->style, "langevin/mdp") == 0)
+      error->all(FLERR, std::string("Fix langevin/mdp: fix ") + f->id + " is a second langevin/mdp; use one thermostat");
+    if (strcmp(f->style, "nve/mdp") == 0) nve = f;
+    else if (f->time_integrate)
+      error->all(FLERR, std::string("Fix langevin/mdp: fix ") + f->id + " (" + f->style +
+                            ") integrates on the host; the device thermostat needs fix nve/mdp as the time integrator");
+  }
+  if (!nve) error->all(FLERR, "Fix langevin/mdp requires fix nve/mdp as the time integrator");
+  int dim = 0;
+  mdp_langevin_config *slot = static_cast<mdp_langevin_config *>(nve->extract("mdp_langevin", dim));
+  int *on = static_cast<int *>(nve->extract("mdp_langevin_on", dim));
+  if (!slot || !on) error->all(FLERR, "Fix langevin/mdp: this fix nve/mdp does not take a thermostat");
+  cfg.boltz = force->boltz;
+  cfg.mvv2e = force->mvv2e;
+  cfg.natoms = (long long) atom->natoms;
+  *slot = cfg;
+  *on = 1;
+}
+
+// FixLangevin::compute_scalar with tally yes: the energy the thermostat took out, back to the last full step
+double FixLangevinMDP::compute_scalar()
+{
+  if (!cfg.tally) return 0.0;
+  Fix *nve = integrator();
+  int dim = 0;
+  mdp_ctx **c = nve ? static_cast<mdp_ctx **>(nve->extract("mdp_run_ctx", dim)) : nullptr;
+  if (!c || !*c) return 0.0;
+  double e = 0.0;
+  if (mdp_langevin_tally(*c, &e) != MDP_OK) error->one(FLERR, std::string("Fix langevin/mdp: ") + mdp_last_error(*c));
+  return e;
+}

@@ -1,0 +1,43 @@
+/* -*- c++ -*- -----------------------------------------------------------------------------------
+   `fix langevin/mdp`: LAMMPS `fix langevin` on the device, for runs that integrate with `fix nve/mdp` (any of its modes:
+   host-linked, `bricks yes`, several ranks).  Not a time integrator: at init() it hands a copy of its settings to the
+   one fix nve/mdp (Fix::extract "mdp_langevin"), which switches the library's thermostat (mdp_langevin_*,
+   csrc/langevin.hip) on in the context its steps run on for the length of each run.
+
+   fix ID all langevin/mdp Tstart Tstop damp seed [scale type ratio ...] [tally yes|no] [zero yes|no]
+
+   Group all; no variables, gjf, angmom or omega; zero and tally on one MPI rank.  The noise is keyed by atom tag and
+   step, not LAMMPS' per-rank stream.  compute_scalar() is the thermostat energy with tally yes
+   (ecouple_flag = 1), 0 otherwise.
+-------------------------------------------------------------------------------------------------- */
+#ifdef FIX_CLASS
+// clang-format off
+FixStyle(langevin/mdp,FixLangevinMDP);
+// clang-format on
+#else
+
+#ifndef MDP_FIX_LANGEVIN_MDP_H
+#define MDP_FIX_LANGEVIN_MDP_H
+
+#include "fix.h"
+
+#include "mdpair_hip.h"
+
+namespace LAMMPS_NS {
+
+class FixLangevinMDP : public Fix {
+ public:
+  FixLangevinMDP(class LAMMPS *, int, char **);
+  int setmask() override;
+  void init() override;
+  double compute_scalar() override;
+
+ private:
+  mdp_langevin_config cfg;
+  class Fix *integrator() const; // the fix nve/mdp of this run (looked up anew: no pointer outlives either fix)
+};
+
+}    // namespace LAMMPS_NS
+
+#endif
+#endif

@@ -74,6 +74,7 @@ FixNVEMDP::FixNVEMDP(LAMMPS *lmp, int narg, char **arg)
     : Fix(lmp, narg, arg), ctxp(nullptr), pair_linked(nullptr), downloads(0), hostcheck(0), took_delay(0), saved_delay(0),
       linked_to(nullptr), bricks(0), bricks_kw(0), bctx(nullptr), bricks_slot(nullptr), bricks_ev(nullptr), style_id(0), comm_up(0), pending_final(0), step_ev(0)
 {
+  memset(&lgv_cfg, 0, sizeof lgv_cfg);
   if (narg < 3 || (narg - 3) % 2) error->all(FLERR, "Illegal fix nve/mdp command");
   for (int k = 3; k + 1 < narg; k += 2) {
     const std::string key = arg[k], val = arg[k + 1];
@@ -181,8 +182,30 @@ void FixNVEMDP::init_bricks()
   next_reneighbor = -1;
 }
 
-// Modify::setup, behind the host's own setup (exchange, borders, lists, forces of step 0 in host mode)
+// Modify::setup, behind the host's own setup (exchange, borders, lists, forces of step 0 in host mode); then the
+// Langevin thermostat, if a fix langevin/mdp handed one over, on the context the steps of this run go through
 void FixNVEMDP::setup(int /*vflag*/)
+{
+  setup_steps();
+  if (!lgv_on) return;
+  mdp_ctx *c = bricks ? bctx : ctx();
+  if (!c) fail(nullptr);
+  if (mdp_langevin_setup(c, &lgv_cfg) != MDP_OK) fail(c);
+  if (mdp_langevin_run(c, (long long) update->beginstep, (long long) update->endstep) != MDP_OK) fail(c);
+  lgv_ctx = c;
+}
+
+// fix langevin/mdp hands its thermostat over here (a copy of its config; no pointer to either fix is kept)
+void *FixNVEMDP::extract(const char *name, int &dim)
+{
+  dim = 0;
+  if (strcmp(name, "mdp_langevin") == 0) return &lgv_cfg;
+  if (strcmp(name, "mdp_langevin_on") == 0) return &lgv_on;
+  if (strcmp(name, "mdp_run_ctx") == 0) return &lgv_ctx;
+  return nullptr;
+}
+
+void FixNVEMDP::setup_steps()
 {
   if (!bricks) return;
   int dim = 0;
@@ -324,6 +347,9 @@ void FixNVEMDP::initial_integrate(int vflag)
 // MDP_FIX_STATS=1: one line per run on how often the host's x / v were brought up to date (bench.py reads it)
 void FixNVEMDP::post_run()
 {
+  if (lgv_ctx && mdp_langevin_off(lgv_ctx) != MDP_OK) fail(lgv_ctx); // (an unfix of the thermostat gives NVE next run)
+  lgv_ctx = nullptr;
+  lgv_on = 0;
   if (bricks) {
     long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (comm->nprocs > 1) (void) mdp_dd_comm_step_info(bctx, info);

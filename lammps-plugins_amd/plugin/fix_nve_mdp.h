@@ -40,6 +40,7 @@ class FixNVEMDP : public Fix {
   void final_integrate() override;
   void post_run() override;
   void reset_dt() override;
+  void *extract(const char *, int &) override;
 
  protected:
   mdp_ctx **ctxp;      // the pair style's device context (created in its init_style)
@@ -60,7 +61,14 @@ class FixNVEMDP : public Fix {
   int *bricks_ev;      // the pair style's copy of "this step was opened with energy / virial"
   int style_id, comm_up, pending_final, step_ev;
 
+  // the Langevin thermostat a `fix langevin/mdp` handed over (extract "mdp_langevin" / "mdp_langevin_on"): switched on in
+  // setup() on the context the steps run on (lgv_ctx, extract "mdp_run_ctx"), off in post_run()
+  mdp_langevin_config lgv_cfg;
+  int lgv_on = 0;
+  mdp_ctx *lgv_ctx = nullptr;
+
   mdp_ctx *ctx() const { return ctxp ? *ctxp : nullptr; }
+  void setup_steps();
   void to_host(bool forces);
   void init_bricks();
   void bricks_to_host();
