@@ -2038,7 +2038,7 @@ static int aeam_fetch(mdp_ctx *c, double *eng, double *virial)
 {
   hipStream_t st = c->stream;
   MDP_HIP(c, hipMemcpyAsync(c->h_pinned, c->acc.p, sizeof(double) * 8, hipMemcpyDeviceToHost, st));
-  int *hflags = (int *) (c->h_pinned + 16);
+  int *hflags = mdp_pin(c, kPinFlags);
   MDP_HIP(c, hipMemcpyAsync(hflags, c->flags.p, sizeof(int) * 5, hipMemcpyDeviceToHost, st));
   MDP_HIP(c, hipStreamSynchronize(st));
   MDP_TRY(mdp_flags_check(c, hflags));

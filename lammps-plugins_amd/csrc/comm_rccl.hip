@@ -579,7 +579,7 @@ int mdp_dd_comm_step_begin(mdp_ctx *c, int with_final, int force_rebuild, int ef
   int glob = 0;
   if (D.glob_pending) {
     MDP_HIP(c, hipEventSynchronize(D.ev_glob_ref));
-    glob = *(int *) (c->h_pinned + 46);
+    glob = *mdp_pin(c, kPinGlob);
     D.glob_pending = false;
   }
   int moved = 0, dangerous = 0;

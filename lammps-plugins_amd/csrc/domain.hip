@@ -824,29 +824,14 @@ int mdp_md_moved_async(mdp_ctx *c, int *moved, int *dangerous)
 {
   if (!c) return MDP_EINVAL;
   if (!c->md) return mdp_fail(c, MDP_ESTATE, "mdp_md_setup not called");
-  MdpDomain &D = c->dd;
-  hipStream_t st = c->stream;
-  int *h = (int *) (c->h_pinned + 28);
-  if (!D.ev_moved) MDP_HIP(c, hipEventCreateWithFlags(&D.ev_moved, hipEventDisableTiming));
-  int m = 0, dg = 0;
-  if (D.moved_pending) {
-    MDP_HIP(c, hipEventSynchronize(D.ev_moved_ref ? D.ev_moved_ref : D.ev_moved));
-    m = h[0];
-    dg = h[1];
-    D.moved_pending = false;
-  }
+  int m = 0;
+  MDP_TRY(mdp_moved_take(c, &m, dangerous));
   if (moved) *moved = m;
-  if (dangerous) *dangerous = dg;
   if (m || !c->nlocal || !c->neigh_set) return MDP_OK; // the caller rebuilds now: nothing to check until then
-  h[0] = h[1] = 0;
-  const double hard = 0.5 * c->cfg.skin;
-  double trig = hard - 0.1 * mdp_margin_scale(c);
-  if (trig < 0.5 * hard) trig = 0.5 * hard;
-  MDP_TRY(mdp_moved(c, c->nlocal, 1024, trig * trig, hard * hard, c->xhold.p, h));
-  MDP_HIP(c, hipEventRecord(D.ev_moved, st));
-  D.ev_moved_ref = D.ev_moved;
-  D.moved_pending = true;
-  return MDP_OK;
+  double trigsq, hardsq;
+  int *h = mdp_moved_arm(c, c->cfg.skin, &trigsq, &hardsq);
+  MDP_TRY(mdp_moved(c, c->nlocal, 1024, trigsq, hardsq, c->xhold.p, h));
+  return mdp_moved_post(c, false);
 }
 
 // mdp_md_initial_integrate (or, with_final, mdp_md_final_initial_integrate) and mdp_md_moved_async in one call and
@@ -856,34 +841,16 @@ int mdp_md_integrate_check(mdp_ctx *c, int with_final, int *moved, int *dangerou
 {
   if (!c) return MDP_EINVAL;
   if (!c->md) return mdp_fail(c, MDP_ESTATE, "mdp_md_setup not called");
-  MdpDomain &D = c->dd;
-  int *h = (int *) (c->h_pinned + 28);
-  if (!D.ev_moved) MDP_HIP(c, hipEventCreateWithFlags(&D.ev_moved, hipEventDisableTiming));
-  int m = 0, dg = 0;
-  if (D.moved_pending) {
-    MDP_HIP(c, hipEventSynchronize(D.ev_moved_ref ? D.ev_moved_ref : D.ev_moved));
-    m = h[0];
-    dg = h[1];
-    D.moved_pending = false;
-  }
+  int m = 0;
+  MDP_TRY(mdp_moved_take(c, &m, dangerous));
   if (moved) *moved = m;
-  if (dangerous) *dangerous = dg;
   if (m || !c->nlocal || !c->neigh_set) return mdp_md_advance(c, with_final != 0, nullptr, 0.0, 0.0);
-  h[0] = h[1] = 0;
-  const double hard = 0.5 * c->cfg.skin;
-  double trig = hard - 0.1 * mdp_margin_scale(c);
-  if (trig < 0.5 * hard) trig = 0.5 * hard;
-  MDP_TRY(mdp_md_advance(c, with_final != 0, h, trig * trig, hard * hard));
+  double trigsq, hardsq;
+  int *h = mdp_moved_arm(c, c->cfg.skin, &trigsq, &hardsq);
+  MDP_TRY(mdp_md_advance(c, with_final != 0, h, trigsq, hardsq));
   // the integrate kernel wrote h; when mdp_md_advance has recorded the style-check event behind that kernel (no remote
   // ghosts), that event serves this reader too
-  if (c->sflag_armed && c->sflag_committed[c->sflag_set]) {
-    D.ev_moved_ref = c->ev_sflag[c->sflag_set];
-  } else {
-    MDP_HIP(c, hipEventRecord(D.ev_moved, c->stream));
-    D.ev_moved_ref = D.ev_moved;
-  }
-  D.moved_pending = true;
-  return MDP_OK;
+  return mdp_moved_post(c, c->sflag_armed && c->sflag_committed[c->sflag_set]);
 }
 
 // owned atoms' integer properties in device order ("tag", "type"); the device re-orders atoms at every reneighboring

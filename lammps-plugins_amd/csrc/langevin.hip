@@ -19,58 +19,19 @@ namespace {
 // zero yes: part[3 b + k] = the sum over block b of the random parts fran_k of the step (mdp_lgv_random)
 __global__ __launch_bounds__(256) void lgv_zero_kernel(const int n, const MdpLgvArgs L, double *__restrict__ part)
 {
-  __shared__ double wsum[3][4];
   const int i = blockIdx.x * 256 + threadIdx.x;
   double r[3] = {0.0, 0.0, 0.0};
   if (i < n) mdp_lgv_random(L, i, r[0], r[1], r[2]);
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    double e = r[k];
-    for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
-    if ((threadIdx.x & 63) == 0) wsum[k][threadIdx.x >> 6] = e;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int k = threadIdx.x;
-    part[3 * (size_t) blockIdx.x + k] = (wsum[k][0] + wsum[k][1]) + (wsum[k][2] + wsum[k][3]);
-  }
-}
-
-// one workgroup: the fixed-order sum of npart slots of width w (component k) into red[0]
-__device__ double lgv_sum_slots(const double *__restrict__ part, int npart, int w, int k, double *red)
-{
-  double s = 0.0;
-  for (int b = threadIdx.x; b < npart; b += 256) s += part[(size_t) w * b + k];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int) threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
+  mdp_block_sum_256<3>(r, part);
 }
 
 // zero yes: st[kLgvMean + k] = (sum of the random parts) / natoms; the three components in one pass over the slots
 __global__ __launch_bounds__(256) void lgv_mean_kernel(const double *__restrict__ part, const int npart,
                                                        const double natoms, double *__restrict__ st)
 {
-  __shared__ double red[3][256];
-  double s[3] = {0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < npart; b += 256)
-#pragma unroll
-    for (int k = 0; k < 3; k++) s[k] += part[3 * (size_t) b + k];
-#pragma unroll
-  for (int k = 0; k < 3; k++) red[k][threadIdx.x] = s[k];
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int) threadIdx.x < h)
-#pragma unroll
-      for (int k = 0; k < 3; k++) red[k][threadIdx.x] += red[k][threadIdx.x + h];
-    __syncthreads();
-  }
-  if (threadIdx.x < 3) st[kLgvMean + threadIdx.x] = red[threadIdx.x][0] / natoms;
+  double s[3];
+  mdp_slot_sum_256<3>(part, npart, s);
+  if (threadIdx.x < 3) st[kLgvMean + threadIdx.x] = (threadIdx.x == 0 ? s[0] : (threadIdx.x == 1 ? s[1] : s[2])) / natoms;
 }
 
 // tally yes: E = the fixed-order sum of the partials of f_L . v; the setup force starts the energy of the run at
@@ -78,8 +39,8 @@ __global__ __launch_bounds__(256) void lgv_mean_kernel(const double *__restrict_
 __global__ __launch_bounds__(256) void lgv_tally_kernel(const double *__restrict__ part, const int npart, const double dt,
                                                         const int setup, double *__restrict__ st)
 {
-  __shared__ double red[256];
-  const double e = lgv_sum_slots(part, npart, 1, 0, red);
+  double e;
+  mdp_slot_sum_256<1>(part, npart, &e);
   if (threadIdx.x == 0) {
     st[kLgvE] = setup ? 0.5 * e * dt : st[kLgvE] + e * dt;
     st[kLgvElast] = e;
@@ -94,12 +55,13 @@ double lgv_target(const MdpLangevin &h, long long n)
 }
 
 // the per-type factors of FixLangevin::init for this time step and unit system (rewritten when they change)
-int lgv_tables(mdp_ctx *c, double dt, double ftm2v)
+int lgv_tables(mdp_ctx *c)
 {
   MdpLangevin &h = c->lgv;
+  const MdpStep s = mdp_step(c);
+  const double dt = s.dt, ftm2v = s.ftm2v, *mass = s.mass;
   if (h.tab_dt == dt && h.tab_ftm2v == ftm2v) return MDP_OK;
   const mdp_langevin_config &g = h.cfg;
-  const double *mass = c->md ? c->h_mass : c->hn_mass;
   double tab[2 * 16] = {};
   for (int t = 1; t < 16; t++) {
     const double m = mass[t] > 0.0 ? mass[t] : 0.0;
@@ -116,13 +78,14 @@ int lgv_tables(mdp_ctx *c, double dt, double ftm2v)
 
 } // namespace
 
-int mdp_lgv_open(mdp_ctx *c, int n, double dt, double ftm2v, bool with_final, bool initial, bool *apply, MdpLgvArgs *L)
+int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvArgs *L)
 {
   MdpLangevin &h = c->lgv;
+  const int n = c->nlocal;
   const bool setup = initial && !with_final && h.need_setup;
   *apply = !initial || with_final || setup;
   if (*apply) {
-    MDP_TRY(lgv_tables(c, dt, ftm2v));
+    MDP_TRY(lgv_tables(c));
     const int nb = nblk(n);
     MDP_HIP(c, h.part.reserve((size_t) 4 * nb + 4));
     L->tag = c->tag.p;
@@ -150,10 +113,11 @@ int mdp_lgv_open(mdp_ctx *c, int n, double dt, double ftm2v, bool with_final, bo
   return MDP_OK;
 }
 
-int mdp_lgv_close(mdp_ctx *c, int n, double dt, const MdpLgvArgs &L)
+int mdp_lgv_close(mdp_ctx *c, const MdpLgvArgs &L)
 {
   if (!L.part) return MDP_OK;
-  lgv_tally_kernel<<<1, 256, 0, c->stream>>>(L.part, n ? nblk(n) : 0, dt, L.phase == 1u ? 1 : 0, c->lgv.st.p);
+  lgv_tally_kernel<<<1, 256, 0, c->stream>>>(L.part, c->nlocal ? nblk(c->nlocal) : 0, mdp_step(c).dt, L.phase == 1u ? 1 : 0,
+                                             c->lgv.st.p);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }
@@ -195,7 +159,7 @@ int mdp_langevin_run(mdp_ctx *c, long long first, long long last)
   if (!c->lgv.on) return mdp_fail(c, MDP_ESTATE, "mdp_langevin_setup not called");
   if (last < first) return mdp_fail(c, MDP_EINVAL, "mdp_langevin_run: last step %lld before first %lld", last, first);
   // a final half the host deferred belongs to the step before the new run: it runs now, with that step's force
-  if (c->md && c->final_pending) MDP_TRY(mdp_md_final_integrate(c));
+  MDP_TRY(mdp_md_flush_final(c));
   MdpLangevin &h = c->lgv;
   h.first = first;
   h.last = last;
@@ -213,11 +177,10 @@ int mdp_langevin_tally(mdp_ctx *c, double *out)
     return MDP_OK;
   }
   MDP_HIP(c, hipSetDevice(c->device));
-  if (c->md && c->final_pending) MDP_TRY(mdp_md_final_integrate(c)); // (the energy of the finished step)
+  MDP_TRY(mdp_md_flush_final(c)); // (the energy of the finished step)
   double e[2];
   MDP_TRY(mdp_read_one(c, c->lgv.st.p + kLgvE, sizeof e, e));
-  const double dt = c->md ? c->cfg.dt : c->hn_dt;
-  *out = -(e[0] - 0.5 * e[1] * dt); // FixLangevin::compute_scalar: back from mid-step to the last full step
+  *out = -(e[0] - 0.5 * e[1] * mdp_step(c).dt); // FixLangevin::compute_scalar: back from mid-step to the last full step
   return MDP_OK;
 }
 
@@ -225,7 +188,7 @@ int mdp_langevin_off(mdp_ctx *c)
 {
   if (!c) return MDP_EINVAL;
   // a deferred final half of the last thermostatted step completes with its Langevin force before NVE takes over
-  if (c->lgv.on && c->md && c->final_pending) MDP_TRY(mdp_md_final_integrate(c));
+  if (c->lgv.on) MDP_TRY(mdp_md_flush_final(c));
   c->lgv.on = false;
   return MDP_OK;
 }

@@ -10,6 +10,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include <cmath>
+#include <type_traits>
 
 void mdp_rebomos_fill_dev(mdp_ctx *c, double skin);
 
@@ -228,18 +229,19 @@ __global__ __launch_bounds__(256) void ang_select_kernel(const int nlocal, const
 // LANGEVIN: this kernel is the first reader of the compute's forces and adds the Langevin force of the step (L,
 // langevin.hip) to them in registers, from the velocities it reads; L.part: the per-block sums of f_L . v for the tally
 // (v after the final half; with FINAL = false the setup force, and v as read).  LANGEVIN = false never reads L.
-template <bool FINAL, bool CHECK, bool SCALE = false, bool LANGEVIN = false>
+template <bool FINAL, bool CHECK, bool SCALE, bool LANGEVIN>
 __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const double *__restrict__ rmass,
                                    double *__restrict__ f, double *__restrict__ v, double4 *__restrict__ xq,
                                    const mdp_hold_t *__restrict__ xhold, const double trigsq, const double hardsq,
                                    int *__restrict__ flag, const MdpStyleCheck SC, const int zero_f,
-                                   double *__restrict__ dflag_set = nullptr, double *__restrict__ dflag_clear = nullptr,
-                                   const double *__restrict__ vscale = nullptr, const MdpLgvArgs L = MdpLgvArgs())
+                                   double *__restrict__ dflag_set, double *__restrict__ dflag_clear,
+                                   const double *__restrict__ vscale, const MdpLgvArgs L)
 {
   double lgv_e = 0.0; // (LANGEVIN, tally: f_L . v of this atom)
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (CHECK && dflag_clear && i == 0) *dflag_clear = 0.0; // (the word of the next step; this step's was cleared a step ago)
-  bool t = false, h = false, sa = false, sah = false, sp = false, sph = false;
+  bool t = false, h = false;
+  MdpStyleVote w;
   if (SC.acc) { // what acc_zero_kernel does
     for (int k = i; k < SC.nacc; k += gridDim.x * 256) SC.acc[k] = 0.0;
     if (i == 0) {
@@ -272,7 +274,7 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
       vy += s * fy;
       vz += s * fz;
     }
-    if (LANGEVIN && L.part) lgv_e = lx * vx + ly * vy + lz * vz; // (end_of_step of step n: v after the final half)
+    if (LANGEVIN && L.part) lgv_e = mdp_dot3(lx, vx, ly, vy, lz, vz); // (end_of_step of step n: v after the final half; x first HERE, y first in lgv_final_kernel: the orders each kernel has always had -- keep both)
     if (SCALE) { // the thermostat's factor (nhc.hip): final half of step n (if FINAL) times initial half of step n+1
       const double S = *vscale;
       vx *= S;
@@ -290,33 +292,15 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
     x.y += dt * vy;
     x.z += dt * vz;
     xq[i] = x;
-    // The triggers are read one compute late and fire early by a fixed margin that stands for two steps of motion (0.07 /
-    // 0.1 A: 35 / 50 A/ps at 1 fs).  An atom faster than that -- the tail of a 5 000 K melt -- fires by its OWN two steps
-    // instead (this step's speed, a quarter on top for its acceleration): whatever it may reach before the answer is
-    // read is then still inside the limit.  (profiles/prune_fuzz.py found the case.)
+    // (the atom's own two steps: this step's speed, a quarter on top for its acceleration -- see mdp_reaches)
     const double two_steps = (CHECK || SC.xa || SC.xp) ? 2.5 * dt * sqrt(vx * vx + vy * vy + vz * vz) : 0.0;
-    auto reaches = [two_steps](const double d2, const double hardsq_) { // will the atom be beyond `hard` two steps on?
-      const double rem = sqrt(hardsq_) - two_steps;
-      return rem <= 0.0 || d2 > rem * rem;
-    };
     if (CHECK) {
       const double dx = x.x - xhold[3 * (size_t) i], dy = x.y - xhold[3 * (size_t) i + 1], dz = x.z - xhold[3 * (size_t) i + 2];
       const double d2 = dx * dx + dy * dy + dz * dz;
-      t = d2 > trigsq || reaches(d2, hardsq);
+      t = d2 > trigsq || mdp_reaches(d2, hardsq, two_steps);
       h = d2 > hardsq;
     }
-    if (SC.xa) {
-      const double dx = x.x - SC.xa[3 * (size_t) i], dy = x.y - SC.xa[3 * (size_t) i + 1], dz = x.z - SC.xa[3 * (size_t) i + 2];
-      const double d2 = dx * dx + dy * dy + dz * dz;
-      sa = d2 > SC.trig_a || reaches(d2, SC.hard_a);
-      sah = d2 > SC.hard_a;
-    }
-    if (SC.xp) {
-      const double dx = x.x - SC.xp[3 * (size_t) i], dy = x.y - SC.xp[3 * (size_t) i + 1], dz = x.z - SC.xp[3 * (size_t) i + 2];
-      const double d2 = dx * dx + dy * dy + dz * dz;
-      sp = d2 > SC.trig_p || reaches(d2, SC.hard_p);
-      sph = d2 > SC.hard_p;
-    }
+    mdp_style_test(SC, (size_t) i, x, two_steps, w);
   }
   if constexpr (LANGEVIN)
     if (L.part) mdp_block_sum_256(lgv_e, L.part);
@@ -327,15 +311,7 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
     }
     if (__ballot(h) && (threadIdx.x & 63) == 0) flag[1] = 1;
   }
-  if (SC.flag) { // (the wave votes with ALL its lanes, then lane 0 stores: a vote inside the lane-0 branch would count lane 0 alone)
-    const bool wa = __any(sa), wah = __any(sah), wp = __any(sp), wph = __any(sph);
-    if ((threadIdx.x & 63) == 0) {
-      if (wa) SC.flag[0] = 1;
-      if (wah) SC.flag[1] = 1;
-      if (wp) SC.flag[2] = 1;
-      if (wph) SC.flag[3] = 1;
-    }
-  }
+  mdp_style_vote(SC, w, 0);
 }
 
 // mass of every owned atom in the device's atom order (host mode: type[] is in the host's order, perm maps positions)
@@ -383,7 +359,7 @@ __global__ __launch_bounds__(256) void lgv_final_kernel(int nlocal, double dtf, 
     v[3 * (size_t) i] = vx;
     v[3 * (size_t) i + 1] = vy;
     v[3 * (size_t) i + 2] = vz;
-    e = lx * vx + ly * vy + lz * vz;
+    e = mdp_dot3(ly, vy, lx, vx, lz, vz); // (y first: the order this kernel has always had, and the tally's last bit depends on it)
   }
   if (L.part) mdp_block_sum_256(e, L.part);
 }
@@ -524,8 +500,8 @@ __global__ void pack_x_kernel(int n, const int *__restrict__ sendlist, const dou
 
 // SC: the style-level displacement checks of the arriving remote ghosts (MdpStyleCheck; flag words [4..7])
 __global__ void unpack_x_kernel(int n, int first, const double *__restrict__ buf, double4 *__restrict__ xq,
-                                const MdpStyleCheck SC, const double *__restrict__ gflag = nullptr, const int ngflag = 0,
-                                int *__restrict__ h_glob = nullptr, double *__restrict__ fzero = nullptr)
+                                const MdpStyleCheck SC, const double *__restrict__ gflag, const int ngflag,
+                                int *__restrict__ h_glob, double *__restrict__ fzero)
 {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (h_glob && k == 0) { // the ranks' "moved" words as gathered behind this halo -> one pinned word (MdpDomain::flagbuf)
@@ -533,44 +509,21 @@ __global__ void unpack_x_kernel(int n, int first, const double *__restrict__ buf
     for (int q = 0; q < ngflag; q++) m = gflag[q] > m ? gflag[q] : m;
     *h_glob = m > 0.0 ? 1 : 0;
   }
-  bool sa = false, sah = false, sp = false, sph = false;
+  MdpStyleVote w;
   if (k < n) {
     const size_t i = (size_t) first + k;
     double4 x = xq[i];
     // (what the slot held is the ghost's position of the step before: its last step is its speed -- see nve_advance_kernel)
     const double ox = buf[3 * (size_t) k] - x.x, oy = buf[3 * (size_t) k + 1] - x.y, oz = buf[3 * (size_t) k + 2] - x.z;
     const double two_steps = (SC.xa || SC.xp) ? 2.5 * sqrt(ox * ox + oy * oy + oz * oz) : 0.0;
-    auto reaches = [two_steps](const double d2, const double hardsq_) {
-      const double rem = sqrt(hardsq_) - two_steps;
-      return rem <= 0.0 || d2 > rem * rem;
-    };
     x.x = buf[3 * (size_t) k];
     x.y = buf[3 * (size_t) k + 1];
     x.z = buf[3 * (size_t) k + 2];
     xq[i] = x;
     if (fzero) fzero[3 * i] = fzero[3 * i + 1] = fzero[3 * i + 2] = 0.0; // (force_clear of a style that accumulates, see mdp_md_advance)
-    if (SC.xa) {
-      const double dx = x.x - SC.xa[3 * i], dy = x.y - SC.xa[3 * i + 1], dz = x.z - SC.xa[3 * i + 2];
-      const double d2 = dx * dx + dy * dy + dz * dz;
-      sa = d2 > SC.trig_a || reaches(d2, SC.hard_a);
-      sah = d2 > SC.hard_a;
-    }
-    if (SC.xp) {
-      const double dx = x.x - SC.xp[3 * i], dy = x.y - SC.xp[3 * i + 1], dz = x.z - SC.xp[3 * i + 2];
-      const double d2 = dx * dx + dy * dy + dz * dz;
-      sp = d2 > SC.trig_p || reaches(d2, SC.hard_p);
-      sph = d2 > SC.hard_p;
-    }
+    mdp_style_test(SC, i, x, two_steps, w);
   }
-  if (SC.flag) { // (all lanes vote, lane 0 stores -- see nve_advance_kernel)
-    const bool wa = __any(sa), wah = __any(sah), wp = __any(sp), wph = __any(sph);
-    if ((threadIdx.x & 63) == 0) {
-      if (wa) SC.flag[4] = 1;
-      if (wah) SC.flag[5] = 1;
-      if (wp) SC.flag[6] = 1;
-      if (wph) SC.flag[7] = 1;
-    }
-  }
+  mdp_style_vote(SC, w, 4);
 }
 
 __global__ void pack_scalar_kernel(int n, const int *__restrict__ sendlist, const double *__restrict__ a,
@@ -621,15 +574,72 @@ __global__ void x3_to_xq_kernel(int n, const double *__restrict__ x3, double4 *_
 
 // a final half on its own with the Langevin thermostat on (mdp_md_final_integrate, mdp_hnve_final).  writeback: the
 // initial half that follows kicks with these forces (false: the forces of a new run's setup come next instead)
-int lgv_final(mdp_ctx *c, double dtf, double dt, double ftm2v, bool writeback = true)
+int lgv_final(mdp_ctx *c, bool writeback)
 {
   bool apply = false;
   MdpLgvArgs L;
-  MDP_TRY(mdp_lgv_open(c, c->nlocal, dt, ftm2v, false, false, &apply, &L));
+  MDP_TRY(mdp_lgv_open(c, false, false, &apply, &L));
   if (c->nlocal)
-    lgv_final_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, dtf, c->rmass.p, c->f.p, c->v.p, L, writeback ? 1 : 0);
+    lgv_final_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, L,
+                                                             writeback ? 1 : 0);
   MDP_HIP(c, hipGetLastError());
-  return mdp_lgv_close(c, c->nlocal, dt, L);
+  return mdp_lgv_close(c, L);
+}
+
+// A final half on its own, for both modes: with the chain (kick, chain update, scaling), with the Langevin force, or
+// plain.  lgv_writeback = false: the forces of a new run's setup come next, so f stays as the compute left it.
+int md_final_half(mdp_ctx *c, bool lgv_writeback = true)
+{
+  if (c->nhc.on) return mdp_nhc_final(c);
+  if (c->lgv.on) return lgv_final(c, lgv_writeback);
+  if (c->nlocal) nve_final_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p);
+  MDP_HIP(c, hipGetLastError());
+  return MDP_OK;
+}
+
+// The one launch path of the integrate kernel, for resident (mdp_md_advance) and host-linked (mdp_hnve_initial)
+// contexts: thermostat open, the kernel, thermostat close.  The caller brings what differs: with_final, the `check yes`
+// words and limits (flag), the style check it armed (sc), zero_f and the two device words for the peers.
+int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double hardsq, const MdpStyleCheck &sc,
+                      bool zero_f, double *dset, double *dclr)
+{
+  // a final half pending across a thermostat set-up (mdp_nhc_setup / _run, mdp_langevin_run by a host that does not
+  // defer it) goes first, on its own, and leaves f as it was: the setup of the new run sees the compute's forces alone,
+  // as after Verlet::setup
+  if (with_final && ((c->nhc.on && c->nhc.need_setup) || (c->lgv.on && c->lgv.need_setup))) {
+    MDP_TRY(md_final_half(c, false));
+    with_final = false;
+  }
+  const double *vscale = nullptr;
+  bool lgv = false;
+  MdpLgvArgs L;
+  if (c->nhc.on) MDP_TRY(mdp_nhc_open(c, with_final, &vscale));
+  if (c->lgv.on) MDP_TRY(mdp_lgv_open(c, with_final, true, &lgv, &L));
+  const int n = c->nlocal;
+  if (!n) return MDP_OK;
+  const MdpStep s = mdp_step(c);
+  // FINAL x CHECK x {plain, SCALE, LANGEVIN}: the twelve instantiations (one thermostat per context: never both)
+  auto launch = [&](auto fv, auto cv, auto sv, auto lv) {
+    nve_advance_kernel<decltype(fv)::value, decltype(cv)::value, decltype(sv)::value, decltype(lv)::value>
+        <<<nblk(n), 256, 0, c->stream>>>(n, s.dtf, s.dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p, trigsq, hardsq, flag, sc,
+                                         zero_f ? 1 : 0, dset, dclr, vscale, L);
+  };
+  constexpr std::true_type T;
+  constexpr std::false_type F;
+  auto thermostat = [&](auto fv, auto cv) {
+    if (vscale) launch(fv, cv, T, F);
+    else if (lgv) launch(fv, cv, F, T);
+    else launch(fv, cv, F, F);
+  };
+  auto check = [&](auto fv) {
+    if (flag) thermostat(fv, T);
+    else thermostat(fv, F);
+  };
+  if (with_final) check(T);
+  else check(F);
+  MDP_HIP(c, hipGetLastError());
+  if (lgv) MDP_TRY(mdp_lgv_close(c, L));
+  return MDP_OK;
 }
 
 } // namespace
@@ -946,7 +956,7 @@ void mdp_sflag_arm(mdp_ctx *c, MdpStyleCheck &sc)
   sc = MdpStyleCheck();
   c->sflag_set ^= 1;
   const int set = c->sflag_set;
-  int *h = (int *) (c->h_pinned + 32) + 8 * set; // (the kernels that wrote this set ran two steps ago)
+  int *h = mdp_pin(c, kPinSflag) + 8 * set; // (the kernels that wrote this set ran two steps ago)
   for (int k = 0; k < 8; k++) h[k] = 0;
   MdpStyleCheckMeta &m = c->sflag_meta[set];
   m = MdpStyleCheckMeta();
@@ -1012,7 +1022,7 @@ int mdp_sflag_collect(mdp_ctx *c, bool *far, bool *toofar)
   if (!c->sflag_committed[set]) return MDP_OK;
   MDP_HIP(c, hipEventSynchronize(c->ev_sflag[set]));
   c->sflag_committed[set] = false;
-  const int *h = (const int *) (c->h_pinned + 32) + 8 * set;
+  const int *h = mdp_pin(c, kPinSflag) + 8 * set;
   const MdpStyleCheckMeta &m = c->sflag_meta[set];
   if (m.has_style && m.build_epoch == c->style_builds) {
     if (far) *far = (h[0] | h[4]) != 0;
@@ -1025,6 +1035,43 @@ int mdp_sflag_collect(mdp_ctx *c, bool *far, bool *toofar)
   return MDP_OK;
 }
 
+int mdp_md_flush_final(mdp_ctx *c) { return c->md && c->final_pending ? mdp_md_final_integrate(c) : MDP_OK; }
+
+// ---- `check yes` of the host-level skin, read one step late (mdp_md_moved_async, mdp_md_integrate_check, mdp_hnve_initial)
+int mdp_moved_take(mdp_ctx *c, int *moved, int *dangerous)
+{
+  MdpDomain &D = c->dd;
+  const int *h = mdp_pin(c, kPinMoved);
+  if (!D.ev_moved) MDP_HIP(c, hipEventCreateWithFlags(&D.ev_moved, hipEventDisableTiming));
+  const bool pending = D.moved_pending;
+  if (pending) MDP_HIP(c, hipEventSynchronize(D.ev_moved_ref ? D.ev_moved_ref : D.ev_moved));
+  D.moved_pending = false;
+  if (moved) *moved = pending ? h[0] : 0;
+  if (dangerous) *dangerous = pending ? h[1] : 0;
+  return MDP_OK;
+}
+
+int *mdp_moved_arm(mdp_ctx *c, double skin, double *trigsq, double *hardsq)
+{
+  int *h = mdp_pin(c, kPinMoved);
+  h[0] = h[1] = 0;
+  const double hard = 0.5 * skin;
+  double trig = hard - 0.1 * mdp_margin_scale(c); // (the margin covers the step of motion before the answer is read)
+  if (trig < 0.5 * hard) trig = 0.5 * hard;
+  *trigsq = trig * trig;
+  *hardsq = hard * hard;
+  return h;
+}
+
+int mdp_moved_post(mdp_ctx *c, bool borrow_sflag)
+{
+  MdpDomain &D = c->dd;
+  if (!borrow_sflag) MDP_HIP(c, hipEventRecord(D.ev_moved, c->stream));
+  D.ev_moved_ref = borrow_sflag ? c->ev_sflag[c->sflag_set] : D.ev_moved;
+  D.moved_pending = true;
+  return MDP_OK;
+}
+
 // launches the integrate kernel of the next step (with_final: after the pending final half-kick of the finished one)
 // and the refresh of the periodic self-images; flag != null: the displacement check of the new positions in the same
 // pass (see mdp_md_integrate_check in domain.hip)
@@ -1034,20 +1081,6 @@ int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double
   // must not be applied twice
   if (c->final_deferred_seen && with_final && !c->final_pending) with_final = false;
   if (with_final) c->final_pending = false;
-  const double dtf = 0.5 * c->cfg.dt * c->cfg.ftm2v;
-  const double *vscale = nullptr;
-  if (c->nhc.on) MDP_TRY(mdp_nhc_open(c, c->nlocal, dtf, c->cfg.dt, &with_final, &vscale));
-  bool lgv = false;
-  MdpLgvArgs L;
-  if (c->lgv.on) {
-    // a final half pending across mdp_langevin_run (a host that does not defer it) goes first, on its own, and leaves f
-    // as it was: the setup force of the new run is added to the compute's forces alone, as after Verlet::setup
-    if (with_final && c->lgv.need_setup) {
-      MDP_TRY(lgv_final(c, dtf, c->cfg.dt, c->cfg.ftm2v, false));
-      with_final = false;
-    }
-    MDP_TRY(mdp_lgv_open(c, c->nlocal, c->cfg.dt, c->cfg.ftm2v, with_final, true, &lgv, &L));
-  }
   // aeam accumulates into f (three-body atomics, tile kernels): its force_clear rides in this kernel and in the refresh
   // of the images when every ghost is a periodic self-image (one GPU).  The flag is dropped by whatever rebuilds or
   // re-orders the atom arrays before the compute (mdp_aeam_prepare) -- the compute then clears f itself.
@@ -1063,31 +1096,12 @@ int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double
     dset = c->dd.flagbuf.p + c->dd.flag_par;
     dclr = c->dd.flagbuf.p + (c->dd.flag_par ^ 1);
   }
+  // (the thermostat is opened, and its step counted, on a rank without owned atoms too)
+  MdpStyleCheck sc;
+  if (c->nlocal) mdp_sflag_arm(c, sc);
+  MDP_TRY(md_launch_advance(c, with_final, flag, trigsq, hardsq, sc, zero_f, dset, dclr));
   if (c->nlocal) {
-    const int g = nblk(c->nlocal);
-    MdpStyleCheck sc;
-    mdp_sflag_arm(c, sc);
-#define MDP_ADV1(FV, CV, SV, LV)                                                                                      \
-  nve_advance_kernel<FV, CV, SV, LV><<<g, 256, 0, c->stream>>>(c->nlocal, dtf, c->cfg.dt, c->rmass.p, c->f.p, c->v.p,   \
-                                                               c->xq.p, c->xhold.p, trigsq, hardsq, flag, sc,           \
-                                                               zero_f ? 1 : 0, dset, dclr, vscale, L)
-#define MDP_ADV(FV, CV)                                                                                               \
-  do {                                                                                                                \
-    if (vscale) MDP_ADV1(FV, CV, true, false);                                                                        \
-    else if (lgv) MDP_ADV1(FV, CV, false, true);                                                                      \
-    else MDP_ADV1(FV, CV, false, false);                                                                              \
-  } while (0)
-    if (with_final) {
-      if (flag) MDP_ADV(true, true);
-      else MDP_ADV(true, false);
-    } else {
-      if (flag) MDP_ADV(false, true);
-      else MDP_ADV(false, false);
-    }
-#undef MDP_ADV
-#undef MDP_ADV1
     c->acc_prezeroed = sc.acc != nullptr;
-    if (lgv) MDP_TRY(mdp_lgv_close(c, c->nlocal, c->cfg.dt, L));
     // the flag words are complete behind this kernel unless remote ghosts arrive later in the step (mdp_md_unpack_x)
     if (!(c->remote_start < c->nall)) MDP_TRY(mdp_sflag_commit(c));
   }
@@ -1131,12 +1145,7 @@ int mdp_md_final_integrate(mdp_ctx *c)
   if (!c) return MDP_EINVAL;
   if (!c->md) return mdp_fail(c, MDP_ESTATE, "mdp_md_setup not called");
   c->final_pending = false;
-  const double dtf = 0.5 * c->cfg.dt * c->cfg.ftm2v;
-  if (c->nhc.on) return mdp_nhc_final(c, c->nlocal, dtf, c->cfg.dt);
-  if (c->lgv.on) return lgv_final(c, dtf, c->cfg.dt, c->cfg.ftm2v);
-  if (c->nlocal) nve_final_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, dtf, c->rmass.p, c->f.p, c->v.p);
-  MDP_HIP(c, hipGetLastError());
-  return MDP_OK;
+  return md_final_half(c);
 }
 
 int mdp_md_aeam_density(mdp_ctx *c, int eflag)
@@ -1294,57 +1303,21 @@ int mdp_hnve_initial(mdp_ctx *c, int *moved, int *dangerous)
   if (!c) return MDP_EINVAL;
   if (!c->hn_on || !c->hn_v_current) return mdp_fail(c, MDP_ESTATE, "mdp_hnve_upload_v not called for the current atoms");
   MDP_HIP(c, hipSetDevice(c->device));
-  MdpDomain &D = c->dd;
-  int *h = (int *) (c->h_pinned + 28);
-  if (!D.ev_moved) MDP_HIP(c, hipEventCreateWithFlags(&D.ev_moved, hipEventDisableTiming));
-  int m = 0, dg = 0;
-  if (D.moved_pending) {
-    MDP_HIP(c, hipEventSynchronize(D.ev_moved_ref ? D.ev_moved_ref : D.ev_moved));
-    m = h[0];
-    dg = h[1];
-    D.moved_pending = false;
-  }
-  if (moved) *moved = m;
-  if (dangerous) *dangerous = dg;
-  const int n = c->nlocal;
-  if (n) {
-    h[0] = h[1] = 0;
-    const double hard = 0.5 * c->skin;
-    double trig = hard - 0.1 * mdp_margin_scale(c);
-    if (trig < 0.5 * hard) trig = 0.5 * hard;
+  MDP_TRY(mdp_moved_take(c, moved, dangerous));
+  if (c->nlocal) { // (without owned atoms nothing is queued, and the thermostat is not opened)
+    double trigsq, hardsq;
+    int *h = mdp_moved_arm(c, c->skin, &trigsq, &hardsq);
     // rebomos: the style's own displacement checks (device-built lists, pruned rows) ride in this kernel and are read
     // by the NEXT compute, as in resident runs (MdpStyleCheck; every ghost is an image that moves with its owner) --
     // a check of its own in front of every compute had the host wait for the stream once per step
     MdpStyleCheck sc;
     c->hn_deferred_check = !c->md && c->have_rebomos && !c->have_aeam && c->host_ghosts_derived;
     if (c->hn_deferred_check) mdp_sflag_arm(c, sc);
-    const double *vscale = nullptr;
-    bool with_final = false;
-    if (c->nhc.on) MDP_TRY(mdp_nhc_open(c, n, c->hn_dtf, c->hn_dt, &with_final, &vscale));
-    bool lgv = false;
-    MdpLgvArgs L;
-    if (c->lgv.on) MDP_TRY(mdp_lgv_open(c, n, c->hn_dt, c->hn_ftm2v, false, true, &lgv, &L));
-    if (lgv) // the setup force of a run (the later steps' forces were completed by mdp_hnve_final)
-      nve_advance_kernel<false, true, false, true><<<nblk(n), 256, 0, c->stream>>>(
-          n, c->hn_dtf, c->hn_dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p, trig * trig, hard * hard, h, sc, 0,
-          nullptr, nullptr, nullptr, L);
-    else if (vscale)
-      nve_advance_kernel<false, true, true><<<nblk(n), 256, 0, c->stream>>>(n, c->hn_dtf, c->hn_dt, c->rmass.p, c->f.p, c->v.p,
-                                                                            c->xq.p, c->xhold.p, trig * trig, hard * hard, h,
-                                                                            sc, 0, nullptr, nullptr, vscale);
-    else
-      nve_advance_kernel<false, true><<<nblk(n), 256, 0, c->stream>>>(n, c->hn_dtf, c->hn_dt, c->rmass.p, c->f.p, c->v.p, c->xq.p,
-                                                                      c->xhold.p, trig * trig, hard * hard, h, sc, 0);
-    MDP_HIP(c, hipGetLastError());
-    if (lgv) MDP_TRY(mdp_lgv_close(c, n, c->hn_dt, L));
-    if (c->hn_deferred_check && c->sflag_armed) { // one event behind the kernel serves both readers of its words
-      MDP_TRY(mdp_sflag_commit(c));
-      D.ev_moved_ref = c->ev_sflag[c->sflag_set];
-    } else {
-      MDP_HIP(c, hipEventRecord(D.ev_moved, c->stream));
-      D.ev_moved_ref = D.ev_moved;
-    }
-    D.moved_pending = true;
+    // (never fused: the forces of every step were completed by mdp_hnve_final; a Langevin run's setup force rides here)
+    MDP_TRY(md_launch_advance(c, false, h, trigsq, hardsq, sc, false, nullptr, nullptr));
+    const bool armed = c->hn_deferred_check && c->sflag_armed; // one event behind the kernel serves both readers of its words
+    if (armed) MDP_TRY(mdp_sflag_commit(c));
+    MDP_TRY(mdp_moved_post(c, armed));
   }
   MDP_TRY(mdp_host_refresh_ghosts(c));  // Comm::forward_comm of x on one periodic rank
   if (!c->hn_deferred_check) {
@@ -1359,12 +1332,7 @@ int mdp_hnve_final(mdp_ctx *c)
   if (!c) return MDP_EINVAL;
   if (!c->hn_on || !c->hn_v_current) return mdp_fail(c, MDP_ESTATE, "mdp_hnve_upload_v not called for the current atoms");
   MDP_HIP(c, hipSetDevice(c->device));
-  if (c->nhc.on) return mdp_nhc_final(c, c->nlocal, c->hn_dtf, c->hn_dt);
-  if (c->lgv.on) return lgv_final(c, c->hn_dtf, c->hn_dt, c->hn_ftm2v);
-  if (c->nlocal)
-    nve_final_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, c->hn_dtf, c->rmass.p, c->f.p, c->v.p);
-  MDP_HIP(c, hipGetLastError());
-  return MDP_OK;
+  return md_final_half(c);
 }
 
 // owned atoms' x / v / f in the host's order (any of them NULL: not wanted); complete on return
@@ -1415,7 +1383,7 @@ int mdp_md_thermo(mdp_ctx *c, double out[9])
 {
   if (!c || !out) return MDP_EINVAL;
   if (!c->md) return mdp_fail(c, MDP_ESTATE, "mdp_md_setup not called");
-  if (c->final_pending) MDP_TRY(mdp_md_final_integrate(c)); // KE is that of full-step velocities
+  MDP_TRY(mdp_md_flush_final(c)); // KE is that of full-step velocities
   hipStream_t st = c->stream;
   MDP_HIP(c, hipMemsetAsync(c->acc.p + 7, 0, sizeof(double) * 2, st));
   const int grid = c->nlocal > 0 ? (nblk(c->nlocal) < 1024 ? nblk(c->nlocal) : 1024) : 0;
@@ -1424,7 +1392,7 @@ int mdp_md_thermo(mdp_ctx *c, double out[9])
                                          c->acc.p);
   MDP_HIP(c, hipGetLastError());
   MDP_HIP(c, hipMemcpyAsync(c->h_pinned, c->acc.p, sizeof(double) * 9, hipMemcpyDeviceToHost, st));
-  int *hflags = (int *) (c->h_pinned + 16);
+  int *hflags = mdp_pin(c, kPinFlags);
   MDP_HIP(c, hipMemcpyAsync(hflags, c->flags.p, sizeof(int) * 5, hipMemcpyDeviceToHost, st));
   MDP_HIP(c, hipStreamSynchronize(st));
   MDP_TRY(mdp_flags_check(c, hflags));
@@ -1439,7 +1407,7 @@ int mdp_md_download(mdp_ctx *c, double *x, double *v, double *f, double *eatom)
 {
   if (!c) return MDP_EINVAL;
   if (!c->md) return mdp_fail(c, MDP_ESTATE, "mdp_md_setup not called");
-  if (v && c->final_pending) MDP_TRY(mdp_md_final_integrate(c)); // full-step velocities
+  if (v) MDP_TRY(mdp_md_flush_final(c)); // full-step velocities
   hipStream_t st = c->stream;
   const int n = c->nlocal;
   if (x && n) {
@@ -1630,9 +1598,9 @@ int mdp_md_class_stats(mdp_ctx *c, long long out[32])
   for (int k = 0; k < 4; k++) out[20 + k] = c->lj_class_base[k + 1] - c->lj_class_base[k];
   if (c->lj_tiled && !c->lj_ordered) out[20] = c->ntile; // (no large unions: one class, natural order)
   if (c->h_pinned) {
-    const int *h = (const int *) (c->h_pinned + 40) + 4 * c->ovf_par; // (the set the last compute published)
+    const int *h = mdp_pin(c, kPinOvf) + 4 * c->ovf_par; // (the set the last compute published)
     for (int k = 0; k < 4; k++) out[25 + k] = h[k];
-    out[24] = ((const int *) (c->h_pinned + 44))[0];
+    out[24] = *mdp_pin(c, kPinGeneral);
   }
   out[29] = c->tile_small;
   return MDP_OK;
@@ -1666,7 +1634,7 @@ int mdp_md_list_state(mdp_ctx *c, double out[8])
   out[2] = c->prune_valid ? c->prune_buf : 0.0;
   out[3] = (double) c->dangerous_builds;
   if (c->h_pinned) {
-    const int *h = (const int *) (c->h_pinned + 40) + 4 * c->ovf_par; // (the set the last compute published)
+    const int *h = mdp_pin(c, kPinOvf) + 4 * c->ovf_par; // (the set the last compute published)
     out[4] = (double) h[0] + h[1] + h[2] + h[3];
   }
   out[5] = (c->ovf3_hot[0] > 0 || c->ovf3_hot[1] > 0 || c->ovf3_hot[2] > 0 || c->ovf3_hot[3] > 0) ? 1.0 : 0.0;
@@ -1704,7 +1672,7 @@ int mdp_md_unpack_x(mdp_ctx *c, int first_ghost, int n, const double *d_buf)
   // (library transport with the displacement words gathered behind this halo: reduced here, read by the next step)
   MdpDomain &D = c->dd;
   const bool glob = D.flagbuf.p && D.nccl_comm && D.fwd_gathered;
-  int *h_glob = (int *) (c->h_pinned + 46);
+  int *h_glob = mdp_pin(c, kPinGlob);
   if (n || glob)
     unpack_x_kernel<<<nblk(n > 0 ? n : 1), 256, 0, c->stream>>>(n, c->nlocal + first_ghost, d_buf, c->xq.p, sc,
                                                                 glob ? D.flagbuf.p + 2 : nullptr, glob ? D.G.nranks : 0,

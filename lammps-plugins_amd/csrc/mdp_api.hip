@@ -784,13 +784,13 @@ int mdp_create(mdp_ctx **out, int device)
   }
   c->own_stream = true;
   if (c->acc.reserve((size_t) MDP_ACC_STRIDE * (2 + MDP_ACC_SLOTS)) != hipSuccess || c->flags.reserve(8) != hipSuccess ||
-      hipHostMalloc((void **) &c->h_pinned, 64 * sizeof(double)) != hipSuccess ||
+      hipHostMalloc((void **) &c->h_pinned, kPinWords * sizeof(double)) != hipSuccess ||
       hipMemset(c->flags.p, 0, 8 * sizeof(int)) != hipSuccess) {
     mdp_destroy(c);
     return MDP_ENOMEM;
   }
   memset(c->map, 0, sizeof c->map);
-  memset(c->h_pinned, 0, 64 * sizeof(double));
+  memset(c->h_pinned, 0, kPinWords * sizeof(double));
   *out = c;
   return MDP_OK;
 }
@@ -1292,7 +1292,7 @@ static int fetch_acc(mdp_ctx *c, double *eng, double *virial)
 {
   hipStream_t st = c->stream;
   MDP_HIP(c, hipMemcpyAsync(c->h_pinned, c->acc.p, sizeof(double) * 8, hipMemcpyDeviceToHost, st));
-  int *hflags = (int *) (c->h_pinned + 16);
+  int *hflags = mdp_pin(c, kPinFlags);
   MDP_HIP(c, hipMemcpyAsync(hflags, c->flags.p, sizeof(int) * 5, hipMemcpyDeviceToHost, st));
   MDP_HIP(c, hipStreamSynchronize(st));
   MDP_TRY(mdp_flags_check(c, hflags));

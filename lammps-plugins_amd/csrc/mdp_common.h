@@ -347,14 +347,87 @@ __device__ __forceinline__ void mdp_lgv_force(const MdpLgvArgs &L, int i, double
   }
 }
 
-// the per-block sum of e over a 256-lane workgroup into part[blockIdx.x] (fixed order; every lane must call it)
-__device__ __forceinline__ void mdp_block_sum_256(double e, double *part)
+// a . b of two 3-vectors with the roundings written out: the first product is rounded, the other two are fused.  Left
+// to -ffp-contract=fast the compiler picks the product it rounds per kernel and per build, and the Langevin tally (a sum
+// of these) would move in its last bit whenever the code around it changes.
+__device__ __forceinline__ double mdp_dot3(double a0, double b0, double a1, double b1, double a2, double b2)
+{ return fma(a2, b2, fma(a1, b1, a0 * b0)); }
+
+// The fixed-order sums behind the bitwise reproducible thermostats.  The per-block sum: W values per lane of a 256-lane
+// workgroup into part[W * blockIdx.x + k] -- lanes by xor-shuffle 32..1, then the four waves as (w0 + w1) + (w2 + w3).
+// Every lane must call it.
+template <int W> __device__ __forceinline__ void mdp_block_sum_256(const double *e, double *part)
 {
-  __shared__ double wsum[4];
-  for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = e;
+  __shared__ double wsum[W][4];
+#pragma unroll
+  for (int k = 0; k < W; k++) {
+    double s = e[k];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) wsum[k][threadIdx.x >> 6] = s;
+  }
   __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+  const int k = threadIdx.x;
+  if (k < W) part[W * (size_t) blockIdx.x + k] = (wsum[k][0] + wsum[k][1]) + (wsum[k][2] + wsum[k][3]);
+}
+__device__ __forceinline__ void mdp_block_sum_256(double e, double *part) { mdp_block_sum_256<1>(&e, part); }
+
+// The slot sum: ONE 256-lane workgroup adds npart slots of W values, out[k] = sum over b of part[W * b + k] on every
+// lane -- slots strided by 256 per lane, then the tree 128..1 in shared memory; one pass over the slots for all W.
+template <int W> __device__ __forceinline__ void mdp_slot_sum_256(const double *__restrict__ part, int npart, double *out)
+{
+  __shared__ double red[W][256];
+  double s[W] = {};
+  for (int b = threadIdx.x; b < npart; b += 256)
+#pragma unroll
+    for (int k = 0; k < W; k++) s[k] += part[W * (size_t) b + k];
+#pragma unroll
+  for (int k = 0; k < W; k++) red[k][threadIdx.x] = s[k];
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int) threadIdx.x < h)
+#pragma unroll
+      for (int k = 0; k < W; k++) red[k][threadIdx.x] += red[k][threadIdx.x + h];
+    __syncthreads();
+  }
+#pragma unroll
+  for (int k = 0; k < W; k++) out[k] = red[k][0];
+}
+
+// The style-level displacement test of one atom (MdpStyleCheck), shared by the integrate kernel (owned atoms, flag words
+// [0..4)) and the halo unpack (remote ghosts, [4..8)).  two_steps: the atom's way in two steps at its current speed, a
+// quarter on top for its acceleration.  The triggers are read one compute late and fire early by a fixed margin that
+// stands for two steps of motion (0.07 / 0.1 A: 35 / 50 A/ps at 1 fs); an atom faster than that -- the tail of a 5 000 K
+// melt -- fires by its OWN two steps instead, so what it reaches before the answer is read is still inside the limit.
+__device__ __forceinline__ bool mdp_reaches(const double d2, const double hardsq, const double two_steps)
+{
+  const double rem = sqrt(hardsq) - two_steps; // will the atom be beyond `hard` two steps on?
+  return rem <= 0.0 || d2 > rem * rem;
+}
+struct MdpStyleVote { bool a = false, ah = false, p = false, ph = false; }; // beyond: list trigger, half the inner skin, pruning trigger, half the buffer
+__device__ __forceinline__ void mdp_style_test(const MdpStyleCheck &SC, const size_t i, const double4 &x, const double two_steps,
+                                               MdpStyleVote &w)
+{
+  auto test = [&](const mdp_hold_t *ref, const double trigsq, const double hardsq, bool &far, bool &toofar) {
+    const double dx = x.x - ref[3 * i], dy = x.y - ref[3 * i + 1], dz = x.z - ref[3 * i + 2];
+    const double d2 = dx * dx + dy * dy + dz * dz;
+    far = d2 > trigsq || mdp_reaches(d2, hardsq, two_steps);
+    toofar = d2 > hardsq;
+  };
+  if (SC.xa) test(SC.xa, SC.trig_a, SC.hard_a, w.a, w.ah);
+  if (SC.xp) test(SC.xp, SC.trig_p, SC.hard_p, w.p, w.ph);
+}
+// Every lane of the workgroup must reach the vote: the wave votes with ALL its lanes, then lane 0 stores (a vote inside
+// the lane-0 branch would count lane 0 alone).  Pinned host words zeroed by the host: plain idempotent stores.
+__device__ __forceinline__ void mdp_style_vote(const MdpStyleCheck &SC, const MdpStyleVote &w, const int base)
+{
+  if (!SC.flag) return;
+  const bool wa = __any(w.a), wah = __any(w.ah), wp = __any(w.p), wph = __any(w.ph);
+  if ((threadIdx.x & 63) == 0) {
+    if (wa) SC.flag[base] = 1;
+    if (wah) SC.flag[base + 1] = 1;
+    if (wp) SC.flag[base + 2] = 1;
+    if (wph) SC.flag[base + 3] = 1;
+  }
 }
 
 struct mdp_ctx {
@@ -411,7 +484,7 @@ struct mdp_ctx {
   DevBuf<double> vatom; // [nall][6] per-atom virial (allocated on first use)
   DevBuf<double> acc;   // [16] eng, virial[6], flags...
   DevBuf<int> flags;    // [4] overflow etc.
-  double *h_pinned = nullptr; // pinned staging for small results (32 doubles)
+  double *h_pinned = nullptr; // pinned words for small results and flag words (MdpPin names the layout)
   char *h_small = nullptr;    // pinned scratch of mdp_read_small / mdp_write_small (counts, totals, flag words)
   size_t h_small_cap = 0;
 
@@ -475,7 +548,7 @@ struct mdp_ctx {
   double hn_mass[16] = {};
   DevBuf<double> hn_mass_dev;
   bool hn_v_current = false;      // c->v / c->rmass match the atoms of the last mdp_set_atoms_host
-  int ovf_par = 0;                // which of the two sets of pinned overflow counts (h_pinned + 40) this compute uses
+  int ovf_par = 0;                // which of the two sets of pinned overflow counts (kPinOvf) this compute uses
   bool hn_deferred_check = false; // host mode + device integrator, rebomos: the style checks ride in the integrate kernel, read a compute late
   int ang_list_n = -1;            // >= 0: ang_list holds exactly the owned angular centres of the current atoms (mdp_md_build_master_list)
   bool f_prezeroed = false;       // f[0 .. nall) was cleared by the integrate kernel / image refresh of this step (aeam)
@@ -582,6 +655,37 @@ struct mdp_ctx {
 
 int mdp_fail(mdp_ctx *c, int code, const char *fmt, ...);
 
+// Layout of mdp_ctx::h_pinned, in doubles (kPinWords of them, zeroed at mdp_create).  The int words are written by kernels
+// with plain stores (or by a copy) and are valid for the host once the event / stream wait named here has returned.
+enum MdpPin {
+  kPinAcc = 0,        // [0..9) doubles: acc[0..9) as copied by fetch_acc / aeam_fetch / mdp_md_thermo; read after their stream wait
+  kPinFlags = 16,     // 5 ints: the overflow flags, copied and read with kPinAcc (mdp_flags_check)
+  kPinHostCheck = 24, // 4 ints: rebomos' immediate displacement check (rebomos_check_launch -> moved_kernel); host zeroes, reads after a stream wait
+  kPinMoved = 28,     // 2 ints: `check yes` of the host-level skin (mdp_moved_arm zeroes; moved_kernel / the integrate kernel write; mdp_moved_take reads behind ev_moved_ref)
+  kPinSflag = 32,     // 2 sets x 8 ints: the style-level checks (mdp_sflag_arm zeroes a set; the integrate kernel writes [0..4),
+                      //         the halo unpack [4..8); mdp_sflag_collect reads the other set behind ev_sflag[set])
+  kPinOvf = 40,       // 2 sets x 4 ints (ovf_par): centres that outgrew the lane-per-centre kernel, per list
+                      //         (rebo_centre_general_kernel writes; read two computes later, behind mdp_sflag_collect's wait)
+  kPinGeneral = 44,   // 1 int: centres handed to the general kernel (same writer; statistics)
+  kPinCubic = 45,     // 1 int: tiles listed for the cubic Lennard-Jones spline (the cubic / queue kernels write; sizes later grids)
+  kPinGlob = 46,      // 1 int: some rank's owned atom moved (unpack_x_kernel writes; mdp_dd_comm_step_begin reads behind ev_glob_ref)
+  kPinCubicWalk = 47, // 1 int: queue mode, tiles whose queues overflowed (rebo_lj_cubic_kernel writes; sizes later grids)
+  kPinWords = 64
+};
+static_assert(kPinCubicWalk < kPinWords, "the last pinned word must fit the allocation");
+inline int *mdp_pin(const mdp_ctx *c, MdpPin word) { return (int *) (c->h_pinned + word); }
+
+// The constants of a velocity-Verlet step, for a resident context (mdp_md_setup) and a host-linked one (mdp_hnve_setup)
+struct MdpStep {
+  double dt, dtf, ftm2v; // dtf = 0.5 dt ftm2v
+  const double *mass;    // per-type host masses [16] (unused types: 0.0 resident, 1.0 host-linked)
+};
+inline MdpStep mdp_step(const mdp_ctx *c)
+{
+  if (c->md) return {c->cfg.dt, 0.5 * c->cfg.dt * c->cfg.ftm2v, c->cfg.ftm2v, c->h_mass};
+  return {c->hn_dt, c->hn_dtf, c->hn_ftm2v, c->hn_mass};
+}
+
 // The deferred displacement triggers are read one compute late, so they fire `margin` early.  The margins were
 // measured for the reference inputs' 1 fs step (0.1 A covers two steps at 50 A/ps); they scale with the time step of a
 // resident run (a 5 fs step moves atoms five times as far before the answer is read).
@@ -651,18 +755,24 @@ int mdp_host_pinned_reserve(mdp_ctx *c, size_t ndoubles); // c->h_down: pinned d
 int mdp_host_upload(mdp_ctx *c, void *d_dst, const void *h_src, size_t bytes); // pageable host array -> device, pipelined through pinned staging
 int mdp_host_refresh_ghosts(mdp_ctx *c);                  // host mode, images kept by the library: owner + count * h of this step
 int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double hardsq); // integrate kernel (+ displacement check)
-// thermostat (nhc.hip), around the integrate kernels when c->nhc.on.  _open: before the kernel of an initial half (after
-// the pending final half if *with_final): the chain update(s) of the step; *vscale = the device word the integrate kernel
-// scales the velocities by.  (*with_final comes back false when the final half had to run on its own first.)
-// _final: a final half on its own (kick, chain update, velocity scaling).
-int mdp_nhc_open(mdp_ctx *c, int n, double dtf, double dt, bool *with_final, const double **vscale);
-int mdp_nhc_final(mdp_ctx *c, int n, double dtf, double dt);
+int mdp_md_flush_final(mdp_ctx *c); // completes a final half the host deferred (resident mode), before anything that needs full-step velocities
+// `neigh_modify check yes` of the host-level skin, one step late (kPinMoved).  _take: the answer of the check the previous
+// call queued (waits for its event; 0 if none is pending); _arm: zeroes the words, gives the squared limits for `skin`;
+// _post: the event behind the kernel that writes the words (borrow_sflag: the style-check event the caller committed there)
+int mdp_moved_take(mdp_ctx *c, int *moved, int *dangerous);
+int *mdp_moved_arm(mdp_ctx *c, double skin, double *trigsq, double *hardsq);
+int mdp_moved_post(mdp_ctx *c, bool borrow_sflag);
+// thermostat (nhc.hip), around the integrate kernels when c->nhc.on.  _open: before the kernel of an initial half (fused
+// with the pending final half if with_final): the chain update(s) of the step; *vscale = the device word the integrate
+// kernel scales the velocities by.  _final: a final half on its own (kick, chain update, velocity scaling).
+int mdp_nhc_open(mdp_ctx *c, bool with_final, const double **vscale);
+int mdp_nhc_final(mdp_ctx *c);
 // Langevin thermostat (langevin.hip), around the integrate kernels when c->lgv.on.  _open: before a kernel that
 // first consumes a compute's forces (the fused final + initial, the setup step's initial half, a final half on its own):
 // *apply = whether this kernel adds the force; if so *L is filled (and the zero pre-pass queued).  Advances the step
 // counter when `initial`.  _close: behind that kernel (the tally of the step).
-int mdp_lgv_open(mdp_ctx *c, int n, double dt, double ftm2v, bool with_final, bool initial, bool *apply, MdpLgvArgs *L);
-int mdp_lgv_close(mdp_ctx *c, int n, double dt, const MdpLgvArgs &L);
+int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvArgs *L);
+int mdp_lgv_close(mdp_ctx *c, const MdpLgvArgs &L);
 void mdp_host_add(double *dst, const double *src, size_t n); // dst += src, threaded for large arrays
 int mdp_host_download_add(mdp_ctx *c, double *h_dst, double *h_stage, const double *d_src, size_t n); // chunked D2H + add
 int mdp_to_host_order(mdp_ctx *c, int n, int w, const double *d_src, double *d_dst);   // per-atom arrays, device -> host order

@@ -19,7 +19,6 @@ __global__ __launch_bounds__(256) void nhc_ke_kernel(const int n, const double d
                                                      const double *__restrict__ f, double *__restrict__ v,
                                                      double *__restrict__ part)
 {
-  __shared__ double wsum[4];
   const int i = blockIdx.x * 256 + threadIdx.x;
   double e = 0.0;
   if (i < n) {
@@ -37,10 +36,7 @@ __global__ __launch_bounds__(256) void nhc_ke_kernel(const int n, const double d
     }
     e = rmass[i] * (vx * vx + vy * vy + vz * vz);
   }
-  for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = e;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+  mdp_block_sum_256(e, part);
 }
 
 __global__ void nhc_scale_kernel(const int n, const double *__restrict__ st, double *__restrict__ v)
@@ -118,18 +114,11 @@ __device__ double nhc_half(double *st, const NhcArgs &a, double tt, double &T)
 __global__ __launch_bounds__(256) void nhc_chain_kernel(const double *__restrict__ part, double *__restrict__ st,
                                                         const NhcArgs a)
 {
-  __shared__ double red[256];
   double T = 0.0;
-  if (a.mode & (kNhcSetup | kNhcFinal)) {
-    double s = 0.0;
-    for (int k = threadIdx.x; k < a.npart; k += 256) s += part[k];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-      if ((int) threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-      __syncthreads();
-    }
-    const double ke = 0.5 * a.mvv2e * red[0];
+  if (a.mode & (kNhcSetup | kNhcFinal)) { // (the mode is the same for every lane: all of them reach the sum)
+    double mv2;
+    mdp_slot_sum_256<1>(part, a.npart, &mv2);
+    const double ke = 0.5 * a.mvv2e * mv2;
     T = a.nf > 0.0 ? 2.0 * ke / (a.nf * a.kb) : 0.0;
   }
   if (threadIdx.x != 0) return;
@@ -159,9 +148,10 @@ double nhc_target(const MdpNhc &h, long long n)
   return h.cfg.t_start + delta * (h.cfg.t_stop - h.cfg.t_start);
 }
 
-NhcArgs nhc_args(const mdp_ctx *c, int mode, int npart, double dt, double tt_a, double tt_b)
+NhcArgs nhc_args(const mdp_ctx *c, int mode, int npart, double tt_a, double tt_b)
 {
   const mdp_nhc_config &g = c->nhc.cfg;
+  const double dt = mdp_step(c).dt;
   NhcArgs a;
   a.mode = mode;
   a.npart = npart;
@@ -186,18 +176,16 @@ int nhc_reserve(mdp_ctx *c, int n)
 
 } // namespace
 
-int mdp_nhc_open(mdp_ctx *c, int n, double dtf, double dt, bool *with_final, const double **vscale)
+int mdp_nhc_open(mdp_ctx *c, bool with_final, const double **vscale)
 {
   MdpNhc &h = c->nhc;
   hipStream_t st = c->stream;
+  const int n = c->nlocal;
+  const double dtf = mdp_step(c).dtf;
   MDP_TRY(nhc_reserve(c, n));
-  if (*with_final && h.need_setup) { // (a final half pending across mdp_nhc_setup: it goes first, on its own)
-    MDP_TRY(mdp_nhc_final(c, n, dtf, dt));
-    *with_final = false;
-  }
   int mode = kNhcInitial;
   double tt_a = h.tt;
-  if (*with_final) {
+  if (with_final) {
     mode |= kNhcFinal; // H of the finished step at its own target
     if (n) nhc_ke_kernel<true, false><<<nblk(n), 256, 0, st>>>(n, dtf, c->rmass.p, c->f.p, c->v.p, h.part.p);
   } else if (h.need_setup) {
@@ -208,19 +196,20 @@ int mdp_nhc_open(mdp_ctx *c, int n, double dtf, double dt, bool *with_final, con
   }
   h.step++;
   h.tt = nhc_target(h, h.step);
-  nhc_chain_kernel<<<1, 256, 0, st>>>(h.part.p, h.st.p, nhc_args(c, mode, n ? nblk(n) : 0, dt, tt_a, h.tt));
+  nhc_chain_kernel<<<1, 256, 0, st>>>(h.part.p, h.st.p, nhc_args(c, mode, n ? nblk(n) : 0, tt_a, h.tt));
   MDP_HIP(c, hipGetLastError());
   *vscale = h.st.p + kNhcS;
   return MDP_OK;
 }
 
-int mdp_nhc_final(mdp_ctx *c, int n, double dtf, double dt)
+int mdp_nhc_final(mdp_ctx *c)
 {
   MdpNhc &h = c->nhc;
   hipStream_t st = c->stream;
+  const int n = c->nlocal;
   MDP_TRY(nhc_reserve(c, n));
-  if (n) nhc_ke_kernel<true, true><<<nblk(n), 256, 0, st>>>(n, dtf, c->rmass.p, c->f.p, c->v.p, h.part.p);
-  nhc_chain_kernel<<<1, 256, 0, st>>>(h.part.p, h.st.p, nhc_args(c, kNhcFinal, n ? nblk(n) : 0, dt, h.tt, h.tt));
+  if (n) nhc_ke_kernel<true, true><<<nblk(n), 256, 0, st>>>(n, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, h.part.p);
+  nhc_chain_kernel<<<1, 256, 0, st>>>(h.part.p, h.st.p, nhc_args(c, kNhcFinal, n ? nblk(n) : 0, h.tt, h.tt));
   if (n) nhc_scale_kernel<<<nblk(3 * (long long) n), 256, 0, st>>>(n, h.st.p, c->v.p);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
@@ -264,7 +253,7 @@ int mdp_nhc_run(mdp_ctx *c, long long first, long long last)
   if (!c->nhc.on) return mdp_fail(c, MDP_ESTATE, "mdp_nhc_setup not called");
   if (last < first) return mdp_fail(c, MDP_EINVAL, "mdp_nhc_run: last step %lld before first %lld", last, first);
   // a final half the host deferred belongs to the step before the new ramp: it runs now, at that step's target
-  if (c->md && c->final_pending) MDP_TRY(mdp_md_final_integrate(c));
+  MDP_TRY(mdp_md_flush_final(c));
   MdpNhc &h = c->nhc;
   h.first = first;
   h.last = last;
@@ -303,7 +292,7 @@ int mdp_nhc_off(mdp_ctx *c)
 {
   if (!c) return MDP_EINVAL;
   // a deferred final half of the last thermostatted step completes with its chain update before the NVE code takes over
-  if (c->nhc.on && c->md && c->final_pending) MDP_TRY(mdp_md_final_integrate(c));
+  if (c->nhc.on) MDP_TRY(mdp_md_flush_final(c));
   c->nhc.on = false;
   return MDP_OK;
 }

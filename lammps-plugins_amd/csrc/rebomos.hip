@@ -3778,7 +3778,7 @@ static int rebomos_check_launch(mdp_ctx *c, const double trig)
 {
   const int nall = c->nall;
   const double hard = 0.5 * c->skin_inner;
-  int *h = (int *) (c->h_pinned + 24); // no check is in flight here: the caller has waited for the previous one
+  int *h = mdp_pin(c, kPinHostCheck); // no check is in flight here: the caller has waited for the previous one
   h[0] = h[1] = h[2] = h[3] = 0;
   // (pruned rows: their own, smaller trigger against the positions of the last pruning)
   const bool pr = c->prune_valid;
@@ -3804,7 +3804,7 @@ static int rebomos_lists_stale(mdp_ctx *c, bool &stale)
 {
   stale = false;
   if (!c->nall) return MDP_OK;
-  int *h = (int *) (c->h_pinned + 24);
+  int *h = mdp_pin(c, kPinHostCheck);
   if (!c->md && c->host_check_armed) { // host mode: launched behind the upload, which has waited for it already
     c->host_check_armed = false;
     stale = h[0] != 0;
@@ -3863,7 +3863,7 @@ static void launch_centre3(mdp_ctx *c, int eflag, int vflag, int part)
     // kernel's list; once centres do overflow they are collected on a list of their own ...
     const int q = (part == 1 ? 2 : 0) + elem; // (a launch over both halves collects on the interior half's list)
     int *list = c->ovf.p + (size_t) (q + 1) * c->ovf_stride + 1; // (count at list[-1]; zeroed with the accumulators)
-    int *h_cnt = (int *) (c->h_pinned + 40) + 4 * c->ovf_par + q;
+    int *h_cnt = mdp_pin(c, kPinOvf) + 4 * c->ovf_par + q;
     if (*h_cnt > 0) c->ovf3_hot[q] = 64;      // (hysteresis: stay in list mode for 64 computes after the last overflow)
     else if (c->ovf3_hot[q] > 0) c->ovf3_hot[q]--;
     const bool list_mode = c->ovf3_hot[q] > 0;
@@ -3999,7 +3999,7 @@ static bool lj_queue_mode(mdp_ctx *c)
   const int forced = fe ? (atoi(fe) != 0 ? 1 : 0) : -1;
   bool on = false;
   if (c->lj_tiled && c->cluster == 2 && c->ntile > 0 && forced != 0) {
-    const int listed = *(const int *) (c->h_pinned + 45);
+    const int listed = *mdp_pin(c, kPinCubic);
     on = forced == 1 || (long long) listed * 8 > c->ntile;
   }
   const char *ce0 = getenv("MDP_LJ_QUEUE_CAP");
@@ -4097,7 +4097,7 @@ static int launch_lj_cubic(mdp_ctx *c, int eflag, int vflag)
   const bool pruned = c->prune_valid;
   const bool queue = c->lj_queue_now;
   if (queue) { // the queues the tile launches of this compute filled; tiles whose queues overflowed go on to the walk below
-    int *h_count = (int *) (c->h_pinned + 45);
+    int *h_count = mdp_pin(c, kPinCubic);
     long long want = (long long) *h_count + *h_count / 4 + 256;
     const int grid = (int) (want < c->ntile ? want : c->ntile);
     const bool ev = eflag || vflag;
@@ -4118,7 +4118,7 @@ static int launch_lj_cubic(mdp_ctx *c, int eflag, int vflag)
   // a workgroup per listed tile, from the count an earlier compute published (any grid covers the list: the kernel
   // strides over it; a crystal lists nothing and gets 256 workgroups that leave at once)
   // (queue mode: this walk only serves the tiles the queue kernel passed on -- normally none; its count has its own word)
-  int *h_count = (int *) (c->h_pinned + (queue ? 47 : 45));
+  int *h_count = mdp_pin(c, queue ? kPinCubicWalk : kPinCubic);
   long long want = (long long) *h_count + *h_count / 4 + 256;
   const int grid = (int) (want < c->ntile ? want : c->ntile);
   const int *fix_list = c->ovf.p + (size_t) (queue ? 6 : 5) * c->ovf_stride;
@@ -4184,8 +4184,8 @@ static int launch_centres(mdp_ctx *c, int eflag, int vflag, int parts, int which
     rebo_centre_general_kernel<false><<<grid, 256, 0, st>>>(c->rebomos, c->ovf.p, -1, c->nlocal, c->xq.p,
                                                             c->cand_off.p, c->cand.p, c->amask.p, c->fnbr.p,
                                                             c->fown.p, nullptr, nullptr, c->acc.p, c->flags.p,
-                                                            eflag, vflag, (int *) (c->h_pinned + 40) + 4 * c->ovf_par,
-                                                            c->ovf_stride, (int *) (c->h_pinned + 44));
+                                                            eflag, vflag, mdp_pin(c, kPinOvf) + 4 * c->ovf_par,
+                                                            c->ovf_stride, mdp_pin(c, kPinGeneral));
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }
