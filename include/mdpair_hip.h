@@ -521,6 +521,45 @@ int mdp_langevin_run(mdp_ctx *ctx, long long first, long long last);
 int mdp_langevin_tally(mdp_ctx *ctx, double *out);
 int mdp_langevin_off(mdp_ctx *ctx);
 
+/* ---- FIRE minimiser on the device (LAMMPS min_style fire, FIRE 2.0 with the eulerimplicit integrator and LAMMPS' defaults)
+ * For a resident context on one rank, after mdp_md_setup + mdp_dd_setup (one brick) + mdp_dd_reneighbor.  An iteration
+ * is two small launches next to the force compute: per-block partial sums of v.f, v.v, f.f and the largest |v_c| in
+ * fixed slots, then one workgroup that adds them in a fixed order, takes the decisions of the iteration (and the stop
+ * tests of the one before) and leaves dtv, the mixing factors and the flags in device memory for the advance kernel.
+ * The host never waits for them: it polls a pinned stop word and may queue an iteration or two too many, which change
+ * nothing -- once the stop code is latched a queued advance kernel leaves x, v and the counters alone.
+ *   setup:   zeroes v, computes the initial energy and force norm.  The starting time step is the context's dt, which
+ *            is not changed.  Refused on a brick of several ranks and with a thermostat on the context (and the
+ *            thermostats and mdp_dd_setup with several ranks are refused while it is on); a deferred final half is
+ *            completed first.  ftol: sqrt(sum f.f) < ftol; etol (only when > 0): |E - Eprev| < etol (|E| + |Eprev| +
+ *            1e-8) / 2, tested only more than delaystep iterations after the last P <= 0.
+ *   iterate: queues up to n iterations (sums, control, advance, a reneighbouring when the device's displacement check
+ *            asked for one, the compute: force-only unless etol > 0); *stop = the stop code the host has seen so far.
+ *   state:   blocking.  out[MDP_FIRE_STATE_LEN] = [0] stop code [1] iterations [2] force evaluations [3] dt [4] alpha
+ *            [5] sqrt(sum f.f) of the current forces [6] initial [7] previous [8] last energy (with etol == 0 the previous
+ *            one is not known and repeats the last, which one energy compute gives; the forces are left as they
+ *            were) [9] reneighbourings since setup [10] dtv [11] dtv of the iteration before [12] s1 [13] s2 [14] mixed
+ *            (P > 0) [15] zeroed (P <= 0) [16] iteration of the last P <= 0 [17] number of P <= 0 [18] P [19] initial
+ *            sqrt(sum f.f) [20] displacement checks that found an atom beyond half the skin already (a late reneighbouring)
+ *   off:     back to the integrate kernels with the context's dt; v stays as the minimiser left it (zero it, or draw
+ *            new velocities, before a run). */
+enum { MDP_FIRE_RUNNING = 0, MDP_FIRE_FTOL = 1, MDP_FIRE_ETOL = 2, MDP_FIRE_MAXITER = 3, MDP_FIRE_MAXEVAL = 4 };
+#define MDP_FIRE_STATE_LEN 21
+typedef struct {
+  double etol, ftol;
+  long long maxiter, maxeval;
+  double dmax;                  /* 0.1  */
+  double tmax, tmin;            /* 10, 0.02: dt stays in [tmin, tmax] x the starting dt */
+  int delaystep;                /* 20   */
+  double dtgrow, dtshrink;      /* 1.1, 0.5   */
+  double alpha0, alphashrink;   /* 0.25, 0.99 */
+  int halfstepback, initialdelay; /* yes, yes */
+} mdp_fire_config;
+int mdp_fire_setup(mdp_ctx *ctx, const mdp_fire_config *cfg);
+int mdp_fire_iterate(mdp_ctx *ctx, long long n, int *stop);
+int mdp_fire_state(mdp_ctx *ctx, double *out);
+int mdp_fire_off(mdp_ctx *ctx);
+
 /* per-phase device time of the last compute in ms (HIP events on the compute stream):
  * rebomos: [0]=REBO centre kernels of the lane-group classes, [1]=the general kernel (centres that outgrew their lane
  * group since the list build), [2]=row pruning (0 unless one was due), [3]=LJ+gather kernel;

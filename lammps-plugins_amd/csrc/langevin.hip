@@ -127,6 +127,7 @@ extern "C" {
 int mdp_langevin_setup(mdp_ctx *c, const mdp_langevin_config *cfg)
 {
   if (!c || !cfg) return MDP_EINVAL;
+  if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_langevin_setup: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
   if (c->nhc.on)
     return mdp_fail(c, MDP_ESTATE, "mdp_langevin_setup: the Nose-Hoover chain (mdp_nhc_setup) is on; one thermostat per context");
   if ((cfg->zero || cfg->tally) && c->dd.on && c->dd.G.nranks > 1)

@@ -1099,7 +1099,10 @@ int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double
   // (the thermostat is opened, and its step counted, on a rank without owned atoms too)
   MdpStyleCheck sc;
   if (c->nlocal) mdp_sflag_arm(c, sc);
-  MDP_TRY(md_launch_advance(c, with_final, flag, trigsq, hardsq, sc, zero_f, dset, dclr));
+  if (c->fire.on) // (one rank, no thermostat, no final half pending: mdp_fire_setup saw to it)
+    MDP_TRY(mdp_fire_launch_advance(c, flag, trigsq, hardsq, sc, zero_f));
+  else
+    MDP_TRY(md_launch_advance(c, with_final, flag, trigsq, hardsq, sc, zero_f, dset, dclr));
   if (c->nlocal) {
     c->acc_prezeroed = sc.acc != nullptr;
     // the flag words are complete behind this kernel unless remote ghosts arrive later in the step (mdp_md_unpack_x)

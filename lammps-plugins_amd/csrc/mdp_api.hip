@@ -915,6 +915,9 @@ int mdp_destroy(mdp_ctx *c)
   c->nhc.part.release();
   c->lgv.st.release();
   c->lgv.part.release();
+  c->fire.st.release();
+  c->fire.part.release();
+  c->fire.fsave.release();
   if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
   delete c;
   return MDP_OK;

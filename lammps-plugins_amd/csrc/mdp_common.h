@@ -289,6 +289,43 @@ struct MdpLangevin {
   DevBuf<double> part;      // per-block partial sums (zero: 3 per block; tally: 1 per block)
 };
 static constexpr int kLgvG2 = 16, kLgvMean = 32, kLgvE = 35, kLgvElast = 36, kLgvWords = 37;
+// FIRE minimiser (fire.hip): the control block lives in st on the device; the host keeps the configuration and what it
+// has queued.  Control block, in doubles (flags and counters as whole numbers):
+enum MdpFireWord {
+  kFireDtv = 0,   // the step of this iteration (dt, shortened by dmax)
+  kFireDtvPrev,   // ... of the iteration before (halfstepback)
+  kFireS1,        // mixing: v = s1 v + s2 f
+  kFireS2,
+  kFireMix,       // 1: P > 0 in this iteration
+  kFireZero,      // 1: P <= 0 in this iteration (half step back, v = 0)
+  kFireDt,
+  kFireAlpha,
+  kFireIter,      // iterations done (the one in flight included once its control kernel has run)
+  kFireLastNeg,   // iteration of the last P <= 0
+  kFireNneg,      // number of P <= 0 so far
+  kFireFF,        // sum f.f as the last control kernel saw it (the forces of the iteration before)
+  kFireStop,      // latched MDP_FIRE_* stop code, 0 while running
+  kFireNeval,     // force evaluations of the iterations
+  kFireEprev,     // energies of the last two evaluations (etol > 0)
+  kFireElast,
+  kFireVdotF,     // P of this iteration
+  kFireFFnow,     // sum f.f of the current forces (a state read refreshes it)
+  kFireWords
+};
+struct MdpFire {
+  bool on = false;
+  mdp_fire_config cfg;
+  double dt0 = 0.0;            // the time step the minimisation started from (dtmax = tmax dt0, dtmin = tmin dt0)
+  double e_initial = 0.0, fnorm_initial = 0.0;
+  double e_cache = 0.0;        // etol == 0: the energy of the last state read ...
+  long long e_cache_iter = -1; // ... and the iteration it belongs to
+  long long reneighbors0 = 0;  // MdpDomain::reneighbors at setup
+  long long late = 0;          // displacement checks that saw an atom beyond half the skin already
+  DevBuf<double> st;           // [kFireWords]
+  DevBuf<double> part;         // per-block partials: 3 sums per block, then one maximum per block
+  DevBuf<double> fsave;        // a state read's energy compute leaves the forces as it found them
+};
+
 // what the integrate kernels need to add the Langevin force of one step (md.hip nve_advance_kernel / nve_final_kernel)
 struct MdpLgvArgs {
   const int *tag = nullptr, *type = nullptr, *perm = nullptr; // owned atom i: tag[perm ? perm[i] : i], same for type
@@ -595,6 +632,7 @@ struct mdp_ctx {
   hipEvent_t ev_sflag[2] = {nullptr, nullptr};
   MdpNhc nhc;                      // thermostat of the integrate calls (mdp_nhc_setup)
   MdpLangevin lgv;                 // Langevin thermostat of the integrate calls (mdp_langevin_setup)
+  MdpFire fire;                    // FIRE minimiser: mdp_md_advance launches its advance kernel while it is on (mdp_fire_setup)
   bool final_pending = false;      // the host deferred the final half-kick of the finished step (mdp_md_defer_final)
   bool final_deferred_seen = false; // the host uses mdp_md_defer_final at all (older hosts: with_final is authoritative)
   bool acc_prezeroed = false; // the integrate kernel reset the accumulators: the next mdp_acc_begin launches nothing
@@ -670,9 +708,11 @@ enum MdpPin {
   kPinCubic = 45,     // 1 int: tiles listed for the cubic Lennard-Jones spline (the cubic / queue kernels write; sizes later grids)
   kPinGlob = 46,      // 1 int: some rank's owned atom moved (unpack_x_kernel writes; mdp_dd_comm_step_begin reads behind ev_glob_ref)
   kPinCubicWalk = 47, // 1 int: queue mode, tiles whose queues overflowed (rebo_lj_cubic_kernel writes; sizes later grids)
+  kPinFire = 48,      // 3 doubles: the minimiser's stop code, iteration count and sum f.f (fire_control_kernel writes; mdp_fire_iterate
+                      //         polls the stop code without waiting: it is valid once a later kernel's event has been waited for)
   kPinWords = 64
 };
-static_assert(kPinCubicWalk < kPinWords, "the last pinned word must fit the allocation");
+static_assert(kPinFire + 3 <= kPinWords, "the last pinned word must fit the allocation");
 inline int *mdp_pin(const mdp_ctx *c, MdpPin word) { return (int *) (c->h_pinned + word); }
 
 // The constants of a velocity-Verlet step, for a resident context (mdp_md_setup) and a host-linked one (mdp_hnve_setup)
@@ -773,6 +813,9 @@ int mdp_nhc_final(mdp_ctx *c);
 // counter when `initial`.  _close: behind that kernel (the tally of the step).
 int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvArgs *L);
 int mdp_lgv_close(mdp_ctx *c, const MdpLgvArgs &L);
+// FIRE minimiser (fire.hip), in place of the integrate kernel when c->fire.on: the half step back / zeroing and the Euler
+// step of the iteration whose control kernel was queued last, with the same votes, accumulator reset and force clear
+int mdp_fire_launch_advance(mdp_ctx *c, int *flag, double trigsq, double hardsq, const MdpStyleCheck &sc, bool zero_f);
 void mdp_host_add(double *dst, const double *src, size_t n); // dst += src, threaded for large arrays
 int mdp_host_download_add(mdp_ctx *c, double *h_dst, double *h_stage, const double *d_src, size_t n); // chunked D2H + add
 int mdp_to_host_order(mdp_ctx *c, int n, int w, const double *d_src, double *d_dst);   // per-atom arrays, device -> host order

@@ -60,6 +60,15 @@ class LangevinConfig(C.Structure):
     _fields_ = [("t_start", C.c_double), ("t_stop", C.c_double), ("t_period", C.c_double), ("seed", C.c_int),
                 ("zero", C.c_int), ("tally", C.c_int), ("boltz", C.c_double), ("mvv2e", C.c_double),
                 ("ratio", C.c_double * 16), ("natoms", C.c_longlong)]
+class FireConfig(C.Structure):
+    _fields_ = [("etol", C.c_double), ("ftol", C.c_double), ("maxiter", C.c_longlong), ("maxeval", C.c_longlong),
+                ("dmax", C.c_double), ("tmax", C.c_double), ("tmin", C.c_double), ("delaystep", C.c_int),
+                ("dtgrow", C.c_double), ("dtshrink", C.c_double), ("alpha0", C.c_double), ("alphashrink", C.c_double),
+                ("halfstepback", C.c_int), ("initialdelay", C.c_int)]
+FIRE_STATE_LEN = 21
+FIRE_STOP = {0: "running", 1: "force tolerance", 2: "energy tolerance", 3: "max iterations", 4: "max force evaluations"}
+FIRE_DEFAULTS = dict(dmax=0.1, tmax=10.0, tmin=0.02, delaystep=20, dtgrow=1.1, dtshrink=0.5, alpha0=0.25,
+                     alphashrink=0.99, halfstepback=True, initialdelay=True)   # LAMMPS min_modify defaults for fire
 BOLTZ_METAL = 8.617343e-5    # force->boltz, metal units
 
 
@@ -87,6 +96,7 @@ EXPORTS = [
     "mdp_md_defer_final", "mdp_md_list_state", "mdp_md_aeam_force_begin", "mdp_md_aeam_state", "mdp_dd_comm_aeam_exchange_begin", "mdp_dd_comm_aeam_exchange_end",
     "mdp_nhc_setup", "mdp_nhc_run", "mdp_nhc_state", "mdp_nhc_set_state", "mdp_nhc_off",
     "mdp_langevin_setup", "mdp_langevin_run", "mdp_langevin_tally", "mdp_langevin_off",
+    "mdp_fire_setup", "mdp_fire_iterate", "mdp_fire_state", "mdp_fire_off",
 ]
 
 
@@ -533,6 +543,40 @@ class Context:
 
     def langevin_off(self):
         self._ck(self.L.mdp_langevin_off(self.h))
+
+    # ---------------- FIRE minimiser of a resident one-brick context (minimize/mdp)
+    def fire_setup(self, etol, ftol, maxiter, maxeval, **modify):
+        """modify: the min_modify values of FIRE_DEFAULTS"""
+        unknown = set(modify) - set(FIRE_DEFAULTS)
+        if unknown:
+            raise ValueError(f"fire_setup: unknown setting(s) {sorted(unknown)}")
+        m = dict(FIRE_DEFAULTS, **modify)
+        cfg = FireConfig(etol, ftol, int(maxiter), int(maxeval), m["dmax"], m["tmax"], m["tmin"], int(m["delaystep"]),
+                         m["dtgrow"], m["dtshrink"], m["alpha0"], m["alphashrink"], int(bool(m["halfstepback"])),
+                         int(bool(m["initialdelay"])))
+        self._ck(self.L.mdp_fire_setup(self.h, C.byref(cfg)))
+
+    def fire_iterate(self, n):
+        """queues up to n iterations; the stop code the host has seen so far (0: running)"""
+        stop = C.c_int(0)
+        self._ck(self.L.mdp_fire_iterate(self.h, C.c_longlong(int(n)), C.byref(stop)))
+        return stop.value
+
+    def fire_state(self):
+        """blocking: the minimiser's state (mdpair_hip.h, mdp_fire_state) as a dict"""
+        out = np.zeros(FIRE_STATE_LEN)
+        self._ck(self.L.mdp_fire_state(self.h, _dp(out)))
+        keys = ("stop", "iterations", "evaluations", "dt", "alpha", "fnorm", "e_initial", "e_previous", "e_final",
+                "reneighbors", "dtv", "dtv_prev", "s1", "s2", "mixed", "zeroed", "last_negative", "negatives", "vdotf",
+                "fnorm_initial", "late")
+        d = dict(zip(keys, (float(v) for v in out)))
+        for k in ("stop", "iterations", "evaluations", "reneighbors", "mixed", "zeroed", "last_negative", "negatives", "late"):
+            d[k] = int(d[k])
+        d["criterion"] = FIRE_STOP[d["stop"]]
+        return d
+
+    def fire_off(self):
+        self._ck(self.L.mdp_fire_off(self.h))
 
     def md_class_stats(self):
         """how the last compute's work was spread over the kernel classes (see mdpair_hip.h)"""

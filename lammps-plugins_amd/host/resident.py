@@ -425,6 +425,32 @@ class DeviceDomain:
         self.flush()
         return self.ctx.langevin_tally()
 
+    def minimize(self, etol, ftol, maxiter, maxeval, chunk=64, **modify):
+        """FIRE minimisation (LAMMPS min_style fire with its defaults; **modify: capi.FIRE_DEFAULTS) of this domain on the
+        device, one GPU only; returns the final state (capi.Context.fire_state).  The velocities are zero afterwards
+        up to what the last iteration left; the time step of the domain is unchanged."""
+        if self.world > 1:
+            raise ValueError("the minimiser runs on one GPU only (its sums would need an all-reduce per iteration)")
+        self.flush()
+        ctx = self.ctx
+        ctx.fire_setup(etol, ftol, maxiter, maxeval, **modify)
+        try:
+            left = int(maxiter) + 2        # (the stop code is seen an iteration or two late; extra iterations change nothing)
+            while left > 0 and not ctx.fire_iterate(min(chunk, left)):
+                left -= min(chunk, left)
+            st = ctx.fire_state()
+        finally:
+            ctx.fire_off()
+        self._after_device_reneighbors(st["reneighbors"])
+        return st
+
+    def _after_device_reneighbors(self, n):
+        """the library reneighboured on its own (the minimiser): the brick's counts as they are now"""
+        info = self.ctx.dd_info()
+        self.nlocal, self.nself, self.nsend, self.nrecv = info["nlocal"], info["nself"], info["nsend"], info["nrecv"]
+        self.nghost = self.nself + self.nrecv
+        self.builds += int(n)
+
     def tune_overlap(self, max_steps=80):
         """library transport: force-only steps until the library's overlap-policy trial has chosen (comm_rccl.hip); returns
         the step info.  Collective: every rank runs the same steps."""

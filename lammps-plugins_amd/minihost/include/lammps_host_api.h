@@ -160,6 +160,7 @@ class Update { // the members of LAMMPS' Update a fix style reads
 class Output { // next step on which the host prints thermo / writes dumps (whichever comes first)
  public:
   bigint next = 0, next_thermo = 0;
+  int thermo_every = 0; // `thermo N`
 };
 
 class NeighList {
@@ -309,6 +310,13 @@ class Fix : protected Pointers {
   virtual void reset_dt() {}
   virtual double compute_scalar() { return 0.0; } // thermo f_ID
   virtual void *extract(const char *, int &) { return nullptr; } // what a fix hands another one (Fix::extract)
+};
+
+// a command style (command.h of the 2 Aug 2023 release): one object per use of the input word, command() runs it
+class Command : protected Pointers {
+ public:
+  explicit Command(LAMMPS *lmp) : Pointers(lmp) {}
+  virtual void command(int, char **) = 0;
 };
 
 // the part of LAMMPS' Modify a fix style reads: the fixes in the order of their definition

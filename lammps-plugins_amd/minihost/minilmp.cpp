@@ -31,6 +31,7 @@
 #include <functional>
 #include <iostream>
 #include <map>
+#include <memory>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -274,6 +275,7 @@ struct Host {
   // registry of plugin styles
   std::map<std::string, lammpsplugin_factory1 *> pair_styles;
   std::map<std::string, lammpsplugin_factory2 *> fix_styles;
+  std::map<std::string, lammpsplugin_factory1 *> command_styles;
   std::vector<void *> handles;
 
   // box: lo, prd, tilt (xy,xz,yz)
@@ -1448,9 +1450,16 @@ struct Script {
     if (c == "units") {
       need(2);
       if (w[1] != "metal") H.error.all(FLERR, "minilmp supports units metal only");
-    } else if (c == "atom_style" || c == "dimension" || c == "boundary" || c == "atom_modify" || c == "echo" ||
+    } else if (c == "boundary") {
+      // the host's own ghosts and lists stay periodic (fixed behaviour: p p p); the flags are kept for the styles that ask
+      // Domain for them and refuse a box that is not periodic
+      need(4);
+      H.domain.xperiodic = w[1] == "p";
+      H.domain.yperiodic = w[2] == "p";
+      H.domain.zperiodic = w[3] == "p";
+    } else if (c == "atom_style" || c == "dimension" || c == "atom_modify" || c == "echo" ||
                c == "log" || c == "dump" || c == "dump_modify" || c == "restart" || c == "comm_modify") {
-      // accepted, fixed behaviour: atomic, 3d, p p p
+      // accepted, fixed behaviour: atomic, 3d
     } else if (c == "newton") {
       need(2);
       H.force.newton_pair = (w[1] == "on");
@@ -1558,7 +1567,7 @@ struct Script {
       void *sym = dlsym(dso, "lammpsplugin_init");
       if (!sym) H.error.all(FLERR, "Plugin symbol lookup failure in file " + w[2] + ": lammpsplugin_init");
       H.handles.push_back(dso);
-      const size_t before = H.pair_styles.size() + H.fix_styles.size();
+      const size_t before = H.pair_styles.size() + H.fix_styles.size() + H.command_styles.size();
       // registration callback: the host behind the LAMMPS* it is handed
       struct Trampoline {
         static void regfunc(lammpsplugin_t *p, void *lmp)
@@ -1566,8 +1575,9 @@ struct Script {
           Host *host = g_host;
           if (!host || lmp != (void *) &host->lmp || !p || !p->style || !p->name) return;
           const bool is_pair = strcmp(p->style, "pair") == 0, is_fix = strcmp(p->style, "fix") == 0;
-          if (!is_pair && !is_fix) {
-            fprintf(stderr, "WARNING: plugin style %s/%s ignored (minilmp hosts pair and fix styles only)\n", p->style, p->name);
+          const bool is_command = strcmp(p->style, "command") == 0;
+          if (!is_pair && !is_fix && !is_command) {
+            fprintf(stderr, "WARNING: plugin style %s/%s ignored (minilmp hosts pair, fix and command styles only)\n", p->style, p->name);
             return;
           }
           if (strcmp(p->version, LAMMPS_VERSION) != 0)
@@ -1578,13 +1588,15 @@ struct Script {
             return;
           }
           if (is_pair) host->pair_styles[p->name] = p->creator.v1;
+          else if (is_command) host->command_styles[p->name] = p->creator.v1;
           else host->fix_styles[p->name] = p->creator.v2;
           printf("Loading plugin: %s by %s\n", p->info, p->author);
         }
       };
       g_host = &H;
       reinterpret_cast<lammpsplugin_initfunc>(sym)(&H.lmp, dso, (void *) &Trampoline::regfunc);
-      printf("Loaded %zu plugins from %s\n", H.pair_styles.size() + H.fix_styles.size() - before, w[2].c_str());
+      printf("Loaded %zu plugins from %s\n", H.pair_styles.size() + H.fix_styles.size() + H.command_styles.size() - before,
+             w[2].c_str());
     } else if (c == "pair_style") {
       need(2);
       if (!H.pair_styles.count(w[1])) H.error.all(FLERR, "Unrecognized pair style '" + w[1] + "' (load its plugin first)");
@@ -1711,6 +1723,23 @@ struct Script {
     } else if (c == "run") {
       need(2);
       H.run(std::stol(w[1]));
+    } else if (H.command_styles.count(c)) { // a command style from a plugin: the host's state as LAMMPS::init() leaves it
+      if (H.pair) H.pair->init();
+      H.force.pair = H.pair;
+      H.update.dt = H.dt;
+      H.update.ntimestep = H.step;
+      H.output.thermo_every = H.thermo_every;
+      H.skin = H.neighbor.skin;
+      H.sync_domain();
+      if (H.box_exists && !H.multi()) {
+        H.wrap_owned();
+        H.set_vviews();
+      }
+      std::unique_ptr<Command> cmd(static_cast<Command *>(H.command_styles[c](&H.lmp)));
+      std::vector<char *> args;
+      for (size_t k = 1; k < w.size(); k++) args.push_back(const_cast<char *>(w[k].c_str()));
+      cmd->command((int) args.size(), args.data());
+      H.step = (long) H.update.ntimestep; // (a following `run` starts from the atoms and the step the command left)
     } else
       H.error.all(FLERR, "Unknown command: " + raw);
   }

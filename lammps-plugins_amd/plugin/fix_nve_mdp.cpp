@@ -49,6 +49,7 @@
    migration); against a real LAMMPS this mode is unverified.
 -------------------------------------------------------------------------------------------------- */
 #include "fix_nve_mdp.h"
+#include "mdp_brick.h"
 
 #include "atom.h"
 #include "atom_vec.h"
@@ -209,42 +210,8 @@ void FixNVEMDP::setup_steps()
 {
   if (!bricks) return;
   int dim = 0;
-  const int n = atom->nlocal;
-  const double skin = neighbor->skin, cutghost = force->pair->cutforce + skin;
-  mdp_md_config cfg;
-  memset(&cfg, 0, sizeof cfg);
-  cfg.style = style_id;
-  cfg.nlocal = n;
-  cfg.ntypes = atom->ntypes;
-  cfg.skin = skin;
-  cfg.dt = update->dt;
-  cfg.ftm2v = force->ftm2v;
-  cfg.mvv2e = force->mvv2e;
-  // provisional bounds (the library sets the brick's at every reneighboring): the box's Cartesian hull + the ghost shell
-  const double *h = domain->h; // xprd, yprd, zprd, yz, xz, xy
-  cfg.bbox_lo[0] = domain->boxlo[0] + fmin(0.0, h[5]) + fmin(0.0, h[4]) - cutghost - 2.0;
-  cfg.bbox_hi[0] = domain->boxlo[0] + h[0] + fmax(0.0, h[5]) + fmax(0.0, h[4]) + cutghost + 2.0;
-  cfg.bbox_lo[1] = domain->boxlo[1] + fmin(0.0, h[3]) - cutghost - 2.0;
-  cfg.bbox_hi[1] = domain->boxlo[1] + h[1] + fmax(0.0, h[3]) + cutghost + 2.0;
-  cfg.bbox_lo[2] = domain->boxlo[2] - cutghost - 2.0;
-  cfg.bbox_hi[2] = domain->boxlo[2] + h[2] + cutghost + 2.0;
   const int *map = style_id == 1 ? static_cast<int *>(force->pair->extract("mdp_map", dim)) : nullptr;
-  const int idummy = 0;
-  const double ddummy[3] = {0, 0, 0};
-  const double xdummy[3] = {0, 0, 0};
-  if (mdp_md_setup(bctx, &cfg, n ? atom->x[0] : xdummy, n ? atom->v[0] : xdummy, atom->type, atom->tag, atom->mass, map, &idummy,
-                   ddummy, &idummy, &idummy) != MDP_OK)
-    fail(bctx);
-  mdp_dd_config dd;
-  memset(&dd, 0, sizeof dd);
-  for (int d = 0; d < 3; d++) {
-    dd.boxlo[d] = domain->boxlo[d];
-    dd.procgrid[d] = comm->procgrid[d];
-  }
-  for (int k = 0; k < 6; k++) dd.h[k] = h[k];
-  dd.rank = comm->me;
-  dd.cutghost = cutghost;
-  if (mdp_dd_setup(bctx, &dd) != MDP_OK) fail(bctx);
+  if (mdp_brick_from_host(bctx, style_id, map, atom, domain, force, neighbor, update, comm) != MDP_OK) fail(bctx);
   if (comm->nprocs == 1) { // one brick: its periodic images are the library's, no communicator
     if (mdp_dd_reneighbor(bctx) != MDP_OK) fail(bctx);
     if (mdp_md_compute(bctx, 0, 0) != MDP_OK) fail(bctx);
@@ -280,16 +247,7 @@ void FixNVEMDP::setup_steps()
 // the atoms the brick owns NOW, in the brick's order, into the host's arrays
 void FixNVEMDP::bricks_to_host()
 {
-  long long di[8];
-  if (mdp_dd_info(bctx, di, nullptr, nullptr) != MDP_OK) fail(bctx);
-  const int n = (int) di[0];
-  if (n + atom->nghost > atom->nmax) atom->avec->grow(n + atom->nghost); // (the host's idle passes over its stale ghosts stay inside)
-  if (n) {
-    if (mdp_md_download(bctx, atom->x[0], atom->v[0], nullptr, nullptr) != MDP_OK) fail(bctx);
-    if (mdp_md_download_int(bctx, "tag", atom->tag) != MDP_OK) fail(bctx);
-    if (mdp_md_download_int(bctx, "type", atom->type) != MDP_OK) fail(bctx);
-  }
-  atom->nlocal = n;
+  if (mdp_brick_to_host(bctx, atom) != MDP_OK) fail(bctx);
   downloads++;
 }
 
