@@ -415,6 +415,12 @@ class DeviceDomain:
                                 boltz=S.BOLTZ, mvv2e=S.MVV2E)
         self.ctx.langevin_run(first, last)
 
+    def langevin_run(self, first, last):
+        """another run (and ramp) of the thermostat that is on; a deferred final half completes inside mdp_langevin_run,
+        with the force of the run it belongs to"""
+        self.ctx.langevin_run(first, last)
+        self._final_pending = False
+
     def langevin_off(self):
         """back to NVE; a deferred final half completes inside mdp_langevin_off, with its Langevin force"""
         self.ctx.langevin_off()

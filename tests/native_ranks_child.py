@@ -51,14 +51,17 @@ def _by_tag(dom, want):
     return dom.tags_local, {k: got[k] for k in want}
 
 
-def _trajectory(world, style, s, v0, steps, native, thermo_at=()):
+def _trajectory(world, style, s, v0, steps, native, thermo_at=(), langevin=None):
     """NVE, reneighboring decided by the run itself: one rank reads its deferred on-device flag ("auto"), the native
-    ranks the word that travelled with the previous step's halo ("halo")."""
+    ranks the word that travelled with the previous step's halo ("halo").  langevin: (Tstart, Tstop, damp, seed) of a
+    Langevin thermostat over the run's steps."""
 
     def rank_fn(r, make_tr):
         ctx, st, cutghost, skin, map_ = _ctx(style)
         tr = make_tr(ctx) if world > 1 else None
         d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0, transport=tr)
+        if langevin is not None:
+            d.langevin(*langevin, first=0, last=steps)
         d.compute(0, 0)
         rows = []
         for step in range(1, steps + 1):
@@ -113,20 +116,20 @@ def _compare(s, one, many):
 _ONE = {}
 
 
-def _one_rank(style, pure, steps, thermo_at):
-    key = (style, pure, steps, tuple(thermo_at))
+def _one_rank(style, pure, steps, thermo_at, langevin=None):
+    key = (style, pure, steps, tuple(thermo_at), langevin)
     if key not in _ONE:
         s, v0 = _system(style, pure)
-        _ONE[key] = (s, v0, _trajectory(1, style, s, v0, steps, False, thermo_at))
+        _ONE[key] = (s, v0, _trajectory(1, style, s, v0, steps, False, thermo_at, langevin))
     return _ONE[key]
 
 
-def case_steps(style, world, pure=False):
+def case_steps(style, world, pure=False, langevin=None):
     """hot drifting system: reneighborings (with migration between the bricks) decided by the flag in the halo,
     aeam's fp / ghost-force exchange behind the interior tiles, prunings that send single ranks down the blocking order"""
     steps, thermo_at = (60, (20, 40)) if style == "rebomos" else (48, (16, 32))
-    s, v0, one = _one_rank(style, pure, steps, thermo_at)
-    many = _trajectory(world, style, s, v0, steps, True, thermo_at)
+    s, v0, one = _one_rank(style, pure, steps, thermo_at, langevin)
+    many = _trajectory(world, style, s, v0, steps, True, thermo_at, langevin)
     return _compare(s, one, many)
 
 
@@ -221,13 +224,21 @@ CASES = {
 }
 
 
+# asked for by name (tests/test_gpu_langevin_mdp.py): the same steps under a Langevin thermostat that heats the system --
+# the only place where mdp_dd_comm_step_begin(with_final = 1) meets the thermostat
+LANGEVIN = (300.0, 900.0, 0.05, 48271)
+NAMED = {f"langevin_{style}_{world}": (lambda style=style, world=world: case_steps(style, world, langevin=LANGEVIN))
+         for style in ("rebomos", "aeam") for world in (2, 4)}
+
+
 def main():
     out_path, names = sys.argv[1], sys.argv[2:] or list(CASES)
+    cases = {**CASES, **NAMED}
     results = {}
     for name in names:
         t0 = time.time()
         try:
-            results[name] = CASES[name]()
+            results[name] = cases[name]()
         except BaseException as e:  # noqa: BLE001 -- reported per case
             results[name] = {"error": f"{type(e).__name__}: {e}", "trace": traceback.format_exc()}
         print(f"[native ranks] {name}: {time.time() - t0:.1f} s", file=sys.stderr, flush=True)

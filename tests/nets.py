@@ -42,6 +42,8 @@ SUITE = {
     "minilmp": [(2, 6)],
     "trajectory": [(1, 12)],
     "block": [(1, 8)],
+    "fire": [(4, 16)],
+    "langevin": [(42, 14)],
 }
 
 
@@ -691,6 +693,322 @@ def line_block(spec, err):
             f"prunings {err['prunings']} late {err['late']} builds {err['builds']}")
 
 
+# --------------------------------------------------------------------------------------------------------------- fire
+# The FIRE minimiser under random `min_modify` settings: every setting from a short list that holds the default, each
+# value that makes a branch degenerate (delaystep 0, dtgrow 1, dtshrink 1, alphashrink 1, tmax 1, tmin 1) and one other;
+# halfstepback and initialdelay on or off; starting time steps of 1, 2 and 4 fs; the small cells of both styles with more
+# jitter and strain.  80 device iterations REPLAYED one at a time (tests/firerig.py): decisions, dt and alpha exact; dtv,
+# s1, s2, x and v to 1e-13; and the forces of every iteration against the oracle's at the downloaded positions (1e-9
+# eV/A), so a pair the advance kernel's displacement prediction misses shows in the iteration it happens.
+# The ceiling of the time step (tmax dt) is kept at or below 10 fs: beyond it fireref with oracle forces itself blows up.
+# Measured on an MI355X (seed 4, 16 cases; 200 more at seed 11): x 3.6e-15 A, v 3.5e-15, dtv / s1 / s2
+# 5.4e-16, forces 5.4e-13 eV/A over all cases; the device sits orders below the limits, which stay where they are.
+FIRE_MODIFY = dict(dmax=(0.1, 0.02, 0.005), tmax=(10.0, 2.0, 1.0), tmin=(0.02, 0.5, 1.0), delaystep=(20, 0, 3, 8),
+                   dtgrow=(1.1, 1.0, 1.3), dtshrink=(0.5, 0.9, 1.0), alpha0=(0.25, 0.05, 0.6), alphashrink=(0.99, 0.9, 1.0),
+                   halfstepback=(True, False), initialdelay=(True, False))
+FIRE_ITERATIONS = 80
+FIRE_SKIPPED = {}     # (id, seed) -> iterations not replayed, of the cases run in this process (a record, not a limit)
+
+
+def draw_fire(rng):
+    style = rng.choice(["rebomos", "aeam"])
+    jitter, scale, sd = rng.choice([0.05, 0.15, 0.3]), rng.choice([1.0, 1.06]), rng.randrange(1, 10**6)
+    dt = rng.choice([0.001, 0.002, 0.004])
+    modify = {k: rng.choice(v) for k, v in FIRE_MODIFY.items()}
+    if modify["tmax"] * dt > 0.0101:
+        # The ceiling of the time step stays at or below 10 fs, what the defaults give at 1 fs.  Beyond it FIRE is no
+        # minimiser for these potentials: with oracle forces fireref itself blows up (atoms fly hundreds of A at a
+        # ceiling of 20 or 40 fs), and forces of 1e5 eV/A cannot be held to 1e-9.  The other values of tmax stay.
+        modify["tmax"] = 2.0
+    odd = [f"{k}{int(v) if isinstance(v, bool) else v}" for k, v in modify.items() if v != FIRE_MODIFY[k][0]]
+    return dict(style=style, jitter=jitter, scale=scale, seed=sd, dt=dt, modify=modify, niter=FIRE_ITERATIONS, env={},
+                id=f"{style}-dt{dt}-" + ("-".join(odd) or "defaults"))
+
+
+def trace_fire(spec):
+    """no GPU: fireref.minimize with ORACLE forces over the case's iterations; one row per iteration, for the corner
+    test of tests/test_net_draws.py: dict(iter, mixed, dt_before, dt, dtv, moved: the farthest an atom went so far)"""
+    import firerig
+    import fireref
+    s = firerig.cell(spec["style"], jitter=spec["jitter"], scale=spec["scale"], seed=spec["seed"])
+    orc_f = firerig.Forces(spec["style"], _res()["orc"], s)
+    x0 = S.wrap(s.box, s.x)
+    rows, last = [], dict(dt=spec["dt"], moved=0.0)
+
+    def fe(x):
+        o = orc_f(x, eflag=1)
+        return o["f_owned"], o["eng"]
+
+    def record(fire, _):
+        last["moved"] = max(last["moved"], float(np.sqrt(((fire.x - x0) ** 2).sum(axis=1)).max()))
+        rows.append(dict(iter=fire.iter, mixed=fire.mixed, dt_before=last["dt"], dt=fire.dt, dtv=fire.dtv, moved=last["moved"]))
+        last["dt"] = fire.dt
+    fireref.minimize(fe, x0, s.mass[s.type], spec["dt"], S.FTM2V, 0.0, 0.0, spec["niter"], 10 ** 9, record=record, **spec["modify"])
+    return rows
+
+
+def run_fire(spec):
+    import firerig
+    s = firerig.cell(spec["style"], jitter=spec["jitter"], scale=spec["scale"], seed=spec["seed"])
+    rig = firerig.Rig(spec["style"], s, _res()["orc"], dt=spec["dt"])
+    try:
+        rig.ctx.fire_setup(0.0, 0.0, firerig.BIG, firerig.BIG, **spec["modify"])
+        r = firerig.replay(rig, spec["niter"], modify=spec["modify"], forces=True)
+        st = rig.ctx.fire_state()
+    finally:
+        rig.close()
+    err = dict(exact=len(r["exact"]), ctl=r["ctl"], x=r["x"], v=r["v"], f=r["f"], skipped=r["skipped"], late=st["late"],
+               first_mismatch=r["exact"][:1], negatives=len(r["negatives"]), grown=r["grown"], limited=r["limited"], ceiling=r["ceiling"],
+               moved=r["moved"], reneighbors=st["reneighbors"])
+    FIRE_SKIPPED[spec["id"], spec["seed"]] = r["skipped"]
+    # (a case may skip one iteration in its 80; that the suite's cases together skip at most 1 in 100 is asserted over
+    # the whole suite by tests/test_gpu_fire_mdp.py)
+    return err, dict(exact=1, ctl=1e-13, x=1e-13, v=1e-13, f=1e-9, skipped=2, late=1)
+
+
+def line_fire(spec, err):
+    return (f"{spec['id']} jitter {spec['jitter']} scale {spec['scale']} seed {spec['seed']} x {err['x']:.1e} v {err['v']:.1e} "
+            f"dtv/s1/s2 {err['ctl']:.1e} dF {err['f']:.1e} P<=0 {err['negatives']} grown {err['grown']} at dtmax {err['ceiling']} "
+            f"dmax-limited {err['limited']} skipped {err['skipped']} moved {err['moved']:.2f} A reneighbourings {err['reneighbors']} "
+            f"late {err['late']}" + (f" MISMATCH {err['first_mismatch']}" if err["exact"] else ""))
+
+
+# ----------------------------------------------------------------------------------------------------------- langevin
+# The Langevin thermostat on every path that reaches the integrate kernel -- resident with the device's own check
+# ("resident"), resident through mdp_md_initial_integrate / mdp_md_final_initial_integrate with forced reneighbourings
+# ("resident-plain": the CHECK = false instantiations), host-linked (mdp_hnve_*, host reneighbourings) and 2 - 8 bricks
+# on the thread transport with a drift that makes atoms change owner -- against velocity Verlet + tests/langevinref.py
+# around the ORACLE (refloops.host_lgv): first steps below, across and above 2^32 (the second counter word
+# of the noise), time steps of 0.5 - 2 fs, targets that ramp up, down to 0 K or stay at 0 K, scale ratios, zero, tally,
+# thermo reads that complete a deferred final half or follow one that ran on its own, sizes whose last 256-atom block
+# varies, sheared alloy boxes.  Limits (from a CPU experiment with the reference, DESIGN.md section 5): positions 1e-9 A,
+# velocities 2e-8 A/ps, tally 1e-8 eV; bricks against the one-rank device run 1e-8 A, 1e-7 A/ps (the dd net's).
+# Measured on an MI355X (seed 42, 14 cases; 200 more at seed 11): 3.0e-13 A, 5.5e-12 A/ps, 1.3e-12 eV; bricks 2.1e-14 A,
+# 1.2e-12 A/ps from one rank.  Four to five orders below the limits, as the NVE nets are; the limits are the reference's, not the device's.
+LGV_PATHS = ("resident", "resident-plain", "hostlinked", "bricks")
+LGV_FIRST = (0, 1000, 2 ** 32 - 30, 2 ** 32 + 7, 5 * 2 ** 32)
+LGV_TEMPS = ((300.0, 300.0), (300.0, 900.0), (900.0, 2000.0), (3000.0, 0.0), (0.0, 0.0))
+LGV_RATIOS = {"none": None, "all": {1: 2.0, 2: 0.5}, "one": {2: 0.5}}
+LGV_SEED = 48271
+LGV_REBUILD = {"rebomos": 25, "aeam": 10}       # steps between the reference's list builds (skins 2.0 and 1.0 A)
+
+
+def draw_langevin(rng):
+    style = rng.choice(["rebomos", "aeam"])
+    path = rng.choice(LGV_PATHS)
+    first, nsteps = rng.choice(LGV_FIRST), rng.choice([40, 60, 100])
+    dt, damp = rng.choice([0.0005, 0.001, 0.002]), rng.choice([0.01, 0.05, 0.1])
+    t0, t1 = rng.choice(LGV_TEMPS)
+    ratio = rng.choice(["none", "all", "one"])
+    zero, tally = rng.random() < 0.5, rng.random() < 0.5
+    if style == "rebomos":
+        size = rng.choice([(1, 1, 1), (2, 1, 1), (3, 1, 1), (2, 2, 1)])
+        spec = dict(size=size, n=_rebo_n(size), frac=None, tilt=None, skin=2.0)
+    else:
+        size, frac = rng.choice([4, 5, 6, 7]), rng.choice([0.0, 0.03])
+        spec = dict(size=size, n=4 * size ** 3, frac=frac, tilt=None, skin=1.0)
+        if rng.random() < 0.5:   # a sheared (triclinic) box
+            spec["tilt"] = [rng.uniform(-0.06, 0.06) * 4.045 * size for _ in range(3)]
+    # thermo reads at random steps, the last step among them; True: the read finds the step's final half deferred and
+    # completes it, False: the final half ran on its own (f + f_L written back) before the read
+    reads = [(st, rng.random() < 0.5) for st in sorted(rng.sample(range(1, nsteps), rng.randint(1, 4))) + [nsteps]]
+    ranks, renb = rng.choice([2, 3, 4, 8]), rng.choice([3, 5, 8])
+    drift = [0, 0, 0]
+    while not any(drift):
+        drift = [rng.choice([-60, -30, 0, 25, 40, 70]) for _ in range(3)]
+    if path == "bricks":
+        zero = tally = False     # (they sum over all atoms every step: one rank only)
+    else:
+        ranks, drift = 1, [0, 0, 0]
+    spec.update(style=style, path=path, first=first, nsteps=nsteps, dt=dt, damp=damp, t0=t0, t1=t1, ratio=ratio, zero=zero,
+                tally=tally, reads=reads, ranks=ranks, drift=drift, renb=renb, seed=rng.randrange(1, 10**6), env={},
+                id=f"{style}-{path}{ranks if ranks > 1 else ''}-n{spec['n']}-first{first}-dt{dt}-T{t0:.0f}-{t1:.0f}")
+    return spec
+
+
+def _lgv_system(spec):
+    """the system, its start velocities (max(Tstart, 300) K, plus the drift) and the steps between forced list builds:
+    the drawn interval, shortened until an atom at the drift plus five thermal sigmas of the hottest target stays
+    inside 0.3 skin"""
+    af = _res()["af"]
+    if spec["style"] == "rebomos":
+        s = S.replicate(S.rebomos_bulk_cell(), spec["size"])
+    else:
+        s = S.fcc_cell(4.045, spec["size"], frac_type2=spec["frac"], seed=spec["seed"]); s.mass[1:3] = af.mass[:2]
+        if spec["tilt"] is not None:
+            nb = S.Box(s.box.lo.copy(), s.box.prd.copy(), np.array(spec["tilt"]))
+            s = S.System(nb, nb.lamda2x(s.box.x2lamda(s.x)), s.type, s.tag, s.mass)
+    assert s.n == spec["n"]
+    v0 = S.gaussian_velocities(s, max(spec["t0"], 300.0), seed=spec["seed"] + 1) + np.array(spec["drift"], dtype=float)
+    hot = max(spec["t0"], spec["t1"], 300.0)
+    vcap = float(np.sqrt((v0 ** 2).sum(axis=1)).max()) + 5.0 * np.sqrt(S.BOLTZ * hot / (float(s.mass[1:3].min()) * S.MVV2E))
+    safe = max(1, int(0.3 * spec["skin"] / (vcap * spec["dt"])))
+    return s, v0, safe
+
+
+def _lgv_context(style):
+    from lammps_plugins_amd.host import capi
+    R = _res()
+    ctx = capi.Context(0)
+    if style == "rebomos":
+        ctx.rebomos_set_params(R["rp"])
+        return ctx, capi.STYLE_REBOMOS, 3.0 * R["rp"].rcmax[0][0] + 2.0, [0, 0, 1]
+    ctx.aeam_set_tables(R["tabs"])
+    return ctx, capi.STYLE_AEAM, float(R["af"].cut_table(R["tabs"]).max()) + 1.0, None
+
+
+def _lgv_device(spec, s, v0, world, rebuild_every):
+    """the case on `world` resident bricks (threads beyond one).  rebuild_every None: the device's own check
+    (rebuild="auto"); a number: the integrate calls without the check, reneighbourings forced every so many steps.
+    Returns {step: (x, v by tag, tally, the rank that holds each tag)}, the atoms that changed owner, whether every tag
+    was held exactly once at every read, list builds, late checks."""
+    from lammps_plugins_amd.host import resident
+    reads = dict(spec["reads"])
+
+    def rank_fn(r, make_tr):
+        ctx, st, cutghost, map_ = _lgv_context(spec["style"])
+        try:
+            d = resident.DeviceDomain(ctx, st, s, cutghost, spec["skin"], map_, v0=v0, dt=spec["dt"],
+                                      transport=make_tr(ctx) if world > 1 else None)
+            d.langevin(spec["t0"], spec["t1"], spec["damp"], LGV_SEED, ratio=LGV_RATIOS[spec["ratio"]], zero=spec["zero"],
+                       tally=spec["tally"], first=spec["first"], last=spec["first"] + spec["nsteps"])
+            d.compute(1, 0)
+            out, left = {}, 0
+            for step in range(1, spec["nsteps"] + 1):
+                ev = step in reads
+                rb = "auto" if rebuild_every is None else step % rebuild_every == 0
+                d.step(1 if ev else 0, 0, rebuild=rb, defer_final=reads.get(step, True))
+                if rb is True:
+                    left += ctx.dd_info()["left_last"]
+                if ev:   # through the library, not DeviceDomain.flush: a deferred final half is completed by the read itself
+                    e = ctx.langevin_tally()
+                    got = ctx.md_download(d.nlocal, want=("x", "v"))
+                    out[step] = (d.tags_local.copy(), got["x"], got["v"], e)
+            return dict(out=out, left=left, builds=d.builds, late=d.dangerous)
+        finally:
+            ctx.close()
+
+    res = [rank_fn(0, None)] if world == 1 else resident.run_ranks(world, rank_fn)
+    dev, once = {}, True
+    for step in reads:
+        x, v, seen, owner = np.zeros((s.n, 3)), np.zeros((s.n, 3)), np.zeros(s.n, dtype=int), np.zeros(s.n, dtype=int)
+        for k, r in enumerate(res):
+            tags, xr, vr, _ = r["out"][step]
+            x[tags - 1], v[tags - 1], owner[tags - 1] = xr, vr, k
+            seen[tags - 1] += 1
+        once = once and bool(np.all(seen == 1))
+        dev[step] = (x, v, res[0]["out"][step][3], owner)
+    return dev, sum(r["left"] for r in res), once, res[0]["builds"], sum(r["late"] for r in res)
+
+
+def _lgv_hostlinked(spec, s, v0, rebuild_every):
+    """mdp_hnve_* with the thermostat: the images kept by the library, host reneighbourings (download, wrap, new atoms,
+    mdp_hnve_upload_v) every rebuild_every steps and earlier whenever mdp_hnve_initial reports `moved`.  REBO-MoS, and the
+    alloy on the library's own lists (mdp_aeam_device_lists): fp and the forces stay on the device, as under the plugin's
+    fix nve/mdp."""
+    import ctypes as C
+    import oracle_bindings as ob
+    from lammps_plugins_amd.host import capi
+    R = _res()
+    style, n, skin = spec["style"], s.n, spec["skin"]
+    cut = (R["P"].cut3rebo if style == "rebomos" else float(R["af"].cut_table(R["tabs"]).max())) + skin
+    c = capi.Context(0)
+
+    def upload(x, v):
+        xa, type_all, tag_all, _, _, nloc, _ = S.with_ghosts(S.System(s.box, x.copy(), s.type, s.tag, s.mass), cut)
+        c.set_atoms_host(nloc, xa, type_all, tag_all, 2, map_=[0, 0, 1] if style == "rebomos" else None)
+        c.set_skin(skin)
+        c.hnve_upload_v(v)
+
+    def compute():   # f == NULL: the forces' only reader is the device's integrator
+        if style == "rebomos":
+            c._ck(c.L.mdp_rebomos_compute_host(c.h, 0, 0, None, None, None, None, None))
+        else:
+            eng, vir = C.c_double(0.0), np.zeros(6)
+            c._ck(c.L.mdp_aeam_density_host(c.h, C.c_int(0), None, None, C.byref(eng), None))
+            c._ck(c.L.mdp_aeam_force_host(c.h, C.c_int(0), C.c_int(0), None, None, C.byref(eng), capi._dp(vir), None, None))
+    try:
+        if style == "rebomos":
+            c.rebomos_set_params(ob.product_rebomos_params(R["P"]))
+        else:
+            c.aeam_set_tables(R["tabs"]); c.aeam_device_lists(True)
+        c.set_box_host(s.box)
+        c.hnve_setup(spec["dt"], S.FTM2V, s.mass)
+        c.langevin_setup(spec["t0"], spec["t1"], spec["damp"], LGV_SEED, n, ratio=LGV_RATIOS[spec["ratio"]], zero=spec["zero"],
+                         tally=spec["tally"], boltz=S.BOLTZ, mvv2e=S.MVV2E)
+        c.langevin_run(spec["first"], spec["first"] + spec["nsteps"])
+        upload(S.wrap(s.box, s.x), v0)
+        assert c.host_ghosts_derived()
+        compute()
+        reads, dev, late_any, rebuilds = dict(spec["reads"]), {}, 0, 0
+        for step in range(1, spec["nsteps"] + 1):
+            moved, late = c.hnve_initial()
+            late_any += int(late)
+            if moved or step % rebuild_every == 0:   # the host reneighbours
+                got = c.hnve_download(n, want=("x", "v"))
+                upload(S.wrap(s.box, got["x"]), got["v"]); rebuilds += 1
+            compute()
+            c.hnve_final()
+            if step in reads:
+                got = c.hnve_download(n, want=("x", "v"))
+                dev[step] = (got["x"], got["v"], c.langevin_tally())
+    finally:
+        c.close()
+    return dev, late_any, rebuilds
+
+
+def run_langevin(spec):
+    import langevinref
+    import mdref
+    import refloops
+    R = _res()
+    s, v0, safe = _lgv_system(spec)
+    style, path, skin, nsteps = spec["style"], spec["path"], spec["skin"], spec["nsteps"]
+    forced = min(spec["renb"], safe)
+    ref_every = min(LGV_REBUILD[style], forced if path in ("resident-plain", "bricks") else safe)
+    make = ((lambda sy: mdref.RebomosCPU(R["orc"], R["P"], sy, skin=skin)) if style == "rebomos" else
+            (lambda sy: mdref.AeamCPU(R["orc"], R["T"], sy, skin=skin)))
+    lgv = langevinref.Langevin(spec["t0"], spec["t1"], spec["damp"], LGV_SEED, s.mass, spec["dt"], S.FTM2V, boltz=S.BOLTZ, mvv2e=S.MVV2E,
+                               ratio=LGV_RATIOS[spec["ratio"]], zero=spec["zero"], tally=spec["tally"])
+    host = refloops.host_lgv(make, s, v0, nsteps, dict(spec["reads"]), ref_every, lgv, dt=spec["dt"], first=spec["first"], skin=skin)
+    err, lim = dict(builds="-", migrated="-"), dict(dx=1e-9, dv=2e-8, de=1e-8)
+    if path == "hostlinked":
+        dev, late, rebuilds = _lgv_hostlinked(spec, s, v0, ref_every)
+        err.update(dangerous=late, builds=rebuilds); lim.update(dangerous=1)
+    else:
+        dev, left, once, builds, late = _lgv_device(spec, s, v0, spec["ranks"], None if path == "resident" else forced)
+        err.update(builds=builds, late=late); lim.update(late=1)
+        if path == "bricks":   # and against the one-rank device run of the same case; atoms changed owner, none lost or doubled
+            one = _lgv_device(spec, s, v0, 1, forced)[0]
+            err.update(dx1=_lgv_worst(s, one, dev, 0), dv1=_lgv_worst(s, one, dev, 1), migrated=left, not_migrated=0 if left > 0 else 1,
+                       not_owned_once=0 if once else 1)
+            lim.update(dx1=1e-8, dv1=1e-7, not_migrated=1, not_owned_once=1)
+    ref = {k: (w[0], w[2], w[1]) for k, w in host.items()}
+    err.update(dx=_lgv_worst(s, ref, dev, 0), dv=_lgv_worst(s, ref, dev, 1), de=float(np.abs(np.array([dev[k][2] - ref[k][2] for k in ref])).max()),
+               tally_energy=ref[nsteps][2])
+    return err, lim
+
+
+def _lgv_worst(s, a, b, k):
+    """the worst difference over the reads of {step: (x, v, ...)}: k = 0 positions (same atom, possibly another image), 1 velocities"""
+    import refloops
+    worst = 0.0
+    for step in a:
+        d = b[step][k] - a[step][k]
+        if k == 0:
+            d = d - np.round(s.box.x2lamda(d + s.box.lo)) @ s.box.h.T
+        worst = refloops.worse(worst, float(np.abs(d).max()))     # (a NaN stays, and fails the limit)
+    return worst
+
+
+def line_langevin(spec, err):
+    more = "".join(f" {q} {_fmt(err[q])}" for q in ("dx1", "dv1", "dangerous", "late") if q in err)
+    return (f"{spec['id']} steps {spec['nsteps']} damp {spec['damp']} ratio {spec['ratio']} zero {int(spec['zero'])} tally {int(spec['tally'])} "
+            f"tilt {spec['tilt'] is not None} reads {[(a, int(b)) for a, b in spec['reads']]} drift {spec['drift']} seed {spec['seed']} "
+            f"dx {err['dx']:.1e} dv {err['dv']:.1e} dE {err['de']:.1e} (E {err['tally_energy']:.3g}){more} builds {err['builds']} "
+            f"migrated {err['migrated']}")
+
+
 # ---------------------------------------------------------------------------------------------------------------- nvt
 # The Nose-Hoover chain thermostat (tests/test_gpu_nvt_net.py): chains of 1-8, 1-3 loops, drag, flat or ramped targets,
 # both styles, the resident path and (REBO-MoS) the host-linked one, atom counts whose last 256-atom block varies.
@@ -720,7 +1038,7 @@ def nvt_cases(seed, ncase):
 
 
 NETS = {name: (globals()["draw_" + name], globals()["run_" + name], globals()["line_" + name])
-        for name in ("force", "hostmode_walk", "aeam_types", "prune", "dd", "hnve", "minilmp", "trajectory", "block")}
+        for name in ("force", "hostmode_walk", "aeam_types", "prune", "dd", "hnve", "minilmp", "trajectory", "block", "fire", "langevin")}
 
 
 def main(net, argv):

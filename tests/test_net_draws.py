@@ -57,6 +57,34 @@ CORNERS = {
     "block": {
         "both styles": lambda c: {s["style"] for s in c} == {"rebomos", "aeam"},
     },
+    "fire": {   # (what the iterations of these cases reach: test_fire_cases_reach_their_corners_in_the_reference)
+        "both styles": lambda c: {s["style"] for s in c} == {"rebomos", "aeam"},
+        "delaystep 0": lambda c: any(s["modify"]["delaystep"] == 0 for s in c),
+        "halfstepback and initialdelay, each on and off": lambda c: all({s["modify"][k] for s in c} == {True, False}
+                                                                         for k in ("halfstepback", "initialdelay")),
+        "every degenerate value": lambda c: all(any(s["modify"][k] == v for s in c) for k, v in
+                                                 (("dtgrow", 1.0), ("dtshrink", 1.0), ("alphashrink", 1.0), ("tmax", 1.0), ("tmin", 1.0))),
+        "every starting time step": lambda c: {s["dt"] for s in c} == {0.001, 0.002, 0.004},
+    },
+    "langevin": {
+        "every path": lambda c: {s["path"] for s in c} == set(nets.LGV_PATHS),
+        "both styles on bricks": lambda c: {s["style"] for s in c if s["path"] == "bricks"} == {"rebomos", "aeam"},
+        "an odd rank count": lambda c: any(s["ranks"] % 2 and s["ranks"] > 1 for s in c),
+        "both styles without the check": lambda c: {s["style"] for s in c if s["path"] == "resident-plain"} == {"rebomos", "aeam"},
+        "both styles host-linked": lambda c: {s["style"] for s in c if s["path"] == "hostlinked"} == {"rebomos", "aeam"},
+        "a run that crosses step 2^32": lambda c: any(s["first"] < 2 ** 32 < s["first"] + s["nsteps"] for s in c),
+        "a run above step 2^32": lambda c: any(s["first"] > 2 ** 32 for s in c),
+        "0 K as a target": lambda c: any(s["t1"] == 0.0 for s in c),
+        "0 K throughout": lambda c: any(s["t0"] == 0.0 and s["t1"] == 0.0 for s in c),
+        "a ramp downwards": lambda c: any(s["t1"] < s["t0"] for s in c),
+        "a time step other than 1 fs": lambda c: {s["dt"] for s in c} >= {0.0005, 0.002},
+        "zero and tally together": lambda c: any(s["zero"] and s["tally"] for s in c),
+        "neither zero nor tally": lambda c: any(not s["zero"] and not s["tally"] and s["path"] != "bricks" for s in c),
+        "a ratio on one type only": lambda c: any(s["ratio"] == "one" for s in c),
+        "a sheared alloy box": lambda c: any(s["style"] == "aeam" and s["tilt"] is not None for s in c),
+        "four fill levels of the last 256-atom block": lambda c: len({s["n"] % 256 for s in c}) >= 4,
+        "reads that find the final half deferred, and not": lambda c: {d for s in c for _, d in s["reads"]} == {True, False},
+    },
 }
 
 
@@ -68,6 +96,9 @@ def test_fixed_seeds_reach_the_corner(net, corner):
 def test_every_net_has_its_corners_and_at_most_8_ranks():
     assert set(CORNERS) == set(nets.NETS) == set(nets.SUITE)
     assert all(s["ranks"] <= 8 for s in SPECS["dd"]) and all(s["np"] <= 8 for s in SPECS["minilmp"])
+    assert all(s["ranks"] <= 8 for s in SPECS["langevin"])
+    assert {s["ranks"] for s in SPECS["langevin"] if s["path"] == "bricks"} <= {2, 3, 4, 8}
+    assert all(s["ranks"] == 1 for s in SPECS["langevin"] if s["path"] != "bricks")
 
 
 def test_draws_are_pure_and_repeatable():
@@ -106,3 +137,38 @@ def test_nvt_seed_reaches_its_corners():
     assert any(s["t0"] != s["t1"] for s in c) and any(s["t0"] == s["t1"] for s in c)
     # the last 256-atom block: several fill levels, a full one among them (n % 256 == 1 no cell of either style allows)
     assert len({s["n"] % 256 for s in c}) >= 4 and any(s["n"] % 256 == 0 for s in c)
+
+
+def test_fire_cases_reach_their_corners_in_the_reference(oracle):
+    """Needs the oracle, no GPU: fireref.minimize with ORACLE forces over the suite's `fire` cases (nets.trace_fire).  The
+    reference alone must reach what the net exists for -- the device then has to follow it there.  And every case stays a
+    minimisation: no atom moves further than the style's skin in its 80 iterations (a run that blows up cannot be held to
+    1e-9 eV/A; draw_fire keeps the ceiling of the time step at 10 fs for that reason)."""
+    seen, far = {}, 0.0
+    for spec in SPECS["fire"]:
+        m, dt0 = spec["modify"], spec["dt"]
+        dtmax, dtmin = m["tmax"] * dt0, m["tmin"] * dt0
+        rows = nets.trace_fire(spec)
+        assert len(rows) == spec["niter"] == 80
+        far = max(far, rows[-1]["moved"])
+        assert rows[-1]["moved"] < {"rebomos": 2.0, "aeam": 1.0}[spec["style"]], (spec["id"], rows[-1]["moved"])
+        assert m["tmax"] * dt0 <= 0.0101
+        for r in rows:
+            held = m["initialdelay"] and r["iter"] < m["delaystep"]
+            negative = not r["mixed"]
+            hit = {
+                "dt == dtmax with tmax < 10": m["tmax"] < 10 and r["dt"] == dtmax and r["dt_before"] * m["dtgrow"] > dtmax,
+                "a shrink refused at dtmin": negative and not held and r["dt_before"] * m["dtshrink"] < dtmin and r["dt"] == r["dt_before"],
+                "P <= 0 inside the initial delay leaves dt alone": negative and held and r["iter"] > 1 and r["dt"] == r["dt_before"],
+                "P <= 0 after iteration 1 with halfstepback off": negative and r["iter"] > 1 and not m["halfstepback"],
+                "dtv < dt": r["dtv"] < r["dt"],
+                "delaystep 0": m["delaystep"] == 0,
+                spec["style"]: True,
+            }
+            for k, v in hit.items():
+                if v:
+                    seen.setdefault(k, set()).add(spec["id"])
+    print({k: len(v) for k, v in seen.items()}, f"farthest atom {far:.2f} A")
+    for corner in ("dt == dtmax with tmax < 10", "a shrink refused at dtmin", "P <= 0 inside the initial delay leaves dt alone",
+                   "P <= 0 after iteration 1 with halfstepback off", "dtv < dt", "delaystep 0", "rebomos", "aeam"):
+        assert corner in seen, f"no fire case of {nets.SUITE['fire']} reaches '{corner}'"
