@@ -2,6 +2,7 @@
    minimize/mdp -- see command_minimize_mdp.h
 -------------------------------------------------------------------------------------------------- */
 #include "command_minimize_mdp.h"
+#include "mdp_args.h"
 #include "mdp_brick.h"
 
 #include "atom.h"
@@ -24,20 +25,6 @@ using namespace LAMMPS_NS;
 
 namespace {
 
-bool number(const char *s, double &v)
-{
-  char *end = nullptr;
-  v = strtod(s, &end);
-  return end != s && *end == '\0' && std::isfinite(v);
-}
-
-bool whole(const char *s, long long &v)
-{
-  char *end = nullptr;
-  v = strtoll(s, &end, 10);
-  return end != s && *end == '\0';
-}
-
 const char *kCriterion[] = {"running", "force tolerance", "energy tolerance", "max iterations", "max force evaluations"};
 
 } // namespace
@@ -57,9 +44,9 @@ void MinimizeMDP::parse(int narg, char **arg)
 {
   if (narg < 4) error->all(FLERR, "Illegal minimize/mdp command: expected etol ftol maxiter maxeval");
   memset(&cfg, 0, sizeof cfg);
-  if (!number(arg[0], cfg.etol) || !number(arg[1], cfg.ftol))
+  if (!mdp_number(arg[0], cfg.etol, true) || !mdp_number(arg[1], cfg.ftol, true))
     error->all(FLERR, "minimize/mdp: etol and ftol must be numbers");
-  if (!whole(arg[2], cfg.maxiter) || !whole(arg[3], cfg.maxeval))
+  if (!mdp_whole(arg[2], cfg.maxiter) || !mdp_whole(arg[3], cfg.maxeval))
     error->all(FLERR, "minimize/mdp: maxiter and maxeval must be integers");
   if (cfg.etol < 0.0 || cfg.ftol < 0.0) error->all(FLERR, "minimize/mdp: etol and ftol must be >= 0.0");
   if (cfg.maxiter < 0 || cfg.maxeval < 0) error->all(FLERR, "minimize/mdp: maxiter and maxeval must be >= 0");
@@ -84,18 +71,16 @@ void MinimizeMDP::parse(int narg, char **arg)
     if (k + 1 >= narg) error->all(FLERR, "minimize/mdp: " + key + " needs a value");
     const std::string val = arg[k + 1];
     if (key == "halfstepback" || key == "initialdelay") {
-      if (val != "yes" && val != "no") error->all(FLERR, "minimize/mdp: " + key + " takes yes or no");
-      (key == "halfstepback" ? cfg.halfstepback : cfg.initialdelay) = val == "yes";
+      (key == "halfstepback" ? cfg.halfstepback : cfg.initialdelay) = mdp_yesno(error, "minimize/mdp: ", key, val.c_str(), false);
       continue;
     }
-    double v = 0.0;
     long long n = 0;
     if (key == "delaystep") {
-      if (!whole(val.c_str(), n) || n < 0 || n > 1000000000) error->all(FLERR, "minimize/mdp: delaystep must be an integer >= 0");
+      if (!mdp_whole(val.c_str(), n) || n < 0 || n > 1000000000) error->all(FLERR, "minimize/mdp: delaystep must be an integer >= 0");
       cfg.delaystep = (int) n;
       continue;
     }
-    if (!number(val.c_str(), v)) error->all(FLERR, "minimize/mdp: bad " + key + " value " + val);
+    const double v = mdp_number(error, "minimize/mdp: ", key, val.c_str(), true);
     if (key == "dmax") {
       if (v <= 0.0) error->all(FLERR, "minimize/mdp: dmax must be > 0.0");
       cfg.dmax = v;
@@ -127,31 +112,18 @@ void MinimizeMDP::command(int narg, char **arg)
   if (comm->nprocs != 1)
     error->all(FLERR, "minimize/mdp runs on one MPI rank (its sums would need an all-reduce per iteration)");
   if (!domain->xperiodic || !domain->yperiodic || !domain->zperiodic) error->all(FLERR, "minimize/mdp needs a periodic box");
-  int dim = 0;
-  const int *sid = force->pair ? static_cast<int *>(force->pair->extract("mdp_style", dim)) : nullptr;
-  if (!sid) error->all(FLERR, "minimize/mdp requires a pair style of this plugin (rebomos or aeam)");
-  const int style_id = *sid;
+  const int style_id = mdp_pair_style_id(force->pair);
+  if (!style_id) error->all(FLERR, "minimize/mdp requires a pair style of this plugin (rebomos or aeam)");
   if (const char *e = getenv("MDP_REBOMOS_HOST_LIST"))
     if (style_id == 1 && atoi(e) != 0)
       error->all(FLERR, "minimize/mdp keeps the atoms on the device and cannot be combined with MDP_REBOMOS_HOST_LIST=1");
   if (!(update->dt > 0.0)) error->all(FLERR, "minimize/mdp: the timestep must be > 0.0");
 
-  const int ndev = mdp_device_count();
-  int id = ndev > 0 ? comm->me % ndev : 0; // (the pair style's rule for its own context)
-  if (const char *env = getenv("MDP_DEVICE")) id = atoi(env);
-  if (mdp_create(&ctx, id) != MDP_OK) error->one(FLERR, "minimize/mdp needs a HIP device: cannot create a device context");
-  const int *map = nullptr;
-  if (style_id == 1) {
-    const mdp_rebomos_params *P = static_cast<mdp_rebomos_params *>(force->pair->extract("mdp_rebomos_params", dim));
-    if (!P) error->all(FLERR, "minimize/mdp: the pair style has no parameters yet (pair_coeff)");
-    if (mdp_rebomos_set_params(ctx, P) != MDP_OK) fail("parameters");
-    map = static_cast<int *>(force->pair->extract("mdp_map", dim));
-  } else {
-    const mdp_aeam_tables *T = static_cast<mdp_aeam_tables *>(force->pair->extract("mdp_aeam_tables", dim));
-    if (!T) error->all(FLERR, "minimize/mdp: the pair style has no tables yet (pair_coeff)");
-    if (mdp_aeam_set_tables(ctx, T) != MDP_OK) fail("tables");
-  }
-  if (mdp_brick_from_host(ctx, style_id, map, atom, domain, force, neighbor, update, comm) != MDP_OK) fail("setup");
+  const mdp_own_context_result own = mdp_own_context(force->pair, comm->me, &ctx);
+  if (own.why) error->all(FLERR, std::string("minimize/mdp") + own.why);
+  if (own.failed && !ctx) error->one(FLERR, "minimize/mdp needs a HIP device: cannot create a device context");
+  if (own.failed) fail(own.failed);
+  if (mdp_brick_from_host(ctx, style_id, own.map, atom, domain, force, neighbor, update, comm) != MDP_OK) fail("setup");
   if (mdp_dd_reneighbor(ctx) != MDP_OK) fail("lists");
   if (mdp_fire_setup(ctx, &cfg) != MDP_OK) fail("setup");
 

@@ -9,6 +9,7 @@
      compute_scalar()   the tally, read through the context fix nve/mdp exposes (Fix::extract("mdp_run_ctx"))
 -------------------------------------------------------------------------------------------------- */
 #include "fix_langevin_mdp.h"
+#include "mdp_args.h"
 
 #include "atom.h"
 #include "comm.h"
@@ -27,18 +28,7 @@ double number(LAMMPS *lmp, const char *s, const char *what)
 {
   if (strncmp(s, "v_", 2) == 0)
     lmp->error->all(FLERR, std::string("Fix langevin/mdp: variables are not supported (") + what + " " + s + ")");
-  char *end = nullptr;
-  const double v = strtod(s, &end);
-  if (!end || end == s || *end) lmp->error->all(FLERR, std::string("Illegal fix langevin/mdp command: bad ") + what + " value " + s);
-  return v;
-}
-
-bool yesno(LAMMPS *lmp, const std::string &key, const char *s)
-{
-  if (strcmp(s, "yes") == 0) return true;
-  if (strcmp(s, "no") == 0) return false;
-  lmp->error->all(FLERR, "Illegal fix langevin/mdp command: " + key + " takes yes or no, not " + s);
-  return false;
+  return mdp_number(lmp->error, "Illegal fix langevin/mdp command: ", what, s);
 }
 } // namespace
 
@@ -73,8 +63,8 @@ FixLangevinMDP::FixLangevinMDP(LAMMPS *lmp, int narg, char **arg) : Fix(lmp, nar
       continue;
     }
     if (k + 1 >= narg) error->all(FLERR, "Illegal fix langevin/mdp command: " + key + " needs a value");
-    if (key == "tally") cfg.tally = yesno(lmp, key, arg[k + 1]);
-    else if (key == "zero") cfg.zero = yesno(lmp, key, arg[k + 1]);
+    if (key == "tally") cfg.tally = mdp_yesno(error, "Illegal fix langevin/mdp command: ", key, arg[k + 1], true);
+    else if (key == "zero") cfg.zero = mdp_yesno(error, "Illegal fix langevin/mdp command: ", key, arg[k + 1], true);
     else error->all(FLERR, "Illegal fix langevin/mdp command: unknown keyword " + key);
     k += 2;
   }

@@ -31,13 +31,13 @@
    takes out of the steps.  So it runs the library's own decomposition instead, as minihost/ddhost.cpp does without a
    LAMMPS around it:
      init()              a context of its own (same device as the pair style's), the style's parameters / tables on it
-                         (Pair::extract); neighbor->delay beyond any run: the host neither checks nor reneighbors
+                         (mdp_own_context, mdp_brick.h); neighbor->delay beyond any run: the host neither checks nor reneighbors
      setup()             this rank's owned atoms (x, v, type, tag as the host holds them after ITS setup) -> the brick
                          (mdp_md_setup, mdp_dd_setup on comm->procgrid, rank = comm->me: LAMMPS' own bricks); RCCL's id from
                          rank 0 with MPI_Bcast(world); first halo and lists (mdp_dd_comm_reneighbor); forces of step 0
      initial_integrate   mdp_dd_comm_step_begin: half-kick + drift, the `check yes` decision from the word that rode in the
                          previous halo, migration + lists or the start of this step's halo, what needs no remote ghost
-     Pair::compute       mdp_dd_comm_step_end (compute_bricks in the adapters): the rest of the step; eng_vdwl / virial of
+     Pair::compute       mdp_dd_comm_step_end (PairMDP::compute_bricks): the rest of the step; eng_vdwl / virial of
                          this rank's atoms on steps that ask (the host sums over ranks as it always does)
      final_integrate     output steps and the last step: atoms come back -- as many as the brick owns NOW (atom->nlocal
                          and, through atom->avec->grow, the arrays follow), x, v, type, tag
@@ -128,8 +128,7 @@ void FixNVEMDP::init()
     init_bricks();
     return;
   }
-  if (mdp_hnve_setup(ctx(), update->dt, force->ftm2v, atom->mass, atom->ntypes) != MDP_OK)
-    error->one(FLERR, std::string("Fix nve/mdp: ") + mdp_last_error(ctx()));
+  if (mdp_hnve_setup(ctx(), update->dt, force->ftm2v, atom->mass, atom->ntypes) != MDP_OK) fail(ctx());
   *pair_linked = 1; // from the next compute on (the setup compute uploads atoms AND velocities)
   next_reneighbor = -1;
   // `check yes`: the device's displacement check decides (see the head of this file); the host's own look at atom->x --
@@ -148,9 +147,7 @@ void FixNVEMDP::init_bricks()
   int dim = 0;
   bricks_slot = static_cast<mdp_ctx **>(force->pair->extract("mdp_bricks_ctx", dim));
   bricks_ev = static_cast<int *>(force->pair->extract("mdp_bricks_ev", dim));
-  const int *sid = static_cast<int *>(force->pair->extract("mdp_style", dim));
-  if (!bricks_slot || !bricks_ev || !sid)
-    error->all(FLERR, "Fix nve/mdp requires a pair style of this plugin (rebomos or aeam)");
+  if (!bricks_slot || !bricks_ev) error->all(FLERR, "Fix nve/mdp requires a pair style of this plugin (rebomos or aeam)");
   if (hostcheck) error->all(FLERR, "Fix nve/mdp: hostcheck yes needs the host's arrays current: one MPI rank without `bricks yes`");
   if (!domain->xperiodic || !domain->yperiodic || !domain->zperiodic)
     error->all(FLERR, "Fix nve/mdp on several MPI ranks (or with bricks yes) needs a periodic box");
@@ -158,22 +155,13 @@ void FixNVEMDP::init_bricks()
   // dimension fastest); another mapping (map xyz, numa, a custom file) would hand every rank another rank's brick
   if ((comm->myloc[0] * comm->procgrid[1] + comm->myloc[1]) * comm->procgrid[2] + comm->myloc[2] != comm->me)
     error->all(FLERR, "Fix nve/mdp on several MPI ranks needs the default mapping of ranks to the processor grid (processors ... map cart)");
-  style_id = *sid;
-  if (!bctx) {
-    const int ndev = mdp_device_count();
-    int id = ndev > 0 ? comm->me % ndev : 0; // (the pair style's rule, pair_rebomos.cpp open_device)
-    if (const char *env = getenv("MDP_DEVICE")) id = atoi(env);
-    if (mdp_create(&bctx, id) != MDP_OK) error->one(FLERR, "Fix nve/mdp: cannot create a device context");
-  }
-  if (style_id == 1) {
-    const mdp_rebomos_params *P = static_cast<mdp_rebomos_params *>(force->pair->extract("mdp_rebomos_params", dim));
-    if (!P) error->all(FLERR, "Fix nve/mdp: the pair style has no parameters yet (pair_coeff)");
-    if (mdp_rebomos_set_params(bctx, P) != MDP_OK) fail(bctx);
-  } else {
-    const mdp_aeam_tables *T = static_cast<mdp_aeam_tables *>(force->pair->extract("mdp_aeam_tables", dim));
-    if (!T) error->all(FLERR, "Fix nve/mdp: the pair style has no tables yet (pair_coeff)");
-    if (mdp_aeam_set_tables(bctx, T) != MDP_OK) fail(bctx);
-  }
+  // the context is created once; the style's parameters go to it at every init()
+  const mdp_own_context_result own = mdp_own_context(force->pair, comm->me, &bctx);
+  if (own.why) error->all(FLERR, std::string("Fix nve/mdp") + own.why);
+  if (own.failed && !bctx) error->one(FLERR, "Fix nve/mdp: cannot create a device context");
+  if (own.failed) fail(bctx);
+  style_id = own.style_id;
+  bricks_map = own.map;
   bricks = 1;
   *bricks_slot = nullptr; // (the setup compute of this run is the host's: its arrays are the current ones)
   // neither a check nor a reneighboring of the host's during the run: both read arrays that are not current
@@ -209,9 +197,7 @@ void *FixNVEMDP::extract(const char *name, int &dim)
 void FixNVEMDP::setup_steps()
 {
   if (!bricks) return;
-  int dim = 0;
-  const int *map = style_id == 1 ? static_cast<int *>(force->pair->extract("mdp_map", dim)) : nullptr;
-  if (mdp_brick_from_host(bctx, style_id, map, atom, domain, force, neighbor, update, comm) != MDP_OK) fail(bctx);
+  if (mdp_brick_from_host(bctx, style_id, bricks_map, atom, domain, force, neighbor, update, comm) != MDP_OK) fail(bctx);
   if (comm->nprocs == 1) { // one brick: its periodic images are the library's, no communicator
     if (mdp_dd_reneighbor(bctx) != MDP_OK) fail(bctx);
     if (mdp_md_compute(bctx, 0, 0) != MDP_OK) fail(bctx);
@@ -257,15 +243,14 @@ void FixNVEMDP::reset_dt()
     if (bricks_slot && *bricks_slot) error->all(FLERR, "Fix nve/mdp on several MPI ranks: the timestep cannot change during a run");
     return; // (setup() hands update->dt to the brick)
   }
-  if (ctx() && mdp_hnve_setup(ctx(), update->dt, force->ftm2v, atom->mass, atom->ntypes) != MDP_OK)
-    error->one(FLERR, std::string("Fix nve/mdp: ") + mdp_last_error(ctx()));
+  if (ctx() && mdp_hnve_setup(ctx(), update->dt, force->ftm2v, atom->mass, atom->ntypes) != MDP_OK) fail(ctx());
 }
 
 void FixNVEMDP::to_host(bool forces)
 {
   const int n = atom->nlocal;
   if (mdp_hnve_download(ctx(), n ? atom->x[0] : nullptr, n ? atom->v[0] : nullptr, (forces && n) ? atom->f[0] : nullptr) != MDP_OK)
-    error->one(FLERR, std::string("Fix nve/mdp: ") + mdp_last_error(ctx()));
+    fail(ctx());
   downloads++;
 }
 
@@ -290,8 +275,7 @@ void FixNVEMDP::initial_integrate(int vflag)
     return;
   }
   int moved = 0, dangerous = 0;
-  if (mdp_hnve_initial(ctx(), &moved, &dangerous) != MDP_OK)
-    error->one(FLERR, std::string("Fix nve/mdp: ") + mdp_last_error(ctx()));
+  if (mdp_hnve_initial(ctx(), &moved, &dangerous) != MDP_OK) fail(ctx());
   const bigint now = update->ntimestep;
   if (getenv("MDP_DEBUG")) fprintf(stderr, "[fix nve/mdp] step %ld moved %d dangerous %d next_reneighbor %ld ago %d\n", (long) now, moved, dangerous, (long) next_reneighbor, neighbor->ago);
   if (moved && next_reneighbor < now) next_reneighbor = now + 1; // (a request for THIS step stands: decide() has not seen it yet)
@@ -333,7 +317,7 @@ void FixNVEMDP::final_integrate()
     if (now == output->next || now == update->laststep) bricks_to_host();
     return;
   }
-  if (mdp_hnve_final(ctx()) != MDP_OK) error->one(FLERR, std::string("Fix nve/mdp: ") + mdp_last_error(ctx()));
+  if (mdp_hnve_final(ctx()) != MDP_OK) fail(ctx());
   const bigint now = update->ntimestep;
   if (now == output->next || now == update->laststep) to_host(false); // thermo, dumps, the state a run ends with
 }

@@ -60,6 +60,7 @@ class FixNVEMDP : public Fix {
   mdp_ctx **bricks_slot;   // the pair style's pointer to it (set while a run is under way: its compute() ends the steps there)
   int *bricks_ev;      // the pair style's copy of "this step was opened with energy / virial"
   int style_id, comm_up, pending_final, step_ev;
+  const int *bricks_map = nullptr; // rebomos: the pair style's type -> element map, as of the last init()
 
   // the Langevin thermostat a `fix langevin/mdp` handed over (extract "mdp_langevin" / "mdp_langevin_on"): switched on in
   // setup() on the context the steps run on (lgv_ctx, extract "mdp_run_ctx"), off in post_run()

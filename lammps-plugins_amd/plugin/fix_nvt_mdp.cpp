@@ -10,6 +10,7 @@
      compute_scalar()   the thermostat energy (FixNH::compute_scalar) at the current target
 -------------------------------------------------------------------------------------------------- */
 #include "fix_nvt_mdp.h"
+#include "mdp_args.h"
 
 #include "atom.h"
 #include "comm.h"
@@ -25,16 +26,6 @@
 #include <string>
 
 using namespace LAMMPS_NS;
-
-namespace {
-double number(LAMMPS *lmp, const char *s, const char *what)
-{
-  char *end = nullptr;
-  const double v = strtod(s, &end);
-  if (!end || end == s || *end) lmp->error->all(FLERR, std::string("Illegal fix nvt/mdp command: bad ") + what + " value " + s);
-  return v;
-}
-} // namespace
 
 FixNVTMDP::Args FixNVTMDP::parse(LAMMPS *lmp, int narg, char **arg)
 {
@@ -55,9 +46,9 @@ FixNVTMDP::Args FixNVTMDP::parse(LAMMPS *lmp, int narg, char **arg)
       if (key == b) lmp->error->all(FLERR, "Fix nvt/mdp is a thermostat only: barostat keyword " + key + " is not supported");
     if (key == "temp") {
       if (k + 3 >= narg) lmp->error->all(FLERR, "Illegal fix nvt/mdp command: temp needs Tstart Tstop Tdamp");
-      a.cfg.t_start = number(lmp, arg[k + 1], "Tstart");
-      a.cfg.t_stop = number(lmp, arg[k + 2], "Tstop");
-      a.cfg.t_period = number(lmp, arg[k + 3], "Tdamp");
+      a.cfg.t_start = mdp_number(lmp->error, "Illegal fix nvt/mdp command: ", "Tstart", arg[k + 1]);
+      a.cfg.t_stop = mdp_number(lmp->error, "Illegal fix nvt/mdp command: ", "Tstop", arg[k + 2]);
+      a.cfg.t_period = mdp_number(lmp->error, "Illegal fix nvt/mdp command: ", "Tdamp", arg[k + 3]);
       have_temp = true;
       k += 4;
       continue;
@@ -65,7 +56,7 @@ FixNVTMDP::Args FixNVTMDP::parse(LAMMPS *lmp, int narg, char **arg)
     if (k + 1 >= narg) lmp->error->all(FLERR, "Illegal fix nvt/mdp command: " + key + " needs a value");
     if (key == "tchain") a.cfg.tchain = atoi(arg[k + 1]);
     else if (key == "tloop") a.cfg.tloop = atoi(arg[k + 1]);
-    else if (key == "drag") a.cfg.drag = number(lmp, arg[k + 1], "drag");
+    else if (key == "drag") a.cfg.drag = mdp_number(lmp->error, "Illegal fix nvt/mdp command: ", "drag", arg[k + 1]);
     else if (key == "hostcheck" || key == "bricks") {
       a.nve.push_back(arg[k]);
       a.nve.push_back(arg[k + 1]);

@@ -1,7 +1,8 @@
 /* -*- c++ -*- -----------------------------------------------------------------------------------
    The host's atoms as one brick of the library's own decomposition and back: what `fix nve/mdp bricks yes` does around a
-   run and `minimize/mdp` around a minimisation.  Free functions over the host's objects, so that a Fix and a Command
-   (whose Pointers members are protected) share them.
+   run and `minimize/mdp` around a minimisation -- and, before that, the way to a context of one's own that carries the
+   pair style's parameters, on the device every context of a rank lives on.  Free functions over the host's objects, so
+   that a Pair, a Fix and a Command (whose Pointers members are protected) share them.
 -------------------------------------------------------------------------------------------------- */
 #ifndef MDP_BRICK_H
 #define MDP_BRICK_H
@@ -18,9 +19,61 @@
 #include "mdpair_hip.h"
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 namespace LAMMPS_NS {
+
+// the device of a rank's contexts: round robin over the devices there are, or what MDP_DEVICE says
+inline int mdp_device_of_rank(int me)
+{
+  const int ndev = mdp_device_count();
+  if (const char *env = getenv("MDP_DEVICE")) return atoi(env);
+  return ndev > 0 ? me % ndev : 0;
+}
+
+inline int mdp_pair_style_id(Pair *pair)
+{
+  int dim = 0;
+  const int *sid = pair ? static_cast<int *>(pair->extract("mdp_style", dim)) : nullptr;
+  return sid ? *sid : 0;
+}
+
+// a context of the caller's own for the pair style's potential: created on this rank's device unless *ctx is there already,
+// then given the style's parameters / tables (Pair::extract).  Failures come back in words for the caller to put its
+// own name in front of: `why` for error->all, `failed` (the library step; the reason is mdp_last_error(*ctx), and *ctx
+// is null if it could not be created) for error->one.
+struct mdp_own_context_result {
+  int style_id = 0;             // 1 rebomos, 2 aeam
+  const int *map = nullptr;     // rebomos: the style's type -> element map
+  const char *why = nullptr, *failed = nullptr;
+};
+
+inline mdp_own_context_result mdp_own_context(Pair *pair, int me, mdp_ctx **ctx)
+{
+  mdp_own_context_result r;
+  int dim = 0;
+  r.style_id = mdp_pair_style_id(pair);
+  if (!r.style_id) {
+    r.why = " requires a pair style of this plugin (rebomos or aeam)";
+    return r;
+  }
+  if (!*ctx && mdp_create(ctx, mdp_device_of_rank(me)) != MDP_OK) {
+    r.failed = "context";
+    return r;
+  }
+  if (r.style_id == 1) {
+    const mdp_rebomos_params *P = static_cast<mdp_rebomos_params *>(pair->extract("mdp_rebomos_params", dim));
+    if (!P) r.why = ": the pair style has no parameters yet (pair_coeff)";
+    else if (mdp_rebomos_set_params(*ctx, P) != MDP_OK) r.failed = "parameters";
+    r.map = static_cast<int *>(pair->extract("mdp_map", dim));
+  } else {
+    const mdp_aeam_tables *T = static_cast<mdp_aeam_tables *>(pair->extract("mdp_aeam_tables", dim));
+    if (!T) r.why = ": the pair style has no tables yet (pair_coeff)";
+    else if (mdp_aeam_set_tables(*ctx, T) != MDP_OK) r.failed = "tables";
+  }
+  return r;
+}
 
 // this rank's owned atoms (x, v, type, tag as the host holds them) -> the brick of rank comm->me on comm->procgrid:
 // mdp_md_setup + mdp_dd_setup.  style_id: 1 rebomos (map: the style's type -> element map), 2 aeam.  Returns the

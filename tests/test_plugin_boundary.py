@@ -78,8 +78,8 @@ def test_plugin_registers_and_refuses_to_run_without_gpu():
         assert rc == 0
 
 
-def _thermo_rows(out):
-    rows = []
+def _thermo_lines(out):
+    lines = []
     grab = False
     for line in out.splitlines():
         if line.strip().startswith("Step"):
@@ -90,8 +90,12 @@ def _thermo_rows(out):
             if not parts or not re.fullmatch(r"\d+", parts[0]):
                 grab = False
                 continue
-            rows.append([float(p) for p in parts])
-    return rows
+            lines.append(line)
+    return lines
+
+
+def _thermo_rows(out):
+    return [[float(p) for p in line.split()] for line in _thermo_lines(out)]
 
 
 @pytest.mark.gpu
@@ -124,3 +128,57 @@ def test_aeam_plugin_runs_sample_system_and_conserves_energy():
     assert max(etot) - min(etot) < 32000 * 2e-5      # NVE drift/fluctuation per atom
     assert -3.45 < rows[0][3] / 32000 < -3.38        # PE/atom of the Al(Si) lattice at 0 K displacement
     assert rows[0][1] == pytest.approx(863.0, rel=1e-6)
+
+
+# ---- both pair plugins in one process.  The host loads plugin files with RTLD_GLOBAL, so what the two files share
+# (fix nve/mdp, the pair styles' common base) resolves to the copy in whichever file came first.
+
+BOTH_ORDERS = [("rebomosplugin.so", "aeamplugin.so"), ("aeamplugin.so", "rebomosplugin.so")]
+PAIR_LINES = {"aeam": "pair_style aeam\npair_coeff * * ../tests/golden/potentials/AlSi.aeam Al Si\n",
+              "rebomos": "pair_style rebomos\npair_coeff * * ../tests/golden/potentials/MoS.REBO.set5b Mo S\n"}
+
+
+@pytest.mark.parametrize("style", ["aeam", "rebomos"])
+@pytest.mark.parametrize("first,second", BOTH_ORDERS)
+def test_both_pair_plugins_in_one_process_name_the_style_asked_for(first, second, style):
+    from lammps_plugins_amd.host import capi
+    script = ("plugin load %s\nplugin load %s\n" % (first, second) + HEAD.replace("block 0 2 0 2 0 2", "block 0 3 0 3 0 3")
+              + PAIR_LINES[style] + "fix integrate all nve/mdp\nrun 1\n")
+    rc, out, err = _run(script)
+    assert "Created 108 atoms" in out
+    assert "Loaded 2 plugins from " + first in out      # its pair style + fix nve/mdp
+    assert "Loaded 1 plugins from " + second in out     # its pair style; fix nve/mdp is there already
+    other = "rebomos" if style == "aeam" else "aeam"
+    assert "Pair style %s (MI355X)" % other not in err
+    if capi.lib().mdp_device_count() == 0:
+        assert rc == 1 and "Pair style %s (MI355X) needs a HIP device; there is no CPU fallback" % style in err
+    else:
+        assert "needs a HIP device" not in err
+        if style == "aeam":
+            assert rc == 0 and "Loop time" in out, err
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("example,own,cuts", [
+    ("in.rebomos-bulk.nve-mdp.mi355x", "rebomosplugin.so", {}),                      # (288 atoms, 20 steps as it stands)
+    ("in.aeam-alsi.nve-mdp.mi355x", "aeamplugin.so", {"thermo 100\n": "thermo 10\n", "run 400\n": "run 20\n"})])
+def test_a_run_does_not_depend_on_which_plugin_files_are_loaded(example, own, cuts):
+    """20 steps of each nve/mdp example with only its own plugin file loaded, then with both files in either order: the
+    printed thermo rows and the MDP_FIX_STATS line are the same text in all three runs."""
+    text = open(os.path.join(PKG, "examples", example)).read()
+    load = "plugin load %s\n" % own
+    for old in list(cuts) + [load, "run 20\n" if not cuts else "run 400\n"]:
+        assert old in text
+    for old, new in cuts.items():
+        text = text.replace(old, new)
+    results = []
+    for files in [(own,)] + BOTH_ORDERS:
+        rc, out, err = _run(text.replace(load, "".join("plugin load %s\n" % f for f in files)), env={"MDP_FIX_STATS": "1"})
+        assert rc == 0, err
+        rows = _thermo_lines(out)
+        stats = [l for l in out.splitlines() if l.startswith("fix nve/mdp:")]
+        print(files, rows, stats)
+        assert [int(r.split()[0]) for r in rows] == [0, 10, 20] and len(stats) == 1
+        results.append((rows, stats))
+    assert results[1] == results[0]
+    assert results[2] == results[0]
