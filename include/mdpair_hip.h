@@ -428,7 +428,7 @@ int mdp_md_moved_async(mdp_ctx *ctx, int *moved, int *dangerous);
 /* mdp_md_initial_integrate (with_final != 0: mdp_md_final_initial_integrate) and mdp_md_moved_async in one call and one
  * pass over the atoms: same results, the check reads the new positions while they are in registers. */
 int mdp_md_integrate_check(mdp_ctx *ctx, int with_final, int *moved, int *dangerous);
-/* owned atoms' "tag" / "type" in device order (the device re-orders atoms at every reneighboring); "tile_nu"
+/* owned atoms' "tag" / "type" / "mask" (mdp_md_set_mask) in device order (the device re-orders atoms at every reneighboring); "tile_nu"
  * (diagnostics): {members of the neighbour union, Mo / first-type members} of every 32-atom tile, 2 ints per tile */
 int mdp_md_download_int(mdp_ctx *ctx, const char *name, int *out);
 
@@ -559,6 +559,30 @@ int mdp_fire_setup(mdp_ctx *ctx, const mdp_fire_config *cfg);
 int mdp_fire_iterate(mdp_ctx *ctx, long long n, int *stop);
 int mdp_fire_state(mdp_ctx *ctx, double *out);
 int mdp_fire_off(mdp_ctx *ctx);
+
+/* ---- groups of atoms (LAMMPS `fix ID GROUP ...`: the per-atom 32-bit atom->mask and a group's bit) --------------------
+ * The device keeps the owned atoms' mask and the integrate calls honour two group bits.
+ *   mdp_md_set_mask:     resident mode.  mask[nlocal] in the CURRENT device order (the order of mdp_md_download and
+ *                        mdp_md_download_int("tag"); right after mdp_md_setup the order of the arrays handed to it).  From
+ *                        then on the mask follows its atom through every reneighboring and migration (the migration record
+ *                        stays 8 doubles: type and mask share one of them); mdp_md_download_int("mask") reads it back.
+ *                        NULL withdraws the mask; so does mdp_md_setup.  Every rank of a brick run sets one, or none does.
+ *   mdp_hnve_set_mask:   host-linked mode.  mask[nlocal] in the host's order, at every reneighboring after
+ *                        mdp_set_atoms_host (next to mdp_hnve_upload_v); NULL withdraws it.
+ *   mdp_integrate_group: groupbit != 0: only atoms with mask & groupbit get the half-kicks, the drift, the Nose-Hoover
+ *                        scale and the FIRE advance; every other atom keeps x and v bit for bit (LAMMPS fix nve on a
+ *                        group; for the minimiser, fix setforce 0 0 0 on the complement: held atoms are left out of its
+ *                        sums and its force norm, and mdp_fire_setup leaves their velocities alone).  The Nose-Hoover
+ *                        temperature is that of the group; nf of mdp_nhc_config is the caller's (3 N_group - 3).
+ *                        0 (default): every atom, through exactly the kernels of a context without groups.
+ *   mdp_langevin_group:  groupbit != 0: only atoms with mask & groupbit (and inside the integrate group) receive the
+ *                        Langevin force; `zero` and `tally` run over them, natoms of mdp_langevin_config is their count.
+ * Both group calls are refused (MDP_ESTATE) while the minimiser is on.  An integrate call with a non-zero group and no
+ * mask for the current atoms fails with MDP_ESTATE. */
+int mdp_md_set_mask(mdp_ctx *ctx, const int *mask);
+int mdp_hnve_set_mask(mdp_ctx *ctx, const int *mask);
+int mdp_integrate_group(mdp_ctx *ctx, int groupbit);
+int mdp_langevin_group(mdp_ctx *ctx, int groupbit);
 
 /* per-phase device time of the last compute in ms (HIP events on the compute stream):
  * rebomos: [0]=REBO centre kernels of the lane-group classes, [1]=the general kernel (centres that outgrew their lane

@@ -91,12 +91,14 @@ __global__ __launch_bounds__(256) void dd_remap_kernel(const DdGeom G, const int
   if (q != G.rank) atomicAdd(&counts[q], 1); // leavers are rare
 }
 
-// 2. exchange: leavers -> records of 8 doubles {x, v, type, tag}, grouped by destination
+// 2. exchange: leavers -> records of 8 doubles {x, v, type, tag}, grouped by destination.  With a mask on the context
+// (mdp_md_set_mask) the record keeps its width: r[6] = type + 64 * (the mask's 32 bits as an unsigned number), exact in a
+// double; without one r[6] is the type alone, and the unpack reads both alike
 __global__ __launch_bounds__(256) void dd_pack_leavers_kernel(const int n, const int rank, const int *__restrict__ dest,
                                                               const int *__restrict__ seg_off, int *__restrict__ cursor,
                                                               const double4 *__restrict__ xq, const double *__restrict__ v,
                                                               const int *__restrict__ type, const int *__restrict__ tag,
-                                                              double *__restrict__ buf)
+                                                              const int *__restrict__ mask, double *__restrict__ buf)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -111,19 +113,22 @@ __global__ __launch_bounds__(256) void dd_pack_leavers_kernel(const int n, const
   r[3] = v[3 * (size_t) i];
   r[4] = v[3 * (size_t) i + 1];
   r[5] = v[3 * (size_t) i + 2];
-  r[6] = (double) type[i];
+  r[6] = mask ? (double) type[i] + 64.0 * (double) (unsigned) mask[i] : (double) type[i];
   r[7] = (double) tag[i];
 }
 
 __global__ __launch_bounds__(256) void dd_unpack_arrivals_kernel(const int n, const int first, const double *__restrict__ buf,
                                                                  const int *__restrict__ map, double4 *__restrict__ xq,
                                                                  double *__restrict__ v, int *__restrict__ type,
-                                                                 int *__restrict__ tag, int *__restrict__ dest, const int rank)
+                                                                 int *__restrict__ tag, int *__restrict__ mask,
+                                                                 int *__restrict__ dest, const int rank)
 {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= n) return;
   const double *r = buf + 8 * (size_t) k;
-  const int i = first + k, t = (int) r[6];
+  const long long tm = (long long) r[6]; // type + 64 * mask (dd_pack_leavers_kernel)
+  const int i = first + k, t = (int) (tm & 63);
+  if (mask) mask[i] = (int) (unsigned) (tm >> 6);
   xq[i] = make_double4(r[0], r[1], r[2], (double) map[t]);
   v[3 * (size_t) i] = r[3];
   v[3 * (size_t) i + 1] = r[4];
@@ -180,7 +185,8 @@ __global__ __launch_bounds__(256) void dd_permute_kernel(const int n, const int 
                                                          const int *__restrict__ type_in, const int *__restrict__ tag_in,
                                                          const double *__restrict__ mass_type, double4 *__restrict__ xq,
                                                          double *__restrict__ v, int *__restrict__ type,
-                                                         int *__restrict__ tag, double *__restrict__ rmass)
+                                                         int *__restrict__ tag, double *__restrict__ rmass,
+                                                         const int *__restrict__ mask_in, int *__restrict__ mask)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -193,6 +199,7 @@ __global__ __launch_bounds__(256) void dd_permute_kernel(const int n, const int 
   type[i] = t;
   tag[i] = tag_in[o];
   rmass[i] = mass_type[t];
+  if (mask) mask[i] = mask_in[o]; // (the mask follows its atom)
 }
 
 // 4. borders.  Per dimension the (image shift, brick) pairs whose shell [lo_b - c, hi_b + c) holds lam + shift;
@@ -424,6 +431,7 @@ void mdp_dd_release(mdp_ctx *c)
   D.sendlist.release();
   D.type_tmp.release();
   D.tag_tmp.release();
+  D.mask_tmp.release();
   D.key_a.release();
   D.key_b.release();
   D.sendshift.release();
@@ -533,7 +541,7 @@ int mdp_dd_migrate_pack(mdp_ctx *c, double *d_buf)
   int *seg = D.counters.p + G.nranks, *cur = D.counters.p + 2 * G.nranks;
   MDP_TRY(mdp_write_small(c, seg, off.data(), sizeof(int) * 2 * G.nranks)); // cursors = 0
   dd_pack_leavers_kernel<<<nblk(D.nlocal_old), 256, 0, st>>>(D.nlocal_old, G.rank, D.dest.p, seg, cur, c->xq.p, c->v.p,
-                                                             c->type.p, c->tag.p, d_buf);
+                                                             c->type.p, c->tag.p, c->mask_set ? c->mask.p : nullptr, d_buf);
   MDP_HIP(c, hipGetLastError());
   MDP_HIP(c, hipStreamSynchronize(st)); // `off` is a host temporary
   return MDP_OK;
@@ -554,6 +562,7 @@ int mdp_dd_migrate_end(mdp_ctx *c, int narrive, const double *d_buf)
   MDP_HIP(c, c->type.reserve((size_t) ntot + 32, true, st));
   MDP_HIP(c, c->tag.reserve((size_t) ntot + 1, true, st));
   MDP_HIP(c, D.dest.reserve((size_t) ntot + 1, true, st));
+  if (c->mask_set) MDP_HIP(c, c->mask.reserve((size_t) ntot + 1, true, st));
   MDP_HIP(c, c->mass_type.reserve(32));
   MDP_HIP(c, hipMemcpyAsync(c->mass_type.p, c->h_mass, sizeof(double) * 16, hipMemcpyHostToDevice, st));
   // the type -> element map rides behind the types (mdp_pack_xq); park a copy where the kernels below can read it
@@ -561,7 +570,7 @@ int mdp_dd_migrate_end(mdp_ctx *c, int narrive, const double *d_buf)
   MDP_HIP(c, hipMemcpyAsync(d_map, c->map, sizeof(int) * 16, hipMemcpyHostToDevice, st));
   if (narrive)
     dd_unpack_arrivals_kernel<<<nblk(narrive), 256, 0, st>>>(narrive, nold, d_buf, d_map, c->xq.p, c->v.p, c->type.p,
-                                                             c->tag.p, D.dest.p, G.rank);
+                                                             c->tag.p, c->mask_set ? c->mask.p : nullptr, D.dest.p, G.rank);
   MDP_HIP(c, D.key_a.reserve((size_t) ntot + 1));
   MDP_HIP(c, D.key_b.reserve((size_t) ntot + 1));
   MDP_HIP(c, D.idx_a.reserve((size_t) ntot + 1));
@@ -572,6 +581,7 @@ int mdp_dd_migrate_end(mdp_ctx *c, int narrive, const double *d_buf)
   MDP_HIP(c, D.v_tmp.reserve((size_t) 3 * nnew + 3));
   MDP_HIP(c, D.type_tmp.reserve(room + 32));
   MDP_HIP(c, D.tag_tmp.reserve(room + 1));
+  if (c->mask_set) MDP_HIP(c, D.mask_tmp.reserve((size_t) nnew + 1));
   MDP_HIP(c, c->rmass.reserve((size_t) nnew + 1));
   if (ntot) {
     const int shell_last = c->cfg.style == 2;
@@ -586,13 +596,18 @@ int mdp_dd_migrate_end(mdp_ctx *c, int narrive, const double *d_buf)
   }
   if (nnew) {
     dd_permute_kernel<<<nblk(nnew), 256, 0, st>>>(nnew, D.idx_b.p, c->xq.p, c->v.p, c->type.p, c->tag.p, c->mass_type.p,
-                                                  D.xq_tmp.p, D.v_tmp.p, D.type_tmp.p, D.tag_tmp.p, c->rmass.p);
+                                                  D.xq_tmp.p, D.v_tmp.p, D.type_tmp.p, D.tag_tmp.p, c->rmass.p,
+                                                  c->mask_set ? c->mask.p : nullptr, c->mask_set ? D.mask_tmp.p : nullptr);
     MDP_HIP(c, hipGetLastError());
   }
   swap_buf(c->xq, D.xq_tmp);
   swap_buf(c->v, D.v_tmp);
   swap_buf(c->type, D.type_tmp);
   swap_buf(c->tag, D.tag_tmp);
+  if (c->mask_set) {
+    swap_buf(c->mask, D.mask_tmp);
+    c->mask_n = nnew;
+  }
   c->nlocal = nnew;
   c->nghost = 0;
   c->nall = nnew;
@@ -855,12 +870,16 @@ int mdp_md_integrate_check(mdp_ctx *c, int with_final, int *moved, int *dangerou
   return mdp_moved_post(c, c->sflag_armed && c->sflag_committed[c->sflag_set]);
 }
 
-// owned atoms' integer properties in device order ("tag", "type"); the device re-orders atoms at every reneighboring
+// owned atoms' integer properties in device order ("tag", "type", "mask"); the device re-orders atoms at every reneighboring
 int mdp_md_download_int(mdp_ctx *c, const char *name, int *out)
 {
   if (!c || !name || !out) return MDP_EINVAL;
   if (!c->md) return mdp_fail(c, MDP_ESTATE, "mdp_md_setup not called");
   const int *src = !strcmp(name, "tag") ? c->tag.p : (!strcmp(name, "type") ? c->type.p : nullptr);
+  if (!strcmp(name, "mask")) {
+    if (!c->mask_set) return mdp_fail(c, MDP_ESTATE, "mdp_md_download_int: no mask set (mdp_md_set_mask)");
+    src = c->mask.p;
+  }
   MDP_HIP(c, hipSetDevice(c->device));
   if (!strcmp(name, "tile_nu")) { // diagnostics: {members of the union, Mo members} of every tile, 2 * ntile <= nlocal ints
     if (2 * c->ntile > c->nlocal) return mdp_fail(c, MDP_EINVAL, "mdp_md_download_int: tile_nu needs 2 * %d ints", c->ntile);

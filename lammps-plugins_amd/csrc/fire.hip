@@ -13,6 +13,7 @@
 #include "mdp_common.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -24,14 +25,20 @@ struct FireArgs {
   const double *acc; // acc[0]: the energy of the last compute (with_energy)
 };
 
+// MASK: held atoms (outside the integrate group, MdpGroupArgs) are left out of the sums and the maximum -- what LAMMPS
+// sees with fix setforce 0 0 0 on them -- and still reach the shuffles and the block sum
+template <bool MASK>
 __global__ __launch_bounds__(256) void fire_sums_kernel(const int n, const double *__restrict__ v,
                                                         const double *__restrict__ f, double *__restrict__ part,
-                                                        double *__restrict__ pmax)
+                                                        double *__restrict__ pmax, const MdpGroupArgs M)
 {
   __shared__ double wmax[4];
   const int i = blockIdx.x * 256 + threadIdx.x;
   double e[3] = {0.0, 0.0, 0.0}, m = 0.0;
-  if (i < n) {
+  bool in = i < n;
+  if constexpr (MASK)
+    if (in) in = mdp_group_moves(M, mdp_group_mask(M, i));
+  if (in) {
     const double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
     const double fx = f[3 * (size_t) i], fy = f[3 * (size_t) i + 1], fz = f[3 * (size_t) i + 2];
     e[0] = mdp_dot3(vx, fx, vy, fy, vz, fz);
@@ -132,14 +139,16 @@ __global__ __launch_bounds__(256) void fire_control_kernel(const double *__restr
 // from the velocity it has now is capped by dmax per component (the control kernel shortens dtv so that dtv max|v_c| <=
 // dmax); the forces of this iteration stand for the next ones.  Two and a half of that, as in the integrate kernel.
 // Once the stop code is latched the kernel moves nothing and votes for nothing; the resets still serve the compute.
-template <bool CHECK>
+// MASK: a held atom (outside the integrate group) keeps x and v; its force is cleared like any other, and it votes with
+// the position it has and no reach.
+template <bool CHECK, bool MASK>
 __global__ __launch_bounds__(256) void fire_advance_kernel(const int nlocal, const double ftm2v, const double dmax,
                                                            const double dtgrow, const double dtmax, const int halfstepback,
                                                            const double *__restrict__ st, const double *__restrict__ rmass,
                                                            double *__restrict__ f, double *__restrict__ v,
                                                            double4 *__restrict__ xq, const mdp_hold_t *__restrict__ xhold,
                                                            const double trigsq, const double hardsq, int *__restrict__ flag,
-                                                           const MdpStyleCheck SC, const int zero_f)
+                                                           const MdpStyleCheck SC, const int zero_f, const MdpGroupArgs M)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   bool t = false, h = false;
@@ -163,7 +172,18 @@ __global__ __launch_bounds__(256) void fire_advance_kernel(const int nlocal, con
       f[3 * (size_t) i + 1] = 0.0;
       f[3 * (size_t) i + 2] = 0.0;
     }
-    if (live) {
+    bool held = false;
+    if constexpr (MASK) held = !mdp_group_moves(M, mdp_group_mask(M, i));
+    if (live && held) { // (MASK only)
+      const double4 x = xq[i];
+      if (CHECK) {
+        const double dx = x.x - xhold[3 * (size_t) i], dy = x.y - xhold[3 * (size_t) i + 1], dz = x.z - xhold[3 * (size_t) i + 2];
+        const double d2 = dx * dx + dy * dy + dz * dz;
+        t = d2 > trigsq;
+        h = d2 > hardsq;
+      }
+      mdp_style_test(SC, (size_t) i, x, 0.0, w);
+    } else if (live) {
       const double dtv = st[kFireDtv], s2 = st[kFireS2];
       double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
       double4 x = xq[i];
@@ -219,6 +239,14 @@ __global__ __launch_bounds__(256) void fire_advance_kernel(const int nlocal, con
   mdp_style_vote(SC, w, 0);
 }
 
+// mdp_fire_setup with an integrate group: the moving atoms start from rest, the held ones keep their velocities
+__global__ void fire_rest_kernel(const int n, double *__restrict__ v, const MdpGroupArgs M)
+{
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= 3 * n) return;
+  if (mdp_group_moves(M, mdp_group_mask(M, k / 3))) v[k] = 0.0;
+}
+
 double *fire_pin(mdp_ctx *c) { return c->h_pinned + kPinFire; }
 
 // the sums of the current v and f, then the control kernel (peek: sum f.f alone)
@@ -228,8 +256,12 @@ int fire_sums_control(mdp_ctx *c, bool peek)
   const mdp_fire_config &g = F.cfg;
   hipStream_t st = c->stream;
   const int n = c->nlocal, nb = n ? nblk(n) : 0;
+  bool masked = false;
+  MdpGroupArgs M;
+  MDP_TRY(mdp_group_args(c, &masked, &M));
   MDP_HIP(c, F.part.reserve((size_t) 4 * nb + 4));
-  if (n) fire_sums_kernel<<<nb, 256, 0, st>>>(n, c->v.p, c->f.p, F.part.p, F.part.p + 3 * (size_t) nb);
+  if (n && masked) fire_sums_kernel<true><<<nb, 256, 0, st>>>(n, c->v.p, c->f.p, F.part.p, F.part.p + 3 * (size_t) nb, M);
+  else if (n) fire_sums_kernel<false><<<nb, 256, 0, st>>>(n, c->v.p, c->f.p, F.part.p, F.part.p + 3 * (size_t) nb, M);
   FireArgs a;
   a.npart = nb;
   a.peek = peek ? 1 : 0;
@@ -278,14 +310,23 @@ int mdp_fire_launch_advance(mdp_ctx *c, int *flag, double trigsq, double hardsq,
   const MdpFire &F = c->fire;
   const mdp_fire_config &g = F.cfg;
   const double dtmax = g.tmax * F.dt0;
-  if (flag)
-    fire_advance_kernel<true><<<nblk(n), 256, 0, c->stream>>>(n, c->cfg.ftm2v, g.dmax, g.dtgrow, dtmax, g.halfstepback, F.st.p,
-                                                              c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p, trigsq, hardsq,
-                                                              flag, sc, zero_f ? 1 : 0);
-  else
-    fire_advance_kernel<false><<<nblk(n), 256, 0, c->stream>>>(n, c->cfg.ftm2v, g.dmax, g.dtgrow, dtmax, g.halfstepback, F.st.p,
-                                                               c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p, 0.0, 0.0,
-                                                               nullptr, sc, zero_f ? 1 : 0);
+  bool masked = false;
+  MdpGroupArgs M;
+  MDP_TRY(mdp_group_args(c, &masked, &M));
+  auto launch = [&](auto cv, auto mv) {
+    fire_advance_kernel<decltype(cv)::value, decltype(mv)::value><<<nblk(n), 256, 0, c->stream>>>(
+        n, c->cfg.ftm2v, g.dmax, g.dtgrow, dtmax, g.halfstepback, F.st.p, c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p,
+        flag ? trigsq : 0.0, flag ? hardsq : 0.0, flag, sc, zero_f ? 1 : 0, M);
+  };
+  constexpr std::true_type T;
+  constexpr std::false_type F_;
+  if (flag) {
+    if (masked) launch(T, T);
+    else launch(T, F_);
+  } else {
+    if (masked) launch(F_, T);
+    else launch(F_, F_);
+  }
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }
@@ -322,7 +363,14 @@ int mdp_fire_setup(mdp_ctx *c, const mdp_fire_config *cfg)
   F.cfg = *cfg;
   F.dt0 = c->cfg.dt;
   MDP_HIP(c, F.st.reserve(kFireWords));
-  if (c->nlocal) MDP_HIP(c, hipMemsetAsync(c->v.p, 0, sizeof(double) * 3 * (size_t) c->nlocal, c->stream));
+  bool masked = false;
+  MdpGroupArgs M;
+  MDP_TRY(mdp_group_args(c, &masked, &M));
+  if (c->nlocal && masked) {
+    fire_rest_kernel<<<nblk(3 * (long long) c->nlocal), 256, 0, c->stream>>>(c->nlocal, c->v.p, M);
+    MDP_HIP(c, hipGetLastError());
+  } else if (c->nlocal)
+    MDP_HIP(c, hipMemsetAsync(c->v.p, 0, sizeof(double) * 3 * (size_t) c->nlocal, c->stream));
   MDP_TRY(mdp_md_compute(c, 1, 0));
   double th[9];
   MDP_TRY(mdp_md_thermo(c, th));

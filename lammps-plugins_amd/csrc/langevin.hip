@@ -17,11 +17,17 @@
 namespace {
 
 // zero yes: part[3 b + k] = the sum over block b of the random parts fran_k of the step (mdp_lgv_random)
-__global__ __launch_bounds__(256) void lgv_zero_kernel(const int n, const MdpLgvArgs L, double *__restrict__ part)
+// MASK: of the Langevin group's atoms alone (MdpGroupArgs); the others add 0 and still reach the block sum
+template <bool MASK>
+__global__ __launch_bounds__(256) void lgv_zero_kernel(const int n, const MdpLgvArgs L, double *__restrict__ part,
+                                                       const MdpGroupArgs M)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   double r[3] = {0.0, 0.0, 0.0};
-  if (i < n) mdp_lgv_random(L, i, r[0], r[1], r[2]);
+  bool in = i < n;
+  if constexpr (MASK)
+    if (in) in = mdp_group_lgv(M, mdp_group_mask(M, i));
+  if (in) mdp_lgv_random(L, i, r[0], r[1], r[2]);
   mdp_block_sum_256<3>(r, part);
 }
 
@@ -100,7 +106,11 @@ int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvA
     L->mean = nullptr;
     L->part = h.cfg.tally ? h.part.p + (size_t) 3 * nb : nullptr;
     if (h.cfg.zero) {
-      if (n) lgv_zero_kernel<<<nb, 256, 0, c->stream>>>(n, *L, h.part.p);
+      bool masked = false;
+      MdpGroupArgs M;
+      MDP_TRY(mdp_group_args(c, &masked, &M));
+      if (n && masked) lgv_zero_kernel<true><<<nb, 256, 0, c->stream>>>(n, *L, h.part.p, M);
+      else if (n) lgv_zero_kernel<false><<<nb, 256, 0, c->stream>>>(n, *L, h.part.p, M);
       lgv_mean_kernel<<<1, 256, 0, c->stream>>>(h.part.p, n ? nb : 0, (double) h.cfg.natoms, h.st.p);
       MDP_HIP(c, hipGetLastError());
       L->mean = h.st.p + kLgvMean;

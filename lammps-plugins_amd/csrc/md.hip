@@ -229,13 +229,13 @@ __global__ __launch_bounds__(256) void ang_select_kernel(const int nlocal, const
 // LANGEVIN: this kernel is the first reader of the compute's forces and adds the Langevin force of the step (L,
 // langevin.hip) to them in registers, from the velocities it reads; L.part: the per-block sums of f_L . v for the tally
 // (v after the final half; with FINAL = false the setup force, and v as read).  LANGEVIN = false never reads L.
-template <bool FINAL, bool CHECK, bool SCALE, bool LANGEVIN>
+template <bool FINAL, bool CHECK, bool SCALE, bool LANGEVIN, bool MASK>
 __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const double *__restrict__ rmass,
                                    double *__restrict__ f, double *__restrict__ v, double4 *__restrict__ xq,
                                    const mdp_hold_t *__restrict__ xhold, const double trigsq, const double hardsq,
                                    int *__restrict__ flag, const MdpStyleCheck SC, const int zero_f,
                                    double *__restrict__ dflag_set, double *__restrict__ dflag_clear,
-                                   const double *__restrict__ vscale, const MdpLgvArgs L)
+                                   const double *__restrict__ vscale, const MdpLgvArgs L, const MdpGroupArgs M)
 {
   double lgv_e = 0.0; // (LANGEVIN, tally: f_L . v of this atom)
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -254,46 +254,66 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
       SC.flags[i] = 0;
   }
   if (i < nlocal) {
-    const double s = dtf / rmass[i];
-    double fx = f[3 * (size_t) i], fy = f[3 * (size_t) i + 1], fz = f[3 * (size_t) i + 2];
-    if (zero_f) { // the forces have had their last reader: force_clear of the next compute (a style that accumulates)
-      f[3 * (size_t) i] = 0.0;
-      f[3 * (size_t) i + 1] = 0.0;
-      f[3 * (size_t) i + 2] = 0.0;
+    // MASK: an atom outside the integrate group keeps x and v bit for bit and skips ONLY their update -- the force clear,
+    // the displacement check and the style test below still see it (at rest: no two_steps), and it stays in every vote
+    // and block sum with nothing to add; one outside the Langevin group is advanced by the compute's forces alone
+    bool move = true, lgv = LANGEVIN;
+    if constexpr (MASK) {
+      const int m = mdp_group_mask(M, i);
+      move = mdp_group_moves(M, m);
+      lgv = LANGEVIN && mdp_group_lgv(M, m);
     }
-    double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
-    double lx = 0.0, ly = 0.0, lz = 0.0;
-    if (LANGEVIN) { // post_force of step n (or the setup force): f += f_L, kept for both half-kicks
-      mdp_lgv_force(L, i, vx, vy, vz, lx, ly, lz);
-      fx = fx + lx;
-      fy = fy + ly;
-      fz = fz + lz;
+    double4 x;
+    double two_steps = 0.0;
+    if (move) {
+      const double s = dtf / rmass[i];
+      double fx = f[3 * (size_t) i], fy = f[3 * (size_t) i + 1], fz = f[3 * (size_t) i + 2];
+      if (zero_f) { // the forces have had their last reader: force_clear of the next compute (a style that accumulates)
+        f[3 * (size_t) i] = 0.0;
+        f[3 * (size_t) i + 1] = 0.0;
+        f[3 * (size_t) i + 2] = 0.0;
+      }
+      double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
+      double lx = 0.0, ly = 0.0, lz = 0.0;
+      if (lgv) { // post_force of step n (or the setup force): f += f_L, kept for both half-kicks
+        mdp_lgv_force(L, i, vx, vy, vz, lx, ly, lz);
+        fx = fx + lx;
+        fy = fy + ly;
+        fz = fz + lz;
+      }
+      if (FINAL) { // final_integrate (step n)
+        vx += s * fx;
+        vy += s * fy;
+        vz += s * fz;
+      }
+      if (lgv && L.part) lgv_e = mdp_dot3(lx, vx, ly, vy, lz, vz); // (end_of_step of step n: v after the final half; x first HERE, y first in lgv_final_kernel: the orders each kernel has always had -- keep both)
+      if (SCALE) { // the thermostat's factor (nhc.hip): final half of step n (if FINAL) times initial half of step n+1
+        const double S = *vscale;
+        vx *= S;
+        vy *= S;
+        vz *= S;
+      }
+      vx = vx + s * fx; // initial_integrate (step n+1)
+      vy = vy + s * fy;
+      vz = vz + s * fz;
+      v[3 * (size_t) i] = vx;
+      v[3 * (size_t) i + 1] = vy;
+      v[3 * (size_t) i + 2] = vz;
+      x = xq[i];
+      x.x += dt * vx;
+      x.y += dt * vy;
+      x.z += dt * vz;
+      xq[i] = x;
+      // (the atom's own two steps: this step's speed, a quarter on top for its acceleration -- see mdp_reaches)
+      two_steps = (CHECK || SC.xa || SC.xp) ? 2.5 * dt * sqrt(vx * vx + vy * vy + vz * vz) : 0.0;
+    } else { // (MASK only)
+      if (zero_f) {
+        f[3 * (size_t) i] = 0.0;
+        f[3 * (size_t) i + 1] = 0.0;
+        f[3 * (size_t) i + 2] = 0.0;
+      }
+      x = xq[i];
     }
-    if (FINAL) { // final_integrate (step n)
-      vx += s * fx;
-      vy += s * fy;
-      vz += s * fz;
-    }
-    if (LANGEVIN && L.part) lgv_e = mdp_dot3(lx, vx, ly, vy, lz, vz); // (end_of_step of step n: v after the final half; x first HERE, y first in lgv_final_kernel: the orders each kernel has always had -- keep both)
-    if (SCALE) { // the thermostat's factor (nhc.hip): final half of step n (if FINAL) times initial half of step n+1
-      const double S = *vscale;
-      vx *= S;
-      vy *= S;
-      vz *= S;
-    }
-    vx = vx + s * fx; // initial_integrate (step n+1)
-    vy = vy + s * fy;
-    vz = vz + s * fz;
-    v[3 * (size_t) i] = vx;
-    v[3 * (size_t) i + 1] = vy;
-    v[3 * (size_t) i + 2] = vz;
-    double4 x = xq[i];
-    x.x += dt * vx;
-    x.y += dt * vy;
-    x.z += dt * vz;
-    xq[i] = x;
-    // (the atom's own two steps: this step's speed, a quarter on top for its acceleration -- see mdp_reaches)
-    const double two_steps = (CHECK || SC.xa || SC.xp) ? 2.5 * dt * sqrt(vx * vx + vy * vy + vz * vz) : 0.0;
     if (CHECK) {
       const double dx = x.x - xhold[3 * (size_t) i], dy = x.y - xhold[3 * (size_t) i + 1], dz = x.z - xhold[3 * (size_t) i + 2];
       const double d2 = dx * dx + dy * dy + dz * dz;
@@ -322,11 +342,15 @@ __global__ void hn_rmass_kernel(const int nlocal, const int *__restrict__ type, 
   if (p < nlocal) rmass[p] = mass_type[type[perm ? perm[p] : p] & 15];
 }
 
+// MASK: atoms outside the integrate group are left alone (MdpGroupArgs)
+template <bool MASK>
 __global__ void nve_final_kernel(int nlocal, double dtf, const double *__restrict__ rmass,
-                                 const double *__restrict__ f, double *__restrict__ v)
+                                 const double *__restrict__ f, double *__restrict__ v, const MdpGroupArgs M)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= nlocal) return;
+  if constexpr (MASK)
+    if (!mdp_group_moves(M, mdp_group_mask(M, i))) return;
   const double s = dtf / rmass[i];
   v[3 * (size_t) i] += s * f[3 * (size_t) i];
   v[3 * (size_t) i + 1] += s * f[3 * (size_t) i + 1];
@@ -335,31 +359,46 @@ __global__ void nve_final_kernel(int nlocal, double dtf, const double *__restric
 
 // a final half on its own with the Langevin force (langevin.hip): f += f_L is written back (writeback), so that the
 // initial half of the next step kicks with the same modified forces (LAMMPS keeps them in atom->f); L.part: the
-// tally's partials
+// tally's partials.  MASK: an atom outside the integrate group is left alone, one outside the Langevin group gets the
+// plain half-kick; both add nothing to the tally and reach its block sum
+template <bool MASK>
 __global__ __launch_bounds__(256) void lgv_final_kernel(int nlocal, double dtf, const double *__restrict__ rmass,
                                                         double *__restrict__ f, double *__restrict__ v, const MdpLgvArgs L,
-                                                        const int writeback)
+                                                        const int writeback, const MdpGroupArgs M)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   double e = 0.0;
   if (i < nlocal) {
-    const double s = dtf / rmass[i];
-    double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
-    double lx, ly, lz;
-    mdp_lgv_force(L, i, vx, vy, vz, lx, ly, lz);
-    const double fx = f[3 * (size_t) i] + lx, fy = f[3 * (size_t) i + 1] + ly, fz = f[3 * (size_t) i + 2] + lz;
-    if (writeback) {
-      f[3 * (size_t) i] = fx;
-      f[3 * (size_t) i + 1] = fy;
-      f[3 * (size_t) i + 2] = fz;
+    bool move = true, lgv = true;
+    if constexpr (MASK) {
+      const int m = mdp_group_mask(M, i);
+      move = mdp_group_moves(M, m);
+      lgv = mdp_group_lgv(M, m);
     }
-    vx += s * fx;
-    vy += s * fy;
-    vz += s * fz;
-    v[3 * (size_t) i] = vx;
-    v[3 * (size_t) i + 1] = vy;
-    v[3 * (size_t) i + 2] = vz;
-    e = mdp_dot3(ly, vy, lx, vx, lz, vz); // (y first: the order this kernel has always had, and the tally's last bit depends on it)
+    if (lgv) {
+      const double s = dtf / rmass[i];
+      double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
+      double lx, ly, lz;
+      mdp_lgv_force(L, i, vx, vy, vz, lx, ly, lz);
+      const double fx = f[3 * (size_t) i] + lx, fy = f[3 * (size_t) i + 1] + ly, fz = f[3 * (size_t) i + 2] + lz;
+      if (writeback) {
+        f[3 * (size_t) i] = fx;
+        f[3 * (size_t) i + 1] = fy;
+        f[3 * (size_t) i + 2] = fz;
+      }
+      vx += s * fx;
+      vy += s * fy;
+      vz += s * fz;
+      v[3 * (size_t) i] = vx;
+      v[3 * (size_t) i + 1] = vy;
+      v[3 * (size_t) i + 2] = vz;
+      e = mdp_dot3(ly, vy, lx, vx, lz, vz); // (y first: the order this kernel has always had, and the tally's last bit depends on it)
+    } else if (move) { // (MASK only)
+      const double s = dtf / rmass[i];
+      v[3 * (size_t) i] += s * f[3 * (size_t) i];
+      v[3 * (size_t) i + 1] += s * f[3 * (size_t) i + 1];
+      v[3 * (size_t) i + 2] += s * f[3 * (size_t) i + 2];
+    }
   }
   if (L.part) mdp_block_sum_256(e, L.part);
 }
@@ -576,12 +615,17 @@ __global__ void x3_to_xq_kernel(int n, const double *__restrict__ x3, double4 *_
 // initial half that follows kicks with these forces (false: the forces of a new run's setup come next instead)
 int lgv_final(mdp_ctx *c, bool writeback)
 {
-  bool apply = false;
+  bool apply = false, masked = false;
   MdpLgvArgs L;
+  MdpGroupArgs M;
+  MDP_TRY(mdp_group_args(c, &masked, &M));
   MDP_TRY(mdp_lgv_open(c, false, false, &apply, &L));
-  if (c->nlocal)
-    lgv_final_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, L,
-                                                             writeback ? 1 : 0);
+  if (c->nlocal && masked)
+    lgv_final_kernel<true><<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, L,
+                                                                   writeback ? 1 : 0, M);
+  else if (c->nlocal)
+    lgv_final_kernel<false><<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, L,
+                                                                    writeback ? 1 : 0, M);
   MDP_HIP(c, hipGetLastError());
   return mdp_lgv_close(c, L);
 }
@@ -592,7 +636,13 @@ int md_final_half(mdp_ctx *c, bool lgv_writeback = true)
 {
   if (c->nhc.on) return mdp_nhc_final(c);
   if (c->lgv.on) return lgv_final(c, lgv_writeback);
-  if (c->nlocal) nve_final_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p);
+  bool masked = false;
+  MdpGroupArgs M;
+  MDP_TRY(mdp_group_args(c, &masked, &M));
+  if (c->nlocal && masked)
+    nve_final_kernel<true><<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, M);
+  else if (c->nlocal)
+    nve_final_kernel<false><<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, M);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }
@@ -611,25 +661,32 @@ int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, dou
     with_final = false;
   }
   const double *vscale = nullptr;
-  bool lgv = false;
+  bool lgv = false, masked = false;
   MdpLgvArgs L;
+  MdpGroupArgs M;
+  MDP_TRY(mdp_group_args(c, &masked, &M)); // (before a thermostat counts the step)
   if (c->nhc.on) MDP_TRY(mdp_nhc_open(c, with_final, &vscale));
   if (c->lgv.on) MDP_TRY(mdp_lgv_open(c, with_final, true, &lgv, &L));
   const int n = c->nlocal;
   if (!n) return MDP_OK;
   const MdpStep s = mdp_step(c);
-  // FINAL x CHECK x {plain, SCALE, LANGEVIN}: the twelve instantiations (one thermostat per context: never both)
-  auto launch = [&](auto fv, auto cv, auto sv, auto lv) {
-    nve_advance_kernel<decltype(fv)::value, decltype(cv)::value, decltype(sv)::value, decltype(lv)::value>
+  // FINAL x CHECK x {plain, SCALE, LANGEVIN}: the twelve instantiations (one thermostat per context: never both), and
+  // their twelve MASK twins, which only a context with a group set ever launches
+  auto launch = [&](auto fv, auto cv, auto sv, auto lv, auto mv) {
+    nve_advance_kernel<decltype(fv)::value, decltype(cv)::value, decltype(sv)::value, decltype(lv)::value, decltype(mv)::value>
         <<<nblk(n), 256, 0, c->stream>>>(n, s.dtf, s.dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p, trigsq, hardsq, flag, sc,
-                                         zero_f ? 1 : 0, dset, dclr, vscale, L);
+                                         zero_f ? 1 : 0, dset, dclr, vscale, L, M);
   };
   constexpr std::true_type T;
   constexpr std::false_type F;
+  auto group = [&](auto fv, auto cv, auto sv, auto lv) {
+    if (masked) launch(fv, cv, sv, lv, T);
+    else launch(fv, cv, sv, lv, F);
+  };
   auto thermostat = [&](auto fv, auto cv) {
-    if (vscale) launch(fv, cv, T, F);
-    else if (lgv) launch(fv, cv, F, T);
-    else launch(fv, cv, F, F);
+    if (vscale) group(fv, cv, T, F);
+    else if (lgv) group(fv, cv, F, T);
+    else group(fv, cv, F, F);
   };
   auto check = [&](auto fv) {
     if (flag) thermostat(fv, T);
@@ -643,6 +700,39 @@ int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, dou
 }
 
 } // namespace
+
+// ---- groups (mdp_integrate_group, mdp_langevin_group) ---------------------------------------------
+int mdp_group_args(mdp_ctx *c, bool *masked, MdpGroupArgs *M)
+{
+  const int lbit = c->lgv.on ? c->lgv_bit : 0;
+  *masked = c->group_bit != 0 || lbit != 0;
+  if (!*masked) return MDP_OK;
+  if (!c->mask_set || c->mask_n != c->nlocal)
+    return mdp_fail(c, MDP_ESTATE, "a group is set (mdp_integrate_group / mdp_langevin_group) but no mask covers the current atoms (%s)",
+                    c->md ? "mdp_md_set_mask" : "mdp_hnve_set_mask after mdp_set_atoms_host");
+  M->mask = c->mask.p;
+  M->perm = !c->md && c->host_sort ? c->host_perm.p : nullptr; // host mode: the mask is in the host's order, as tags and types are
+  M->gbit = c->group_bit;
+  M->lbit = lbit;
+  return MDP_OK;
+}
+
+static int set_mask(mdp_ctx *c, const int *mask)
+{
+  if (!mask) {
+    c->mask_set = false;
+    c->mask_n = 0;
+    return MDP_OK;
+  }
+  MDP_HIP(c, hipSetDevice(c->device));
+  const int n = c->nlocal;
+  MDP_HIP(c, c->mask.reserve((size_t) n + 1));
+  if (n) MDP_TRY(mdp_host_upload(c, c->mask.p, mask, sizeof(int) * (size_t) n));
+  MDP_HIP(c, hipStreamSynchronize(c->stream)); // the caller's array may change after return
+  c->mask_set = true;
+  c->mask_n = n;
+  return MDP_OK;
+}
 
 // ---- the per-atom helpers other translation units launch -----------------------------------------
 
@@ -922,6 +1012,43 @@ int mdp_md_setup(mdp_ctx *c, const mdp_md_config *cfg, const double *x, const do
       return mdp_fail(c, MDP_EINVAL, "mdp_md_setup: ghost %d is declared a periodic self-image (nghost_self = %d) but has no owner",
                       g, c->remote_start - nlocal);
   c->md = true;
+  c->mask_set = false; // (a mask belongs to the atoms it was set for)
+  c->mask_n = 0;
+  return MDP_OK;
+}
+
+int mdp_md_set_mask(mdp_ctx *c, const int *mask)
+{
+  if (!c) return MDP_EINVAL;
+  if (!c->md) return mdp_fail(c, MDP_ESTATE, "mdp_md_setup not called");
+  MDP_TRY(mdp_md_flush_final(c)); // (a final half the host deferred belongs to the atoms as they were grouped)
+  return set_mask(c, mask);
+}
+
+int mdp_hnve_set_mask(mdp_ctx *c, const int *mask)
+{
+  if (!c) return MDP_EINVAL;
+  if (c->md) return mdp_fail(c, MDP_ESTATE, "mdp_hnve_set_mask: a resident-mode context takes its mask through mdp_md_set_mask");
+  if (!c->hn_on) return mdp_fail(c, MDP_ESTATE, "mdp_hnve_setup not called");
+  if (!c->atoms_set) return mdp_fail(c, MDP_ESTATE, "atoms not set");
+  return set_mask(c, mask);
+}
+
+int mdp_integrate_group(mdp_ctx *c, int groupbit)
+{
+  if (!c) return MDP_EINVAL;
+  if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_integrate_group: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
+  if (c->md) MDP_TRY(mdp_md_flush_final(c)); // (the finished step's final half belongs to the group it ran with)
+  c->group_bit = groupbit;
+  return MDP_OK;
+}
+
+int mdp_langevin_group(mdp_ctx *c, int groupbit)
+{
+  if (!c) return MDP_EINVAL;
+  if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_langevin_group: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
+  if (c->md) MDP_TRY(mdp_md_flush_final(c));
+  c->lgv_bit = groupbit;
   return MDP_OK;
 }
 

@@ -918,6 +918,7 @@ int mdp_destroy(mdp_ctx *c)
   c->fire.st.release();
   c->fire.part.release();
   c->fire.fsave.release();
+  c->mask.release();
   if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
   delete c;
   return MDP_OK;
@@ -1125,6 +1126,7 @@ int mdp_set_atoms_host(mdp_ctx *c, int nlocal, int nghost, const double *x, cons
   if (tag && nall) MDP_HIP(c, hipMemcpyAsync(c->tag.p, tag, sizeof(int) * nall, hipMemcpyHostToDevice, st));
   c->atoms_set = true;
   c->host_check_armed = false;
+  if (!c->md) c->mask_set = false; // (host mode: the mask of the new atoms follows, mdp_hnve_set_mask)
   if (!c->md) { // host mode: bounding box for the device binning, padded so that motion inside the skin stays inside
     double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
     for (int i = 0; i < nall; i++)

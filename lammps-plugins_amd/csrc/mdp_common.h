@@ -212,7 +212,7 @@ struct MdpDomain {
   int mig_total = 0, nself = 0, nsend = 0, nrecv = 0, nent = 0;
   int nlocal_old = 0, nghost_old = 0;
   long long reneighbors = 0;
-  DevBuf<int> dest, counters, idx_a, idx_b, ent_atom, ent_code, ent_cnt, ent_off, sendlist, type_tmp, tag_tmp;
+  DevBuf<int> dest, counters, idx_a, idx_b, ent_atom, ent_code, ent_cnt, ent_off, sendlist, type_tmp, tag_tmp, mask_tmp;
   DevBuf<unsigned long long> key_a, key_b;
   DevBuf<double> sendshift, v_tmp;
   DevBuf<double4> xq_tmp;
@@ -335,6 +335,18 @@ struct MdpLgvArgs {
   double tsqrt = 0.0;           // sqrt(T(n))
   unsigned seed = 0, lo = 0, hi = 0, phase = 0; // the Philox key and counter words of the step
 };
+
+// what the MASK variants of the integrate kernels need to honour the groups (mdp_integrate_group, mdp_langevin_group);
+// the variants without MASK never read it
+struct MdpGroupArgs {
+  const int *mask = nullptr, *perm = nullptr; // owned atom i: mask[perm ? perm[i] : i] (host mode: the host's order)
+  int gbit = 0;                               // 0: every atom is advanced
+  int lbit = 0;                               // 0: every advanced atom receives the Langevin force
+};
+__device__ __forceinline__ int mdp_group_mask(const MdpGroupArgs &M, int i) { return M.mask[M.perm ? M.perm[i] : i]; }
+__device__ __forceinline__ bool mdp_group_moves(const MdpGroupArgs &M, int m) { return !M.gbit || (m & M.gbit); }
+__device__ __forceinline__ bool mdp_group_lgv(const MdpGroupArgs &M, int m)
+{ return mdp_group_moves(M, m) && (!M.lbit || (m & M.lbit)); }
 
 // Philox4x32-10 (Salmon et al., SC11; the Random123 constants), in place on the counter c
 __device__ __forceinline__ void mdp_philox4x32_10(unsigned c[4], unsigned k0, unsigned k1)
@@ -633,6 +645,11 @@ struct mdp_ctx {
   MdpNhc nhc;                      // thermostat of the integrate calls (mdp_nhc_setup)
   MdpLangevin lgv;                 // Langevin thermostat of the integrate calls (mdp_langevin_setup)
   MdpFire fire;                    // FIRE minimiser: mdp_md_advance launches its advance kernel while it is on (mdp_fire_setup)
+  // groups (mdp_md_set_mask / mdp_hnve_set_mask, mdp_integrate_group, mdp_langevin_group)
+  DevBuf<int> mask;                // [nlocal] atom->mask: device order (resident; permuted and migrated with the atoms) or the host's order
+  bool mask_set = false;
+  int mask_n = 0;                  // owned atoms the mask covers (host mode: as of the last mdp_hnve_set_mask)
+  int group_bit = 0, lgv_bit = 0;  // 0: every atom
   bool final_pending = false;      // the host deferred the final half-kick of the finished step (mdp_md_defer_final)
   bool final_deferred_seen = false; // the host uses mdp_md_defer_final at all (older hosts: with_final is authoritative)
   bool acc_prezeroed = false; // the integrate kernel reset the accumulators: the next mdp_acc_begin launches nothing
@@ -812,6 +829,9 @@ int mdp_nhc_final(mdp_ctx *c);
 // *apply = whether this kernel adds the force; if so *L is filled (and the zero pre-pass queued).  Advances the step
 // counter when `initial`.  _close: behind that kernel (the tally of the step).
 int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvArgs *L);
+// groups: *masked = whether the integrate calls take the MASK variants now (a group bit is set), *M filled if so; fails
+// with MDP_ESTATE when a group is set and no mask covers the current atoms
+int mdp_group_args(mdp_ctx *c, bool *masked, MdpGroupArgs *M);
 int mdp_lgv_close(mdp_ctx *c, const MdpLgvArgs &L);
 // FIRE minimiser (fire.hip), in place of the integrate kernel when c->fire.on: the half step back / zeroing and the Euler
 // step of the iteration whose control kernel was queued last, with the same votes, accumulator reset and force clear

@@ -14,14 +14,19 @@
 namespace {
 
 // w_i = v_i (+ dtf / m_i f_i if KICK; stored if STORE); part[block] = sum over the block of m_i |w_i|^2 in a fixed order
-template <bool KICK, bool STORE>
+// MASK: over the integrate group alone (MdpGroupArgs) -- the other atoms are left as they are and add 0 to the sum,
+// which every lane still reaches
+template <bool KICK, bool STORE, bool MASK>
 __global__ __launch_bounds__(256) void nhc_ke_kernel(const int n, const double dtf, const double *__restrict__ rmass,
                                                      const double *__restrict__ f, double *__restrict__ v,
-                                                     double *__restrict__ part)
+                                                     double *__restrict__ part, const MdpGroupArgs M)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   double e = 0.0;
-  if (i < n) {
+  bool in = i < n;
+  if constexpr (MASK)
+    if (in) in = mdp_group_moves(M, mdp_group_mask(M, i));
+  if (in) {
     double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
     if (KICK) { // the same expressions as the integrate kernels' final half-kick
       const double s = dtf / rmass[i];
@@ -44,6 +49,25 @@ __global__ void nhc_scale_kernel(const int n, const double *__restrict__ st, dou
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 3 * n) return;
   v[i] *= st[kNhcS];
+}
+
+// the same for the atoms of the integrate group alone
+__global__ void nhc_scale_group_kernel(const int n, const double *__restrict__ st, double *__restrict__ v, const MdpGroupArgs M)
+{
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= 3 * n) return;
+  if (mdp_group_moves(M, mdp_group_mask(M, k / 3))) v[k] *= st[kNhcS];
+}
+
+// the launch of nhc_ke_kernel with or without the group
+template <bool KICK, bool STORE>
+void nhc_ke_launch(mdp_ctx *c, const int n, const double dtf, const bool masked, const MdpGroupArgs &M)
+{
+  MdpNhc &h = c->nhc;
+  if (masked)
+    nhc_ke_kernel<KICK, STORE, true><<<nblk(n), 256, 0, c->stream>>>(n, dtf, c->rmass.p, c->f.p, c->v.p, h.part.p, M);
+  else
+    nhc_ke_kernel<KICK, STORE, false><<<nblk(n), 256, 0, c->stream>>>(n, dtf, c->rmass.p, c->f.p, c->v.p, h.part.p, M);
 }
 
 enum { kNhcSetup = 1, kNhcFinal = 2, kNhcInitial = 4 };
@@ -182,16 +206,19 @@ int mdp_nhc_open(mdp_ctx *c, bool with_final, const double **vscale)
   hipStream_t st = c->stream;
   const int n = c->nlocal;
   const double dtf = mdp_step(c).dtf;
+  bool masked = false;
+  MdpGroupArgs M;
+  MDP_TRY(mdp_group_args(c, &masked, &M));
   MDP_TRY(nhc_reserve(c, n));
   int mode = kNhcInitial;
   double tt_a = h.tt;
   if (with_final) {
     mode |= kNhcFinal; // H of the finished step at its own target
-    if (n) nhc_ke_kernel<true, false><<<nblk(n), 256, 0, st>>>(n, dtf, c->rmass.p, c->f.p, c->v.p, h.part.p);
+    if (n) nhc_ke_launch<true, false>(c, n, dtf, masked, M);
   } else if (h.need_setup) {
     mode |= kNhcSetup;
     tt_a = nhc_target(h, h.step);
-    if (n) nhc_ke_kernel<false, false><<<nblk(n), 256, 0, st>>>(n, dtf, c->rmass.p, c->f.p, c->v.p, h.part.p);
+    if (n) nhc_ke_launch<false, false>(c, n, dtf, masked, M);
     h.need_setup = false;
   }
   h.step++;
@@ -207,10 +234,14 @@ int mdp_nhc_final(mdp_ctx *c)
   MdpNhc &h = c->nhc;
   hipStream_t st = c->stream;
   const int n = c->nlocal;
+  bool masked = false;
+  MdpGroupArgs M;
+  MDP_TRY(mdp_group_args(c, &masked, &M));
   MDP_TRY(nhc_reserve(c, n));
-  if (n) nhc_ke_kernel<true, true><<<nblk(n), 256, 0, st>>>(n, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, h.part.p);
+  if (n) nhc_ke_launch<true, true>(c, n, mdp_step(c).dtf, masked, M);
   nhc_chain_kernel<<<1, 256, 0, st>>>(h.part.p, h.st.p, nhc_args(c, kNhcFinal, n ? nblk(n) : 0, h.tt, h.tt));
-  if (n) nhc_scale_kernel<<<nblk(3 * (long long) n), 256, 0, st>>>(n, h.st.p, c->v.p);
+  if (n && masked) nhc_scale_group_kernel<<<nblk(3 * (long long) n), 256, 0, st>>>(n, h.st.p, c->v.p, M);
+  else if (n) nhc_scale_kernel<<<nblk(3 * (long long) n), 256, 0, st>>>(n, h.st.p, c->v.p);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }

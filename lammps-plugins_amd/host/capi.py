@@ -97,6 +97,7 @@ EXPORTS = [
     "mdp_nhc_setup", "mdp_nhc_run", "mdp_nhc_state", "mdp_nhc_set_state", "mdp_nhc_off",
     "mdp_langevin_setup", "mdp_langevin_run", "mdp_langevin_tally", "mdp_langevin_off",
     "mdp_fire_setup", "mdp_fire_iterate", "mdp_fire_state", "mdp_fire_off",
+    "mdp_md_set_mask", "mdp_hnve_set_mask", "mdp_integrate_group", "mdp_langevin_group",
 ]
 
 
@@ -730,6 +731,33 @@ class Context:
         out = np.zeros(max(nlocal, 1), dtype=np.int32)
         self._ck(self.L.mdp_md_download_int(self.h, name.encode(), _ip(out)))
         return out[:nlocal]
+
+    # ---------------- groups: the owned atoms' mask and the bits the integrate calls honour
+    def _mask_ptr(self, mask):
+        if mask is None:
+            return None, None
+        m = np.ascontiguousarray(mask, dtype=np.int32)
+        keep = m if len(m) else np.zeros(1, dtype=np.int32)   # (an empty brick still SETS a mask: NULL withdraws it)
+        return keep, _ip(keep)
+
+    def md_set_mask(self, mask):
+        """resident mode: atom->mask of the owned atoms in the current device order (md_download_int("tag") gives it);
+        None withdraws the mask"""
+        keep, ptr = self._mask_ptr(mask)
+        self._ck(self.L.mdp_md_set_mask(self.h, ptr))
+
+    def hnve_set_mask(self, mask):
+        """host-linked mode: atom->mask of the owned atoms in the host's order, after every set_atoms_host; None withdraws it"""
+        keep, ptr = self._mask_ptr(mask)
+        self._ck(self.L.mdp_hnve_set_mask(self.h, ptr))
+
+    def integrate_group(self, groupbit):
+        """the integrate calls advance the atoms with mask & groupbit only (0: every atom)"""
+        self._ck(self.L.mdp_integrate_group(self.h, C.c_int(int(groupbit))))
+
+    def langevin_group(self, groupbit):
+        """the Langevin force goes to the atoms with mask & groupbit (inside the integrate group) only (0: every atom)"""
+        self._ck(self.L.mdp_langevin_group(self.h, C.c_int(int(groupbit))))
 
     # halo plumbing (device pointers as ints)
     def md_pack_x(self, n, d_sendlist, d_shift, d_buf):

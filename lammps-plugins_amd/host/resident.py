@@ -387,12 +387,35 @@ class DeviceDomain:
         else:
             ctx.md_final_integrate()
 
-    def thermostat(self, t_start, t_stop, t_period, tchain=3, tloop=1, drag=0.0, first=0, last=0):
-        """Nose-Hoover chain thermostat (LAMMPS fix nvt on group all) in the integrate calls of this domain, from the
-        chain at rest; one GPU only.  first / last: the ramp of the run that follows (nhc_run)."""
+    def set_group(self, mask_by_tag, integrate_bit, langevin_bit=0):
+        """LAMMPS groups for the integrate calls of this domain: mask_by_tag[t] is atom->mask of the atom with tag t (an
+        integer array indexed by tag; bit 1 on every atom, as in LAMMPS), integrate_bit the group bit of the integrating
+        fix -- every other atom keeps x and v bit for bit --, langevin_bit that of the Langevin thermostat (0: all of the
+        integrate group).  The mask then travels with the atoms (reneighborings, migration).  mask_by_tag=None
+        withdraws the mask and both groups.  With several ranks every rank makes the same call."""
+        self.flush()
+        if mask_by_tag is None:
+            self.ctx.integrate_group(0)
+            self.ctx.langevin_group(0)
+            self.ctx.md_set_mask(None)
+            return
+        m = np.asarray(mask_by_tag)
+        tags = self.tags_local
+        self.ctx.md_set_mask(m[tags].astype(np.int32))
+        self.ctx.integrate_group(integrate_bit)
+        self.ctx.langevin_group(langevin_bit)
+
+    def mask_local(self):
+        """the owned atoms' mask in device order (next to tags_local)"""
+        return self.ctx.md_download_int("mask", self.nlocal)
+
+    def thermostat(self, t_start, t_stop, t_period, tchain=3, tloop=1, drag=0.0, first=0, last=0, nf=None):
+        """Nose-Hoover chain thermostat (LAMMPS fix nvt) in the integrate calls of this domain, from the chain at rest; one
+        GPU only.  first / last: the ramp of the run that follows (nhc_run).  nf: the degrees of freedom, 3 N - 3 of all
+        atoms unless given -- with an integrate group (set_group) 3 N_group - 3."""
         if self.world > 1:
             raise ValueError("the thermostat runs on one GPU only (multi-rank NVT would need a per-step all-reduce)")
-        self.ctx.nhc_setup(t_start, t_stop, t_period, 3.0 * self.natoms_total - 3.0, tchain=tchain, tloop=tloop,
+        self.ctx.nhc_setup(t_start, t_stop, t_period, 3.0 * self.natoms_total - 3.0 if nf is None else float(nf), tchain=tchain, tloop=tloop,
                            drag=drag, boltz=S.BOLTZ, mvv2e=S.MVV2E)
         self.ctx.nhc_run(first, last)
 
@@ -406,12 +429,13 @@ class DeviceDomain:
         self.flush()
         return self.ctx.nhc_state()
 
-    def langevin(self, t_start, t_stop, damp, seed, ratio=None, zero=False, tally=False, first=0, last=0):
-        """Langevin thermostat (LAMMPS fix langevin on group all, noise keyed by tag and step) in the integrate calls of
-        this domain.  zero / tally need one GPU.  first / last: the ramp of the run that follows (langevin_run)."""
+    def langevin(self, t_start, t_stop, damp, seed, ratio=None, zero=False, tally=False, first=0, last=0, natoms=None):
+        """Langevin thermostat (LAMMPS fix langevin, noise keyed by tag and step) in the integrate calls of this domain.
+        zero / tally need one GPU.  first / last: the ramp of the run that follows (langevin_run).  natoms: the atoms
+        `zero` divides by, all of them unless given -- with a Langevin group (set_group) that group's count."""
         if self.world > 1 and (zero or tally):
             raise ValueError("Langevin zero and tally run on one GPU only (they sum over all atoms every step)")
-        self.ctx.langevin_setup(t_start, t_stop, damp, seed, self.natoms_total, ratio=ratio, zero=zero, tally=tally,
+        self.ctx.langevin_setup(t_start, t_stop, damp, seed, self.natoms_total if natoms is None else int(natoms), ratio=ratio, zero=zero, tally=tally,
                                 boltz=S.BOLTZ, mvv2e=S.MVV2E)
         self.ctx.langevin_run(first, last)
 
@@ -434,7 +458,8 @@ class DeviceDomain:
     def minimize(self, etol, ftol, maxiter, maxeval, chunk=64, **modify):
         """FIRE minimisation (LAMMPS min_style fire with its defaults; **modify: capi.FIRE_DEFAULTS) of this domain on the
         device, one GPU only; returns the final state (capi.Context.fire_state).  The velocities are zero afterwards
-        up to what the last iteration left; the time step of the domain is unchanged."""
+        up to what the last iteration left; the time step of the domain is unchanged.  With an integrate group
+        (set_group) only its atoms move: the others are held with their velocities, and the force norm is the group's."""
         if self.world > 1:
             raise ValueError("the minimiser runs on one GPU only (its sums would need an all-reduce per iteration)")
         self.flush()

@@ -55,6 +55,7 @@ class Update;
 class Output;
 class Fix;
 class Modify;
+class Group;
 
 namespace NeighConst {
   enum { REQ_DEFAULT = 0, REQ_FULL = 1 << 0, REQ_GHOST = 1 << 1 };
@@ -107,7 +108,7 @@ class Memory {
 class AtomVec { // Atom::avec: per-atom array storage of the atom style
  public:
   virtual ~AtomVec() = default;
-  virtual void grow(int n) = 0; // room for n atoms (owned + ghost) in x, v, f, type, tag; contents kept (AtomVec::grow)
+  virtual void grow(int n) = 0; // room for n atoms (owned + ghost) in x, v, f, type, mask, tag; contents kept (AtomVec::grow)
 };
 
 class Atom {
@@ -115,11 +116,23 @@ class Atom {
   AtomVec *avec = nullptr;
   double **x = nullptr, **f = nullptr, **v = nullptr;
   int *type = nullptr;
+  int *mask = nullptr; // group membership, one bit per group (bit 1: group all)
   tagint *tag = nullptr;
   double *mass = nullptr;
   int nlocal = 0, nghost = 0, nmax = 0, ntypes = 0, tag_enable = 1;
   bigint natoms = 0;
   void set_mass(const char *file, int line, int itype, double value);
+};
+
+class Group { // the members of LAMMPS' Group a fix style reads (group.h); group 0 is "all" with bit 1
+ public:
+  static constexpr int MAX_GROUP = 32;
+  int ngroup = 0;               // groups defined
+  char **names = nullptr;       // [MAX_GROUP], nullptr where no group is
+  int *bitmask = nullptr;       // [MAX_GROUP]: the bit of atom->mask that means membership
+  int find(const std::string &name); // the group's index, -1 if there is none of this name
+  bigint count(int igroup);          // atoms in the group, over all ranks (collective)
+  void *host = nullptr;         // (the mini-host's own)
 };
 
 class Domain { // the members of LAMMPS' Domain the adapters read (box of this step)
@@ -197,6 +210,7 @@ class LAMMPS {
   Update *update = nullptr;
   Output *output = nullptr;
   Modify *modify = nullptr;
+  Group *group = nullptr;
   MPI_Comm world = 0;
 };
 
@@ -204,7 +218,7 @@ class Pointers {
  public:
   explicit Pointers(LAMMPS *ptr) :
       lmp(ptr), memory(ptr->memory), error(ptr->error), atom(ptr->atom), comm(ptr->comm), domain(ptr->domain), force(ptr->force),
-      neighbor(ptr->neighbor), update(ptr->update), output(ptr->output), modify(ptr->modify), world(ptr->world)
+      neighbor(ptr->neighbor), update(ptr->update), output(ptr->output), modify(ptr->modify), group(ptr->group), world(ptr->world)
   {
   }
   virtual ~Pointers() = default;
@@ -221,6 +235,7 @@ class Pointers {
   Update *&update;
   Output *&output;
   Modify *&modify;
+  Group *&group;
   MPI_Comm &world;
 };
 
@@ -291,10 +306,16 @@ class Fix : protected Pointers {
   int ecouple_flag = 0;         // 1: compute_scalar() is energy the fix exchanges with a reservoir (thermo `ecouple`)
   bigint next_reneighbor = -1;
 
+  // (a real LAMMPS stops here with "Could not find fix group ID"; this host leaves igroup = -1 and no bit for an unknown
+  // ID, so that the style says in its own words what it takes)
   Fix(LAMMPS *lmp, int narg, char **arg) : Pointers(lmp)
   {
     id = strdup(narg > 0 ? arg[0] : "");
     style = strdup(narg > 2 ? arg[2] : "");
+    if (narg > 1 && lmp->group) {
+      igroup = lmp->group->find(arg[1]);
+      groupbit = igroup >= 0 ? lmp->group->bitmask[igroup] : 0;
+    }
   }
   ~Fix() override
   {

@@ -220,7 +220,7 @@ struct GhostRec {
 };
 struct MoveRec {
   double x[3], v[3];
-  int type, tag;
+  int type, tag, mask;
 };
 
 struct HostAtomVec : AtomVec {
@@ -253,6 +253,10 @@ struct Host {
   Fix *fix = nullptr; // a time-integration fix style from a plugin (fix nve/mdp); built-in nve / nvt: fix_style
   std::vector<Fix *> fixes; // every fix style from a plugin, in the order of definition (Modify::fix), fix among them
   Modify modify;
+  Group group; // `group ID ...`: names and bits (group 0 is all, bit 1), the atoms' membership in masks / atom.mask
+  char *group_names[Group::MAX_GROUP] = {};
+  int group_bits[Group::MAX_GROUP] = {};
+  int nve_bit = 1; // the group bit of the host's own `fix ID GROUP nve`
   void sync_modify()
   {
     modify.nfix = (int) fixes.size();
@@ -291,7 +295,7 @@ struct Host {
   // atoms (owned + ghost), contiguous storage behind the double** views
   std::vector<double> xs, vs, fs;
   std::vector<double *> xrow, vrow, frow;
-  std::vector<int> types, tags;
+  std::vector<int> types, tags, masks;
   std::vector<double> masses;
   std::vector<int> ghost_owner;
   std::vector<Vec3> ghost_shift;
@@ -401,7 +405,8 @@ struct Host {
   }
 
   // owned atoms := the given ones (no ghosts)
-  void set_owned(const std::vector<double> &x, const std::vector<double> &v, const std::vector<int> &ty, const std::vector<int> &tg)
+  void set_owned(const std::vector<double> &x, const std::vector<double> &v, const std::vector<int> &ty, const std::vector<int> &tg,
+                 const std::vector<int> &mk)
   {
     const int n = (int) ty.size();
     atom.nlocal = n;
@@ -410,6 +415,7 @@ struct Host {
     std::copy(x.begin(), x.end(), xs.begin());
     std::copy(ty.begin(), ty.end(), types.begin());
     std::copy(tg.begin(), tg.end(), tags.begin());
+    std::copy(mk.begin(), mk.end(), masks.begin());
     set_vviews();
     std::copy(v.begin(), v.end(), vs.begin());
   }
@@ -421,7 +427,7 @@ struct Host {
     const int n = atom.nlocal;
     natoms_all = n;
     std::vector<double> x, v;
-    std::vector<int> ty, tg;
+    std::vector<int> ty, tg, mk;
     for (int i = 0; i < n; i++) {
       double l[3];
       x2lamda(xrow[i], l);
@@ -430,8 +436,9 @@ struct Host {
       v.insert(v.end(), vs.begin() + 3 * (size_t) i, vs.begin() + 3 * (size_t) i + 3);
       ty.push_back(types[i]);
       tg.push_back(tags[i]);
+      mk.push_back(masks[i]);
     }
-    set_owned(x, v, ty, tg);
+    set_owned(x, v, ty, tg, mk);
     world->host[me] = this;
     outbox.assign(np, {});
     cbuf.assign(np, {});
@@ -444,7 +451,7 @@ struct Host {
     if (!multi()) return;
     const int n = atom.nlocal;
     std::vector<double> x, v;
-    std::vector<int> ty, tg;
+    std::vector<int> ty, tg, mk;
     for (auto &o : outbox) o.clear();
     for (int i = 0; i < n; i++) {
       double l[3];
@@ -455,6 +462,7 @@ struct Host {
         v.insert(v.end(), vs.begin() + 3 * (size_t) i, vs.begin() + 3 * (size_t) i + 3);
         ty.push_back(types[i]);
         tg.push_back(tags[i]);
+        mk.push_back(masks[i]);
       } else {
         MoveRec r;
         for (int d = 0; d < 3; d++) {
@@ -463,6 +471,7 @@ struct Host {
         }
         r.type = types[i];
         r.tag = tags[i];
+        r.mask = masks[i];
         outbox[dest].push_back(r);
       }
     }
@@ -474,10 +483,11 @@ struct Host {
         v.insert(v.end(), r.v, r.v + 3);
         ty.push_back(r.type);
         tg.push_back(r.tag);
+        mk.push_back(r.mask);
       }
     }
     world->barrier();
-    set_owned(x, v, ty, tg);
+    set_owned(x, v, ty, tg, mk);
   }
 
   Host()
@@ -492,6 +502,13 @@ struct Host {
     lmp.update = &update;
     lmp.output = &output;
     lmp.modify = &modify;
+    lmp.group = &group;
+    for (int k = 0; k < Group::MAX_GROUP; k++) group_bits[k] = (int) (1u << k);
+    group_names[0] = strdup("all");
+    group.names = group_names;
+    group.bitmask = group_bits;
+    group.ngroup = 1;
+    group.host = this;
     comm.h = this;
     avec.h = this;
     atom.avec = &avec;
@@ -551,6 +568,7 @@ struct Host {
     fs.resize((size_t) 3 * nall);
     types.resize(nall);
     tags.resize(nall);
+    masks.resize(std::max(nall, 1), 1); // (a new atom is in group all)
     xrow.resize(nall + 1);
     frow.resize(nall + 1);
     for (int i = 0; i < nall; i++) {
@@ -567,6 +585,7 @@ struct Host {
     atom.f = frow.data();
     atom.type = types.data();
     atom.tag = tags.data();
+    atom.mask = masks.data();
     atom.nmax = nall;
     atom.mass = masses.data();
   }
@@ -597,13 +616,20 @@ struct Host {
     return c + skin;
   }
 
+  // Domain::remap.  Only an atom that left the box is rewritten: the way through lamda space and back would move every
+  // other one in its last digits, and an atom no fix moves (outside the integrator's group) stays where it was created
   void wrap_owned()
   {
     for (int i = 0; i < atom.nlocal; i++) {
       double l[3];
       x2lamda(xrow[i], l);
-      for (int d = 0; d < 3; d++) l[d] -= floor(l[d]);
-      lamda2x(l, xrow[i]);
+      bool left = false;
+      for (int d = 0; d < 3; d++) {
+        const double fl = floor(l[d]);
+        left = left || fl != 0.0;
+        l[d] -= fl;
+      }
+      if (left) lamda2x(l, xrow[i]);
     }
   }
 
@@ -655,15 +681,17 @@ struct Host {
     const int ng = (int) ghost_owner.size();
     // re-seat views, keeping owned data
     std::vector<double> xo(xs.begin(), xs.begin() + 3 * (size_t) n);
-    std::vector<int> to(types.begin(), types.begin() + n), go(tags.begin(), tags.begin() + n);
+    std::vector<int> to(types.begin(), types.begin() + n), go(tags.begin(), tags.begin() + n), mo(masks.begin(), masks.begin() + n);
     set_views(n + ng);
     std::copy(xo.begin(), xo.end(), xs.begin());
     std::copy(to.begin(), to.end(), types.begin());
     std::copy(go.begin(), go.end(), tags.begin());
+    std::copy(mo.begin(), mo.end(), masks.begin());
     atom.nghost = ng;
     for (int g = 0; g < ng; g++) {
       types[n + g] = types[ghost_owner[g]];
       tags[n + g] = tags[ghost_owner[g]];
+      masks[n + g] = masks[ghost_owner[g]];
     }
     refresh_ghosts();
   }
@@ -727,11 +755,13 @@ struct Host {
     world->barrier(); // (nobody reads my arrays any more: they may move)
     const int ng = (int) recs.size();
     std::vector<double> xo(xs.begin(), xs.begin() + 3 * (size_t) n);
-    std::vector<int> to(types.begin(), types.begin() + n), go(tags.begin(), tags.begin() + n);
+    std::vector<int> to(types.begin(), types.begin() + n), go(tags.begin(), tags.begin() + n), mo(masks.begin(), masks.begin() + n);
     set_views(n + ng);
     std::copy(xo.begin(), xo.end(), xs.begin());
     std::copy(to.begin(), to.end(), types.begin());
     std::copy(go.begin(), go.end(), tags.begin());
+    std::copy(mo.begin(), mo.end(), masks.begin());
+    std::fill(masks.begin() + n, masks.end(), 1); // (ghosts need no mask)
     std::copy(gx.begin(), gx.end(), xs.begin() + 3 * (size_t) n);
     std::copy(gty.begin(), gty.end(), types.begin() + n);
     std::copy(gtg.begin(), gtg.end(), tags.begin() + n);
@@ -975,6 +1005,7 @@ struct Host {
 
   // ---------------------------------------------------------------- Verlet
   void force_clear() { std::fill(fs.begin(), fs.end(), 0.0); }
+  void write_dump(int bit, const std::string &path);
 
   void sync_domain() // Domain::set_global_box
   {
@@ -1076,7 +1107,9 @@ struct Host {
         nvt_eta_dot += 0.5 * dt * (tcur / ttarget - 1.0) / (nvt_damp * nvt_damp);
         tscale = exp(-0.5 * dt * nvt_eta_dot);
       }
+      const int gbit = fix_style == "nve" ? nve_bit : 1; // (the built-in nve honours its group; the built-in nvt takes all)
       for (int i = 0; i < n; i++) {
+        if (!(masks[i] & gbit)) continue;
         const double s = dtf / masses[types[i]];
         for (int d = 0; d < 3; d++) {
           double &v = vs[3 * (size_t) i + d];
@@ -1097,6 +1130,7 @@ struct Host {
       const bool last = k == nsteps;
       compute_forces((out || last) ? 1 : 0, (out || last) ? 2 : 0);
       for (int i = 0; i < atom.nlocal; i++) { // (nlocal: atoms may have changed ranks at the reneighboring)
+        if (!(masks[i] & gbit)) continue;
         const double s = dtf / masses[types[i]];
         for (int d = 0; d < 3; d++) vs[3 * (size_t) i + d] += s * fs[3 * (size_t) i + d];
       }
@@ -1147,6 +1181,40 @@ struct Host {
 };
 
 void HostAtomVec::grow(int n) { h->grow_arrays(n); }
+
+// the atoms of a group, from every rank, sorted by id: "id x y z vx vy vz" with %.17g (rank 0 writes)
+void Host::write_dump(int bit, const std::string &path)
+{
+  struct Row {
+    int id;
+    double x[3], v[3];
+  };
+  if (multi()) world->barrier(); // (every rank's atoms are where they are)
+  if (me == 0) {
+    std::vector<Row> rows;
+    for (int q = 0; q < (multi() ? np : 1); q++) {
+      const Host *o = multi() ? world->host[q] : this;
+      for (int i = 0; i < o->atom.nlocal; i++) {
+        if (!(o->masks[i] & bit)) continue;
+        Row r;
+        r.id = o->tags[i];
+        for (int d = 0; d < 3; d++) {
+          r.x[d] = o->xs[3 * (size_t) i + d];
+          r.v[d] = o->vs[3 * (size_t) i + d];
+        }
+        rows.push_back(r);
+      }
+    }
+    std::sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) { return a.id < b.id; });
+    FILE *fp = fopen(path.c_str(), "w");
+    if (!fp) error.one(FLERR, "Cannot open dump file " + path);
+    fprintf(fp, "ITEM: TIMESTEP\n%ld\nITEM: NUMBER OF ATOMS\n%zu\nITEM: ATOMS id x y z vx vy vz\n", step, rows.size());
+    for (const Row &r : rows)
+      fprintf(fp, "%d %.17g %.17g %.17g %.17g %.17g %.17g\n", r.id, r.x[0], r.x[1], r.x[2], r.v[0], r.v[1], r.v[2]);
+    fclose(fp);
+  }
+  if (multi()) world->barrier(); // (nobody moves its atoms while rank 0 reads them)
+}
 
 void PeriodicComm::forward_comm(Pair *pair)
 {
@@ -1376,16 +1444,19 @@ struct Script {
     const int n0 = H.atom.nlocal, nadd = (int) tn.size();
     std::vector<double> xo(H.xs.begin(), H.xs.begin() + 3 * (size_t) n0);
     std::vector<int> to(H.types.begin(), H.types.begin() + n0), go(H.tags.begin(), H.tags.begin() + n0);
+    std::vector<int> mo(H.masks.begin(), H.masks.begin() + n0);
     H.atom.nlocal = n0 + nadd;
     H.atom.nghost = 0;
     H.set_views(n0 + nadd);
     std::copy(xo.begin(), xo.end(), H.xs.begin());
     std::copy(to.begin(), to.end(), H.types.begin());
     std::copy(go.begin(), go.end(), H.tags.begin());
+    std::copy(mo.begin(), mo.end(), H.masks.begin());
     for (int a = 0; a < nadd; a++) {
       for (int d = 0; d < 3; d++) H.xs[3 * (size_t) (n0 + a) + d] = xn[3 * (size_t) a + d];
       H.types[n0 + a] = tn[a];
       H.tags[n0 + a] = n0 + a + 1;
+      H.masks[n0 + a] = 1;
     }
     std::vector<double> vo(H.vs.begin(), H.vs.end());
     H.set_vviews();
@@ -1402,7 +1473,7 @@ struct Script {
     double h[3][3];
     H.h_matrix(h);
     std::vector<double> xo(H.xs.begin(), H.xs.begin() + 3 * (size_t) n0), vo(H.vs.begin(), H.vs.begin() + 3 * (size_t) n0);
-    std::vector<int> to(H.types.begin(), H.types.begin() + n0);
+    std::vector<int> to(H.types.begin(), H.types.begin() + n0), mo(H.masks.begin(), H.masks.begin() + n0);
     const int nn = n0 * nx * ny * nz;
     H.atom.nlocal = nn;
     H.atom.nghost = 0;
@@ -1418,6 +1489,7 @@ struct Script {
               H.vs[3 * (size_t) a + d] = vo[3 * (size_t) q + d];
             }
             H.types[a] = to[q];
+            H.masks[a] = mo[q];
             H.tags[a] = a + 1;
           }
     H.prd[0] *= nx;
@@ -1649,9 +1721,86 @@ struct Script {
         count = (int) cnt;
       }
       printf("Setting atom values ...\n  %d settings made for type/fraction\n", count);
+    } else if (c == "group") { // group ID region R | type T ... | id lo:hi ... | subtract G1 G2 ... | intersect G1 G2 ...
+                               // (the atoms named are ADDED to the group, as in LAMMPS)
+      need(4);
+      int ig = H.group.find(w[1]);
+      if (ig == 0) H.error.all(FLERR, "Group all cannot be redefined");
+      if (ig < 0) {
+        if (H.group.ngroup >= Group::MAX_GROUP) H.error.all(FLERR, "Too many groups");
+        ig = H.group.ngroup++;
+        H.group_names[ig] = strdup(w[1].c_str());
+      }
+      const int bit = H.group_bits[ig];
+      const int n = H.atom.nlocal;
+      if (w[2] == "region") {
+        if (!H.regions.count(w[3])) H.error.all(FLERR, "Group region " + w[3] + " does not exist");
+        const Region &r = H.regions[w[3]];
+        if (r.prism) H.error.all(FLERR, "minilmp supports `group ID region` with block regions only");
+        double lo[3], hi[3], tl[3];
+        region_bounds(r, lo, hi, tl);
+        for (int i = 0; i < n; i++) {
+          bool in = true;
+          for (int d = 0; d < 3; d++) in = in && H.xs[3 * (size_t) i + d] >= lo[d] && H.xs[3 * (size_t) i + d] <= hi[d];
+          if (in) H.masks[i] |= bit;
+        }
+      } else if (w[2] == "type" || w[2] == "id") {
+        for (size_t k = 3; k < w.size(); k++) { // N or lo:hi
+          const size_t colon = w[k].find(':');
+          long a, b;
+          try {
+            a = std::stol(w[k].substr(0, colon));
+            b = colon == std::string::npos ? a : std::stol(w[k].substr(colon + 1));
+          } catch (const std::exception &) {
+            H.error.all(FLERR, "Illegal group command: " + w[k] + " is neither a number nor a range lo:hi");
+          }
+          for (int i = 0; i < n; i++) {
+            const long v = w[2] == "type" ? H.types[i] : H.tags[i];
+            if (v >= a && v <= b) H.masks[i] |= bit;
+          }
+        }
+      } else if (w[2] == "subtract" || w[2] == "intersect") { // the first group's atoms that are in none / in all of the others
+        std::vector<int> bits;
+        for (size_t k = 3; k < w.size(); k++) {
+          const int jg = H.group.find(w[k]);
+          if (jg < 0) H.error.all(FLERR, "Group ID " + w[k] + " does not exist");
+          bits.push_back(H.group_bits[jg]);
+        }
+        if (bits.size() < 2) H.error.all(FLERR, "Illegal group command: " + w[2] + " needs two groups or more");
+        for (int i = 0; i < n; i++) {
+          bool in = (H.masks[i] & bits[0]) != 0;
+          for (size_t k = 1; k < bits.size() && in; k++) in = ((H.masks[i] & bits[k]) != 0) == (w[2] == "intersect");
+          if (in) H.masks[i] |= bit;
+        }
+      } else
+        H.error.all(FLERR, "minilmp supports `group ID region R`, `type T ...`, `id lo:hi ...`, `subtract G1 G2 ...` and `intersect G1 G2 ...` only");
+      printf("%ld atoms in group %s\n", (long) H.group.count(ig), w[1].c_str());
+    } else if (c == "write_dump") { // write_dump ID custom FILE id x y z vx vy vz: the group's atoms, sorted by id, %.17g
+      need(4);
+      static const std::vector<std::string> cols = {"id", "x", "y", "z", "vx", "vy", "vz"};
+      if (w[2] != "custom" || std::vector<std::string>(w.begin() + 4, w.end()) != cols)
+        H.error.all(FLERR, "minilmp supports `write_dump ID custom FILE id x y z vx vy vz` only");
+      const int ig = H.group.find(w[1]);
+      if (ig < 0) H.error.all(FLERR, "Could not find dump group ID " + w[1]);
+      H.write_dump(H.group_bits[ig], w[3]);
+    } else if (c == "velocity" && w.size() > 2 && w[2] == "set") { // velocity ID set vx vy vz
+      need(6);
+      const int ig = H.group.find(w[1]);
+      if (ig < 0) H.error.all(FLERR, "Could not find velocity group ID " + w[1]);
+      double v[3];
+      for (int d = 0; d < 3; d++) {
+        try {
+          v[d] = std::stod(w[3 + d]);
+        } catch (const std::exception &) {
+          H.error.all(FLERR, "minilmp supports `velocity ID set vx vy vz` with numbers only");
+        }
+      }
+      for (int i = 0; i < H.atom.nlocal; i++)
+        if (H.masks[i] & H.group_bits[ig])
+          for (int d = 0; d < 3; d++) H.vs[3 * (size_t) i + d] = v[d];
     } else if (c == "velocity") {
       need(5);
-      if (w[1] != "all" || w[2] != "create") H.error.all(FLERR, "minilmp supports `velocity all create T seed` only");
+      if (w[1] != "all" || w[2] != "create") H.error.all(FLERR, "minilmp supports `velocity all create T seed` and `velocity ID set vx vy vz` only");
       const double T = std::stod(w[3]);
       uint64_t seed = std::stoull(w[4]);
       const int n = H.atom.nlocal;
@@ -1683,9 +1832,12 @@ struct Script {
       H.remove_fix(f);
     } else if (c == "fix") {
       need(4);
-      if (w[3] == "nve")
+      if (w[3] == "nve") {
+        const int ig = H.group.find(w[2]);
+        if (ig < 0) H.error.all(FLERR, "Could not find fix group ID " + w[2]);
         H.fix_style = "nve";
-      else if (w[3] == "nvt") {
+        H.nve_bit = H.group_bits[ig];
+      } else if (w[3] == "nvt") {
         need(8);
         H.fix_style = "nvt";
         H.nvt_t0 = std::stod(w[5]);
@@ -1763,6 +1915,25 @@ struct Script {
 };
 
 } // namespace
+
+// Group of lammps_host_api.h on this host's atoms
+int LAMMPS_NS::Group::find(const std::string &name)
+{
+  for (int k = 0; k < MAX_GROUP; k++)
+    if (names[k] && name == names[k]) return k;
+  return -1;
+}
+
+LAMMPS_NS::bigint LAMMPS_NS::Group::count(int igroup)
+{
+  Host *h = static_cast<Host *>(host);
+  if (igroup < 0 || igroup >= MAX_GROUP || !h) return 0;
+  double n = 0.0;
+  for (int i = 0; i < h->atom.nlocal; i++)
+    if (h->masks[i] & bitmask[igroup]) n += 1.0;
+  h->sum(&n, 1);
+  return (bigint) n;
+}
 
 // the one MPI call a plugin style makes (lammps_host_api.h): root's bytes to every rank thread
 extern "C" int MPI_Bcast(void *buffer, int count, MPI_Datatype, int root, MPI_Comm)

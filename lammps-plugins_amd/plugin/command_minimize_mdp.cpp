@@ -10,6 +10,7 @@
 #include "domain.h"
 #include "error.h"
 #include "force.h"
+#include "group.h"
 #include "neighbor.h"
 #include "output.h"
 #include "pair.h"
@@ -61,8 +62,17 @@ void MinimizeMDP::parse(int narg, char **arg)
   cfg.alphashrink = 0.99;
   cfg.halfstepback = 1;
   cfg.initialdelay = 1;
+  igroup = 0;
   for (int k = 4; k < narg; k += 2) {
     const std::string key = arg[k];
+    if (key == "group") { // the atoms that move; the others are held (fix setforce 0 0 0 on them)
+      if (k + 1 >= narg) error->all(FLERR, "minimize/mdp: group needs a group ID");
+      igroup = group->find(arg[k + 1]);
+      if (igroup < 0) error->all(FLERR, std::string("minimize/mdp: could not find group ID ") + arg[k + 1]);
+      if (igroup > 0 && group->count(igroup) == 0)
+        error->all(FLERR, std::string("minimize/mdp: group ") + arg[k + 1] + " is empty: there is no atom to move");
+      continue;
+    }
     if (key == "integrator" || key == "norm" || key == "line")
       error->all(FLERR, "minimize/mdp: keyword " + key + " is not supported (integrator eulerimplicit, norm two, no line search)");
     const bool known = key == "dmax" || key == "tmax" || key == "tmin" || key == "delaystep" || key == "dtgrow" ||
@@ -123,8 +133,10 @@ void MinimizeMDP::command(int narg, char **arg)
   if (own.why) error->all(FLERR, std::string("minimize/mdp") + own.why);
   if (own.failed && !ctx) error->one(FLERR, "minimize/mdp needs a HIP device: cannot create a device context");
   if (own.failed) fail(own.failed);
-  if (mdp_brick_from_host(ctx, style_id, own.map, atom, domain, force, neighbor, update, comm) != MDP_OK) fail("setup");
+  const bool with_mask = igroup > 0 || mdp_host_has_groups(group);
+  if (mdp_brick_from_host(ctx, style_id, own.map, atom, domain, force, neighbor, update, comm, with_mask) != MDP_OK) fail("setup");
   if (mdp_dd_reneighbor(ctx) != MDP_OK) fail("lists");
+  if (mdp_integrate_group(ctx, igroup > 0 ? group->bitmask[igroup] : 0) != MDP_OK) fail("group");
   if (mdp_fire_setup(ctx, &cfg) != MDP_OK) fail("setup");
 
   const bigint step0 = update->ntimestep;
@@ -148,7 +160,7 @@ void MinimizeMDP::command(int narg, char **arg)
   if (mdp_fire_state(ctx, st) != MDP_OK) fail("state");
   if (every && comm->me == 0) printf("%10lld %18.12g %18.12g\n", (long long) step0 + (long long) st[1], st[8], st[5]);
   if (mdp_fire_off(ctx) != MDP_OK) fail("off");
-  if (mdp_brick_to_host(ctx, atom) != MDP_OK) fail("return of the atoms");
+  if (mdp_brick_to_host(ctx, atom, with_mask) != MDP_OK) fail("return of the atoms");
   update->ntimestep = step0 + (bigint) st[1];
   const int code = (int) st[0];
   if (comm->me == 0) {

@@ -1,6 +1,7 @@
 /* ------------------------------------------------------------------------------------------------
    fix langevin/mdp -- see fix_langevin_mdp.h.  What runs where:
-     constructor        the arguments (refused here: group, variables, gjf / angmom / omega, bad numbers)
+     constructor        the arguments (refused here: an unknown or empty group, a group with atoms outside the integrator's
+                        if that is defined already, variables, gjf / angmom / omega, bad numbers)
      init()             the one fix nve/mdp found through modify; a copy of the settings (with natoms, boltz, mvv2e)
                         handed to it through Fix::extract("mdp_langevin") -- virtual dispatch, since fix nve/mdp is
                         compiled into several plugin files
@@ -15,6 +16,7 @@
 #include "comm.h"
 #include "error.h"
 #include "force.h"
+#include "group.h"
 #include "modify.h"
 
 #include <cstdlib>
@@ -37,7 +39,10 @@ FixLangevinMDP::FixLangevinMDP(LAMMPS *lmp, int narg, char **arg) : Fix(lmp, nar
   memset(&cfg, 0, sizeof cfg);
   for (int t = 0; t < 16; t++) cfg.ratio[t] = 1.0;
   if (narg < 7) error->all(FLERR, "Illegal fix langevin/mdp command: fix ID all langevin/mdp Tstart Tstop damp seed [keywords]");
-  if (strcmp(arg[1], "all") != 0) error->all(FLERR, "Fix langevin/mdp requires group all");
+  if (igroup < 0)
+    error->all(FLERR, std::string("Fix langevin/mdp requires group all or a group defined by the group command: could not find fix group ID ") + arg[1]);
+  if (igroup > 0 && group->count(igroup) == 0)
+    error->all(FLERR, std::string("Fix langevin/mdp: group ") + arg[1] + " is empty: there is no atom to thermostat");
   cfg.t_start = number(lmp, arg[3], "Tstart");
   cfg.t_stop = number(lmp, arg[4], "Tstop");
   cfg.t_period = number(lmp, arg[5], "damp");
@@ -69,6 +74,20 @@ FixLangevinMDP::FixLangevinMDP(LAMMPS *lmp, int narg, char **arg) : Fix(lmp, nar
     k += 2;
   }
   ecouple_flag = cfg.tally ? 1 : 0;
+  if (Fix *nve = integrator()) inside(nve); // (said here already when the integrator is defined; init() looks again)
+}
+
+// the thermostat acts inside the device's integrate pass: an atom it is to thermostat must be one the integrator moves
+void FixLangevinMDP::inside(Fix *nve)
+{
+  if (igroup == nve->igroup || nve->igroup == 0) return;
+  long outside = 0;
+  for (int i = 0; i < atom->nlocal; i++)
+    if ((atom->mask[i] & groupbit) && !(atom->mask[i] & nve->groupbit)) outside++;
+  if (outside)
+    error->one(FLERR, std::string("Fix langevin/mdp: group ") + group->names[igroup] + " has " + std::to_string(outside) +
+                          " atoms outside group " + group->names[nve->igroup] + " of fix " + nve->id +
+                          " (nve/mdp): the thermostat acts on atoms the integrator moves");
 }
 
 int FixLangevinMDP::setmask() { return 0; } // (the force is applied inside fix nve/mdp's device steps)
@@ -101,12 +120,18 @@ void FixLangevinMDP::init()
   int dim = 0;
   mdp_langevin_config *slot = static_cast<mdp_langevin_config *>(nve->extract("mdp_langevin", dim));
   int *on = static_cast<int *>(nve->extract("mdp_langevin_on", dim));
-  if (!slot || !on) error->all(FLERR, "Fix langevin/mdp: this fix nve/mdp does not take a thermostat");
+  int *bit = static_cast<int *>(nve->extract("mdp_langevin_bit", dim));
+  if (!slot || !on || !bit) error->all(FLERR, "Fix langevin/mdp: this fix nve/mdp does not take a thermostat");
+  inside(nve);
+  // the atoms the thermostat acts on: its group, which lies inside the integrator's (zero yes divides by their number)
+  const int acts = igroup;
   cfg.boltz = force->boltz;
   cfg.mvv2e = force->mvv2e;
-  cfg.natoms = (long long) atom->natoms;
+  cfg.natoms = acts == 0 ? (long long) atom->natoms : (long long) group->count(acts);
+  if (cfg.natoms < 1) error->all(FLERR, std::string("Fix langevin/mdp: group ") + group->names[acts] + " is empty: there is no atom to thermostat");
   *slot = cfg;
   *on = 1;
+  *bit = igroup == nve->igroup ? 0 : groupbit; // (0: every atom the integrator moves)
 }
 
 // FixLangevin::compute_scalar with tally yes: the energy the thermostat took out, back to the last full step

@@ -4,9 +4,10 @@
    one fix nve/mdp (Fix::extract "mdp_langevin"), which switches the library's thermostat (mdp_langevin_*,
    csrc/langevin.hip) on in the context its steps run on for the length of each run.
 
-   fix ID all langevin/mdp Tstart Tstop damp seed [scale type ratio ...] [tally yes|no] [zero yes|no]
+   fix ID GROUP langevin/mdp Tstart Tstop damp seed [scale type ratio ...] [tally yes|no] [zero yes|no]
 
-   Group all; no variables, gjf, angmom or omega; zero and tally on one MPI rank.  The noise is keyed by atom tag and
+   GROUP: a group whose atoms fix nve/mdp integrates (its group or a part of it; all only next to fix ID all nve/mdp): the
+   force, the mean `zero yes` takes out and the tally then run over that group alone.  No variables, gjf, angmom or omega; zero and tally on one MPI rank.  The noise is keyed by atom tag and
    step, not LAMMPS' per-rank stream.  compute_scalar() is the thermostat energy with tally yes
    (ecouple_flag = 1), 0 otherwise.
 -------------------------------------------------------------------------------------------------- */
@@ -35,6 +36,7 @@ class FixLangevinMDP : public Fix {
  private:
   mdp_langevin_config cfg;
   class Fix *integrator() const; // the fix nve/mdp of this run (looked up anew: no pointer outlives either fix)
+  void inside(class Fix *nve);   // refuses a group with an atom the integrator does not move
 };
 
 }    // namespace LAMMPS_NS

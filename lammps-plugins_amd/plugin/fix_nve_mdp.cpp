@@ -43,8 +43,15 @@
                          and, through atom->avec->grow, the arrays follow), x, v, type, tag
      post_run            the pair style is released: the next run starts from the host's arrays like the first
    What the host still does every step is idle work on stale arrays (Comm::forward_comm / reverse_comm of its ghosts, a
-   memset of f); arrays never shrink below nlocal + the stale ghosts, so that work stays inside them.  Mask, image flags
-   and per-atom properties beyond the atomic style's are not carried -- group all, atom_style atomic.  Run in the mini-host
+   memset of f); arrays never shrink below nlocal + the stale ghosts, so that work stays inside them.  atom->mask travels
+   with the atoms whenever the host has a group besides all; image flags and per-atom properties beyond the atomic
+   style's are not carried -- atom_style atomic.
+
+   Groups (`fix ID GROUP nve/mdp`, GROUP other than all).  The fix's group bit goes to the library (mdp_integrate_group),
+   and atom->mask with the atoms: next to the velocities at every host reneighboring in the host-linked mode
+   (PairMDP::upload_host, mdp_hnve_set_mask), with the atoms into the brick otherwise (mdp_brick.h, mdp_md_set_mask),
+   from where it comes back with them.  A fix langevin/mdp on a sub-group hands its bit over the same way
+   (mdp_langevin_group).  Group all sets both bits to 0 and uploads no mask for the fix's sake.  Run in the mini-host
    on 2, 4 and 8 ranks (tests/test_gpu_minilmp_ranks.py: log.rebomos-bulk.4's rows, the one-rank thermo of hot runs with
    migration); against a real LAMMPS this mode is unverified.
 -------------------------------------------------------------------------------------------------- */
@@ -57,6 +64,7 @@
 #include "domain.h"
 #include "error.h"
 #include "force.h"
+#include "group.h"
 #include "neighbor.h"
 #include "output.h"
 #include "pair.h"
@@ -72,11 +80,15 @@ using namespace LAMMPS_NS;
 using namespace FixConst;
 
 FixNVEMDP::FixNVEMDP(LAMMPS *lmp, int narg, char **arg)
-    : Fix(lmp, narg, arg), ctxp(nullptr), pair_linked(nullptr), downloads(0), hostcheck(0), took_delay(0), saved_delay(0),
+    : Fix(lmp, narg, arg), ctxp(nullptr), pair_linked(nullptr), pair_mask(nullptr), downloads(0), hostcheck(0), took_delay(0), saved_delay(0),
       linked_to(nullptr), bricks(0), bricks_kw(0), bctx(nullptr), bricks_slot(nullptr), bricks_ev(nullptr), style_id(0), comm_up(0), pending_final(0), step_ev(0)
 {
   memset(&lgv_cfg, 0, sizeof lgv_cfg);
   if (narg < 3 || (narg - 3) % 2) error->all(FLERR, "Illegal fix nve/mdp command");
+  if (igroup < 0)
+    error->all(FLERR, std::string("Fix ") + arg[2] + " requires group all or a group defined by the group command: could not find fix group ID " + arg[1]);
+  if (grouped() && group->count(igroup) == 0)
+    error->all(FLERR, std::string("Fix ") + arg[2] + ": group " + arg[1] + " is empty: there is no atom to integrate");
   for (int k = 3; k + 1 < narg; k += 2) {
     const std::string key = arg[k], val = arg[k + 1];
     if ((key != "hostcheck" && key != "bricks") || (val != "yes" && val != "no")) error->all(FLERR, "Illegal fix nve/mdp command");
@@ -96,12 +108,16 @@ FixNVEMDP::~FixNVEMDP()
   if (took_delay && neighbor) neighbor->delay = saved_delay;
   const bool pair_alive = force && force->pair && force->pair == linked_to;
   if (pair_alive && pair_linked) *pair_linked = 0;
+  if (pair_alive && pair_mask) *pair_mask = 0;
   if (pair_alive && bricks_slot) *bricks_slot = nullptr;
   if (bctx) {
     if (comm_up) (void) mdp_dd_comm_destroy(bctx);
     mdp_destroy(bctx);
-  } else if (pair_alive && ctx())
+  } else if (pair_alive && ctx()) {
     (void) mdp_hnve_off(ctx());
+    (void) mdp_integrate_group(ctx(), 0); // (the pair style's context may serve another fix next)
+    (void) mdp_langevin_group(ctx(), 0);
+  }
 }
 
 // Neighbor::init() -- which runs behind Modify::init() -- insists that a non-zero delay be a multiple of `every`
@@ -122,7 +138,9 @@ void FixNVEMDP::init()
   linked_to = force->pair;
   ctxp = static_cast<mdp_ctx **>(force->pair->extract("mdp_ctx", dim));
   pair_linked = static_cast<int *>(force->pair->extract("mdp_nve_linked", dim));
-  if (!ctxp || !pair_linked || !ctx())
+  pair_mask = static_cast<int *>(force->pair->extract("mdp_nve_mask", dim));
+  if (grouped() && group_count() == 0.0) error->all(FLERR, std::string("Fix ") + style + ": group " + group->names[igroup] + " is empty: there is no atom to integrate");
+  if (!ctxp || !pair_linked || !pair_mask || !ctx())
     error->all(FLERR, "Fix nve/mdp requires a pair style of this plugin (rebomos or aeam)");
   if (comm->nprocs != 1 || bricks_kw) { // several ranks, or `bricks yes` on one: the library's decomposition runs the steps
     init_bricks();
@@ -130,6 +148,7 @@ void FixNVEMDP::init()
   }
   if (mdp_hnve_setup(ctx(), update->dt, force->ftm2v, atom->mass, atom->ntypes) != MDP_OK) fail(ctx());
   *pair_linked = 1; // from the next compute on (the setup compute uploads atoms AND velocities)
+  *pair_mask = grouped() ? 1 : 0; // ... and atom->mask (a thermostat on a group switches it on in setup())
   next_reneighbor = -1;
   // `check yes`: the device's displacement check decides (see the head of this file); the host's own look at atom->x --
   // a pass over every owned atom per step, of positions that are not current on the host -- leaves the steps
@@ -176,9 +195,10 @@ void FixNVEMDP::init_bricks()
 void FixNVEMDP::setup(int /*vflag*/)
 {
   setup_steps();
-  if (!lgv_on) return;
   mdp_ctx *c = bricks ? bctx : ctx();
   if (!c) fail(nullptr);
+  apply_groups(c);
+  if (!lgv_on) return;
   if (mdp_langevin_setup(c, &lgv_cfg) != MDP_OK) fail(c);
   if (mdp_langevin_run(c, (long long) update->beginstep, (long long) update->endstep) != MDP_OK) fail(c);
   lgv_ctx = c;
@@ -190,14 +210,34 @@ void *FixNVEMDP::extract(const char *name, int &dim)
   dim = 0;
   if (strcmp(name, "mdp_langevin") == 0) return &lgv_cfg;
   if (strcmp(name, "mdp_langevin_on") == 0) return &lgv_on;
+  if (strcmp(name, "mdp_langevin_bit") == 0) return &lgv_bit;
   if (strcmp(name, "mdp_run_ctx") == 0) return &lgv_ctx;
   return nullptr;
+}
+
+double FixNVEMDP::group_count() { return grouped() ? (double) group->count(igroup) : (double) atom->natoms; }
+
+bool FixNVEMDP::brick_mask() const { return masked() || mdp_host_has_groups(group); }
+
+// The groups of this run on the context its steps go through.  Group all (and no thermostat on a group): both bits 0, the
+// kernels of a context without groups.  Host-linked: the setup compute that has just run uploaded the atoms of this step;
+// their mask follows here, and PairMDP::upload_host re-uploads it at every later reneighboring of the host.
+void FixNVEMDP::apply_groups(mdp_ctx *c)
+{
+  if (!bricks) {
+    *pair_mask = masked() ? 1 : 0;
+    static const int none = 0;
+    if (masked() && mdp_hnve_set_mask(c, atom->nlocal ? atom->mask : &none) != MDP_OK) fail(c);
+  }
+  if (mdp_integrate_group(c, grouped() ? groupbit : 0) != MDP_OK) fail(c);
+  if (mdp_langevin_group(c, lgv_on ? lgv_bit : 0) != MDP_OK) fail(c);
 }
 
 void FixNVEMDP::setup_steps()
 {
   if (!bricks) return;
-  if (mdp_brick_from_host(bctx, style_id, bricks_map, atom, domain, force, neighbor, update, comm) != MDP_OK) fail(bctx);
+  brick_masked = brick_mask() ? 1 : 0;
+  if (mdp_brick_from_host(bctx, style_id, bricks_map, atom, domain, force, neighbor, update, comm, brick_masked != 0) != MDP_OK) fail(bctx);
   if (comm->nprocs == 1) { // one brick: its periodic images are the library's, no communicator
     if (mdp_dd_reneighbor(bctx) != MDP_OK) fail(bctx);
     if (mdp_md_compute(bctx, 0, 0) != MDP_OK) fail(bctx);
@@ -233,7 +273,7 @@ void FixNVEMDP::setup_steps()
 // the atoms the brick owns NOW, in the brick's order, into the host's arrays
 void FixNVEMDP::bricks_to_host()
 {
-  if (mdp_brick_to_host(bctx, atom) != MDP_OK) fail(bctx);
+  if (mdp_brick_to_host(bctx, atom, brick_masked != 0) != MDP_OK) fail(bctx);
   downloads++;
 }
 
@@ -292,6 +332,7 @@ void FixNVEMDP::post_run()
   if (lgv_ctx && mdp_langevin_off(lgv_ctx) != MDP_OK) fail(lgv_ctx); // (an unfix of the thermostat gives NVE next run)
   lgv_ctx = nullptr;
   lgv_on = 0;
+  lgv_bit = 0;
   if (bricks) {
     long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (comm->nprocs > 1) (void) mdp_dd_comm_step_info(bctx, info);

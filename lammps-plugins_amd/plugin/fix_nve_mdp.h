@@ -7,7 +7,11 @@
    A plugin registering a fix style is what the reference repository itself does (USER-BFIELD/bfieldplugin.cpp:15-29,
    creator.v2; virtuals USER-BFIELD/fix_bfield.h:33-38).
 
-   fix ID all nve/mdp [hostcheck yes|no] [bricks yes|no]     (defaults no, no: see fix_nve_mdp.cpp)
+   fix ID GROUP nve/mdp [hostcheck yes|no] [bricks yes|no]     (defaults no, no: see fix_nve_mdp.cpp)
+
+   GROUP: all, or any group of the group command.  The atoms outside it keep their positions and velocities bit for bit
+   (LAMMPS' fix nve on a group): atom->mask goes to the device with the atoms, in every mode, and the integrate kernels
+   honour the fix's group bit (mdp_integrate_group).  Group all runs exactly the kernels it always did.
 
    On several MPI ranks the fix runs the library's own domain decomposition (csrc/domain.hip: one brick per rank on
    Comm's processor grid, halo / migration / `check yes` decision on the device, RCCL between the GPUs) on a context of
@@ -45,6 +49,7 @@ class FixNVEMDP : public Fix {
  protected:
   mdp_ctx **ctxp;      // the pair style's device context (created in its init_style)
   int *pair_linked;    // the pair style's "positions and forces stay on the device" switch
+  int *pair_mask;      // the pair style's "atom->mask goes up with the velocities" switch (a group, or a thermostat on one)
   long downloads;      // steps on which the host's x / v were brought up to date (statistics)
   int hostcheck;       // `hostcheck yes`: Neighbor::decide() keeps looking at atom->x, which is downloaded for it
   int took_delay;      // init() raised neighbor->delay (`check yes`: the device's check decides) ...
@@ -66,6 +71,8 @@ class FixNVEMDP : public Fix {
   // setup() on the context the steps run on (lgv_ctx, extract "mdp_run_ctx"), off in post_run()
   mdp_langevin_config lgv_cfg;
   int lgv_on = 0;
+  int brick_masked = 0; // this run's brick was set up with atom->mask (it comes back with the atoms)
+  int lgv_bit = 0;     // the thermostat's group bit (extract "mdp_langevin_bit"; 0: every atom the fix integrates)
   mdp_ctx *lgv_ctx = nullptr;
 
   mdp_ctx *ctx() const { return ctxp ? *ctxp : nullptr; }
@@ -75,6 +82,11 @@ class FixNVEMDP : public Fix {
   void bricks_to_host();
   void fail(mdp_ctx *c);
   int taken_delay() const;
+  bool grouped() const { return igroup > 0; }                  // the fix acts on a group other than all
+  bool masked() const { return grouped() || (lgv_on && lgv_bit); } // ... or its thermostat does: the device needs atom->mask
+  bool brick_mask() const;                                     // bricks: atom->mask travels with the atoms
+  double group_count();                                        // atoms the fix integrates, over all ranks
+  void apply_groups(mdp_ctx *c);                               // the group bits (and, host-linked, the mask) of this run on c
 };
 
 }    // namespace LAMMPS_NS

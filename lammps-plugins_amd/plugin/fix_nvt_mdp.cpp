@@ -1,7 +1,8 @@
 /* ------------------------------------------------------------------------------------------------
    fix nvt/mdp -- see fix_nvt_mdp.h.  The steps are fix nve/mdp's (fix_nve_mdp.cpp) in its one-rank modes; what this
    subclass adds is the thermostat of the context those steps run on:
-     setup()            mdp_nhc_setup with Tstart Tstop Tdamp tchain tloop drag, 3N - 3 degrees of freedom, force->boltz /
+     setup()            mdp_nhc_setup with Tstart Tstop Tdamp tchain tloop drag, 3N - 3 degrees of freedom (N: the atoms of
+                        the fix's group, whose temperature the chain sees and whose velocities it scales), force->boltz /
                         mvv2e; the chain of the previous run seeded again (mdp_nhc_set_state); the ramp of this run
                         (mdp_nhc_run, update->beginstep .. endstep)
      initial / final    fix nve/mdp's calls, which apply the chain on the device (mdp_hnve_*, mdp_md_integrate_check and
@@ -35,7 +36,6 @@ FixNVTMDP::Args FixNVTMDP::parse(LAMMPS *lmp, int narg, char **arg)
   a.cfg.tloop = 1;
   if (narg < 3) lmp->error->all(FLERR, "Illegal fix nvt/mdp command");
   for (int k = 0; k < 3; k++) a.nve.push_back(arg[k]);
-  if (strcmp(arg[1], "all") != 0) lmp->error->all(FLERR, "Fix nvt/mdp requires group all");
   static const char *const barostat[] = {"iso", "aniso", "tri", "x", "y", "z", "xy", "xz", "yz", "couple", "ptemp", "mtk",
                                          "dilate", "pchain", "ploop", "nreset", "scalexy", "scalexz", "scaleyz", "flip",
                                          "fixedpoint", "update", "disc", "ext"};
@@ -102,7 +102,7 @@ void FixNVTMDP::setup(int vflag)
   FixNVEMDP::setup(vflag);
   mdp_ctx *c = bricks ? bctx : ctx();
   if (!c) nhc_fail(nullptr);
-  ncfg.nf = 3.0 * (double) atom->natoms - 3.0;
+  ncfg.nf = 3.0 * group_count() - 3.0; // (FixNH: the degrees of freedom of the fix's group)
   ncfg.boltz = force->boltz;
   ncfg.mvv2e = force->mvv2e;
   if (mdp_nhc_setup(c, &ncfg) != MDP_OK) nhc_fail(c);
@@ -136,7 +136,7 @@ double FixNVTMDP::compute_scalar()
   const double delta = run_last == run_first ? 0.0 : (double) (n - run_first) / (double) (run_last - run_first);
   const double tt = ncfg.t_start + delta * (ncfg.t_stop - ncfg.t_start);
   const double kt = force->boltz * tt, tf = 1.0 / ncfg.t_period;
-  const double nf = 3.0 * (double) atom->natoms - 3.0;
+  const double nf = 3.0 * group_count() - 3.0;
   const double *eta = st + 3, *ed = st + 11;
   double q = nf * kt / (tf * tf);
   double e = nf * kt * eta[0] + 0.5 * q * ed[0] * ed[0];

@@ -3,9 +3,10 @@
    this project's.  A subclass of `fix nve/mdp` in its one-rank modes (host-linked, and `bricks yes`): the same steps, with
    the library's thermostat (mdp_nhc_*, csrc/nhc.hip) switched on in the context the steps run on.
 
-   fix ID all nvt/mdp temp Tstart Tstop Tdamp [tchain M] [tloop L] [drag d] [hostcheck yes|no] [bricks yes|no]
+   fix ID GROUP nvt/mdp temp Tstart Tstop Tdamp [tchain M] [tloop L] [drag d] [hostcheck yes|no] [bricks yes|no]
 
-   One MPI rank, group all, no barostat.  compute_scalar() is the thermostat energy (ecouple_flag = 1); the chain persists
+   One MPI rank, no barostat.  GROUP: all, or any group of the group command -- the chain then thermostats that group
+   (its kinetic energy, 3 N_group - 3 degrees of freedom, its velocities) and the other atoms keep x and v (fix_nve_mdp.h).  compute_scalar() is the thermostat energy (ecouple_flag = 1); the chain persists
    across `run` commands (read back in post_run, seeded again in setup).
 -------------------------------------------------------------------------------------------------- */
 #ifdef FIX_CLASS

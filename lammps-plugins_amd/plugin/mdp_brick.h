@@ -12,6 +12,7 @@
 #include "comm.h"
 #include "domain.h"
 #include "force.h"
+#include "group.h"
 #include "neighbor.h"
 #include "pair.h"
 #include "update.h"
@@ -75,11 +76,15 @@ inline mdp_own_context_result mdp_own_context(Pair *pair, int me, mdp_ctx **ctx)
   return r;
 }
 
+// does the host have a group besides `all`?  Then atom->mask says something, and a brick carries it (mdp_md_set_mask)
+inline bool mdp_host_has_groups(Group *group) { return group && group->ngroup > 1; }
+
 // this rank's owned atoms (x, v, type, tag as the host holds them) -> the brick of rank comm->me on comm->procgrid:
-// mdp_md_setup + mdp_dd_setup.  style_id: 1 rebomos (map: the style's type -> element map), 2 aeam.  Returns the
+// mdp_md_setup + mdp_dd_setup.  style_id: 1 rebomos (map: the style's type -> element map), 2 aeam.  with_mask: atom->mask
+// goes with the atoms (mdp_md_set_mask) and follows them through every reneighboring and migration.  Returns the
 // library's code; the message is mdp_last_error(ctx).
 inline int mdp_brick_from_host(mdp_ctx *ctx, int style_id, const int *map, Atom *atom, Domain *domain, Force *force,
-                               Neighbor *neighbor, Update *update, Comm *comm)
+                               Neighbor *neighbor, Update *update, Comm *comm, bool with_mask)
 {
   const int n = atom->nlocal;
   const double skin = neighbor->skin, cutghost = force->pair->cutforce + skin;
@@ -106,6 +111,10 @@ inline int mdp_brick_from_host(mdp_ctx *ctx, int style_id, const int *map, Atom 
   int rc = mdp_md_setup(ctx, &cfg, n ? atom->x[0] : xdummy, n ? atom->v[0] : xdummy, atom->type, atom->tag, atom->mass,
                         style_id == 1 ? map : nullptr, &idummy, ddummy, &idummy, &idummy);
   if (rc != MDP_OK) return rc;
+  if (with_mask) { // (an empty brick still SETS a mask: NULL would withdraw it)
+    rc = mdp_md_set_mask(ctx, n ? atom->mask : &idummy);
+    if (rc != MDP_OK) return rc;
+  }
   mdp_dd_config dd;
   memset(&dd, 0, sizeof dd);
   for (int d = 0; d < 3; d++) {
@@ -118,8 +127,10 @@ inline int mdp_brick_from_host(mdp_ctx *ctx, int style_id, const int *map, Atom 
   return mdp_dd_setup(ctx, &dd);
 }
 
-// the atoms the brick owns NOW, in the brick's order, into the host's arrays (x, v, tag, type; atom->nlocal follows)
-inline int mdp_brick_to_host(mdp_ctx *ctx, Atom *atom)
+// the atoms the brick owns NOW, in the brick's order, into the host's arrays (x, v, tag, type; atom->nlocal follows).
+// with_mask: atom->mask comes back with them (as mdp_brick_from_host sent it); without, the host has no group but `all`
+// and every atom that comes back is in it
+inline int mdp_brick_to_host(mdp_ctx *ctx, Atom *atom, bool with_mask)
 {
   long long di[8];
   int rc = mdp_dd_info(ctx, di, nullptr, nullptr);
@@ -130,6 +141,10 @@ inline int mdp_brick_to_host(mdp_ctx *ctx, Atom *atom)
     if ((rc = mdp_md_download(ctx, atom->x[0], atom->v[0], nullptr, nullptr)) != MDP_OK) return rc;
     if ((rc = mdp_md_download_int(ctx, "tag", atom->tag)) != MDP_OK) return rc;
     if ((rc = mdp_md_download_int(ctx, "type", atom->type)) != MDP_OK) return rc;
+    if (with_mask) {
+      if ((rc = mdp_md_download_int(ctx, "mask", atom->mask)) != MDP_OK) return rc;
+    } else
+      for (int i = 0; i < n; i++) atom->mask[i] = 1;
   }
   atom->nlocal = n;
   return MDP_OK;

@@ -16,7 +16,7 @@
 using namespace LAMMPS_NS;
 
 PairMDP::PairMDP(LAMMPS *lmp, const char *name_, int style_id_)
-    : Pair(lmp), name(name_), style_id(style_id_), overflow_is_neigh_one(false), dev(nullptr), nve_linked(0), bricks(nullptr),
+    : Pair(lmp), name(name_), style_id(style_id_), overflow_is_neigh_one(false), dev(nullptr), nve_linked(0), nve_mask(0), bricks(nullptr),
       bricks_ev(0), nall_uploaded(-1)
 {
 }
@@ -126,6 +126,11 @@ bool PairMDP::upload_host(const HostUpload &u)
     if (linked) {
       rc = mdp_hnve_upload_v(dev, nlocal ? atom->v[0] : nullptr);
       if (rc != MDP_OK) fail_one(rc, "velocity upload");
+      if (nve_mask) { // ... and, when the fix (or its thermostat) acts on a group, atom->mask
+        static const int none = 0;
+        rc = mdp_hnve_set_mask(dev, nlocal ? atom->mask : &none);
+        if (rc != MDP_OK) fail_one(rc, "mask upload");
+      }
     }
   } else if (!linked) {
     rc = mdp_set_positions_host(dev, nall ? atom->x[0] : nullptr);
@@ -167,6 +172,7 @@ void *PairMDP::extract(const char *str, int &dim)
   dim = 0;
   if (strcmp(str, "mdp_ctx") == 0) return (void *) &dev;
   if (strcmp(str, "mdp_nve_linked") == 0) return (void *) &nve_linked;
+  if (strcmp(str, "mdp_nve_mask") == 0) return (void *) &nve_mask; // (the fix acts on a group: atom->mask goes up with the velocities)
   // ... and where the fix (or minimize/mdp) runs a brick on a context of its own: which style to set that context up for
   // (the derived classes answer for their parameters)
   if (strcmp(str, "mdp_bricks_ctx") == 0) return (void *) &bricks;

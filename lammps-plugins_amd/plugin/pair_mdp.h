@@ -29,6 +29,7 @@ class PairMDP : public Pair {
   bool overflow_is_neigh_one;   // fail_one() words MDP_EOVERFLOW as the reference does (pair_rebomos.cpp:350)
   mdp_ctx *dev;                 // device context (one GPU per rank)
   int nve_linked;               // set by fix nve/mdp: x, v and f of the owned atoms stay on the device between reneighborings
+  int nve_mask;                 // set by fix nve/mdp on a group (or with a thermostat on one): atom->mask goes up with the velocities
   mdp_ctx *bricks;              // set by fix nve/mdp on several ranks: its context holds this rank's brick, whole steps run there
   int bricks_ev;                // ... and whether it opened the current step with energy / virial
   int nall_uploaded;            // atoms on the device match the host's (nlocal+nghost) of the last upload
