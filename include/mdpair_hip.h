@@ -428,7 +428,7 @@ int mdp_md_moved_async(mdp_ctx *ctx, int *moved, int *dangerous);
 /* mdp_md_initial_integrate (with_final != 0: mdp_md_final_initial_integrate) and mdp_md_moved_async in one call and one
  * pass over the atoms: same results, the check reads the new positions while they are in registers. */
 int mdp_md_integrate_check(mdp_ctx *ctx, int with_final, int *moved, int *dangerous);
-/* owned atoms' "tag" / "type" / "mask" (mdp_md_set_mask) in device order (the device re-orders atoms at every reneighboring); "tile_nu"
+/* owned atoms' "tag" / "type" / "mask" (mdp_md_set_mask) / "image" (mdp_md_set_image) in device order (the device re-orders atoms at every reneighboring); "tile_nu"
  * (diagnostics): {members of the neighbour union, Mo / first-type members} of every 32-atom tile, 2 ints per tile */
 int mdp_md_download_int(mdp_ctx *ctx, const char *name, int *out);
 
@@ -583,6 +583,40 @@ int mdp_md_set_mask(mdp_ctx *ctx, const int *mask);
 int mdp_hnve_set_mask(mdp_ctx *ctx, const int *mask);
 int mdp_integrate_group(mdp_ctx *ctx, int groupbit);
 int mdp_langevin_group(mdp_ctx *ctx, int groupbit);
+
+/* ---- image flags and the mean-squared displacement (LAMMPS atom->image, compute msd) ----------------------------------
+ * The device keeps the owned atoms' image flag, LAMMPS' 32-bit imageint (ix + 512) | (iy + 512) << 10 | (iz + 512) << 20.
+ *   mdp_md_set_image:   resident mode.  image[nlocal] in the CURRENT device order, as mdp_md_set_mask takes the mask.  From
+ *                       then on every reneighboring adds the box vectors its remap takes off an atom to the atom's flag
+ *                       (periodic dimensions only; a field wraps modulo 1024 as LAMMPS' does), and the flag follows its atom
+ *                       through the re-ordering and the migration.  The migration record stays 8 doubles: with an image,
+ *                       r[6] = type + 64 mask + 2^38 (iz + 512) and r[7] = tag + 2^31 ((ix + 512) | (iy + 512) << 10), both
+ *                       exact in a double; without one the record is what it always was.  The minimiser reneighbours through
+ *                       the same remap and keeps the flag too.  mdp_md_download_int("image") reads it back.  NULL withdraws
+ *                       it; so does mdp_md_setup.  Every rank of a brick run sets one, or none does.
+ *   mdp_md_download_unwrapped: xu[nlocal][3] = x + h . image of the owned atoms in device order, with the triclinic box of
+ *                       mdp_dd_setup: xu_x = x + h0 ix + h5 iy + h4 iz, xu_y = y + h1 iy + h3 iz, xu_z = z + h2 iz.
+ *   mdp_msd_setup:      starts a measurement.  x0_by_tag[ntag][3]: the unwrapped origin of the atom with tag t at [t - 1], for
+ *                       ALL atoms of the system on every rank (24 bytes per atom; an atom that migrates finds its origin on its
+ *                       new rank).  NULL: the current unwrapped positions of the owned atoms -- one rank only (ntag = nlocal);
+ *                       refused (MDP_ESTATE) on a brick of several ranks, where an arrival's origin would be unknown.
+ *                       groupbit != 0: the atoms with mask & groupbit only; needs a mask (MDP_ESTATE without one).
+ *   mdp_msd_sums:       blocking.  out = this rank's sums over the group's owned atoms of dx^2, dy^2, dz^2, 1, m xu_x, m xu_y,
+ *                       m xu_z, m, with d = xu - x0[tag - 1] - shift (shift NULL: 0).  The caller divides by the count, and on
+ *                       several ranks sums over the ranks first.  LAMMPS' `com yes` is two calls: the mass sums give the
+ *                       centre of mass cm(t), then shift = cm(t) - cm(0).  Fixed-order sums: two reads of one state agree
+ *                       bit for bit.  MDP_EINVAL if an owned atom of the group has a tag outside 1 .. ntag.
+ *   mdp_msd_info:       out = {a measurement is on, its ntag, its groupbit, its serial}.  The serial is unique in the process
+ *                       (every mdp_msd_setup takes the next number, over all contexts): two users of one context tell by
+ *                       it whether the origins the context holds are still theirs.
+ *   mdp_msd_off:        releases the origins.
+ * All but mdp_md_set_image are refused (MDP_ESTATE) without mdp_dd_setup and without an image. */
+int mdp_md_set_image(mdp_ctx *ctx, const int *image);
+int mdp_md_download_unwrapped(mdp_ctx *ctx, double *xu);
+int mdp_msd_setup(mdp_ctx *ctx, int ntag, const double *x0_by_tag, int groupbit);
+int mdp_msd_sums(mdp_ctx *ctx, const double *shift, double out[8]);
+int mdp_msd_info(mdp_ctx *ctx, long long out[4]);
+int mdp_msd_off(mdp_ctx *ctx);
 
 /* per-phase device time of the last compute in ms (HIP events on the compute stream):
  * rebomos: [0]=REBO centre kernels of the lane-group classes, [1]=the general kernel (centres that outgrew their lane

@@ -47,9 +47,13 @@ __device__ __forceinline__ unsigned dd_cell10(const double u) // u in [0,1) -> 0
 }
 
 // 1. remap + destination brick.  Positions are only rewritten for atoms that left the box (a round trip through
-// lamda space would move every atom by rounding error).
+// lamda space would move every atom by rounding error).  IMAGE (mdp_md_set_image): the s box vectors taken off an atom are
+// added to its image flag, field by field modulo 1024 as LAMMPS' Domain::remap does, so x + h . image stays what it was;
+// the variant without IMAGE never reads the pointer
+template <bool IMAGE>
 __global__ __launch_bounds__(256) void dd_remap_kernel(const DdGeom G, const int n, double4 *__restrict__ xq,
-                                                       int *__restrict__ dest, int *__restrict__ counts)
+                                                       int *__restrict__ dest, int *__restrict__ counts,
+                                                       int *__restrict__ image)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -79,6 +83,14 @@ __global__ __launch_bounds__(256) void dd_remap_kernel(const DdGeom G, const int
     x.y -= sh[1];
     x.z -= sh[2];
     xq[i] = x;
+    if constexpr (IMAGE) {
+      const int im = image[i];
+      int out = 0;
+#pragma unroll
+      for (int d = 0; d < 3; d++) // (a non-periodic dimension has s = 0: its field stays)
+        out |= ((((im >> kImgBits * d) & kImgMask) + (int) s[d]) & kImgMask) << kImgBits * d;
+      image[i] = out;
+    }
   }
   int b[3];
 #pragma unroll
@@ -93,12 +105,16 @@ __global__ __launch_bounds__(256) void dd_remap_kernel(const DdGeom G, const int
 
 // 2. exchange: leavers -> records of 8 doubles {x, v, type, tag}, grouped by destination.  With a mask on the context
 // (mdp_md_set_mask) the record keeps its width: r[6] = type + 64 * (the mask's 32 bits as an unsigned number), exact in a
-// double; without one r[6] is the type alone, and the unpack reads both alike
+// double; without one r[6] is the type alone, and the unpack reads both alike.  IMAGE (mdp_md_set_image): the image flag
+// rides in the same two words, r[6] += 2^38 * (iz + 512) (< 2^48) and r[7] = tag + 2^31 * ((ix + 512) | (iy + 512) << 10)
+// (< 2^51), both exact in a double; the variant without IMAGE packs what it always packed
+template <bool IMAGE>
 __global__ __launch_bounds__(256) void dd_pack_leavers_kernel(const int n, const int rank, const int *__restrict__ dest,
                                                               const int *__restrict__ seg_off, int *__restrict__ cursor,
                                                               const double4 *__restrict__ xq, const double *__restrict__ v,
                                                               const int *__restrict__ type, const int *__restrict__ tag,
-                                                              const int *__restrict__ mask, double *__restrict__ buf)
+                                                              const int *__restrict__ mask, const int *__restrict__ image,
+                                                              double *__restrict__ buf)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -115,26 +131,34 @@ __global__ __launch_bounds__(256) void dd_pack_leavers_kernel(const int n, const
   r[5] = v[3 * (size_t) i + 2];
   r[6] = mask ? (double) type[i] + 64.0 * (double) (unsigned) mask[i] : (double) type[i];
   r[7] = (double) tag[i];
+  if constexpr (IMAGE) {
+    const int im = image[i];
+    r[6] += 0x1p38 * (double) ((im >> 2 * kImgBits) & kImgMask);
+    r[7] += 0x1p31 * (double) (im & (kImgMask | kImgMask << kImgBits));
+  }
 }
 
 __global__ __launch_bounds__(256) void dd_unpack_arrivals_kernel(const int n, const int first, const double *__restrict__ buf,
                                                                  const int *__restrict__ map, double4 *__restrict__ xq,
                                                                  double *__restrict__ v, int *__restrict__ type,
                                                                  int *__restrict__ tag, int *__restrict__ mask,
-                                                                 int *__restrict__ dest, const int rank)
+                                                                 int *__restrict__ image, int *__restrict__ dest,
+                                                                 const int rank)
 {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= n) return;
   const double *r = buf + 8 * (size_t) k;
-  const long long tm = (long long) r[6]; // type + 64 * mask (dd_pack_leavers_kernel)
+  // type + 64 * mask + 2^38 * iz, tag + 2^31 * (ix | iy << 10) (dd_pack_leavers_kernel): through 64-bit integers
+  const long long tm = (long long) r[6], tg = (long long) r[7];
   const int i = first + k, t = (int) (tm & 63);
   if (mask) mask[i] = (int) (unsigned) (tm >> 6);
+  if (image) image[i] = (int) ((tg >> 31) & (kImgMask | kImgMask << kImgBits)) | (int) ((tm >> 38) & kImgMask) << 2 * kImgBits;
   xq[i] = make_double4(r[0], r[1], r[2], (double) map[t]);
   v[3 * (size_t) i] = r[3];
   v[3 * (size_t) i + 1] = r[4];
   v[3 * (size_t) i + 2] = r[5];
   type[i] = t;
-  tag[i] = (int) r[7];
+  tag[i] = (int) (tg & 0x7fffffff);
   dest[i] = rank;
 }
 
@@ -186,7 +210,8 @@ __global__ __launch_bounds__(256) void dd_permute_kernel(const int n, const int 
                                                          const double *__restrict__ mass_type, double4 *__restrict__ xq,
                                                          double *__restrict__ v, int *__restrict__ type,
                                                          int *__restrict__ tag, double *__restrict__ rmass,
-                                                         const int *__restrict__ mask_in, int *__restrict__ mask)
+                                                         const int *__restrict__ mask_in, int *__restrict__ mask,
+                                                         const int *__restrict__ image_in, int *__restrict__ image)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -200,6 +225,7 @@ __global__ __launch_bounds__(256) void dd_permute_kernel(const int n, const int 
   tag[i] = tag_in[o];
   rmass[i] = mass_type[t];
   if (mask) mask[i] = mask_in[o]; // (the mask follows its atom)
+  if (image) image[i] = image_in[o]; // (and so does the image flag)
 }
 
 // 4. borders.  Per dimension the (image shift, brick) pairs whose shell [lo_b - c, hi_b + c) holds lam + shift;
@@ -432,6 +458,7 @@ void mdp_dd_release(mdp_ctx *c)
   D.type_tmp.release();
   D.tag_tmp.release();
   D.mask_tmp.release();
+  D.image_tmp.release();
   D.key_a.release();
   D.key_b.release();
   D.sendshift.release();
@@ -516,7 +543,8 @@ int mdp_dd_migrate_begin(mdp_ctx *c, int *send_counts)
   D.nghost_old = c->nghost;
   MDP_HIP(c, D.dest.reserve((size_t) n + 1));
   MDP_HIP(c, hipMemsetAsync(D.counters.p, 0, sizeof(int) * (4 * G.nranks + 16), st));
-  if (n) dd_remap_kernel<<<nblk(n), 256, 0, st>>>(G, n, c->xq.p, D.dest.p, D.counters.p);
+  if (n && c->image_set) dd_remap_kernel<true><<<nblk(n), 256, 0, st>>>(G, n, c->xq.p, D.dest.p, D.counters.p, c->image.p);
+  else if (n) dd_remap_kernel<false><<<nblk(n), 256, 0, st>>>(G, n, c->xq.p, D.dest.p, D.counters.p, nullptr);
   MDP_HIP(c, hipGetLastError());
   MDP_TRY(mdp_read_one(c, D.counters.p, sizeof(int) * G.nranks, D.mig_send.data()));
   D.mig_send[G.rank] = 0;
@@ -540,8 +568,13 @@ int mdp_dd_migrate_pack(mdp_ctx *c, double *d_buf)
   for (int q = 1; q < G.nranks; q++) off[q] = off[q - 1] + D.mig_send[q - 1];
   int *seg = D.counters.p + G.nranks, *cur = D.counters.p + 2 * G.nranks;
   MDP_TRY(mdp_write_small(c, seg, off.data(), sizeof(int) * 2 * G.nranks)); // cursors = 0
-  dd_pack_leavers_kernel<<<nblk(D.nlocal_old), 256, 0, st>>>(D.nlocal_old, G.rank, D.dest.p, seg, cur, c->xq.p, c->v.p,
-                                                             c->type.p, c->tag.p, c->mask_set ? c->mask.p : nullptr, d_buf);
+  const int *mask = c->mask_set ? c->mask.p : nullptr;
+  if (c->image_set)
+    dd_pack_leavers_kernel<true><<<nblk(D.nlocal_old), 256, 0, st>>>(D.nlocal_old, G.rank, D.dest.p, seg, cur, c->xq.p, c->v.p,
+                                                                     c->type.p, c->tag.p, mask, c->image.p, d_buf);
+  else
+    dd_pack_leavers_kernel<false><<<nblk(D.nlocal_old), 256, 0, st>>>(D.nlocal_old, G.rank, D.dest.p, seg, cur, c->xq.p, c->v.p,
+                                                                      c->type.p, c->tag.p, mask, nullptr, d_buf);
   MDP_HIP(c, hipGetLastError());
   MDP_HIP(c, hipStreamSynchronize(st)); // `off` is a host temporary
   return MDP_OK;
@@ -563,6 +596,7 @@ int mdp_dd_migrate_end(mdp_ctx *c, int narrive, const double *d_buf)
   MDP_HIP(c, c->tag.reserve((size_t) ntot + 1, true, st));
   MDP_HIP(c, D.dest.reserve((size_t) ntot + 1, true, st));
   if (c->mask_set) MDP_HIP(c, c->mask.reserve((size_t) ntot + 1, true, st));
+  if (c->image_set) MDP_HIP(c, c->image.reserve((size_t) ntot + 1, true, st));
   MDP_HIP(c, c->mass_type.reserve(32));
   MDP_HIP(c, hipMemcpyAsync(c->mass_type.p, c->h_mass, sizeof(double) * 16, hipMemcpyHostToDevice, st));
   // the type -> element map rides behind the types (mdp_pack_xq); park a copy where the kernels below can read it
@@ -570,7 +604,8 @@ int mdp_dd_migrate_end(mdp_ctx *c, int narrive, const double *d_buf)
   MDP_HIP(c, hipMemcpyAsync(d_map, c->map, sizeof(int) * 16, hipMemcpyHostToDevice, st));
   if (narrive)
     dd_unpack_arrivals_kernel<<<nblk(narrive), 256, 0, st>>>(narrive, nold, d_buf, d_map, c->xq.p, c->v.p, c->type.p,
-                                                             c->tag.p, c->mask_set ? c->mask.p : nullptr, D.dest.p, G.rank);
+                                                             c->tag.p, c->mask_set ? c->mask.p : nullptr,
+                                                             c->image_set ? c->image.p : nullptr, D.dest.p, G.rank);
   MDP_HIP(c, D.key_a.reserve((size_t) ntot + 1));
   MDP_HIP(c, D.key_b.reserve((size_t) ntot + 1));
   MDP_HIP(c, D.idx_a.reserve((size_t) ntot + 1));
@@ -582,6 +617,7 @@ int mdp_dd_migrate_end(mdp_ctx *c, int narrive, const double *d_buf)
   MDP_HIP(c, D.type_tmp.reserve(room + 32));
   MDP_HIP(c, D.tag_tmp.reserve(room + 1));
   if (c->mask_set) MDP_HIP(c, D.mask_tmp.reserve((size_t) nnew + 1));
+  if (c->image_set) MDP_HIP(c, D.image_tmp.reserve((size_t) nnew + 1));
   MDP_HIP(c, c->rmass.reserve((size_t) nnew + 1));
   if (ntot) {
     const int shell_last = c->cfg.style == 2;
@@ -597,7 +633,8 @@ int mdp_dd_migrate_end(mdp_ctx *c, int narrive, const double *d_buf)
   if (nnew) {
     dd_permute_kernel<<<nblk(nnew), 256, 0, st>>>(nnew, D.idx_b.p, c->xq.p, c->v.p, c->type.p, c->tag.p, c->mass_type.p,
                                                   D.xq_tmp.p, D.v_tmp.p, D.type_tmp.p, D.tag_tmp.p, c->rmass.p,
-                                                  c->mask_set ? c->mask.p : nullptr, c->mask_set ? D.mask_tmp.p : nullptr);
+                                                  c->mask_set ? c->mask.p : nullptr, c->mask_set ? D.mask_tmp.p : nullptr,
+                                                  c->image_set ? c->image.p : nullptr, c->image_set ? D.image_tmp.p : nullptr);
     MDP_HIP(c, hipGetLastError());
   }
   swap_buf(c->xq, D.xq_tmp);
@@ -608,6 +645,7 @@ int mdp_dd_migrate_end(mdp_ctx *c, int narrive, const double *d_buf)
     swap_buf(c->mask, D.mask_tmp);
     c->mask_n = nnew;
   }
+  if (c->image_set) swap_buf(c->image, D.image_tmp);
   c->nlocal = nnew;
   c->nghost = 0;
   c->nall = nnew;
@@ -870,7 +908,7 @@ int mdp_md_integrate_check(mdp_ctx *c, int with_final, int *moved, int *dangerou
   return mdp_moved_post(c, c->sflag_armed && c->sflag_committed[c->sflag_set]);
 }
 
-// owned atoms' integer properties in device order ("tag", "type", "mask"); the device re-orders atoms at every reneighboring
+// owned atoms' integer properties in device order ("tag", "type", "mask", "image"); the device re-orders atoms at every reneighboring
 int mdp_md_download_int(mdp_ctx *c, const char *name, int *out)
 {
   if (!c || !name || !out) return MDP_EINVAL;
@@ -879,6 +917,10 @@ int mdp_md_download_int(mdp_ctx *c, const char *name, int *out)
   if (!strcmp(name, "mask")) {
     if (!c->mask_set) return mdp_fail(c, MDP_ESTATE, "mdp_md_download_int: no mask set (mdp_md_set_mask)");
     src = c->mask.p;
+  }
+  if (!strcmp(name, "image")) {
+    if (!c->image_set) return mdp_fail(c, MDP_ESTATE, "mdp_md_download_int: no image set (mdp_md_set_image)");
+    src = c->image.p;
   }
   MDP_HIP(c, hipSetDevice(c->device));
   if (!strcmp(name, "tile_nu")) { // diagnostics: {members of the union, Mo members} of every tile, 2 * ntile <= nlocal ints

@@ -1014,6 +1014,24 @@ int mdp_md_setup(mdp_ctx *c, const mdp_md_config *cfg, const double *x, const do
   c->md = true;
   c->mask_set = false; // (a mask belongs to the atoms it was set for)
   c->mask_n = 0;
+  c->image_set = false; // (and so do the image flags)
+  return MDP_OK;
+}
+
+int mdp_md_set_image(mdp_ctx *c, const int *image)
+{
+  if (!c) return MDP_EINVAL;
+  if (!c->md) return mdp_fail(c, MDP_ESTATE, "mdp_md_setup not called");
+  if (!image) {
+    c->image_set = false;
+    return MDP_OK;
+  }
+  MDP_HIP(c, hipSetDevice(c->device));
+  const int n = c->nlocal;
+  MDP_HIP(c, c->image.reserve((size_t) n + 1));
+  if (n) MDP_TRY(mdp_host_upload(c, c->image.p, image, sizeof(int) * (size_t) n));
+  MDP_HIP(c, hipStreamSynchronize(c->stream)); // the caller's array may change after return
+  c->image_set = true;
   return MDP_OK;
 }
 

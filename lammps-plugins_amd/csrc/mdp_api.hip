@@ -919,6 +919,8 @@ int mdp_destroy(mdp_ctx *c)
   c->fire.part.release();
   c->fire.fsave.release();
   c->mask.release();
+  c->image.release();
+  mdp_msd_release(c);
   if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
   delete c;
   return MDP_OK;

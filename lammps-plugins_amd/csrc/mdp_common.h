@@ -204,6 +204,18 @@ struct DdGeom {
   int nonper[3];        // 1: no periodic images / no wrap in this dimension (slab, free surface)
 };
 
+// LAMMPS' 32-bit imageint: (ix + 512) | (iy + 512) << 10 | (iz + 512) << 20; a field wraps modulo 1024
+constexpr int kImgBits = 10, kImgMask = 1023, kImgBias = 512;
+// unwrapped position x + h . image of an atom, the roundings written out (both kernels that form it give the same bits)
+__device__ __forceinline__ void mdp_unwrap(const DdGeom &G, const double4 &x, const int image, double xu[3])
+{
+  const double ix = (double) ((image & kImgMask) - kImgBias), iy = (double) (((image >> kImgBits) & kImgMask) - kImgBias),
+               iz = (double) (((image >> 2 * kImgBits) & kImgMask) - kImgBias);
+  xu[0] = fma(G.h[4], iz, fma(G.h[5], iy, fma(G.h[0], ix, x.x)));
+  xu[1] = fma(G.h[3], iz, fma(G.h[1], iy, x.y));
+  xu[2] = fma(G.h[2], iz, x.z);
+}
+
 struct MdpDomain {
   bool on = false;
   DdGeom G;
@@ -212,7 +224,7 @@ struct MdpDomain {
   int mig_total = 0, nself = 0, nsend = 0, nrecv = 0, nent = 0;
   int nlocal_old = 0, nghost_old = 0;
   long long reneighbors = 0;
-  DevBuf<int> dest, counters, idx_a, idx_b, ent_atom, ent_code, ent_cnt, ent_off, sendlist, type_tmp, tag_tmp, mask_tmp;
+  DevBuf<int> dest, counters, idx_a, idx_b, ent_atom, ent_code, ent_cnt, ent_off, sendlist, type_tmp, tag_tmp, mask_tmp, image_tmp;
   DevBuf<unsigned long long> key_a, key_b;
   DevBuf<double> sendshift, v_tmp;
   DevBuf<double4> xq_tmp;
@@ -325,6 +337,17 @@ struct MdpFire {
   DevBuf<double> part;         // per-block partials: 3 sums per block, then one maximum per block
   DevBuf<double> fsave;        // a state read's energy compute leaves the forces as it found them
 };
+
+// mean-squared displacement (msd.hip): the origins of the WHOLE system by tag on every rank, so nothing has to migrate
+struct MdpMsd {
+  bool on = false;
+  int ntag = 0, gbit = 0;
+  long long serial = 0; // which mdp_msd_setup of this process filled x0 (mdp_msd_info)
+  DevBuf<double> x0;   // [ntag][3] unwrapped origin of the atom with tag t at [t - 1]
+  DevBuf<double> xu;   // [nlocal][3] unwrapped positions (mdp_md_download_unwrapped)
+  DevBuf<double> part; // per-block partials, kMsdW per block, then the kMsdW sums
+};
+static constexpr int kMsdW = 9; // sum dx^2, dy^2, dz^2, count, sum m xu (3), sum m, atoms whose tag has no origin
 
 // what the integrate kernels need to add the Langevin force of one step (md.hip nve_advance_kernel / nve_final_kernel)
 struct MdpLgvArgs {
@@ -650,6 +673,10 @@ struct mdp_ctx {
   bool mask_set = false;
   int mask_n = 0;                  // owned atoms the mask covers (host mode: as of the last mdp_hnve_set_mask)
   int group_bit = 0, lgv_bit = 0;  // 0: every atom
+  // image flags (mdp_md_set_image) and the mean-squared displacement measured with them (msd.hip)
+  DevBuf<int> image;               // [nlocal] atom->image, LAMMPS' 32-bit imageint: device order, remapped, permuted and migrated with the atoms
+  bool image_set = false;
+  MdpMsd msd;
   bool final_pending = false;      // the host deferred the final half-kick of the finished step (mdp_md_defer_final)
   bool final_deferred_seen = false; // the host uses mdp_md_defer_final at all (older hosts: with_final is authoritative)
   bool acc_prezeroed = false; // the integrate kernel reset the accumulators: the next mdp_acc_begin launches nothing
@@ -833,6 +860,7 @@ int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvA
 // with MDP_ESTATE when a group is set and no mask covers the current atoms
 int mdp_group_args(mdp_ctx *c, bool *masked, MdpGroupArgs *M);
 int mdp_lgv_close(mdp_ctx *c, const MdpLgvArgs &L);
+void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
 // FIRE minimiser (fire.hip), in place of the integrate kernel when c->fire.on: the half step back / zeroing and the Euler
 // step of the iteration whose control kernel was queued last, with the same votes, accumulator reset and force clear
 int mdp_fire_launch_advance(mdp_ctx *c, int *flag, double trigsq, double hardsq, const MdpStyleCheck &sc, bool zero_f);

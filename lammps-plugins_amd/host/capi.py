@@ -98,6 +98,7 @@ EXPORTS = [
     "mdp_langevin_setup", "mdp_langevin_run", "mdp_langevin_tally", "mdp_langevin_off",
     "mdp_fire_setup", "mdp_fire_iterate", "mdp_fire_state", "mdp_fire_off",
     "mdp_md_set_mask", "mdp_hnve_set_mask", "mdp_integrate_group", "mdp_langevin_group",
+    "mdp_md_set_image", "mdp_md_download_unwrapped", "mdp_msd_setup", "mdp_msd_sums", "mdp_msd_info", "mdp_msd_off",
 ]
 
 
@@ -758,6 +759,43 @@ class Context:
     def langevin_group(self, groupbit):
         """the Langevin force goes to the atoms with mask & groupbit (inside the integrate group) only (0: every atom)"""
         self._ck(self.L.mdp_langevin_group(self.h, C.c_int(int(groupbit))))
+
+    # ---------------- image flags, unwrapped positions and the mean-squared displacement (csrc/msd.hip)
+    def md_set_image(self, image):
+        """resident mode: atom->image (LAMMPS' 32-bit imageint) of the owned atoms in the current device order, as
+        md_set_mask takes the mask; None withdraws it.  md_download_int("image") reads it back."""
+        keep, ptr = self._mask_ptr(image)
+        self._ck(self.L.mdp_md_set_image(self.h, ptr))
+
+    def md_download_unwrapped(self, nlocal):
+        """x + h . image of the owned atoms in device order"""
+        xu = np.zeros((max(nlocal, 1), 3))
+        self._ck(self.L.mdp_md_download_unwrapped(self.h, _dp(xu)))
+        return xu[:nlocal]
+
+    def msd_setup(self, ntag, x0_by_tag=None, groupbit=0):
+        """starts a measurement: x0_by_tag[ntag][3] the unwrapped origins of ALL atoms, [tag - 1]; None: the owned atoms'
+        current unwrapped positions (one rank only).  groupbit 0: every atom"""
+        x0 = None if x0_by_tag is None else np.ascontiguousarray(x0_by_tag, dtype=np.float64)
+        if x0 is not None and x0.shape != (int(ntag), 3):
+            raise ValueError(f"msd_setup: x0_by_tag must be [{int(ntag)}][3], not {x0.shape}")
+        self._ck(self.L.mdp_msd_setup(self.h, C.c_int(int(ntag)), _dp(x0), C.c_int(int(groupbit))))
+
+    def msd_sums(self, shift=None):
+        """this rank's sums over the group: [sum dx^2, dy^2, dz^2, count, sum m xu (3), sum m], d = xu - x0 - shift"""
+        sh = None if shift is None else np.ascontiguousarray(shift, dtype=np.float64)
+        out = np.zeros(8)
+        self._ck(self.L.mdp_msd_sums(self.h, _dp(sh), _dp(out)))
+        return out
+
+    def msd_info(self):
+        """whether a measurement is on, its ntag and group bit, and its serial (unique in the process per msd_setup)"""
+        out = (C.c_longlong * 4)()
+        self._ck(self.L.mdp_msd_info(self.h, out))
+        return dict(on=bool(out[0]), ntag=int(out[1]), groupbit=int(out[2]), serial=int(out[3]))
+
+    def msd_off(self):
+        self._ck(self.L.mdp_msd_off(self.h))
 
     # halo plumbing (device pointers as ints)
     def md_pack_x(self, n, d_sendlist, d_shift, d_buf):

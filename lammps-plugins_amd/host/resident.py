@@ -20,6 +20,21 @@ from . import system as S
 # re-derives its ghosts on the GPU at each reneighboring and only exchanges counts and packed records.
 # ---------------------------------------------------------------------------------------------------
 
+IMAGE0 = 512 | 512 << 10 | 512 << 20   # LAMMPS' imageint of the central image: (ix + 512) | (iy + 512) << 10 | (iz + 512) << 20
+
+
+def image_counts(image):
+    """imageint [n] -> the counts (ix, iy, iz) [n][3]"""
+    im = np.asarray(image, dtype=np.int64)
+    return np.stack([(im & 1023) - 512, ((im >> 10) & 1023) - 512, ((im >> 20) & 1023) - 512], axis=1)
+
+
+def image_pack(counts):
+    """the counts (ix, iy, iz) [n][3] -> imageint [n]; a field wraps modulo 1024"""
+    c = np.asarray(counts, dtype=np.int64) + 512
+    return ((c[:, 0] & 1023) | (c[:, 1] & 1023) << 10 | (c[:, 2] & 1023) << 20).astype(np.int32)
+
+
 class Transport:
     """all-to-all of device buffers between the ranks of a torch.distributed group.  backend "nccl" is
     RCCL over xGMI (device buffers go straight in); any other backend is a rehearsal path for boxes with
@@ -121,6 +136,7 @@ class DeviceDomain:
         self.rank = 0 if transport is None else transport.rank
         self.grid = decomp.proc_grid(self.world)
         self.natoms_total = s.n
+        self._mass_by_type = np.array(s.mass, dtype=np.float64)
         # (dimensions that are not periodic -- a slab, a free surface -- are neither wrapped nor given images)
         lam0 = s.box.x2lamda(s.x)
         per = np.array([0.0 if nonperiodic[d] else 1.0 for d in range(3)])
@@ -408,6 +424,70 @@ class DeviceDomain:
     def mask_local(self):
         """the owned atoms' mask in device order (next to tags_local)"""
         return self.ctx.md_download_int("mask", self.nlocal)
+
+    # ------------------------------------------------------------------ image flags and the mean-squared displacement
+    def track_images(self, image_by_tag=None):
+        """LAMMPS image flags for the atoms of this domain: image_by_tag[t - 1] is atom->image (the 32-bit imageint) of the
+        atom with tag t; None: every atom starts in the central image.  From here on every reneighbouring counts the
+        box vectors it takes off an atom, and the flag travels with the atom (re-ordering, migration, the minimiser's
+        reneighbourings).  With several ranks every rank makes the same call."""
+        tags = self.tags_local
+        if image_by_tag is None:
+            img = np.full(self.nlocal, IMAGE0, dtype=np.int32)
+        else:
+            img = np.asarray(image_by_tag)[tags - 1].astype(np.int32)
+        self.ctx.md_set_image(img)
+
+    def images_local(self):
+        """the owned atoms' image counts (ix, iy, iz) [nlocal][3] in device order (next to tags_local)"""
+        return image_counts(self.ctx.md_download_int("image", self.nlocal))
+
+    def unwrapped_local(self):
+        """the owned atoms' unwrapped positions x + h . image in device order"""
+        return self.ctx.md_download_unwrapped(self.nlocal)
+
+    def _group_sum(self, values):
+        return np.asarray(values, dtype=np.float64) if self.tr is None else np.asarray(self.tr.sum(values))
+
+    def msd(self, x0_by_tag=None, group_bit=0):
+        """starts a mean-squared displacement measurement (LAMMPS compute msd) over the atoms with mask & group_bit (0:
+        every atom; otherwise set_group must have given a mask).  x0_by_tag[t - 1]: the unwrapped origin of the atom with
+        tag t, for all atoms of the system; None: where the atoms are now.  Needs track_images.  With several ranks every
+        rank makes the same call."""
+        n = self.natoms_total
+        if x0_by_tag is None and self.tr is not None:
+            x0 = np.zeros((n, 3))            # every rank fills in its own atoms; the sum is the whole system by tag
+            x0[self.tags_local - 1] = self.unwrapped_local()
+            x0_by_tag = self._group_sum(x0.ravel()).reshape(n, 3)
+        self.ctx.msd_setup(n, x0_by_tag, group_bit)
+        # the group's centre of mass at the origins: mass and membership do not change, so it is the sum over the atoms
+        # each rank holds now
+        m = self._mass_local()
+        if group_bit:
+            m = m * ((self.mask_local() & group_bit) != 0)
+        x0 = self.unwrapped_local() if x0_by_tag is None else np.asarray(x0_by_tag, dtype=np.float64)[self.tags_local - 1]
+        w = self._group_sum([*(m[:, None] * x0).sum(axis=0), m.sum()])
+        if not w[3] > 0.0:
+            raise ValueError("msd: the group holds no atom")
+        self._msd_cm0 = w[:3] / w[3]
+
+    def _mass_local(self):
+        return np.asarray(self._mass_by_type)[self.ctx.md_download_int("type", self.nlocal)]
+
+    def msd_read(self, com=False):
+        """the four values of LAMMPS compute msd -- dx^2, dy^2, dz^2 and their total, means over the group, summed over the
+        ranks through the domain's transport.  com: with the drift of the group's centre of mass taken out (com yes)."""
+        self.flush()
+        shift = None
+        if com:
+            w = self._group_sum(self.ctx.msd_sums())
+            shift = w[4:7] / w[7] - self._msd_cm0
+        s = self._group_sum(self.ctx.msd_sums(shift))
+        v = s[:3] / s[3]
+        return np.array([v[0], v[1], v[2], v[0] + v[1] + v[2]])
+
+    def msd_off(self):
+        self.ctx.msd_off()
 
     def thermostat(self, t_start, t_stop, t_period, tchain=3, tloop=1, drag=0.0, first=0, last=0, nf=None):
         """Nose-Hoover chain thermostat (LAMMPS fix nvt) in the integrate calls of this domain, from the chain at rest; one

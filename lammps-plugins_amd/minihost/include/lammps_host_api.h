@@ -32,13 +32,24 @@
 typedef int MPI_Comm; // the communicator is a token: one process, `minilmp -np N` runs its ranks as threads
 typedef int MPI_Datatype;
 #define MPI_BYTE 1
+#define MPI_DOUBLE 2
+typedef int MPI_Op;
+#define MPI_SUM 1
 // the one MPI call a style of these plugins makes (fix nve/mdp on several ranks hands RCCL's unique id from rank 0 to
 // the others): defined by the host executable for its rank threads, resolved from it when the plugin is loaded
 extern "C" int MPI_Bcast(void *buffer, int count, MPI_Datatype datatype, int root, MPI_Comm comm);
+// ... and the one a compute style makes (compute msd/mdp: the origins and the sums of all ranks): MPI_SUM of MPI_DOUBLE,
+// added in rank order on every rank, so that all ranks hold the same bits
+extern "C" int MPI_Allreduce(const void *sendbuf, void *recvbuf, int count, MPI_Datatype datatype, MPI_Op op, MPI_Comm comm);
 
 namespace LAMMPS_NS {
 
 typedef int tagint;
+typedef int imageint; // 32 bits (LAMMPS_SMALLBIG): 10 bits per dimension, biased by 512
+#define IMGMASK 1023
+#define IMGMAX 512
+#define IMGBITS 10
+#define IMG2BITS 20
 typedef int64_t bigint;
 
 class LAMMPS;
@@ -54,6 +65,7 @@ class Pair;
 class Update;
 class Output;
 class Fix;
+class Compute;
 class Modify;
 class Group;
 
@@ -108,7 +120,7 @@ class Memory {
 class AtomVec { // Atom::avec: per-atom array storage of the atom style
  public:
   virtual ~AtomVec() = default;
-  virtual void grow(int n) = 0; // room for n atoms (owned + ghost) in x, v, f, type, mask, tag; contents kept (AtomVec::grow)
+  virtual void grow(int n) = 0; // room for n atoms (owned + ghost) in x, v, f, type, mask, image, tag; contents kept (AtomVec::grow)
 };
 
 class Atom {
@@ -117,6 +129,7 @@ class Atom {
   double **x = nullptr, **f = nullptr, **v = nullptr;
   int *type = nullptr;
   int *mask = nullptr; // group membership, one bit per group (bit 1: group all)
+  imageint *image = nullptr; // box vectors Domain::remap has taken off the atom: (ix + 512) | (iy + 512) << 10 | (iz + 512) << 20
   tagint *tag = nullptr;
   double *mass = nullptr;
   int nlocal = 0, nghost = 0, nmax = 0, ntypes = 0, tag_enable = 1;
@@ -331,6 +344,34 @@ class Fix : protected Pointers {
   virtual void reset_dt() {}
   virtual double compute_scalar() { return 0.0; } // thermo f_ID
   virtual void *extract(const char *, int &) { return nullptr; } // what a fix hands another one (Fix::extract)
+};
+
+// the part of LAMMPS' Compute a global-vector compute style touches (compute.h of the 2 Aug 2023 release)
+class Compute : protected Pointers {
+ public:
+  char *id = nullptr, *style = nullptr;
+  int igroup = 0, groupbit = 1;
+  double *vector = nullptr;     // the values compute_vector() leaves (thermo c_ID[k] reads vector[k - 1])
+  int vector_flag = 0, size_vector = 0, extvector = 0, create_attribute = 0;
+  bigint invoked_vector = -1;   // the step compute_vector() ran last
+
+  // (as Fix: an unknown group ID leaves igroup = -1 and no bit, and the style says what it takes)
+  Compute(LAMMPS *lmp, int narg, char **arg) : Pointers(lmp)
+  {
+    id = strdup(narg > 0 ? arg[0] : "");
+    style = strdup(narg > 2 ? arg[2] : "");
+    if (narg > 1 && lmp->group) {
+      igroup = lmp->group->find(arg[1]);
+      groupbit = igroup >= 0 ? lmp->group->bitmask[igroup] : 0;
+    }
+  }
+  ~Compute() override
+  {
+    free(id);
+    free(style);
+  }
+  virtual void init() = 0;
+  virtual void compute_vector() {}
 };
 
 // a command style (command.h of the 2 Aug 2023 release): one object per use of the input word, command() runs it

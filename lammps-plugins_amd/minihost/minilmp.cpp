@@ -160,6 +160,7 @@ void Pair::init()
 namespace {
 
 const double BOLTZ = 8.617343e-5, MVV2E = 1.0364269e-4, FTM2V = 1.0 / 1.0364269e-4, NKTV2P = 1.6021765e6;
+const int kImage0 = IMGMAX | IMGMAX << IMGBITS | IMGMAX << IMG2BITS; // atom->image of an atom in the central image
 
 struct Vec3 {
   double v[3];
@@ -184,13 +185,14 @@ struct World {
   std::vector<Host *> host;
   std::vector<double> red;
   std::vector<char> bbuf; // MPI_Bcast
+  std::vector<const double *> abuf; // MPI_Allreduce: every rank's send buffer
   static constexpr int kRed = 16;
   std::mutex m;
   std::condition_variable cv;
   int waiting = 0;
   long generation = 0;
   bool dead = false;
-  explicit World(int n_) : n(n_), host(n_, nullptr), red((size_t) n_ * kRed, 0.0) {}
+  explicit World(int n_) : n(n_), host(n_, nullptr), red((size_t) n_ * kRed, 0.0), abuf(n_, nullptr) {}
   void barrier()
   {
     if (n == 1) return;
@@ -220,7 +222,7 @@ struct GhostRec {
 };
 struct MoveRec {
   double x[3], v[3];
-  int type, tag, mask;
+  int type, tag, mask, image;
 };
 
 struct HostAtomVec : AtomVec {
@@ -280,6 +282,14 @@ struct Host {
   std::map<std::string, lammpsplugin_factory1 *> pair_styles;
   std::map<std::string, lammpsplugin_factory2 *> fix_styles;
   std::map<std::string, lammpsplugin_factory1 *> command_styles;
+  std::map<std::string, lammpsplugin_factory2 *> compute_styles;
+  std::vector<Compute *> computes; // every compute style from a plugin, in the order of definition
+  Compute *compute_by_id(const std::string &id)
+  {
+    for (Compute *c : computes)
+      if (id == c->id) return c;
+    return nullptr;
+  }
   std::vector<void *> handles;
 
   // box: lo, prd, tilt (xy,xz,yz)
@@ -296,6 +306,7 @@ struct Host {
   std::vector<double> xs, vs, fs;
   std::vector<double *> xrow, vrow, frow;
   std::vector<int> types, tags, masks;
+  std::vector<int> images; // atom->image: kept by wrap_owned (Domain::remap), moved with the atoms
   std::vector<double> masses;
   std::vector<int> ghost_owner;
   std::vector<Vec3> ghost_shift;
@@ -406,7 +417,7 @@ struct Host {
 
   // owned atoms := the given ones (no ghosts)
   void set_owned(const std::vector<double> &x, const std::vector<double> &v, const std::vector<int> &ty, const std::vector<int> &tg,
-                 const std::vector<int> &mk)
+                 const std::vector<int> &mk, const std::vector<int> &im)
   {
     const int n = (int) ty.size();
     atom.nlocal = n;
@@ -416,6 +427,7 @@ struct Host {
     std::copy(ty.begin(), ty.end(), types.begin());
     std::copy(tg.begin(), tg.end(), tags.begin());
     std::copy(mk.begin(), mk.end(), masks.begin());
+    std::copy(im.begin(), im.end(), images.begin());
     set_vviews();
     std::copy(v.begin(), v.end(), vs.begin());
   }
@@ -427,7 +439,7 @@ struct Host {
     const int n = atom.nlocal;
     natoms_all = n;
     std::vector<double> x, v;
-    std::vector<int> ty, tg, mk;
+    std::vector<int> ty, tg, mk, im;
     for (int i = 0; i < n; i++) {
       double l[3];
       x2lamda(xrow[i], l);
@@ -437,8 +449,9 @@ struct Host {
       ty.push_back(types[i]);
       tg.push_back(tags[i]);
       mk.push_back(masks[i]);
+      im.push_back(images[i]);
     }
-    set_owned(x, v, ty, tg, mk);
+    set_owned(x, v, ty, tg, mk, im);
     world->host[me] = this;
     outbox.assign(np, {});
     cbuf.assign(np, {});
@@ -451,7 +464,7 @@ struct Host {
     if (!multi()) return;
     const int n = atom.nlocal;
     std::vector<double> x, v;
-    std::vector<int> ty, tg, mk;
+    std::vector<int> ty, tg, mk, im;
     for (auto &o : outbox) o.clear();
     for (int i = 0; i < n; i++) {
       double l[3];
@@ -463,6 +476,7 @@ struct Host {
         ty.push_back(types[i]);
         tg.push_back(tags[i]);
         mk.push_back(masks[i]);
+        im.push_back(images[i]);
       } else {
         MoveRec r;
         for (int d = 0; d < 3; d++) {
@@ -472,6 +486,7 @@ struct Host {
         r.type = types[i];
         r.tag = tags[i];
         r.mask = masks[i];
+        r.image = images[i];
         outbox[dest].push_back(r);
       }
     }
@@ -484,10 +499,11 @@ struct Host {
         ty.push_back(r.type);
         tg.push_back(r.tag);
         mk.push_back(r.mask);
+        im.push_back(r.image);
       }
     }
     world->barrier();
-    set_owned(x, v, ty, tg, mk);
+    set_owned(x, v, ty, tg, mk, im);
   }
 
   Host()
@@ -569,6 +585,7 @@ struct Host {
     types.resize(nall);
     tags.resize(nall);
     masks.resize(std::max(nall, 1), 1); // (a new atom is in group all)
+    images.resize(std::max(nall, 1), kImage0); // (... and in the central image)
     xrow.resize(nall + 1);
     frow.resize(nall + 1);
     for (int i = 0; i < nall; i++) {
@@ -586,6 +603,7 @@ struct Host {
     atom.type = types.data();
     atom.tag = tags.data();
     atom.mask = masks.data();
+    atom.image = images.data();
     atom.nmax = nall;
     atom.mass = masses.data();
   }
@@ -628,6 +646,10 @@ struct Host {
         const double fl = floor(l[d]);
         left = left || fl != 0.0;
         l[d] -= fl;
+        if (fl != 0.0) { // the box vectors taken off are counted in the image flag, a field modulo 1024
+          const int sh = IMGBITS * d, field = (((images[i] >> sh) & IMGMASK) + (int) fl) & IMGMASK;
+          images[i] = (images[i] & ~(IMGMASK << sh)) | (field << sh);
+        }
       }
       if (left) lamda2x(l, xrow[i]);
     }
@@ -988,6 +1010,17 @@ struct Host {
           if (!f) error.all(FLERR, "Could not find thermo custom fix ID: " + c.substr(2));
           v = f->compute_scalar();
         }
+        else if (c.compare(0, 2, "c_") == 0) { // c_ID[k]: element k of a global vector compute, evaluated once per step
+          const size_t lb = c.find('['), rb = c.find(']');
+          Compute *cp = compute_by_id(c.substr(2, lb == std::string::npos ? lb : lb - 2));
+          if (!cp) error.all(FLERR, "Could not find thermo custom compute ID: " + c.substr(2, lb == std::string::npos ? lb : lb - 2));
+          int k = 0;
+          if (lb != std::string::npos && rb != std::string::npos && rb > lb + 1) k = atoi(c.substr(lb + 1, rb - lb - 1).c_str());
+          if (!cp->vector_flag || k < 1 || k > cp->size_vector)
+            error.all(FLERR, "Thermo custom compute " + std::string(cp->id) + " is a vector of " + std::to_string(cp->size_vector) + ": " + c + " is not one of its elements");
+          if (cp->invoked_vector != (bigint) step) cp->compute_vector();
+          v = cp->vector[k - 1];
+        }
         else if (c == "vol") v = volume();
         else if (c == "cellgamma") {
           // angle between a and b edge vectors
@@ -1005,7 +1038,7 @@ struct Host {
 
   // ---------------------------------------------------------------- Verlet
   void force_clear() { std::fill(fs.begin(), fs.end(), 0.0); }
-  void write_dump(int bit, const std::string &path);
+  void write_dump(int bit, const std::string &path, bool with_image = false);
 
   void sync_domain() // Domain::set_global_box
   {
@@ -1047,6 +1080,7 @@ struct Host {
     build_neighbor_lists();
     if (!multi()) set_vviews();
     for (Fix *f : fixes) f->init(); // (LAMMPS::init: force->init() before modify->init())
+    for (Compute *c : computes) c->init(); // (Modify::init: the computes behind the fixes)
     // Neighbor::init(), behind Modify::init() in LAMMPS::init(): its check of the settings a fix may have touched
     if (neighbor.delay > 0 && neighbor.delay % neighbor.every != 0)
       error.all(FLERR, "Neighbor delay must be 0 or multiple of every setting");
@@ -1183,10 +1217,10 @@ struct Host {
 void HostAtomVec::grow(int n) { h->grow_arrays(n); }
 
 // the atoms of a group, from every rank, sorted by id: "id x y z vx vy vz" with %.17g (rank 0 writes)
-void Host::write_dump(int bit, const std::string &path)
+void Host::write_dump(int bit, const std::string &path, bool with_image)
 {
   struct Row {
-    int id;
+    int id, image;
     double x[3], v[3];
   };
   if (multi()) world->barrier(); // (every rank's atoms are where they are)
@@ -1198,6 +1232,7 @@ void Host::write_dump(int bit, const std::string &path)
         if (!(o->masks[i] & bit)) continue;
         Row r;
         r.id = o->tags[i];
+        r.image = o->images[i];
         for (int d = 0; d < 3; d++) {
           r.x[d] = o->xs[3 * (size_t) i + d];
           r.v[d] = o->vs[3 * (size_t) i + d];
@@ -1208,9 +1243,13 @@ void Host::write_dump(int bit, const std::string &path)
     std::sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) { return a.id < b.id; });
     FILE *fp = fopen(path.c_str(), "w");
     if (!fp) error.one(FLERR, "Cannot open dump file " + path);
-    fprintf(fp, "ITEM: TIMESTEP\n%ld\nITEM: NUMBER OF ATOMS\n%zu\nITEM: ATOMS id x y z vx vy vz\n", step, rows.size());
-    for (const Row &r : rows)
-      fprintf(fp, "%d %.17g %.17g %.17g %.17g %.17g %.17g\n", r.id, r.x[0], r.x[1], r.x[2], r.v[0], r.v[1], r.v[2]);
+    fprintf(fp, "ITEM: TIMESTEP\n%ld\nITEM: NUMBER OF ATOMS\n%zu\nITEM: ATOMS id x y z vx vy vz%s\n", step, rows.size(), with_image ? " ix iy iz" : "");
+    for (const Row &r : rows) {
+      fprintf(fp, "%d %.17g %.17g %.17g %.17g %.17g %.17g", r.id, r.x[0], r.x[1], r.x[2], r.v[0], r.v[1], r.v[2]);
+      if (with_image)
+        fprintf(fp, " %d %d %d", (r.image & IMGMASK) - IMGMAX, ((r.image >> IMGBITS) & IMGMASK) - IMGMAX, ((r.image >> IMG2BITS) & IMGMASK) - IMGMAX);
+      fprintf(fp, "\n");
+    }
     fclose(fp);
   }
   if (multi()) world->barrier(); // (nobody moves its atoms while rank 0 reads them)
@@ -1474,6 +1513,7 @@ struct Script {
     H.h_matrix(h);
     std::vector<double> xo(H.xs.begin(), H.xs.begin() + 3 * (size_t) n0), vo(H.vs.begin(), H.vs.begin() + 3 * (size_t) n0);
     std::vector<int> to(H.types.begin(), H.types.begin() + n0), mo(H.masks.begin(), H.masks.begin() + n0);
+    std::vector<int> io(H.images.begin(), H.images.begin() + n0);
     const int nn = n0 * nx * ny * nz;
     H.atom.nlocal = nn;
     H.atom.nghost = 0;
@@ -1490,6 +1530,7 @@ struct Script {
             }
             H.types[a] = to[q];
             H.masks[a] = mo[q];
+            H.images[a] = io[q];
             H.tags[a] = a + 1;
           }
     H.prd[0] *= nx;
@@ -1639,7 +1680,7 @@ struct Script {
       void *sym = dlsym(dso, "lammpsplugin_init");
       if (!sym) H.error.all(FLERR, "Plugin symbol lookup failure in file " + w[2] + ": lammpsplugin_init");
       H.handles.push_back(dso);
-      const size_t before = H.pair_styles.size() + H.fix_styles.size() + H.command_styles.size();
+      const size_t before = H.pair_styles.size() + H.fix_styles.size() + H.command_styles.size() + H.compute_styles.size();
       // registration callback: the host behind the LAMMPS* it is handed
       struct Trampoline {
         static void regfunc(lammpsplugin_t *p, void *lmp)
@@ -1647,9 +1688,9 @@ struct Script {
           Host *host = g_host;
           if (!host || lmp != (void *) &host->lmp || !p || !p->style || !p->name) return;
           const bool is_pair = strcmp(p->style, "pair") == 0, is_fix = strcmp(p->style, "fix") == 0;
-          const bool is_command = strcmp(p->style, "command") == 0;
-          if (!is_pair && !is_fix && !is_command) {
-            fprintf(stderr, "WARNING: plugin style %s/%s ignored (minilmp hosts pair, fix and command styles only)\n", p->style, p->name);
+          const bool is_command = strcmp(p->style, "command") == 0, is_compute = strcmp(p->style, "compute") == 0;
+          if (!is_pair && !is_fix && !is_command && !is_compute) {
+            fprintf(stderr, "WARNING: plugin style %s/%s ignored (minilmp hosts pair, fix, compute and command styles only)\n", p->style, p->name);
             return;
           }
           if (strcmp(p->version, LAMMPS_VERSION) != 0)
@@ -1661,13 +1702,14 @@ struct Script {
           }
           if (is_pair) host->pair_styles[p->name] = p->creator.v1;
           else if (is_command) host->command_styles[p->name] = p->creator.v1;
+          else if (is_compute) host->compute_styles[p->name] = p->creator.v2;
           else host->fix_styles[p->name] = p->creator.v2;
           printf("Loading plugin: %s by %s\n", p->info, p->author);
         }
       };
       g_host = &H;
       reinterpret_cast<lammpsplugin_initfunc>(sym)(&H.lmp, dso, (void *) &Trampoline::regfunc);
-      printf("Loaded %zu plugins from %s\n", H.pair_styles.size() + H.fix_styles.size() + H.command_styles.size() - before,
+      printf("Loaded %zu plugins from %s\n", H.pair_styles.size() + H.fix_styles.size() + H.command_styles.size() + H.compute_styles.size() - before,
              w[2].c_str());
     } else if (c == "pair_style") {
       need(2);
@@ -1775,14 +1817,16 @@ struct Script {
       } else
         H.error.all(FLERR, "minilmp supports `group ID region R`, `type T ...`, `id lo:hi ...`, `subtract G1 G2 ...` and `intersect G1 G2 ...` only");
       printf("%ld atoms in group %s\n", (long) H.group.count(ig), w[1].c_str());
-    } else if (c == "write_dump") { // write_dump ID custom FILE id x y z vx vy vz: the group's atoms, sorted by id, %.17g
+    } else if (c == "write_dump") { // write_dump ID custom FILE id x y z vx vy vz [ix iy iz]: the group's atoms, sorted by id, %.17g
       need(4);
       static const std::vector<std::string> cols = {"id", "x", "y", "z", "vx", "vy", "vz"};
-      if (w[2] != "custom" || std::vector<std::string>(w.begin() + 4, w.end()) != cols)
-        H.error.all(FLERR, "minilmp supports `write_dump ID custom FILE id x y z vx vy vz` only");
+      static const std::vector<std::string> cols_image = {"id", "x", "y", "z", "vx", "vy", "vz", "ix", "iy", "iz"};
+      const std::vector<std::string> asked(w.begin() + 4, w.end());
+      if (w[2] != "custom" || (asked != cols && asked != cols_image))
+        H.error.all(FLERR, "minilmp supports `write_dump ID custom FILE id x y z vx vy vz` only (the image flags: the same with `ix iy iz` behind it)");
       const int ig = H.group.find(w[1]);
       if (ig < 0) H.error.all(FLERR, "Could not find dump group ID " + w[1]);
-      H.write_dump(H.group_bits[ig], w[3]);
+      H.write_dump(H.group_bits[ig], w[3], asked == cols_image);
     } else if (c == "velocity" && w.size() > 2 && w[2] == "set") { // velocity ID set vx vy vz
       need(6);
       const int ig = H.group.find(w[1]);
@@ -1861,6 +1905,18 @@ struct Script {
         H.sync_modify();
       } else
         H.error.all(FLERR, "minilmp supports fix nve|nvt and time-integration fix styles of loaded plugins only");
+    } else if (c == "compute") { // compute ID group style args: a compute style from a plugin
+      need(4);
+      if (!H.compute_styles.count(w[3])) H.error.all(FLERR, "Unrecognized compute style '" + w[3] + "' (minilmp hosts the compute styles of loaded plugins only)");
+      H.update.ntimestep = H.step;
+      std::vector<char *> args;
+      for (size_t k = 1; k < w.size(); k++) args.push_back(const_cast<char *>(w[k].c_str()));
+      Compute *cp = static_cast<Compute *>(H.compute_styles[w[3]](&H.lmp, (int) args.size(), args.data()));
+      if (Compute *old = H.compute_by_id(cp->id)) { // (a compute with the ID of an existing one replaces it)
+        H.computes.erase(std::find(H.computes.begin(), H.computes.end(), old));
+        delete old;
+      }
+      H.computes.push_back(cp);
     } else if (c == "timestep") {
       need(2);
       H.dt = std::stod(w[1]);
@@ -1947,6 +2003,26 @@ extern "C" int MPI_Bcast(void *buffer, int count, MPI_Datatype, int root, MPI_Co
   return 0;
 }
 
+// ... and the one a compute style makes: the sum of every rank's doubles, added in rank order on every rank
+extern "C" int MPI_Allreduce(const void *sendbuf, void *recvbuf, int count, MPI_Datatype, MPI_Op, MPI_Comm)
+{
+  World *w = t_world;
+  if (count <= 0) return 0;
+  // (before the first `run` of `-np N` every rank thread still holds ALL atoms: what it has is the sum already)
+  if (!w || w->n == 1 || !w->host[t_rank] || !w->host[t_rank]->multi()) {
+    if (recvbuf != sendbuf) memcpy(recvbuf, sendbuf, sizeof(double) * (size_t) count);
+    return 0;
+  }
+  w->abuf[t_rank] = static_cast<const double *>(sendbuf);
+  w->barrier();
+  std::vector<double> tot((size_t) count, 0.0);
+  for (int q = 0; q < w->n; q++)
+    for (int i = 0; i < count; i++) tot[i] += w->abuf[q][i];
+  w->barrier(); // (every rank has read every send buffer: a receive buffer may be one of them)
+  memcpy(recvbuf, tot.data(), sizeof(double) * (size_t) count);
+  return 0;
+}
+
 int main(int argc, char **argv)
 {
   std::string infile;
@@ -2003,6 +2079,8 @@ int main(int argc, char **argv)
       delete H.pair;
       H.pair = nullptr;
       H.force.pair = nullptr;
+      for (Compute *c : H.computes) delete c;
+      H.computes.clear();
       for (Fix *f : H.fixes) delete f;
       H.fixes.clear();
       H.sync_modify();

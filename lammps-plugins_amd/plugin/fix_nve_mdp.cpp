@@ -44,8 +44,10 @@
      post_run            the pair style is released: the next run starts from the host's arrays like the first
    What the host still does every step is idle work on stale arrays (Comm::forward_comm / reverse_comm of its ghosts, a
    memset of f); arrays never shrink below nlocal + the stale ghosts, so that work stays inside them.  atom->mask travels
-   with the atoms whenever the host has a group besides all; image flags and per-atom properties beyond the atomic
-   style's are not carried -- atom_style atomic.
+   with the atoms whenever the host has a group besides all, and atom->image always does: the device's remap counts the
+   box vectors it takes off an atom (mdp_md_set_image), so unwrapped coordinates and displacements are right after a
+   bricks run, and compute msd/mdp reads them during one (Fix::extract("mdp_steps_ctx"), "mdp_bricks").  Per-atom
+   properties beyond the atomic style's are not carried -- atom_style atomic.
 
    Groups (`fix ID GROUP nve/mdp`, GROUP other than all).  The fix's group bit goes to the library (mdp_integrate_group),
    and atom->mask with the atoms: next to the velocities at every host reneighboring in the host-linked mode
@@ -198,6 +200,7 @@ void FixNVEMDP::setup(int /*vflag*/)
   mdp_ctx *c = bricks ? bctx : ctx();
   if (!c) fail(nullptr);
   apply_groups(c);
+  run_ctx = c;
   if (!lgv_on) return;
   if (mdp_langevin_setup(c, &lgv_cfg) != MDP_OK) fail(c);
   if (mdp_langevin_run(c, (long long) update->beginstep, (long long) update->endstep) != MDP_OK) fail(c);
@@ -212,6 +215,8 @@ void *FixNVEMDP::extract(const char *name, int &dim)
   if (strcmp(name, "mdp_langevin_on") == 0) return &lgv_on;
   if (strcmp(name, "mdp_langevin_bit") == 0) return &lgv_bit;
   if (strcmp(name, "mdp_run_ctx") == 0) return &lgv_ctx;
+  if (strcmp(name, "mdp_steps_ctx") == 0) return &run_ctx;
+  if (strcmp(name, "mdp_bricks") == 0) return &bricks;
   return nullptr;
 }
 
@@ -331,6 +336,7 @@ void FixNVEMDP::post_run()
 {
   if (lgv_ctx && mdp_langevin_off(lgv_ctx) != MDP_OK) fail(lgv_ctx); // (an unfix of the thermostat gives NVE next run)
   lgv_ctx = nullptr;
+  run_ctx = nullptr;
   lgv_on = 0;
   lgv_bit = 0;
   if (bricks) {

@@ -74,6 +74,9 @@ class FixNVEMDP : public Fix {
   int brick_masked = 0; // this run's brick was set up with atom->mask (it comes back with the atoms)
   int lgv_bit = 0;     // the thermostat's group bit (extract "mdp_langevin_bit"; 0: every atom the fix integrates)
   mdp_ctx *lgv_ctx = nullptr;
+  // the context the steps of the run under way go through, thermostat or not, null between runs (extract "mdp_steps_ctx":
+  // compute msd/mdp reads its sums there); extract "mdp_bricks": whether that context is a brick of the library's own
+  mdp_ctx *run_ctx = nullptr;
 
   mdp_ctx *ctx() const { return ctxp ? *ctxp : nullptr; }
   void setup_steps();

@@ -81,8 +81,9 @@ inline bool mdp_host_has_groups(Group *group) { return group && group->ngroup > 
 
 // this rank's owned atoms (x, v, type, tag as the host holds them) -> the brick of rank comm->me on comm->procgrid:
 // mdp_md_setup + mdp_dd_setup.  style_id: 1 rebomos (map: the style's type -> element map), 2 aeam.  with_mask: atom->mask
-// goes with the atoms (mdp_md_set_mask) and follows them through every reneighboring and migration.  Returns the
-// library's code; the message is mdp_last_error(ctx).
+// goes with the atoms (mdp_md_set_mask) and follows them through every reneighboring and migration.  atom->image always goes
+// with them (mdp_md_set_image): the device's remap counts the box vectors it takes off an atom, as Domain::remap does.
+// Returns the library's code; the message is mdp_last_error(ctx).
 inline int mdp_brick_from_host(mdp_ctx *ctx, int style_id, const int *map, Atom *atom, Domain *domain, Force *force,
                                Neighbor *neighbor, Update *update, Comm *comm, bool with_mask)
 {
@@ -115,6 +116,9 @@ inline int mdp_brick_from_host(mdp_ctx *ctx, int style_id, const int *map, Atom 
     rc = mdp_md_set_mask(ctx, n ? atom->mask : &idummy);
     if (rc != MDP_OK) return rc;
   }
+  static_assert(sizeof(imageint) == sizeof(int), "the device carries LAMMPS' 32-bit image flags (LAMMPS_SMALLBIG / SMALLSMALL)");
+  rc = mdp_md_set_image(ctx, n ? reinterpret_cast<const int *>(atom->image) : &idummy);
+  if (rc != MDP_OK) return rc;
   mdp_dd_config dd;
   memset(&dd, 0, sizeof dd);
   for (int d = 0; d < 3; d++) {
@@ -127,7 +131,7 @@ inline int mdp_brick_from_host(mdp_ctx *ctx, int style_id, const int *map, Atom 
   return mdp_dd_setup(ctx, &dd);
 }
 
-// the atoms the brick owns NOW, in the brick's order, into the host's arrays (x, v, tag, type; atom->nlocal follows).
+// the atoms the brick owns NOW, in the brick's order, into the host's arrays (x, v, tag, type, image; atom->nlocal follows).
 // with_mask: atom->mask comes back with them (as mdp_brick_from_host sent it); without, the host has no group but `all`
 // and every atom that comes back is in it
 inline int mdp_brick_to_host(mdp_ctx *ctx, Atom *atom, bool with_mask)
@@ -141,6 +145,7 @@ inline int mdp_brick_to_host(mdp_ctx *ctx, Atom *atom, bool with_mask)
     if ((rc = mdp_md_download(ctx, atom->x[0], atom->v[0], nullptr, nullptr)) != MDP_OK) return rc;
     if ((rc = mdp_md_download_int(ctx, "tag", atom->tag)) != MDP_OK) return rc;
     if ((rc = mdp_md_download_int(ctx, "type", atom->type)) != MDP_OK) return rc;
+    if ((rc = mdp_md_download_int(ctx, "image", reinterpret_cast<int *>(atom->image))) != MDP_OK) return rc;
     if (with_mask) {
       if ((rc = mdp_md_download_int(ctx, "mask", atom->mask)) != MDP_OK) return rc;
     } else
