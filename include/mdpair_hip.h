@@ -618,6 +618,40 @@ int mdp_msd_sums(mdp_ctx *ctx, const double *shift, double out[8]);
 int mdp_msd_info(mdp_ctx *ctx, long long out[4]);
 int mdp_msd_off(mdp_ctx *ctx);
 
+/* ---- pair-distance histograms: g(r) and coordination numbers (LAMMPS compute rdf), in integers ---------------------------
+ * For a resident context with mdp_dd_setup (MDP_ESTATE otherwise).  Nothing of a run is changed by a read: the binning is
+ * the measurement's own.
+ *   mdp_rdf_setup:   starts a measurement of npair columns (1 .. MDP_RDF_MAXPAIR) of nbin bins over 0 <= r < cutoff.  Column m
+ *                    counts the pairs with type(i) in ilo[m] .. ihi[m] and type(j) in jlo[m] .. jhi[m] (LAMMPS types
+ *                    1 .. ntypes, inclusive).  member_by_tag[ntag]: non-zero at [t - 1] if the atom with tag t belongs to
+ *                    the group, for ALL atoms of the system on every rank (a ghost is looked up by its tag; an atom that
+ *                    migrates keeps its membership); NULL: every atom.  A second call replaces the first.
+ *                    MDP_EINVAL: nbin < 1, npair outside 1 .. MDP_RDF_MAXPAIR, a type outside 1 .. ntypes, lo > hi,
+ *                    cutoff <= 0, nbin * npair > MDP_RDF_MAXCOUNTERS (the workgroup's histogram in LDS: 32 KB of 32-bit
+ *                    counters), and cutoff + skin > the cutghost of mdp_dd_setup: the ghost shell is as of the last
+ *                    reneighbouring and atoms have since moved up to half a skin each, so only the pairs within
+ *                    cutghost - skin are guaranteed present.
+ *   mdp_rdf_counts:  blocking.  hist[m][b] = this rank's number of ordered pairs (i owned, j owned or ghost, j != i as an
+ *                    array entry -- a periodic image of an atom is a separate j, the atom's own image included, as LAMMPS'
+ *                    ghost atoms are) of members with the types of column m and b = (int) (r nbin / cutoff) < nbin,
+ *                    r = sqrt(dx^2 + dy^2 + dz^2) in double from the current positions.  icount[m], jcount[m], dup[m]: this
+ *                    rank's owned members whose type lies in the i range, the j range, both.  The caller sums the four arrays
+ *                    over the ranks and normalises.  All integers: two reads of one state agree exactly, and the sum over
+ *                    the bricks equals the one-brick histogram.  MDP_ESTATE without a setup; MDP_EINVAL if an owned or ghost
+ *                    atom has a tag outside 1 .. ntag of the member table.
+ *                    Types: a resident context has 1 .. 15 atom types (mdp_md_setup refuses more), which is what the 4-bit
+ *                    type code of the cell-ordered records and the 16 x 16 table of column masks hold.
+ *   mdp_rdf_info:    out = {a measurement is on, its nbin, its npair, its serial}; the serial is unique in the process, as
+ *                    that of mdp_msd_info: two users of one context tell by it whether the setup is still theirs.
+ *   mdp_rdf_off:     releases the tables and the buffers of the binning. */
+#define MDP_RDF_MAXPAIR 32
+#define MDP_RDF_MAXCOUNTERS 8192
+int mdp_rdf_setup(mdp_ctx *ctx, int nbin, double cutoff, int npair, const int *ilo, const int *ihi, const int *jlo,
+                  const int *jhi, int ntag, const unsigned char *member_by_tag);
+int mdp_rdf_counts(mdp_ctx *ctx, long long *hist, long long *icount, long long *jcount, long long *dup);
+int mdp_rdf_info(mdp_ctx *ctx, long long out[4]);
+int mdp_rdf_off(mdp_ctx *ctx);
+
 /* per-phase device time of the last compute in ms (HIP events on the compute stream):
  * rebomos: [0]=REBO centre kernels of the lane-group classes, [1]=the general kernel (centres that outgrew their lane
  * group since the list build), [2]=row pruning (0 unless one was due), [3]=LJ+gather kernel;

@@ -921,6 +921,7 @@ int mdp_destroy(mdp_ctx *c)
   c->mask.release();
   c->image.release();
   mdp_msd_release(c);
+  mdp_rdf_release(c);
   if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
   delete c;
   return MDP_OK;

@@ -347,6 +347,22 @@ struct MdpMsd {
   DevBuf<double> xu;   // [nlocal][3] unwrapped positions (mdp_md_download_unwrapped)
   DevBuf<double> part; // per-block partials, kMsdW per block, then the kMsdW sums
 };
+// pair-distance histograms (rdf.hip): a binning of its own and the counters of a read; nothing here is shared with the list
+// builders, so a read leaves the run's scratch alone
+struct MdpRdf {
+  bool on = false;
+  int nbin = 0, npair = 0, ntypes = 0, ntag = 0; // ntag 0: every atom is a member
+  double cutoff = 0.0;
+  long long serial = 0;            // which mdp_rdf_setup of this process the tables belong to (mdp_rdf_info)
+  DevBuf<unsigned char> member;    // [ntag] membership of the atom with tag t at [t - 1], the WHOLE system on every rank
+  DevBuf<int> tab;                 // column masks per (type i, type j), then the i and j masks per type
+  DevBuf<unsigned> key_a, key_b;   // cell of every atom, before and after the sort
+  DevBuf<int> val_a, perm, code;   // atom indices before / after the sort; type, membership and ownership per atom
+  DevBuf<int> cell_start;          // [ncell + 1]
+  DevBuf<double4> rec;             // [nall] {x, y, z, code} in cell order
+  DevBuf<char> sort_tmp;
+  DevBuf<unsigned long long> out;  // [npair][nbin] histogram, then icount / jcount / dup [MDP_RDF_MAXPAIR] each, then the bad tags
+};
 static constexpr int kMsdW = 9; // sum dx^2, dy^2, dz^2, count, sum m xu (3), sum m, atoms whose tag has no origin
 
 // what the integrate kernels need to add the Langevin force of one step (md.hip nve_advance_kernel / nve_final_kernel)
@@ -677,6 +693,7 @@ struct mdp_ctx {
   DevBuf<int> image;               // [nlocal] atom->image, LAMMPS' 32-bit imageint: device order, remapped, permuted and migrated with the atoms
   bool image_set = false;
   MdpMsd msd;
+  MdpRdf rdf;                      // pair-distance histograms of the current positions (mdp_rdf_setup)
   bool final_pending = false;      // the host deferred the final half-kick of the finished step (mdp_md_defer_final)
   bool final_deferred_seen = false; // the host uses mdp_md_defer_final at all (older hosts: with_final is authoritative)
   bool acc_prezeroed = false; // the integrate kernel reset the accumulators: the next mdp_acc_begin launches nothing
@@ -861,6 +878,7 @@ int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvA
 int mdp_group_args(mdp_ctx *c, bool *masked, MdpGroupArgs *M);
 int mdp_lgv_close(mdp_ctx *c, const MdpLgvArgs &L);
 void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
+void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds
 // FIRE minimiser (fire.hip), in place of the integrate kernel when c->fire.on: the half step back / zeroing and the Euler
 // step of the iteration whose control kernel was queued last, with the same votes, accumulator reset and force clear
 int mdp_fire_launch_advance(mdp_ctx *c, int *flag, double trigsq, double hardsq, const MdpStyleCheck &sc, bool zero_f);

@@ -99,6 +99,7 @@ EXPORTS = [
     "mdp_fire_setup", "mdp_fire_iterate", "mdp_fire_state", "mdp_fire_off",
     "mdp_md_set_mask", "mdp_hnve_set_mask", "mdp_integrate_group", "mdp_langevin_group",
     "mdp_md_set_image", "mdp_md_download_unwrapped", "mdp_msd_setup", "mdp_msd_sums", "mdp_msd_info", "mdp_msd_off",
+    "mdp_rdf_setup", "mdp_rdf_counts", "mdp_rdf_info", "mdp_rdf_off",
 ]
 
 
@@ -796,6 +797,36 @@ class Context:
 
     def msd_off(self):
         self._ck(self.L.mdp_msd_off(self.h))
+
+    # ---------------- pair-distance histograms: g(r) and coordination numbers (csrc/rdf.hip)
+    def rdf_setup(self, nbin, cutoff, pairs, member_by_tag=None):
+        """starts a measurement: pairs = [(ilo, ihi, jlo, jhi), ...] inclusive ranges of LAMMPS types, one column each;
+        member_by_tag[t - 1] non-zero: the atom with tag t belongs to the group (ALL atoms of the system); None: every atom"""
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 4)
+        cols = [np.ascontiguousarray(pr[:, k]) for k in range(4)]
+        mem = None if member_by_tag is None else np.ascontiguousarray(np.asarray(member_by_tag) != 0, dtype=np.uint8)
+        self._ck(self.L.mdp_rdf_setup(self.h, C.c_int(int(nbin)), C.c_double(float(cutoff)), C.c_int(len(pr)), _ip(cols[0]),
+                                      _ip(cols[1]), _ip(cols[2]), _ip(cols[3]), C.c_int(0 if mem is None else len(mem)),
+                                      None if mem is None else mem.ctypes.data_as(C.POINTER(C.c_ubyte))))
+
+    def rdf_counts(self):
+        """this rank's (hist[npair][nbin], icount, jcount, dup) as int64"""
+        info = self.rdf_info()
+        nbin, npair = max(info["nbin"], 1), max(info["npair"], 1)
+        hist = np.zeros((npair, nbin), dtype=np.int64)
+        cnt = np.zeros((3, npair), dtype=np.int64)
+        lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_longlong))
+        self._ck(self.L.mdp_rdf_counts(self.h, lp(hist), lp(cnt[0]), lp(cnt[1]), lp(cnt[2])))
+        return hist, cnt[0].copy(), cnt[1].copy(), cnt[2].copy()
+
+    def rdf_info(self):
+        """whether a measurement is on, its nbin and npair, and its serial (unique in the process per rdf_setup)"""
+        out = (C.c_longlong * 4)()
+        self._ck(self.L.mdp_rdf_info(self.h, out))
+        return dict(on=bool(out[0]), nbin=int(out[1]), npair=int(out[2]), serial=int(out[3]))
+
+    def rdf_off(self):
+        self._ck(self.L.mdp_rdf_off(self.h))
 
     # halo plumbing (device pointers as ints)
     def md_pack_x(self, n, d_sendlist, d_shift, d_buf):

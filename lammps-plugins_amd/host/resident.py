@@ -120,6 +120,27 @@ class NativeTransport:
         return self.ctx.dd_comm_allreduce(list(values), op=0)
 
 
+def rdf_normalise(hist, icount, jcount, dup, cutoff, volume):
+    """LAMMPS' compute rdf array [nbin][1 + 2 npair] from rank-summed counts (DeviceDomain.rdf_read): column 0 the bin centres,
+    then g(r) and the coordination number per pair.  volume = xprd yprd zprd, triclinic included."""
+    hist = np.atleast_2d(np.asarray(hist, dtype=np.float64))
+    npair, nbin = hist.shape
+    delr = cutoff / nbin
+    const = 4.0 * np.pi / (3.0 * volume)
+    b = np.arange(nbin, dtype=np.float64)
+    vfrac = const * (((b + 1.0) * delr) ** 3 - (b * delr) ** 3)
+    out = np.zeros((nbin, 1 + 2 * npair))
+    out[:, 0] = (b + 0.5) * delr
+    for m in range(npair):
+        ic, jc, du = float(icount[m]), float(jcount[m]), float(dup[m])
+        normfac = jc - du / ic if ic > 0 else 0.0
+        den = vfrac * normfac * ic
+        g = np.divide(hist[m], den, out=np.zeros(nbin), where=den != 0.0)
+        out[:, 1 + 2 * m] = g
+        out[:, 2 + 2 * m] = np.cumsum(g * vfrac * normfac)
+    return out
+
+
 class DeviceDomain:
     """One brick of the periodic box per GPU, all bookkeeping on the device.
 
@@ -488,6 +509,30 @@ class DeviceDomain:
 
     def msd_off(self):
         self.ctx.msd_off()
+
+    # ------------------------------------------------------------------ g(r) and coordination numbers
+    def rdf(self, nbin, cutoff, pairs, member_by_tag=None):
+        """starts a pair-distance histogram (LAMMPS compute rdf) of nbin bins below cutoff (at most cutghost - skin: what the
+        ghost shell guarantees between two reneighbourings).  pairs: one (itype, jtype) per column, each a LAMMPS type or an
+        inclusive range (lo, hi).  member_by_tag[t - 1] non-zero: the atom with tag t is in the group, for all atoms of the
+        system; None: every atom.  With several ranks every rank makes the same call."""
+        rng = lambda t: (int(t), int(t)) if np.ndim(t) == 0 else (int(t[0]), int(t[1]))
+        self._rdf = dict(nbin=int(nbin), cutoff=float(cutoff), pairs=[rng(i) + rng(j) for i, j in pairs])
+        self.ctx.rdf_setup(nbin, cutoff, self._rdf["pairs"], member_by_tag)
+
+    def rdf_read(self):
+        """(hist[npair][nbin], icount[npair], jcount[npair], dup[npair]) as int64, summed over the ranks through the domain's
+        transport; rdf_normalise makes LAMMPS' array of them"""
+        self.flush()
+        hist, ic, jc, du = self.ctx.rdf_counts()
+        flat = np.concatenate([hist.ravel(), ic, jc, du])
+        assert int(flat.max(initial=0)) < 2 ** 53          # (the transports sum doubles: exact below 2^53)
+        tot = np.rint(self._group_sum(flat.astype(np.float64))).astype(np.int64)
+        nh, npair = hist.size, len(ic)
+        return (tot[:nh].reshape(hist.shape), tot[nh:nh + npair], tot[nh + npair:nh + 2 * npair], tot[nh + 2 * npair:])
+
+    def rdf_off(self):
+        self.ctx.rdf_off()
 
     def thermostat(self, t_start, t_stop, t_period, tchain=3, tloop=1, drag=0.0, first=0, last=0, nf=None):
         """Nose-Hoover chain thermostat (LAMMPS fix nvt) in the integrate calls of this domain, from the chain at rest; one

@@ -346,7 +346,7 @@ class Fix : protected Pointers {
   virtual void *extract(const char *, int &) { return nullptr; } // what a fix hands another one (Fix::extract)
 };
 
-// the part of LAMMPS' Compute a global-vector compute style touches (compute.h of the 2 Aug 2023 release)
+// the part of LAMMPS' Compute a global-vector or global-array compute style touches (compute.h of the 2 Aug 2023 release)
 class Compute : protected Pointers {
  public:
   char *id = nullptr, *style = nullptr;
@@ -354,6 +354,9 @@ class Compute : protected Pointers {
   double *vector = nullptr;     // the values compute_vector() leaves (thermo c_ID[k] reads vector[k - 1])
   int vector_flag = 0, size_vector = 0, extvector = 0, create_attribute = 0;
   bigint invoked_vector = -1;   // the step compute_vector() ran last
+  double **array = nullptr;     // the values compute_array() leaves (thermo c_ID[i][j] reads array[i - 1][j - 1])
+  int array_flag = 0, size_array_rows = 0, size_array_cols = 0, extarray = 0;
+  bigint invoked_array = -1;    // the step compute_array() ran last
 
   // (as Fix: an unknown group ID leaves igroup = -1 and no bit, and the style says what it takes)
   Compute(LAMMPS *lmp, int narg, char **arg) : Pointers(lmp)
@@ -372,6 +375,7 @@ class Compute : protected Pointers {
   }
   virtual void init() = 0;
   virtual void compute_vector() {}
+  virtual void compute_array() {}
 };
 
 // a command style (command.h of the 2 Aug 2023 release): one object per use of the input word, command() runs it

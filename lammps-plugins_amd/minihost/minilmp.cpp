@@ -984,6 +984,34 @@ struct Host {
     return e;
   }
 
+  // A thermo column c_ID[k] (element k of a global vector compute) or c_ID[i][j] (element (i, j) of a global array
+  // compute): the compute and the indices, j = 0 for a vector.  Refused: an unknown ID (must_exist; otherwise nullptr:
+  // the compute may be defined later, and the column is looked at again when it is printed), a compute of the other
+  // kind, an index out of bounds.
+  Compute *compute_ref(const std::string &c, bool must_exist, int &i, int &j)
+  {
+    const size_t lb = c.find('['), rb = c.find(']');
+    const std::string id = c.substr(2, lb == std::string::npos ? lb : lb - 2);
+    Compute *cp = compute_by_id(id);
+    i = j = 0;
+    if (!cp) {
+      if (must_exist) error.all(FLERR, "Could not find thermo custom compute ID: " + id);
+      return nullptr;
+    }
+    if (lb != std::string::npos && rb != std::string::npos && rb > lb + 1) i = atoi(c.substr(lb + 1, rb - lb - 1).c_str());
+    const size_t lb2 = rb == std::string::npos ? rb : c.find('[', rb), rb2 = lb2 == std::string::npos ? lb2 : c.find(']', lb2);
+    if (lb2 != std::string::npos) {
+      if (rb2 != std::string::npos && rb2 > lb2 + 1) j = atoi(c.substr(lb2 + 1, rb2 - lb2 - 1).c_str());
+      if (!cp->array_flag || i < 1 || i > cp->size_array_rows || j < 1 || j > cp->size_array_cols)
+        error.all(FLERR, "Thermo custom compute " + std::string(cp->id) + " is an array of " + std::to_string(cp->size_array_rows) + " x " +
+                             std::to_string(cp->size_array_cols) + ": " + c + " is not one of its elements");
+      return cp;
+    }
+    if (!cp->vector_flag || i < 1 || i > cp->size_vector)
+      error.all(FLERR, "Thermo custom compute " + std::string(cp->id) + " is a vector of " + std::to_string(cp->size_vector) + ": " + c + " is not one of its elements");
+    return cp;
+  }
+
   void print_thermo()
   {
     const double ke = kinetic(), t = dof() > 0 ? 2.0 * ke / (dof() * BOLTZ) : 0.0;
@@ -1010,16 +1038,16 @@ struct Host {
           if (!f) error.all(FLERR, "Could not find thermo custom fix ID: " + c.substr(2));
           v = f->compute_scalar();
         }
-        else if (c.compare(0, 2, "c_") == 0) { // c_ID[k]: element k of a global vector compute, evaluated once per step
-          const size_t lb = c.find('['), rb = c.find(']');
-          Compute *cp = compute_by_id(c.substr(2, lb == std::string::npos ? lb : lb - 2));
-          if (!cp) error.all(FLERR, "Could not find thermo custom compute ID: " + c.substr(2, lb == std::string::npos ? lb : lb - 2));
-          int k = 0;
-          if (lb != std::string::npos && rb != std::string::npos && rb > lb + 1) k = atoi(c.substr(lb + 1, rb - lb - 1).c_str());
-          if (!cp->vector_flag || k < 1 || k > cp->size_vector)
-            error.all(FLERR, "Thermo custom compute " + std::string(cp->id) + " is a vector of " + std::to_string(cp->size_vector) + ": " + c + " is not one of its elements");
-          if (cp->invoked_vector != (bigint) step) cp->compute_vector();
-          v = cp->vector[k - 1];
+        else if (c.compare(0, 2, "c_") == 0) { // c_ID[k] / c_ID[i][j]: evaluated once per step
+          int i = 0, j = 0;
+          Compute *cp = compute_ref(c, true, i, j);
+          if (j) {
+            if (cp->invoked_array != (bigint) step) cp->compute_array();
+            v = cp->array[i - 1][j - 1];
+          } else {
+            if (cp->invoked_vector != (bigint) step) cp->compute_vector();
+            v = cp->vector[i - 1];
+          }
         }
         else if (c == "vol") v = volume();
         else if (c == "cellgamma") {
@@ -1925,7 +1953,14 @@ struct Script {
       H.thermo_every = std::stoi(w[1]);
     } else if (c == "thermo_style") {
       need(2);
-      if (w[1] == "custom") H.thermo_cols.assign(w.begin() + 2, w.end());
+      if (w[1] == "custom") {
+        H.thermo_cols.assign(w.begin() + 2, w.end());
+        for (auto &col : H.thermo_cols) // a column of a compute defined by now is checked now, as at every print
+          if (col.compare(0, 2, "c_") == 0) {
+            int i, j;
+            H.compute_ref(col, false, i, j);
+          }
+      }
       else if (w[1] == "one") H.thermo_cols = {"step", "temp", "epair", "emol", "etotal", "press"};
     } else if (c == "thermo_modify") {
     } else if (c == "run") {
