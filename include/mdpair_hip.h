@@ -310,6 +310,12 @@ int mdp_md_list_state(mdp_ctx *ctx, double out[8]);
  * [4]=row entries incl. padding, [5]=#clusters, [6]=#tiles in the large-union launch classes,
  * [7]=style-list builds so far.  (No reference counterpart: the CPU style reads the host's list.) */
 int mdp_rebomos_list_info(mdp_ctx *ctx, long long out[8]);
+/* rebomos, diagnostics: which pair loops the waves of the lane-group centre kernels took in the computes run with
+ * MDP_CENTRE_COUNT=1 in the environment since the last reset: out[0] = waves on the full-group path (every lane group
+ * of the wave holds a centre with exactly as many neighbours as the group has lanes), out[1] = waves that hold a centre
+ * and took the general loops (all of them with MDP_CENTRE_FULL=0).  reset != 0 clears both afterwards.  Waits for the
+ * stream.  (No reference counterpart.) */
+int mdp_rebomos_centre_paths(mdp_ctx *ctx, long long out[2], int reset);
 /* how the work of the last compute was spread over the kernel classes (diagnostics of a bench line; no reference
  * counterpart -- the CPU style has one loop, pair_rebomos.cpp:358-447, pair_aeam.cpp:337-475):
  * rebomos: out[0..19] = centres per launch class at the last style-list build, class = 2 * (lane-group index: 0 one lane

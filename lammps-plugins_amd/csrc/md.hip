@@ -1731,6 +1731,19 @@ int mdp_rebomos_list_info(mdp_ctx *c, long long out[8])
   return MDP_OK;
 }
 
+int mdp_rebomos_centre_paths(mdp_ctx *c, long long out[2], int reset)
+{
+  if (!c || !out) return MDP_EINVAL;
+  out[0] = out[1] = 0;
+  if (!c->centre_paths.p) return MDP_OK; // (no compute has counted yet)
+  unsigned long long h[2];
+  MDP_TRY(mdp_read_one(c, c->centre_paths.p, sizeof h, h));
+  out[0] = (long long) h[0];
+  out[1] = (long long) h[1];
+  if (reset) MDP_HIP(c, hipMemsetAsync(c->centre_paths.p, 0, sizeof h, c->stream));
+  return MDP_OK;
+}
+
 int mdp_md_class_stats(mdp_ctx *c, long long out[32])
 {
   if (!c || !out) return MDP_EINVAL;

@@ -854,6 +854,7 @@ int mdp_destroy(mdp_ctx *c)
   c->class_count.release();
   c->pk_cand.release();
   c->amask.release();
+  c->centre_paths.release();
   c->xhold_all.release();
   c->ovf.release();
   c->rev.release();

@@ -27,6 +27,18 @@
 
 #include <type_traits>
 
+// The series coefficients live in constant memory, not in the instruction stream: a uniform address makes them scalar
+// loads, so they sit in SGPR pairs and every Horner step is ONE three-operand v_fma_f64 with the coefficient as its
+// scalar addend.  As literals they were kept in VGPR pairs and each step was a v_mov_b64 of the coefficient followed by
+// the two-address v_fmac_f64: a copy per coefficient and 34 VGPRs.
+// (Outside the unnamed namespace on purpose: with internal linkage the compiler folds the loads back into literals.)
+// (one copy of the coefficients: the lane-group centre kernel reads them from the arrays, every other kernel keeps them
+//  as literals -- sincospi_half)
+#define MDP_SINPI_COEFFS 3.14159265358979312e+00, -5.16771278004996937e+00, 2.55016403987734508e+00, -5.99264529320791883e-01, 8.21458866111281910e-02, -7.37043094571434784e-03, 4.66302805767612337e-04, -2.19153534478302037e-05
+#define MDP_COSPI_COEFFS 1.00000000000000000e+00, -4.93480220054467900e+00, 4.05871212641676760e+00, -1.33526276885458928e+00, 2.35330630358893123e-01, -2.58068913900140508e-02, 1.92957430940392206e-03, -1.04638104924845650e-04, 4.30306958703294391e-06
+__constant__ double mdp_sinpi_series[8] = {MDP_SINPI_COEFFS};
+__constant__ double mdp_cospi_series[9] = {MDP_COSPI_COEFFS};
+
 namespace {
 
 #ifndef MDP_LJ_WAVES
@@ -124,18 +136,50 @@ __device__ __forceinline__ double sp_switch(double r, double rmin, double rinv, 
 // sin(pi u) and cos(pi u) for u in [0, 1/2] (the only range the G(cos) blend needs): fold to [0, 1/4] and
 // evaluate the Taylor series in v^2 there (truncation < 5e-17); ~25 instructions instead of the general
 // sincospi's argument reduction and quadrant logic.
-__device__ __forceinline__ void sincospi_half(const double u, double &sn, double &cs)
+// The leading coefficients of the two series, pinned to VGPRs: an instruction reads one scalar operand, and with both
+// the coefficient and the addend in SGPRs the first Horner step would start with a copy.  A kernel that evaluates the
+// series in a loop fetches them once in front of it.
+struct SeriesLead {
+  double s7, c8;
+};
+__device__ __forceinline__ SeriesLead series_lead()
+{
+  SeriesLead l = {mdp_sinpi_series[7], mdp_cospi_series[8]};
+  asm("" : "+v"(l.s7));
+  asm("" : "+v"(l.c8));
+  return l;
+}
+
+// Kernels that evaluate the series once per lane, outside a loop, keep the coefficients as literals (rebo_centre3_kernel,
+// rebo_centre_general_kernel: their code is what it was before the arrays existed).
+struct SeriesLiteral {};
+
+template <class L>
+__device__ __forceinline__ void sincospi_half(const double u, double &sn, double &cs, const L &lead)
 {
   const bool fold = u > 0.25;
   const double v = fold ? 0.5 - u : u;
   const double w = v * v;
-  constexpr double S[8] = {3.14159265358979312e+00, -5.16771278004996937e+00, 2.55016403987734508e+00, -5.99264529320791883e-01, 8.21458866111281910e-02, -7.37043094571434784e-03, 4.66302805767612337e-04, -2.19153534478302037e-05};
-  constexpr double C[9] = {1.00000000000000000e+00, -4.93480220054467900e+00, 4.05871212641676760e+00, -1.33526276885458928e+00, 2.35330630358893123e-01, -2.58068913900140508e-02, 1.92957430940392206e-03, -1.04638104924845650e-04, 4.30306958703294391e-06};
-  double ps = S[7], pc = C[8];
+  double ps, pc;
+  if constexpr (std::is_same<L, SeriesLead>::value) {
+    const double *S = mdp_sinpi_series, *C = mdp_cospi_series;
+    ps = lead.s7;
+    pc = lead.c8;
 #pragma unroll
-  for (int k = 6; k >= 0; k--) ps = fma(ps, w, S[k]);
+    for (int k = 6; k >= 0; k--) ps = fma(ps, w, S[k]);
 #pragma unroll
-  for (int k = 7; k >= 0; k--) pc = fma(pc, w, C[k]);
+    for (int k = 7; k >= 1; k--) pc = fma(pc, w, C[k]);
+    pc = fma(pc, w, 1.0); // (C[0], an inline constant)
+  } else {
+    constexpr double S[8] = {MDP_SINPI_COEFFS};
+    constexpr double C[9] = {MDP_COSPI_COEFFS};
+    ps = S[7];
+    pc = C[8];
+#pragma unroll
+    for (int k = 6; k >= 0; k--) ps = fma(ps, w, S[k]);
+#pragma unroll
+    for (int k = 7; k >= 0; k--) pc = fma(pc, w, C[k]);
+  }
   ps *= v;
   sn = fold ? pc : ps;
   cs = fold ? ps : pc;
@@ -184,7 +228,8 @@ __device__ __forceinline__ double gspline_val(const double *cb, const double *cg
 }
 
 // G(cos) and dG/dcos, pair_rebomos.h:68-167.  cb/cg: the centre element's b0..b6 / bg0..bg6.
-__device__ __forceinline__ double gspline(const double *cb, const double *cg, double c, double &dgdc)
+template <class L>
+__device__ __forceinline__ double gspline(const double *cb, const double *cg, double c, double &dgdc, const L &lead)
 {
   if (c < 0.5) { // caller clamps to [-1,1] (pair_rebomos.cpp:617-618)
     return poly6(cb, c, dgdc);
@@ -194,11 +239,16 @@ __device__ __forceinline__ double gspline(const double *cb, const double *cg, do
   const double gamma = poly6(cg, c, dgamma);
   // psi = (1 - cos 2 pi u)/2 = sin^2(pi u),  psi' = pi sin 2 pi u = 2 pi sin(pi u) cos(pi u),  u = c - 1/2
   double s, co;
-  sincospi_half(c - 0.5, s, co);
+  sincospi_half(c - 0.5, s, co, lead);
   const double psi = s * s;
   const double dpsi = 2.0 * kPi * s * co;
   dgdc = dgcos + dpsi * (gamma - gcos) + psi * (dgamma - dgcos);
   return gcos + psi * (gamma - gcos);
+}
+
+__device__ __forceinline__ double gspline(const double *cb, const double *cg, double c, double &dgdc)
+{
+  return gspline(cb, cg, c, dgdc, SeriesLiteral{});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -333,6 +383,24 @@ __device__ __forceinline__ void centre_take(const RebomosDev &P, const int tc, c
   if (base < 64) active |= gb << base;
 }
 
+// lane shuffle of a double by a ready-made byte address (4 * source lane): what __shfl does, without its index arithmetic
+__device__ __forceinline__ double bpermute_f64(const int addr4, const double v)
+{
+  const int lo = __builtin_amdgcn_ds_bpermute(addr4, __double2loint(v));
+  const int hi = __builtin_amdgcn_ds_bpermute(addr4, __double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
+// a double nobody reads: a register pair as it stands (what lanes ship that own no pair in a trip), defined so that
+// the compiler neither zeroes it nor reasons about an uninitialised value.  K tells the values of one trip apart: equal
+// statements would be merged into one value, and that one copied into every register that carries it.
+template <int K> __device__ __forceinline__ double unread_f64()
+{
+  double v;
+  asm("; unread value %1" : "=v"(v) : "n"(K));
+  return v;
+}
+
 template <int G> struct CentreCfg {
   static constexpr int CAP = G;          // fast kernel: every neighbour has its own lane
   static constexpr int GPW = 64 / G;     // centres per wave (G = 12: five, lanes 60..63 idle)
@@ -359,7 +427,9 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
     const double4 *__restrict__ xq, const int *__restrict__ cand_off, const int *__restrict__ cand,
     const int *__restrict__ pk, unsigned long long *__restrict__ amask, double *__restrict__ fnbr,
     double *__restrict__ fown, double *__restrict__ acc, int *__restrict__ ovf, const int eflag, const int vflag,
-    const int tc /* element of every centre of this launch: a scalar, and with it all per-element constants */)
+    const int tc /* element of every centre of this launch: a scalar, and with it all per-element constants */,
+    const int full_on /* 0: every wave takes the general pair loops (MDP_CENTRE_FULL=0) */,
+    unsigned long long *__restrict__ path_cnt /* null, or {waves on the full-group path, other waves} (MDP_CENTRE_COUNT=1) */)
 {
   using C = CentreCfg<G>;
   __shared__ double s_rec[C::WPB * C::GPW * C::STRIDE];
@@ -448,6 +518,11 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
     if (s == 0) ovf[1 + atomicAdd(&ovf[0], 1)] = c;
     n = 0;
   }
+  // The centre once more, -1 unless it is an owned one that this kernel finishes: "owned" for the tallies and the store
+  // of the centre's own share at the end, carried in the register that held c.  (As lane masks the two conditions sit
+  // in SGPR pairs through both pair loops, which need every SGPR for the polynomial and series coefficients.)
+  int c_own = (have && c < nlocal && !outgrown) ? c : -1;
+  asm("" : "+v"(c_own));
   const double Ntot = group_sum_any<G>(nsum, s, lane);
   wave_lds_fence();
 
@@ -463,9 +538,9 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
   const double dp = -P.a[tc][0] + P.a[tc][1] * P.a[tc][2] * ea;
   const double PS = -P.a[tc][0] * (Ntot - 1.0) - P.a[tc][1] * ea + P.a[tc][3];
 
+  const SeriesLead lead = series_lead();
   const int nw = wave_max_int(n);
   CentreOut o = {0, 0, 0, 0, 0, 0, 0};
-  const bool owned = have && c < nlocal;
 
   const int m = s;
   const bool act = m < n;
@@ -487,7 +562,56 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
   //    a lane shuffle (lane q reads from lane q-d).  S_m = sum_q w_q G(m,q) (pair_rebomos.cpp:607-630) is
   //    complete when the loop ends -- no second pass over the pairs.
   const int lane_base = (threadIdx.x & 63) - s;
+  // -- the full-group path: every lane group of this wave that can hold a centre has exactly G neighbours (the crystal
+  //    and the warm crystal: a Mo centre of MoS2 has 6 S + 6 Mo and 12 lanes).  Then every lane of a group is active, the
+  //    trip count is G/2 and d is a compile-time value: the partner's record and the lane's matrix entry sit at immediate
+  //    offsets from two per-lane bases (one select for the wrap), the shuffle sources are computed once per wave and
+  //    kept, and nothing is zeroed or selected for inactive lanes.  Same pairs, same order of the sums as the general
+  //    loops below, which every other wave takes (a group with fewer neighbours, an outgrown centre, a partial wave).
+  constexpr bool kFullPath = G <= 16;
+  constexpr bool kAllLanes = C::GPW * G == 64; // (G = 12: lanes 60..63 form no group and stay out of the full path)
+  // (the lane number once more, from the exec-independent count: the two tests of the full path then cost a compare each
+  //  instead of a lane mask of `lane_ok` that is held in two SGPRs from the first line of the kernel to the last loop)
+  const int lane_again = (int) __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  bool full = false;
+  if constexpr (kFullPath) full = full_on && __all(!lane_ok || n == G);
+  if (path_cnt && __any(have) && lane == 0) atomicAdd(&path_cnt[full ? 0 : 1], 1ull);
+  const double *qm = rec + m * kRecF;          // own record: the partner (m + d) is d records on,
+  const double *qwrap = qm - G * kRecF;        // ... or G - d records back
+  double *em = mat + 2 * m;
+  int from4[kFullPath ? G / 2 : 1];            // byte address of lane (m - d) mod G of the group, d = 1 .. G/2
+  if constexpr (kFullPath)
+    if (full) {
+#pragma unroll
+      for (int d = 1; d <= G / 2; d++) from4[d - 1] = 4 * (lane - d + (m < d ? G : 0));
+    }
   double S = 0.0;
+  if (full) {
+    if constexpr (kFullPath)
+      if (kAllLanes || lane_again < C::GPW * G) {
+#pragma unroll
+        for (int d = 1; d <= G / 2; d++) {
+          const bool half = 2 * d == G; // the distance-G/2 pairs: taken by the lower half of the lanes
+          const double *q = (m >= G - d ? qwrap : qm) + d * kRecF;
+          double give = unread_f64<0>(); // (lanes that own no pair this trip ship nothing anyone reads)
+          if (!half || m < d) {
+            double cs = (ux * q[0] + uy * q[1] + uz * q[2]) * q[kInvF];
+            cs = fmin(cs, 1.0);
+            cs = fmax(cs, -1.0);
+            double dg, g;
+            if (__any(cs >= 0.5)) g = gspline(cb, cg, cs, dg, lead);
+            else g = poly6(cb, cs, dg);
+            em[2 * (d - 1) * G] = g;
+            em[2 * (d - 1) * G + 1] = dg;
+            S += q[4] * g;
+            give = mw * g;
+          }
+          const double got = bpermute_f64(from4[d - 1], give);
+          if (!half || m >= d) S += got;
+          __builtin_amdgcn_sched_barrier(0); // (keeps a trip's loads out of the trips before it: 128 VGPRs hold)
+        }
+      }
+  } else
   for (int d = 1; d <= nw / 2; d++) {
     const bool mine = act && (2 * d < n || (2 * d == n && m < d));
     double give = 0.0; // w_m G(m,q): the partner's share
@@ -500,7 +624,7 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
       cs = fmax(cs, -1.0);
       double dg, g;
       // (wave-uniform test: the blend of the two polynomials is skipped when no pair of this trip has cos >= 1/2)
-      if (__any(cs >= 0.5)) g = gspline(cb, cg, cs, dg);
+      if (__any(cs >= 0.5)) g = gspline(cb, cg, cs, dg, lead);
       else g = poly6(cb, cs, dg);
       double *e = mat + 2 * ((d - 1) * G + m);
       e[0] = g;
@@ -527,6 +651,45 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
   // -- phase C: forces on the slots (pair_rebomos.cpp:634-725), again once per unordered pair: the lane of
   //    m adds its own part and ships the partner's part (force on q and C_m G for q's radial term)
   double fx = 0, fy = 0, fz = 0, acc1 = 0;
+  if (full) { // (the full-group path, as in the first pass)
+    if constexpr (kFullPath)
+      if (kAllLanes || lane_again < C::GPW * G) {
+#pragma unroll
+        for (int d = 1; d <= G / 2; d++) {
+          const bool half = 2 * d == G;
+          const double *q = (m >= G - d ? qwrap : qm) + d * kRecF;
+          double sx = unread_f64<0>(), sy = unread_f64<1>(), sz = unread_f64<2>(), sa = unread_f64<3>();
+          if (!half || m < d) {
+            const double qrinv = q[kInvF];
+            const double qx = q[0] * qrinv, qy = q[1] * qrinv, qz = q[2] * qrinv;
+            double cs = ux * qx + uy * qy + uz * qz;
+            cs = fmin(cs, 1.0);
+            cs = fmax(cs, -1.0);
+            const double g = em[2 * (d - 1) * G], dg = em[2 * (d - 1) * G + 1];
+            const double common = (mC * q[4] + q[6] * mw) * dg;
+            const double cm = common * mri, cq = common * qrinv;
+            fx += cm * (qx - cs * ux);
+            fy += cm * (qy - cs * uy);
+            fz += cm * (qz - cs * uz);
+            acc1 += q[6] * g;
+            sx = cq * (ux - cs * qx);
+            sy = cq * (uy - cs * qy);
+            sz = cq * (uz - cs * qz);
+            sa = mC * g;
+          }
+          const int from = from4[d - 1];
+          const double rx = bpermute_f64(from, sx), ry = bpermute_f64(from, sy), rz = bpermute_f64(from, sz);
+          const double ra = bpermute_f64(from, sa);
+          if (!half || m >= d) {
+            fx += rx;
+            fy += ry;
+            fz += rz;
+            acc1 += ra;
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+  } else
   for (int d = 1; d <= nw / 2; d++) {
     const bool mine = act && (2 * d < n || (2 * d == n && m < d));
     double sx = 0, sy = 0, sz = 0, sa = 0;
@@ -567,13 +730,13 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
   }
   double eh = 0.0;
   if (act)
-    finish_slot(P, tc, je[m], off, dp, owned, eflag, mx, my, mz, mr, mw, mdw, mp, mri, mVA, fx, fy, fz, acc1, Csum,
+    finish_slot(P, tc, je[m], off, dp, c_own >= 0, eflag, mx, my, mz, mr, mw, mdw, mp, mri, mVA, fx, fy, fz, acc1, Csum,
                 fnbr, eh, o);
   // the centre's own share: minus the sum of its slot forces, plus the centre halves of the pair energies.
   // Written once here so that the gather only has to follow the reverse slots.
   const double ox = group_sum_any<G>(act ? fx : 0.0, s, lane), oy = group_sum_any<G>(act ? fy : 0.0, s, lane), oz = group_sum_any<G>(act ? fz : 0.0, s, lane);
   const double oe = (eflag & MDP_EFLAG_ATOM) ? group_sum_any<G>(eh, s, lane) : 0.0;
-  if (owned && s == 0 && !outgrown) reinterpret_cast<double4 *>(fown)[c] = make_double4(-ox, -oy, -oz, oe);
+  if (c_own >= 0 && s == 0) reinterpret_cast<double4 *>(fown)[c_own] = make_double4(-ox, -oy, -oz, oe);
   centre_tally(o, acc, eflag, vflag);
 }
 
@@ -3828,6 +3991,26 @@ static int rebomos_lists_stale(mdp_ctx *c, bool &stale)
   return MDP_OK;
 }
 
+// Which pair loops the lane-group kernels of this compute take, and whether their waves are counted (once per compute).
+// MDP_CENTRE_FULL=0 keeps every wave on the general loops (tests, A/B); MDP_CENTRE_COUNT=1 has every wave that holds a
+// centre add one to the context's pair of counts (mdp_rebomos_centre_paths) -- off by default: the kernels then get a null
+// pointer and the step pays one scalar test per wave.  (Read per compute: the tests switch both within one process.)
+static int centre_path_mode(mdp_ctx *c)
+{
+  const char *fe = getenv("MDP_CENTRE_FULL");
+  c->centre_full_now = !(fe && atoi(fe) == 0);
+  const char *ce = getenv("MDP_CENTRE_COUNT");
+  c->centre_cnt_now = nullptr;
+  if (ce && atoi(ce) != 0) {
+    if (!c->centre_paths.p) {
+      MDP_HIP(c, c->centre_paths.reserve(2));
+      MDP_HIP(c, hipMemsetAsync(c->centre_paths.p, 0, sizeof(unsigned long long) * 2, c->stream));
+    }
+    c->centre_cnt_now = c->centre_paths.p;
+  }
+  return MDP_OK;
+}
+
 template <int G>
 static void launch_centre(mdp_ctx *c, int kg, int eflag, int vflag, int part)
 {
@@ -3843,7 +4026,7 @@ static void launch_centre(mdp_ctx *c, int kg, int eflag, int vflag, int part)
     rebo_centre_kernel<G><<<grid, 64 * CentreCfg<G>::WPB, 0, c->stream>>>(c->rebomos, list, n, c->nlocal,
                                                        c->xq.p, c->cand_off.p, c->cand.p, c->pk_cand.p + c->pk_base[k],
                                                        c->amask.p, c->fnbr.p, c->fown.p, c->acc.p, c->ovf.p, eflag, vflag,
-                                                       elem);
+                                                       elem, c->centre_full_now ? 1 : 0, c->centre_cnt_now);
   }
 }
 
@@ -3884,7 +4067,7 @@ static void launch_centre3(mdp_ctx *c, int eflag, int vflag, int part)
     const int grid = (int) ((est + per_block - 1) / per_block);
     rebo_centre_kernel<8, true><<<grid, 64 * CentreCfg<8>::WPB, 0, c->stream>>>(
         c->rebomos, list, 0, c->nlocal, c->xq.p, c->cand_off.p, c->cand.p, h_cnt, c->amask.p, c->fnbr.p, c->fown.p,
-        c->acc.p, c->ovf.p, eflag, vflag, elem);
+        c->acc.p, c->ovf.p, eflag, vflag, elem, c->centre_full_now ? 1 : 0, c->centre_cnt_now);
   }
 }
 
@@ -4150,6 +4333,7 @@ static int launch_lj_cubic(mdp_ctx *c, int eflag, int vflag)
 // first centre launch of the compute
 static int launch_centres(mdp_ctx *c, int eflag, int vflag, int parts, int which = 3, bool first = true)
 {
+  if ((parts & 1) && first) MDP_TRY(centre_path_mode(c)); // (once per compute, as the line below)
   if ((parts & 1) && first) c->ovf_par ^= 1; // (a new compute: the set of pinned overflow counts it reads first and writes last)
   hipStream_t st = c->stream; // (the overflow counter ovf[0] was zeroed by mdp_acc_begin of this compute)
   if (c->centre_split && parts == 3 && which == 3) {

@@ -100,6 +100,7 @@ EXPORTS = [
     "mdp_md_set_mask", "mdp_hnve_set_mask", "mdp_integrate_group", "mdp_langevin_group",
     "mdp_md_set_image", "mdp_md_download_unwrapped", "mdp_msd_setup", "mdp_msd_sums", "mdp_msd_info", "mdp_msd_off",
     "mdp_rdf_setup", "mdp_rdf_counts", "mdp_rdf_info", "mdp_rdf_off",
+    "mdp_rebomos_centre_paths",
 ]
 
 
@@ -468,6 +469,13 @@ class Context:
         self._ck(self.L.mdp_rebomos_list_info(self.h, out))
         keys = ("tiled", "tiles", "union_stride", "union_max", "row_entries", "clusters", "large_tiles", "builds")
         return dict(zip(keys, (int(v) for v in out)))
+
+    def rebomos_centre_paths(self, reset=True):
+        """(waves of the lane-group centre kernels on the full-group path, waves on the general loops) over the computes
+        run with MDP_CENTRE_COUNT=1 since the last reset (see mdpair_hip.h)"""
+        out = (C.c_longlong * 2)()
+        self._ck(self.L.mdp_rebomos_centre_paths(self.h, out, C.c_int(1 if reset else 0)))
+        return int(out[0]), int(out[1])
 
     def md_neighbor_stats(self):
         out = (C.c_longlong * 8)()
