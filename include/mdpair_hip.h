@@ -658,6 +658,38 @@ int mdp_rdf_counts(mdp_ctx *ctx, long long *hist, long long *icount, long long *
 int mdp_rdf_info(mdp_ctx *ctx, long long out[4]);
 int mdp_rdf_off(mdp_ctx *ctx);
 
+/* ---- binned mass, momentum and kinetic energy: temperature, density and flow profiles (LAMMPS compute chunk/atom bin/1d|2d|3d
+ * with compute temp/chunk, vcm/chunk, fix ave/chunk), in integers ----------------------------------------------------------
+ * For a resident context with mdp_dd_setup (MDP_ESTATE otherwise).  Nothing a step, a list build, msd or rdf reads is touched.
+ *   mdp_profile_setup:    bins over the box of mdp_dd_setup in ndim = 1 .. 3 distinct dimensions dim[k] in {0, 1, 2} with
+ *                         nbin[k] >= 1 bins each, nbin[0] * .. <= MDP_PROFILE_MAXBINS rows (MDP_EINVAL otherwise).  An owned
+ *                         atom with fractional coordinate s_d (Domain::x2lamda, triclinic included) has b_d = (int)
+ *                         floor(s_d nbin_d), wrapped ((b % n) + n) % n in a periodic dimension (an atom that drifted out of
+ *                         the box since the last remap lands where its image would) and clamped to 0 .. n - 1 in a
+ *                         non-periodic one; row = the first named dimension slowest.  groupbit: 0 every owned atom, else the
+ *                         atoms whose mask (mdp_md_set_mask) has the bit.  A second call replaces the first.
+ *   The terms of an atom with mass m and full-step velocity v: t = (m, m vx, m vy, m vz, m (v . v)); both reads first
+ *   complete a final half-kick the host deferred.
+ *   mdp_profile_range:    blocking.  out[k] = this rank's max |t_k| over the group's owned atoms (0 without one).
+ *   mdp_profile_exponent: pure host function.  0 for range == 0, else 61 - ceil(log2(max(natoms_total, 2))) - E with range < 2^E
+ *                         (E the frexp exponent): natoms_total * (range * 2^e + 1/2) < 2^62, so no sum of natoms_total
+ *                         quantised terms overflows.  Every rank must use the exponents of the GLOBAL range maximum.
+ *   mdp_profile_sums:     blocking.  count[b] = the group's owned atoms of this rank in row b; sums[b][k] = the sum of
+ *                         llrint(ldexp(t_k, exponent[k])) over them as 64-bit integers.  All integers, no float atomics:
+ *                         two reads of one state agree exactly, and the sum over the bricks equals the one-brick table bit
+ *                         for bit.  MDP_EINVAL when an |ldexp(t_k, exponent[k])| >= 2^62 / max(nlocal, 1) (the message names the
+ *                         column); MDP_ESTATE without a setup, or with a group and no mask that covers the current atoms.
+ *   mdp_profile_info:     out = {a measurement is on, its rows, its ndim, its serial}; the serial as that of mdp_rdf_info.
+ *   mdp_profile_off:      releases the buffers. */
+#define MDP_PROFILE_W 5
+#define MDP_PROFILE_MAXBINS (1 << 20)
+int mdp_profile_setup(mdp_ctx *ctx, int ndim, const int *dim, const int *nbin, int groupbit);
+int mdp_profile_range(mdp_ctx *ctx, double out[MDP_PROFILE_W]);
+int mdp_profile_exponent(double range, long long natoms_total);
+int mdp_profile_sums(mdp_ctx *ctx, const int exponent[MDP_PROFILE_W], long long *count, long long *sums);
+int mdp_profile_info(mdp_ctx *ctx, long long out[4]);
+int mdp_profile_off(mdp_ctx *ctx);
+
 /* per-phase device time of the last compute in ms (HIP events on the compute stream):
  * rebomos: [0]=REBO centre kernels of the lane-group classes, [1]=the general kernel (centres that outgrew their lane
  * group since the list build), [2]=row pruning (0 unless one was due), [3]=LJ+gather kernel;

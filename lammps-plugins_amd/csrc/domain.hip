@@ -22,14 +22,6 @@
 
 namespace {
 
-__device__ __forceinline__ void dd_x2lamda(const DdGeom &G, const double x, const double y, const double z, double lam[3])
-{
-  const double d0 = x - G.lo[0], d1 = y - G.lo[1], d2 = z - G.lo[2];
-  lam[0] = G.hinv[0] * d0 + G.hinv[5] * d1 + G.hinv[4] * d2;
-  lam[1] = G.hinv[1] * d1 + G.hinv[3] * d2;
-  lam[2] = G.hinv[2] * d2;
-}
-
 // Cartesian displacement of s box vectors
 __device__ __forceinline__ void dd_shift_cart(const DdGeom &G, const double s0, const double s1, const double s2,
                                               double out[3])

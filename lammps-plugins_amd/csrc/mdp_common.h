@@ -204,7 +204,16 @@ struct DdGeom {
   int nonper[3];        // 1: no periodic images / no wrap in this dimension (slab, free surface)
 };
 
-// LAMMPS' 32-bit imageint: (ix + 512) | (iy + 512) << 10 | (iz + 512) << 20; a field wraps modulo 1024
+// fractional (lamda) coordinates of a position in the box of mdp_dd_setup (Domain::x2lamda), triclinic included
+__device__ __forceinline__ void dd_x2lamda(const DdGeom &G, const double x, const double y, const double z, double lam[3])
+{
+  const double d0 = x - G.lo[0], d1 = y - G.lo[1], d2 = z - G.lo[2];
+  lam[0] = G.hinv[0] * d0 + G.hinv[5] * d1 + G.hinv[4] * d2;
+  lam[1] = G.hinv[1] * d1 + G.hinv[3] * d2;
+  lam[2] = G.hinv[2] * d2;
+}
+
+// LAMMPS' 32-bit imageint:(ix + 512) | (iy + 512) << 10 | (iz + 512) << 20; a field wraps modulo 1024
 constexpr int kImgBits = 10, kImgMask = 1023, kImgBias = 512;
 // unwrapped position x + h . image of an atom, the roundings written out (both kernels that form it give the same bits)
 __device__ __forceinline__ void mdp_unwrap(const DdGeom &G, const double4 &x, const int image, double xu[3])
@@ -363,7 +372,17 @@ struct MdpRdf {
   DevBuf<char> sort_tmp;
   DevBuf<unsigned long long> out;  // [npair][nbin] histogram, then icount / jcount / dup [MDP_RDF_MAXPAIR] each, then the bad tags
 };
-static constexpr int kMsdW = 9; // sum dx^2, dy^2, dz^2, count, sum m xu (3), sum m, atoms whose tag has no origin
+// binned sums of m, m v and m v^2 (profile.hip): the bins and the table of a read; nothing here is read by a step, a list build,
+// msd or rdf
+struct MdpProfile {
+  bool on = false;
+  int ndim = 0, dim[3] = {0, 0, 0}, nbin[3] = {1, 1, 1}, gbit = 0;
+  long long rows = 0;
+  long long serial = 0;            // which mdp_profile_setup of this process the bins belong to (mdp_profile_info)
+  DevBuf<double> part;             // per-block maxima of |t_k|, MDP_PROFILE_W per block, then the MDP_PROFILE_W maxima
+  DevBuf<unsigned long long> out;  // [rows][MDP_PROFILE_W] sums (two's complement), [rows] counts, then the column flags
+};
+static constexpr int kMsdW = 9;// sum dx^2, dy^2, dz^2, count, sum m xu (3), sum m, atoms whose tag has no origin
 
 // what the integrate kernels need to add the Langevin force of one step (md.hip nve_advance_kernel / nve_final_kernel)
 struct MdpLgvArgs {
@@ -697,6 +716,7 @@ struct mdp_ctx {
   bool image_set = false;
   MdpMsd msd;
   MdpRdf rdf;                      // pair-distance histograms of the current positions (mdp_rdf_setup)
+  MdpProfile profile;              // binned mass, momentum and kinetic energy of the current atoms (mdp_profile_setup)
   bool final_pending = false;      // the host deferred the final half-kick of the finished step (mdp_md_defer_final)
   bool final_deferred_seen = false; // the host uses mdp_md_defer_final at all (older hosts: with_final is authoritative)
   bool acc_prezeroed = false; // the integrate kernel reset the accumulators: the next mdp_acc_begin launches nothing
@@ -882,6 +902,7 @@ int mdp_group_args(mdp_ctx *c, bool *masked, MdpGroupArgs *M);
 int mdp_lgv_close(mdp_ctx *c, const MdpLgvArgs &L);
 void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
 void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds
+void mdp_profile_release(mdp_ctx *c); // frees what profile.hip holds
 // FIRE minimiser (fire.hip), in place of the integrate kernel when c->fire.on: the half step back / zeroing and the Euler
 // step of the iteration whose control kernel was queued last, with the same votes, accumulator reset and force clear
 int mdp_fire_launch_advance(mdp_ctx *c, int *flag, double trigsq, double hardsq, const MdpStyleCheck &sc, bool zero_f);

@@ -73,6 +73,9 @@ BOLTZ_METAL = 8.617343e-5    # force->boltz, metal units
 
 
 STYLE_REBOMOS, STYLE_AEAM = 1, 2
+PROFILE_W = 5                # MDP_PROFILE_W of include/mdpair_hip.h
+PROFILE_MAXBINS = 1 << 20
+
 EXPORTS = [
     "mdp_abi_version", "mdp_device_count", "mdp_create", "mdp_destroy", "mdp_last_error", "mdp_set_stream",
     "mdp_sync", "mdp_rebomos_set_params", "mdp_rebomos_read_file", "mdp_rebomos_params_from_scalars",
@@ -100,6 +103,7 @@ EXPORTS = [
     "mdp_md_set_mask", "mdp_hnve_set_mask", "mdp_integrate_group", "mdp_langevin_group",
     "mdp_md_set_image", "mdp_md_download_unwrapped", "mdp_msd_setup", "mdp_msd_sums", "mdp_msd_info", "mdp_msd_off",
     "mdp_rdf_setup", "mdp_rdf_counts", "mdp_rdf_info", "mdp_rdf_off",
+    "mdp_profile_setup", "mdp_profile_range", "mdp_profile_exponent", "mdp_profile_sums", "mdp_profile_info", "mdp_profile_off",
     "mdp_rebomos_centre_paths",
 ]
 
@@ -131,6 +135,12 @@ def lib():
         _lib.mdp_md_ptr.restype = C.c_void_p
         _lib.mdp_device_bytes.restype = C.c_double
     return _lib
+
+
+def profile_exponent(rng, natoms_total):
+    """mdp_profile_exponent: the power of two a profile column with global range rng is scaled by -- the library's one copy of
+    the rule (a pure host function: no context, no device)"""
+    return int(lib().mdp_profile_exponent(C.c_double(float(rng)), C.c_longlong(int(natoms_total))))
 
 
 def _dp(a):
@@ -835,6 +845,45 @@ class Context:
 
     def rdf_off(self):
         self._ck(self.L.mdp_rdf_off(self.h))
+
+    # ---------------- binned mass, momentum and kinetic energy (csrc/profile.hip)
+    def profile_setup(self, dims, nbins, group_bit=0):
+        """starts a measurement: bins over the box in the distinct dimensions dims (0, 1, 2; the first slowest) with nbins[k]
+        bins each; group_bit 0: every owned atom, else the atoms whose mask has the bit"""
+        dm = np.ascontiguousarray(dims, dtype=np.int32).reshape(-1)
+        nb = np.ascontiguousarray(nbins, dtype=np.int32).reshape(-1)
+        if len(dm) != len(nb):
+            raise ValueError("profile_setup: one number of bins per dimension")
+        self._ck(self.L.mdp_profile_setup(self.h, C.c_int(len(dm)), _ip(dm), _ip(nb), C.c_int(int(group_bit))))
+
+    def profile_range(self):
+        """this rank's max |t_k| of the terms (m, m vx, m vy, m vz, m v.v) over the group's owned atoms"""
+        out = (C.c_double * PROFILE_W)()
+        self._ck(self.L.mdp_profile_range(self.h, out))
+        return np.array(out[:], dtype=np.float64)
+
+    def profile_exponent(self, rng, natoms_total):
+        """the power of two a column with global range rng is scaled by (the library's one copy of the rule)"""
+        return profile_exponent(rng, natoms_total)
+
+    def profile_sums(self, exponents):
+        """this rank's (count[rows], sums[rows][5]) as int64, the terms scaled by 2^exponents[k] and rounded"""
+        rows = max(self.profile_info()["rows"], 1)
+        ex = (C.c_int * PROFILE_W)(*[int(e) for e in exponents])
+        count = np.zeros(rows, dtype=np.int64)
+        sums = np.zeros((rows, PROFILE_W), dtype=np.int64)
+        lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_longlong))
+        self._ck(self.L.mdp_profile_sums(self.h, ex, lp(count), lp(sums)))
+        return count, sums
+
+    def profile_info(self):
+        """whether a measurement is on, its rows and dimensions, and its serial (unique in the process per profile_setup)"""
+        out = (C.c_longlong * 4)()
+        self._ck(self.L.mdp_profile_info(self.h, out))
+        return dict(on=bool(out[0]), rows=int(out[1]), ndim=int(out[2]), serial=int(out[3]))
+
+    def profile_off(self):
+        self._ck(self.L.mdp_profile_off(self.h))
 
     # halo plumbing (device pointers as ints)
     def md_pack_x(self, n, d_sendlist, d_shift, d_buf):

@@ -141,6 +141,45 @@ def rdf_normalise(hist, icount, jcount, dup, cutoff, volume):
     return out
 
 
+def profile_split(q):
+    """an int64 array as two float64 arrays (q >> 31, q & (2^31 - 1)): both halves, and their sums over up to 2^22 ranks, are
+    whole numbers below 2^53, so a transport that adds doubles adds them exactly"""
+    q = np.asarray(q, dtype=np.int64)
+    return (q >> 31).astype(np.float64), (q & (2 ** 31 - 1)).astype(np.float64)
+
+
+def profile_join(hi, lo):
+    """the int64 sum from the summed halves of profile_split"""
+    return (np.asarray(hi, dtype=np.int64) << 31) + np.asarray(lo, dtype=np.int64)
+
+
+def profile_normalise(count, sums, exponents, nbins, volume, boltz, mvv2e, mv2d, com):
+    """compute profile/mdp's array [rows][ndim + 7] from rank-summed integer tables (DeviceDomain.profile_read): the bin centre
+    in each named dimension in reduced units (the first slowest), count, density/number, density/mass, temp and the three
+    components of the bin's centre-of-mass velocity.  volume: of the whole box; com: temp from the kinetic energy about the
+    bin's centre-of-mass velocity.  An empty bin reads 0 in every value column."""
+    nbins = [int(n) for n in np.atleast_1d(nbins)]
+    rows, ndim = int(np.prod(nbins)), len(nbins)
+    count = np.asarray(count, dtype=np.float64).reshape(rows)
+    t = np.ldexp(np.asarray(sums, dtype=np.int64).reshape(rows, capi.PROFILE_W).astype(np.float64), -np.asarray(exponents, dtype=np.int32))
+    out = np.zeros((rows, ndim + 7))
+    idx = np.unravel_index(np.arange(rows), nbins)
+    for k in range(ndim):
+        out[:, k] = (idx[k] + 0.5) / nbins[k]
+    vbin = volume / rows
+    full = count > 0
+    msum, p, kin = t[:, 0], t[:, 1:4], t[:, 4]
+    safe_m = np.where(msum > 0.0, msum, 1.0)
+    if com:
+        kin = kin - (p ** 2).sum(axis=1) / safe_m
+    out[:, ndim] = count
+    out[:, ndim + 1] = count / vbin
+    out[:, ndim + 2] = np.where(full, mv2d * msum / vbin, 0.0)
+    out[:, ndim + 3] = np.where(full, mvv2e * kin / (3.0 * np.where(full, count, 1.0) * boltz), 0.0)
+    out[:, ndim + 4:] = np.where(full[:, None], p / safe_m[:, None], 0.0)
+    return out
+
+
 class DeviceDomain:
     """One brick of the periodic box per GPU, all bookkeeping on the device.
 
@@ -533,6 +572,40 @@ class DeviceDomain:
 
     def rdf_off(self):
         self.ctx.rdf_off()
+
+    # ------------------------------------------------------------------ temperature, density and flow profiles
+    def profile(self, dims, nbins, group_bit=0):
+        """starts a binned measurement of mass, momentum and kinetic energy (LAMMPS compute chunk/atom bin/1d|2d|3d with
+        temp/chunk and vcm/chunk): bins over the box in the distinct dimensions dims (0, 1, 2; the first slowest) with
+        nbins[k] bins each, over the atoms with mask & group_bit (0: every atom; otherwise set_group must have given a
+        mask).  With several ranks every rank makes the same call."""
+        self._profile = dict(dims=[int(d) for d in np.atleast_1d(dims)], nbins=[int(n) for n in np.atleast_1d(nbins)])
+        self.ctx.profile_setup(self._profile["dims"], self._profile["nbins"], group_bit)
+
+    def profile_read(self):
+        """(count[rows], sums[rows][5], exponents[5]): the atoms per bin and the sums of llrint(t_k 2^exponents[k]) over them,
+        t = (m, m vx, m vy, m vz, m v.v), as int64 summed over the ranks; profile_normalise makes the compute's array of
+        them.  Exact: the exponents come from the global maximum of |t_k|, so every rank rounds alike and the integer sums
+        do not depend on the decomposition."""
+        self.flush()
+        w = capi.PROFILE_W
+        slots = np.zeros((self.world, w))            # a maximum through the transports' sum: every rank fills its own slot
+        slots[self.rank] = self.ctx.profile_range()
+        gmax = self._group_sum(slots.ravel()).reshape(self.world, w).max(axis=0)
+        ex = [self.ctx.profile_exponent(r, self.natoms_total) for r in gmax]
+        count, sums = self.ctx.profile_sums(ex)
+        if self.tr is not None:
+            # the transports add doubles: an int64 travels as q >> 31 and q & (2^31 - 1), each sum exact below 2^53
+            hi, lo = profile_split(sums)
+            flat = np.concatenate([count.astype(np.float64), hi.ravel(), lo.ravel()])
+            tot = np.rint(self._group_sum(flat)).astype(np.int64)
+            n = count.size
+            count = tot[:n]
+            sums = profile_join(tot[n:n + sums.size], tot[n + sums.size:]).reshape(sums.shape)
+        return count, sums, np.array(ex, dtype=np.int32)
+
+    def profile_off(self):
+        self.ctx.profile_off()
 
     def thermostat(self, t_start, t_stop, t_period, tchain=3, tloop=1, drag=0.0, first=0, last=0, nf=None):
         """Nose-Hoover chain thermostat (LAMMPS fix nvt) in the integrate calls of this domain, from the chain at rest; one

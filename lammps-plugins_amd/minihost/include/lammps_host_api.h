@@ -174,6 +174,7 @@ class Force {
   double mvv2e = 1.0364269e-4;
   double boltz = 8.617343e-5;
   Pair *pair = nullptr;
+  double mv2d = 1.0 / 0.602214129; // mass / volume -> g/cm^3 (metal units)
 };
 
 class Update { // the members of LAMMPS' Update a fix style reads
