@@ -526,6 +526,26 @@ int mdp_langevin_setup(mdp_ctx *ctx, const mdp_langevin_config *cfg);
 int mdp_langevin_run(mdp_ctx *ctx, long long first, long long last);
 int mdp_langevin_tally(mdp_ctx *ctx, double *out);
 int mdp_langevin_off(mdp_ctx *ctx);
+/* Several baths on disjoint groups in one run (several `fix langevin/mdp` next to one `fix nve/mdp`): up to
+ * MDP_LANGEVIN_MAXBATH thermostats, bath k on the atoms whose mask (mdp_md_set_mask / mdp_hnve_set_mask) has groupbit[k]
+ * and that are inside the integrate group, each with its own configuration (natoms: the atoms of ITS group) and its own
+ * tally.  All are applied in the one pass of the integrate kernels; lanes of different baths differ in the indices they
+ * read, not in the code they run.
+ *   baths:      replaces whatever thermostat set-up is on.  nbath == 1 is mdp_langevin_setup(cfg) followed by
+ *               mdp_langevin_group(groupbit[0]): the kernels of one thermostat.  Refused (MDP_EINVAL / MDP_ESTATE, each
+ *               with its cause): nbath outside 1 .. MDP_LANGEVIN_MAXBATH, a zero bit or a bit two baths share, a bath's
+ *               argument errors as in mdp_langevin_setup, the Nose-Hoover chain or the minimiser on the context (in
+ *               either order), zero or tally in any bath on a brick of several ranks (in either call order), and atoms
+ *               of the current mask that are in more than one bath -- LAMMPS would add both forces on such an atom, the
+ *               device refuses it and says how many there are.  That count is taken once per mdp_langevin_baths and per
+ *               mask upload, never in a step.  An integrate call with several baths and no mask fails with MDP_ESTATE,
+ *               and so does mdp_langevin_group while several baths are on.
+ *   run / off:  apply to all baths: one first / last, one step counter, one setup force.
+ *   tally:      the sum over the baths, in bath order (what `ecouple` adds up).
+ *   tally_bath: *out = the energy bath k has taken out (0 without tally yes); with one thermostat on, k = 0. */
+#define MDP_LANGEVIN_MAXBATH 4
+int mdp_langevin_baths(mdp_ctx *ctx, int nbath, const mdp_langevin_config *cfg, const int *groupbit);
+int mdp_langevin_tally_bath(mdp_ctx *ctx, int bath, double *out);
 
 /* ---- FIRE minimiser on the device (LAMMPS min_style fire, FIRE 2.0 with the eulerimplicit integrator and LAMMPS' defaults)
  * For a resident context on one rank, after mdp_md_setup + mdp_dd_setup (one brick) + mdp_dd_reneighbor.  An iteration

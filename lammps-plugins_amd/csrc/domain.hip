@@ -469,7 +469,7 @@ int mdp_dd_setup(mdp_ctx *c, const mdp_dd_config *cfg)
   if (!c->md) return mdp_fail(c, MDP_ESTATE, "mdp_md_setup not called");
   if (c->nhc.on && (long long) cfg->procgrid[0] * cfg->procgrid[1] * cfg->procgrid[2] > 1)
     return mdp_fail(c, MDP_ESTATE, "mdp_dd_setup: the thermostat (mdp_nhc_setup) runs on one rank only, not on a brick of several ranks");
-  if (c->lgv.on && (c->lgv.cfg.zero || c->lgv.cfg.tally) &&
+  if (c->lgv.sums() &&
       (long long) cfg->procgrid[0] * cfg->procgrid[1] * cfg->procgrid[2] > 1)
     return mdp_fail(c, MDP_ESTATE, "mdp_dd_setup: Langevin zero and tally (mdp_langevin_setup) run on one rank only, not on a brick of several ranks");
   if (c->fire.on && (long long) cfg->procgrid[0] * cfg->procgrid[1] * cfg->procgrid[2] > 1)

@@ -228,16 +228,21 @@ __global__ __launch_bounds__(256) void ang_select_kernel(const int nlocal, const
 // (SCALE = false) never read it, so their code is what it was without a thermostat.
 // LANGEVIN: this kernel is the first reader of the compute's forces and adds the Langevin force of the step (L,
 // langevin.hip) to them in registers, from the velocities it reads; L.part: the per-block sums of f_L . v for the tally
-// (v after the final half; with FINAL = false the setup force, and v as read).  LANGEVIN = false never reads L.
-template <bool FINAL, bool CHECK, bool SCALE, bool LANGEVIN, bool MASK>
+// (v after the final half; with FINAL = false the setup force, and v as read).  LANGEVIN = 0 never reads L.
+// LANGEVIN = 2 (with MASK): several baths on disjoint groups (mdp_langevin_baths); L is then MdpLgvBathArgs, the bath of an
+// atom is picked from the mask word the kernel reads anyway, and the block sum carries one slot per bath.  The
+// instantiations with LANGEVIN 0 and 1 compile the code they had before there was a 2.
+template <bool FINAL, bool CHECK, bool SCALE, int LANGEVIN, bool MASK>
 __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const double *__restrict__ rmass,
                                    double *__restrict__ f, double *__restrict__ v, double4 *__restrict__ xq,
                                    const mdp_hold_t *__restrict__ xhold, const double trigsq, const double hardsq,
                                    int *__restrict__ flag, const MdpStyleCheck SC, const int zero_f,
                                    double *__restrict__ dflag_set, double *__restrict__ dflag_clear,
-                                   const double *__restrict__ vscale, const MdpLgvArgs L, const MdpGroupArgs M)
+                                   const double *__restrict__ vscale,
+                                   const std::conditional_t<LANGEVIN == 2, MdpLgvBathArgs, MdpLgvArgs> L, const MdpGroupArgs M)
 {
   double lgv_e = 0.0; // (LANGEVIN, tally: f_L . v of this atom)
+  [[maybe_unused]] int bath = 0; // (LANGEVIN == 2: the bath of this atom)
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (CHECK && dflag_clear && i == 0) *dflag_clear = 0.0; // (the word of the next step; this step's was cleared a step ago)
   bool t = false, h = false;
@@ -262,6 +267,7 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
       const int m = mdp_group_mask(M, i);
       move = mdp_group_moves(M, m);
       lgv = LANGEVIN && mdp_group_lgv(M, m);
+      if constexpr (LANGEVIN == 2) bath = mdp_lgv_bath(L, m);
     }
     double4 x;
     double two_steps = 0.0;
@@ -276,7 +282,8 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
       double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
       double lx = 0.0, ly = 0.0, lz = 0.0;
       if (lgv) { // post_force of step n (or the setup force): f += f_L, kept for both half-kicks
-        mdp_lgv_force(L, i, vx, vy, vz, lx, ly, lz);
+        if constexpr (LANGEVIN == 2) mdp_lgv_force(L, i, bath, vx, vy, vz, lx, ly, lz);
+        else mdp_lgv_force(L, i, vx, vy, vz, lx, ly, lz);
         fx = fx + lx;
         fy = fy + ly;
         fz = fz + lz;
@@ -322,7 +329,14 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
     }
     mdp_style_test(SC, (size_t) i, x, two_steps, w);
   }
-  if constexpr (LANGEVIN)
+  if constexpr (LANGEVIN == 2) {
+    if (L.part) { // one slot per bath; an atom adds to its own
+      double e[MDP_LANGEVIN_MAXBATH];
+#pragma unroll
+      for (int k = 0; k < MDP_LANGEVIN_MAXBATH; k++) e[k] = bath == k ? lgv_e : 0.0;
+      mdp_block_sum_256<MDP_LANGEVIN_MAXBATH>(e, L.part);
+    }
+  } else if constexpr (LANGEVIN == 1)
     if (L.part) mdp_block_sum_256(lgv_e, L.part);
   if (CHECK) { // (pinned host words zeroed by the host before the launch: plain idempotent stores)
     if (__ballot(t) && (threadIdx.x & 63) == 0) {
@@ -401,6 +415,51 @@ __global__ __launch_bounds__(256) void lgv_final_kernel(int nlocal, double dtf, 
     }
   }
   if (L.part) mdp_block_sum_256(e, L.part);
+}
+
+// ... with several baths (always with a mask): the same half, the bath's force, one slot of the block sum per bath
+__global__ __launch_bounds__(256) void lgv_final_baths_kernel(int nlocal, double dtf, const double *__restrict__ rmass,
+                                                              double *__restrict__ f, double *__restrict__ v,
+                                                              const MdpLgvBathArgs L, const int writeback, const MdpGroupArgs M)
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double e = 0.0;
+  int bath = 0;
+  if (i < nlocal) {
+    const int m = mdp_group_mask(M, i);
+    const bool move = mdp_group_moves(M, m), lgv = mdp_group_lgv(M, m);
+    bath = mdp_lgv_bath(L, m);
+    if (lgv) {
+      const double s = dtf / rmass[i];
+      double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
+      double lx, ly, lz;
+      mdp_lgv_force(L, i, bath, vx, vy, vz, lx, ly, lz);
+      const double fx = f[3 * (size_t) i] + lx, fy = f[3 * (size_t) i + 1] + ly, fz = f[3 * (size_t) i + 2] + lz;
+      if (writeback) {
+        f[3 * (size_t) i] = fx;
+        f[3 * (size_t) i + 1] = fy;
+        f[3 * (size_t) i + 2] = fz;
+      }
+      vx += s * fx;
+      vy += s * fy;
+      vz += s * fz;
+      v[3 * (size_t) i] = vx;
+      v[3 * (size_t) i + 1] = vy;
+      v[3 * (size_t) i + 2] = vz;
+      e = mdp_dot3(ly, vy, lx, vx, lz, vz); // (y first, as lgv_final_kernel)
+    } else if (move) {
+      const double s = dtf / rmass[i];
+      v[3 * (size_t) i] += s * f[3 * (size_t) i];
+      v[3 * (size_t) i + 1] += s * f[3 * (size_t) i + 1];
+      v[3 * (size_t) i + 2] += s * f[3 * (size_t) i + 2];
+    }
+  }
+  if (L.part) {
+    double eb[MDP_LANGEVIN_MAXBATH];
+#pragma unroll
+    for (int k = 0; k < MDP_LANGEVIN_MAXBATH; k++) eb[k] = bath == k ? e : 0.0;
+    mdp_block_sum_256<MDP_LANGEVIN_MAXBATH>(eb, L.part);
+  }
 }
 
 __global__ void ghost_refresh_kernel(int nlocal, int nghost, const int *__restrict__ owner,
@@ -619,6 +678,15 @@ int lgv_final(mdp_ctx *c, bool writeback)
   MdpLgvArgs L;
   MdpGroupArgs M;
   MDP_TRY(mdp_group_args(c, &masked, &M));
+  if (c->lgv.many()) {
+    MdpLgvBathArgs B;
+    MDP_TRY(mdp_lgv_open_baths(c, false, false, &apply, &B));
+    if (c->nlocal)
+      lgv_final_baths_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, B,
+                                                                     writeback ? 1 : 0, M);
+    MDP_HIP(c, hipGetLastError());
+    return mdp_lgv_close_baths(c, B);
+  }
   MDP_TRY(mdp_lgv_open(c, false, false, &apply, &L));
   if (c->nlocal && masked)
     lgv_final_kernel<true><<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, L,
@@ -662,31 +730,45 @@ int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, dou
   }
   const double *vscale = nullptr;
   bool lgv = false, masked = false;
+  const bool baths = c->lgv.many();
   MdpLgvArgs L;
+  MdpLgvBathArgs B;
   MdpGroupArgs M;
   MDP_TRY(mdp_group_args(c, &masked, &M)); // (before a thermostat counts the step)
   if (c->nhc.on) MDP_TRY(mdp_nhc_open(c, with_final, &vscale));
-  if (c->lgv.on) MDP_TRY(mdp_lgv_open(c, with_final, true, &lgv, &L));
+  if (baths) MDP_TRY(mdp_lgv_open_baths(c, with_final, true, &lgv, &B));
+  else if (c->lgv.on) MDP_TRY(mdp_lgv_open(c, with_final, true, &lgv, &L));
   const int n = c->nlocal;
   if (!n) return MDP_OK;
   const MdpStep s = mdp_step(c);
   // FINAL x CHECK x {plain, SCALE, LANGEVIN}: the twelve instantiations (one thermostat per context: never both), and
-  // their twelve MASK twins, which only a context with a group set ever launches
+  // their twelve MASK twins, which only a context with a group set ever launches; several baths: FINAL x CHECK more,
+  // LANGEVIN = 2 with MASK
   auto launch = [&](auto fv, auto cv, auto sv, auto lv, auto mv) {
-    nve_advance_kernel<decltype(fv)::value, decltype(cv)::value, decltype(sv)::value, decltype(lv)::value, decltype(mv)::value>
-        <<<nblk(n), 256, 0, c->stream>>>(n, s.dtf, s.dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p, trigsq, hardsq, flag, sc,
-                                         zero_f ? 1 : 0, dset, dclr, vscale, L, M);
+    constexpr int LV = decltype(lv)::value;
+    if constexpr (LV == 2)
+      nve_advance_kernel<decltype(fv)::value, decltype(cv)::value, false, 2, true>
+          <<<nblk(n), 256, 0, c->stream>>>(n, s.dtf, s.dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p, trigsq, hardsq, flag, sc,
+                                           zero_f ? 1 : 0, dset, dclr, vscale, B, M);
+    else
+      nve_advance_kernel<decltype(fv)::value, decltype(cv)::value, decltype(sv)::value, LV, decltype(mv)::value>
+          <<<nblk(n), 256, 0, c->stream>>>(n, s.dtf, s.dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p, trigsq, hardsq, flag, sc,
+                                           zero_f ? 1 : 0, dset, dclr, vscale, L, M);
   };
   constexpr std::true_type T;
   constexpr std::false_type F;
+  constexpr std::integral_constant<int, 0> L0;
+  constexpr std::integral_constant<int, 1> L1;
+  constexpr std::integral_constant<int, 2> L2;
   auto group = [&](auto fv, auto cv, auto sv, auto lv) {
     if (masked) launch(fv, cv, sv, lv, T);
     else launch(fv, cv, sv, lv, F);
   };
   auto thermostat = [&](auto fv, auto cv) {
-    if (vscale) group(fv, cv, T, F);
-    else if (lgv) group(fv, cv, F, T);
-    else group(fv, cv, F, F);
+    if (vscale) group(fv, cv, T, L0);
+    else if (lgv && baths) launch(fv, cv, F, L2, T);
+    else if (lgv) group(fv, cv, F, L1);
+    else group(fv, cv, F, L0);
   };
   auto check = [&](auto fv) {
     if (flag) thermostat(fv, T);
@@ -695,7 +777,8 @@ int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, dou
   if (with_final) check(T);
   else check(F);
   MDP_HIP(c, hipGetLastError());
-  if (lgv) MDP_TRY(mdp_lgv_close(c, L));
+  if (lgv && baths) MDP_TRY(mdp_lgv_close_baths(c, B));
+  else if (lgv) MDP_TRY(mdp_lgv_close(c, L));
   return MDP_OK;
 }
 
@@ -704,9 +787,18 @@ int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, dou
 // ---- groups (mdp_integrate_group, mdp_langevin_group) ---------------------------------------------
 int mdp_group_args(mdp_ctx *c, bool *masked, MdpGroupArgs *M)
 {
-  const int lbit = c->lgv.on ? c->lgv_bit : 0;
+  const bool baths = c->lgv.many();
+  int lbit = c->lgv.on ? c->lgv_bit : 0;
+  if (baths) { // the baths' atoms: the OR of their bits
+    lbit = 0;
+    for (int k = 0; k < c->lgv.nbath; k++) lbit |= c->lgv.bbit[k];
+  }
   *masked = c->group_bit != 0 || lbit != 0;
   if (!*masked) return MDP_OK;
+  if (baths && (!c->mask_set || c->mask_n != c->nlocal))
+    return mdp_fail(c, MDP_ESTATE, "%d Langevin baths are on (mdp_langevin_baths) but no mask covers the current atoms (%s)", c->lgv.nbath,
+                    c->md ? "mdp_md_set_mask" : "mdp_hnve_set_mask after mdp_set_atoms_host");
+  if (baths) MDP_TRY(mdp_lgv_check_disjoint(c, "integrate")); // (a no-op once the mask has been counted)
   if (!c->mask_set || c->mask_n != c->nlocal)
     return mdp_fail(c, MDP_ESTATE, "a group is set (mdp_integrate_group / mdp_langevin_group) but no mask covers the current atoms (%s)",
                     c->md ? "mdp_md_set_mask" : "mdp_hnve_set_mask after mdp_set_atoms_host");
@@ -731,6 +823,8 @@ static int set_mask(mdp_ctx *c, const int *mask)
   MDP_HIP(c, hipStreamSynchronize(c->stream)); // the caller's array may change after return
   c->mask_set = true;
   c->mask_n = n;
+  c->lgv.disjoint_checked = false;
+  if (c->lgv.many()) MDP_TRY(mdp_lgv_check_disjoint(c, c->md ? "mdp_md_set_mask" : "mdp_hnve_set_mask"));
   return MDP_OK;
 }
 
@@ -1065,6 +1159,8 @@ int mdp_langevin_group(mdp_ctx *c, int groupbit)
 {
   if (!c) return MDP_EINVAL;
   if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_langevin_group: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
+  if (c->lgv.many())
+    return mdp_fail(c, MDP_ESTATE, "mdp_langevin_group: %d Langevin baths are on (mdp_langevin_baths); each has the group bit it was given", c->lgv.nbath);
   if (c->md) MDP_TRY(mdp_md_flush_final(c));
   c->lgv_bit = groupbit;
   return MDP_OK;

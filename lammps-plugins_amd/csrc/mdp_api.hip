@@ -916,6 +916,7 @@ int mdp_destroy(mdp_ctx *c)
   c->nhc.part.release();
   c->lgv.st.release();
   c->lgv.part.release();
+  c->lgv.overlap.release();
   c->fire.st.release();
   c->fire.part.release();
   c->fire.fsave.release();

@@ -308,6 +308,17 @@ struct MdpLangevin {
   double tab_dt = 0.0, tab_ftm2v = 0.0;    // what the factors in st were computed for
   DevBuf<double> st;        // [0..16) gfactor1, [16..32) gfactor2, [32..35) mean, [35] energy, [36] E of the last step
   DevBuf<double> part;      // per-block partial sums (zero: 3 per block; tally: 1 per block)
+  // several baths on disjoint groups (mdp_langevin_baths with nbath > 1; 0 otherwise: the one thermostat above).  They
+  // share first / last / step / need_setup; bath k keeps its words at st + k * kLgvWords, the partials are
+  // 3 MDP_LANGEVIN_MAXBATH per block (zero), then MDP_LANGEVIN_MAXBATH per block (tally)
+  int nbath = 0;
+  mdp_langevin_config bcfg[MDP_LANGEVIN_MAXBATH];
+  int bbit[MDP_LANGEVIN_MAXBATH] = {0, 0, 0, 0};
+  bool any_zero = false, any_tally = false;
+  bool disjoint_checked = false; // the current mask has been counted for atoms in more than one bath
+  DevBuf<int> overlap;           // [1] that count
+  bool many() const { return on && nbath > 1; }
+  bool sums() const { return on && (nbath > 1 ? any_zero || any_tally : cfg.zero || cfg.tally); } // one rank only
 };
 static constexpr int kLgvG2 = 16, kLgvMean = 32, kLgvE = 35, kLgvElast = 36, kLgvWords = 37;
 // FIRE minimiser (fire.hip): the control block lives in st on the device; the host keeps the configuration and what it
@@ -394,6 +405,20 @@ struct MdpLgvArgs {
   unsigned seed = 0, lo = 0, hi = 0, phase = 0; // the Philox key and counter words of the step
 };
 
+// ... of several baths (MdpLangevin::nbath > 1).  Everything a lane takes from its bath is picked by unrolled selects on
+// the bath index, never by indexing these arrays (no scratch) and never by a branch (lanes of different baths run the
+// same code); a slot beyond nbath has bit 0 and is never picked.
+struct MdpLgvBathArgs {
+  const int *tag = nullptr, *type = nullptr, *perm = nullptr;
+  const double *st = nullptr; // bath k: st + k * kLgvWords; the mean of a bath without zero yes stays 0
+  double *part = nullptr;     // some bath has tally yes: MDP_LANGEVIN_MAXBATH partial sums of f_L . v per block, [bath]
+  double tsqrt[MDP_LANGEVIN_MAXBATH] = {0.0, 0.0, 0.0, 0.0};
+  unsigned seed[MDP_LANGEVIN_MAXBATH] = {0, 0, 0, 0};
+  int bit[MDP_LANGEVIN_MAXBATH] = {0, 0, 0, 0};
+  int zero = 0;               // some bath has zero yes: the means are read
+  unsigned lo = 0, hi = 0, phase = 0;
+};
+
 // what the MASK variants of the integrate kernels need to honour the groups (mdp_integrate_group, mdp_langevin_group);
 // the variants without MASK never read it
 struct MdpGroupArgs {
@@ -451,6 +476,53 @@ __device__ __forceinline__ void mdp_lgv_force(const MdpLgvArgs &L, int i, double
     lx -= L.mean[0];
     ly -= L.mean[1];
     lz -= L.mean[2];
+  }
+}
+
+// several baths: the bath of an atom with mask m (its groups are disjoint: at most one bit matches)
+__device__ __forceinline__ int mdp_lgv_bath(const MdpLgvBathArgs &B, int m)
+{
+  int k = 0;
+  k = (m & B.bit[1]) ? 1 : k;
+  k = (m & B.bit[2]) ? 2 : k;
+  k = (m & B.bit[3]) ? 3 : k;
+  return k;
+}
+template <class T> __device__ __forceinline__ T mdp_lgv_pick(const T (&a)[MDP_LANGEVIN_MAXBATH], int k)
+{
+  T r = a[0];
+  r = k == 1 ? a[1] : r;
+  r = k == 2 ? a[2] : r;
+  r = k == 3 ? a[3] : r;
+  return r;
+}
+// owned atom i of bath k: the random part of its Langevin force, as mdp_lgv_random with the bath's table, T and seed
+__device__ __forceinline__ void mdp_lgv_random(const MdpLgvBathArgs &B, int i, int k, double &rx, double &ry, double &rz)
+{
+  const int a = B.perm ? B.perm[i] : i;
+  const int t = B.type[a] & 15;
+  unsigned c[4] = {(unsigned) B.tag[a], B.lo, B.hi, B.phase};
+  mdp_philox4x32_10(c, mdp_lgv_pick(B.seed, k), 0u);
+  const double g2 = B.st[k * kLgvWords + kLgvG2 + t] * mdp_lgv_pick(B.tsqrt, k);
+  rx = g2 * (((double) c[0] + 0.5) * 0x1p-32 - 0.5);
+  ry = g2 * (((double) c[1] + 0.5) * 0x1p-32 - 0.5);
+  rz = g2 * (((double) c[2] + 0.5) * 0x1p-32 - 0.5);
+}
+// ... and its Langevin force, as mdp_lgv_force (a bath without zero yes subtracts the 0 its mean holds: the same bits)
+__device__ __forceinline__ void mdp_lgv_force(const MdpLgvBathArgs &B, int i, int k, double vx, double vy, double vz,
+                                              double &lx, double &ly, double &lz)
+{
+  double rx, ry, rz;
+  mdp_lgv_random(B, i, k, rx, ry, rz);
+  const double *st = B.st + k * kLgvWords;
+  const double g1 = st[B.type[B.perm ? B.perm[i] : i] & 15];
+  lx = g1 * vx + rx;
+  ly = g1 * vy + ry;
+  lz = g1 * vz + rz;
+  if (B.zero) {
+    lx -= st[kLgvMean];
+    ly -= st[kLgvMean + 1];
+    lz -= st[kLgvMean + 2];
   }
 }
 
@@ -900,6 +972,11 @@ int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvA
 // with MDP_ESTATE when a group is set and no mask covers the current atoms
 int mdp_group_args(mdp_ctx *c, bool *masked, MdpGroupArgs *M);
 int mdp_lgv_close(mdp_ctx *c, const MdpLgvArgs &L);
+// ... with several baths on (c->lgv.many()): the same two calls around the bath instantiations
+int mdp_lgv_open_baths(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvBathArgs *B);
+int mdp_lgv_close_baths(mdp_ctx *c, const MdpLgvBathArgs &B);
+// several baths and a mask: count the atoms in more than one bath, once per mask or bath set-up, and refuse any
+int mdp_lgv_check_disjoint(mdp_ctx *c, const char *who);
 void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
 void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds
 void mdp_profile_release(mdp_ctx *c); // frees what profile.hip holds

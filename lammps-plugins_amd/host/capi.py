@@ -70,6 +70,7 @@ FIRE_STOP = {0: "running", 1: "force tolerance", 2: "energy tolerance", 3: "max 
 FIRE_DEFAULTS = dict(dmax=0.1, tmax=10.0, tmin=0.02, delaystep=20, dtgrow=1.1, dtshrink=0.5, alpha0=0.25,
                      alphashrink=0.99, halfstepback=True, initialdelay=True)   # LAMMPS min_modify defaults for fire
 BOLTZ_METAL = 8.617343e-5    # force->boltz, metal units
+LANGEVIN_MAXBATH = 4         # MDP_LANGEVIN_MAXBATH of include/mdpair_hip.h
 
 
 STYLE_REBOMOS, STYLE_AEAM = 1, 2
@@ -99,6 +100,7 @@ EXPORTS = [
     "mdp_md_defer_final", "mdp_md_list_state", "mdp_md_aeam_force_begin", "mdp_md_aeam_state", "mdp_dd_comm_aeam_exchange_begin", "mdp_dd_comm_aeam_exchange_end",
     "mdp_nhc_setup", "mdp_nhc_run", "mdp_nhc_state", "mdp_nhc_set_state", "mdp_nhc_off",
     "mdp_langevin_setup", "mdp_langevin_run", "mdp_langevin_tally", "mdp_langevin_off",
+    "mdp_langevin_baths", "mdp_langevin_tally_bath",
     "mdp_fire_setup", "mdp_fire_iterate", "mdp_fire_state", "mdp_fire_off",
     "mdp_md_set_mask", "mdp_hnve_set_mask", "mdp_integrate_group", "mdp_langevin_group",
     "mdp_md_set_image", "mdp_md_download_unwrapped", "mdp_msd_setup", "mdp_msd_sums", "mdp_msd_info", "mdp_msd_off",
@@ -541,25 +543,46 @@ class Context:
         self._ck(self.L.mdp_nhc_off(self.h))
 
     # ---------------- Langevin thermostat of the integrate calls (fix langevin/mdp)
-    def langevin_setup(self, t_start, t_stop, t_period, seed, natoms, ratio=None, zero=False, tally=False,
-                       boltz=BOLTZ_METAL, mvv2e=1.0364269e-4):
-        """ratio: {type: ratio} of `scale` (1 for the other types)"""
-        cfg = LangevinConfig()
+    @staticmethod
+    def _langevin_config(cfg, t_start, t_stop, t_period, seed, natoms, ratio=None, zero=False, tally=False,
+                         boltz=BOLTZ_METAL, mvv2e=1.0364269e-4):
         cfg.t_start, cfg.t_stop, cfg.t_period, cfg.seed = t_start, t_stop, t_period, seed
         cfg.zero, cfg.tally, cfg.boltz, cfg.mvv2e, cfg.natoms = int(zero), int(tally), boltz, mvv2e, natoms
         for t in range(16):
             cfg.ratio[t] = 1.0
         for t, r in (ratio or {}).items():
             cfg.ratio[t] = r
+
+    def langevin_setup(self, t_start, t_stop, t_period, seed, natoms, ratio=None, zero=False, tally=False,
+                       boltz=BOLTZ_METAL, mvv2e=1.0364269e-4):
+        """ratio: {type: ratio} of `scale` (1 for the other types)"""
+        cfg = LangevinConfig()
+        self._langevin_config(cfg, t_start, t_stop, t_period, seed, natoms, ratio, zero, tally, boltz, mvv2e)
         self._ck(self.L.mdp_langevin_setup(self.h, C.byref(cfg)))
+
+    def langevin_baths(self, baths, boltz=BOLTZ_METAL, mvv2e=1.0364269e-4):
+        """several thermostats on disjoint groups (mdp_langevin_baths): baths is a list of dicts with the keywords of
+        langevin_setup (t_start, t_stop, t_period, seed, natoms, ratio, zero, tally) and `bit`, the bath's group bit"""
+        n = len(baths)
+        cfgs = (LangevinConfig * max(n, 1))()
+        bits = (C.c_int * max(n, 1))()
+        for k, b in enumerate(baths):
+            b = dict(b)
+            bits[k] = int(b.pop("bit"))
+            self._langevin_config(cfgs[k], boltz=boltz, mvv2e=mvv2e, **b)
+        self._ck(self.L.mdp_langevin_baths(self.h, C.c_int(n), cfgs, bits))
 
     def langevin_run(self, first, last):
         self._ck(self.L.mdp_langevin_run(self.h, C.c_longlong(first), C.c_longlong(last)))
 
-    def langevin_tally(self):
-        """the thermostat energy (FixLangevin::compute_scalar; 0 without tally)"""
+    def langevin_tally(self, bath=None):
+        """the thermostat energy (FixLangevin::compute_scalar; 0 without tally); with several baths their sum in bath
+        order, or that of bath `bath`"""
         out = C.c_double(0.0)
-        self._ck(self.L.mdp_langevin_tally(self.h, C.byref(out)))
+        if bath is None:
+            self._ck(self.L.mdp_langevin_tally(self.h, C.byref(out)))
+        else:
+            self._ck(self.L.mdp_langevin_tally_bath(self.h, C.c_int(int(bath)), C.byref(out)))
         return out.value
 
     def langevin_off(self):

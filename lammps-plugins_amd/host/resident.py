@@ -234,6 +234,8 @@ class DeviceDomain:
         self.dangerous = 0
         self.aeam_overlapped = 0       # multi-GPU aeam steps whose exchanges travelled behind the interior tiles
         self._final_pending = False
+        self._nbath = 0                # baths set through langevin_baths (0: langevin() or none), and the one bath's bit
+        self._bath_bit = 0
         self.reneighbor()
 
     # ------------------------------------------------------------------ reneighboring
@@ -468,18 +470,26 @@ class DeviceDomain:
         integer array indexed by tag; bit 1 on every atom, as in LAMMPS), integrate_bit the group bit of the integrating
         fix -- every other atom keeps x and v bit for bit --, langevin_bit that of the Langevin thermostat (0: all of the
         integrate group).  The mask then travels with the atoms (reneighborings, migration).  mask_by_tag=None
-        withdraws the mask and both groups.  With several ranks every rank makes the same call."""
+        withdraws the mask and both groups.  With several ranks every rank makes the same call.  Baths set through
+        langevin_baths keep the bits they were given: with several on, a non-zero langevin_bit is refused; with one on,
+        langevin_bit=0 leaves that bath's bit in place."""
         self.flush()
+        several = self._nbath > 1
+        if several and langevin_bit:
+            raise ValueError(f"set_group: {self._nbath} Langevin baths are on (langevin_baths); each has the bit it was given")
         if mask_by_tag is None:
             self.ctx.integrate_group(0)
-            self.ctx.langevin_group(0)
+            if not several:
+                self.ctx.langevin_group(0)
+                self._bath_bit = 0
             self.ctx.md_set_mask(None)
             return
         m = np.asarray(mask_by_tag)
         tags = self.tags_local
         self.ctx.md_set_mask(m[tags].astype(np.int32))
         self.ctx.integrate_group(integrate_bit)
-        self.ctx.langevin_group(langevin_bit)
+        if not several:
+            self.ctx.langevin_group(langevin_bit or self._bath_bit)
 
     def mask_local(self):
         """the owned atoms' mask in device order (next to tags_local)"""
@@ -635,6 +645,27 @@ class DeviceDomain:
             raise ValueError("Langevin zero and tally run on one GPU only (they sum over all atoms every step)")
         self.ctx.langevin_setup(t_start, t_stop, damp, seed, self.natoms_total if natoms is None else int(natoms), ratio=ratio, zero=zero, tally=tally,
                                 boltz=S.BOLTZ, mvv2e=S.MVV2E)
+        self._nbath = self._bath_bit = 0
+        self.ctx.langevin_run(first, last)
+
+    def langevin_baths(self, baths, first=0, last=0):
+        """Several Langevin thermostats on disjoint groups in the integrate calls of this domain: baths is a list of
+        dicts with the keywords of langevin() (t_start, t_stop, damp, seed, ratio, zero, tally) plus `bit`, the bath's
+        group bit in the mask of set_group, and `natoms`, the atoms of that group (`zero` divides by it).  All baths
+        share first / last.  The groups must be disjoint and inside the integrate group; one bath is langevin() with
+        set_group's langevin_bit.  zero / tally need one GPU."""
+        if self.world > 1 and any(b.get("zero") or b.get("tally") for b in baths):
+            raise ValueError("Langevin zero and tally run on one GPU only (they sum over all atoms every step)")
+        self.flush()
+        cfgs = []
+        for b in baths:
+            b = dict(b)
+            b["t_period"] = b.pop("damp")
+            b["natoms"] = int(b["natoms"]) if b.get("natoms") is not None else self.natoms_total
+            cfgs.append(b)
+        self.ctx.langevin_baths(cfgs, boltz=S.BOLTZ, mvv2e=S.MVV2E)
+        self._nbath = len(cfgs)
+        self._bath_bit = int(cfgs[0]["bit"]) if len(cfgs) == 1 else 0
         self.ctx.langevin_run(first, last)
 
     def langevin_run(self, first, last):
@@ -646,12 +677,14 @@ class DeviceDomain:
     def langevin_off(self):
         """back to NVE; a deferred final half completes inside mdp_langevin_off, with its Langevin force"""
         self.ctx.langevin_off()
+        self._nbath = self._bath_bit = 0
         self._final_pending = False
 
-    def langevin_tally(self):
-        """the thermostat energy of the last full step (completes a deferred final half first)"""
+    def langevin_tally(self, bath=None):
+        """the thermostat energy of the last full step (completes a deferred final half first); with several baths
+        their sum in bath order, or that of bath `bath`"""
         self.flush()
-        return self.ctx.langevin_tally()
+        return self.ctx.langevin_tally(bath)
 
     def minimize(self, etol, ftol, maxiter, maxeval, chunk=64, **modify):
         """FIRE minimisation (LAMMPS min_style fire with its defaults; **modify: capi.FIRE_DEFAULTS) of this domain on the

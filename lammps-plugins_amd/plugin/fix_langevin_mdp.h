@@ -1,8 +1,13 @@
 /* -*- c++ -*- -----------------------------------------------------------------------------------
    `fix langevin/mdp`: LAMMPS `fix langevin` on the device, for runs that integrate with `fix nve/mdp` (any of its modes:
    host-linked, `bricks yes`, several ranks).  Not a time integrator: at init() it hands a copy of its settings to the
-   one fix nve/mdp (Fix::extract "mdp_langevin"), which switches the library's thermostat (mdp_langevin_*,
-   csrc/langevin.hip) on in the context its steps run on for the length of each run.
+   one fix nve/mdp (its slot of Fix::extract "mdp_langevin_baths", mdp_baths.h), which switches the library's thermostat
+   (mdp_langevin_*, csrc/langevin.hip) on in the context its steps run on for the length of each run.
+
+   Up to MDP_LANGEVIN_MAXBATH (4) of these fixes may stand next to one fix nve/mdp -- a hot and a cold bath, say -- if no
+   atom is in the groups of two of them (LAMMPS would add both forces on such an atom; init() refuses it and names both
+   fixes and the number of atoms).  Each then is a bath of its own: its numbers, its `zero` mean over its group, and its
+   tally, which its compute_scalar() returns (thermo f_ID; ecouple sums them).
 
    fix ID GROUP langevin/mdp Tstart Tstop damp seed [scale type ratio ...] [tally yes|no] [zero yes|no]
 
@@ -35,8 +40,11 @@ class FixLangevinMDP : public Fix {
 
  private:
   mdp_langevin_config cfg;
+  int bath = 0;                  // this fix's position among the langevin/mdp fixes of Modify's list, as of the last init()
   class Fix *integrator() const; // the fix nve/mdp of this run (looked up anew: no pointer outlives either fix)
   void inside(class Fix *nve);   // refuses a group with an atom the integrator does not move
+  void disjoint();               // refuses atoms shared with a langevin/mdp fix earlier in Modify's list
+  void too_many(int n);          // refuses langevin/mdp fix number n > MDP_LANGEVIN_MAXBATH
 };
 
 }    // namespace LAMMPS_NS

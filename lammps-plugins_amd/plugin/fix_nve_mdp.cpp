@@ -53,7 +53,7 @@
    and atom->mask with the atoms: next to the velocities at every host reneighboring in the host-linked mode
    (PairMDP::upload_host, mdp_hnve_set_mask), with the atoms into the brick otherwise (mdp_brick.h, mdp_md_set_mask),
    from where it comes back with them.  A fix langevin/mdp on a sub-group hands its bit over the same way
-   (mdp_langevin_group).  Group all sets both bits to 0 and uploads no mask for the fix's sake.  Run in the mini-host
+   (mdp_langevin_group), several of them on disjoint sub-groups their bits and settings together (mdp_langevin_baths).  Group all sets both bits to 0 and uploads no mask for the fix's sake.  Run in the mini-host
    on 2, 4 and 8 ranks (tests/test_gpu_minilmp_ranks.py: log.rebomos-bulk.4's rows, the one-rank thermo of hot runs with
    migration); against a real LAMMPS this mode is unverified.
 -------------------------------------------------------------------------------------------------- */
@@ -85,7 +85,7 @@ FixNVEMDP::FixNVEMDP(LAMMPS *lmp, int narg, char **arg)
     : Fix(lmp, narg, arg), ctxp(nullptr), pair_linked(nullptr), pair_mask(nullptr), downloads(0), hostcheck(0), took_delay(0), saved_delay(0),
       linked_to(nullptr), bricks(0), bricks_kw(0), bctx(nullptr), bricks_slot(nullptr), bricks_ev(nullptr), style_id(0), comm_up(0), pending_final(0), step_ev(0)
 {
-  memset(&lgv_cfg, 0, sizeof lgv_cfg);
+  memset(&baths, 0, sizeof baths);
   if (narg < 3 || (narg - 3) % 2) error->all(FLERR, "Illegal fix nve/mdp command");
   if (igroup < 0)
     error->all(FLERR, std::string("Fix ") + arg[2] + " requires group all or a group defined by the group command: could not find fix group ID " + arg[1]);
@@ -201,19 +201,20 @@ void FixNVEMDP::setup(int /*vflag*/)
   if (!c) fail(nullptr);
   apply_groups(c);
   run_ctx = c;
-  if (!lgv_on) return;
-  if (mdp_langevin_setup(c, &lgv_cfg) != MDP_OK) fail(c);
+  if (!baths.count) return;
+  if (baths.count == 1) {
+    if (mdp_langevin_setup(c, &baths.cfg[0]) != MDP_OK) fail(c);
+  } else if (mdp_langevin_baths(c, baths.count, baths.cfg, baths.bit) != MDP_OK) // (counts the atoms in two baths: the mask is up)
+    fail(c);
   if (mdp_langevin_run(c, (long long) update->beginstep, (long long) update->endstep) != MDP_OK) fail(c);
   lgv_ctx = c;
 }
 
-// fix langevin/mdp hands its thermostat over here (a copy of its config; no pointer to either fix is kept)
+// the langevin/mdp fixes hand their thermostats over here (copies of their configs; no pointer to either fix is kept)
 void *FixNVEMDP::extract(const char *name, int &dim)
 {
   dim = 0;
-  if (strcmp(name, "mdp_langevin") == 0) return &lgv_cfg;
-  if (strcmp(name, "mdp_langevin_on") == 0) return &lgv_on;
-  if (strcmp(name, "mdp_langevin_bit") == 0) return &lgv_bit;
+  if (strcmp(name, "mdp_langevin_baths") == 0) return &baths;
   if (strcmp(name, "mdp_run_ctx") == 0) return &lgv_ctx;
   if (strcmp(name, "mdp_steps_ctx") == 0) return &run_ctx;
   if (strcmp(name, "mdp_bricks") == 0) return &bricks;
@@ -235,7 +236,7 @@ void FixNVEMDP::apply_groups(mdp_ctx *c)
     if (masked() && mdp_hnve_set_mask(c, atom->nlocal ? atom->mask : &none) != MDP_OK) fail(c);
   }
   if (mdp_integrate_group(c, grouped() ? groupbit : 0) != MDP_OK) fail(c);
-  if (mdp_langevin_group(c, lgv_on ? lgv_bit : 0) != MDP_OK) fail(c);
+  if (mdp_langevin_group(c, baths.count == 1 ? baths.bit[0] : 0) != MDP_OK) fail(c); // (several baths bring their bits along)
 }
 
 void FixNVEMDP::setup_steps()
@@ -337,8 +338,7 @@ void FixNVEMDP::post_run()
   if (lgv_ctx && mdp_langevin_off(lgv_ctx) != MDP_OK) fail(lgv_ctx); // (an unfix of the thermostat gives NVE next run)
   lgv_ctx = nullptr;
   run_ctx = nullptr;
-  lgv_on = 0;
-  lgv_bit = 0;
+  memset(&baths, 0, sizeof baths);
   if (bricks) {
     long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (comm->nprocs > 1) (void) mdp_dd_comm_step_info(bctx, info);

@@ -29,6 +29,7 @@ FixStyle(nve/mdp,FixNVEMDP);
 
 #include "fix.h"
 
+#include "mdp_baths.h"
 #include "mdpair_hip.h"
 
 namespace LAMMPS_NS {
@@ -67,12 +68,11 @@ class FixNVEMDP : public Fix {
   int style_id, comm_up, pending_final, step_ev;
   const int *bricks_map = nullptr; // rebomos: the pair style's type -> element map, as of the last init()
 
-  // the Langevin thermostat a `fix langevin/mdp` handed over (extract "mdp_langevin" / "mdp_langevin_on"): switched on in
-  // setup() on the context the steps run on (lgv_ctx, extract "mdp_run_ctx"), off in post_run()
-  mdp_langevin_config lgv_cfg;
-  int lgv_on = 0;
+  // the Langevin thermostats the `fix langevin/mdp` fixes handed over (extract "mdp_langevin_baths", mdp_baths.h): switched
+  // on in setup() on the context the steps run on (lgv_ctx, extract "mdp_run_ctx"), off in post_run().  One: the calls of
+  // one thermostat (mdp_langevin_setup, mdp_langevin_group); several: mdp_langevin_baths
+  MdpLangevinBaths baths;
   int brick_masked = 0; // this run's brick was set up with atom->mask (it comes back with the atoms)
-  int lgv_bit = 0;     // the thermostat's group bit (extract "mdp_langevin_bit"; 0: every atom the fix integrates)
   mdp_ctx *lgv_ctx = nullptr;
   // the context the steps of the run under way go through, thermostat or not, null between runs (extract "mdp_steps_ctx":
   // compute msd/mdp reads its sums there); extract "mdp_bricks": whether that context is a brick of the library's own
@@ -86,7 +86,8 @@ class FixNVEMDP : public Fix {
   void fail(mdp_ctx *c);
   int taken_delay() const;
   bool grouped() const { return igroup > 0; }                  // the fix acts on a group other than all
-  bool masked() const { return grouped() || (lgv_on && lgv_bit); } // ... or its thermostat does: the device needs atom->mask
+  bool lgv_masked() const { return baths.count > 1 || (baths.count == 1 && baths.bit[0]); }
+  bool masked() const { return grouped() || lgv_masked(); }    // ... or a thermostat does: the device needs atom->mask
   bool brick_mask() const;                                     // bricks: atom->mask travels with the atoms
   double group_count();                                        // atoms the fix integrates, over all ranks
   void apply_groups(mdp_ctx *c);                               // the group bits (and, host-linked, the mask) of this run on c
