@@ -710,6 +710,30 @@ int mdp_profile_sums(mdp_ctx *ctx, const int exponent[MDP_PROFILE_W], long long 
 int mdp_profile_info(mdp_ctx *ctx, long long out[4]);
 int mdp_profile_off(mdp_ctx *ctx);
 
+/* ---- the heat current J = sum (ke_i + pe_i) v_i + sum W_i . v_i (LAMMPS compute heat/flux fed ke/atom, pe/atom and
+ * stress/atom NULL virial), from the per-atom tallies a compute left on the device -------------------------------------------
+ * For a resident context (MDP_ESTATE otherwise).  pe_i and W_i (xx yy zz xy xz yz) are what mdp_md_compute(eflag | 2,
+ * vflag | 4) -- or mdp_dd_comm_step_begin / _end with those flags -- tallied, in the reference's split (v_tally2/3,
+ * ev_tally3: not the centroid form).  In resident mode the shares of periodic self-images end on their owners inside the
+ * tallying compute.  The context remembers the flags of its last finished compute; a new compute, anything that moves the
+ * atoms (an integrate call, mdp_md_upload_x), a reneighbouring that re-orders them and mdp_md_setup make the tallies stale until the next
+ * tallying compute.  A final half-kick -- also the one a read here completes -- leaves them valid.
+ *   mdp_heatflux_sums:     blocking.  This rank's sums over the owned atoms (groupbit != 0: those with mask & groupbit) with
+ *                          full-step velocities (a final half the host deferred is completed first):
+ *                          out[0..2] = sum (1/2 mvv2e m v.v + eatom_i) v_i, out[3..5] = sum W_i . v_i
+ *                          (x: W0 vx + W3 vy + W4 vz, y: W3 vx + W1 vy + W5 vz, z: W4 vx + W5 vy + W2 vz),
+ *                          out[6] = the atoms summed, out[7] = sum (ke_i + eatom_i).  Extensive, not divided by the volume;
+ *                          the caller adds over ranks and forms LAMMPS' vector [out[0..2] + out[3..5], out[0..2]].  Fixed
+ *                          order, no float atomics: two reads of one state agree bit for bit.
+ *   mdp_md_download_vatom: blocking.  vatom [nlocal][6] of the owned atoms in device order, the sibling of the eatom
+ *                          argument of mdp_md_download.
+ * Both: MDP_ESTATE unless the last finished compute ran with MDP_EFLAG_ATOM and MDP_VFLAG_ATOM and its tallies are not
+ * stale; MDP_ENOTIMPL for an aeam brick of several ranks whose angular centres may reach a remote ghost (mdp_md_aeam_state
+ * out[3] == 1): the thirds three-body terms put on remote ghosts would need a reverse exchange of 7 doubles per ghost.
+ * mdp_heatflux_sums: MDP_ESTATE with a group bit and no mask that covers the current atoms. */
+int mdp_heatflux_sums(mdp_ctx *ctx, int groupbit, double out[8]);
+int mdp_md_download_vatom(mdp_ctx *ctx, double *vatom /* [nlocal][6], device order */);
+
 /* per-phase device time of the last compute in ms (HIP events on the compute stream):
  * rebomos: [0]=REBO centre kernels of the lane-group classes, [1]=the general kernel (centres that outgrew their lane
  * group since the list build), [2]=row pruning (0 unless one was due), [3]=LJ+gather kernel;

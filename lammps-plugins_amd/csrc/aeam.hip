@@ -1686,6 +1686,7 @@ static int aeam_open(mdp_ctx *c)
 {
   if (c->aeam_phase & AE_OPEN) return MDP_OK;
   if (!c->have_aeam || !c->neigh_set) return mdp_fail(c, MDP_ESTATE, "aeam: tables / neighbor list not set");
+  mdp_tally_drop(c);
   MDP_TRY(mdp_acc_begin(c, true));
   if (!c->f_prezeroed) // (resident runs on one GPU: the integrate kernel and the image refresh of this step did it)
     MDP_HIP(c, hipMemsetAsync(c->f.p, 0, sizeof(double) * 3 * c->nall, c->stream));
@@ -1922,8 +1923,15 @@ int mdp_aeam_run_force(mdp_ctx *c, int eflag, int vflag)
     mdp_span_end(c, 4);
   }
   MDP_HIP(c, hipGetLastError());
+  // resident runs: the thirds of the per-atom virial that angular centres put on periodic self-images go to their owners
+  // (Comm::reverse_comm of vatom on one rank), so that the owned rows are complete for whoever reads them on the device.
+  // eatom has no such shares: the pair energy is credited to the visiting atom, the embedding energy to its own.
+  if (c->md && (vflag & MDP_VFLAG_ATOM) && c->h_ang_count) MDP_TRY(mdp_md_ghost_fold(c, 6, c->vatom.p));
   c->aeam_phase = 0;
-  return mdp_acc_end(c, eflag || vflag); // force-only steps tally nothing: no slots to fold
+  MDP_TRY(mdp_acc_end(c, eflag || vflag)); // force-only steps tally nothing: no slots to fold
+  c->tally_eflag = eflag; // (the per-atom tallies of this compute, if it took any, stand until the atoms move)
+  c->tally_vflag = vflag;
+  return MDP_OK;
 }
 
 extern "C" {

@@ -533,6 +533,7 @@ int mdp_dd_migrate_begin(mdp_ctx *c, int *send_counts)
   const int n = c->nlocal;
   D.nlocal_old = n;
   D.nghost_old = c->nghost;
+  mdp_tally_drop(c); // (the atoms are about to be re-ordered: eatom / vatom do not follow them)
   MDP_HIP(c, D.dest.reserve((size_t) n + 1));
   MDP_HIP(c, hipMemsetAsync(D.counters.p, 0, sizeof(int) * (4 * G.nranks + 16), st));
   if (n && c->image_set) dd_remap_kernel<true><<<nblk(n), 256, 0, st>>>(G, n, c->xq.p, D.dest.p, D.counters.p, c->image.p);

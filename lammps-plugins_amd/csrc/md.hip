@@ -865,6 +865,15 @@ int mdp_host_ghost_fold(mdp_ctx *c, int w, double *d_a)
   return MDP_OK;
 }
 
+// resident mode: the same fold over the periodic self-images of the brick (remote ghosts, owner < 0, are left alone)
+int mdp_md_ghost_fold(mdp_ctx *c, int w, double *d_a)
+{
+  if (!c->md || c->nghost <= 0) return MDP_OK;
+  ghost_fold_kernel<<<nblk(c->nghost), 256, 0, c->stream>>>(c->nlocal, c->nghost, w, c->ghost_owner.p, d_a);
+  MDP_HIP(c, hipGetLastError());
+  return MDP_OK;
+}
+
 // ---- neighbor-list cutoffs the style's init_one() would hand the host ----------------------------
 // aeam: squared list cutoffs (cut[ti][tj] + skin)^2 per type pair (pair_aeam.cpp:618-620), in the kernel arguments up
 // to MDP_AEAM_MAXT types, in device memory beyond
@@ -1066,6 +1075,7 @@ int mdp_md_setup(mdp_ctx *c, const mdp_md_config *cfg, const double *x, const do
     ta[nlocal + g] = ghost_type[g];
     if (ghost_tag) ga[nlocal + g] = ghost_tag[g];
   }
+  mdp_tally_drop(c); // (tallies of an earlier set of atoms)
   c->md = true; // before the upload: resident atoms keep the caller's order and their staging arrays are temporaries
   MDP_TRY(mdp_set_atoms_host(c, nlocal, nghost, xa.data(), ta.data(), ga.data(), cfg->ntypes, map));
   for (int d = 0; d < 3; d++) { // resident mode bins over the caller's box
@@ -1322,6 +1332,7 @@ int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double
   // must not be applied twice
   if (c->final_deferred_seen && with_final && !c->final_pending) with_final = false;
   if (with_final) c->final_pending = false;
+  mdp_tally_drop(c); // (the atoms move: eatom / vatom describe the state they leave)
   // aeam accumulates into f (three-body atomics, tile kernels): its force_clear rides in this kernel and in the refresh
   // of the images when every ghost is a periodic self-image (one GPU).  The flag is dropped by whatever rebuilds or
   // re-orders the atom arrays before the compute (mdp_aeam_prepare) -- the compute then clears f itself.
@@ -1703,6 +1714,7 @@ int mdp_md_upload_x(mdp_ctx *c, const double *x)
   c->prune_epoch++;
   mdp_sflag_drop(c);
   c->check_now = true;
+  mdp_tally_drop(c); // (eatom / vatom belong to the positions that were replaced)
   return MDP_OK;
 }
 

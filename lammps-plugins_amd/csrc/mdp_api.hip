@@ -925,6 +925,7 @@ int mdp_destroy(mdp_ctx *c)
   mdp_msd_release(c);
   mdp_rdf_release(c);
   mdp_profile_release(c);
+  mdp_heatflux_release(c);
   if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
   delete c;
   return MDP_OK;

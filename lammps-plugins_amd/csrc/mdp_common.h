@@ -393,6 +393,11 @@ struct MdpProfile {
   DevBuf<double> part;             // per-block maxima of |t_k|, MDP_PROFILE_W per block, then the MDP_PROFILE_W maxima
   DevBuf<unsigned long long> out;  // [rows][MDP_PROFILE_W] sums (two's complement), [rows] counts, then the column flags
 };
+// the heat current (heatflux.hip): nothing but the partials of a read; the tallies it reads are the run's own (eatom, vatom)
+struct MdpHeatflux {
+  DevBuf<double> part; // per-block partials, kHfW per block, then the kHfW sums
+};
+static constexpr int kHfW = 8; // sum (ke + pe) v (3), sum W.v (3), count, sum (ke + pe)
 static constexpr int kMsdW = 9;// sum dx^2, dy^2, dz^2, count, sum m xu (3), sum m, atoms whose tag has no origin
 
 // what the integrate kernels need to add the Langevin force of one step (md.hip nve_advance_kernel / nve_final_kernel)
@@ -789,6 +794,10 @@ struct mdp_ctx {
   MdpMsd msd;
   MdpRdf rdf;                      // pair-distance histograms of the current positions (mdp_rdf_setup)
   MdpProfile profile;              // binned mass, momentum and kinetic energy of the current atoms (mdp_profile_setup)
+  MdpHeatflux heatflux;            // partial sums of a heat-current read (mdp_heatflux_sums)
+  // eflag / vflag of the last FINISHED compute while its per-atom tallies (eatom, vatom) still describe the owned atoms in
+  // their current order and state; -1 after anything that starts a compute, moves the atoms or re-orders them
+  int tally_eflag = -1, tally_vflag = -1;
   bool final_pending = false;      // the host deferred the final half-kick of the finished step (mdp_md_defer_final)
   bool final_deferred_seen = false; // the host uses mdp_md_defer_final at all (older hosts: with_final is authoritative)
   bool acc_prezeroed = false; // the integrate kernel reset the accumulators: the next mdp_acc_begin launches nothing
@@ -951,6 +960,7 @@ int mdp_host_pinned_reserve(mdp_ctx *c, size_t ndoubles); // c->h_down: pinned d
 int mdp_host_upload(mdp_ctx *c, void *d_dst, const void *h_src, size_t bytes); // pageable host array -> device, pipelined through pinned staging
 int mdp_host_refresh_ghosts(mdp_ctx *c);                  // host mode, images kept by the library: owner + count * h of this step
 int mdp_md_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double hardsq); // integrate kernel (+ displacement check)
+int mdp_md_ghost_fold(mdp_ctx *c, int w, double *d_a); // resident mode: what the periodic self-images collected (w doubles per atom) onto their owners
 int mdp_md_flush_final(mdp_ctx *c); // completes a final half the host deferred (resident mode), before anything that needs full-step velocities
 // `neigh_modify check yes` of the host-level skin, one step late (kPinMoved).  _take: the answer of the check the previous
 // call queued (waits for its event; 0 if none is pending); _arm: zeroes the words, gives the squared limits for `skin`;
@@ -980,6 +990,9 @@ int mdp_lgv_check_disjoint(mdp_ctx *c, const char *who);
 void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
 void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds
 void mdp_profile_release(mdp_ctx *c); // frees what profile.hip holds
+void mdp_heatflux_release(mdp_ctx *c); // frees what heatflux.hip holds
+// the per-atom tallies are stale from here on (a compute starts, the atoms move, are re-ordered or replaced)
+inline void mdp_tally_drop(mdp_ctx *c) { c->tally_eflag = c->tally_vflag = -1; }
 // FIRE minimiser (fire.hip), in place of the integrate kernel when c->fire.on: the half step back / zeroing and the Euler
 // step of the iteration whose control kernel was queued last, with the same votes, accumulator reset and force clear
 int mdp_fire_launch_advance(mdp_ctx *c, int *flag, double trigsq, double hardsq, const MdpStyleCheck &sc, bool zero_f);

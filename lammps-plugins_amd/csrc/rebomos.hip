@@ -4395,6 +4395,7 @@ static int launch_centres_vatom(mdp_ctx *c, int eflag, int vflag)
 // upkeep and the REBO centres whose candidate sets reach no remote ghost.  Runs while the halo exchange is in flight.
 int mdp_rebomos_run_begin(mdp_ctx *c, int eflag, int vflag)
 {
+  mdp_tally_drop(c);
   c->computes_since_build++;
   if (c->rebo_packed) {
     bool stale = false;
@@ -4483,7 +4484,10 @@ int mdp_rebomos_run_end(mdp_ctx *c, int eflag, int vflag)
   }
   MDP_HIP(c, hipGetLastError());
   mdp_time_mark(c, 4);
-  return mdp_acc_end(c, eflag || vflag);
+  MDP_TRY(mdp_acc_end(c, eflag || vflag));
+  c->tally_eflag = eflag; // (the per-atom tallies of this compute, if it took any, stand until the atoms move)
+  c->tally_vflag = vflag;
+  return MDP_OK;
 }
 
 // force_clear + compute on the device; results stay on the device (f, eatom, acc)

@@ -107,6 +107,7 @@ EXPORTS = [
     "mdp_rdf_setup", "mdp_rdf_counts", "mdp_rdf_info", "mdp_rdf_off",
     "mdp_profile_setup", "mdp_profile_range", "mdp_profile_exponent", "mdp_profile_sums", "mdp_profile_info", "mdp_profile_off",
     "mdp_rebomos_centre_paths",
+    "mdp_heatflux_sums", "mdp_md_download_vatom",
 ]
 
 
@@ -907,6 +908,20 @@ class Context:
 
     def profile_off(self):
         self._ck(self.L.mdp_profile_off(self.h))
+
+    # ---------------- the heat current from the per-atom tallies of the last compute (csrc/heatflux.hip)
+    def heatflux_sums(self, group_bit=0):
+        """this rank's sums over the group's owned atoms: [sum (ke + pe) v (3), sum W.v (3), count, sum (ke + pe)]; needs the last
+        compute to have run with eflag | 2 and vflag | 4"""
+        out = np.zeros(8)
+        self._ck(self.L.mdp_heatflux_sums(self.h, C.c_int(int(group_bit)), _dp(out)))
+        return out
+
+    def md_download_vatom(self, nlocal):
+        """the owned atoms' per-atom virial [nlocal][6] (xx yy zz xy xz yz) in device order, under the rule of heatflux_sums"""
+        va = np.zeros((nlocal, 6))
+        self._ck(self.L.mdp_md_download_vatom(self.h, _dp(va)))
+        return va
 
     # halo plumbing (device pointers as ints)
     def md_pack_x(self, n, d_sendlist, d_shift, d_buf):

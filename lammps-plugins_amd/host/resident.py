@@ -617,6 +617,15 @@ class DeviceDomain:
     def profile_off(self):
         self.ctx.profile_off()
 
+    # ------------------------------------------------------------------ the heat current
+    def heatflux(self, group_bit=0):
+        """LAMMPS compute heat/flux's six values -- J = sum (ke + pe) v + sum W.v, then its convective part sum (ke + pe) v --
+        over the atoms with mask & group_bit (0: every atom), summed over the ranks through the domain's transport; extensive,
+        not divided by the volume.  The last step (or compute) must have run with eflag | 2 and vflag | 4."""
+        self.flush()
+        s = self._group_sum(self.ctx.heatflux_sums(group_bit))
+        return np.concatenate([s[0:3] + s[3:6], s[0:3]])
+
     def thermostat(self, t_start, t_stop, t_period, tchain=3, tloop=1, drag=0.0, first=0, last=0, nf=None):
         """Nose-Hoover chain thermostat (LAMMPS fix nvt) in the integrate calls of this domain, from the chain at rest; one
         GPU only.  first / last: the ramp of the run that follows (nhc_run).  nf: the degrees of freedom, 3 N - 3 of all

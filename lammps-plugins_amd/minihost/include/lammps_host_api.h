@@ -358,6 +358,9 @@ class Compute : protected Pointers {
   double **array = nullptr;     // the values compute_array() leaves (thermo c_ID[i][j] reads array[i - 1][j - 1])
   int array_flag = 0, size_array_rows = 0, size_array_cols = 0, extarray = 0;
   bigint invoked_array = -1;    // the step compute_array() ran last
+  // what Integrate::ev_set reads: the compute needs per-atom energy / per-atom virial tallied on the steps it is due,
+  // and (timeflag) it is due only on the steps its readers -- thermo, fix ave/time -- announce
+  int peatomflag = 0, pressatomflag = 0, timeflag = 0;
 
   // (as Fix: an unknown group ID leaves igroup = -1 and no bit, and the style says what it takes)
   Compute(LAMMPS *lmp, int narg, char **arg) : Pointers(lmp)
@@ -391,6 +394,8 @@ class Modify {
  public:
   int nfix = 0;
   Fix **fix = nullptr;
+  int ncompute = 0;             // ... and the computes
+  Compute **compute = nullptr;
   // Modify::get_fix_by_style: the fixes whose style matches the pattern (utils::strmatch: a regular expression search)
   const std::vector<Fix *> get_fix_by_style(const std::string &style) const
   {

@@ -263,6 +263,8 @@ struct Host {
   {
     modify.nfix = (int) fixes.size();
     modify.fix = fixes.data();
+    modify.ncompute = (int) computes.size();
+    modify.compute = computes.data();
   }
   Fix *fix_by_id(const std::string &id)
   {
@@ -1081,6 +1083,22 @@ struct Host {
     domain.h[3] = tilt[2]; domain.h[4] = tilt[1]; domain.h[5] = tilt[0];
   }
 
+  // Integrate::ev_set on a thermo step: the per-atom bits (ENERGY_ATOM 2 in *eflag, VIRIAL_ATOM 4 in *vflag) when a compute
+  // that needs those tallies is due -- a compute with timeflag is due on the steps its reader announces, and the one
+  // reader here is a thermo column
+  void atom_tallies_due(int *eflag, int *vflag)
+  {
+    *eflag = *vflag = 0;
+    for (auto &col : thermo_cols) {
+      if (col.compare(0, 2, "c_") != 0) continue;
+      int i = 0, j = 0;
+      const Compute *cp = compute_ref(col, false, i, j);
+      if (!cp || !cp->timeflag) continue; // (Modify::addstep_compute announces steps to computes with timeflag only)
+      if (cp->peatomflag) *eflag |= 2;
+      if (cp->pressatomflag) *vflag |= 4;
+    }
+  }
+
   void compute_forces(int eflag, int vflag)
   {
     sync_domain();
@@ -1119,8 +1137,10 @@ struct Host {
     printf("  pair %s, perpetual\n      attributes: full, newton on%s\n", "style", (neighbor.request_flags & NeighConst::REQ_GHOST) ? ", ghost" : "");
     const int every = thermo_every;
     output.next = output.next_thermo = step; // (setup: thermo of the initial state)
-    compute_forces(1, 2);
-    for (Fix *f : fixes) f->setup(2);
+    int ea = 0, va = 0; // the per-atom bits of a thermo step of this run (0 without a due compute that needs the tallies)
+    if (fix) atom_tallies_due(&ea, &va);
+    compute_forces(1 | ea, 2 | va);
+    for (Fix *f : fixes) f->setup(2 | va);
     print_thermo_header();
     print_thermo();
     const double dtf = 0.5 * dt * FTM2V;
@@ -1135,7 +1155,7 @@ struct Host {
         output.next = output.next_thermo = std::min<long>(nt, first + nsteps);
       }
       if (fix) { // Verlet::run with a time-integration fix style from a plugin
-        fix->initial_integrate((every > 0 && step % every == 0) || k == nsteps ? 2 : 0); // (ev_set: this step's vflag)
+        fix->initial_integrate((every > 0 && step % every == 0) || k == nsteps ? 2 | va : 0); // (ev_set: this step's vflag)
         // Neighbor::decide(): fixes that ask for a reneighboring on this step, then every / delay / check
         bool nflag = fix->force_reneighbor && fix->next_reneighbor == step;
         if (!nflag) {
@@ -1151,7 +1171,7 @@ struct Host {
         const bool out = every > 0 && (step % every == 0);
         const bool last = k == nsteps;
         if (out || last)
-          compute_forces(1, 2);
+          compute_forces(1 | ea, 2 | va);
         else { // (the style adds nothing to the host's f on such a step -- its reader is on the device: no force_clear
                //  of 24 bytes per atom, no fold of ghost forces.  Verlet::force_clear of a real LAMMPS is a memset per step.)
           sync_domain();
@@ -1945,6 +1965,7 @@ struct Script {
         delete old;
       }
       H.computes.push_back(cp);
+      H.sync_modify();
     } else if (c == "timestep") {
       need(2);
       H.dt = std::stod(w[1]);
@@ -2116,6 +2137,7 @@ int main(int argc, char **argv)
       H.force.pair = nullptr;
       for (Compute *c : H.computes) delete c;
       H.computes.clear();
+      H.sync_modify();
       for (Fix *f : H.fixes) delete f;
       H.fixes.clear();
       H.sync_modify();

@@ -24,8 +24,10 @@
    periodic images, the lists and every reneighboring are then the device's too (mdp_md_integrate_check, mdp_dd_reneighbor,
    mdp_md_compute) and the host's Neighbor idles for the length of the run -- 2.88 against 3.08 ms per step at 3.98 M atoms
    from rest, and for hot runs the difference between a reneighboring of 2 ms on the device and one on the host (sample.in's
-   alloy at 1.0 M atoms: 1.12 ms per step).  Not the default on one rank: per-atom energy / virial and a non-periodic box
-   need the mode above.
+   alloy at 1.0 M atoms: 1.12 ms per step).  Not the default on one rank: per-atom energy / virial for a compute on the host
+   and a non-periodic box need the mode above.  (Per-atom tallies for a reader on the device -- compute heatflux/mdp -- are
+   taken on the brick: a step LAMMPS opens with VIRIAL_ATOM runs with eflag | 2, vflag | 4 there when every compute that
+   asks for per-atom tallies is a /mdp style, see init_bricks; bit 4 of the pair style's bricks_ev.)
 
    Several ranks ("bricks").  There the host's Comm owns ghosts and migration, on host arrays -- which is what this fix
    takes out of the steps.  So it runs the library's own decomposition instead, as minihost/ddhost.cpp does without a
@@ -66,7 +68,9 @@
 #include "domain.h"
 #include "error.h"
 #include "force.h"
+#include "compute.h"
 #include "group.h"
+#include "modify.h"
 #include "neighbor.h"
 #include "output.h"
 #include "pair.h"
@@ -184,6 +188,17 @@ void FixNVEMDP::init_bricks()
   style_id = own.style_id;
   bricks_map = own.map;
   bricks = 1;
+  // a step with per-atom tallies is let through only when everything that asks for them reads them on the device
+  int asking = 0, on_device = 0;
+  for (int i = 0; i < modify->ncompute; i++) {
+    const Compute *cp = modify->compute[i];
+    if (!cp->peatomflag && !cp->pressatomflag) continue;
+    asking++;
+    const size_t n = strlen(cp->style);
+    if (n > 4 && strcmp(cp->style + n - 4, "/mdp") == 0) on_device++;
+  }
+  atom_ok = asking > 0 && asking == on_device;
+  atom_steps = 0;
   *bricks_slot = nullptr; // (the setup compute of this run is the host's: its arrays are the current ones)
   // neither a check nor a reneighboring of the host's during the run: both read arrays that are not current
   if (!took_delay) saved_delay = neighbor->delay;
@@ -194,9 +209,9 @@ void FixNVEMDP::init_bricks()
 
 // Modify::setup, behind the host's own setup (exchange, borders, lists, forces of step 0 in host mode); then the
 // Langevin thermostat, if a fix langevin/mdp handed one over, on the context the steps of this run go through
-void FixNVEMDP::setup(int /*vflag*/)
+void FixNVEMDP::setup(int vflag)
 {
-  setup_steps();
+  setup_steps(vflag);
   mdp_ctx *c = bricks ? bctx : ctx();
   if (!c) fail(nullptr);
   apply_groups(c);
@@ -239,14 +254,18 @@ void FixNVEMDP::apply_groups(mdp_ctx *c)
   if (mdp_langevin_group(c, baths.count == 1 ? baths.bit[0] : 0) != MDP_OK) fail(c); // (several baths bring their bits along)
 }
 
-void FixNVEMDP::setup_steps()
+void FixNVEMDP::setup_steps(int vflag)
 {
   if (!bricks) return;
+  // step 0 with per-atom tallies when LAMMPS opened its setup that way (a compute heatflux/mdp is due): energy and virial
+  // with them, as on every such step
+  const int at = atom_step(vflag) ? 1 : 0, ef = at ? 3 : 0, vf = at ? 5 : 0;
+  atom_steps += at;
   brick_masked = brick_mask() ? 1 : 0;
   if (mdp_brick_from_host(bctx, style_id, bricks_map, atom, domain, force, neighbor, update, comm, brick_masked != 0) != MDP_OK) fail(bctx);
   if (comm->nprocs == 1) { // one brick: its periodic images are the library's, no communicator
     if (mdp_dd_reneighbor(bctx) != MDP_OK) fail(bctx);
-    if (mdp_md_compute(bctx, 0, 0) != MDP_OK) fail(bctx);
+    if (mdp_md_compute(bctx, ef, vf) != MDP_OK) fail(bctx);
     pending_final = 0;
     *bricks_slot = bctx;
     return;
@@ -265,12 +284,12 @@ void FixNVEMDP::setup_steps()
   // forces of step 0 for the first half-kick (the host printed its own setup thermo from its host-mode compute)
   int rc;
   if (style_id == 2) {
-    rc = mdp_md_aeam_density(bctx, 0);
+    rc = mdp_md_aeam_density(bctx, ef);
     if (rc == MDP_OK) rc = mdp_dd_comm_forward_scalar(bctx);
-    if (rc == MDP_OK) rc = mdp_md_aeam_force(bctx, 0, 0);
+    if (rc == MDP_OK) rc = mdp_md_aeam_force(bctx, ef, vf);
     if (rc == MDP_OK) rc = mdp_dd_comm_reverse(bctx);
   } else
-    rc = mdp_md_compute(bctx, 0, 0);
+    rc = mdp_md_compute(bctx, ef, vf);
   if (rc != MDP_OK) fail(bctx);
   pending_final = 0;
   *bricks_slot = bctx; // from now on Pair::compute ends the steps this fix opens
@@ -305,7 +324,9 @@ void FixNVEMDP::initial_integrate(int vflag)
   if (bricks) {
     const bigint now = update->ntimestep;
     step_ev = (vflag || now == output->next || now == update->laststep) ? 1 : 0;
-    *bricks_ev = step_ev | (comm->nprocs == 1 ? 2 : 0);
+    const int at = atom_step(vflag) ? 1 : 0; // (VIRIAL_ATOM: vflag != 0, so the step has energy and virial too)
+    atom_steps += at;
+    *bricks_ev = step_ev | (comm->nprocs == 1 ? 2 : 0) | (at ? 4 : 0);
     if (comm->nprocs == 1) { // one brick: the deferred on-device `check yes` flag, the lists rebuilt on the device when it fired
       int moved = 0, dangerous = 0;
       if (mdp_md_integrate_check(bctx, pending_final, &moved, &dangerous) != MDP_OK) fail(bctx);
@@ -315,7 +336,7 @@ void FixNVEMDP::initial_integrate(int vflag)
       }
     } else {
       int ren = 0;
-      if (mdp_dd_comm_step_begin(bctx, pending_final, -1, step_ev, step_ev, &ren) != MDP_OK) fail(bctx);
+      if (mdp_dd_comm_step_begin(bctx, pending_final, -1, step_ev | (at ? 2 : 0), step_ev | (at ? 4 : 0), &ren) != MDP_OK) fail(bctx);
     }
     pending_final = step_ev ? 0 : 1; // (Pair::compute ends the step with the half-kick deferred on steps without output)
     return;
@@ -345,9 +366,10 @@ void FixNVEMDP::post_run()
     else info[3] = one_rank_builds;
     one_rank_builds = 0;
     if (comm->me == 0 && getenv("MDP_FIX_STATS"))
-      printf("fix nve/mdp: %d bricks, %lld reneighborings on the device, %ld returns of the atoms to the host in this run\n", comm->nprocs,
-             info[3], downloads);
+      printf("fix nve/mdp: %d bricks, %lld reneighborings on the device, %ld returns of the atoms to the host, %ld computes with per-atom "
+             "tallies in this run\n", comm->nprocs, info[3], downloads, atom_steps);
     downloads = 0;
+    atom_steps = 0;
     *bricks_slot = nullptr; // the next run's setup is the host's again, from the arrays the last step brought back
     return;
   }

@@ -67,6 +67,13 @@ class FixNVEMDP : public Fix {
   int *bricks_ev;      // the pair style's copy of "this step was opened with energy / virial"
   int style_id, comm_up, pending_final, step_ev;
   const int *bricks_map = nullptr; // rebomos: the pair style's type -> element map, as of the last init()
+  // per-atom tally steps (compute heatflux/mdp): every compute that asks for per-atom energy or virial reads them on the
+  // device (a /mdp style) -- then a step LAMMPS opens with VIRIAL_ATOM tallies eatom / vatom on the brick; a host
+  // compute among them would read zeros, so the pair style stops such a step as it always has
+  int atom_ok = 0;
+  long atom_steps = 0; // computes with per-atom tallies in this run (MDP_FIX_STATS)
+  static constexpr int kVirialAtom = 4; // VIRIAL_ATOM of LAMMPS' force.h: the bit of the vflag Integrate::ev_set hands out
+  bool atom_step(int vflag) const { return atom_ok && (vflag & kVirialAtom); }
 
   // the Langevin thermostats the `fix langevin/mdp` fixes handed over (extract "mdp_langevin_baths", mdp_baths.h): switched
   // on in setup() on the context the steps run on (lgv_ctx, extract "mdp_run_ctx"), off in post_run().  One: the calls of
@@ -79,7 +86,7 @@ class FixNVEMDP : public Fix {
   mdp_ctx *run_ctx = nullptr;
 
   mdp_ctx *ctx() const { return ctxp ? *ctxp : nullptr; }
-  void setup_steps();
+  void setup_steps(int vflag);
   void to_host(bool forces);
   void init_bricks();
   void bricks_to_host();

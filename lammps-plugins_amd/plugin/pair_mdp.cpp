@@ -146,17 +146,20 @@ bool PairMDP::upload_host(const HostUpload &u)
 // the steps that ask.
 void PairMDP::compute_bricks()
 {
-  if (eflag_atom || vflag_atom)
+  // per-atom tallies stay on the brick for a reader on the device (compute heatflux/mdp): only on a step the fix opened
+  // for them (bit 4: every compute that asks for them is such a reader)
+  const int at = (bricks_ev & 4) ? 1 : 0;
+  if ((eflag_atom || vflag_atom) && !at)
     error->all(FLERR, prefix() + ": per-atom energy / virial is not available while fix nve/mdp keeps the atoms on its bricks");
   const int want = (eflag_global || vflag_global) ? 1 : 0;
   if (want && !(bricks_ev & 1)) error->all(FLERR, prefix() + ": energy / virial asked for on a step fix nve/mdp opened without them");
-  const int ev = (bricks_ev & 1) ? 1 : 0;
+  const int ev = (bricks_ev & 1) ? 1 : 0, ef = ev | (at ? 2 : 0), vf = ev | (at ? 4 : 0);
   int rc;
   if (bricks_ev & 2) { // one rank (`bricks yes`): no exchange to wait for -- compute, then the half-kick now or with the next step's
-    rc = mdp_md_compute(bricks, ev, ev);
+    rc = mdp_md_compute(bricks, ef, vf);
     if (rc == MDP_OK) rc = ev ? mdp_md_final_integrate(bricks) : mdp_md_defer_final(bricks);
   } else
-    rc = mdp_dd_comm_step_end(bricks, ev, ev, ev ? 0 : 1);
+    rc = mdp_dd_comm_step_end(bricks, ef, vf, ev ? 0 : 1);
   if (rc != MDP_OK) error->one(FLERR, prefix() + ": " + mdp_last_error(bricks));
   if (!want) return;
   double t[9];

@@ -31,7 +31,7 @@ class PairMDP : public Pair {
   int nve_linked;               // set by fix nve/mdp: x, v and f of the owned atoms stay on the device between reneighborings
   int nve_mask;                 // set by fix nve/mdp on a group (or with a thermostat on one): atom->mask goes up with the velocities
   mdp_ctx *bricks;              // set by fix nve/mdp on several ranks: its context holds this rank's brick, whole steps run there
-  int bricks_ev;                // ... and whether it opened the current step with energy / virial
+  int bricks_ev;                // ... and how it opened the current step: 1 energy / virial, 2 one brick, 4 per-atom tallies
   int nall_uploaded;            // atoms on the device match the host's (nlocal+nghost) of the last upload
 
   // what differs between the styles in the upload stage of compute()
