@@ -40,16 +40,6 @@ __global__ __launch_bounds__(256) void heatflux_partial_kernel(const int n, cons
   mdp_block_sum_256<kHfW>(e, part);
 }
 
-__global__ __launch_bounds__(256) void heatflux_total_kernel(const double *__restrict__ part, const int npart,
-                                                             double *__restrict__ out)
-{
-  double s[kHfW];
-  mdp_slot_sum_256<kHfW>(part, npart, s);
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < kHfW; k++) out[k] = s[k];
-}
-
 // both reads: a resident context whose last finished compute took eatom and vatom for the atoms as they are now
 int heatflux_require(mdp_ctx *c, const char *who)
 {
@@ -79,8 +69,7 @@ int mdp_heatflux_sums(mdp_ctx *c, int groupbit, double out[8])
 {
   MDP_TRY(heatflux_require(c, "mdp_heatflux_sums"));
   if (!out) return MDP_EINVAL;
-  if (groupbit && (!c->mask_set || c->mask_n != c->nlocal))
-    return mdp_fail(c, MDP_ESTATE, "mdp_heatflux_sums: a group is set but no mask covers the current atoms (mdp_md_set_mask)");
+  MDP_TRY(mdp_require_group_mask(c, "mdp_heatflux_sums", groupbit, true));
   MDP_TRY(mdp_md_flush_final(c)); // full-step velocities (a final half is no compute and moves no atom: the tallies stand)
   MdpHeatflux &h = c->heatflux;
   hipStream_t st = c->stream;
@@ -90,7 +79,7 @@ int mdp_heatflux_sums(mdp_ctx *c, int groupbit, double out[8])
   if (n)
     heatflux_partial_kernel<<<nb, 256, 0, st>>>(n, groupbit, 0.5 * c->cfg.mvv2e, groupbit ? c->mask.p : nullptr, c->rmass.p, c->v.p,
                                                 c->eatom.p, reinterpret_cast<const double2 *>(c->vatom.p), h.part.p);
-  heatflux_total_kernel<<<1, 256, 0, st>>>(h.part.p, nb, tot);
+  mdp_slot_total_kernel<kHfW><<<1, 256, 0, st>>>(h.part.p, nb, tot);
   MDP_HIP(c, hipGetLastError());
   return mdp_read_one(c, tot, sizeof(double) * kHfW, out);
 }

@@ -358,22 +358,24 @@ struct MdpFire {
   DevBuf<double> fsave;        // a state read's energy compute leaves the forces as it found them
 };
 
-// mean-squared displacement (msd.hip): the origins of the WHOLE system by tag on every rank, so nothing has to migrate
-struct MdpMsd {
+// A measurement a context holds one of per kind (msd, rdf, profile): whether it is set up, and which setup of this process
+// it is (mdp_measure_start; mdp_*_info hands the serial out, so that a caller knows its own setup from another's)
+struct MdpMeasure {
   bool on = false;
+  long long serial = 0;
+};
+// mean-squared displacement (msd.hip): the origins of the WHOLE system by tag on every rank, so nothing has to migrate
+struct MdpMsd : MdpMeasure {
   int ntag = 0, gbit = 0;
-  long long serial = 0; // which mdp_msd_setup of this process filled x0 (mdp_msd_info)
   DevBuf<double> x0;   // [ntag][3] unwrapped origin of the atom with tag t at [t - 1]
   DevBuf<double> xu;   // [nlocal][3] unwrapped positions (mdp_md_download_unwrapped)
   DevBuf<double> part; // per-block partials, kMsdW per block, then the kMsdW sums
 };
 // pair-distance histograms (rdf.hip): a binning of its own and the counters of a read; nothing here is shared with the list
 // builders, so a read leaves the run's scratch alone
-struct MdpRdf {
-  bool on = false;
+struct MdpRdf : MdpMeasure {
   int nbin = 0, npair = 0, ntypes = 0, ntag = 0; // ntag 0: every atom is a member
   double cutoff = 0.0;
-  long long serial = 0;            // which mdp_rdf_setup of this process the tables belong to (mdp_rdf_info)
   DevBuf<unsigned char> member;    // [ntag] membership of the atom with tag t at [t - 1], the WHOLE system on every rank
   DevBuf<int> tab;                 // column masks per (type i, type j), then the i and j masks per type
   DevBuf<unsigned> key_a, key_b;   // cell of every atom, before and after the sort
@@ -385,11 +387,9 @@ struct MdpRdf {
 };
 // binned sums of m, m v and m v^2 (profile.hip): the bins and the table of a read; nothing here is read by a step, a list build,
 // msd or rdf
-struct MdpProfile {
-  bool on = false;
+struct MdpProfile : MdpMeasure {
   int ndim = 0, dim[3] = {0, 0, 0}, nbin[3] = {1, 1, 1}, gbit = 0;
   long long rows = 0;
-  long long serial = 0;            // which mdp_profile_setup of this process the bins belong to (mdp_profile_info)
   DevBuf<double> part;             // per-block maxima of |t_k|, MDP_PROFILE_W per block, then the MDP_PROFILE_W maxima
   DevBuf<unsigned long long> out;  // [rows][MDP_PROFILE_W] sums (two's complement), [rows] counts, then the column flags
 };
@@ -575,6 +575,16 @@ template <int W> __device__ __forceinline__ void mdp_slot_sum_256(const double *
   }
 #pragma unroll
   for (int k = 0; k < W; k++) out[k] = red[k][0];
+}
+// ... as a kernel of its own, launched <<<1, 256>>>: out[k] = the sum of slot k (the reads of msd.hip and heatflux.hip)
+template <int W>
+__global__ __launch_bounds__(256) void mdp_slot_total_kernel(const double *__restrict__ part, const int npart, double *__restrict__ out)
+{
+  double s[W];
+  mdp_slot_sum_256<W>(part, npart, s);
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int k = 0; k < W; k++) out[k] = s[k];
 }
 
 // The style-level displacement test of one atom (MdpStyleCheck), shared by the integrate kernel (owned atoms, flag words
@@ -991,6 +1001,38 @@ void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
 void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds
 void mdp_profile_release(mdp_ctx *c); // frees what profile.hip holds
 void mdp_heatflux_release(mdp_ctx *c); // frees what heatflux.hip holds
+// the end of an mdp_{msd,rdf,profile}_setup: the measurement is on, under a serial that is new in this process (one
+// counter for all kinds and contexts: unique per setup, and growing)
+inline void mdp_measure_start(MdpMeasure &h)
+{
+  static std::atomic<long long> serial{0};
+  h.serial = ++serial;
+  h.on = true;
+}
+// the four words of mdp_*_info: on, two words of the kind's own, the serial; all 0 while off
+inline int mdp_measure_info(const MdpMeasure &h, const long long a, const long long b, long long out[4])
+{
+  out[0] = h.on ? 1 : 0;
+  out[1] = h.on ? a : 0;
+  out[2] = h.on ? b : 0;
+  out[3] = h.on ? h.serial : 0;
+  return MDP_OK;
+}
+// mdp_*_off
+inline int mdp_measure_off(mdp_ctx *c, void (*release)(mdp_ctx *))
+{
+  if (!c) return MDP_EINVAL;
+  MDP_HIP(c, hipSetDevice(c->device));
+  release(c);
+  return MDP_OK;
+}
+// a read or a setup over a group: a mask is there, and (need_current) it covers the atoms as they are now
+inline int mdp_require_group_mask(mdp_ctx *c, const char *who, const int gbit, const bool need_current)
+{
+  if (gbit && (!c->mask_set || (need_current && c->mask_n != c->nlocal)))
+    return mdp_fail(c, MDP_ESTATE, "%s: a group is set but no mask covers the current atoms (mdp_md_set_mask)", who);
+  return MDP_OK;
+}
 // the per-atom tallies are stale from here on (a compute starts, the atoms move, are re-ordered or replaced)
 inline void mdp_tally_drop(mdp_ctx *c) { c->tally_eflag = c->tally_vflag = -1; }
 // FIRE minimiser (fire.hip), in place of the integrate kernel when c->fire.on: the half step back / zeroing and the Euler

@@ -8,11 +8,7 @@
 // agree bit for bit.  The caller divides, and on several ranks sums over the ranks first.
 #include "mdp_common.h"
 
-#include <atomic>
-
 namespace {
-
-std::atomic<long long> g_msd_serial{0}; // counts the measurements started in this process, over all contexts
 
 __global__ __launch_bounds__(256) void msd_unwrap_kernel(const DdGeom G, const int n, const double4 *__restrict__ xq,
                                                          const int *__restrict__ image, double *__restrict__ xu)
@@ -78,16 +74,6 @@ __global__ __launch_bounds__(256) void msd_partial_kernel(const DdGeom G, const 
   mdp_block_sum_256<kMsdW>(e, part);
 }
 
-__global__ __launch_bounds__(256) void msd_total_kernel(const double *__restrict__ part, const int npart,
-                                                        double *__restrict__ out)
-{
-  double s[kMsdW];
-  mdp_slot_sum_256<kMsdW>(part, npart, s);
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < kMsdW; k++) out[k] = s[k];
-}
-
 int msd_require(mdp_ctx *c, const char *who)
 {
   if (!c) return MDP_EINVAL;
@@ -135,8 +121,7 @@ int mdp_msd_setup(mdp_ctx *c, int ntag, const double *x0_by_tag, int groupbit)
                     c->dd.G.nranks);
   if (!x0_by_tag && c->nlocal != ntag)
     return mdp_fail(c, MDP_EINVAL, "mdp_msd_setup: origins from the current positions need ntag = the %d owned atoms", c->nlocal);
-  if (groupbit && !c->mask_set)
-    return mdp_fail(c, MDP_ESTATE, "mdp_msd_setup: a group is set but no mask covers the current atoms (mdp_md_set_mask)");
+  MDP_TRY(mdp_require_group_mask(c, "mdp_msd_setup", groupbit, false));
   MdpMsd &h = c->msd;
   hipStream_t st = c->stream;
   MDP_HIP(c, h.x0.reserve((size_t) 3 * ntag + 3));
@@ -150,8 +135,7 @@ int mdp_msd_setup(mdp_ctx *c, int ntag, const double *x0_by_tag, int groupbit)
   MDP_HIP(c, hipStreamSynchronize(st)); // the caller's array may change after return
   h.ntag = ntag;
   h.gbit = groupbit;
-  h.serial = ++g_msd_serial;
-  h.on = true;
+  mdp_measure_start(h);
   return MDP_OK;
 }
 
@@ -161,8 +145,7 @@ int mdp_msd_sums(mdp_ctx *c, const double *shift, double out[8])
   if (!out) return MDP_EINVAL;
   MdpMsd &h = c->msd;
   if (!h.on) return mdp_fail(c, MDP_ESTATE, "mdp_msd_setup not called");
-  if (h.gbit && (!c->mask_set || c->mask_n != c->nlocal))
-    return mdp_fail(c, MDP_ESTATE, "mdp_msd_sums: a group is set but no mask covers the current atoms (mdp_md_set_mask)");
+  MDP_TRY(mdp_require_group_mask(c, "mdp_msd_sums", h.gbit, true));
   hipStream_t st = c->stream;
   const int n = c->nlocal, nb = n ? nblk(n) : 0;
   MDP_HIP(c, h.part.reserve((size_t) kMsdW * (nb + 1)));
@@ -171,7 +154,7 @@ int mdp_msd_sums(mdp_ctx *c, const double *shift, double out[8])
     msd_partial_kernel<<<nb, 256, 0, st>>>(c->dd.G, n, h.ntag, h.gbit, c->xq.p, c->image.p, c->tag.p,
                                            h.gbit ? c->mask.p : nullptr, c->rmass.p, h.x0.p, shift ? shift[0] : 0.0,
                                            shift ? shift[1] : 0.0, shift ? shift[2] : 0.0, h.part.p);
-  msd_total_kernel<<<1, 256, 0, st>>>(h.part.p, nb, tot);
+  mdp_slot_total_kernel<kMsdW><<<1, 256, 0, st>>>(h.part.p, nb, tot);
   MDP_HIP(c, hipGetLastError());
   double s[kMsdW];
   MDP_TRY(mdp_read_one(c, tot, sizeof s, s));
@@ -185,20 +168,9 @@ int mdp_msd_sums(mdp_ctx *c, const double *shift, double out[8])
 int mdp_msd_info(mdp_ctx *c, long long out[4])
 {
   if (!c || !out) return MDP_EINVAL;
-  const MdpMsd &h = c->msd;
-  out[0] = h.on ? 1 : 0;
-  out[1] = h.on ? h.ntag : 0;
-  out[2] = h.on ? h.gbit : 0;
-  out[3] = h.on ? h.serial : 0;
-  return MDP_OK;
+  return mdp_measure_info(c->msd, c->msd.ntag, c->msd.gbit, out);
 }
 
-int mdp_msd_off(mdp_ctx *c)
-{
-  if (!c) return MDP_EINVAL;
-  MDP_HIP(c, hipSetDevice(c->device));
-  mdp_msd_release(c);
-  return MDP_OK;
-}
+int mdp_msd_off(mdp_ctx *c) { return mdp_measure_off(c, mdp_msd_release); }
 
 } // extern "C"

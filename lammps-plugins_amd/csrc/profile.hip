@@ -10,12 +10,9 @@
 // msd or rdf reads is written.
 #include "mdp_common.h"
 
-#include <atomic>
 #include <cmath>
 
 namespace {
-
-std::atomic<long long> g_profile_serial{0}; // counts the measurements started in this process, over all contexts
 
 constexpr int kProfW = MDP_PROFILE_W;
 constexpr int kProfLdsWords = 4096; // rows * kProfW 64-bit sums a workgroup keeps in LDS (32 KB), with rows 32-bit counts
@@ -178,8 +175,7 @@ int profile_open(mdp_ctx *c, const char *who)
   MDP_TRY(profile_require(c, who));
   const MdpProfile &h = c->profile;
   if (!h.on) return mdp_fail(c, MDP_ESTATE, "mdp_profile_setup not called");
-  if (h.gbit && (!c->mask_set || c->mask_n != c->nlocal))
-    return mdp_fail(c, MDP_ESTATE, "%s: a group is set but no mask covers the current atoms (mdp_md_set_mask)", who);
+  MDP_TRY(mdp_require_group_mask(c, who, h.gbit, true));
   return mdp_md_flush_final(c);
 }
 
@@ -211,8 +207,7 @@ int mdp_profile_setup(mdp_ctx *c, int ndim, const int *dim, const int *nbin, int
     if (rows > MDP_PROFILE_MAXBINS)
       return mdp_fail(c, MDP_EINVAL, "mdp_profile_setup: more than %d rows", MDP_PROFILE_MAXBINS);
   }
-  if (groupbit && !c->mask_set)
-    return mdp_fail(c, MDP_ESTATE, "mdp_profile_setup: a group is set but no mask covers the current atoms (mdp_md_set_mask)");
+  MDP_TRY(mdp_require_group_mask(c, "mdp_profile_setup", groupbit, false));
   MdpProfile &h = c->profile;
   MDP_HIP(c, h.out.reserve((size_t) rows * (kProfW + 1) + 1));
   h.ndim = ndim;
@@ -222,8 +217,7 @@ int mdp_profile_setup(mdp_ctx *c, int ndim, const int *dim, const int *nbin, int
   }
   h.rows = rows;
   h.gbit = groupbit;
-  h.serial = ++g_profile_serial;
-  h.on = true;
+  mdp_measure_start(h);
   return MDP_OK;
 }
 
@@ -301,20 +295,9 @@ int mdp_profile_sums(mdp_ctx *c, const int exponent[MDP_PROFILE_W], long long *c
 int mdp_profile_info(mdp_ctx *c, long long out[4])
 {
   if (!c || !out) return MDP_EINVAL;
-  const MdpProfile &h = c->profile;
-  out[0] = h.on ? 1 : 0;
-  out[1] = h.on ? h.rows : 0;
-  out[2] = h.on ? h.ndim : 0;
-  out[3] = h.on ? h.serial : 0;
-  return MDP_OK;
+  return mdp_measure_info(c->profile, c->profile.rows, c->profile.ndim, out);
 }
 
-int mdp_profile_off(mdp_ctx *c)
-{
-  if (!c) return MDP_EINVAL;
-  MDP_HIP(c, hipSetDevice(c->device));
-  mdp_profile_release(c);
-  return MDP_OK;
-}
+int mdp_profile_off(mdp_ctx *c) { return mdp_measure_off(c, mdp_profile_release); }
 
 } // extern "C"

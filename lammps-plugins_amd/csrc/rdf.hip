@@ -11,11 +11,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include <atomic>
-
 namespace {
-
-std::atomic<long long> g_rdf_serial{0}; // counts the measurements started in this process, over all contexts
 
 constexpr int kRdfTypes = 16;          // type codes 0 .. 15: 0 = not a member, t = LAMMPS type t
 constexpr int kRdfOwned = 32;          // code bit: an owned atom (a lane that counts)
@@ -285,8 +281,7 @@ int mdp_rdf_setup(mdp_ctx *c, int nbin, double cutoff, int npair, const int *ilo
   h.npair = npair;
   h.ntypes = ntypes;
   h.cutoff = cutoff;
-  h.serial = ++g_rdf_serial;
-  h.on = true;
+  mdp_measure_start(h);
   return MDP_OK;
 }
 
@@ -365,20 +360,9 @@ int mdp_rdf_counts(mdp_ctx *c, long long *hist, long long *icount, long long *jc
 int mdp_rdf_info(mdp_ctx *c, long long out[4])
 {
   if (!c || !out) return MDP_EINVAL;
-  const MdpRdf &h = c->rdf;
-  out[0] = h.on ? 1 : 0;
-  out[1] = h.on ? h.nbin : 0;
-  out[2] = h.on ? h.npair : 0;
-  out[3] = h.on ? h.serial : 0;
-  return MDP_OK;
+  return mdp_measure_info(c->rdf, c->rdf.nbin, c->rdf.npair, out);
 }
 
-int mdp_rdf_off(mdp_ctx *c)
-{
-  if (!c) return MDP_EINVAL;
-  MDP_HIP(c, hipSetDevice(c->device));
-  mdp_rdf_release(c);
-  return MDP_OK;
-}
+int mdp_rdf_off(mdp_ctx *c) { return mdp_measure_off(c, mdp_rdf_release); }
 
 } // extern "C"

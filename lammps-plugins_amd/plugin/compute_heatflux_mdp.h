@@ -21,13 +21,11 @@ ComputeStyle(heatflux/mdp,ComputeHeatFluxMDP);
 #ifndef MDP_COMPUTE_HEATFLUX_MDP_H
 #define MDP_COMPUTE_HEATFLUX_MDP_H
 
-#include "compute.h"
-
-#include "mdpair_hip.h"
+#include "compute_mdp.h"
 
 namespace LAMMPS_NS {
 
-class ComputeHeatFluxMDP : public Compute {
+class ComputeHeatFluxMDP : public ComputeMDP {
  public:
   ComputeHeatFluxMDP(class LAMMPS *, int, char **);
   ~ComputeHeatFluxMDP() override;
@@ -36,8 +34,6 @@ class ComputeHeatFluxMDP : public Compute {
 
  protected:
   double out6[6];
-
-  class Fix *integrator() const;
 };
 
 }    // namespace LAMMPS_NS

@@ -1,13 +1,12 @@
 /* ------------------------------------------------------------------------------------------------
    compute msd/mdp -- see compute_msd_mdp.h.  What runs where:
-     constructor        the arguments (refused here: an unknown or empty group, average yes, an unknown keyword); the
-                        origins: a zeroed [natoms][3] array filled at this rank's tags with x + h . image of the host's
-                        atoms, summed over the ranks; the group's centre of mass there
-     init()             the one fix nve/mdp (or nvt/mdp) found through modify, in bricks mode (refused: none, the
-                        host-linked mode -- there the host keeps atom->image itself, and compute msd is right)
-     compute_vector()   the run's context through Fix::extract("mdp_steps_ctx"); the origins go up once per context
-                        (mdp_msd_setup; mdp_msd_info tells whether they are still there); mdp_msd_sums on this rank's
+     constructor        the arguments (refused here: average yes, an unknown keyword); the origins: a zeroed [natoms][3]
+                        array filled at this rank's tags with x + h . image of the host's atoms, summed over the ranks;
+                        the group's centre of mass there
+     init()             bricks mode (the host-linked mode: there the host keeps atom->image itself, and compute msd is right)
+     compute_vector()   the origins go up once per context, not once per run (mdp_msd_setup); mdp_msd_sums on this rank's
                         brick -- twice with com yes: the mass sums, then the pass with the shift -- and MPI_Allreduce
+   The group refusals, the integrator, the run's context and the once-per-context protocol: compute_mdp.h.
 -------------------------------------------------------------------------------------------------- */
 #include "compute_msd_mdp.h"
 #include "mdp_args.h"
@@ -16,25 +15,16 @@
 #include "comm.h"
 #include "domain.h"
 #include "error.h"
-#include "fix.h"
-#include "group.h"
-#include "modify.h"
 #include "update.h"
 
-#include <cstring>
 #include <string>
 
 using namespace LAMMPS_NS;
 
 ComputeMSDMDP::ComputeMSDMDP(LAMMPS *lmp, int narg, char **arg)
-    : Compute(lmp, narg, arg), comflag(0), nall(0), sent_to(nullptr), sent_serial(0)
+    : ComputeMDP(lmp, narg, arg, "msd/mdp", "there is no atom to measure"), comflag(0), nall(0)
 {
-  const std::string head = "Illegal compute msd/mdp command: ";
   if (narg < 3) error->all(FLERR, head + "compute ID GROUP msd/mdp [com yes|no]");
-  if (igroup < 0)
-    error->all(FLERR, std::string("Compute msd/mdp requires group all or a group defined by the group command: could not find compute group ID ") + arg[1]);
-  if (igroup > 0 && group->count(igroup) == 0)
-    error->all(FLERR, std::string("Compute msd/mdp: group ") + arg[1] + " is empty: there is no atom to measure");
   for (int k = 3; k < narg; k += 2) {
     const std::string key = arg[k];
     if (key != "com" && key != "average") error->all(FLERR, head + "unknown keyword " + key);
@@ -80,47 +70,15 @@ ComputeMSDMDP::ComputeMSDMDP(LAMMPS *lmp, int narg, char **arg)
 
 ComputeMSDMDP::~ComputeMSDMDP() {}
 
-void ComputeMSDMDP::fail(mdp_ctx *c) { error->one(FLERR, std::string("Compute msd/mdp: ") + (c ? mdp_last_error(c) : "no device context")); }
-
-// the one time integrator of this plugin family: fix nve/mdp, or fix nvt/mdp that is built on it
-Fix *ComputeMSDMDP::integrator() const
-{
-  Fix *found = nullptr;
-  for (int i = 0; i < modify->nfix; i++) {
-    Fix *f = modify->fix[i];
-    if (strcmp(f->style, "nve/mdp") != 0 && strcmp(f->style, "nvt/mdp") != 0) continue;
-    if (found) error->all(FLERR, std::string("Compute msd/mdp: fixes ") + found->id + " and " + f->id + " both integrate on the device; it reads one run's context");
-    found = f;
-  }
-  return found;
-}
-
-void ComputeMSDMDP::init()
-{
-  Fix *nve = integrator();
-  if (!nve) error->all(FLERR, "Compute msd/mdp requires fix nve/mdp (or fix nvt/mdp) with bricks yes as the time integrator");
-  int dim = 0;
-  const int *bricks = static_cast<int *>(nve->extract("mdp_bricks", dim));
-  if (!bricks || !nve->extract("mdp_steps_ctx", dim)) error->all(FLERR, std::string("Compute msd/mdp: fix ") + nve->id + " does not expose its run's context");
-  if (!*bricks)
-    error->all(FLERR, std::string("Compute msd/mdp: fix ") + nve->id + " runs in the host-linked mode, where the host keeps atom->image itself: use compute msd (or run the fix with bricks yes)");
-}
+void ComputeMSDMDP::init() { require_bricks("where the host keeps atom->image itself: use compute msd (or run the fix with bricks yes)"); }
 
 void ComputeMSDMDP::compute_vector()
 {
   invoked_vector = update->ntimestep;
-  Fix *nve = integrator();
-  int dim = 0;
-  mdp_ctx **slot = nve ? static_cast<mdp_ctx **>(nve->extract("mdp_steps_ctx", dim)) : nullptr;
-  mdp_ctx *c = slot ? *slot : nullptr;
-  if (!c) error->all(FLERR, "Compute msd/mdp: no run of fix nve/mdp is under way; the atoms are on the device only during one");
-  long long info[4] = {0, 0, 0, 0};
-  if (mdp_msd_info(c, info) != MDP_OK) fail(c);
-  if (c != sent_to || !info[0] || info[3] != sent_serial) { // once per context, unless another measurement took its place
-    if (mdp_msd_setup(c, (int) nall, x0.data(), igroup > 0 ? groupbit : 0) != MDP_OK) fail(c);
-    if (mdp_msd_info(c, info) != MDP_OK) fail(c);
-    sent_to = c;
-    sent_serial = info[3];
+  mdp_ctx *c = run_context();
+  if (!sent(c, mdp_msd_info)) {
+    if (mdp_msd_setup(c, (int) nall, x0.data(), gbit()) != MDP_OK) fail(c);
+    record(c, mdp_msd_info);
   }
   double s[8], tot[8];
   const double *shift = nullptr;

@@ -7,7 +7,7 @@
    x + h . image.  LAMMPS' own compute msd cannot serve a brick run: its origins are a host per-atom array, and the
    brick's atoms come back in another order, on other ranks.  Here the origins of ALL atoms are kept by tag (recorded at
    construction from the host's atom->x and atom->image, summed over the ranks) and uploaded once to the context the
-   run's steps go through (Fix::extract("mdp_steps_ctx")); an evaluation is one pass over the brick's atoms on the device
+   run's steps go through (compute_mdp.h); an evaluation is one pass over the brick's atoms on the device
    (mdp_msd_sums) and one sum over the ranks.  com yes: the displacement of the group's centre of mass is taken out.
    A context holds one measurement: a second compute msd/mdp in the same input makes both upload their origins again at
    every evaluation (24 bytes per atom each; the values stay right).
@@ -21,15 +21,11 @@ ComputeStyle(msd/mdp,ComputeMSDMDP);
 #ifndef MDP_COMPUTE_MSD_MDP_H
 #define MDP_COMPUTE_MSD_MDP_H
 
-#include "compute.h"
-
-#include "mdpair_hip.h"
-
-#include <vector>
+#include "compute_mdp.h"
 
 namespace LAMMPS_NS {
 
-class ComputeMSDMDP : public Compute {
+class ComputeMSDMDP : public ComputeMDP {
  public:
   ComputeMSDMDP(class LAMMPS *, int, char **);
   ~ComputeMSDMDP() override;
@@ -42,11 +38,6 @@ class ComputeMSDMDP : public Compute {
   std::vector<double> x0;      // [nall][3] unwrapped positions at construction, the same on every rank
   double cm0[3];               // the group's centre of mass there
   double out4[4];
-  mdp_ctx *sent_to;            // the context that holds the origins, and which of its measurements is ours (mdp_msd_info)
-  long long sent_serial;
-
-  class Fix *integrator() const;
-  void fail(mdp_ctx *c);
 };
 
 }    // namespace LAMMPS_NS

@@ -2,15 +2,14 @@
    compute profile/mdp -- see compute_profile_mdp.h.  What runs where:
      constructor        the arguments, before any device is touched (refused here: no dimension, a dimension named twice, N
                         that is not a whole number >= 1, more than MDP_PROFILE_MAXBINS rows, an unknown keyword, a bad com
-                        value, an unknown or empty group)
-     init()             the one fix nve/mdp (or nvt/mdp) found through modify, in bricks mode (refused: none, the
-                        host-linked mode -- there the host's atom->x and atom->v are current, and the chunk computes are right)
-     compute_array()    the run's context through Fix::extract("mdp_steps_ctx"); the bins go up once per context
-                        (mdp_profile_setup; mdp_profile_info tells whether they are still there); this rank's range, the
-                        global maximum, the exponents (mdp_profile_exponent), this rank's integer table, its exact sum
-                        over the ranks, the normalisation.  The mini-host's MPI subset has one reduction, MPI_SUM of
-                        MPI_DOUBLE: the maximum is taken over per-rank slots of a summed vector of zeros, and a 64-bit
-                        integer travels as q >> 31 and q & (2^31 - 1), whole numbers whose sums stay below 2^53.
+                        value)
+     init()             bricks mode (the host-linked mode: there the host's atom->x and atom->v are current, and the chunk
+                        computes are right)
+     compute_array()    the bins go up once per context and run (mdp_profile_setup); this rank's range, the global
+                        maximum, the exponents (mdp_profile_exponent), this rank's integer table, its exact sum over the
+                        ranks (sum_whole), the normalisation.  The mini-host's MPI subset has one reduction, MPI_SUM of
+                        MPI_DOUBLE: the maximum is taken over per-rank slots of a summed vector of zeros.
+   The group refusals, the integrator, the run's context, the once-per-context protocol and the exact sum: compute_mdp.h.
 -------------------------------------------------------------------------------------------------- */
 #include "compute_profile_mdp.h"
 #include "mdp_args.h"
@@ -19,27 +18,18 @@
 #include "comm.h"
 #include "domain.h"
 #include "error.h"
-#include "fix.h"
 #include "force.h"
-#include "group.h"
-#include "modify.h"
 #include "update.h"
 
 #include <cmath>
-#include <cstring>
 #include <string>
 
 using namespace LAMMPS_NS;
 
 ComputeProfileMDP::ComputeProfileMDP(LAMMPS *lmp, int narg, char **arg)
-    : Compute(lmp, narg, arg), ndim(0), comflag(0), nrows(1), sent_to(nullptr), sent_serial(0)
+    : ComputeMDP(lmp, narg, arg, "profile/mdp", "there is no atom to bin"), ndim(0), comflag(0), nrows(1)
 {
-  const std::string head = "Illegal compute profile/mdp command: ";
   const std::string usage = "compute ID GROUP profile/mdp dim N [dim N [dim N]] [com yes|no], dim = x | y | z";
-  if (igroup < 0)
-    error->all(FLERR, std::string("Compute profile/mdp requires group all or a group defined by the group command: could not find compute group ID ") + arg[1]);
-  if (igroup > 0 && group->count(igroup) == 0)
-    error->all(FLERR, std::string("Compute profile/mdp: group ") + arg[1] + " is empty: there is no atom to bin");
   for (int k = 0; k < 3; k++) {
     dim[k] = 0;
     nbin[k] = 1;
@@ -70,60 +60,24 @@ ComputeProfileMDP::ComputeProfileMDP(LAMMPS *lmp, int narg, char **arg)
   if (ndim == 0) error->all(FLERR, head + "no dimension: " + usage);
   if (atom->natoms < 1) error->all(FLERR, "Compute profile/mdp: there are no atoms");
 
-  array_flag = 1;
-  extarray = 0;
-  size_array_rows = (int) nrows;
-  size_array_cols = ndim + 7;
-  values.assign((size_t) nrows * size_array_cols, 0.0);
-  rows.resize((size_t) nrows);
-  for (long long b = 0; b < nrows; b++) rows[(size_t) b] = values.data() + (size_t) b * size_array_cols;
-  array = rows.data();
+  global_array(nrows, ndim + 7);
 }
 
 ComputeProfileMDP::~ComputeProfileMDP() {}
 
-void ComputeProfileMDP::fail(mdp_ctx *c) { error->one(FLERR, std::string("Compute profile/mdp: ") + (c ? mdp_last_error(c) : "no device context")); }
-
-// the one time integrator of this plugin family: fix nve/mdp, or fix nvt/mdp that is built on it
-Fix *ComputeProfileMDP::integrator() const
-{
-  Fix *found = nullptr;
-  for (int i = 0; i < modify->nfix; i++) {
-    Fix *f = modify->fix[i];
-    if (strcmp(f->style, "nve/mdp") != 0 && strcmp(f->style, "nvt/mdp") != 0) continue;
-    if (found) error->all(FLERR, std::string("Compute profile/mdp: fixes ") + found->id + " and " + f->id + " both integrate on the device; it reads one run's context");
-    found = f;
-  }
-  return found;
-}
-
 void ComputeProfileMDP::init()
 {
-  Fix *nve = integrator();
-  if (!nve) error->all(FLERR, "Compute profile/mdp requires fix nve/mdp (or fix nvt/mdp) with bricks yes as the time integrator");
-  int dm = 0;
-  const int *bricks = static_cast<int *>(nve->extract("mdp_bricks", dm));
-  if (!bricks || !nve->extract("mdp_steps_ctx", dm)) error->all(FLERR, std::string("Compute profile/mdp: fix ") + nve->id + " does not expose its run's context");
-  if (!*bricks)
-    error->all(FLERR, std::string("Compute profile/mdp: fix ") + nve->id + " runs in the host-linked mode, where the host's atom->x and atom->v are current: use compute chunk/atom with fix ave/chunk (or run the fix with bricks yes)");
-  sent_to = nullptr; // a new run may bring a new context: the bins go up again
+  require_bricks("where the host's atom->x and atom->v are current: use compute chunk/atom with fix ave/chunk (or run the fix with bricks yes)");
+  forget(); // a new run may bring a new context: the bins go up again
 }
 
 void ComputeProfileMDP::compute_array()
 {
   invoked_array = update->ntimestep;
-  Fix *nve = integrator();
-  int dm = 0;
-  mdp_ctx **slot = nve ? static_cast<mdp_ctx **>(nve->extract("mdp_steps_ctx", dm)) : nullptr;
-  mdp_ctx *c = slot ? *slot : nullptr;
-  if (!c) error->all(FLERR, "Compute profile/mdp: no run of fix nve/mdp is under way; the atoms are on the device only during one");
-  long long info[4] = {0, 0, 0, 0};
-  if (mdp_profile_info(c, info) != MDP_OK) fail(c);
-  if (c != sent_to || !info[0] || info[3] != sent_serial) { // once per context, unless another measurement took its place
-    if (mdp_profile_setup(c, ndim, dim, nbin, igroup > 0 ? groupbit : 0) != MDP_OK) fail(c);
-    if (mdp_profile_info(c, info) != MDP_OK) fail(c);
-    sent_to = c;
-    sent_serial = info[3];
+  mdp_ctx *c = run_context();
+  if (!sent(c, mdp_profile_info)) {
+    if (mdp_profile_setup(c, ndim, dim, nbin, gbit()) != MDP_OK) fail(c);
+    record(c, mdp_profile_info);
   }
   constexpr int W = MDP_PROFILE_W;
   const int me = comm->me, np = comm->nprocs;
@@ -141,29 +95,12 @@ void ComputeProfileMDP::compute_array()
     ex[k] = mdp_profile_exponent(r, (long long) atom->natoms);
   }
 
-  // this rank's integer table, then its exact sum over the ranks: counts as doubles, a 64-bit sum as its two halves
+  // this rank's integer table, then its exact sum over the ranks
   const size_t nr = (size_t) nrows, ns = nr * W;
   std::vector<long long> count(nr, 0), sums(ns, 0);
   if (mdp_profile_sums(c, ex, count.data(), sums.data()) != MDP_OK) fail(c);
-  const long long lomask = (1ll << 31) - 1;
-  const size_t piece = 65536; // the reduction goes in pieces: a megabyte of transient buffers whatever the number of rows
-  std::vector<double> mine(3 * piece), all(3 * piece);
-  for (size_t at = 0; at < ns; at += piece) {
-    const size_t len = ns - at < piece ? ns - at : piece;
-    for (size_t k = 0; k < len; k++) {
-      const long long q = sums[at + k];
-      mine[k] = (double) (q >> 31);
-      mine[len + k] = (double) (q & lomask);
-    }
-    MPI_Allreduce(mine.data(), all.data(), (int) (2 * len), MPI_DOUBLE, MPI_SUM, world);
-    for (size_t k = 0; k < len; k++) sums[at + k] = (llrint(all[k]) << 31) + llrint(all[len + k]);
-  }
-  for (size_t at = 0; at < nr; at += piece) {
-    const size_t len = nr - at < piece ? nr - at : piece;
-    for (size_t k = 0; k < len; k++) mine[k] = (double) count[at + k];
-    MPI_Allreduce(mine.data(), all.data(), (int) len, MPI_DOUBLE, MPI_SUM, world);
-    for (size_t k = 0; k < len; k++) count[at + k] = llrint(all[k]);
-  }
+  sum_whole(sums.data(), ns);
+  sum_whole(count.data(), nr);
 
   // the normalisation (host/resident.py profile_normalise is the same arithmetic)
   const double vbin = domain->xprd * domain->yprd * domain->zprd / (double) nrows;

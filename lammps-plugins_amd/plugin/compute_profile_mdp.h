@@ -12,7 +12,7 @@
    The bins span the box in reduced units, triclinic included; a periodic dimension wraps, a non-periodic one counts an
    atom beyond the box in its edge bin.  LAMMPS' own chunk computes read the host's atom->x and atom->v, which are stale
    while a brick run is under way.  Here the sums are formed on the device (mdp_profile_* through
-   Fix::extract("mdp_steps_ctx")) as 64-bit integers with one power-of-two scale per column that every rank derives from the
+   the run's context, compute_mdp.h) as 64-bit integers with one power-of-two scale per column that every rank derives from the
    global range: the table does not depend on the decomposition.  Membership of the group goes with the atoms (atom->mask
    on the device).  A context holds one measurement: two compute profile/mdp in one input make each other send their bins
    again at every evaluation (a few words; the values stay right).
@@ -26,15 +26,11 @@ ComputeStyle(profile/mdp,ComputeProfileMDP);
 #ifndef MDP_COMPUTE_PROFILE_MDP_H
 #define MDP_COMPUTE_PROFILE_MDP_H
 
-#include "compute.h"
-
-#include "mdpair_hip.h"
-
-#include <vector>
+#include "compute_mdp.h"
 
 namespace LAMMPS_NS {
 
-class ComputeProfileMDP : public Compute {
+class ComputeProfileMDP : public ComputeMDP {
  public:
   ComputeProfileMDP(class LAMMPS *, int, char **);
   ~ComputeProfileMDP() override;
@@ -44,14 +40,7 @@ class ComputeProfileMDP : public Compute {
  protected:
   int ndim, comflag;
   int dim[3], nbin[3];                  // the named dimensions in the order given, and their bins
-  long long nrows;
-  std::vector<double> values;           // [nrows][ndim + 7]
-  std::vector<double *> rows;
-  mdp_ctx *sent_to;                     // the context that holds our bins, and which of its measurements is ours (mdp_profile_info)
-  long long sent_serial;
-
-  class Fix *integrator() const;
-  void fail(mdp_ctx *c);
+  long long nrows;                      // the array is [nrows][ndim + 7]
 };
 
 }    // namespace LAMMPS_NS

@@ -7,8 +7,8 @@
    type pair, as compute rdf lays them out (a type argument is N, *, N*, *M or N*M; without pairs one column pair of all
    types with all types).  LAMMPS' own compute rdf cannot serve a brick run: it walks a host neighbour list of host
    positions, and the host's atom->x is stale while the run is under way.  Here the pairs are counted on the device from
-   the brick's current atoms and ghosts (mdp_rdf_counts through Fix::extract("mdp_steps_ctx")) in integers, summed over
-   the ranks as doubles (whole numbers below 2^53: exact), and normalised with the box of the current step.  The default cutoff, and the largest one, is the pair style's
+   the brick's current atoms and ghosts (mdp_rdf_counts through the run's context, compute_mdp.h) in integers, summed
+   exactly over the ranks, and normalised with the box of the current step.  The default cutoff, and the largest one, is the pair style's
    cutforce: the ghost shell is cutforce + skin wide as of the last reneighbouring.  Membership of the group is taken at
    init(), by tag.  A context holds one measurement: two compute rdf/mdp in one input make each other send their setup
    again at every evaluation (a few hundred bytes and the member table; the values stay right).
@@ -22,15 +22,11 @@ ComputeStyle(rdf/mdp,ComputeRDFMDP);
 #ifndef MDP_COMPUTE_RDF_MDP_H
 #define MDP_COMPUTE_RDF_MDP_H
 
-#include "compute.h"
-
-#include "mdpair_hip.h"
-
-#include <vector>
+#include "compute_mdp.h"
 
 namespace LAMMPS_NS {
 
-class ComputeRDFMDP : public Compute {
+class ComputeRDFMDP : public ComputeMDP {
  public:
   ComputeRDFMDP(class LAMMPS *, int, char **);
   ~ComputeRDFMDP() override;
@@ -42,13 +38,6 @@ class ComputeRDFMDP : public Compute {
   double cutoff_user, cutoff;           // cutoff: the one in force (init())
   std::vector<int> ilo, ihi, jlo, jhi;  // [npairs] inclusive type ranges
   std::vector<unsigned char> member;    // [natoms] membership by tag - 1, the same on every rank; empty for group all
-  std::vector<double> values;           // [nbin][1 + 2 npairs]
-  std::vector<double *> rows;
-  mdp_ctx *sent_to;                     // the context that holds our setup, and which of its measurements is ours (mdp_rdf_info)
-  long long sent_serial;
-
-  class Fix *integrator() const;
-  void fail(mdp_ctx *c);
 };
 
 }    // namespace LAMMPS_NS

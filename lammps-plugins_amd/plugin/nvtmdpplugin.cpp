@@ -1,26 +1,12 @@
 // `plugin load nvtmdpplugin.so`: registers fix nvt/mdp (fix_nvt_mdp.h), the device thermostat for the pair styles of
-// rebomosplugin.so and aeamplugin.so.  A plugin file of its own, so that those two keep registering their two styles.
-#include "lammpsplugin.h"
-#include "version.h"
+// rebomosplugin.so and aeamplugin.so.
+#include "mdp_register.h"
 
 #include "fix_nvt_mdp.h"
 
-namespace {
-void *make_fix_nvt_mdp(void *lmp, int narg, char **arg)
-{
-  return new LAMMPS_NS::FixNVTMDP(static_cast<LAMMPS_NS::LAMMPS *>(lmp), narg, arg);
-}
-}    // namespace
+using namespace LAMMPS_NS;
 
 extern "C" void lammpsplugin_init(void *lmp, void *handle, void *regfunc)
 {
-  lammpsplugin_t desc;
-  desc.version = LAMMPS_VERSION;
-  desc.style = "fix";
-  desc.name = "nvt/mdp";
-  desc.info = "Nose-Hoover chain NVT on the device for the MI355X pair styles v1.0";
-  desc.author = "lammps-plugins_amd";
-  desc.creator.v2 = &make_fix_nvt_mdp;
-  desc.handle = handle;
-  reinterpret_cast<lammpsplugin_regfunc>(regfunc)(&desc, lmp);
+  mdp_register(lmp, handle, regfunc, "fix", "nvt/mdp", "Nose-Hoover chain NVT on the device for the MI355X pair styles v1.0", mdp_make3<FixNVTMDP>);
 }

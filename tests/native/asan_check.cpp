@@ -3,6 +3,7 @@
 //   * csrc/potfile.cpp: both potential-file front ends on the bundled files and on damaged copies
 //   * oracle/*.c: readers and one full compute() each on a small isolated cluster (every tally enabled)
 //   * cross-check: the product's table builder and the oracle's produce the same numbers (bit for bit)
+//   * plugin/mdp_whole_sum.h: the split and join behind the computes' exact sum over ranks, negative values included
 // Built and run by `make -C lammps-plugins_amd asan-check`; exits non-zero on any mismatch or sanitizer report.
 #include <cmath>
 #include <cstdio>
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "aeam_oracle.h"
+#include "mdp_whole_sum.h"
 #include "mdpair_hip.h"
 #include "rebomos_oracle.h"
 
@@ -199,6 +201,38 @@ int main(int argc, char **argv)
       for (int d = 0; d < 3; d++) fs[d] += f[3 * i + d];
     CHECK(rc == 0 && std::isfinite(eng) && eng < 0, "aeam oracle compute failed (rc %d, E %g)", rc, eng);
     CHECK(fabs(fs[0]) + fabs(fs[1]) + fabs(fs[2]) < 1e-9, "aeam net force %g %g %g", fs[0], fs[1], fs[2]);
+  }
+
+  // ---- the exact sum over ranks: a 64-bit integer travels as two whole-number doubles and comes back; 8 "ranks" of signed
+  // values are summed half by half as MPI_SUM of MPI_DOUBLE would, and joined (UBSan: no shift of a negative value)
+  {
+    using LAMMPS_NS::mdp_whole_join;
+    using LAMMPS_NS::mdp_whole_split;
+    const long long edge[6] = {0, 1, (1ll << 31) - 1, 1ll << 31, (1ll << 53) - 1, 1ll << 61};
+    for (int k = 0; k < 6; k++)
+      for (int sign = 1; sign >= -1; sign -= 2) {
+        const long long q = sign * edge[k];
+        double hi, lo;
+        mdp_whole_split(q, hi, lo);
+        CHECK(hi == floor(hi) && lo == floor(lo) && lo >= 0.0 && lo < 2147483648.0, "split of %lld: halves %g %g", q, hi, lo);
+        CHECK(mdp_whole_join(hi, lo) == q, "join(split(%lld)) = %lld", q, mdp_whole_join(hi, lo));
+      }
+    unsigned long long rng = 0x9E3779B97F4A7C15ull;
+    auto next = [&rng]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return rng; };
+    for (int trial = 0; trial < 1000; trial++) {
+      const int bits = 1 + (int) (next() % 59); // |q| < 2^59: the sum of 8 stays below 2^62
+      long long sum = 0;
+      double his = 0.0, los = 0.0;
+      for (int r = 0; r < 8; r++) {
+        const long long mag = (long long) (next() & ((1ull << bits) - 1)), q = next() & 1 ? -mag : mag;
+        double hi, lo;
+        mdp_whole_split(q, hi, lo);
+        sum += q;
+        his += hi;
+        los += lo;
+      }
+      CHECK(mdp_whole_join(his, los) == sum, "trial %d: the joined halves give %lld, the integer sum is %lld", trial, mdp_whole_join(his, los), sum);
+    }
   }
   aeam_oracle_free(&T);
   if (F) mdp_aeam_file_free(F);
