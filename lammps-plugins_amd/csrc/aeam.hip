@@ -194,13 +194,7 @@ __device__ __forceinline__ double rsqrt_n1(double x)
   return fma(0.5 * y, e, y);
 }
 
-constexpr int kTile = 16; // clusters per tile (= MDP_TILE of rebomos.hip)
-
-__device__ __forceinline__ int xcd_contiguous(const int b, const int n)
-{
-  const int q = n >> 3, r = n & 7, xcd = b & 7, idx = b >> 3;
-  return xcd * q + (xcd < r ? xcd : r) + idx;
-}
+constexpr int kTile = MDP_TILE; // clusters per tile
 
 // parameters of the visit (i = cluster atom of type ta, j of type TJ), or transposed (i = j's type, j = ta)
 struct TilePar {
@@ -1503,9 +1497,7 @@ int mdp_aeam_prepare(mdp_ctx *c)
   c->aeam_ang_remote = false;
   c->aeam_phase = 0;
   c->f_prezeroed = c->f_zero_remote_due = false; // (the atom arrays were rebuilt or re-ordered)
-  const char *e = getenv("MDP_AEAM_TILE");
-  // (tile kernels: up to MDP_AEAM_MAXT types -- their parameter block lives in the kernel arguments / in LDS)
-  if ((c->md || c->aeam_device_lists) && c->nlocal > 0 && !(e && atoi(e) == 0) && c->aeam.ntypes <= MDP_AEAM_MAXT) {
+  if (aeam_wants_tiles(c) && c->nlocal > 0) {
     double cutsq[4];
     aeam_class_cuts(c, cutsq); // either visit of the pair may need it
     for (int k = 0; k < 4; k++) cutsq[k] = (cutsq[k] + c->cfg.skin) * (cutsq[k] + c->cfg.skin);
@@ -1631,9 +1623,10 @@ static int aeam_ptile_launch(mdp_ctx *c, const int t_begin, const int t_end, boo
   P.tu = c->tu.p;
   P.tile_nu = c->tile_nu.p;
   P.lj_off = c->lj_off.p;
-  P.lj_len = c->prune_valid ? c->lj_len_in.p : nullptr;
-  P.lj_split = c->prune_valid ? c->lj_split_in.p : c->lj_split.p;
-  P.lj16 = c->prune_valid ? c->lj16_in.p : c->lj16.p;
+  const MdpRows rows = mdp_rows(c);
+  P.lj_len = rows.len;
+  P.lj_split = rows.split;
+  P.lj16 = rows.lj16;
   P.rho = c->rho.p;
   {
     // the reference skips a pair when sqrt(rsq) > cut: the largest rsq that passes, found once on the host
@@ -1644,23 +1637,11 @@ static int aeam_ptile_launch(mdp_ctx *c, const int t_begin, const int t_end, boo
     P.hot_rsqmax = t;
   }
   const size_t lds = (size_t) nw * 16 + (size_t) nsub * sub_bytes;
-#define MDP_PT(NS)                                                                                                    \
-  do {                                                                                                                \
-    if (c->aeam_cl == 2) {                                                                                            \
-      MDP_HIP(c, hipFuncSetAttribute((const void *) aeam_ptile_kernel<NS, 2>,                                         \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));                         \
-      aeam_ptile_kernel<NS, 2><<<grid, NS * 256, lds, c->stream>>>(c->aeam, P);                                       \
-    } else {                                                                                                          \
-      MDP_HIP(c, hipFuncSetAttribute((const void *) aeam_ptile_kernel<NS, 1>,                                         \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));                         \
-      aeam_ptile_kernel<NS, 1><<<grid, NS * 256, lds, c->stream>>>(c->aeam, P);                                       \
-    }                                                                                                                 \
-  } while (0)
-  if (nsub == 4) MDP_PT(4);
-  else if (nsub == 3) MDP_PT(3);
-  else MDP_PT(2);
-#undef MDP_PT
-  MDP_HIP(c, hipGetLastError());
+  const bool cl2 = c->aeam_cl == 2;
+  const auto kernel = nsub == 4   ? (cl2 ? aeam_ptile_kernel<4, 2> : aeam_ptile_kernel<4, 1>)
+                      : nsub == 3 ? (cl2 ? aeam_ptile_kernel<3, 2> : aeam_ptile_kernel<3, 1>)
+                                  : (cl2 ? aeam_ptile_kernel<2, 2> : aeam_ptile_kernel<2, 1>);
+  MDP_TRY(mdp_launch(c, kernel, grid, nsub * 256, lds, c->stream, c->aeam, P));
   if (getenv("MDP_DEBUG") && !c->ptile_reported[0]) {
     c->ptile_reported[0] = true;
     fprintf(stderr, "[mdp] aeam persistent density kernel: %d workgroups x %d sub-blocks, %d tiles each, window rows [%d, %d] of %d (%.1f KB), staging %zu B per sub-block\n",
@@ -1707,26 +1688,12 @@ static int aeam_density_tiles(mdp_ctx *c, const int t_begin, const int t_end)
   const int capL = (aeam_range_maxu(c, t_end) + 1 + 7) & ~7;
   const bool multi = c->aeam.ntypes != 2; // per-entry types and an LDS parameter block (see par_fill)
   const size_t lds = (size_t) capL * 3 * sizeof(double) + (multi ? kParBytes + (size_t) capL * sizeof(int) : 0);
-#define MDP_ATD(CLV, MV)                                                                                             \
-  do {                                                                                                                \
-    if (lds > 48 * 1024)                                                                                              \
-      MDP_HIP(c, hipFuncSetAttribute((const void *) aeam_tile_density_kernel<CLV, MV>,                                \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));                         \
-    aeam_tile_density_kernel<CLV, MV><<<t_end - t_begin, 256, lds, st>>>(                                             \
-        c->aeam, nlocal, c->nclus, t_begin, c->xq.p, c->tile_cap, capL, c->tu.p, c->tile_nu.p, c->lj_off.p,           \
-        c->prune_valid ? c->lj_len_in.p : nullptr, c->prune_valid ? c->lj_split_in.p : c->lj_split.p,                 \
-        c->prune_valid ? c->lj16_in.p : c->lj16.p, c->rho.p);                                                         \
-  } while (0)
-  if (multi) {
-    if (c->aeam_cl == 1) MDP_ATD(1, true);
-    else MDP_ATD(2, true);
-  } else {
-    if (c->aeam_cl == 1) MDP_ATD(1, false);
-    else MDP_ATD(2, false);
-  }
-#undef MDP_ATD
-  MDP_HIP(c, hipGetLastError());
-  return MDP_OK;
+  const MdpRows rows = mdp_rows(c);
+  const bool cl1 = c->aeam_cl == 1;
+  const auto kernel = multi ? (cl1 ? aeam_tile_density_kernel<1, true> : aeam_tile_density_kernel<2, true>)
+                            : (cl1 ? aeam_tile_density_kernel<1, false> : aeam_tile_density_kernel<2, false>);
+  return mdp_launch(c, kernel, t_end - t_begin, 256, lds, st, c->aeam, nlocal, c->nclus, t_begin, c->xq.p, c->tile_cap, capL,
+                    c->tu.p, c->tile_nu.p, c->lj_off.p, rows.len, rows.split, rows.lj16, c->rho.p);
 }
 
 // pass 3, pair part, over the tiles [t_begin, t_end)
@@ -1738,32 +1705,16 @@ static int aeam_force_tiles(mdp_ctx *c, const int t_begin, const int t_end, cons
   const bool multi = c->aeam.ntypes != 2;
   const size_t lds = (size_t) capL * 4 * sizeof(double) + (multi ? kParBytes + (size_t) capL * sizeof(int) : 0);
   const bool ev = eflag || vflag;
-#define MDP_ATF(CLV, EVV, MV)                                                                                        \
-  do {                                                                                                                \
-    if (lds > 48 * 1024)                                                                                              \
-      MDP_HIP(c, hipFuncSetAttribute((const void *) aeam_tile_force_kernel<CLV, EVV, MV>,                             \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));                         \
-    aeam_tile_force_kernel<CLV, EVV, MV><<<t_end - t_begin, 256, lds, st>>>(                                          \
-        c->aeam, c->nlocal, c->nclus, t_begin, c->xq.p, c->fp.p, c->tile_cap, capL, c->tu.p, c->tile_nu.p,            \
-        c->lj_off.p, c->prune_valid ? c->lj_len_in.p : nullptr, c->prune_valid ? c->lj_split_in.p : c->lj_split.p,    \
-        c->prune_valid ? c->lj16_in.p : c->lj16.p, c->f.p, c->eatom.p, c->acc.p, eflag, vflag);                       \
-  } while (0)
-#define MDP_ATF_M(CLV, EVV)                                                                                          \
-  do {                                                                                                                \
-    if (multi) MDP_ATF(CLV, EVV, true);                                                                               \
-    else MDP_ATF(CLV, EVV, false);                                                                                    \
-  } while (0)
-  if (c->aeam_cl == 1) {
-    if (ev) MDP_ATF_M(1, true);
-    else MDP_ATF_M(1, false);
-  } else {
-    if (ev) MDP_ATF_M(2, true);
-    else MDP_ATF_M(2, false);
-  }
-#undef MDP_ATF_M
-#undef MDP_ATF
-  MDP_HIP(c, hipGetLastError());
-  return MDP_OK;
+  const MdpRows rows = mdp_rows(c);
+  return mdp_with_bool(ev, [&](auto ev_c) {
+    return mdp_with_bool(multi, [&](auto multi_c) {
+      constexpr bool EV = decltype(ev_c)::value, M = decltype(multi_c)::value;
+      const auto kernel = c->aeam_cl == 1 ? aeam_tile_force_kernel<1, EV, M> : aeam_tile_force_kernel<2, EV, M>;
+      return mdp_launch(c, kernel, t_end - t_begin, 256, lds, st, c->aeam, c->nlocal, c->nclus, t_begin, c->xq.p, c->fp.p,
+                        c->tile_cap, capL, c->tu.p, c->tile_nu.p, c->lj_off.p, rows.len, rows.split, rows.lj16, c->f.p,
+                        c->eatom.p, c->acc.p, eflag, vflag);
+    });
+  });
 }
 
 static int aeam_ang_forces(mdp_ctx *c, const int vflag)
@@ -1795,7 +1746,7 @@ int mdp_aeam_run_begin(mdp_ctx *c, int eflag, int vflag)
   double cut[4];
   aeam_prune_cuts(c, cut);
   bool due = false;
-  MDP_TRY(mdp_prune_upkeep(c, cut, c->cfg.skin, /*may_prune=*/false, &due));
+  MDP_TRY(mdp_prune_upkeep(c, cut, c->cfg.skin, /*own_check=*/false, /*may_prune=*/false, &due));
   if (due) return MDP_OK;
   MDP_TRY(aeam_open(c));
   mdp_span_begin(c, 5);
@@ -1816,11 +1767,11 @@ int mdp_aeam_run_density(mdp_ctx *c, int eflag)
   MDP_TRY(aeam_open(c));
   if (!early) {
     if (c->aeam_tiled) {
-      // resident runs walk rows pruned to the pairs within reach right now (tile_prune_kernel in rebomos.hip): a third
+      // resident runs walk rows pruned to the pairs within reach right now (tile_prune_kernel in tiles.hip): a third
       // of the entries of a list built with 1 A of skin on a 6.5 A cutoff are skin
       double cut[4];
       aeam_prune_cuts(c, cut);
-      MDP_TRY(mdp_prune_upkeep(c, cut, c->cfg.skin, /*may_prune=*/true, nullptr));
+      MDP_TRY(mdp_prune_upkeep(c, cut, c->cfg.skin, /*own_check=*/false, /*may_prune=*/true, nullptr));
     } else
       c->prune_valid = false;
   }
@@ -1902,19 +1853,21 @@ int mdp_aeam_run_force(mdp_ctx *c, int eflag, int vflag)
       MDP_TRY(mdp_md_build_master_list(c));
     }
     const int grid = nblk(nlocal, 256 / AE_L);
-    const bool ev = eflag || vflag;
-#define MDP_AF(NTV, EVV)                                                                                              \
-  aeam_force_kernel<AE_L, NTV, EVV><<<grid, 256, 0, st>>>(c->aeam, nlocal, c->xq.p, c->nb_off.p, c->nb.p, c->fp.p,      \
-                                                          c->f.p, c->eatom.p, c->vatom.p, c->acc.p, eflag, vflag)
-    switch (c->aeam.ntypes) {
-      case 1: if (ev) MDP_AF(1, true); else MDP_AF(1, false); break;
-      case 2: if (ev) MDP_AF(2, true); else MDP_AF(2, false); break;
-      case 3: if (ev) MDP_AF(3, true); else MDP_AF(3, false); break;
-      case 4: if (ev) MDP_AF(4, true); else MDP_AF(4, false); break;
-      case 5: case 6: case 7: case 8: if (ev) MDP_AF(MDP_AEAM_MAXT, true); else MDP_AF(MDP_AEAM_MAXT, false); break;
-      default: if (ev) MDP_AF(0, true); else MDP_AF(0, false); break; // more than MDP_AEAM_MAXT types
-    }
-#undef MDP_AF
+    const auto launch = [&](auto kernel) {
+      return mdp_launch(c, kernel, grid, 256, 0, st, c->aeam, nlocal, c->xq.p, c->nb_off.p, c->nb.p, c->fp.p, c->f.p, c->eatom.p,
+                        c->vatom.p, c->acc.p, eflag, vflag);
+    };
+    MDP_TRY(mdp_with_bool(eflag || vflag, [&](auto ev_c) {
+      constexpr bool EV = decltype(ev_c)::value;
+      switch (c->aeam.ntypes) {
+        case 1: return launch(aeam_force_kernel<AE_L, 1, EV>);
+        case 2: return launch(aeam_force_kernel<AE_L, 2, EV>);
+        case 3: return launch(aeam_force_kernel<AE_L, 3, EV>);
+        case 4: return launch(aeam_force_kernel<AE_L, 4, EV>);
+        case 5: case 6: case 7: case 8: return launch(aeam_force_kernel<AE_L, MDP_AEAM_MAXT, EV>);
+        default: return launch(aeam_force_kernel<AE_L, 0, EV>); // more than MDP_AEAM_MAXT types
+      }
+    }));
   }
   mdp_span_end(c, 3);
   if (!(c->aeam_phase & AE_ANG_F)) {

@@ -925,8 +925,7 @@ int mdp_md_download_int(mdp_ctx *c, const char *name, int *out)
   const bool rows = !strcmp(name, "lj_len") || !strcmp(name, "lj_split");
   if (rows) {
     if (!c->lj_tiled || !c->nclus) return mdp_fail(c, MDP_ESTATE, "mdp_md_download_int: no tile rows");
-    const bool pr = c->prune_valid;
-    src = !strcmp(name, "lj_len") ? (pr ? c->lj_len_in.p : nullptr) : (pr ? c->lj_split_in.p : c->lj_split.p);
+    src = !strcmp(name, "lj_len") ? mdp_rows(c).len : mdp_rows(c).split;
     if (!src) return mdp_fail(c, MDP_ESTATE, "mdp_md_download_int: lj_len needs pruned rows (the rows as built: mdp_rebomos_list_info)");
   }
   if (!src) return mdp_fail(c, MDP_EINVAL, "mdp_md_download_int: unknown array '%s'", name);

@@ -924,9 +924,7 @@ static int md_cut_tables(mdp_ctx *c, CutTables &ct, double &maxcut)
     // virial steps run the tile kernels.  Only the angular centres (0.75 % in sample.in) read it, so only their
     // rows are built -- a quarter of the reneighboring time at 1 M atoms.  A per-atom-virial step (CSR kernels)
     // asks for the full list (c->csr_want_full) and gets it rebuilt on the spot.
-    const char *e = getenv("MDP_AEAM_TILE");
-    const bool tiles = (c->md || c->aeam_device_lists) && !(e && atoi(e) == 0) && nt <= MDP_AEAM_MAXT;
-    ct.min_type = (tiles && !c->csr_want_full && !c->cfg.master_list) ? c->aeam.nnonangular : 0;
+    ct.min_type = (aeam_wants_tiles(c) && !c->csr_want_full && !c->cfg.master_list) ? c->aeam.nnonangular : 0;
     c->csr_full = ct.min_type == 0;
     MDP_TRY(aeam_cut_table(c, ct, skin, maxcut));
   } else

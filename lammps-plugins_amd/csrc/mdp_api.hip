@@ -294,12 +294,6 @@ __global__ void acc_zero_kernel(double *__restrict__ acc, const int n, int *__re
     flags[i] = 0;
 }
 
-__global__ void add_f_kernel(int n3, const double *__restrict__ src, double *__restrict__ dst)
-{
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n3) dst[i] += src[i];
-}
-
 __global__ void acc_reduce_kernel(double *__restrict__ acc)
 {
   // one wave per quantity k = 0..6: sum the slots

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -19,6 +20,7 @@
 // followed by MDP_ACC_SLOTS partial slots of MDP_ACC_STRIDE doubles each
 #define MDP_CLUSTER 2
 static_assert(MDP_CLUSTER == 1 || MDP_CLUSTER == 2, "the Lennard-Jones kernels are instantiated for 1- and 2-atom clusters only");
+#define MDP_TILE 16 // clusters per tile of the tile rows (tiles.hip) = 256 threads / 16 lanes per cluster
 #define MDP_ACC_SLOTS 512
 #define MDP_ACC_STRIDE 16
 // REBO centre classes: lane-group size (4, 8, 12, 16, 32) x element, x {interior, boundary}: classes 10..19 hold the
@@ -155,6 +157,15 @@ template <int W> __device__ __forceinline__ double group_sum(double v)
 #pragma unroll
   for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// Workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  Work items that are neighbours
+// in space (consecutive along the Hilbert curve) share most of what they gather, so every XCD is given one
+// contiguous stretch of the items instead of every eighth one.
+__device__ __forceinline__ int xcd_contiguous(const int b, const int n)
+{
+  const int q = n >> 3, r = n & 7, xcd = b & 7, idx = b >> 3;
+  return xcd * q + (xcd < r ? xcd : r) + idx;
 }
 
 // 30-bit key of a cell (10 bits per axis) along a 3-D Hilbert curve (Skilling, "Programming the Hilbert curve":
@@ -932,6 +943,50 @@ int mdp_write_small(mdp_ctx *c, void *d_dst, const void *h_src, size_t bytes); /
     if (rc_ != MDP_OK) return rc_;                                                                   \
   } while (0)
 
+// One kernel launch: raises the kernel's dynamic-LDS limit when `lds` needs more than the 48 KB a kernel gets unasked,
+// launches, and reports a launch error through the context.  The arguments convert to the kernel's parameter types as in
+// a launch written out.
+template <typename... P, typename... A>
+inline int mdp_launch(mdp_ctx *c, void (*kernel)(P...), int grid, int block, size_t lds, hipStream_t st, A &&...args)
+{
+  if (lds > 48 * 1024)
+    MDP_HIP(c, hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+  kernel<<<grid, block, lds, st>>>(std::forward<A>(args)...);
+  MDP_HIP(c, hipGetLastError());
+  return MDP_OK;
+}
+
+// A run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{}), for picking a kernel's template arguments
+template <class F> inline int mdp_with_bool(const bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// The tile rows the kernels walk now: the pruned copy while a pruning is valid (lengths in `len`), the rows as built
+// otherwise (len null: a row's length is the distance to the next row's offset)
+struct MdpRows {
+  const int *len, *split;
+  const unsigned short *lj16;
+};
+inline MdpRows mdp_rows(const mdp_ctx *c)
+{
+  if (c->prune_valid) return {c->lj_len_in.p, c->lj_split_in.p, c->lj16_in.p};
+  return {nullptr, c->lj_split.p, c->lj16.p};
+}
+// new rows were built: the pruned copy is made by the next compute that wants it
+inline void mdp_rows_renewed(mdp_ctx *c)
+{
+  c->prune_valid = false;
+  c->prune_stale = false;
+  c->prune_epoch++;
+}
+
+// Does aeam take tile lists (resident mode, or host mode with lists built on the device)?  MDP_AEAM_TILE=0 keeps the CSR
+// kernels; the tile kernels carry the parameters of up to MDP_AEAM_MAXT types in their arguments / in LDS.  Asked by the
+// master-list builder (which rows the CSR list needs) and by mdp_aeam_prepare (whether to build the tiles): one answer.
+inline bool aeam_wants_tiles(const mdp_ctx *c)
+{
+  const char *e = getenv("MDP_AEAM_TILE");
+  return (c->md || c->aeam_device_lists) && !(e && atoi(e) == 0) && c->aeam.ntypes <= MDP_AEAM_MAXT;
+}
+
 // modules
 int mdp_pack_xq(mdp_ctx *c, const double *d_x3, const int *d_type_or_null, int count = -1); // xraw/type -> xq (first `count` atoms; -1: all)
 int mdp_rebomos_host_precheck(mdp_ctx *c);                 // host mode: displacement check behind the position upload
@@ -947,10 +1002,14 @@ int mdp_chunk_by_element(mdp_ctx *c, int n, int n_owned, const int *d_idx_in, in
                          const int *d_type, const int *d_map); // element-sorted runs of 32 owned atoms (stable)
 int mdp_scan_exclusive_i64(mdp_ctx *c, const int *d_in, long long *d_out, int n);
 int mdp_rebomos_repack(mdp_ctx *c);
-int mdp_tile_prune(mdp_ctx *c, const double lim_rsq[4]);                 // (re-)prune the tile rows from the current positions
-void mdp_prune_adapt(mdp_ctx *c, double buf_max, bool fired);
-int mdp_prune_upkeep(mdp_ctx *c, const double cut[4], double skin, bool may_prune, bool *due); // trigger + pruning for a style without its own displacement check
-int mdp_tile_lists_build(mdp_ctx *c, const double cutsq[4], int cl, bool *ok); // tile lists (cl atoms per cluster), two classes of atoms (type 0 | others); needs the bin grid
+// keeps the pruned rows current before the kernels walk them: adapts the buffer, prunes (again) when due.  own_check: the
+// style reads the displacement flags itself (rebomos); may_prune false: a pruning that is due is only reported (tiles.hip)
+int mdp_prune_upkeep(mdp_ctx *c, const double cut[4], double skin, bool own_check, bool may_prune, bool *due);
+// the tile rows (cl atoms per cluster; two classes of atoms: type 0 | others) within P.ljlist_cutsq, members from the bin
+// grid (mdp_bin_atoms) or, from_csr, from the host's neighbor list; `ride` (may be null): a small read of the caller's
+// that goes with the builder's own blocking read of the row total (made only when *ok)
+int mdp_tile_rows_build(mdp_ctx *c, const RebomosDev &P, int cl, bool from_csr, const MdpRead *ride, bool *ok);
+int mdp_tile_lists_build(mdp_ctx *c, const double cutsq[4], int cl, bool *ok); // ... for another two-type style (aeam), from the bin grid
 int mdp_rebomos_run(mdp_ctx *c, int eflag, int vflag, bool zero_f);
 int mdp_rebomos_run_begin(mdp_ctx *c, int eflag, int vflag);
 int mdp_rebomos_run_end(mdp_ctx *c, int eflag, int vflag);

@@ -60,15 +60,6 @@ __device__ __forceinline__ void wave_lds_fence()
 // bounded tree towards lane 0 of the group, then broadcast
 template <int G> __device__ __forceinline__ double group_sum_any(double v, const int s, const int lane);
 
-// Workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  Work items that are neighbours
-// in space (consecutive along the Hilbert curve) share most of what they gather, so every XCD is given one
-// contiguous stretch of the items instead of every eighth one.
-__device__ __forceinline__ int xcd_contiguous(const int b, const int n)
-{
-  const int q = n >> 3, r = n & 7, xcd = b & 7, idx = b >> 3;
-  return xcd * q + (xcd < r ? xcd : r) + idx;
-}
-
 template <int G> __device__ __forceinline__ double group_sum_any(double v, const int s, const int lane)
 {
   if constexpr ((G & (G - 1)) == 0) {
@@ -1535,8 +1526,6 @@ __global__ __launch_bounds__(256, MDP_LJ_WAVES) void rebo_lj_gather_kernel(
 // that union.  The old kernel's bound was the L1 tag rate of its per-lane gathers (each gathered atom
 // was used by 2 pair evaluations); here a gathered atom serves ~13, and the inner loop reads LDS.
 // ------------------------------------------------------------------------------------------------
-#define MDP_TILE 16 // clusters per tile = 256 threads / 16 lanes per cluster
-
 // Corrections for the pairs of a tile's rows that sit on the cubic inner spline (rcLJmin <= r < 0.95 sigma,
 // pair_rebomos.cpp:532-543): none in an equilibrium crystal, a few per atom in a strained, hot or disordered structure.
 // rebo_lj_tile_kernel evaluates every pair as 12-6 and puts the tiles with a flagged pair on a list; this kernel follows
@@ -2276,609 +2265,6 @@ __global__ __launch_bounds__(256) void cluster_build_kernel(const MdpGrid g, con
   }
 }
 
-// ---- tile lists -------------------------------------------------------------------------------
-// Pass 1, one workgroup per tile: sweep the stencil of the tile's bounding cells; every candidate is
-// tested against all atoms of the tile (broadcast LDS reads) giving a 16-bit mask of the clusters that
-// list it.  Each wave takes every fourth (y,z) row and compacts its members with ballots into its own
-// LDS segment (Mo from the front, S from the back); the segments are then concatenated Mo-first, so the
-// result is deterministic.  Outputs: the union (tu), the masks, and the row lengths of the 16 clusters.
-template <int CL>
-__global__ __launch_bounds__(256) void tile_scan_kernel(const MdpGrid g, const RebomosDev P, const int nclus,
-                                                        const int nlocal, const double4 *__restrict__ xq,
-                                                        const int *__restrict__ perm,
-                                                        const int *__restrict__ cell_start, const int cap,
-                                                        int *__restrict__ tu, unsigned short *__restrict__ tmask,
-                                                        int *__restrict__ tile_nu, int *__restrict__ cnt,
-                                                        int *__restrict__ split, int *__restrict__ tile_flag,
-                                                        const double4 *__restrict__ xq_cell)
-{
-  constexpr int NA = MDP_TILE * CL;
-  extern __shared__ int s_dyn[];
-  const int wcap = cap / 2; // per-wave segment (a wave sees about a quarter of the union)
-  int *s_idx = s_dyn;                                                    // [4][wcap]
-  unsigned short *s_m = (unsigned short *) (s_dyn + 4 * wcap);           // [4][wcap]
-  unsigned short *s_fm = s_m + 4 * wcap;                                 // [cap] masks in final order
-  __shared__ double4 s_xa[NA];
-  __shared__ double s_cut[NA][2];
-  __shared__ int s_lo[3], s_hi[3], s_n0[4], s_n1[4], s_over, s_rowsum;
-  __shared__ double s_bb[6], s_cmax; // bounding box of the tile's atoms (lo x y z | hi x y z), their largest list cutoff
-  const int t = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  if (tid < 3) {
-    s_lo[tid] = 1 << 30;
-    s_hi[tid] = -1;
-  }
-  if (tid == 0) s_over = s_rowsum = 0;
-  __syncthreads();
-  if (tid < NA) {
-    const int ia = t * NA + tid;
-    bool valid = ia < nlocal;
-    const double4 xa = xq[valid ? ia : (nlocal > 0 ? nlocal - 1 : 0)];
-    int ta = (int) xa.w;
-    if (ta < 0) valid = false; // NULL-mapped atom: lists nothing
-    ta = ta > 1 ? 1 : ta;      // two classes: type 0 | every other type (a style with more types sorts them out itself)
-    s_xa[tid] = xa;
-    s_cut[tid][0] = valid ? P.ljlist_cutsq[ta * 2 + 0] : -1.0;
-    s_cut[tid][1] = valid ? P.ljlist_cutsq[ta * 2 + 1] : -1.0;
-    {
-      // (the NA <= 64 atom threads are the first lanes of wave 0: min / max by shuffles; absent atoms do not count)
-      static_assert(NA <= 64, "the tile's atoms are held by one wave");
-      double lo3[3] = {valid ? xa.x : 1.0e300, valid ? xa.y : 1.0e300, valid ? xa.z : 1.0e300};
-      double hi3[3] = {valid ? xa.x : -1.0e300, valid ? xa.y : -1.0e300, valid ? xa.z : -1.0e300};
-      double cm = valid ? fmax(s_cut[tid][0], s_cut[tid][1]) : -1.0;
-#pragma unroll
-      for (int o = 1; o < NA; o <<= 1) {
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          lo3[d] = fmin(lo3[d], __shfl_xor(lo3[d], o, 64));
-          hi3[d] = fmax(hi3[d], __shfl_xor(hi3[d], o, 64));
-        }
-        cm = fmax(cm, __shfl_xor(cm, o, 64));
-      }
-      if (tid == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          s_bb[d] = lo3[d];
-          s_bb[3 + d] = hi3[d];
-        }
-        s_cmax = cm;
-      }
-    }
-    if (valid) {
-      int cc[3];
-      cc[0] = (int) ((xa.x - g.lo[0]) * g.inv[0]);
-      cc[1] = (int) ((xa.y - g.lo[1]) * g.inv[1]);
-      cc[2] = (int) ((xa.z - g.lo[2]) * g.inv[2]);
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        cc[d] = cc[d] < 0 ? 0 : (cc[d] >= g.n[d] ? g.n[d] - 1 : cc[d]);
-        atomicMin(&s_lo[d], cc[d]);
-        atomicMax(&s_hi[d], cc[d]);
-      }
-    }
-  }
-  __syncthreads();
-  const int R = g.range;
-  const bool any = s_hi[0] >= 0;
-  const int xlo = max(s_lo[0] - R, 0), xhi = min(s_hi[0] + R, g.n[0] - 1);
-  const int ylo = max(s_lo[1] - R, 0), yhi = min(s_hi[1] + R, g.n[1] - 1);
-  const int zlo = max(s_lo[2] - R, 0), zhi = min(s_hi[2] + R, g.n[2] - 1);
-  const int ny = yhi - ylo + 1, nz = zhi - zlo + 1;
-  const int nrows = any ? ny * nz : 0;
-  int *seg_i = s_idx + wave * wcap;
-  unsigned short *seg_m = s_m + wave * wcap;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int n0 = 0, n1 = 0;
-  bool over = false;
-  // The candidates of the (y,z) rows of cells are taken as ONE concatenated list, 64 per wave and trip: a row by
-  // itself holds 15-40 atoms, so a wave walking row after row had a quarter to a half of its lanes busy in front of
-  // two dependent round trips per row.  (The order in which members are found does not matter: tile_sort_kernel
-  // sorts every segment by atom index.)
-  constexpr int kRows = 256;
-  __shared__ int s_pb[kRows], s_off[kRows + 1], s_wsum[4];
-  for (int rbase = 0; rbase < nrows; rbase += kRows) {
-    const int nr = nrows - rbase < kRows ? nrows - rbase : kRows;
-    int pb = 0, len = 0;
-    if (tid < nr) {
-      const int r = rbase + tid;
-      const int y = ylo + r % ny, z = zlo + r / ny;
-      // The stencil is a box of cells, what can hold a neighbour is the tile's bounding box grown by the largest list
-      // cutoff -- about half of that box: a row of cells farther than the cutoff from the bounding box (in the y-z plane)
-      // is left out, and of the others only the cells along x that the remaining distance reaches.  Conservative by
-      // construction (cell and box faces, a 1e-9 A margin), so the union is what the full sweep finds.
-      const double cy0 = g.lo[1] + y / g.inv[1], cy1 = g.lo[1] + (y + 1) / g.inv[1];
-      const double cz0 = g.lo[2] + z / g.inv[2], cz1 = g.lo[2] + (z + 1) / g.inv[2];
-      // (the first and the last cell of a dimension also hold what lies beyond the grid: that face is at infinity)
-      const double dy = y < g.n[1] - 1 && s_bb[1] > cy1 ? s_bb[1] - cy1 : (y > 0 && cy0 > s_bb[4] ? cy0 - s_bb[4] : 0.0);
-      const double dz = z < g.n[2] - 1 && s_bb[2] > cz1 ? s_bb[2] - cz1 : (z > 0 && cz0 > s_bb[5] ? cz0 - s_bb[5] : 0.0);
-      const double left = s_cmax - dy * dy - dz * dz; // squared reach along x
-      if (left >= -1.0e-9) {
-        const double rx = sqrt(left > 0.0 ? left : 0.0) + 1.0e-9;
-        int x0 = (int) floor((s_bb[0] - rx - g.lo[0]) * g.inv[0]), x1 = (int) floor((s_bb[3] + rx - g.lo[0]) * g.inv[0]);
-        x0 = x0 < xlo ? xlo : x0;
-        x1 = x1 > xhi ? xhi : x1;
-        if (x0 <= x1) {
-          pb = cell_start[x0 + g.n[0] * (y + g.n[1] * z)];
-          len = cell_start[x1 + g.n[0] * (y + g.n[1] * z) + 1] - pb;
-        }
-      }
-    }
-    int incl = len;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    int wbase = 0;
-    for (int w = 0; w < wave; w++) wbase += s_wsum[w];
-    const int total = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
-    s_pb[tid] = pb;
-    s_off[tid] = wbase + incl - len;
-    if (tid == 0) s_off[kRows] = total;
-    __syncthreads();
-    // the candidate of the NEXT trip is located and its two loads (position in cell order, atom index) are in flight
-    // while the current one is tested against the tile's atoms: a trip was two dependent round trips to memory in
-    // front of 32 distance tests, at five waves per SIMD
-    const auto locate = [&](const int gi) {
-      int lo = 0, hi = kRows; // s_off[lo] <= gi < s_off[hi]  (rows past nr are empty: offset = total)
-#pragma unroll
-      for (int it = 0; it < 8; it++) {
-        const int mid = (lo + hi) >> 1;
-        if (s_off[mid] <= gi) lo = mid;
-        else hi = mid;
-      }
-      return s_pb[lo] + gi - s_off[lo];
-    };
-    double4 xn = make_double4(0.0, 0.0, 0.0, -1.0);
-    int jn = 0;
-    if (wave * 64 + lane < total) {
-      const int p = locate(wave * 64 + lane);
-      xn = xq_cell[p];
-      jn = perm[p];
-    }
-    for (int g0 = wave * 64; g0 < total && !over; g0 += 256) {
-      const int gi = g0 + lane;
-      unsigned m = 0;
-      int j = 0, tj = 0;
-      const double4 xj = xn;
-      const int jcur = jn;
-      if (gi + 256 < total) {
-        const int p = locate(gi + 256);
-        xn = xq_cell[p];
-        jn = perm[p];
-      }
-      if (gi < total) {
-        j = jcur;
-        tj = (int) xj.w;
-        tj = tj > 1 ? 1 : tj;
-        if (tj >= 0) {
-#pragma unroll 8
-          for (int a = 0; a < NA; a++) {
-            const double4 xa = s_xa[a];
-            const double dx = xa.x - xj.x, dy = xa.y - xj.y, dz = xa.z - xj.z;
-            if (dx * dx + dy * dy + dz * dz <= s_cut[a][tj]) m |= 1u << (a / CL);
-          }
-        }
-      }
-      const bool k0 = m != 0 && tj == 0, k1 = m != 0 && tj != 0;
-      const unsigned long long b0 = __ballot(k0), b1 = __ballot(k1);
-      const int c0 = __popcll(b0), c1 = __popcll(b1);
-      if (n0 + n1 + c0 + c1 > wcap) {
-        over = true;
-        break;
-      }
-      if (k0) {
-        const int pos = n0 + __popcll(b0 & below);
-        seg_i[pos] = j;
-        seg_m[pos] = (unsigned short) m;
-      }
-      if (k1) {
-        const int pos = wcap - 1 - (n1 + __popcll(b1 & below));
-        seg_i[pos] = j;
-        seg_m[pos] = (unsigned short) m;
-      }
-      n0 += c0;
-      n1 += c1;
-    }
-    __syncthreads(); // (s_pb / s_off are rewritten by the next block of rows)
-  }
-  if (lane == 0) {
-    s_n0[wave] = n0;
-    s_n1[wave] = n1;
-    if (over) s_over = 1;
-  }
-  __syncthreads();
-  const int N0 = s_n0[0] + s_n0[1] + s_n0[2] + s_n0[3];
-  const int N1 = s_n1[0] + s_n1[1] + s_n1[2] + s_n1[3];
-  int nU = N0 + N1;
-  if (s_over || nU > cap - 1) { // (slot nU is the kernel's dummy entry, so nU <= cap-1)
-    if (tid == 0) {
-      atomicOr(&tile_flag[0], 1);
-      tile_nu[2 * t] = tile_nu[2 * t + 1] = 0;
-    }
-    if (tid < MDP_TILE) cnt[t * MDP_TILE + tid] = split[t * MDP_TILE + tid] = 0;
-    return;
-  }
-  int base0 = 0, base1 = N0;
-  for (int w = 0; w < wave; w++) {
-    base0 += s_n0[w];
-    base1 += s_n1[w];
-  }
-  int *mem = tu + (size_t) t * cap;
-  unsigned short *mm = tmask + (size_t) t * cap;
-  for (int i = lane; i < n0; i += 64) {
-    const int u = base0 + i;
-    const unsigned short m = seg_m[i];
-    mem[u] = seg_i[i];
-    mm[u] = m;
-    s_fm[u] = m;
-  }
-  for (int i = lane; i < n1; i += 64) {
-    const int u = base1 + i, src = wcap - 1 - i;
-    const unsigned short m = seg_m[src];
-    mem[u] = seg_i[src];
-    mm[u] = m;
-    s_fm[u] = m;
-  }
-  __syncthreads();
-  const int gq = tid / 16, sq = tid % 16;
-  int c0 = 0, c1 = 0;
-  for (int u = sq; u < nU; u += 16) {
-    const int bit = (s_fm[u] >> gq) & 1;
-    c0 += u < N0 ? bit : 0;
-    c1 += u < N0 ? 0 : bit;
-  }
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) {
-    c0 += __shfl_xor(c0, o, 64);
-    c1 += __shfl_xor(c1, o, 64);
-  }
-  // Row layout: every tile has MDP_TILE rows (absent clusters get all-dummy rows); both segments are padded
-  // with the dummy index to whole 16-lane steps AND to the longest of the four clusters that share a wave
-  // in the compute kernel, so that its loops are wave-uniform (idle lanes would cost the same time).
-  int p0 = (c0 + 15) & ~15, p1 = (c1 + 15) & ~15;
-#pragma unroll
-  for (int o = 16; o < 64; o <<= 1) {
-    p0 = max(p0, __shfl_xor(p0, o, 64));
-    p1 = max(p1, __shfl_xor(p1, o, 64));
-  }
-  const int kc = t * MDP_TILE + gq;
-  if (sq == 0) {
-    cnt[kc] = p0 + p1;
-    split[kc] = p0;
-    atomicAdd(&s_rowsum, p0 + p1);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    tile_nu[2 * t] = nU;
-    tile_nu[2 * t + 1] = N0;
-    // running maxima over all tiles, two words for the whole grid.  A look first -- the word only grows, so a stale smaller
-    // value costs at most a redundant atomic -- leaves a handful of atomics per launch instead of two per tile on ONE
-    // address (the look goes to the L2, where the atomics land: a CU's L1 would keep the first value it saw).  Measured:
-    // no difference at 124 416 tiles (the atomics are fire-and-forget at the end of a workgroup); the per-WAVE atomics
-    // with a return value in classify_kernel were the ones that cost a millisecond.
-    if (nU > __hip_atomic_load(&tile_flag[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&tile_flag[1], nU);
-    if (s_rowsum > __hip_atomic_load(&tile_flag[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      atomicMax(&tile_flag[2], s_rowsum); // row entries of the whole tile (kernels that stage a tile's rows in LDS)
-  }
-}
-
-// Between the passes: the members of a union are sorted by atom index (each element segment by itself).  The
-// kernels that stage a union gather xq[member] with consecutive lanes taking consecutive members; atoms are stored
-// along a Hilbert curve, so after the sort neighbouring lanes mostly hit the same 128-byte line (four atoms) instead
-// of one line each -- the staging gathers were a quarter of the L1 lookups of the AEAM tile kernels.
-__global__ __launch_bounds__(256) void tile_sort_kernel(const int cap, const int *__restrict__ tile_nu,
-                                                        int *__restrict__ tu, unsigned short *__restrict__ tmask)
-{
-  extern __shared__ unsigned long long s_key[];
-  const int t = blockIdx.x, tid = threadIdx.x;
-  const int nU = tile_nu[2 * t], N0 = tile_nu[2 * t + 1];
-  int *mem = tu + (size_t) t * cap;
-  unsigned short *mm = tmask + (size_t) t * cap;
-  for (int seg = 0; seg < 2; seg++) {
-    const int b = seg ? N0 : 0, n = (seg ? nU : N0) - b;
-    if (n <= 1) continue; // (block-uniform)
-    int np = 2;
-    while (np < n) np <<= 1;
-    for (int i = tid; i < np; i += 256)
-      s_key[i] = i < n ? (((unsigned long long) (unsigned) mem[b + i]) << 16) | mm[b + i] : ~0ull;
-    __syncthreads();
-    for (int k = 2; k <= np; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        // every thread takes whole compare-exchange pairs (i, i + j): q-th pair, i = q with a zero inserted at bit log2 j
-        for (int q = tid; q < (np >> 1); q += 256) {
-          const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), p = i | j;
-          const unsigned long long x = s_key[i], y = s_key[p];
-          if ((x > y) == ((i & k) == 0)) {
-            s_key[i] = y;
-            s_key[p] = x;
-          }
-        }
-        __syncthreads();
-      }
-    for (int i = tid; i < n; i += 256) {
-      const unsigned long long v = s_key[i];
-      mem[b + i] = (int) (v >> 16);
-      mm[b + i] = (unsigned short) (v & 0xFFFFull);
-    }
-    __syncthreads();
-  }
-}
-
-// tile_sort_kernel and tile_fill_kernel (below) in one launch: the sorted masks stay in LDS and the rows are filled from
-// there -- the masks of a tile are needed by nothing else, so their way back to global memory and a launch with its
-// dependent loads (tile -> union size -> masks) are saved.
-__global__ __launch_bounds__(256) void tile_sort_fill_kernel(const int cap, const int np_max, const int *__restrict__ tile_nu,
-                                                             int *__restrict__ tu, const unsigned short *__restrict__ tmask,
-                                                             const int nclus, const long long *__restrict__ off,
-                                                             const int *__restrict__ split, unsigned short *__restrict__ lj16)
-{
-  extern __shared__ unsigned long long s_key[];                                   // [np_max] keys of the segment being sorted
-  unsigned short *s_fm = reinterpret_cast<unsigned short *>(s_key + np_max);      // [cap] masks in final order
-  const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  const int nU = tile_nu[2 * t], N0 = tile_nu[2 * t + 1];
-  int *mem = tu + (size_t) t * cap;
-  const unsigned short *mm = tmask + (size_t) t * cap;
-  // (everything the fill needs from global memory is requested before the sort)
-  const int gq = tid / 16, sq = tid % 16, glane0 = lane - sq;
-  const int kc = t * MDP_TILE + gq;
-  const bool have = kc < nclus;
-  const long long b0 = off[kc];
-  const int len[2] = {split[kc], (int) (off[kc + 1] - b0) - split[kc]}; // padded segment lengths (tile_scan_kernel)
-  for (int seg = 0; seg < 2; seg++) {
-    const int b = seg ? N0 : 0, n = (seg ? nU : N0) - b;
-    if (n <= 1) { // (block-uniform)
-      if (n == 1 && tid == 0) s_fm[b] = mm[b];
-      continue;
-    }
-    int np = 2;
-    while (np < n) np <<= 1;
-    for (int i = tid; i < np; i += 256)
-      s_key[i] = i < n ? (((unsigned long long) (unsigned) mem[b + i]) << 16) | mm[b + i] : ~0ull;
-    __syncthreads();
-    for (int k = 2; k <= np; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int q = tid; q < (np >> 1); q += 256) {
-          const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), p = i | j;
-          const unsigned long long x = s_key[i], y = s_key[p];
-          if ((x > y) == ((i & k) == 0)) {
-            s_key[i] = y;
-            s_key[p] = x;
-          }
-        }
-        __syncthreads();
-      }
-    for (int i = tid; i < n; i += 256) {
-      const unsigned long long v = s_key[i];
-      mem[b + i] = (int) (v >> 16);
-      s_fm[b + i] = (unsigned short) (v & 0xFFFFull);
-    }
-    __syncthreads();
-  }
-  __syncthreads();
-  unsigned short *row = lj16 + b0;
-  const unsigned long long below = (1ull << sq) - 1ull;
-  for (int seg = 0; seg < 2; seg++) {
-    const int ub = seg ? N0 : 0, ue = seg ? nU : N0;
-    int n = 0;
-    for (int base = ub; base < ue; base += 16) {
-      const int u = base + sq;
-      const bool k = have && u < ue && ((s_fm[u < ue ? u : ub] >> gq) & 1);
-      const unsigned long long bal = (__ballot(k) >> glane0) & 0xFFFFull;
-      if (k) row[n + __popcll(bal & below)] = (unsigned short) u;
-      n += __popcll(bal);
-    }
-    for (int q = n + sq; q < len[seg]; q += 16) row[q] = (unsigned short) nU; // padding: the dummy slot
-    row += len[seg];
-  }
-}
-
-// sorts the unions; with `fill` also writes the rows (then tile_fill_kernel must not follow).  *filled tells the caller.
-static int tile_sort_launch(mdp_ctx *c, int ntile, int nclus = 0, bool fill = false, bool *filled = nullptr)
-{
-  if (filled) *filled = false;
-  if (const char *e = getenv("MDP_TILE_SORT"))
-    if (atoi(e) == 0) return MDP_OK;
-  int np = 2;
-  while (np < c->tile_maxu) np <<= 1;
-  if (fill) {
-    const size_t lds = (size_t) np * sizeof(unsigned long long) + (size_t) c->tile_cap * sizeof(unsigned short);
-    if (lds > 48 * 1024)
-      MDP_HIP(c, hipFuncSetAttribute((const void *) tile_sort_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    tile_sort_fill_kernel<<<ntile, 256, lds, c->stream>>>(c->tile_cap, np, c->tile_nu.p, c->tu.p, c->tmask.p, nclus,
-                                                          c->lj_off.p, c->lj_split.p, c->lj16.p);
-    MDP_HIP(c, hipGetLastError());
-    if (filled) *filled = true;
-    return MDP_OK;
-  }
-  const size_t lds = (size_t) np * sizeof(unsigned long long);
-  if (lds > 48 * 1024)
-    MDP_HIP(c, hipFuncSetAttribute((const void *) tile_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-  tile_sort_kernel<<<ntile, 256, lds, c->stream>>>(c->tile_cap, c->tile_nu.p, c->tu.p, c->tmask.p);
-  MDP_HIP(c, hipGetLastError());
-  return MDP_OK;
-}
-
-// Pass 2: each cluster (16 lanes) walks its tile's masks in union order and keeps the entries with its bit;
-// the Mo segment and the S segment are each padded to a whole 16-lane step with the dummy index nU
-__global__ __launch_bounds__(256) void tile_fill_kernel(const int nclus, const int cap,
-                                                        const int *__restrict__ tile_nu,
-                                                        const unsigned short *__restrict__ tmask,
-                                                        const long long *__restrict__ off,
-                                                        const int *__restrict__ split,
-                                                        unsigned short *__restrict__ lj16)
-{
-  const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  const int gq = tid / 16, sq = tid % 16, glane0 = lane - sq;
-  const int kc = t * MDP_TILE + gq;
-  const bool have = kc < nclus;
-  const int nU = tile_nu[2 * t], N0 = tile_nu[2 * t + 1];
-  const unsigned short *mm = tmask + (size_t) t * cap;
-  const long long b = off[kc];
-  const int len[2] = {split[kc], (int) (off[kc + 1] - b) - split[kc]}; // padded segment lengths (tile_scan_kernel)
-  unsigned short *row = lj16 + b;
-  const unsigned long long below = (1ull << sq) - 1ull;
-  for (int seg = 0; seg < 2; seg++) {
-    const int ub = seg ? N0 : 0, ue = seg ? nU : N0;
-    int n = 0;
-    for (int base = ub; base < ue; base += 16) {
-      const int u = base + sq;
-      const bool k = have && u < ue && ((mm[u] >> gq) & 1);
-      const unsigned long long bal = (__ballot(k) >> glane0) & 0xFFFFull;
-      if (k) row[n + __popcll(bal & below)] = (unsigned short) u;
-      n += __popcll(bal);
-    }
-    for (int q = n + sq; q < len[seg]; q += 16) row[q] = (unsigned short) nU; // padding: the dummy slot
-    row += len[seg];
-  }
-}
-
-// Dynamic pruning of the rows (between list builds): every row entry is tested against the cluster's atoms at
-// the CURRENT positions and kept when it lies within (upper window bound + buffer) of one of them; the kept entries
-// are compacted into a second set of rows at the same offsets (segments padded as tile_scan_kernel pads them).
-// The list skin -- a third of the entries of a list built with 1 A of it -- then costs a pass of this kernel every
-// few tens of steps instead of an evaluation in every step; the rows as built stay, the buffer has its own
-// displacement trigger (moved_kernel), and an entry is never missed: it enters a window only after the two atoms
-// together moved the buffer, i.e. one of them half of it.
-struct PruneLimits {
-  double rsq[4]; // (window upper bound + buffer)^2 per pair type ti * 2 + tj
-};
-template <int CL>
-__global__ __launch_bounds__(256) void tile_prune_kernel(const PruneLimits lim, const int nlocal, const int nclus,
-                                                         const double4 *__restrict__ xq, const int cap, const int capL,
-                                                         const int *__restrict__ tu, const int *__restrict__ tile_nu,
-                                                         const long long *__restrict__ lj_off,
-                                                         const int *__restrict__ lj_split,
-                                                         const unsigned short *__restrict__ lj16,
-                                                         unsigned short *__restrict__ lj16_in,
-                                                         int *__restrict__ len_in, int *__restrict__ split_in)
-{
-  // The tile's rows (contiguous in memory) are staged in LDS with 16-byte loads, compacted there in place -- a
-  // row's kept entries never outrun its read position, and a row belongs to one 16-lane group of one wave -- and
-  // written back whole with 16-byte stores: no 2-byte global traffic, no global load inside the loop.  What lies
-  // behind a row's new length stays what it was (valid indices: the kernels read a few entries past a segment).
-  constexpr int L = 16, SK = 3;
-  extern __shared__ double s_pos[]; // [capL][3], then the rows
-  unsigned short *__restrict__ s_rows = reinterpret_cast<unsigned short *>(s_pos + 3 * (size_t) capL);
-  const int tid = threadIdx.x, lane = tid & 63, s = lane % L, glane0 = lane - s;
-  const int t = blockIdx.x;
-  const int kc = t * MDP_TILE + tid / L;
-  const int nU = tile_nu[2 * t];
-  const int *__restrict__ mem = tu + (size_t) t * cap;
-  const long long rb = lj_off[(size_t) t * MDP_TILE];
-  const int rtot = (int) (lj_off[(size_t) t * MDP_TILE + MDP_TILE] - rb); // entries of the whole tile (multiple of 16)
-  {
-    int sidx[SK];
-#pragma unroll
-    for (int k = 0; k < SK; k++) sidx[k] = mem[tid + 256 * k]; // (rows are cap >= 2048 long: always in bounds)
-    double4 sv[SK];
-#pragma unroll
-    for (int k = 0; k < SK; k++) sv[k] = xq[tid + 256 * k < nU ? sidx[k] : 0];
-    const uint4 *__restrict__ src = reinterpret_cast<const uint4 *>(lj16 + rb);
-    uint4 *__restrict__ dst = reinterpret_cast<uint4 *>(s_rows);
-    for (int e = tid; e * 8 < rtot; e += 256) dst[e] = src[e];
-#pragma unroll
-    for (int k = 0; k < SK; k++) {
-      const int u = tid + 256 * k;
-      if (u < nU) {
-        s_pos[3 * u] = sv[k].x;
-        s_pos[3 * u + 1] = sv[k].y;
-        s_pos[3 * u + 2] = sv[k].z;
-      }
-    }
-    for (int u = tid + 256 * SK; u < nU; u += 256) {
-      const double4 v = xq[mem[u]];
-      s_pos[3 * u] = v.x;
-      s_pos[3 * u + 1] = v.y;
-      s_pos[3 * u + 2] = v.z;
-    }
-  }
-  const long long b = lj_off[kc];
-  const int cnt = __builtin_amdgcn_readfirstlane((int) (lj_off[kc + 1] - b));
-  const int split = __builtin_amdgcn_readfirstlane(lj_split[kc]);
-  unsigned short *__restrict__ row = s_rows + (int) (b - rb);
-  double4 xa[CL];
-  bool real[CL];
-  int ta[CL];
-#pragma unroll
-  for (int c = 0; c < CL; c++) {
-    const int ia = kc * CL + c;
-    real[c] = kc < nclus && ia < nlocal;
-    xa[c] = xq[real[c] ? ia : nlocal - 1];
-    ta[c] = (int) xa[c].w;
-    if (ta[c] < 0) { // type mapped to NULL: takes part in nothing
-      real[c] = false;
-      ta[c] = 0;
-    }
-    ta[c] = ta[c] > 1 ? 1 : ta[c]; // (the two classes of tile_scan_kernel)
-  }
-  __syncthreads();
-  const unsigned long long below = (1ull << s) - 1ull;
-  int pseg[2];
-  int base = 0;
-#pragma unroll
-  for (int seg = 0; seg < 2; seg++) {
-    const int kb = seg ? split : 0, ke = seg ? cnt : split;
-    double lim_c[CL];
-#pragma unroll
-    for (int c = 0; c < CL; c++) lim_c[c] = lim.rsq[ta[c] * 2 + seg];
-    int n = 0;
-    for (int k = kb; k < ke; k += L) { // (segments are whole 16-lane steps, equally long for the rows of a wave)
-      const int li = (int) row[k + s];
-      bool keep = false;
-      if (li < nU) {
-        const double xj = s_pos[3 * li], yj = s_pos[3 * li + 1], zj = s_pos[3 * li + 2];
-#pragma unroll
-        for (int c = 0; c < CL; c++) {
-          const double dx = xa[c].x - xj, dy = xa[c].y - yj, dz = xa[c].z - zj;
-          keep = keep || (real[c] && dx * dx + dy * dy + dz * dz <= lim_c[c]);
-        }
-      }
-      const unsigned long long gb = (__ballot(keep) >> glane0) & 0xFFFFull;
-      // (the read of this trip is complete for the whole wave before any lane writes: same instruction stream)
-      if (keep) row[base + n + __popcll(gb & below)] = (unsigned short) li;
-      n += __popcll(gb);
-    }
-    int p = (n + 15) & ~15;
-#pragma unroll
-    for (int o = 16; o < 64; o <<= 1) p = max(p, __shfl_xor(p, o, 64));
-    for (int q = n + s; q < p; q += L) row[base + q] = (unsigned short) nU; // padding: the dummy slot
-    pseg[seg] = p;
-    base += p;
-  }
-  if (s == 0) {
-    split_in[kc] = pseg[0];
-    len_in[kc] = pseg[0] + pseg[1];
-  }
-  __syncthreads();
-  {
-    const uint4 *__restrict__ src = reinterpret_cast<const uint4 *>(s_rows);
-    uint4 *__restrict__ dst = reinterpret_cast<uint4 *>(lj16_in + rb);
-    for (int e = tid; e * 8 < rtot; e += 256) dst[e] = src[e];
-  }
-}
-
-// does the tile's union reach a remote ghost?  Such tiles wait for the halo.
-__global__ __launch_bounds__(256) void tile_boundary_kernel(const int ntile, const int cap, const int remote_start,
-                                                            const int *__restrict__ tile_nu,
-                                                            const int *__restrict__ tu, int *__restrict__ is_int,
-                                                            int *__restrict__ is_bnd)
-{
-  const int lane = threadIdx.x & 63;
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= ntile) return;
-  const int *mem = tu + (size_t) t * cap;
-  const int nU = tile_nu[2 * t];
-  int hit = 0;
-  for (int u = lane; u < nU; u += 64) hit |= mem[u] >= remote_start;
-  hit = __any(hit);
-  if (lane == 0) {
-    is_int[t] = !hit;
-    is_bnd[t] = hit;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // repack at every neighbor (re)build: master CSR list -> REBO candidates + trimmed LJ list
 // ------------------------------------------------------------------------------------------------
@@ -3061,164 +2447,6 @@ __global__ __launch_bounds__(256) void cand_csr_kernel(const RebomosDev P, const
   if (have && s == 0) cnt[i] = n;
 }
 
-// tile_scan_kernel with the union gathered from the host rows of the tile's atoms: the same atom is listed by many of
-// them, so the members go through a hash table in LDS (key = atom index, value = the 16-bit cluster mask | element
-// class << 16) and are compacted element 0 first.  tile_sort_kernel orders every segment by atom index afterwards, so
-// the order of insertion leaves no trace.
-template <int CL>
-__global__ __launch_bounds__(256) void tile_scan_csr_kernel(const RebomosDev P, const int nclus, const int nlocal,
-                                                            const double4 *__restrict__ xq,
-                                                            const long long *__restrict__ nb_off,
-                                                            const int *__restrict__ nb, const int cap,
-                                                            int *__restrict__ tu, unsigned short *__restrict__ tmask,
-                                                            int *__restrict__ tile_nu, int *__restrict__ cnt,
-                                                            int *__restrict__ split, int *__restrict__ tile_flag)
-{
-  constexpr int NA = MDP_TILE * CL;
-  extern __shared__ int s_dyn[];
-  const int HS = 2 * cap; // (power of two: cap is)
-  int *s_key = s_dyn;                                       // [HS]
-  int *s_val = s_dyn + HS;                                  // [HS]
-  unsigned short *s_fm = (unsigned short *) (s_dyn + 2 * HS); // [cap] masks in final order
-  __shared__ double4 s_xa[NA];
-  __shared__ double s_cut[NA][2];
-  __shared__ int s_count, s_over, s_rowsum, s_w0[4], s_w1[4];
-  const int t = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  for (int h = tid; h < HS; h += 256) {
-    s_key[h] = -1;
-    s_val[h] = 0;
-  }
-  if (tid == 0) s_count = s_over = s_rowsum = 0;
-  if (tid < NA) {
-    const int ia = t * NA + tid;
-    bool valid = ia < nlocal;
-    const double4 xa = xq[valid ? ia : (nlocal > 0 ? nlocal - 1 : 0)];
-    int ta = (int) xa.w;
-    if (ta < 0) valid = false;
-    ta = ta > 1 ? 1 : ta;
-    s_xa[tid] = xa;
-    s_cut[tid][0] = valid ? P.ljlist_cutsq[ta * 2 + 0] : -1.0;
-    s_cut[tid][1] = valid ? P.ljlist_cutsq[ta * 2 + 1] : -1.0;
-  }
-  __syncthreads();
-  // every wave walks the rows of NA/4 atoms, 64 entries a trip
-  for (int a = wave; a < NA; a += 4) {
-    const int ia = t * NA + a;
-    if (ia >= nlocal || s_cut[a][0] < 0.0) continue; // (wave-uniform)
-    const double4 xa = s_xa[a];
-    const long long b = nb_off[ia];
-    const int len = (int) (nb_off[ia + 1] - b);
-    for (int k = lane; k < len; k += 64) {
-      const int j = nb[b + k];
-      const double4 xj = xq[j];
-      int tj = (int) xj.w;
-      tj = tj > 1 ? 1 : tj;
-      if (tj < 0 || j == ia) continue; // (the host lists no atom in its own row; guarded anyway)
-      const double dx = xa.x - xj.x, dy = xa.y - xj.y, dz = xa.z - xj.z;
-      if (!(dx * dx + dy * dy + dz * dz <= s_cut[a][tj])) continue;
-      const int val = (1 << (a / CL)) | (tj << 16);
-      unsigned h = ((unsigned) j * 2654435761u) & (unsigned) (HS - 1);
-      for (int probe = 0; probe < HS; probe++) {
-        const int old = atomicCAS(&s_key[h], -1, j);
-        if (old == -1) {
-          if (atomicAdd(&s_count, 1) >= cap - 1) s_over = 1; // (slot nU is the kernels' dummy entry: nU <= cap - 1)
-        }
-        if (old == -1 || old == j) {
-          atomicOr(&s_val[h], val);
-          break;
-        }
-        h = (h + 1) & (unsigned) (HS - 1);
-      }
-    }
-  }
-  __syncthreads();
-  if (s_over) {
-    if (tid == 0) {
-      atomicOr(&tile_flag[0], 1);
-      tile_nu[2 * t] = tile_nu[2 * t + 1] = 0;
-    }
-    if (tid < MDP_TILE) cnt[t * MDP_TILE + tid] = split[t * MDP_TILE + tid] = 0;
-    return;
-  }
-  // compaction: thread tid owns the slots [tid * HS/256, (tid+1) * HS/256)
-  const int per = HS / 256;
-  int m0 = 0, m1 = 0;
-  for (int q = 0; q < per; q++) {
-    const int h = tid * per + q;
-    if (s_key[h] >= 0) {
-      if ((s_val[h] >> 16) & 1) m1++;
-      else m0++;
-    }
-  }
-  int i0 = m0, i1 = m1;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u0 = __shfl_up(i0, o, 64), u1 = __shfl_up(i1, o, 64);
-    if (lane >= o) {
-      i0 += u0;
-      i1 += u1;
-    }
-  }
-  if (lane == 63) {
-    s_w0[wave] = i0;
-    s_w1[wave] = i1;
-  }
-  __syncthreads();
-  const int N0 = s_w0[0] + s_w0[1] + s_w0[2] + s_w0[3];
-  const int N1 = s_w1[0] + s_w1[1] + s_w1[2] + s_w1[3];
-  const int nU = N0 + N1;
-  int p0 = i0 - m0, p1 = N0 + i1 - m1;
-  for (int w = 0; w < wave; w++) {
-    p0 += s_w0[w];
-    p1 += s_w1[w];
-  }
-  int *mem = tu + (size_t) t * cap;
-  unsigned short *mm = tmask + (size_t) t * cap;
-  for (int q = 0; q < per; q++) {
-    const int h = tid * per + q;
-    const int j = s_key[h];
-    if (j < 0) continue;
-    const int v = s_val[h];
-    const int u = ((v >> 16) & 1) ? p1++ : p0++;
-    mem[u] = j;
-    mm[u] = (unsigned short) (v & 0xFFFF);
-    s_fm[u] = (unsigned short) (v & 0xFFFF);
-  }
-  __syncthreads();
-  // row lengths: as tile_scan_kernel
-  const int gq = tid / 16, sq = tid % 16;
-  int c0 = 0, c1 = 0;
-  for (int u = sq; u < nU; u += 16) {
-    const int bit = (s_fm[u] >> gq) & 1;
-    c0 += u < N0 ? bit : 0;
-    c1 += u < N0 ? 0 : bit;
-  }
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) {
-    c0 += __shfl_xor(c0, o, 64);
-    c1 += __shfl_xor(c1, o, 64);
-  }
-  int q0 = (c0 + 15) & ~15, q1 = (c1 + 15) & ~15;
-#pragma unroll
-  for (int o = 16; o < 64; o <<= 1) {
-    q0 = max(q0, __shfl_xor(q0, o, 64));
-    q1 = max(q1, __shfl_xor(q1, o, 64));
-  }
-  const int kc = t * MDP_TILE + gq;
-  if (sq == 0) {
-    cnt[kc] = q0 + q1;
-    split[kc] = q0;
-    atomicAdd(&s_rowsum, q0 + q1);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    tile_nu[2 * t] = nU;
-    tile_nu[2 * t + 1] = N0;
-    if (nU > __hip_atomic_load(&tile_flag[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&tile_flag[1], nU);
-    if (s_rowsum > __hip_atomic_load(&tile_flag[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&tile_flag[2], s_rowsum);
-  }
-}
-
 // rev[slot of j in cand(a)] = absolute slot of a in cand(j), for owned a (static between list builds)
 // rev16: the first 16 reverse slots of every owned atom at a fixed stride (-1 beyond the row), so that the
 // gather reaches a slot record in two dependent loads instead of three (no row offset to fetch first)
@@ -3351,11 +2579,6 @@ __global__ __launch_bounds__(256) void pack_cand_kernel(const int n, const int W
   const int c = list[gid];
   const int off = cand_off[c], nc = cand_off[c + 1] - off;
   pk[idx] = t < nc ? cand[off + t] : -1;
-}
-
-__global__ void zero_small_kernel(double *acc, int n)
-{
-  if (threadIdx.x < n) acc[threadIdx.x] = 0.0;
 }
 
 } // namespace
@@ -3498,31 +2721,45 @@ static void repack_diag(mdp_ctx *c)
   }
 }
 
-int mdp_rebomos_repack(mdp_ctx *c)
+// ---- the stages of mdp_rebomos_repack, in the order it runs them ------------------------------------------------------
+// what the stages of one list build share
+struct Repack {
+  bool from_host = false; // candidates and rows from the host's neighbor list instead of the bin grid
+  bool want16 = false;    // tile rows wanted (else, or when a union outgrows LDS: per-cluster lists of global indices)
+  int cl = MDP_CLUSTER, nclus = 0;
+  int Rc = 1;             // stencil half width of the candidate sweep, in cells
+  int self_end = 0;       // atoms [nlocal, self_end) are periodic images of owned atoms: no centres of their own
+  const int *tag_dev = nullptr; // tags in the device's atom order
+  int *stage = nullptr;   // candidate rows at a fixed stride, written by the counting sweep (null: MDP_CAND_TWO_PASS)
+  int cand_total = 0;
+};
+constexpr int kRpPerBlock = 256 / RP_L; // atoms per workgroup of the list-building kernels
+
+// Inner skin (A): starts at 1.0 and ADAPTS -- when the displacement trigger fires again within 200 computes
+// (thermal vibration reaching half the skin: every ~60 steps at 300 K), the next lists get 0.2 A more, up to
+// the host's skin.  Rows grow ~5 % per step of 0.2 A; a rebuild costs ~10 steps' worth of compute.
+// MDP_INNER_SKIN fixes the value instead.
+static void repack_inner_skin(mdp_ctx *c)
 {
-  if (!c->have_rebomos) return mdp_fail(c, MDP_ESTATE, "rebomos parameters not set");
-  if (!c->atoms_set) return mdp_fail(c, MDP_ESTATE, "atoms not set");
-  c->host_check_armed = false;
   double s_in = c->skin > 0.0 ? c->skin : 2.0;
-  {
-    // Inner skin (A): starts at 1.0 and ADAPTS -- when the displacement trigger fires again within 200 computes
-    // (thermal vibration reaching half the skin: every ~60 steps at 300 K), the next lists get 0.2 A more, up to
-    // the host's skin.  Rows grow ~5 % per step of 0.2 A; a rebuild costs ~10 steps' worth of compute.
-    // MDP_INNER_SKIN fixes the value instead.
-    double want = c->skin_inner_auto;
-    if (const char *e = getenv("MDP_INNER_SKIN")) {
-      want = atof(e);
-    } else if (c->stale_rebuild && c->computes_since_build < 200 && want + 0.2 < s_in + 1e-9 &&
-               want + 0.2 < c->skin_inner_cap - 1e-9) { // (never back to a skin whose candidate rows overflowed)
-      want += 0.2;
-      c->skin_inner_auto = want;
-    }
-    c->stale_rebuild = false;
-    c->computes_since_build = 0;
-    if (want > 0.0 && want < s_in) s_in = want;
+  double want = c->skin_inner_auto;
+  if (const char *e = getenv("MDP_INNER_SKIN")) {
+    want = atof(e);
+  } else if (c->stale_rebuild && c->computes_since_build < 200 && want + 0.2 < s_in + 1e-9 &&
+             want + 0.2 < c->skin_inner_cap - 1e-9) { // (never back to a skin whose candidate rows overflowed)
+    want += 0.2;
+    c->skin_inner_auto = want;
   }
+  c->stale_rebuild = false;
+  c->computes_since_build = 0;
+  if (want > 0.0 && want < s_in) s_in = want;
   c->skin_inner = s_in;
   mdp_rebomos_fill_dev(c, s_in);
+}
+
+// layout of this build, the buffers every stage writes, the bin grid
+static int repack_setup(mdp_ctx *c, Repack &R)
+{
   const int nall = c->nall, nlocal = c->nlocal;
   hipStream_t st = c->stream;
   MDP_HIP(c, c->cand_cnt.reserve(nall + 1));
@@ -3530,19 +2767,19 @@ int mdp_rebomos_repack(mdp_ctx *c)
   // candidates and rows from the host's neighbor list instead of the bin grid (mdp_rebomos_host_list): see
   // cand_csr_kernel.  One atom per row then: the two atoms of a cluster share a row, and a pair the host excluded for
   // one of them must not come in through the other.
-  const bool from_host = c->rebo_host_list;
-  if (from_host && (!c->neigh_set || !c->nb_off.p || c->md))
+  R.from_host = c->rebo_host_list;
+  if (R.from_host && (!c->neigh_set || !c->nb_off.p || c->md))
     return mdp_fail(c, MDP_ESTATE, "rebomos: lists from the host's neighbor list were asked for (mdp_rebomos_host_list) but no list was handed over (mdp_set_neighbors_host)");
-  const int cl = from_host ? 1 : MDP_CLUSTER;
+  R.cl = R.from_host ? 1 : MDP_CLUSTER;
   // Lennard-Jones list layout: tiles of 16 two-atom rows; MDP_LJ_TILE=0: per-cluster lists of global indices (the
   // fallback when a union outgrows LDS).  (Tiles of 32 one-atom rows evaluate 25 % fewer pairs and measured slower,
   // 1.35 against 1.28 ms at 3.98 M atoms -- every LDS read and row index then serves one atom: DESIGN.md section 4.)
-  bool want16 = cl == 2 || from_host;
-  if (const char *e = getenv("MDP_LJ_TILE")) want16 = want16 && (atoi(e) != 0 || from_host);
-  c->cluster = cl;
-  const int nclus = (nlocal + cl - 1) / cl;
-  c->nclus = nclus;
-  const int nrow_max = ((nclus + MDP_TILE - 1) / MDP_TILE) * MDP_TILE + MDP_TILE; // whole tiles of rows
+  R.want16 = R.cl == 2 || R.from_host;
+  if (const char *e = getenv("MDP_LJ_TILE")) R.want16 = R.want16 && (atoi(e) != 0 || R.from_host);
+  c->cluster = R.cl;
+  R.nclus = (nlocal + R.cl - 1) / R.cl;
+  c->nclus = R.nclus;
+  const int nrow_max = ((R.nclus + MDP_TILE - 1) / MDP_TILE) * MDP_TILE + MDP_TILE; // whole tiles of rows
   MDP_HIP(c, c->lj_split.reserve(nrow_max + 1));
   MDP_HIP(c, c->lj_cnt.reserve(nrow_max + 1));
   MDP_HIP(c, c->lj_off.reserve(nrow_max + 2));
@@ -3555,9 +2792,8 @@ int mdp_rebomos_repack(mdp_ctx *c)
   // multi-GPU runs hide the halo exchange behind the REBO centres that reach no remote ghost.  (Round 1 split the
   // Lennard-Jones tiles instead, which needs the slot gather as a kernel of its own: 0.495 against 0.462 ms per
   // step of an 8-GPU sub-domain)
-  const bool centre_split = c->md && c->remote_start < nall;
-  c->centre_split = centre_split;
-  MDP_HIP(c, c->class_list.reserve((size_t) (centre_split ? MDP_NCLASS : MDP_NCLASS_HALF) * nall + 8));
+  c->centre_split = c->md && c->remote_start < nall;
+  MDP_HIP(c, c->class_list.reserve((size_t) (c->centre_split ? MDP_NCLASS : MDP_NCLASS_HALF) * nall + 8));
   MDP_HIP(c, c->class_count.reserve(MDP_NCLASS));
   MDP_HIP(c, c->xhold_all.reserve((size_t) 3 * nall + 3));
   MDP_HIP(c, hipMemsetAsync(c->is_center.p, 0, sizeof(int) * nall, st));
@@ -3574,171 +2810,118 @@ int mdp_rebomos_repack(mdp_ctx *c)
   ljcut = sqrt(ljcut);
   candcut = sqrt(candcut);
   MDP_TRY(mdp_bin_atoms(c, ljcut, c->bbox_lo, c->bbox_hi));
-  const int Rc = candcut <= 0.5 * ljcut ? 1 : 2; // cells are >= ljcut/2 wide
+  R.Rc = candcut <= 0.5 * ljcut ? 1 : 2; // cells are >= ljcut/2 wide
   // Resident runs know which ghosts are periodic images of owned atoms (owner, shift): those are no centres of their
   // own, the gather of their owned neighbours reads the owner centre's slots instead (rev_kernel).
   // Host mode knows the same once the library keeps the images itself (mdp_set_box_host): every ghost is one.
   const bool host_images = !c->md && c->host_ghosts_derived && c->ghost_owner.p && c->host_tag_dev.p;
-  const int self_end = host_images ? nall
-                       : (c->md && c->ghost_owner.p && c->tag.p && c->remote_start > nlocal)
-                           ? (c->remote_start < nall ? c->remote_start : nall) : nlocal;
-  const int *tag_dev = host_images ? c->host_tag_dev.p : c->tag.p; // tags in the device's atom order
-  const int per_block = 256 / RP_L;
-  const int nghost = nall - nlocal;
-  static const bool two_pass_env = getenv("MDP_CAND_TWO_PASS") && atoi(getenv("MDP_CAND_TWO_PASS")) != 0; // (A/B, tests)
-  const bool two_pass = two_pass_env && !from_host;
-  int *stage = nullptr;
-  if (!two_pass) {
-    MDP_HIP(c, c->cand_stage.reserve((size_t) nall * kCandStride + kCandStride));
-    stage = c->cand_stage.p;
-  }
-  if (from_host) {
-    if (nlocal)
-      cand_csr_kernel<0><<<(nlocal + per_block - 1) / per_block, 256, 0, st>>>(
-          c->rebomos, nall, nlocal, c->xq.p, c->nb_off.p, c->nb.p, c->cand_cnt.p, stage, c->is_center.p, self_end);
-    if (nghost)
-      cand_csr_kernel<1><<<(nghost + per_block - 1) / per_block, 256, 0, st>>>(
-          c->rebomos, nall, nlocal, c->xq.p, c->nb_off.p, c->nb.p, c->cand_cnt.p, stage, c->is_center.p, self_end);
-  } else {
-    if (nlocal)
-      cand_build_kernel<0><<<(nlocal + per_block - 1) / per_block, 256, 0, st>>>(
-          c->grid, Rc, c->rebomos, nall, nlocal, c->xq.p, c->cell_perm.p, c->cell_start.p, c->cand_cnt.p, nullptr,
-          stage, c->is_center.p, self_end, c->xq_cell.p);
-    if (nghost)
-      cand_build_kernel<1><<<(nghost + per_block - 1) / per_block, 256, 0, st>>>(
-          c->grid, Rc, c->rebomos, nall, nlocal, c->xq.p, c->cell_perm.p, c->cell_start.p, c->cand_cnt.p, nullptr,
-          stage, c->is_center.p, self_end, c->xq_cell.p);
-  }
-  MDP_HIP(c, hipGetLastError());
-  MDP_TRY(mdp_scan_exclusive_int(c, c->cand_cnt.p, c->cand_off.p, nall));
-  // Lennard-Jones lists: tile lists for the default cluster size, unless switched off or a union outgrows LDS
-  bool tiled = want16 && nclus > 0;
-  const int ntile = (nclus + MDP_TILE - 1) / MDP_TILE;
-  if (tiled) {
-    int cap = c->tile_cap > 0 ? c->tile_cap : 2048;
-    MDP_HIP(c, c->tile_flag.reserve(4));
-    MDP_HIP(c, c->tile_nu.reserve((size_t) 2 * ntile + 2));
-    MDP_HIP(c, c->lj_fix_stamp.reserve((size_t) ntile + 1));
-    MDP_HIP(c, hipMemsetAsync(c->lj_fix_stamp.p, 0, sizeof(int) * ((size_t) ntile + 1), st)); // (no compute has stamp 0)
-    for (;;) {
-      MDP_HIP(c, c->tu.reserve((size_t) ntile * cap));
-      MDP_HIP(c, c->tmask.reserve((size_t) ntile * cap));
-      MDP_HIP(c, hipMemsetAsync(c->tile_flag.p, 0, sizeof(int) * 3, st));
-      const size_t lds = (size_t) 14 * cap; // 4 wave segments of cap/2 (int + ushort) + cap ushort
-#define MDP_TS(CLV)                                                                                                   \
-  do {                                                                                                                \
-    if (lds > 48 * 1024)                                                                                              \
-      MDP_HIP(c, hipFuncSetAttribute((const void *) tile_scan_kernel<CLV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                     (int) lds));                                                                     \
-    tile_scan_kernel<CLV><<<ntile, 256, lds, st>>>(c->grid, c->rebomos, nclus, nlocal, c->xq.p, c->cell_perm.p,         \
-                                                   c->cell_start.p, cap, c->tu.p, c->tmask.p, c->tile_nu.p,           \
-                                                   c->lj_cnt.p, c->lj_split.p, c->tile_flag.p, c->xq_cell.p);         \
-  } while (0)
-      if (from_host) {
-        const size_t ldsh = (size_t) 18 * cap; // hash table of 2 cap (key, value) slots + cap masks
-#define MDP_TSH(CLV)                                                                                                  \
-  do {                                                                                                                \
-    if (ldsh > 48 * 1024)                                                                                             \
-      MDP_HIP(c, hipFuncSetAttribute((const void *) tile_scan_csr_kernel<CLV>,                                        \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsh));                        \
-    tile_scan_csr_kernel<CLV><<<ntile, 256, ldsh, st>>>(c->rebomos, nclus, nlocal, c->xq.p, c->nb_off.p, c->nb.p, cap,   \
-                                                        c->tu.p, c->tmask.p, c->tile_nu.p, c->lj_cnt.p, c->lj_split.p, \
-                                                        c->tile_flag.p);                                              \
-  } while (0)
-        if (cl == 1) MDP_TSH(1);
-        else MDP_TSH(2);
-#undef MDP_TSH
-      } else if (cl == 1) MDP_TS(1);
-      else MDP_TS(2);
-#undef MDP_TS
-      MDP_HIP(c, hipGetLastError());
-      int tf[3] = {0, 0, 0};
-      MDP_TRY(mdp_read_one(c, c->tile_flag.p, sizeof(int) * 3, tf));
-      if (!tf[0]) {
-        c->tile_cap = cap;
-        c->tile_maxu = tf[1];
-        c->tile_rowmax = tf[2];
-        break;
-      }
-      cap *= 2; // a union outgrew the segment: retry larger, give up beyond what LDS can stage
-      if (cap > 4096) {
-        tiled = false;
-        break;
-      }
-    }
-  }
-  c->lj_tiled = tiled;
-  c->ntile = tiled ? ntile : 0;
-  if (tiled) c->tile_rows_cl = cl;
-  if (tiled && getenv("MDP_DEBUG")) {
-    std::vector<int> h(2 * (size_t) ntile);
-    MDP_HIP(c, hipMemcpy(h.data(), c->tile_nu.p, sizeof(int) * 2 * ntile, hipMemcpyDeviceToHost));
-    double sum = 0;
-    for (int k = 0; k < ntile; k++) sum += h[2 * k];
-    fprintf(stderr, "[mdp] tile lists: %d tiles, cap %d, union mean %.1f max %d\n", ntile, c->tile_cap, sum / ntile,
-            c->tile_maxu);
+  R.self_end = host_images ? nall
+               : (c->md && c->ghost_owner.p && c->tag.p && c->remote_start > nlocal)
+                   ? (c->remote_start < nall ? c->remote_start : nall) : nlocal;
+  R.tag_dev = host_images ? c->host_tag_dev.p : c->tag.p;
+  return MDP_OK;
+}
 
-    int hist[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int k = 0; k < ntile; k++) hist[h[2 * k] / 200 < 8 ? h[2 * k] / 200 : 8]++;
-    for (int k = 0; k < 9; k++) fprintf(stderr, "[mdp]   union %4d.. : %d tiles\n", 200 * k, hist[k]);
+// candidate rows, first half: the counting sweep (which also writes what it counts into the staging rows) and the offsets
+static int repack_cand_count(mdp_ctx *c, Repack &R)
+{
+  const int nall = c->nall, nlocal = c->nlocal, nghost = nall - nlocal;
+  hipStream_t st = c->stream;
+  static const bool two_pass_env = getenv("MDP_CAND_TWO_PASS") && atoi(getenv("MDP_CAND_TWO_PASS")) != 0; // (A/B, tests)
+  if (!(two_pass_env && !R.from_host)) {
+    MDP_HIP(c, c->cand_stage.reserve((size_t) nall * kCandStride + kCandStride));
+    R.stage = c->cand_stage.p;
   }
-  if (nclus && !tiled && from_host)
+  for (int mode = 0; mode < 2; mode++) { // 0: owned atoms, 1: the ghosts they marked
+    const int n = mode ? nghost : nlocal;
+    if (!n) continue;
+    if (R.from_host)
+      MDP_TRY(mdp_launch(c, mode ? cand_csr_kernel<1> : cand_csr_kernel<0>, nblk(n, kRpPerBlock), 256, 0, st, c->rebomos, nall,
+                         nlocal, c->xq.p, c->nb_off.p, c->nb.p, c->cand_cnt.p, R.stage, c->is_center.p, R.self_end));
+    else
+      MDP_TRY(mdp_launch(c, mode ? cand_build_kernel<1> : cand_build_kernel<0>, nblk(n, kRpPerBlock), 256, 0, st, c->grid, R.Rc,
+                         c->rebomos, nall, nlocal, c->xq.p, c->cell_perm.p, c->cell_start.p, c->cand_cnt.p, nullptr, R.stage,
+                         c->is_center.p, R.self_end, c->xq_cell.p));
+  }
+  return mdp_scan_exclusive_int(c, c->cand_cnt.p, c->cand_off.p, nall);
+}
+
+// MDP_DEBUG=1: what the builder of the tile rows made
+static int repack_debug_unions(mdp_ctx *c)
+{
+  const int ntile = c->ntile;
+  std::vector<int> h(2 * (size_t) ntile);
+  MDP_HIP(c, hipMemcpy(h.data(), c->tile_nu.p, sizeof(int) * 2 * ntile, hipMemcpyDeviceToHost));
+  double sum = 0;
+  for (int k = 0; k < ntile; k++) sum += h[2 * k];
+  fprintf(stderr, "[mdp] tile lists: %d tiles, cap %d, union mean %.1f max %d\n", ntile, c->tile_cap, sum / ntile,
+          c->tile_maxu);
+  int hist[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int k = 0; k < ntile; k++) hist[h[2 * k] / 200 < 8 ? h[2 * k] / 200 : 8]++;
+  for (int k = 0; k < 9; k++) fprintf(stderr, "[mdp]   union %4d.. : %d tiles\n", 200 * k, hist[k]);
+  fprintf(stderr, "[mdp] row entries incl. padding: %lld (%.1f per cluster)\n", c->lj_total, (double) c->lj_total / c->nclus);
+  return MDP_OK;
+}
+
+// Lennard-Jones rows: tile rows through the builder of tiles.hip, unless switched off or a union outgrows LDS -- then
+// per-cluster lists of global indices.  The read of the candidate total rides on the read of the row total, either way.
+static int repack_lj_rows(mdp_ctx *c, Repack &R)
+{
+  const int nclus = R.nclus;
+  const MdpRead cand_read = {c->cand_off.p + c->nall, sizeof(int), &R.cand_total};
+  bool tiled = false;
+  if (R.want16 && nclus > 0) MDP_TRY(mdp_tile_rows_build(c, c->rebomos, R.cl, R.from_host, &cand_read, &tiled));
+  c->lj_tiled = tiled;
+  if (tiled) {
+    return getenv("MDP_DEBUG") ? repack_debug_unions(c) : MDP_OK;
+  }
+  c->ntile = 0;
+  if (nclus && R.from_host)
     return mdp_fail(c, MDP_ENOTIMPL, "rebomos: lists from the host's neighbor list need the tile lists (two-atom clusters, unions within LDS)");
-  if (nclus && !tiled) {
-    const int gb = (nclus + 15) / 16;
-#define MDP_CB(CLV, FILLV, OFFP, OUTP)                                                                              \
-  cluster_build_kernel<CLV, FILLV><<<gb, 256, 0, st>>>(c->grid, c->rebomos, nclus, nlocal, c->xq.p, c->cell_perm.p, \
-                                                       c->cell_start.p, c->lj_cnt.p, c->lj_split.p, OFFP, OUTP)
-    if (cl == 1) MDP_CB(1, false, nullptr, nullptr);
-    else MDP_CB(2, false, nullptr, nullptr);
-  }
-  MDP_HIP(c, hipGetLastError());
-  const int nrow = tiled ? ntile * MDP_TILE : nclus;
-  MDP_TRY(mdp_scan_exclusive_i64(c, c->lj_cnt.p, c->lj_off.p, nrow));
-  int cand_total = 0;
-  long long lj_total = 0;
-  {
-    const MdpRead rd[2] = {{c->cand_off.p + nall, sizeof(int), &cand_total}, {c->lj_off.p + nrow, sizeof(long long), &lj_total}};
-    MDP_TRY(mdp_read_small(c, rd, 2));
-  }
+  const auto count = R.cl == 1 ? cluster_build_kernel<1, false> : cluster_build_kernel<2, false>;
+  const auto fill = R.cl == 1 ? cluster_build_kernel<1, true> : cluster_build_kernel<2, true>;
+  if (nclus)
+    MDP_TRY(mdp_launch(c, count, nblk(nclus, 16), 256, 0, c->stream, c->grid, c->rebomos, nclus, c->nlocal, c->xq.p,
+                       c->cell_perm.p, c->cell_start.p, c->lj_cnt.p, c->lj_split.p, nullptr, nullptr));
+  MDP_TRY(mdp_scan_exclusive_i64(c, c->lj_cnt.p, c->lj_off.p, nclus));
+  const MdpRead rd[2] = {cand_read, {c->lj_off.p + nclus, sizeof(long long), &c->lj_total}};
+  MDP_TRY(mdp_read_small(c, rd, 2));
+  MDP_HIP(c, c->lj.reserve((size_t) c->lj_total + 1));
+  if (nclus)
+    MDP_TRY(mdp_launch(c, fill, nblk(nclus, 16), 256, 0, c->stream, c->grid, c->rebomos, nclus, c->nlocal, c->xq.p,
+                       c->cell_perm.p, c->cell_start.p, c->lj_cnt.p, c->lj_split.p, c->lj_off.p, c->lj.p));
+  mdp_rows_renewed(c);
+  return MDP_OK;
+}
+
+// candidate rows, second half: their CSR storage (the total is known now) and what is sized by it
+static int repack_cand_fill(mdp_ctx *c, const Repack &R)
+{
+  const int nall = c->nall, nlocal = c->nlocal, cand_total = R.cand_total;
+  hipStream_t st = c->stream;
   c->cand_total = cand_total;
-  c->lj_total = lj_total;
-  if (tiled && getenv("MDP_DEBUG"))
-    fprintf(stderr, "[mdp] row entries incl. padding: %lld (%.1f per cluster)\n", lj_total, (double) lj_total / nclus);
   MDP_HIP(c, c->cand.reserve((size_t) cand_total + 1));
-  if (tiled)
-    MDP_HIP(c, c->lj16.reserve((size_t) lj_total + 256)); // slack: rows are read a few steps past their end
-  else
-    MDP_HIP(c, c->lj.reserve((size_t) lj_total + 1));
   MDP_HIP(c, c->rev.reserve((size_t) cand_total + 1));
   MDP_HIP(c, c->rev16.reserve((size_t) 16 * nlocal + 16));
   MDP_HIP(c, c->fnbr.reserve((size_t) 4 * cand_total + 4));
   MDP_HIP(c, c->fown.reserve((size_t) 4 * nall + 4));
   MDP_HIP(c, hipMemsetAsync(c->fown.p, 0, sizeof(double) * 4 * nall, st)); // atoms that are no centre (NULL type) keep 0
-  if (nall && stage)
-    cand_compact_kernel<<<(nall + per_block - 1) / per_block, 256, 0, st>>>(nall, c->cand_off.p, stage, c->cand.p);
+  if (nall && R.stage)
+    MDP_TRY(mdp_launch(c, cand_compact_kernel, nblk(nall, kRpPerBlock), 256, 0, st, nall, c->cand_off.p, R.stage, c->cand.p));
   else if (nall)
-    cand_build_kernel<2><<<(nall + per_block - 1) / per_block, 256, 0, st>>>(
-        c->grid, Rc, c->rebomos, nall, nlocal, c->xq.p, c->cell_perm.p, c->cell_start.p, nullptr, c->cand_off.p,
-        c->cand.p, c->is_center.p, self_end, c->xq_cell.p);
-  bool rows_filled = false;
-  if (tiled) MDP_TRY(tile_sort_launch(c, ntile, nclus, /*fill=*/true, &rows_filled));
-  if (tiled && !rows_filled) // (MDP_TILE_SORT=0: the unions stay as found)
-    tile_fill_kernel<<<ntile, 256, 0, st>>>(nclus, c->tile_cap, c->tile_nu.p, c->tmask.p, c->lj_off.p, c->lj_split.p,
-                                            c->lj16.p);
-  c->prune_valid = false; // (new rows: the pruned copy is made at the next compute that wants it)
-  c->prune_stale = false;
-  c->prune_epoch++;
-  if (nclus && !tiled) {
-    const int gb = (nclus + 15) / 16;
-    if (cl == 1) MDP_CB(1, true, c->lj_off.p, c->lj.p);
-    else MDP_CB(2, true, c->lj_off.p, c->lj.p);
-  }
-#undef MDP_CB
-  MDP_HIP(c, hipGetLastError());
-  // launch classes of the units (tiles, or clusters without tile lists): small/large union for the LDS allocation
-  // of the tile kernel
-  const int nunit = tiled ? ntile : nclus;
+    MDP_TRY(mdp_launch(c, cand_build_kernel<2>, nblk(nall, kRpPerBlock), 256, 0, st, c->grid, R.Rc, c->rebomos, nall, nlocal,
+                       c->xq.p, c->cell_perm.p, c->cell_start.p, nullptr, c->cand_off.p, c->cand.p, c->is_center.p, R.self_end,
+                       c->xq_cell.p));
+  return MDP_OK;
+}
+
+// launch classes of the units (tiles, or clusters without tile lists): small/large union for the LDS allocation
+// of the tile kernel
+static int repack_launch_classes(mdp_ctx *c)
+{
+  hipStream_t st = c->stream;
+  const bool tiled = c->lj_tiled;
+  const int nunit = tiled ? c->ntile : c->nclus;
   c->lj_ordered = false;
   for (int q = 0; q <= 4; q++) c->lj_class_base[q] = q ? nunit : 0; // everything in class 0
   // the tile kernel is latency-bound (measured: t = 0.65 ms + 3.96 ms / resident workgroups per CU), so the
@@ -3746,38 +2929,40 @@ int mdp_rebomos_repack(mdp_ctx *c)
   int kSmallUnion = 1210; // (1210 + 1) * 24 B + 1.5 KB of static LDS = 30.6 KB: five workgroups and their allocation granules fit 160 KB
   if (const char *e = getenv("MDP_TILE_SMALL")) kSmallUnion = atoi(e) > 0 ? atoi(e) : kSmallUnion; // (tests)
   c->tile_small = tiled ? (c->tile_maxu < kSmallUnion ? c->tile_maxu : kSmallUnion) : 0;
-  if (nunit > 0 && tiled && c->tile_maxu > kSmallUnion) {
-    MDP_HIP(c, c->cl_flag.reserve((size_t) 6 * (nunit + 1)));
-    MDP_HIP(c, c->cl_pos.reserve((size_t) 4 * (nunit + 2)));
-    MDP_HIP(c, c->cl_order.reserve(nunit + 1));
-    int *flag4 = c->cl_flag.p;
-    unit_class_kernel<<<nblk(nunit), 256, 0, st>>>(nunit, nullptr,
-                                                   tiled ? c->tile_nu.p : nullptr, kSmallUnion, flag4);
-    MDP_HIP(c, hipGetLastError());
-    int total[4] = {0, 0, 0, 0};
-    MdpRead rd[4];
-    for (int q = 0; q < 4; q++) {
-      int *pos = c->cl_pos.p + (size_t) q * (nunit + 2);
-      MDP_TRY(mdp_scan_exclusive_int(c, flag4 + (size_t) q * (nunit + 1), pos, nunit));
-      rd[q] = {pos + nunit, sizeof(int), &total[q]};
-    }
-    MDP_TRY(mdp_read_small(c, rd, 4));
-    for (int q = 0; q < 4; q++) c->lj_class_base[q + 1] = c->lj_class_base[q] + total[q];
-    unit_order_kernel<<<nblk(nunit), 256, 0, st>>>(nunit, flag4, c->cl_pos.p, c->lj_class_base[1],
-                                                   c->lj_class_base[2], c->lj_class_base[3], c->cl_order.p);
-    MDP_HIP(c, hipGetLastError());
-    c->lj_ordered = true;
+  if (!(nunit > 0 && tiled && c->tile_maxu > kSmallUnion)) return MDP_OK;
+  MDP_HIP(c, c->cl_flag.reserve((size_t) 6 * (nunit + 1)));
+  MDP_HIP(c, c->cl_pos.reserve((size_t) 4 * (nunit + 2)));
+  MDP_HIP(c, c->cl_order.reserve(nunit + 1));
+  int *flag4 = c->cl_flag.p;
+  MDP_TRY(mdp_launch(c, unit_class_kernel, nblk(nunit), 256, 0, st, nunit, nullptr, c->tile_nu.p, kSmallUnion, flag4));
+  int total[4] = {0, 0, 0, 0};
+  MdpRead rd[4];
+  for (int q = 0; q < 4; q++) {
+    int *pos = c->cl_pos.p + (size_t) q * (nunit + 2);
+    MDP_TRY(mdp_scan_exclusive_int(c, flag4 + (size_t) q * (nunit + 1), pos, nunit));
+    rd[q] = {pos + nunit, sizeof(int), &total[q]};
   }
+  MDP_TRY(mdp_read_small(c, rd, 4));
+  for (int q = 0; q < 4; q++) c->lj_class_base[q + 1] = c->lj_class_base[q] + total[q];
+  MDP_TRY(mdp_launch(c, unit_order_kernel, nblk(nunit), 256, 0, st, nunit, flag4, c->cl_pos.p, c->lj_class_base[1],
+                     c->lj_class_base[2], c->lj_class_base[3], c->cl_order.p));
+  c->lj_ordered = true;
+  return MDP_OK;
+}
+
+// centre classes, reverse slots and the packed candidate heads of the classes.  *overflow: a candidate row outgrew the
+// 64-bit active mask (nothing is packed then).
+static int repack_centres(mdp_ctx *c, const Repack &R, bool *overflow)
+{
+  const int nall = c->nall, nlocal = c->nlocal;
+  hipStream_t st = c->stream;
+  *overflow = false;
   if (nall)
-    classify_kernel<<<nblk(nall), 256, 0, st>>>(c->rebomos, nall, nlocal, c->xq.p, c->cand_off.p, c->cand.p,
-                                                c->is_center.p, c->class_list.p, c->class_count.p,
-                                                centre_split ? c->remote_start : 0x7fffffff);
-  MDP_HIP(c, hipGetLastError());
+    MDP_TRY(mdp_launch(c, classify_kernel, nblk(nall), 256, 0, st, c->rebomos, nall, nlocal, c->xq.p, c->cand_off.p, c->cand.p,
+                       c->is_center.p, c->class_list.p, c->class_count.p, c->centre_split ? c->remote_start : 0x7fffffff));
   if (nlocal)
-    rev_kernel<<<(nlocal + per_block - 1) / per_block, 256, 0, st>>>(nlocal, c->cand_off.p, c->cand.p, c->rev.p,
-                                                                     c->rev16.p, c->flags.p, self_end, c->xq.p, tag_dev,
-                                                                     c->ghost_owner.p, c->rebomos);
-  MDP_HIP(c, hipGetLastError());
+    MDP_TRY(mdp_launch(c, rev_kernel, nblk(nlocal, kRpPerBlock), 256, 0, st, nlocal, c->cand_off.p, c->cand.p, c->rev.p,
+                       c->rev16.p, c->flags.p, R.self_end, c->xq.p, R.tag_dev, c->ghost_owner.p, c->rebomos));
   MDP_TRY(mdp_hold(c, nall, c->xhold_all.p));
   int hflags[4] = {0, 0, 0, 0};
   {
@@ -3788,6 +2973,66 @@ int mdp_rebomos_repack(mdp_ctx *c)
     return mdp_fail(c, MDP_ESTATE, "rebomos: a periodic image within rcmax + half the inner skin of an owned atom has no mirror "
                                    "slot in its owner's row (images inconsistent with the owned atoms' positions)");
   if (hflags[1]) {
+    *overflow = true;
+    return MDP_OK;
+  }
+  // packed candidate heads of the lane-group classes (widths = UA*G of rebo_centre_kernel<G>), per element
+  const int width[5] = {CentreCfg<4>::UA * 4, CentreCfg<8>::UA * 8, CentreCfg<12>::UA * 12, CentreCfg<16>::UA * 16,
+                        CentreCfg<32>::UA * 32};
+  // (the boundary half of a class directly behind its interior half: a launch over both -- the blocking orders of a
+  //  multi-GPU step, which have no use for two launches per class -- then finds one contiguous block)
+  size_t total = 0;
+  for (int g = 0; g < MDP_NCLASS_HALF; g++)
+    for (int half = 0; half < 2; half++) {
+      const int k = g + half * MDP_NCLASS_HALF;
+      c->pk_base[k] = total;
+      total += (size_t) c->h_class_count[k] * width[g / 2];
+    }
+  MDP_HIP(c, c->pk_cand.reserve(total + 1));
+  if (c->centre_split) { // ... and the two halves' centre lists once more as one list per class
+    size_t mtot = 0;
+    for (int g = 0; g < MDP_NCLASS_HALF; g++) {
+      c->merged_base[g] = mtot;
+      mtot += (size_t) c->h_class_count[g] + c->h_class_count[g + MDP_NCLASS_HALF];
+    }
+    MDP_HIP(c, c->class_merged.reserve(mtot + 1));
+    for (int g = 0; g < MDP_NCLASS_HALF; g++) {
+      const int n0 = c->h_class_count[g], n1 = c->h_class_count[g + MDP_NCLASS_HALF];
+      if (n0)
+        MDP_HIP(c, hipMemcpyAsync(c->class_merged.p + c->merged_base[g], c->class_list.p + (size_t) g * nall, sizeof(int) * n0,
+                                  hipMemcpyDeviceToDevice, st));
+      if (n1)
+        MDP_HIP(c, hipMemcpyAsync(c->class_merged.p + c->merged_base[g] + n0,
+                                  c->class_list.p + (size_t) (g + MDP_NCLASS_HALF) * nall, sizeof(int) * n1,
+                                  hipMemcpyDeviceToDevice, st));
+    }
+  }
+  for (int k = 0; k < MDP_NCLASS; k++) {
+    const int w = width[(k % MDP_NCLASS_HALF) / 2];
+    const long long n = (long long) c->h_class_count[k] * w;
+    if (n > 0)
+      MDP_TRY(mdp_launch(c, pack_cand_kernel, nblk(n), 256, 0, st, c->h_class_count[k], w, c->class_list.p + (size_t) k * nall,
+                         c->cand_off.p, c->cand.p, c->pk_cand.p + c->pk_base[k]));
+  }
+  return MDP_OK;
+}
+
+// The style's lists from the positions at hand; reads as its table of contents.
+int mdp_rebomos_repack(mdp_ctx *c)
+{
+  if (!c->have_rebomos) return mdp_fail(c, MDP_ESTATE, "rebomos parameters not set");
+  if (!c->atoms_set) return mdp_fail(c, MDP_ESTATE, "atoms not set");
+  c->host_check_armed = false;
+  Repack R;
+  bool overflow = false;
+  repack_inner_skin(c);
+  MDP_TRY(repack_setup(c, R));
+  MDP_TRY(repack_cand_count(c, R));
+  MDP_TRY(repack_lj_rows(c, R));
+  MDP_TRY(repack_cand_fill(c, R));
+  MDP_TRY(repack_launch_classes(c));
+  MDP_TRY(repack_centres(c, R, &overflow));
+  if (overflow) {
     if (getenv("MDP_DIAG")) repack_diag(c);
     // A candidate row holds the atoms within rcmax + inner skin and the active mask has 64 bits.  Rows that
     // overflow because of the SKIN (a dense system: the reference's REBO list itself, pair_rebomos.cpp:337-350,
@@ -3804,127 +3049,8 @@ int mdp_rebomos_repack(mdp_ctx *c)
     }
     return mdp_fail(c, MDP_EOVERFLOW, "rebomos: an atom has more than 64 neighbours inside rcmax+skin (Neighbor list overflow)");
   }
-  { // packed candidate heads of the lane-group classes (widths = UA*G of rebo_centre_kernel<G>), per element
-    const int width[5] = {CentreCfg<4>::UA * 4, CentreCfg<8>::UA * 8, CentreCfg<12>::UA * 12, CentreCfg<16>::UA * 16,
-                          CentreCfg<32>::UA * 32};
-    // (the boundary half of a class directly behind its interior half: a launch over both -- the blocking orders of a
-    //  multi-GPU step, which have no use for two launches per class -- then finds one contiguous block)
-    size_t total = 0;
-    for (int g = 0; g < MDP_NCLASS_HALF; g++)
-      for (int half = 0; half < 2; half++) {
-        const int k = g + half * MDP_NCLASS_HALF;
-        c->pk_base[k] = total;
-        total += (size_t) c->h_class_count[k] * width[g / 2];
-      }
-    MDP_HIP(c, c->pk_cand.reserve(total + 1));
-    if (centre_split) { // ... and the two halves' centre lists once more as one list per class
-      size_t mtot = 0;
-      for (int g = 0; g < MDP_NCLASS_HALF; g++) {
-        c->merged_base[g] = mtot;
-        mtot += (size_t) c->h_class_count[g] + c->h_class_count[g + MDP_NCLASS_HALF];
-      }
-      MDP_HIP(c, c->class_merged.reserve(mtot + 1));
-      for (int g = 0; g < MDP_NCLASS_HALF; g++) {
-        const int n0 = c->h_class_count[g], n1 = c->h_class_count[g + MDP_NCLASS_HALF];
-        if (n0)
-          MDP_HIP(c, hipMemcpyAsync(c->class_merged.p + c->merged_base[g], c->class_list.p + (size_t) g * nall, sizeof(int) * n0,
-                                    hipMemcpyDeviceToDevice, st));
-        if (n1)
-          MDP_HIP(c, hipMemcpyAsync(c->class_merged.p + c->merged_base[g] + n0,
-                                    c->class_list.p + (size_t) (g + MDP_NCLASS_HALF) * nall, sizeof(int) * n1,
-                                    hipMemcpyDeviceToDevice, st));
-      }
-    }
-    for (int k = 0; k < MDP_NCLASS; k++) {
-      const int w = width[(k % MDP_NCLASS_HALF) / 2];
-      const long long n = (long long) c->h_class_count[k] * w;
-      if (n > 0)
-        pack_cand_kernel<<<nblk(n), 256, 0, st>>>(c->h_class_count[k], w,
-                                                  c->class_list.p + (size_t) k * nall,
-                                                  c->cand_off.p, c->cand.p,
-                                                  c->pk_cand.p + c->pk_base[k]);
-    }
-    MDP_HIP(c, hipGetLastError());
-  }
   c->rebo_packed = true;
   c->style_builds++;
-  return MDP_OK;
-}
-
-// The same tile lists for another two-type style (AEAM, resident mode): `cutsq[ti*2+tj]` = squared list radius of
-// the pair; needs the bin grid of the current positions (mdp_bin_atoms).  Fills tu / tile_nu / lj_off / lj_split /
-// lj16 and c->nclus, ntile, tile_cap, tile_maxu; *ok = false when a union does not fit (caller keeps its CSR path).
-int mdp_tile_lists_build(mdp_ctx *c, const double cutsq[4], int cl, bool *ok)
-{
-  *ok = false;
-  const int nlocal = c->nlocal;
-  hipStream_t st = c->stream;
-  if (cl != 1) cl = 2;
-  const int nclus = (nlocal + cl - 1) / cl;
-  if (nclus <= 0) return MDP_OK;
-  const int ntile = (nclus + MDP_TILE - 1) / MDP_TILE;
-  const int nrow = ntile * MDP_TILE;
-  RebomosDev P = {};
-  for (int k = 0; k < 4; k++) P.ljlist_cutsq[k] = cutsq[k];
-  MDP_HIP(c, c->lj_split.reserve(nrow + 1));
-  MDP_HIP(c, c->lj_cnt.reserve(nrow + 1));
-  MDP_HIP(c, c->lj_off.reserve(nrow + 2));
-  MDP_HIP(c, c->tile_flag.reserve(4));
-  MDP_HIP(c, c->tile_nu.reserve((size_t) 2 * ntile + 2));
-  int cap = c->tile_cap > 0 ? c->tile_cap : 2048;
-  for (;;) {
-    MDP_HIP(c, c->tu.reserve((size_t) ntile * cap));
-    MDP_HIP(c, c->tmask.reserve((size_t) ntile * cap));
-    MDP_HIP(c, hipMemsetAsync(c->tile_flag.p, 0, sizeof(int) * 3, st));
-    const size_t lds = (size_t) 14 * cap;
-    if (cl == 1) {
-      if (lds > 48 * 1024)
-        MDP_HIP(c, hipFuncSetAttribute((const void *) tile_scan_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int) lds));
-      tile_scan_kernel<1><<<ntile, 256, lds, st>>>(c->grid, P, nclus, nlocal, c->xq.p, c->cell_perm.p, c->cell_start.p,
-                                                   cap, c->tu.p, c->tmask.p, c->tile_nu.p, c->lj_cnt.p, c->lj_split.p,
-                                                   c->tile_flag.p, c->xq_cell.p);
-    } else {
-      if (lds > 48 * 1024)
-        MDP_HIP(c, hipFuncSetAttribute((const void *) tile_scan_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int) lds));
-      tile_scan_kernel<2><<<ntile, 256, lds, st>>>(c->grid, P, nclus, nlocal, c->xq.p, c->cell_perm.p, c->cell_start.p,
-                                                   cap, c->tu.p, c->tmask.p, c->tile_nu.p, c->lj_cnt.p, c->lj_split.p,
-                                                   c->tile_flag.p, c->xq_cell.p);
-    }
-    MDP_HIP(c, hipGetLastError());
-    int tf[3] = {0, 0, 0};
-    MDP_TRY(mdp_read_one(c, c->tile_flag.p, sizeof(int) * 3, tf));
-    if (!tf[0]) {
-      c->tile_cap = cap;
-      c->tile_maxu = tf[1];
-      c->tile_rowmax = tf[2];
-      break;
-    }
-    cap *= 2;
-    if (cap > 4096) return MDP_OK; // *ok stays false
-  }
-  MDP_TRY(mdp_scan_exclusive_i64(c, c->lj_cnt.p, c->lj_off.p, nrow));
-  long long total = 0;
-  MDP_TRY(mdp_read_one(c, c->lj_off.p + nrow, sizeof(long long), &total));
-  MDP_HIP(c, c->lj16.reserve((size_t) total + 256));
-  bool rows_filled = false;
-  MDP_TRY(tile_sort_launch(c, ntile, nclus, /*fill=*/true, &rows_filled));
-  if (!rows_filled)
-    tile_fill_kernel<<<ntile, 256, 0, st>>>(nclus, c->tile_cap, c->tile_nu.p, c->tmask.p, c->lj_off.p, c->lj_split.p,
-                                            c->lj16.p);
-  MDP_HIP(c, hipGetLastError());
-  c->nclus = nclus;
-  c->ntile = ntile;
-  c->lj_total = total;
-  c->tile_rows_cl = cl;
-  c->prune_valid = false; // (new rows)
-  c->prune_stale = false;
-  c->prune_epoch++;
-  if (getenv("MDP_DEBUG"))
-    fprintf(stderr, "[mdp] tile lists (generic): %d tiles, cap %d, largest union %d, %.1f row entries per cluster\n", ntile,
-            c->tile_cap, c->tile_maxu, (double) total / nclus);
-  *ok = true;
   return MDP_OK;
 }
 
@@ -4071,103 +3197,6 @@ static void launch_centre3(mdp_ctx *c, int eflag, int vflag, int part)
   }
 }
 
-// (Re-)prune the tile rows from the current positions (tile_prune_kernel) and remember those positions.
-// lim_rsq[ti * 2 + tj]: (largest pair distance the kernels act on + buffer)^2.
-int mdp_tile_prune(mdp_ctx *c, const double lim_rsq[4])
-{
-  hipStream_t st = c->stream;
-  const int nrow = c->ntile * MDP_TILE;
-  MDP_HIP(c, c->lj_len_in.reserve(nrow + 1));
-  MDP_HIP(c, c->lj_split_in.reserve(nrow + 1));
-  MDP_HIP(c, c->xhold_prune.reserve((size_t) 3 * c->nall + 3));
-  if (c->prune_copied_epoch != c->prune_epoch) { // rows were rebuilt: the slack behind the last row as well
-    MDP_HIP(c, c->lj16_in.reserve((size_t) c->lj_total + 256)); // (reads past a segment's end must find valid indices)
-    MDP_HIP(c, hipMemcpyAsync(c->lj16_in.p + c->lj_total, c->lj16.p + c->lj_total, sizeof(unsigned short) * 256,
-                              hipMemcpyDeviceToDevice, st));
-    c->prune_copied_epoch = c->prune_epoch;
-  }
-  PruneLimits lim;
-  for (int k = 0; k < 4; k++) lim.rsq[k] = lim_rsq[k];
-  const int capL = (c->tile_maxu + 1 + 1) & ~1; // (the rows behind it start 16-byte aligned)
-  const size_t lds = (size_t) capL * 3 * sizeof(double) + (size_t) 2 * c->tile_rowmax + 32;
-  if (c->tile_rowmax <= 0 || lds > 160 * 1024) { // (rows of a tile do not fit LDS next to its union: no pruning)
-    c->prune_valid = false;
-    return MDP_OK;
-  }
-#define MDP_TP(CLV)                                                                                                    \
-  do {                                                                                                                 \
-    if (lds > 48 * 1024)                                                                                               \
-      MDP_HIP(c, hipFuncSetAttribute((const void *) tile_prune_kernel<CLV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                     (int) lds));                                                                      \
-    tile_prune_kernel<CLV><<<c->ntile, 256, lds, st>>>(lim, c->nlocal, c->nclus, c->xq.p, c->tile_cap, capL, c->tu.p,    \
-                                                       c->tile_nu.p, c->lj_off.p, c->lj_split.p, c->lj16.p,            \
-                                                       c->lj16_in.p, c->lj_len_in.p, c->lj_split_in.p);               \
-  } while (0)
-  if (c->tile_rows_cl == 1)
-    MDP_TP(1);
-  else
-    MDP_TP(2);
-#undef MDP_TP
-  MDP_HIP(c, hipGetLastError());
-  MDP_TRY(mdp_hold(c, c->nall, c->xhold_prune.p));
-  c->prune_valid = true;
-  c->prune_stale = false;
-  c->prune_epoch++; // (a displacement check launched before this says nothing about the new reference)
-  c->prune_copied_epoch = c->prune_epoch;
-  c->prunes++;
-  c->computes_since_prune = 0;
-  return MDP_OK;
-}
-
-// the buffer adapts like the inner skin: a pruning costs about a third of a pass over the rows, so a trigger that
-// fires within a dozen computes (thermal vibration reaching half the buffer) widens it, one that stays quiet for
-// long narrows it.  fired: the trigger of the current pruning has fired (MDP_PRUNE_BUFFER fixes the buffer).
-void mdp_prune_adapt(mdp_ctx *c, const double buf_max, const bool fired)
-{
-  const char *eb = getenv("MDP_PRUNE_BUFFER");
-  const double fixed_buf = eb ? atof(eb) : 0.0;
-  if (fixed_buf > 0.0) {
-    c->prune_buf = fixed_buf;
-    return;
-  }
-  if (!fired) return;
-  if (c->computes_since_prune < 12 && c->prune_buf + 0.1 <= buf_max + 1e-9) c->prune_buf += 0.1;
-  else if (c->computes_since_prune > 60 && c->prune_buf - 0.05 >= 0.2 - 1e-9) c->prune_buf -= 0.05;
-}
-
-// A style without list upkeep of its own (aeam) keeps the pruned rows current with this: reads the flags the
-// integrate kernel and the halo unpack of the previous step left (MdpStyleCheck) and prunes (again) when needed.
-// Call before the first kernel that walks the rows; positions (ghosts included) must be current -- unless
-// may_prune is false: then a pruning that is due is only reported (*due; the caller comes back once the halo has
-// arrived).
-int mdp_prune_upkeep(mdp_ctx *c, const double cut[4], const double skin, const bool may_prune, bool *due)
-{
-  if (due) *due = false;
-  const char *ep = getenv("MDP_PRUNE");
-  const int prune_on = ep ? atoi(ep) : 1;
-  if (!prune_on || !c->md || c->ntile <= 0 || c->tile_rows_cl != 2) {
-    c->prune_valid = false;
-    return MDP_OK;
-  }
-  MDP_TRY(mdp_sflag_collect(c, nullptr, nullptr)); // the previous step's check (integrate kernel, halo unpack)
-  mdp_prune_adapt(c, skin - 0.2, c->prune_valid && c->prune_stale);
-  if (!(c->prune_buf < skin)) {
-    c->prune_valid = false;
-    return MDP_OK;
-  }
-  if (!c->prune_valid || c->prune_stale) {
-    if (!may_prune) {
-      if (due) *due = true;
-      return MDP_OK;
-    }
-    double lim[4];
-    for (int k = 0; k < 4; k++) lim[k] = (cut[k] + c->prune_buf) * (cut[k] + c->prune_buf);
-    MDP_TRY(mdp_tile_prune(c, lim));
-  }
-  c->computes_since_prune++;
-  return MDP_OK;
-}
-
 // force_clear (optional) + compute on the device; results stay on the device (f, eatom, acc)
 // one launch class of the Lennard-Jones units (see unit_class_kernel): 0 small unions, 1 large unions (2, 3: unused)
 // Which variant of the tile kernel this compute takes (once per compute: the first class launch decides, the follow-up
@@ -4217,59 +3246,32 @@ static int launch_lj(mdp_ctx *c, int klass, bool gather, int eflag, int vflag, b
     skip_above = c->tile_small;
   }
   const bool ev = eflag || vflag; // force-only steps take the variant without energy/virial arithmetic
-  if (c->lj_tiled) {
-    const bool pruned = c->prune_valid; // rows pruned to the pairs that can be inside a window right now
-    const bool queue = c->lj_queue_now; // (decided once per compute: mdp_rebomos_run_end)
-    const bool small = !(klass & 1);
-    const int capL = ((small ? c->tile_small : c->tile_maxu) + 1 + 7) & ~7;
-    const size_t lds = (size_t) capL * 3 * sizeof(double);
-#define MDP_LJT_(EVV, GV, WV, CLV, QV)                                                                              \
-  do {                                                                                                              \
-    if (lds > 48 * 1024)                                                                                            \
-      MDP_HIP(c, hipFuncSetAttribute((const void *) rebo_lj_tile_kernel<EVV, GV, WV, CLV, QV>,                      \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));                       \
-    rebo_lj_tile_kernel<EVV, GV, WV, CLV, QV><<<count, 256, lds, st>>>(                                             \
-        c->rebomos, c->nlocal, order, first, c->nclus, c->xq.p, c->tile_cap, capL, skip_above, c->tu.p,            \
-        c->tile_nu.p, c->lj_off.p, pruned ? c->lj_len_in.p : nullptr, pruned ? c->lj_split_in.p : c->lj_split.p,    \
-        pruned ? c->lj16_in.p : c->lj16.p, c->cand_off.p, c->amask.p, c->rev.p, c->rev16.p,                         \
-        c->fnbr.p,                                                                                                  \
-        c->fown.p, c->f.p, c->eatom.p, c->acc.p, eflag, vflag, accumulate ? 1 : 0,                                 \
-        c->ovf.p + (size_t) 5 * c->ovf_stride, c->lj_fix_stamp.p, c->lj_stamp, c->lj_cq.p, c->lj_cq_cnt.p,          \
-        c->lj_cq_cap);                                                                                              \
-  } while (0)
-#define MDP_LJT(EVV, GV, WV)                                                                                        \
-  do {                                                                                                              \
-    if (c->cluster == 1) MDP_LJT_(EVV, GV, WV, 1, false);                                                           \
-    else if (queue) MDP_LJT_(EVV, GV, WV, 2, true);                                                                 \
-    else MDP_LJT_(EVV, GV, WV, 2, false);                                                                           \
-  } while (0)
-    // the force-only variants fit 5 waves per SIMD (<= 102 VGPRs); with small unions LDS allows 5 workgroups too
-    if (ev && gather) MDP_LJT(true, true, 4);
-    else if (ev) MDP_LJT(true, false, 4);
-    else if (gather) MDP_LJT(false, true, 5);
-    else MDP_LJT(false, false, 5);
-#undef MDP_LJT
-#undef MDP_LJT_
-    return MDP_OK;
-  }
-  constexpr int L = 16;
-  const int grid = (count + 256 / L - 1) / (256 / L);
-#define MDP_LJ(CLV, EVV, GV)                                                                                        \
-  rebo_lj_gather_kernel<CLV, L, EVV, GV><<<grid, 256, 0, st>>>(                                                      \
-      c->rebomos, c->nlocal, order, first, count, c->xq.p, c->lj_off.p, c->lj_split.p, c->lj.p, c->cand_off.p,       \
-      c->amask.p, c->rev.p, c->fnbr.p, c->fown.p, c->f.p, c->eatom.p, c->acc.p, eflag, vflag, accumulate ? 1 : 0)
-#define MDP_LJ2(CLV)                                                                                                \
-  do {                                                                                                              \
-    if (ev && gather) MDP_LJ(CLV, true, true);                                                                      \
-    else if (ev) MDP_LJ(CLV, true, false);                                                                          \
-    else if (gather) MDP_LJ(CLV, false, true);                                                                      \
-    else MDP_LJ(CLV, false, false);                                                                                 \
-  } while (0)
-  if (c->cluster == 1) MDP_LJ2(1);
-  else MDP_LJ2(2);
-#undef MDP_LJ2
-#undef MDP_LJ
-  return MDP_OK;
+  const MdpRows rows = mdp_rows(c); // (tiles: pruned to the pairs that can be inside a window right now, while a pruning is valid)
+  return mdp_with_bool(ev, [&](auto ev_c) {
+    return mdp_with_bool(gather, [&](auto gather_c) {
+      constexpr bool EV = decltype(ev_c)::value, G = decltype(gather_c)::value;
+      if (c->lj_tiled) {
+        const bool small = !(klass & 1);
+        const int capL = ((small ? c->tile_small : c->tile_maxu) + 1 + 7) & ~7;
+        // the force-only variants fit 5 waves per SIMD (<= 102 VGPRs); with small unions LDS allows 5 workgroups too
+        constexpr int W = EV ? 4 : 5;
+        // (the queue variant: decided once per compute, mdp_rebomos_run_end)
+        const auto kernel = c->cluster == 1     ? rebo_lj_tile_kernel<EV, G, W, 1, false>
+                            : c->lj_queue_now ? rebo_lj_tile_kernel<EV, G, W, 2, true>
+                                              : rebo_lj_tile_kernel<EV, G, W, 2, false>;
+        return mdp_launch(c, kernel, count, 256, (size_t) capL * 3 * sizeof(double), st, c->rebomos, c->nlocal, order, first,
+                          c->nclus, c->xq.p, c->tile_cap, capL, skip_above, c->tu.p, c->tile_nu.p, c->lj_off.p, rows.len,
+                          rows.split, rows.lj16, c->cand_off.p, c->amask.p, c->rev.p, c->rev16.p, c->fnbr.p, c->fown.p, c->f.p,
+                          c->eatom.p, c->acc.p, eflag, vflag, accumulate ? 1 : 0, c->ovf.p + (size_t) 5 * c->ovf_stride,
+                          c->lj_fix_stamp.p, c->lj_stamp, c->lj_cq.p, c->lj_cq_cnt.p, c->lj_cq_cap);
+      }
+      constexpr int L = 16;
+      const auto kernel = c->cluster == 1 ? rebo_lj_gather_kernel<1, L, EV, G> : rebo_lj_gather_kernel<2, L, EV, G>;
+      return mdp_launch(c, kernel, nblk(count, 256 / L), 256, 0, st, c->rebomos, c->nlocal, order, first, count, c->xq.p,
+                        c->lj_off.p, c->lj_split.p, c->lj.p, c->cand_off.p, c->amask.p, c->rev.p, c->fnbr.p, c->fown.p, c->f.p,
+                        c->eatom.p, c->acc.p, eflag, vflag, accumulate ? 1 : 0);
+    });
+  });
 }
 
 // behind the Lennard-Jones tile launches of a compute: the corrections of the pairs on the cubic inner spline, for the
@@ -4277,24 +3279,17 @@ static int launch_lj(mdp_ctx *c, int klass, bool gather, int eflag, int vflag, b
 static int launch_lj_cubic(mdp_ctx *c, int eflag, int vflag)
 {
   if (!c->lj_tiled || c->ntile <= 0) return MDP_OK;
-  const bool pruned = c->prune_valid;
   const bool queue = c->lj_queue_now;
+  const bool ev = eflag || vflag;
   if (queue) { // the queues the tile launches of this compute filled; tiles whose queues overflowed go on to the walk below
     int *h_count = mdp_pin(c, kPinCubic);
     long long want = (long long) *h_count + *h_count / 4 + 256;
     const int grid = (int) (want < c->ntile ? want : c->ntile);
-    const bool ev = eflag || vflag;
     const int *fix_list = c->ovf.p + (size_t) 5 * c->ovf_stride;
     int *walk_list = c->ovf.p + (size_t) 6 * c->ovf_stride;
-    if (ev)
-      rebo_lj_cubicq_kernel<2, true><<<grid, 256, 0, c->stream>>>(c->lj_fixtab.p, fix_list, walk_list, c->nlocal, c->nclus,
-                                                                  c->xq.p, c->tile_cap, c->tu.p, c->lj_cq.p, c->lj_cq_cnt.p,
-                                                                  c->lj_cq_cap, c->f.p, c->eatom.p, c->acc.p, eflag, vflag, h_count);
-    else
-      rebo_lj_cubicq_kernel<2, false><<<grid, 256, 0, c->stream>>>(c->lj_fixtab.p, fix_list, walk_list, c->nlocal, c->nclus,
-                                                                   c->xq.p, c->tile_cap, c->tu.p, c->lj_cq.p, c->lj_cq_cnt.p,
-                                                                   c->lj_cq_cap, c->f.p, c->eatom.p, c->acc.p, eflag, vflag, h_count);
-    MDP_HIP(c, hipGetLastError());
+    MDP_TRY(mdp_launch(c, ev ? rebo_lj_cubicq_kernel<2, true> : rebo_lj_cubicq_kernel<2, false>, grid, 256, 0, c->stream,
+                       c->lj_fixtab.p, fix_list, walk_list, c->nlocal, c->nclus, c->xq.p, c->tile_cap, c->tu.p, c->lj_cq.p,
+                       c->lj_cq_cnt.p, c->lj_cq_cap, c->f.p, c->eatom.p, c->acc.p, eflag, vflag, h_count));
   }
   const int capL = (c->tile_maxu + 1 + 7) & ~7;
   const size_t lds = (size_t) capL * 3 * sizeof(double);
@@ -4305,27 +3300,12 @@ static int launch_lj_cubic(mdp_ctx *c, int eflag, int vflag)
   long long want = (long long) *h_count + *h_count / 4 + 256;
   const int grid = (int) (want < c->ntile ? want : c->ntile);
   const int *fix_list = c->ovf.p + (size_t) (queue ? 6 : 5) * c->ovf_stride;
-#define MDP_LJC(CLV, EVV)                                                                                            \
-  do {                                                                                                                \
-    if (lds > 48 * 1024)                                                                                              \
-      MDP_HIP(c, hipFuncSetAttribute((const void *) rebo_lj_cubic_kernel<CLV, EVV>,                                   \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));                         \
-    rebo_lj_cubic_kernel<CLV, EVV><<<grid, 256, lds, c->stream>>>(                                                    \
-        c->lj_fixtab.p, fix_list, c->nlocal, c->nclus, c->xq.p, c->tile_cap, c->tu.p, c->tile_nu.p, c->lj_off.p,      \
-        pruned ? c->lj_len_in.p : nullptr, pruned ? c->lj_split_in.p : c->lj_split.p,                                 \
-        pruned ? c->lj16_in.p : c->lj16.p, c->f.p, c->eatom.p, c->acc.p, eflag, vflag, h_count);                      \
-  } while (0)
-  const bool ev = eflag || vflag;
-  if (c->cluster == 1) {
-    if (ev) MDP_LJC(1, true);
-    else MDP_LJC(1, false);
-  } else {
-    if (ev) MDP_LJC(2, true);
-    else MDP_LJC(2, false);
-  }
-#undef MDP_LJC
-  MDP_HIP(c, hipGetLastError());
-  return MDP_OK;
+  const MdpRows rows = mdp_rows(c);
+  const auto kernel = c->cluster == 1 ? (ev ? rebo_lj_cubic_kernel<1, true> : rebo_lj_cubic_kernel<1, false>)
+                                      : (ev ? rebo_lj_cubic_kernel<2, true> : rebo_lj_cubic_kernel<2, false>);
+  return mdp_launch(c, kernel, grid, 256, lds, c->stream, c->lj_fixtab.p, fix_list, c->nlocal, c->nclus, c->xq.p, c->tile_cap,
+                    c->tu.p, c->tile_nu.p, c->lj_off.p, rows.len, rows.split, rows.lj16, c->f.p, c->eatom.p, c->acc.p, eflag,
+                    vflag, h_count);
 }
 
 // parts: bit 0 = interior centres, bit 1 = boundary centres (+ the overflow pass, which must follow both)
@@ -4460,22 +3440,10 @@ int mdp_rebomos_run_end(mdp_ctx *c, int eflag, int vflag)
     // the kernels walk pruned rows (see tile_prune_kernel) -- resident runs with the deferred displacement trigger,
     // host mode with the blocking check every compute does anyway (rebomos_lists_stale); a per-atom-virial step
     // reads the rows as built
-    const char *ep = getenv("MDP_PRUNE");
-    const int prune_on = ep ? atoi(ep) : 1;
-    if (prune_on && c->lj_tiled && c->ntile > 0) {
-      mdp_prune_adapt(c, c->skin_inner - 0.2, c->prune_valid && c->prune_stale);
-      if (c->prune_buf < c->skin_inner) { // (a buffer as wide as the skin prunes nothing)
-        if (!c->prune_valid || c->prune_stale) {
-          double lim[4];
-          for (int k = 0; k < 4; k++) {
-            const double r = sqrt(c->rebomos.lj_rsq_hi[k]) + c->prune_buf;
-            lim[k] = r * r;
-          }
-          MDP_TRY(mdp_tile_prune(c, lim));
-        }
-        c->computes_since_prune++;
-      } else
-        c->prune_valid = false;
+    if (c->lj_tiled) {
+      double cut[4]; // (cut + buffer)^2 is the limit of the pruning
+      for (int k = 0; k < 4; k++) cut[k] = sqrt(c->rebomos.lj_rsq_hi[k]);
+      MDP_TRY(mdp_prune_upkeep(c, cut, c->skin_inner, /*own_check=*/true, /*may_prune=*/true, nullptr));
     } else
       c->prune_valid = false;
     mdp_time_mark(c, 3); // (a row pruning, when one was due, lies between marks 2 and 3)

@@ -236,6 +236,40 @@ def test_tile_kernel_variants_match_oracle(oracle, T, pot, env, monkeypatch):
     ctx.close()
 
 
+@pytest.mark.parametrize("cluster", ["2", "1"])
+def test_tile_rows_as_found_match_the_sorted_ones(pot, cluster, monkeypatch):
+    """The style's tile rows (mdp_tile_lists_build) with MDP_TILE_SORT=0 -- the unions as the scan found them, rows filled
+    by tile_fill_kernel -- against the default, which sorts the unions and fills the rows in one launch: a force-only
+    and a tallying compute on 500 atoms (250 two-atom clusters: the last tile is not full), both tile layouts."""
+    monkeypatch.setenv("MDP_AEAM_CLUSTER", cluster)
+    af, tabs = pot
+    s = S.jitter(S.fcc_cell(4.045, 5, frac_type2=0.1, seed=41), 0.06, seed=42)
+    s.mass[1:3] = af.mass
+    ntile = (s.n // int(cluster) + 15) // 16
+    res = []
+    for sort in ("1", "0"):
+        monkeypatch.setenv("MDP_TILE_SORT", sort)
+        ctx = capi.Context(0)
+        ctx.aeam_set_tables(tabs)
+        d = resident.DeviceDomain(ctx, capi.STYLE_AEAM, s, float(af.cut_table(tabs).max()) + 1.0, 1.0, None)
+        d.compute(0, 0)
+        f_only = ctx.md_download(d.nlocal, want=("f",))["f"]
+        d.compute(3, 1)
+        th = d.thermo()
+        got = ctx.md_download(d.nlocal, want=("f", "eatom"))
+        nu = ctx.md_download_int("tile_nu", d.nlocal)[:2 * ntile]    # (refused unless the tile rows were built)
+        order = np.argsort(d.tags_local)
+        ctx.close()
+        res.append((f_only[order], got["f"][order], got["eatom"][order], th, nu))
+    a, b = res
+    assert np.array_equal(a[4], b[4]) and a[4][::2].min() > 0    # the same unions, in another order
+    assert np.abs(b[0] - a[0]).max() < 1e-9
+    assert np.abs(b[1] - a[1]).max() < 1e-9
+    assert np.abs(b[2] - a[2]).max() < 1e-9
+    assert b[3]["pe"] == pytest.approx(a[3]["pe"], rel=1e-11)
+    assert np.allclose(b[3]["virial"], a[3]["virial"], rtol=1e-9, atol=1e-7)
+
+
 @pytest.mark.parametrize("nmetal,nang", [(3, 2), (7, 5)])
 def test_host_mode_with_device_lists_more_types(oracle, tmp_path, nmetal, nang):
     """the same drop-in path with five atom types (three metals, two angular: tile lists with per-entry types in

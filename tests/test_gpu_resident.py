@@ -142,6 +142,21 @@ def test_tile_lists_against_the_per_cluster_path_and_large_union_classes():
         assert np.allclose(th["virial"], th0["virial"], rtol=1e-10, atol=1e-7)
 
 
+def test_tile_rows_as_found_match_the_sorted_ones():
+    """MDP_TILE_SORT=0 leaves the unions in the order the scan found them and fills the rows with tile_fill_kernel, the
+    only route to that kernel; the default sorts every union and fills the rows in the same launch.  Both on 576
+    jittered atoms (18 tiles: more than one workgroup), with the tolerances of the test above."""
+    s = S.jitter(S.replicate(S.rebomos_bulk_cell(), (2, 1, 1)), 0.05, seed=3)
+    f0, e0, th0, i0 = _forces(s, {"MDP_TILE_SORT": "1"})
+    f1, e1, th1, i1 = _forces(s, {"MDP_TILE_SORT": "0"})
+    assert i0["tiled"] == 1 and i1["tiled"] == 1
+    assert i0["tiles"] == i1["tiles"] > 1 and i0["row_entries"] == i1["row_entries"]
+    assert np.abs(f1 - f0).max() < 1e-10
+    assert np.abs(e1 - e0).max() < 1e-10
+    assert th1["pe"] == pytest.approx(th0["pe"], rel=1e-12)
+    assert np.allclose(th1["virial"], th0["virial"], rtol=1e-10, atol=1e-7)
+
+
 def test_device_bytes_are_reported_per_context():
     """Pair::memory_usage() of a style must report ITS device memory, not every context's in the process"""
     L = capi.lib()
