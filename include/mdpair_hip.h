@@ -547,6 +547,46 @@ int mdp_langevin_off(mdp_ctx *ctx);
 int mdp_langevin_baths(mdp_ctx *ctx, int nbath, const mdp_langevin_config *cfg, const int *groupbit);
 int mdp_langevin_tally_bath(mdp_ctx *ctx, int bath, double *out);
 
+/* ---- Constant-flux heat sources on groups (LAMMPS fix heat with a constant eflux and no region; the plugin style
+ * `fix heat/mdp`) -----
+ * Up to MDP_HEAT_MAXSRC sources, source k on the atoms whose mask (mdp_md_set_mask / mdp_hnve_set_mask) has groupbit[k].
+ * Every final half that completes step n -- mdp_md_final_integrate, mdp_hnve_final, a deferred final half completed by a
+ * thermo / download / state read, the final half of mdp_md_final_initial_integrate -- is followed on the stream by the
+ * heat pass of step n for the sources with n % nevery == 0 (FixHeat::end_of_step):
+ *     heat   = eflux nevery dt ftm2v,   ke = (0.5 sum m v.v mvv2e) ftm2v,   vcm = sum m v / M      (sums over the group)
+ *     escale = (ke + heat - 0.5 vcm.vcm M) / (ke - 0.5 vcm.vcm M),   scale = sqrt(escale),   v = scale v - (scale - 1) vcm
+ * so the group keeps its momentum and its kinetic energy about its centre of mass changes by eflux nevery dt.  Three
+ * launches: per-block partial sums in fixed slots, one workgroup that adds them in a fixed order and leaves scale and
+ * (scale - 1) vcm in device memory, and the pass that rescales.  No float atomics, no host wait: a run is bitwise
+ * reproducible, and the same whether or not the host defers final halves -- with sources on the final and the initial
+ * half are never fused into one kernel.  dt and ftm2v are the context's own; M is summed once per set-up and mask upload.
+ *   setup:  replaces the sources that are on.  A final half pending at the call completes first, without heat.  Refused
+ *           (MDP_EINVAL / MDP_ESTATE, each with its cause): nsrc outside 1 .. MDP_HEAT_MAXSRC, a zero bit or a bit two
+ *           sources share, nevery < 1, a non-finite eflux, no mask for the current atoms, a source without atoms, atoms
+ *           in two sources and source atoms outside the integrate group (both with their count, taken on the device once
+ *           per set-up and per mask upload), a thermostat (mdp_nhc_setup, mdp_langevin_*) or the minimiser on the
+ *           context and a brick of several ranks -- those calls in turn refuse while sources are on.
+ *   run:    the step counter of the run that follows = first; it advances with every initial half, and a final half
+ *           before the first initial half (it belongs to the run before) gets no pass: step `first` is never heated.
+ *   state:  blocking; completes a deferred final half first.  out[0] scale of source src's last application (1 before
+ *           the first), [1..4) vcm, [4] the kinetic energy about the centre of mass before it (times ftm2v, as ke above),
+ *           [5] M, [6] applications so far, [7] the step of a latched error or -1.
+ *   errors: escale < 0 or a denominator that is not positive latches (step, source) on the device; this and every later
+ *           application leave v alone.  The next call that waits for the stream anyway (mdp_md_thermo, mdp_md_download,
+ *           mdp_hnve_download, mdp_heat_state, mdp_sync) fails with MDP_ESTATE "fix heat kinetic energy went negative
+ *           (source k, step n)", until mdp_heat_off. */
+#define MDP_HEAT_MAXSRC 4
+#define MDP_HEAT_STATE_LEN 8
+typedef struct {
+  double eflux;  /* energy / time, either sign */
+  int nevery;
+  double mvv2e;
+} mdp_heat_config;
+int mdp_heat_setup(mdp_ctx *ctx, int nsrc, const mdp_heat_config *cfg, const int *groupbit);
+int mdp_heat_run(mdp_ctx *ctx, long long first);
+int mdp_heat_state(mdp_ctx *ctx, int src, double *out /* MDP_HEAT_STATE_LEN */);
+int mdp_heat_off(mdp_ctx *ctx);
+
 /* ---- FIRE minimiser on the device (LAMMPS min_style fire, FIRE 2.0 with the eulerimplicit integrator and LAMMPS' defaults)
  * For a resident context on one rank, after mdp_md_setup + mdp_dd_setup (one brick) + mdp_dd_reneighbor.  An iteration
  * is two small launches next to the force compute: per-block partial sums of v.f, v.v, f.f and the largest |v_c| in

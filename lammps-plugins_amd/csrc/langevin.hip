@@ -319,6 +319,7 @@ int mdp_langevin_setup(mdp_ctx *c, const mdp_langevin_config *cfg)
 {
   if (!c || !cfg) return MDP_EINVAL;
   if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_langevin_setup: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
+  if (c->heat.on) return mdp_fail(c, MDP_ESTATE, "mdp_langevin_setup: heat sources (mdp_heat_setup) are on; mdp_heat_off first");
   if (c->nhc.on)
     return mdp_fail(c, MDP_ESTATE, "mdp_langevin_setup: the Nose-Hoover chain (mdp_nhc_setup) is on; one thermostat per context");
   MDP_TRY(lgv_check_config(c, "mdp_langevin_setup", cfg));
@@ -342,6 +343,7 @@ int mdp_langevin_baths(mdp_ctx *c, int nbath, const mdp_langevin_config *cfg, co
   if (nbath < 1 || nbath > MDP_LANGEVIN_MAXBATH)
     return mdp_fail(c, MDP_EINVAL, "mdp_langevin_baths: %d baths; a context takes 1 to %d", nbath, MDP_LANGEVIN_MAXBATH);
   if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_langevin_baths: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
+  if (c->heat.on) return mdp_fail(c, MDP_ESTATE, "mdp_langevin_baths: heat sources (mdp_heat_setup) are on; mdp_heat_off first");
   if (c->nhc.on)
     return mdp_fail(c, MDP_ESTATE, "mdp_langevin_baths: the Nose-Hoover chain (mdp_nhc_setup) is on; one kind of thermostat per context");
   for (int k = 0; k < nbath; k++) {

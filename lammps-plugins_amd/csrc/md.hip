@@ -712,6 +712,7 @@ int md_final_half(mdp_ctx *c, bool lgv_writeback = true)
   else if (c->nlocal)
     nve_final_kernel<false><<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, M);
   MDP_HIP(c, hipGetLastError());
+  if (c->heat.on) return mdp_heat_pass(c); // (heat sources: FixHeat::end_of_step of the step this half completes)
   return MDP_OK;
 }
 
@@ -727,6 +728,13 @@ int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, dou
   if (with_final && ((c->nhc.on && c->nhc.need_setup) || (c->lgv.on && c->lgv.need_setup))) {
     MDP_TRY(md_final_half(c, false));
     with_final = false;
+  }
+  // heat sources act between the final half of a step and the initial half of the next: the plain final half and their
+  // pass go first, on their own, and the kernel below is the initial half alone -- what a host that does not defer runs
+  if (c->heat.on) {
+    if (with_final) MDP_TRY(md_final_half(c));
+    with_final = false;
+    mdp_heat_count_step(c);
   }
   const double *vscale = nullptr;
   bool lgv = false, masked = false;
@@ -814,7 +822,7 @@ static int set_mask(mdp_ctx *c, const int *mask)
   if (!mask) {
     c->mask_set = false;
     c->mask_n = 0;
-    return MDP_OK;
+    return mdp_heat_mask(c, "");
   }
   MDP_HIP(c, hipSetDevice(c->device));
   const int n = c->nlocal;
@@ -825,6 +833,7 @@ static int set_mask(mdp_ctx *c, const int *mask)
   c->mask_n = n;
   c->lgv.disjoint_checked = false;
   if (c->lgv.many()) MDP_TRY(mdp_lgv_check_disjoint(c, c->md ? "mdp_md_set_mask" : "mdp_hnve_set_mask"));
+  if (c->heat.on) MDP_TRY(mdp_heat_mask(c, c->md ? "mdp_md_set_mask" : "mdp_hnve_set_mask"));
   return MDP_OK;
 }
 
@@ -1160,6 +1169,7 @@ int mdp_integrate_group(mdp_ctx *c, int groupbit)
   if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_integrate_group: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
   if (c->md) MDP_TRY(mdp_md_flush_final(c)); // (the finished step's final half belongs to the group it ran with)
   c->group_bit = groupbit;
+  c->heat.counted = false; // (heat sources: their atoms are counted against the new group by the next pass)
   return MDP_OK;
 }
 
@@ -1629,7 +1639,7 @@ int mdp_hnve_download(mdp_ctx *c, double *x, double *v, double *f)
   if (x) memcpy(x, h0, sizeof(double) * 3 * n);
   if (v) memcpy(v, h1, sizeof(double) * 3 * n);
   if (f) memcpy(f, h2, sizeof(double) * 3 * n);
-  return MDP_OK;
+  return mdp_heat_check(c);
 }
 
 int mdp_md_thermo(mdp_ctx *c, double out[9])
@@ -1649,6 +1659,7 @@ int mdp_md_thermo(mdp_ctx *c, double out[9])
   MDP_HIP(c, hipMemcpyAsync(hflags, c->flags.p, sizeof(int) * 5, hipMemcpyDeviceToHost, st));
   MDP_HIP(c, hipStreamSynchronize(st));
   MDP_TRY(mdp_flags_check(c, hflags));
+  MDP_TRY(mdp_heat_check(c));
   out[0] = c->h_pinned[7];
   out[1] = c->h_pinned[0];
   for (int k = 0; k < 6; k++) out[2 + k] = c->h_pinned[1 + k];
@@ -1671,7 +1682,7 @@ int mdp_md_download(mdp_ctx *c, double *x, double *v, double *f, double *eatom)
   if (f && n) MDP_HIP(c, hipMemcpyAsync(f, c->f.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, st));
   if (eatom && n) MDP_HIP(c, hipMemcpyAsync(eatom, c->eatom.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
   MDP_HIP(c, hipStreamSynchronize(st));
-  return MDP_OK;
+  return mdp_heat_check(c);
 }
 
 int mdp_md_download_x_all(mdp_ctx *c, double *x_all)

@@ -911,6 +911,9 @@ int mdp_destroy(mdp_ctx *c)
   c->lgv.st.release();
   c->lgv.part.release();
   c->lgv.overlap.release();
+  c->heat.st.release();
+  c->heat.part.release();
+  c->heat.count.release();
   c->fire.st.release();
   c->fire.part.release();
   c->fire.fsave.release();
@@ -989,7 +992,7 @@ int mdp_sync(mdp_ctx *c)
 {
   if (!c) return MDP_EINVAL;
   MDP_HIP(c, hipStreamSynchronize(c->stream));
-  return MDP_OK;
+  return mdp_heat_check(c);
 }
 
 int mdp_set_timing(mdp_ctx *c, int on)

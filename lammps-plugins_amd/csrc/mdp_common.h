@@ -332,6 +332,26 @@ struct MdpLangevin {
   bool sums() const { return on && (nbath > 1 ? any_zero || any_tally : cfg.zero || cfg.tally); } // one rank only
 };
 static constexpr int kLgvG2 = 16, kLgvMean = 32, kLgvE = 35, kLgvElast = 36, kLgvWords = 37;
+// Constant-flux heat sources (heat.hip): the host keeps the step counter and which sources are due; the sums, the scale
+// factors and the latched error live on the device.  st: source k keeps kHeatWords words at st + k * kHeatWords -- its
+// MDP_HEAT_STATE_LEN state words (mdp_heat_state layout), then the scale and (scale - 1) vcm of the pass in flight (1 and 0
+// for a source that is not due); behind the sources the error latch (kHeatErr: 1 once latched, then its source)
+struct MdpHeat {
+  bool on = false;
+  bool started = false;     // an initial half has run since mdp_heat_run: the next final half completes a step of this run
+  bool counted = false;     // the current mask has been counted (atoms in two sources, outside the integrate group, per source)
+  bool mass_due = false;    // the next pass sums M again (set-up, mask upload)
+  int nsrc = 0;
+  mdp_heat_config cfg[MDP_HEAT_MAXSRC];
+  int bit[MDP_HEAT_MAXSRC] = {0, 0, 0, 0};
+  long long step = 0;       // the step the last initial half began
+  DevBuf<double> st;        // [MDP_HEAT_MAXSRC * kHeatWords + 2]
+  DevBuf<double> part;      // per-block partial sums, kHeatW per block (fixed slots)
+  DevBuf<int> count;        // [2 + MDP_HEAT_MAXSRC] the counts of a set-up or mask upload
+};
+static constexpr int kHeatScale = 0, kHeatVcm = 1, kHeatKe = 4, kHeatM = 5, kHeatN = 6, kHeatErrStep = 7, kHeatS = 8, kHeatVsub = 9,
+                     kHeatWords = 12, kHeatErr = MDP_HEAT_MAXSRC * kHeatWords, kHeatTotal = kHeatErr + 2;
+static constexpr int kHeatW = 5 * MDP_HEAT_MAXSRC; // per source: sum m v.v, m vx, m vy, m vz, m
 // FIRE minimiser (fire.hip): the control block lives in st on the device; the host keeps the configuration and what it
 // has queued.  Control block, in doubles (flags and counters as whole numbers):
 enum MdpFireWord {
@@ -804,6 +824,7 @@ struct mdp_ctx {
   MdpNhc nhc;                      // thermostat of the integrate calls (mdp_nhc_setup)
   MdpLangevin lgv;                 // Langevin thermostat of the integrate calls (mdp_langevin_setup)
   MdpFire fire;                    // FIRE minimiser: mdp_md_advance launches its advance kernel while it is on (mdp_fire_setup)
+  MdpHeat heat;                    // constant-flux heat sources behind every final half (mdp_heat_setup)
   // groups (mdp_md_set_mask / mdp_hnve_set_mask, mdp_integrate_group, mdp_langevin_group)
   DevBuf<int> mask;                // [nlocal] atom->mask: device order (resident; permuted and migrated with the atoms) or the host's order
   bool mask_set = false;
@@ -1056,6 +1077,19 @@ int mdp_lgv_open_baths(mdp_ctx *c, bool with_final, bool initial, bool *apply, M
 int mdp_lgv_close_baths(mdp_ctx *c, const MdpLgvBathArgs &B);
 // several baths and a mask: count the atoms in more than one bath, once per mask or bath set-up, and refuse any
 int mdp_lgv_check_disjoint(mdp_ctx *c, const char *who);
+// heat sources (heat.hip) when c->heat.on.  _pass: behind a plain final half that completes a step: the sums, the control
+// workgroup and the rescaling of the sources that are due at that step (nothing when none is).  _count_step: an initial
+// half begins the next step.  _mask: a mask was uploaded (counts it again).  _check: behind a stream wait: the latched
+// error, as MDP_ESTATE
+int mdp_heat_pass(mdp_ctx *c);
+inline void mdp_heat_count_step(mdp_ctx *c)
+{
+  if (!c->heat.on) return;
+  c->heat.step++;
+  c->heat.started = true;
+}
+int mdp_heat_mask(mdp_ctx *c, const char *who);
+int mdp_heat_check(mdp_ctx *c);
 void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
 void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds
 void mdp_profile_release(mdp_ctx *c); // frees what profile.hip holds

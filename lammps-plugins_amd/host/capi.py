@@ -60,6 +60,10 @@ class LangevinConfig(C.Structure):
     _fields_ = [("t_start", C.c_double), ("t_stop", C.c_double), ("t_period", C.c_double), ("seed", C.c_int),
                 ("zero", C.c_int), ("tally", C.c_int), ("boltz", C.c_double), ("mvv2e", C.c_double),
                 ("ratio", C.c_double * 16), ("natoms", C.c_longlong)]
+class HeatConfig(C.Structure):
+    """mirror of mdp_heat_config"""
+    _fields_ = [("eflux", C.c_double), ("nevery", C.c_int), ("mvv2e", C.c_double)]
+HEAT_MAXSRC, HEAT_STATE_LEN = 4, 8   # MDP_HEAT_MAXSRC, MDP_HEAT_STATE_LEN of include/mdpair_hip.h
 class FireConfig(C.Structure):
     _fields_ = [("etol", C.c_double), ("ftol", C.c_double), ("maxiter", C.c_longlong), ("maxeval", C.c_longlong),
                 ("dmax", C.c_double), ("tmax", C.c_double), ("tmin", C.c_double), ("delaystep", C.c_int),
@@ -108,6 +112,7 @@ EXPORTS = [
     "mdp_profile_setup", "mdp_profile_range", "mdp_profile_exponent", "mdp_profile_sums", "mdp_profile_info", "mdp_profile_off",
     "mdp_rebomos_centre_paths",
     "mdp_heatflux_sums", "mdp_md_download_vatom",
+    "mdp_heat_setup", "mdp_heat_run", "mdp_heat_state", "mdp_heat_off",
 ]
 
 
@@ -588,6 +593,31 @@ class Context:
 
     def langevin_off(self):
         self._ck(self.L.mdp_langevin_off(self.h))
+
+    # ---------------- constant-flux heat sources behind the final halves (fix heat/mdp)
+    def heat_setup(self, sources, mvv2e=1.0364269e-4):
+        """mdp_heat_setup: sources is a list of dicts eflux (energy / time, either sign), nevery, bit (the source's group bit)"""
+        n = len(sources)
+        cfgs = (HeatConfig * max(n, 1))()
+        bits = (C.c_int * max(n, 1))()
+        for k, s in enumerate(sources):
+            cfgs[k].eflux, cfgs[k].nevery, cfgs[k].mvv2e = float(s["eflux"]), int(s["nevery"]), float(s.get("mvv2e", mvv2e))
+            bits[k] = int(s["bit"])
+        self._ck(self.L.mdp_heat_setup(self.h, C.c_int(n), cfgs, bits))
+
+    def heat_run(self, first):
+        self._ck(self.L.mdp_heat_run(self.h, C.c_longlong(first)))
+
+    def heat_state(self, src):
+        """source src after the last finished step (blocking): scale of its last application, vcm and the kinetic energy
+        about the centre of mass before it (times ftm2v), M, applications so far, step of a latched error or -1"""
+        out = np.zeros(HEAT_STATE_LEN)
+        self._ck(self.L.mdp_heat_state(self.h, C.c_int(int(src)), _dp(out)))
+        return dict(scale=float(out[0]), vcm=out[1:4].copy(), kecm=float(out[4]), mass=float(out[5]), applied=int(out[6]),
+                    error_step=int(out[7]))
+
+    def heat_off(self):
+        self._ck(self.L.mdp_heat_off(self.h))
 
     # ---------------- FIRE minimiser of a resident one-brick context (minimize/mdp)
     def fire_setup(self, etol, ftol, maxiter, maxeval, **modify):

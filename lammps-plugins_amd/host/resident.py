@@ -695,6 +695,28 @@ class DeviceDomain:
         self.flush()
         return self.ctx.langevin_tally(bath)
 
+    def heat(self, sources, first=0):
+        """Constant-flux heat sources (LAMMPS fix heat) behind the final halves of this domain: sources is a list of up to
+        four dicts eflux (energy / time; negative: a sink), nevery, bit -- the source's group bit in the mask of set_group.
+        Source k's atoms gain eflux nevery dt of kinetic energy about their centre of mass every nevery steps and keep
+        their momentum.  The groups must be disjoint and inside the integrate group; one GPU, no thermostat.  first: the
+        step the run that follows starts from (it is never heated itself).  A pending final half completes first."""
+        if self.world > 1:
+            raise ValueError("heat sources run on one GPU only (their sums would need an all-reduce per step)")
+        self.ctx.heat_setup(sources, mvv2e=S.MVV2E)
+        self.ctx.heat_run(first)
+        self._final_pending = False
+
+    def heat_state(self, src):
+        """source src after the last full step (completes a deferred final half first): capi.Context.heat_state"""
+        self.flush()
+        return self.ctx.heat_state(src)
+
+    def heat_off(self):
+        """back to plain NVE; a deferred final half completes inside mdp_heat_off, with its heat pass"""
+        self.ctx.heat_off()
+        self._final_pending = False
+
     def minimize(self, etol, ftol, maxiter, maxeval, chunk=64, **modify):
         """FIRE minimisation (LAMMPS min_style fire with its defaults; **modify: capi.FIRE_DEFAULTS) of this domain on the
         device, one GPU only; returns the final state (capi.Context.fire_state).  The velocities are zero afterwards

@@ -55,7 +55,8 @@
    and atom->mask with the atoms: next to the velocities at every host reneighboring in the host-linked mode
    (PairMDP::upload_host, mdp_hnve_set_mask), with the atoms into the brick otherwise (mdp_brick.h, mdp_md_set_mask),
    from where it comes back with them.  A fix langevin/mdp on a sub-group hands its bit over the same way
-   (mdp_langevin_group), several of them on disjoint sub-groups their bits and settings together (mdp_langevin_baths).  Group all sets both bits to 0 and uploads no mask for the fix's sake.  Run in the mini-host
+   (mdp_langevin_group), several of them on disjoint sub-groups their bits and settings together (mdp_langevin_baths), and
+   the fix heat/mdp fixes of a run theirs (mdp_heat_setup, in setup() behind the mask).  Group all sets both bits to 0 and uploads no mask for the fix's sake.  Run in the mini-host
    on 2, 4 and 8 ranks (tests/test_gpu_minilmp_ranks.py: log.rebomos-bulk.4's rows, the one-rank thermo of hot runs with
    migration); against a real LAMMPS this mode is unverified.
 -------------------------------------------------------------------------------------------------- */
@@ -90,6 +91,7 @@ FixNVEMDP::FixNVEMDP(LAMMPS *lmp, int narg, char **arg)
       linked_to(nullptr), bricks(0), bricks_kw(0), bctx(nullptr), bricks_slot(nullptr), bricks_ev(nullptr), style_id(0), comm_up(0), pending_final(0), step_ev(0)
 {
   memset(&baths, 0, sizeof baths);
+  memset(&heat, 0, sizeof heat);
   if (narg < 3 || (narg - 3) % 2) error->all(FLERR, "Illegal fix nve/mdp command");
   if (igroup < 0)
     error->all(FLERR, std::string("Fix ") + arg[2] + " requires group all or a group defined by the group command: could not find fix group ID " + arg[1]);
@@ -216,6 +218,14 @@ void FixNVEMDP::setup(int vflag)
   if (!c) fail(nullptr);
   apply_groups(c);
   run_ctx = c;
+  // heat sources (fix heat/mdp): behind the groups and the mask, which mdp_heat_setup counts their atoms in; step
+  // beginstep itself is not heated, as Verlet::setup does not call end_of_step
+  if (heat.count) {
+    if (baths.count) error->all(FLERR, "Fix nve/mdp: heat sources (fix heat/mdp) and a thermostat (fix langevin/mdp) in one run");
+    if (mdp_heat_setup(c, heat.count, heat.cfg, heat.bit) != MDP_OK) fail(c);
+    if (mdp_heat_run(c, (long long) update->beginstep) != MDP_OK) fail(c);
+    heat_ctx = c;
+  }
   if (!baths.count) return;
   if (baths.count == 1) {
     if (mdp_langevin_setup(c, &baths.cfg[0]) != MDP_OK) fail(c);
@@ -231,6 +241,8 @@ void *FixNVEMDP::extract(const char *name, int &dim)
   dim = 0;
   if (strcmp(name, "mdp_langevin_baths") == 0) return &baths;
   if (strcmp(name, "mdp_run_ctx") == 0) return &lgv_ctx;
+  if (strcmp(name, "mdp_heat_sources") == 0) return &heat;
+  if (strcmp(name, "mdp_heat_ctx") == 0) return &heat_ctx;
   if (strcmp(name, "mdp_steps_ctx") == 0) return &run_ctx;
   if (strcmp(name, "mdp_bricks") == 0) return &bricks;
   return nullptr;
@@ -360,6 +372,9 @@ void FixNVEMDP::post_run()
   lgv_ctx = nullptr;
   run_ctx = nullptr;
   memset(&baths, 0, sizeof baths);
+  if (heat_ctx && mdp_heat_off(heat_ctx) != MDP_OK) fail(heat_ctx); // (an unfix of the sources gives plain NVE next run)
+  heat_ctx = nullptr;
+  memset(&heat, 0, sizeof heat);
   if (bricks) {
     long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (comm->nprocs > 1) (void) mdp_dd_comm_step_info(bctx, info);

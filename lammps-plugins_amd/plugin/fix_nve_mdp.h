@@ -30,6 +30,7 @@ FixStyle(nve/mdp,FixNVEMDP);
 #include "fix.h"
 
 #include "mdp_baths.h"
+#include "mdp_heat.h"
 #include "mdpair_hip.h"
 
 namespace LAMMPS_NS {
@@ -79,6 +80,11 @@ class FixNVEMDP : public Fix {
   // on in setup() on the context the steps run on (lgv_ctx, extract "mdp_run_ctx"), off in post_run().  One: the calls of
   // one thermostat (mdp_langevin_setup, mdp_langevin_group); several: mdp_langevin_baths
   MdpLangevinBaths baths;
+  // the heat sources the `fix heat/mdp` fixes handed over (extract "mdp_heat_sources", mdp_heat.h): switched on in setup()
+  // behind the groups and the mask (mdp_heat_setup, mdp_heat_run(beginstep)) on the context the steps run on (heat_ctx,
+  // extract "mdp_heat_ctx"), off in post_run()
+  MdpHeatSources heat;
+  mdp_ctx *heat_ctx = nullptr;
   int brick_masked = 0; // this run's brick was set up with atom->mask (it comes back with the atoms)
   mdp_ctx *lgv_ctx = nullptr;
   // the context the steps of the run under way go through, thermostat or not, null between runs (extract "mdp_steps_ctx":
@@ -94,7 +100,7 @@ class FixNVEMDP : public Fix {
   int taken_delay() const;
   bool grouped() const { return igroup > 0; }                  // the fix acts on a group other than all
   bool lgv_masked() const { return baths.count > 1 || (baths.count == 1 && baths.bit[0]); }
-  bool masked() const { return grouped() || lgv_masked(); }    // ... or a thermostat does: the device needs atom->mask
+  bool masked() const { return grouped() || lgv_masked() || heat.count > 0; } // ... or a thermostat or a heat source does: the device needs atom->mask
   bool brick_mask() const;                                     // bricks: atom->mask travels with the atoms
   double group_count();                                        // atoms the fix integrates, over all ranks
   void apply_groups(mdp_ctx *c);                               // the group bits (and, host-linked, the mask) of this run on c
