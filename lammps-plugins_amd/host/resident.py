@@ -704,6 +704,12 @@ class DeviceDomain:
         if self.world > 1:
             raise ValueError("heat sources run on one GPU only (their sums would need an all-reduce per step)")
         self.ctx.heat_setup(sources, mvv2e=S.MVV2E)
+        self.heat_run(first)
+
+    def heat_run(self, first):
+        """A further run of the sources set by heat(), from step `first` (LAMMPS' second `run`): the phase of
+        step % nevery starts over and step `first` itself is not heated again.  A pending final half completes first,
+        WITHOUT the sources -- a host that wants the last step of the run before heated completes it first (flush)."""
         self.ctx.heat_run(first)
         self._final_pending = False
 

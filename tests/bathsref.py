@@ -38,6 +38,26 @@ def masks(s):
     return by_tag, g, baths
 
 
+BATH_BITS4 = BATH_BITS + (32,)
+
+
+def masks4(s):
+    """masks() with a fourth bath D (bit 32) cut out of what the three leave unthermostatted, for the fourth slot of the
+    baths and of the heat sources; A, B, C, the integrate group and the held atoms are those of masks():
+      D (bit 32) two of every three atoms with tag % 4 == 3 between x = 1/2 and 3/4 (counted in the order of s), and the
+                 even tags between x = 1/4 and 1/2
+    Between x = 1/2 and 3/4 a wave then holds atoms of all four baths, of none (the third atoms) and held atoms; the quarter
+    x < 1/4 and the odd tags of the second quarter stay integrated and unthermostatted."""
+    by_tag, g, baths = masks(s)
+    lam = s.box.x2lamda(S.wrap(s.box, s.x))
+    x = lam[:, 0]
+    zone = g & (s.tag % 4 == 3) & (x >= 0.5) & (x < 0.75)
+    d = (zone & (np.cumsum(zone) % 3 != 0)) | (g & (s.tag % 2 == 0) & (x >= 0.25) & (x < 0.5))
+    by_tag = by_tag.copy()
+    by_tag[s.tag] |= np.where(d, BATH_BITS4[3], 0).astype(np.int32)
+    return by_tag, g, baths + [d]
+
+
 def check_masks(s, g, baths):
     """the conditions on the input every several-bath test states before anything is launched"""
     any_bath = np.zeros(s.n, dtype=bool)

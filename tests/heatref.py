@@ -1,4 +1,4 @@
-"""The host reference of the constant-flux heat sources (tests/test_heatref.py, tests/test_gpu_heat_mdp.py): LAMMPS
+"""The host reference of the constant-flux heat sources (tests/test_heatref.py, tests/test_gpu_heat_mdp.py, tests/nets.py): LAMMPS
 FixHeat::end_of_step with a constant eflux and no region, restated, and the masked velocity-Verlet loops around it -- LAMMPS
 `fix nve` on a group next to several `fix heat` on disjoint groups inside it.  A source is a dict
     dict(group=<boolean array>, eflux=<energy / time, either sign>, nevery=<steps between applications>)
@@ -76,10 +76,22 @@ def run(x, v, m, force, sources, first, last, dt, ftm2v, mvv2e, group, on_step=N
     return x, v
 
 
-def host_heat(make_engine, s, v0, nsteps, every, rebuild_every, group, sources, dt=0.001, orders=None):
+def host_heat(make_engine, s, v0, nsteps, every, rebuild_every, group, sources, dt=0.001, orders=None, first=0, cut=None,
+              skin=None, dforce=0.0, states=False):
     """groupref.host_group with the sources: velocity Verlet on `group` around the oracle, the lists built anew every
     rebuild_every steps; {step: (x by tag, [scale of source k's last application], v by tag)} for the steps in `every`, and
-    the smallest escale of the run.  orders: per source a permutation its atoms are summed in (None: the order of s)"""
+    the smallest escale of the run.  orders: per source a permutation its atoms are summed in (None: the order of s).
+    The run's steps are numbered first + 1 .. first + nsteps as in run(): step `first` is never heated, step first + n is
+    if (first + n) % nevery == 0.
+    cut = (k, completed): the host starts a second run at step first + k of this one (mdp_heat_run(first + k)).  Step
+    first + k belongs to the first run, whose end_of_step heats it; it is not heated again as the second run's first step.
+    completed False: the host left that step's final half pending across the call -- the library completes it there
+    WITHOUT the sources, so the applications of step first + k do not happen at all.
+    skin: assert that no atom has moved more than half of it since the last build (refloops.host_lgv's rule).
+    dforce: every force component of every step gets an error drawn uniformly from +-dforce (the experiment behind the
+    nets' limits).
+    states True: a fourth entry per read, [dict(scale, vcm, kecm, applied, due) of source k]: its last application (1, 0,
+    0 before the first), its applications so far and whether it was due at the read step itself"""
     g = np.asarray(group, dtype=bool)
     m = s.mass[s.type]
     mg = m[g]
@@ -87,9 +99,14 @@ def host_heat(make_engine, s, v0, nsteps, every, rebuild_every, group, sources, 
     x = S.wrap(s.box, s.x)
     v = v0.copy()
     eng = make_engine(S.System(s.box, x.copy(), s.type, s.tag, s.mass))
+    x_built = x.copy()
+    noise = np.random.default_rng(20261) if dforce else None
     f = eng.compute(x, eflag=1, vflag=0)["f_owned"]
+    if dforce:
+        f = f + noise.uniform(-dforce, dforce, f.shape)
     dtf = 0.5 * dt * S.FTM2V
     scales = [1.0] * len(sources)
+    last = [dict(scale=1.0, vcm=np.zeros(3), kecm=0.0, applied=0, due=False) for _ in sources]
     out, lowest = {}, np.inf
     for step in range(1, nsteps + 1):
         v[g] += dtf * f[g] / mg[:, None]
@@ -97,11 +114,21 @@ def host_heat(make_engine, s, v0, nsteps, every, rebuild_every, group, sources, 
         if step % rebuild_every == 0:
             x = S.wrap(s.box, x)
             eng = make_engine(S.System(s.box, x.copy(), s.type, s.tag, s.mass))
+            x_built = x.copy()
+        elif skin is not None:
+            far = float(np.sqrt(((x - x_built) ** 2).sum(axis=1)).max())
+            assert far <= 0.5 * skin, f"the reference's own list is stale at step {step}: an atom moved {far:.3f} A"
         f = eng.compute(x, eflag=1, vflag=0)["f_owned"]
+        if dforce:
+            f = f + noise.uniform(-dforce, dforce, f.shape)
         v[g] += dtf * f[g] / mg[:, None]
-        for k, r in end_of_step(step, v, m, sources, dt, S.FTM2V, S.MVV2E, masses, orders).items():
-            scales[k] = r[0]
-            lowest = min(lowest, r[3])
+        for q in last:
+            q["due"] = False
+        if cut is None or step != cut[0] or cut[1]:
+            for k, r in end_of_step(first + step, v, m, sources, dt, S.FTM2V, S.MVV2E, masses, orders).items():
+                scales[k] = r[0]
+                lowest = min(lowest, r[3])
+                last[k] = dict(scale=r[0], vcm=r[1].copy(), kecm=r[2], applied=last[k]["applied"] + 1, due=True)
         if step in every:
-            out[step] = (x.copy(), list(scales), v.copy())
+            out[step] = (x.copy(), list(scales), v.copy()) + (([dict(q) for q in last],) if states else ())
     return out, lowest

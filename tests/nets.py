@@ -44,6 +44,7 @@ SUITE = {
     "block": [(1, 8)],
     "fire": [(4, 16)],
     "langevin": [(42, 14)],
+    "heat": [(2, 12)],
 }
 
 
@@ -1009,6 +1010,334 @@ def line_langevin(spec, err):
             f"migrated {err['migrated']}")
 
 
+# --------------------------------------------------------------------------------------------------------------- heat
+# The constant-flux heat sources (csrc/heat.hip behind every final half) on the three one-rank paths of the integrate
+# kernel -- "resident", "resident-plain", "hostlinked" (shuffled host order, host reneighbourings that re-upload atoms,
+# velocities and mask); several ranks are refused -- against tests/heatref.host_heat around the ORACLE: 1 - 4 sources on
+# group bits drawn from {4, 8, 16, 32, 64} in a shuffled order (slot k does not have the k-th lowest bit), a nevery per
+# source from {1, 2, 3, 5, 7} (so the `due` word of a step is empty, partial or full), first steps 0, 1, 7, 1000 and
+# 2^32 + 7 (the phase of step % nevery), 40 / 60 / 100 steps of 0.5 / 1 / 2 fs, the integrate group `all` (a mask, but no
+# integrate bit) or groupref's, and per source a group shape: every third atom, by tag, of a half of the free atoms, a contiguous
+# slab (whole waves of one source), 2 or 3 atoms that are no neighbours, or -- the last source -- the rest of the
+# integrate group, so that the sources cover it.  eflux_k = c KEcm_k(0) / dt with c from {0, +-5e-4, +-1e-3, +-3e-3}; one
+# source's atoms start with a drift, so that vsub != 0.  Optionally the host starts a second run (mdp_heat_run) at a step
+# that is due for some source: that step belongs to the first run; with its final half left pending across the call it
+# completes there without the sources, as INTEGRATION.md says.
+# At every read: x (minimum image) and v by tag; scale, vcm, ke and the application count of every source's state words
+# against the reference's LAST application of that source (a source that was not due at the read step still reports it;
+# the count is exact); the atoms outside the integrate group bit for bit; no late check.
+# Limits (the reference's, not the device's; both experiments run on the CPU in tests/test_net_draws.py over the suite's
+# cases): tests/test_gpu_heat_mdp.py holds the sources to 1e-9 A, 2e-8 A/ps and 1e-12 of the scale.
+# With an error of +-1e-9 eV/A on every force component (experiment (ii)) the reference itself moves by 4.6e-10 A,
+# 1.3e-8 A/ps and 4.3e-11 of the scale -- more than a quarter of each of those bounds: a tiny group's scale
+# sqrt(1 + heat / den) follows its few atoms' velocities --, so for this net each becomes four times the experiment's
+# worst: 1.9e-9 A, 5.2e-8 A/ps, 1.8e-10.  The state words vcm and ke had no bound yet: 100 times what the order of a
+# source's sum does to them in the reference (experiment (i): 2.14e-14 A/ps, 1.40e-14 relative).
+# These five numbers belong to SUITE["heat"]'s seed and case count: they ARE the two experiments' worst over those cases
+# (times 4, times 100), and tests/test_net_draws.py compares them with the same experiments, so its margins are thin by
+# construction (2.14e-14 < 0.01 * 2.2e-12; 4.56e-10 < 0.25 * 1.9e-9).  Whoever changes the seed, the case count, the draw
+# or the rounding of the oracle measures both experiments again (that test prints their worst per quantity) and sets
+# the limits and DESIGN.md section 5 from what it prints -- never from what the device gives.
+HEAT_PATHS = ("resident", "resident-plain", "hostlinked")
+HEAT_FIRST = (0, 1, 7, 1000, 2 ** 32 + 7)
+HEAT_BITS = (4, 8, 16, 32, 64)
+HEAT_NEVERY = (1, 2, 3, 5, 7)
+HEAT_C = (0.0, 5e-4, -5e-4, 1e-3, -1e-3, 3e-3, -3e-3)
+HEAT_DRIFT = (0.5, -0.3, 0.2)
+HEAT_VCM_LIMIT = 2.2e-12   # A/ps, absolute
+HEAT_KE_LIMIT = 1.4e-12    # relative
+HEAT_LIMITS = dict(dx=1.9e-9, dv=5.2e-8, dscale=1.8e-10, dvcm=HEAT_VCM_LIMIT, dke=HEAT_KE_LIMIT)
+
+
+def draw_heat(rng):
+    style = rng.choice(["rebomos", "aeam"])
+    if style == "rebomos":
+        size = rng.choice([(1, 1, 1), (2, 1, 1), (3, 1, 1), (2, 2, 1)])
+        spec = dict(size=size, n=_rebo_n(size), frac=None, tilt=None, skin=2.0)
+    else:
+        size, frac = rng.choice([4, 5, 6, 7]), rng.choice([0.0, 0.03])
+        spec = dict(size=size, n=4 * size ** 3, frac=frac, tilt=None, skin=1.0)
+        if rng.random() < 0.5:   # a sheared (triclinic) box
+            spec["tilt"] = [rng.uniform(-0.06, 0.06) * 4.045 * size for _ in range(3)]
+    temp = rng.choice([300.0, 900.0])
+    path = rng.choice(HEAT_PATHS)
+    nsrc = rng.choice([1, 2, 3, 4])
+    bits = list(HEAT_BITS)
+    rng.shuffle(bits)
+    bits = bits[:nsrc]
+    nevery = [rng.choice(HEAT_NEVERY) for _ in range(nsrc)]
+    first = rng.choice(HEAT_FIRST)
+    nsteps, dt = rng.choice([40, 60, 100]), rng.choice([0.0005, 0.001, 0.002])
+    group = rng.choice(["all", "slab"])
+    shapes = []
+    for k in range(nsrc):
+        kind = rng.choice(["modulus", "slab", "tiny", "rest"] if k == nsrc - 1 else ["modulus", "slab", "tiny"])
+        axis, width, count, pick = rng.randrange(3), rng.choice([0.15, 0.25]), rng.choice([2, 3]), rng.randrange(10**6)
+        shapes.append(dict(kind=kind, axis=axis, width=width, count=count, pick=pick))
+    c = [rng.choice(HEAT_C) for _ in range(nsrc)]
+    drifting = rng.randrange(nsrc)
+    # thermo reads at random steps, the last step among them; True: the read finds the step's final half deferred and
+    # completes it (heat pass included), False: the final half ran on its own before the read
+    reads = [(st, rng.random() < 0.5) for st in sorted(rng.sample(range(1, nsteps), rng.randint(1, 4))) + [nsteps]]
+    cut = None
+    if rng.random() < 0.4:   # a second run from a step that is due for source j
+        j = rng.randrange(nsrc)
+        k = rng.choice([k for k in range(2, nsteps - 1) if (first + k) % nevery[j] == 0])
+        pending = rng.random() < 0.5     # the host leaves that step's final half pending across mdp_heat_run
+        cut = (k, not pending or path == "hostlinked" or k in dict(reads))
+    renb = rng.choice([3, 5, 8])
+    spec.update(style=style, temp=temp, path=path, nsrc=nsrc, bits=bits, nevery=nevery, first=first, nsteps=nsteps, dt=dt, group=group,
+                shapes=shapes, c=c, drifting=drifting, reads=reads, cut=cut, renb=renb, seed=rng.randrange(1, 10**6), env={},
+                id=f"{style}-{path}-n{spec['n']}-{group}-src{nsrc}-every{'.'.join(map(str, nevery))}-first{first}-dt{dt}"
+                   + (f"-cut{cut[0]}{'' if cut[1] else 'p'}" if cut else ""))
+    return spec
+
+
+def heat_due(spec, step):
+    """the `due` word of run step `step`: bit k set if source k is applied behind it"""
+    if spec["cut"] is not None and step == spec["cut"][0] and not spec["cut"][1]:
+        return 0
+    return sum(1 << k for k, ne in enumerate(spec["nevery"]) if (spec["first"] + step) % ne == 0)
+
+
+def _heat_system(spec):
+    """no GPU, no oracle: (system, start velocities with the drift, mask by tag, integrate group, [group of source k],
+    [eflux of source k], the steps between forced list builds by the _lgv_system rule)"""
+    import groupref
+    import heatref
+    af = _res()["af"]
+    if spec["style"] == "rebomos":
+        s = S.replicate(S.rebomos_bulk_cell(), spec["size"])
+    else:
+        s = S.fcc_cell(4.045, spec["size"], frac_type2=spec["frac"], seed=spec["seed"]); s.mass[1:3] = af.mass[:2]
+        if spec["tilt"] is not None:
+            # the sites a quarter of the lattice constant off the box faces: a site ON a face of a sheared box has a lamda
+            # coordinate that rounds to just outside at some builds, and the remap rewrites every atom that left the box,
+            # held ones included, by a box vector -- the held atoms could not be compared bit for bit then
+            nb = S.Box(s.box.lo.copy(), s.box.prd.copy(), np.array(spec["tilt"]))
+            s = S.System(nb, nb.lamda2x(s.box.x2lamda(s.x) + 0.25 / spec["size"]), s.type, s.tag, s.mass)
+    assert s.n == spec["n"]
+    lam = s.box.x2lamda(S.wrap(s.box, s.x))
+    g = np.ones(s.n, dtype=bool) if spec["group"] == "all" else groupref.masks(s)[1]
+    free, groups = g.copy(), []
+    for k, sh in enumerate(spec["shapes"]):
+        a = lam[:, sh["axis"]]
+        if sh["kind"] == "modulus":    # every third, in the order of the tags, of the upper half, along the axis, of the atoms still
+            up = free & (a >= np.median(a[free]))     # free: lanes of a wave alternate between this source and others
+            l = up & (np.cumsum(up) % 3 == 0)
+        elif sh["kind"] == "slab":     # contiguous: of the integrate group's atoms in their order along the axis, those from
+            rank = np.empty(s.n)       # k / 4 on, `width` of them -- whole planes of the crystal, a plane cut at the ends
+            rank[np.argsort(np.where(g, a, np.inf), kind="stable")] = np.arange(s.n) / g.sum()
+            l = free & (rank >= 0.25 * k) & (rank < 0.25 * k + sh["width"])
+        elif sh["kind"] == "rest":
+            l = free.copy()
+        else:                          # 2 or 3 atoms, no two of them within 6 A of each other
+            r = np.random.default_rng(sh["pick"])
+            l = np.zeros(s.n, dtype=bool)
+            for i in r.permutation(np.flatnonzero(free)):
+                d = s.x[l] - s.x[i]
+                d = d - np.round(s.box.x2lamda(d + s.box.lo)) @ s.box.h.T
+                if not l.any() or float(np.sqrt((d ** 2).sum(axis=1)).min()) > 6.0:
+                    l[i] = True
+                if l.sum() == sh["count"]:
+                    break
+        assert l.sum() >= 2, (spec["id"], k, sh["kind"], int(l.sum()))
+        groups.append(l)
+        free &= ~l
+    by_tag = np.zeros(int(s.tag.max()) + 1, dtype=np.int32)
+    m = groupref.ALL_BIT | np.where(g, groupref.INTEGRATE_BIT, 0)
+    for bit, l in zip(spec["bits"], groups):
+        m = m | np.where(l, bit, 0)
+    by_tag[s.tag] = m
+    v0 = S.gaussian_velocities(s, spec["temp"], seed=spec["seed"] + 1)
+    v0[groups[spec["drifting"]]] += np.array(HEAT_DRIFT)
+    mass = s.mass[s.type]
+    flux = [c * heatref.kecm(v0, mass, l, S.FTM2V, S.MVV2E) * S.MVV2E / spec["dt"] for c, l in zip(spec["c"], groups)]
+    vcap = float(np.sqrt((v0 ** 2).sum(axis=1)).max()) + 5.0 * np.sqrt(S.BOLTZ * 1.5 * spec["temp"] / (float(s.mass[1:3].min()) * S.MVV2E))
+    safe = max(1, int(0.3 * spec["skin"] / (vcap * spec["dt"])))
+    return s, v0, by_tag, g, groups, flux, safe
+
+
+def _heat_intervals(spec, safe):
+    """(the interval of the device's forced builds on "resident-plain"; the interval of the reference's builds and of the
+    host's reneighbourings on "hostlinked": refloops.host_lgv's rule, a fixed interval shortened to what is safe)"""
+    return min(spec["renb"], safe), min(LGV_REBUILD[spec["style"]], safe)
+
+
+def heat_reference(spec, permuted=False, dforce=0.0):
+    """no GPU: heatref.host_heat of the case around the oracle; ({read step: (x, scales, v, states)}, lowest escale).
+    permuted: every source's atoms summed in a random order (experiment (i)); dforce: experiment (ii)"""
+    import heatref
+    import mdref
+    R = _res()
+    s, v0, by_tag, g, groups, flux, safe = _heat_system(spec)
+    skin = spec["skin"]
+    make = ((lambda sy: mdref.RebomosCPU(R["orc"], R["P"], sy, skin=skin)) if spec["style"] == "rebomos" else
+            (lambda sy: mdref.AeamCPU(R["orc"], R["T"], sy, skin=skin)))
+    sources = [dict(group=l, eflux=fl, nevery=ne) for l, fl, ne in zip(groups, flux, spec["nevery"])]
+    orders = None
+    if permuted:
+        r = np.random.default_rng(spec["seed"] + 2)
+        orders = [r.permutation(int(l.sum())) for l in groups]
+    return heatref.host_heat(make, s, v0, spec["nsteps"], dict(spec["reads"]), _heat_intervals(spec, safe)[1], g, sources, dt=spec["dt"],
+                             orders=orders, first=spec["first"], cut=spec["cut"], skin=skin, dforce=dforce, states=True)
+
+
+def heat_worst(spec, s, g, ref, dev, x_in=None, v_in=None):
+    """the worst deviations of {step: (x, scales, v, states)} `dev` from `ref` over the reads; with x_in / v_in also
+    whether an atom outside the integrate group changed (held) and whether an application count differs (count)"""
+    import refloops
+    w = dict(dx=0.0, dv=0.0, dscale=0.0, dvcm=0.0, dke=0.0)
+    held = count = 0
+    for step in ref:
+        xh, _, vh, sth = ref[step]
+        xd, _, vd, std = dev[step]
+        d = xd - xh
+        d = d - np.round(s.box.x2lamda(d + s.box.lo)) @ s.box.h.T
+        w["dx"] = refloops.worse(w["dx"], float(np.abs(d).max()))
+        w["dv"] = refloops.worse(w["dv"], float(np.abs(vd - vh).max()))
+        for a, b in zip(std, sth):
+            w["dscale"] = refloops.worse(w["dscale"], abs(a["scale"] - b["scale"]) / abs(b["scale"]))
+            w["dvcm"] = refloops.worse(w["dvcm"], float(np.abs(a["vcm"] - b["vcm"]).max()))
+            w["dke"] = refloops.worse(w["dke"], abs(a["kecm"] - b["kecm"]) / abs(b["kecm"]) if b["kecm"] else abs(a["kecm"]))
+            count += int(a["applied"] != b["applied"])
+        if x_in is not None:
+            held += int(not (np.array_equal(xd[~g], x_in[~g]) and np.array_equal(vd[~g], v_in[~g])))
+    if x_in is not None:
+        w.update(held=held, count=count)
+    return w
+
+
+def _heat_states(ctx, nsrc):
+    return [dict(scale=q["scale"], vcm=q["vcm"], kecm=q["kecm"], applied=q["applied"]) for q in (ctx.heat_state(k) for k in range(nsrc))]
+
+
+def _heat_resident(spec, s, v0, by_tag, g, dsrc, rebuild_every):
+    """one resident brick.  rebuild_every None: the device's own check; a number: the integrate calls without the check,
+    reneighbourings forced every so many steps.  The reads go through the library (mdp_heat_state completes a deferred
+    final half, heat pass included), not through DeviceDomain.flush"""
+    import groupref
+    from lammps_plugins_amd.host import resident
+    reads, cut = dict(spec["reads"]), spec["cut"]
+    ctx, st, cutghost, map_ = _lgv_context(spec["style"])
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, spec["skin"], map_, v0=v0, dt=spec["dt"])
+        d.set_group(by_tag, 0 if spec["group"] == "all" else groupref.INTEGRATE_BIT)
+        d.heat(dsrc, first=spec["first"])
+        d.compute(1, 0)
+        out = {}
+        for step in range(1, spec["nsteps"] + 1):
+            rb = "auto" if rebuild_every is None else step % rebuild_every == 0
+            defer = reads.get(step, True)
+            if cut is not None and step == cut[0] and step not in reads:
+                defer = not cut[1]
+            d.step(0, 0, rebuild=rb, defer_final=defer)
+            if step in reads:
+                sts = _heat_states(ctx, spec["nsrc"])
+                got = ctx.md_download(d.nlocal, want=("x", "v"))
+                x, v = np.zeros((s.n, 3)), np.zeros((s.n, 3))
+                x[d.tags_local - 1], v[d.tags_local - 1] = got["x"], got["v"]
+                out[step] = (x, [q["scale"] for q in sts], v, sts)
+            if cut is not None and step == cut[0]:
+                d.heat_run(spec["first"] + step)         # (completes a pending final half, without the sources)
+        return out, d.builds, d.dangerous
+    finally:
+        ctx.close()
+
+
+def _heat_hostlinked(spec, s, v0, by_tag, g, dsrc, rebuild_every):
+    """mdp_hnve_* with mdp_hnve_set_mask from a shuffled host order; a host reneighbouring (every rebuild_every steps and
+    whenever mdp_hnve_initial reports `moved`) downloads, wraps the integrated atoms and uploads atoms, velocities and
+    mask again"""
+    import ctypes as C
+    import groupref
+    import oracle_bindings as ob
+    from lammps_plugins_amd.host import capi
+    R = _res()
+    style, n, skin = spec["style"], s.n, spec["skin"]
+    cut = (R["P"].cut3rebo if style == "rebomos" else float(R["af"].cut_table(R["tabs"]).max())) + skin
+    perm = np.random.default_rng(spec["seed"] + 3).permutation(n)
+    type_p, tag_p, gp = s.type[perm].copy(), s.tag[perm].copy(), g[perm]
+    mask_p = by_tag[tag_p]
+    c = capi.Context(0)
+
+    def upload(x, v):
+        xa, type_all, tag_all, _, _, nloc, _ = S.with_ghosts(S.System(s.box, x.copy(), type_p, tag_p, s.mass), cut)
+        c.set_atoms_host(nloc, xa, type_all, tag_all, 2, map_=[0, 0, 1] if style == "rebomos" else None)
+        c.set_skin(skin)
+        c.hnve_upload_v(v)
+
+    def compute():   # f == NULL: the forces' only reader is the device's integrator
+        if style == "rebomos":
+            c._ck(c.L.mdp_rebomos_compute_host(c.h, 0, 0, None, None, None, None, None))
+        else:
+            eng, vir = C.c_double(0.0), np.zeros(6)
+            c._ck(c.L.mdp_aeam_density_host(c.h, C.c_int(0), None, None, C.byref(eng), None))
+            c._ck(c.L.mdp_aeam_force_host(c.h, C.c_int(0), C.c_int(0), None, None, C.byref(eng), capi._dp(vir), None, None))
+    try:
+        if style == "rebomos":
+            c.rebomos_set_params(ob.product_rebomos_params(R["P"]))
+        else:
+            c.aeam_set_tables(R["tabs"]); c.aeam_device_lists(True)
+        c.set_box_host(s.box)
+        c.hnve_setup(spec["dt"], S.FTM2V, s.mass)
+        c.integrate_group(0 if spec["group"] == "all" else groupref.INTEGRATE_BIT)
+        upload(S.wrap(s.box, s.x)[perm], v0[perm])
+        c.hnve_set_mask(mask_p)
+        c.heat_setup(dsrc, mvv2e=S.MVV2E)
+        c.heat_run(spec["first"])
+        compute()
+        reads, out, late_any, rebuilds = dict(spec["reads"]), {}, 0, 0
+        for step in range(1, spec["nsteps"] + 1):
+            moved, late = c.hnve_initial()
+            late_any += int(late)
+            if moved or step % rebuild_every == 0:
+                got = c.hnve_download(n, want=("x", "v"))
+                xw = S.wrap(s.box, got["x"])
+                xw[~gp] = got["x"][~gp]     # (a host that wraps rewrites only atoms that left the box: the held ones did not)
+                upload(xw, got["v"])
+                c.hnve_set_mask(mask_p)
+                rebuilds += 1
+            compute()
+            c.hnve_final()
+            if step in reads:
+                sts = _heat_states(c, spec["nsrc"])
+                got = c.hnve_download(n, want=("x", "v"))
+                x, v = np.zeros((n, 3)), np.zeros((n, 3))
+                x[tag_p - 1], v[tag_p - 1] = got["x"], got["v"]
+                out[step] = (x, [q["scale"] for q in sts], v, sts)
+            if spec["cut"] is not None and step == spec["cut"][0]:
+                c.heat_run(spec["first"] + step)
+    finally:
+        c.close()
+    return out, rebuilds, late_any
+
+
+def run_heat(spec):
+    s, v0, by_tag, g, groups, flux, safe = _heat_system(spec)
+    forced, ref_every = _heat_intervals(spec, safe)
+    ref, lowest = heat_reference(spec)
+    dsrc = [dict(eflux=fl, nevery=ne, bit=b) for fl, ne, b in zip(flux, spec["nevery"], spec["bits"])]
+    if spec["path"] == "hostlinked":
+        dev, builds, late = _heat_hostlinked(spec, s, v0, by_tag, g, dsrc, ref_every)
+    else:
+        dev, builds, late = _heat_resident(spec, s, v0, by_tag, g, dsrc, None if spec["path"] == "resident" else forced)
+    # The atoms outside the integrate group keep, bit for bit, the positions (wrapped into the box, as every path uploads
+    # them) and the velocities they were given
+    err = heat_worst(spec, s, g, ref, dev, S.wrap(s.box, s.x), v0)
+    err.update(late=late, builds=builds, lowest=lowest, sizes=[int(l.sum()) for l in groups],
+               applied=[q["applied"] for q in dev[spec["nsteps"]][3]])
+    return err, dict(HEAT_LIMITS, held=1, count=1, late=1)
+
+
+def line_heat(spec, err):
+    return (f"{spec['id']} steps {spec['nsteps']} T {spec['temp']:.0f} bits {spec['bits']} shapes {[q['kind'] for q in spec['shapes']]} sizes {err['sizes']} "
+            f"c {spec['c']} drifting {spec['drifting']} tilt {spec['tilt'] is not None} reads {[(a, int(b)) for a, b in spec['reads']]} "
+            f"seed {spec['seed']} dx {err['dx']:.1e} dv {err['dv']:.1e} scale {err['dscale']:.1e} vcm {err['dvcm']:.1e} ke {err['dke']:.1e} "
+            f"applied {err['applied']} count {err['count']} held {err['held']} late {err['late']} lowest escale {err['lowest']:.4f} "
+            f"builds {err['builds']}")
+
+
 # ---------------------------------------------------------------------------------------------------------------- nvt
 # The Nose-Hoover chain thermostat (tests/test_gpu_nvt_net.py): chains of 1-8, 1-3 loops, drag, flat or ramped targets,
 # both styles, the resident path and (REBO-MoS) the host-linked one, atom counts whose last 256-atom block varies.
@@ -1038,7 +1367,7 @@ def nvt_cases(seed, ncase):
 
 
 NETS = {name: (globals()["draw_" + name], globals()["run_" + name], globals()["line_" + name])
-        for name in ("force", "hostmode_walk", "aeam_types", "prune", "dd", "hnve", "minilmp", "trajectory", "block", "fire", "langevin")}
+        for name in ("force", "hostmode_walk", "aeam_types", "prune", "dd", "hnve", "minilmp", "trajectory", "block", "fire", "langevin", "heat")}
 
 
 def main(net, argv):

@@ -105,6 +105,13 @@ def test_the_masks_of_the_gpu_tests_satisfy_their_conditions_on_both_cells():
         assert np.array_equal(g, groupref.masks(s)[1])              # the integrate group of the group tests
         for bit, b in zip(bathsref.BATH_BITS, baths):
             assert np.array_equal((by_tag[s.tag] & bit) != 0, b), name
+        by4, g4, baths4 = bathsref.masks4(s)                        # the fourth bath: the three and the group stay as they are
+        bathsref.check_masks(s, g4, baths4)
+        assert np.array_equal(g4, g) and all(np.array_equal(a, b) for a, b in zip(baths4, baths)) and len(baths4) == 4
+        assert np.array_equal(by4[s.tag] & ~32, by_tag[s.tag]) and np.array_equal((by4[s.tag] & 32) != 0, baths4[3]), name
+        lam = s.box.x2lamda(S.wrap(s.box, s.x))[:, 0]
+        zone = (lam >= 0.5) & (lam < 0.75)                          # ... where lanes of one wave can belong to every bath and to none
+        assert all((b & zone).sum() >= 5 for b in baths4) and (g & zone & ~np.logical_or.reduce(baths4)).sum() >= 5, name
     # the check refuses overlapping baths and a bath that leaves the integrate group
     with pytest.raises(AssertionError):
         bathsref.check_masks(s, g, [baths[0], baths[1] | baths[0], baths[2]])

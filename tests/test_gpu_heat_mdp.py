@@ -8,7 +8,16 @@ the cell is held.  B's atoms carry an extra drift of (0.5, -0.3, 0.2) A/ps, so t
 eflux_k = +-1e-3 KEcm_k(0) / dt.  Tolerances are the project's own for these cells and step counts under a global-sum
 feedback: positions 1e-9 A (the grouped thermostats), velocities 2e-8 A/ps (VTOL of tests/test_gpu_langevin_mdp.py, the
 one velocity bound those tests hold against a host loop), held atoms bit for bit, the scale 1e-12 relative.  The reference
-with every source's atoms summed in a permuted order stays 100 times inside them (test_a_permuted_sum_..., no GPU)."""
+with every source's atoms summed in a permuted order stays 100 times inside them (test_a_permuted_sum_..., no GPU).
+
+The fixed cases above use two sources, one nevery, first = 0 and one run.  Section 6 holds what tests/nets.py's `heat` net
+cannot carry: four sources with four different nevery from first = 7 with the state read at every step, two runs in a row on
+one context (mdp_heat_run at a due step; resident with the seam's final half pending or completed, and host-linked), and
+275 684 atoms -- 270 partial slots, the control workgroup's second trip -- against math.fsum."""
+import math
+import os
+from fractions import Fraction
+
 import numpy as np
 import pytest
 
@@ -19,6 +28,7 @@ from refloops import worse
 import bathsref
 import heatref
 import mdref
+import nets
 import oracle_bindings as ob
 
 gpu = pytest.mark.gpu
@@ -213,6 +223,32 @@ def test_a_permuted_sum_stays_a_hundred_times_inside_the_bounds(oracle, style, c
     with capsys.disabled():
         _compare(s, a, b, g, None, v0, f"permuted sums {style}", every, scale=0.01)
     assert all(a[n][1][1] < 1.0 < a[n][1][0] for n in every)
+
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "heatref", "host_heat_fixed_cases.npz")
+
+
+@pytest.mark.parametrize("style", ["rebomos", "aeam"])
+def test_the_generalised_host_loop_gives_the_fixed_cases_bit_for_bit(oracle, style):
+    """no GPU.  heatref.host_heat took first, dt, a cut, the skin assertion and the state words for the net; with none of
+    them given it is the loop the fixed cases were merged with: the scales of all 17 reads and x, v of the last step,
+    plain and with permuted sums, against a run saved from the loop before it was generalised.
+
+    Where the file comes from: tests/heatref.py of commit 1696e2d ("Add fix heat/mdp: constant-flux heat sources on
+    groups, on the device"), the loop as merged, put in place of today's; then, for both styles and permuted in (False,
+    True), r = _reference(oracle, style, permuted=permuted) of this module (same cells, sources and arguments then as
+    now) and np.savez_compressed(GOLDEN, ...) of, under key = f"{style}_{'permuted' if permuted else 'plain'}":
+    key_steps = sorted(r), key_scales = [r[n][1] for n in steps], key_x = r[NSTEPS][0], key_v = r[NSTEPS][2].
+    Repeating that reproduces every array of the file bit for bit.  The file changes only if the reference is MEANT to
+    give other numbers for the fixed cases; anything else that breaks this test is a regression of the loop."""
+    gold = np.load(GOLDEN)
+    for permuted in (False, True):
+        r = _reference(oracle, style, permuted=permuted)
+        key = f"{style}_{'permuted' if permuted else 'plain'}"
+        steps = sorted(r)
+        assert steps == gold[key + "_steps"].tolist()
+        assert np.array_equal(np.array([r[n][1] for n in steps]), gold[key + "_scales"]), key
+        assert np.array_equal(r[NSTEPS][0], gold[key + "_x"]) and np.array_equal(r[NSTEPS][2], gold[key + "_v"]), key
 
 
 # ---- 1. resident, both styles, both step sets ---------------------------------------------------------------------
@@ -425,6 +461,297 @@ def test_a_sink_that_runs_dry_is_a_handled_error_and_heat_off_gives_the_context_
     x, v = _one_step(dry, after)
     x_off, v_off, _ = _without_sources()
     assert np.array_equal(x, x_off) and np.array_equal(v, v_off)   # neither source was applied: v is what the step left
+
+
+# ---- 6. four slots, four nevery, first != 0; two runs on one context; the control workgroup's second trip ----------------
+BITS4 = (16, 4, 32, 8)          # slot k's group: bathsref.masks4's A, B, C, D on these bits -- slot k does not hold the k-th lowest
+C4 = (1e-3, -1e-3, 2e-3, -5e-4)
+_CASE4 = []
+
+
+def _case4():
+    """the REBO-MoS case with four sources: (system, v0 with a drift on B and D, mask by tag, integrate group, [A, B, C, D],
+    wrapped positions, [eflux])"""
+    if not _CASE4:
+        s, v0 = _system("rebomos")
+        _, g, groups = bathsref.masks4(s)
+        bathsref.check_masks(s, g, groups)
+        by_tag = np.zeros(int(s.tag.max()) + 1, dtype=np.int32)
+        m = bathsref.ALL_BIT | np.where(g, GBIT, 0)
+        for bit, l in zip(BITS4, groups):
+            m = m | np.where(l, bit, 0)
+        by_tag[s.tag] = m
+        v0 = v0.copy()
+        v0[groups[1]] += DRIFT
+        v0[groups[3]] -= 2.0 * DRIFT
+        flux = [c * _kecm(s, v0, l) / DT for c, l in zip(C4, groups)]
+        _CASE4.append((s, v0, by_tag, g, groups, S.wrap(s.box, s.x), flux))
+    return _CASE4[0]
+
+
+def _xsv(run):
+    return {n: q[:3] for n, q in run.items()}
+
+
+def _states(read, n):
+    return [read(k) for k in range(n)]
+
+
+def _compare_states(what, host, dev, every):
+    """scale (STOL), vcm and ke of every source's LAST application and its application count, at every read.  vcm and ke
+    are held to the `heat` net's limits for the same words (nets.HEAT_VCM_LIMIT, absolute in A/ps, and nets.HEAT_KE_LIMIT,
+    relative: 100 times what the order of a source's sum does to them in the reference)"""
+    ws = wc = wk = 0.0
+    for step in every:
+        for k, (a, b) in enumerate(zip(dev[step][3], host[step][3])):
+            assert a["applied"] == b["applied"], (what, step, k, a["applied"], b["applied"])
+            assert a["error_step"] == -1
+            ws = worse(ws, abs(a["scale"] - b["scale"]) / abs(b["scale"]))
+            wc = worse(wc, float(np.abs(a["vcm"] - b["vcm"]).max()))
+            wk = worse(wk, abs(a["kecm"] - b["kecm"]) / abs(b["kecm"]) if b["kecm"] else abs(a["kecm"]))
+            if b["applied"] == 0:
+                assert a["scale"] == 1.0 and not a["vcm"].any() and a["kecm"] == 0.0, (what, step, k)
+    print(f"{what}: state words, worst scale {ws:.2e} relative, vcm {wc:.2e} A/ps, ke {wk:.2e} relative")
+    assert ws < STOL and wc < nets.HEAT_VCM_LIMIT and wk < nets.HEAT_KE_LIMIT, (ws, wc, wk)
+
+
+def _resident4(sources, nsteps, every, first, cut=None):
+    """one resident brick of the four-source case.  A read at an even step finds its final half deferred (the state read
+    completes it); cut = (k, completed): mdp_heat_run(first + k) behind step k, whose final half is left pending across the
+    call unless `completed`.  {step: (x, [scale], v, [state])} by tag"""
+    s, v0, by_tag, g, groups, x_in, flux = _case4()
+    ctx, st, cutghost, skin, map_ = _context("rebomos")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        d.set_group(by_tag, GBIT)
+        d.heat(sources, first=first)
+        d.compute(1, 0)
+        out = {}
+        for step in range(1, nsteps + 1):
+            ev = step in every
+            defer = step % 2 == 0 if ev else True
+            if cut is not None and step == cut[0]:
+                assert not ev
+                defer = not cut[1]
+            d.step(0, 0, rebuild="auto", defer_final=defer)
+            if ev:
+                sts = _states(d.heat_state, len(sources))
+                x, v = _by_tag(ctx, d, s)
+                out[step] = (x, [q["scale"] for q in sts], v, sts)
+            if cut is not None and step == cut[0]:
+                d.heat_run(first + step)       # a pending final half completes inside, without the sources (INTEGRATION.md)
+        return out
+    finally:
+        ctx.close()
+
+
+@gpu
+def test_four_sources_with_four_nevery_from_first_seven(oracle, capsys):
+    """slots 2 and 3 of heat_src, of the apply kernel's select and of the sums; a `due` word that is partial at most steps
+    (nevery 1, 2, 3, 5: full only where 30 divides the step); first = 7, so step n of the run is due where (7 + n) % nevery
+    == 0.  60 steps, the state read at EVERY step: a source that was not due reports its previous application, and the
+    application counts are exact"""
+    s, v0, by_tag, g, groups, x_in, flux = _case4()
+    nevery, first, nsteps = (1, 2, 3, 5), 7, 60
+    every = tuple(range(1, nsteps + 1))
+    make, rebuild_every = _oracle_engine(oracle, "rebomos")
+    host, lowest = heatref.host_heat(make, s, v0, nsteps, set(every), rebuild_every, g,
+                                     [dict(group=l, eflux=f, nevery=ne) for l, f, ne in zip(groups, flux, nevery)], dt=DT, first=first,
+                                     skin=2.0, states=True)
+    assert lowest > 0.5
+    dev = _resident4([dict(eflux=f, nevery=ne, bit=b) for f, ne, b in zip(flux, nevery, BITS4)], nsteps, every, first)
+    with capsys.disabled():
+        _compare(s, _xsv(host), _xsv(dev), g, x_in, v0, "four sources, nevery 1 2 3 5, first 7", every)
+        _compare_states("four sources, nevery 1 2 3 5, first 7", host, dev, every)
+    assert [q["applied"] for q in dev[nsteps][3]] == [60, 30, 20, 12]
+    # at step 1 (8 = 7 + 1) sources 0 and 1 alone were due; a source that is not due keeps what it reported
+    assert [q["applied"] for q in dev[1][3]] == [1, 1, 0, 0]
+    a, b = dev[4][3][2], dev[2][3][2]      # source 2 (nevery 3) is due at steps 2, 5, ...: at 3 and 4 it reports step 2's words
+    assert (a["scale"], a["kecm"], a["applied"]) == (b["scale"], b["kecm"], 1) and np.array_equal(a["vcm"], b["vcm"])
+    assert dev[5][3][2]["applied"] == 2 and dev[5][3][2]["kecm"] != b["kecm"]
+    assert all(q["scale"] != 1.0 for q in dev[nsteps][3])
+
+
+_REF2 = {}
+
+
+@gpu
+@pytest.mark.parametrize("path", ["resident-pending", "resident-completed", "hostlinked"])
+def test_two_runs_in_a_row_on_one_context(oracle, path, capsys):
+    """mdp_heat_run a second time, at step 30 of 60, which is due for all four sources (nevery 3, 5, 2, 1): step 30 belongs
+    to the first run and is heated once -- not again as the second run's first step, whose counter starts at 30.  Resident
+    with the seam's final half left pending across the call it completes there WITHOUT the sources (what INTEGRATION.md
+    says of a final half pending at mdp_heat_run): the reference skips the applications of step 30 then.  Host-linked
+    (mdp_hnve_final has run) and resident with the half completed: heated"""
+    s, v0, by_tag, g, groups, x_in, flux = _case4()
+    nevery, nsteps, k = (3, 5, 2, 1), 60, 30
+    every = (7, 29, 31, 33, 45, 60)
+    completed = path != "resident-pending"
+    if completed not in _REF2:
+        make, rebuild_every = _oracle_engine(oracle, "rebomos")
+        _REF2[completed] = heatref.host_heat(make, s, v0, nsteps, set(every), rebuild_every, g,
+                                             [dict(group=l, eflux=f, nevery=ne) for l, f, ne in zip(groups, flux, nevery)], dt=DT,
+                                             cut=(k, completed), skin=2.0, states=True)
+    host, lowest = _REF2[completed]
+    assert lowest > 0.5
+    sources = [dict(eflux=f, nevery=ne, bit=b) for f, ne, b in zip(flux, nevery, BITS4)]
+    if path != "hostlinked":
+        dev = _resident4(sources, nsteps, every, 0, cut=(k, completed))
+    else:
+        dev = _hostlinked4(oracle, sources, nsteps, every, k)
+    with capsys.disabled():
+        _compare(s, _xsv(host), _xsv(dev), g, x_in, v0, f"two runs, {path}", every)
+        _compare_states(f"two runs, {path}", host, dev, every)
+    assert [q["applied"] for q in dev[nsteps][3]] == ([20, 12, 30, 60] if completed else [19, 11, 29, 59])
+
+
+def _hostlinked4(oracle, sources, nsteps, every, k):
+    """the four-source case host-linked from shuffled atoms, mdp_heat_run(k) behind step k"""
+    s, v0, by_tag, g, groups, x_in, flux = _case4()
+    perm = np.random.default_rng(17).permutation(s.n)
+    type_p, tag_p = s.type[perm].copy(), s.tag[perm].copy()
+    mask_p, gp, skin = by_tag[tag_p], g[perm], 2.0
+    c = capi.Context(0)
+    try:
+        P = oracle.rebomos_params(POT_REBOMOS)
+        c.rebomos_set_params(ob.product_rebomos_params(P))
+        cut = P.cut3rebo + skin
+
+        def upload(x, v):
+            xa, type_all, tag_all, _, _, nloc, _ = S.with_ghosts(S.System(s.box, x.copy(), type_p, tag_p, s.mass), cut)
+            c.set_atoms_host(nloc, xa, type_all, tag_all, 2, map_=[0, 0, 1])
+            c.set_skin(skin)
+            c.hnve_upload_v(v)
+            c.hnve_set_mask(mask_p)
+        c.set_box_host(s.box)
+        c.hnve_setup(DT, S.FTM2V, s.mass)
+        c.integrate_group(GBIT)
+        upload(x_in[perm].copy(), v0[perm])
+        c.heat_setup(sources, mvv2e=S.MVV2E)
+        c.heat_run(0)
+        c._ck(c.L.mdp_rebomos_compute_host(c.h, 0, 0, None, None, None, None, None))
+        dev = {}
+        for step in range(1, nsteps + 1):
+            moved, late = c.hnve_initial()
+            if moved or step % 25 == 0:
+                got = c.hnve_download(s.n, want=("x", "v"))
+                xw = S.wrap(s.box, got["x"])
+                xw[~gp] = got["x"][~gp]
+                upload(xw, got["v"])
+            c._ck(c.L.mdp_rebomos_compute_host(c.h, 0, 0, None, None, None, None, None))
+            c.hnve_final()
+            if step in every:
+                sts = _states(c.heat_state, len(sources))
+                got = c.hnve_download(s.n, want=("x", "v"))
+                xd, vd = np.zeros((s.n, 3)), np.zeros((s.n, 3))
+                xd[tag_p - 1], vd[tag_p - 1] = got["x"], got["v"]
+                dev[step] = (xd, [q["scale"] for q in sts], vd, sts)
+            if step == k:
+                c.heat_run(k)
+        return dev
+    finally:
+        c.close()
+
+
+def _fma(a, b, c):
+    """fl(a b + c) with ONE rounding, elementwise: Dekker's exact product and Knuth's exact sum give a b + c = s + t + e
+    exactly; s + (t + e) is then the rounded value except in rare ties, which the caller settles with _fma_exact"""
+    split = 134217729.0 * a
+    ah = split - (split - a)
+    al = a - ah
+    split = 134217729.0 * b
+    bh = split - (split - b)
+    bl = b - bh
+    p = a * b
+    e = ((ah * bh - p) + ah * bl + al * bh) + al * bl
+    s = p + c
+    bb = s - p
+    t = (p - (s - bb)) + (c - bb)
+    return s + (t + e)
+
+
+def _fma_exact(a, b, c):
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def _big_step(sources, s, v0, by_tag):
+    """one step of the 275 684-atom alloy on a fresh brick, final half on its own: (v by tag, [state of source k])"""
+    ctx, st, cutghost, skin, map_ = _context("aeam")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        d.set_group(by_tag, GBIT)
+        if sources is not None:
+            d.heat(sources, first=0)
+        d.compute(0, 0)
+        d.step(0, 0, rebuild=False, defer_final=False)
+        states = [d.heat_state(k) for k in range(len(sources))] if sources is not None else []
+        got = ctx.md_download(d.nlocal, want=("v",))
+        v = np.zeros((s.n, 3))
+        v[d.tags_local - 1] = got["v"]
+        return v, states
+    finally:
+        ctx.close()
+
+
+@gpu
+def test_the_control_workgroups_second_trip_against_fsum(capsys):
+    """275 684 aluminium atoms (fcc 41^3): heat_sums_kernel leaves 270 partial slots, so mdp_slot_sum_256<kHeatW> of the control
+    workgroup takes a second trip (the Langevin sums have the 70 304-atom case for theirs), and the last block holds 228
+    atoms: its first j only.  Four sources on tag classes modulo 8 inside an integrate group that leaves tag % 7 == 0 held,
+    each with a drift of its own.  One step; the velocities before the application come from a twin without sources.
+    scale, vcm and ke of every source against math.fsum over them to STOL = 1e-12 relative (any order of adding 275 684
+    terms stays within n 2^-53 = 3.1e-11; the device's fixed tree and fsum over ~30 000 terms of one sign for ke and m, and
+    a vcm that the drift keeps at some tenths of A/ps, do far better: measured below).  Every source atom's new velocity is
+    fma(scale, v, -vsub) of the downloaded words bit for bit; every other atom's is the twin's bit for bit."""
+    af = capi.AeamFile(POT_AEAM)
+    s = S.fcc_cell(4.045, 41)      # (aluminium alone: no three-body forces, whose float atomics would make the twin differ)
+    s.mass[1:3] = af.mass[:2]
+    assert s.n == 275684 and -(-s.n // 1024) == 270 and s.n % 1024 == 228
+    v0 = S.gaussian_velocities(s, 300.0, seed=95)
+    g = s.tag % 7 != 0
+    groups = [g & (s.tag % 8 == r) for r in (1, 2, 5, 6)]
+    drifts = [np.array(q) for q in ((0.5, -0.3, 0.2), (-0.4, 0.6, 0.3), (0.2, 0.3, -0.7), (-0.6, -0.2, -0.4))]
+    for l, dr in zip(groups, drifts):
+        v0[l] += dr
+    by_tag = np.zeros(s.n + 1, dtype=np.int32)
+    m = bathsref.ALL_BIT | np.where(g, GBIT, 0)
+    for bit, l in zip(BITS4, groups):
+        m = m | np.where(l, bit, 0)
+    by_tag[s.tag] = m
+    mass = s.mass[s.type]
+    flux = [c * heatref.kecm(v0, mass, l, S.FTM2V, S.MVV2E) * S.MVV2E / DT for c, l in zip(C4, groups)]
+    v_on, states = _big_step([dict(eflux=f, nevery=1, bit=b) for f, b in zip(flux, BITS4)], s, v0, by_tag)
+    v_off, _ = _big_step(None, s, v0, by_tag)
+    other = ~np.logical_or.reduce(groups)
+    assert np.array_equal(v_on[other], v_off[other]), "an atom of no source changed"
+    assert np.array_equal(v_off[~g], v0[~g])
+    worst = dict(scale=0.0, vcm=0.0, ke=0.0, mass=0.0)
+    for k, l in enumerate(groups):
+        st = states[k]
+        assert st["applied"] == 1 and st["error_step"] == -1
+        ml, vl = mass[l], v_off[l]
+        M = math.fsum(ml)
+        vcm = np.array([math.fsum(ml * vl[:, c]) for c in range(3)]) / M
+        ke = (0.5 * S.MVV2E * math.fsum(ml * (vl * vl).sum(axis=1))) * S.FTM2V
+        den = ke - 0.5 * float(vcm @ vcm) * M
+        assert den > 0.9 * ke                              # (ke - t keeps its digits: the drift is small against the thermal motion)
+        scale = math.sqrt((den + flux[k] * DT * S.FTM2V) / den)
+        worst["scale"] = max(worst["scale"], abs(st["scale"] - scale) / scale)
+        worst["vcm"] = max(worst["vcm"], float((np.abs(st["vcm"] - vcm) / np.abs(vcm)).max()))
+        worst["ke"] = max(worst["ke"], abs(st["kecm"] - den) / den)
+        worst["mass"] = max(worst["mass"], abs(st["mass"] - M) / M)
+        assert (st["scale"] > 1.0) == (C4[k] > 0.0) and st["scale"] != 1.0
+        # the rescaled velocities, from the words the control workgroup left
+        sc = np.float64(st["scale"])
+        vsub = (sc - 1.0) * st["vcm"]
+        assert np.all(vsub != 0.0)
+        want = _fma(sc, vl, -vsub[None, :])
+        for i, c in zip(*np.nonzero(v_on[l] != want)):     # (ties of the vectorised form: settled exactly)
+            want[i, c] = _fma_exact(float(sc), float(vl[i, c]), -float(vsub[c]))
+        assert np.array_equal(v_on[l], want), (k, int((v_on[l] != want).sum()))
+    with capsys.disabled():
+        print("275 684 atoms, four sources against fsum: " + ", ".join(f"{q} {w:.2e}" for q, w in worst.items()) + " relative")
+    assert all(w < STOL for w in worst.values()), worst
 
 
 # ---- 5. refusals ----------------------------------------------------------------------------------------------------

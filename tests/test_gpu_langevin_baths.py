@@ -8,6 +8,8 @@ inside it, integrated atoms in no bath, held atoms.  The three baths:
     A  300 -> 900 K, damp 0.05, seed 48271, scale {1: 2.0, 2: 0.5}, zero yes, tally yes
     B  100 -> 100 K, damp 0.02, seed 7919,                          zero no,  tally yes
     C  600 -> 200 K, damp 0.1,  seed 48271 (A's: the tags differ),  zero yes, tally no
+The fourth slot (bathsref.masks4: bath D on bit 32, cut out of what the three leave unthermostatted):
+    D  200 -> 500 K, damp 0.03, seed 104729,                        zero yes, tally yes
 Tolerances are the grouped thermostat's own: positions 1e-9 A, each tally 1e-9 eV; held atoms bit for bit."""
 import numpy as np
 import pytest
@@ -32,6 +34,8 @@ EVERY_ODD = (7, 14, 21, 49, 98, 133, 140, 161, 200)
 BATHS = (dict(t_start=300.0, t_stop=900.0, damp=0.05, seed=48271, ratio={1: 2.0, 2: 0.5}, zero=True, tally=True),
          dict(t_start=100.0, t_stop=100.0, damp=0.02, seed=7919, ratio=None, zero=False, tally=True),
          dict(t_start=600.0, t_stop=200.0, damp=0.1, seed=48271, ratio=None, zero=True, tally=False))
+BITS4 = bathsref.BATH_BITS4
+BATHS4 = BATHS + (dict(t_start=200.0, t_stop=500.0, damp=0.03, seed=104729, ratio=None, zero=True, tally=True),)
 
 
 def _system(style):
@@ -102,11 +106,11 @@ def _by_tag(ctx, d, s):
     return x, v
 
 
-def _layout(tags_local, by_tag):
-    """what the device's atom order offers the kernels: (a 64-atom wave with atoms of all three baths, an unthermostatted
+def _layout(tags_local, by_tag, BITS=BITS):
+    """what the device's atom order offers the kernels: (a 64-atom wave with atoms of all the baths, an unthermostatted
     and a held atom; a 256-atom block without a bath atom)"""
     m = by_tag[tags_local]
-    anyb = BITS[0] | BITS[1] | BITS[2]
+    anyb = sum(BITS)
     wave = block = False
     for i in range(0, len(m), 64):
         w = m[i:i + 64]
@@ -117,7 +121,7 @@ def _layout(tags_local, by_tag):
     return wave, block
 
 
-def _resident(style, s, v0, by_tag, setup, ntally, every, nsteps=NSTEPS, check_layout=False):
+def _resident(style, s, v0, by_tag, setup, ntally, every, nsteps=NSTEPS, check_layout=False, bits=BITS):
     """one resident brick; setup(d) sets the groups and the thermostat(s) (first = 0, last = nsteps).  Reads at `every`: a
     multiple of 14 among them finds its final half deferred (the tally read completes it), the others run it on their own.
     {step: (x, [tally of bath k], v)} by tag, and the device reneighborings while it ran"""
@@ -126,9 +130,9 @@ def _resident(style, s, v0, by_tag, setup, ntally, every, nsteps=NSTEPS, check_l
         d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
         setup(d)
         if check_layout:
-            wave, block = _layout(d.tags_local, by_tag)
-            assert wave, "no 64-atom wave holds all three baths, an unthermostatted and a held atom"
-            assert block, "no 256-atom block is free of bath atoms"
+            wave, block = _layout(d.tags_local, by_tag, bits)
+            assert wave, f"no 64-atom wave holds all {len(bits)} baths, an unthermostatted and a held atom"
+            assert block or len(bits) > 3, "no 256-atom block is free of bath atoms"     # (the fourth bath reaches into the left half)
         d.compute(1, 0)
         r0 = ctx.dd_info()["reneighbors"]
         out = {}
@@ -153,14 +157,16 @@ def _three(by_tag, groups, order=(0, 1, 2), nsteps=NSTEPS):
 
 
 def _compare(s, host, dev, g, x_in, v_in, what, every, xtol=1e-9, etol=1e-9):
-    worst_x, worst_e = 0.0, [0.0] * len(BATHS)
+    nb = len(next(iter(host.values()))[1])
+    worst_x, worst_e = 0.0, [0.0] * nb
     for step in every:
         xh, eh, vh = host[step]
         xd, ed, vd = dev[step]
         dx = xd - xh
         dx -= np.round(s.box.x2lamda(dx + s.box.lo)) @ s.box.h.T
         worst_x = worse(worst_x, float(np.abs(dx).max()))
-        for k in range(len(BATHS)):
+        assert len(ed) == len(eh) == nb
+        for k in range(nb):
             worst_e[k] = worse(worst_e[k], abs(ed[k] - eh[k]))
         assert np.array_equal(xd[~g], x_in[~g]), (what, step, "a held atom moved")
         assert np.array_equal(vd[~g], v_in[~g]), (what, step, "a held atom's velocity changed")
@@ -276,6 +282,63 @@ def test_the_order_of_the_slots_changes_nothing():
         assert np.array_equal(a[step][0], b[step][0]) and np.array_equal(a[step][2], b[step][2]), step
         for slot, k in enumerate(order):
             assert b[step][1][slot] == a[step][1][k], (step, k)
+
+
+# ---- 4b. the fourth slot: four baths against the reference, and every bath in slot 3 once --------------------------------
+def _case4(style):
+    s, v0 = _system(style)
+    by_tag, g, groups = bathsref.masks4(s)
+    bathsref.check_masks(s, g, groups)
+    return s, v0, by_tag, g, groups, S.wrap(s.box, s.x)
+
+
+def _four(by_tag, groups, order=(0, 1, 2, 3), nsteps=NSTEPS):
+    def setup(d):
+        d.set_group(by_tag, GBIT)
+        d.langevin_baths([_dev_bath(BATHS4[k], BITS4[k], groups[k]) for k in order], first=0, last=nsteps)
+    return setup
+
+
+def _four_baths_run(style):
+    key = (style, "four")
+    if key not in _DEV:
+        s, v0, by_tag, g, groups, x_in = _case4(style)
+        _DEV[key] = _resident(style, s, v0, by_tag, _four(by_tag, groups), 4, EVERY_ODD, check_layout=True, bits=BITS4)
+    return _DEV[key]
+
+
+@pytest.mark.parametrize("style", ["rebomos", "aeam"])
+def test_four_baths_follow_the_host_reference(oracle, style, capsys):
+    """the fourth select of mdp_lgv_bath and the fourth tally slot: own ramp, damp, seed and tally per bath, `zero yes` on
+    the fourth (its mean is taken over D's atoms alone).  The bounds of the three-bath cases"""
+    s, v0, by_tag, g, groups, x_in = _case4(style)
+    make, rebuild_every = _oracle_engine(oracle, style)
+    baths = [(_ref_bath(s, b), l) for b, l in zip(BATHS4, groups)]
+    host = bathsref.host_baths(make, s, v0, NSTEPS, set(EVERY_ODD), rebuild_every, g, baths)
+    dev, renb = _four_baths_run(style)
+    assert renb >= 1, "the device never reneighbored: the mask was not permuted"
+    with capsys.disabled():
+        _compare(s, host, dev, g, x_in, v0, f"four baths {style} ({[int(l.sum()) for l in groups]} of {int(g.sum())} group atoms, "
+                 f"{renb} reneighborings)", EVERY_ODD)
+    last = host[NSTEPS][1]
+    assert abs(last[0]) > 1e-3 and abs(last[1]) > 1e-3 and last[2] == 0.0 and abs(last[3]) > 1e-3 and dev[NSTEPS][1][2] == 0.0
+    # D's atoms are thermostatted: the run differs from the three-bath run on them
+    three, _ = _three_baths_run(style, EVERY_ODD)
+    assert np.abs(dev[NSTEPS][2][groups[3]] - three[NSTEPS][2][groups[3]]).max() > 1e-3
+
+
+def test_the_order_of_four_slots_changes_nothing():
+    """the three rotations of (A, B, C, D): with the run in order, every bath sits in slot 3 -- and in every other slot -- once"""
+    s, v0, by_tag, g, groups, x_in = _case4("rebomos")
+    a, _ = _four_baths_run("rebomos")
+    for order in ((1, 2, 3, 0), (2, 3, 0, 1), (3, 0, 1, 2)):
+        b, renb = _resident("rebomos", s, v0, by_tag, _four(by_tag, groups, order), 4, EVERY_ODD)
+        assert renb >= 1
+        for step in EVERY_ODD:
+            assert np.array_equal(a[step][0], b[step][0]) and np.array_equal(a[step][2], b[step][2]), (order, step)
+            for slot, k in enumerate(order):
+                assert b[step][1][slot] == a[step][1][k], (order, step, k)
+    assert all(a[NSTEPS][1][k] != 0.0 for k in (0, 1, 3))
 
 
 @pytest.mark.parametrize("style", ["rebomos", "aeam"])
