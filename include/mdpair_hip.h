@@ -587,6 +587,58 @@ int mdp_heat_run(mdp_ctx *ctx, long long first);
 int mdp_heat_state(mdp_ctx *ctx, int src, double *out /* MDP_HEAT_STATE_LEN */);
 int mdp_heat_off(mdp_ctx *ctx);
 
+/* ---- Indenters: spheres, cylinders and planes that push on the atoms (LAMMPS fix indent with `units box` and a centre
+ * that moves at a constant velocity; the plugin style `fix indent/mdp`) -----
+ * Up to MDP_INDENT_MAX indenters, indenter k on the owned atoms whose mask has groupbit[k]; a bit of 0 means every owned
+ * atom and needs no mask.  Indenters may share atoms: their forces add.  For the forces of step n the centre is
+ *     ctr = c + vel (n - first) dt                                   (LAMMPS' vdisplace(c, vel); dt is the context's own)
+ * and an atom at x, with D = x - ctr through Domain::minimum_image of the context's box (mdp_dd_setup / mdp_set_box_host:
+ * one wrap per periodic dimension, z then y then x, a wrap in z carrying (xz, yz) and one in y carrying xy), feels what
+ * follows.  A brick's periodicity is that of mdp_dd_config; the box of mdp_set_box_host carries no boundary flags and is
+ * taken to be periodic in all three dimensions (what that call is for: one periodic rank) -- a host whose box is not must
+ * not set indenters on a host-linked context, and the plugin's fix refuses such a box.
+ *     sphere, cylinder (D without its component along dim):  r = |D|,  dr = r - R (side out) or R - r (side in)
+ *     plane:  dr = x[dim] - c[dim] (lo) or c[dim] - x[dim] (hi); no minimum image, as in LAMMPS
+ *     dr < 0:  a force of magnitude K dr^2 out of the indenter's body (along D / r for side out, against it for side in,
+ *              along +dim for lo and -dim for hi); the indenter's energy gains -K/3 dr^3, the force on the indenter
+ *              minus the atom's force.  r == 0: no force (LAMMPS divides by zero there), the energy is counted.
+ * The pass is two launches: one lane per owned atom adds the force into f and the blocks leave per-indenter sums in
+ * fixed slots; one workgroup adds the slots in a fixed order and leaves the state in device memory.  No float atomics and
+ * no host wait: a run is bitwise reproducible, and the same whether or not the host defers final halves.
+ * Every kick of v by f begins with the pass unless the forces the context holds have had theirs already.  That flag is
+ * cleared behind every initial half (a compute follows and overwrites f) and by _setup / _run, which take the forces of
+ * the context at the call to be the pair style's alone -- true of what Verlet::setup has just computed; a host that calls
+ * either in mid-run computes the forces again before its next kick.  The step of the current forces is `first` plus the
+ * initial halves since _run.  The minimiser does not run the pass.
+ *   setup:  replaces the indenters that are on.  A final half pending at the call completes first, without indenters.
+ *           Refused (MDP_EINVAL / MDP_ESTATE, each with its cause): n outside 1 .. MDP_INDENT_MAX, K or R negative or not
+ *           finite, a centre or velocity that is not finite, a shape, dim or side out of range, a cylinder with a velocity
+ *           along its axis, a group bit with no mask for the current atoms, no box on the context, the minimiser, the
+ *           Nose-Hoover chain or heat sources on the context and a brick of several ranks -- those calls in turn refuse
+ *           while indenters are on.  Langevin thermostats are welcome.
+ *   run:    a final half pending at the call completes first, with the pass of its step if that is still due; then the
+ *           centre starts again at c: the forces the context holds count as those of step `first`, without a pass.
+ *   state:  blocking; completes a deferred final half, and runs the pass if the current forces have not had it (the
+ *           state of step `first` before any kick).  out[0] energy, [1..4) force on the indenter, [4] atoms in contact,
+ *           [5] the step these belong to, [6..9) the centre at that step, [9] passes since setup.
+ *   off:    a pending final half completes first, with its pass; frees what was held. */
+#define MDP_INDENT_MAX 4
+#define MDP_INDENT_STATE_LEN 10
+enum { MDP_INDENT_SPHERE = 0, MDP_INDENT_CYLINDER = 1, MDP_INDENT_PLANE = 2 };
+typedef struct {
+  int shape;     /* MDP_INDENT_SPHERE, _CYLINDER, _PLANE */
+  int dim;       /* 0, 1, 2: the cylinder's axis, the plane's normal; a sphere ignores it */
+  int side;      /* sphere, cylinder: 0 out, 1 in; plane: 0 lo, 1 hi */
+  double k;      /* force / length^2 */
+  double c[3];   /* the centre at step `first`; a cylinder uses the two components across dim, a plane c[dim] */
+  double r;
+  double vel[3]; /* length / time */
+} mdp_indent_config;
+int mdp_indent_setup(mdp_ctx *ctx, int n, const mdp_indent_config *cfg, const int *groupbit);
+int mdp_indent_run(mdp_ctx *ctx, long long first);
+int mdp_indent_state(mdp_ctx *ctx, int k, double *out /* MDP_INDENT_STATE_LEN */);
+int mdp_indent_off(mdp_ctx *ctx);
+
 /* ---- FIRE minimiser on the device (LAMMPS min_style fire, FIRE 2.0 with the eulerimplicit integrator and LAMMPS' defaults)
  * For a resident context on one rank, after mdp_md_setup + mdp_dd_setup (one brick) + mdp_dd_reneighbor.  An iteration
  * is two small launches next to the force compute: per-block partial sums of v.f, v.v, f.f and the largest |v_c| in

@@ -35,30 +35,6 @@ __device__ __forceinline__ int heat_src(const HeatBits &B, int m)
   return k;
 }
 
-// The per-block sum of mdp_block_sum_256 (lanes by xor-shuffle 32..1, then the four waves as (w0 + w1) + (w2 + w3)) with
-// one difference: a wave none of whose lanes met an atom of source b leaves the five sums of b at the 0.0 they are,
-// without shuffling zeros around -- the same bits, and what the pass costs where the sources are strips of a large box
-// (most waves see no source atom, the others one source).  seen: bit b set if this lane met an atom of source b; the
-// branch is on a ballot, so a wave takes it as one.  Every lane must call it.
-__device__ __forceinline__ void heat_block_sum(const double *e, const int seen, double *part)
-{
-  __shared__ double wsum[kHeatW][4];
-#pragma unroll
-  for (int b = 0; b < kS; b++) {
-    const bool any = __ballot((seen >> b) & 1) != 0;
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-      double s = e[5 * b + j];
-      if (any)
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-      if ((threadIdx.x & 63) == 0) wsum[5 * b + j][threadIdx.x >> 6] = s;
-    }
-  }
-  __syncthreads();
-  const int k = threadIdx.x;
-  if (k < kHeatW) part[kHeatW * (size_t) blockIdx.x + k] = (wsum[k][0] + wsum[k][1]) + (wsum[k][2] + wsum[k][3]);
-}
-
 // part[kHeatW b + 5 k + j]: the sums over block b of m v.v, m vx, m vy, m vz and m of source k's atoms.  A block takes
 // kHeatPer x 256 consecutive atoms, a lane kHeatPer of them at a stride of 256 (coalesced), added in that order: a quarter
 // of the slots for the control workgroup to read and a quarter of the shuffles.  Every lane reaches the block sum; an
@@ -97,7 +73,7 @@ __global__ __launch_bounds__(256) void heat_sums_kernel(const int n, const doubl
       e[5 * b + 4] += k == b ? m : 0.0;
     }
   }
-  heat_block_sum(e, seen, part);
+  mdp_block_sum_256_seen<kS>(e, seen, part);
 }
 
 // what the one workgroup needs besides the partials
@@ -338,6 +314,7 @@ int mdp_heat_setup(mdp_ctx *c, int nsrc, const mdp_heat_config *cfg, const int *
   }
   if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
   if (c->nhc.on) return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: the Nose-Hoover chain (mdp_nhc_setup) is on; heat sources run without a thermostat");
+  if (c->indent.on) return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: indenters (mdp_indent_setup) are on; mdp_indent_off first");
   if (c->lgv.on)
     return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: the Langevin thermostat (mdp_langevin_setup) is on; heat sources run without a thermostat");
   if (c->dd.on && c->dd.G.nranks > 1)

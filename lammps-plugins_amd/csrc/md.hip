@@ -702,6 +702,7 @@ int lgv_final(mdp_ctx *c, bool writeback)
 // plain.  lgv_writeback = false: the forces of a new run's setup come next, so f stays as the compute left it.
 int md_final_half(mdp_ctx *c, bool lgv_writeback = true)
 {
+  if (c->indent.on && !c->indent.applied) MDP_TRY(mdp_indent_pass(c)); // (indenters: post_force of the step this half completes)
   if (c->nhc.on) return mdp_nhc_final(c);
   if (c->lgv.on) return lgv_final(c, lgv_writeback);
   bool masked = false;
@@ -722,6 +723,7 @@ int md_final_half(mdp_ctx *c, bool lgv_writeback = true)
 int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double hardsq, const MdpStyleCheck &sc,
                       bool zero_f, double *dset, double *dclr)
 {
+  if (c->indent.on && !c->indent.applied) MDP_TRY(mdp_indent_pass(c)); // (indenters: post_force of the forces this kernel kicks with first)
   // a final half pending across a thermostat set-up (mdp_nhc_setup / _run, mdp_langevin_run by a host that does not
   // defer it) goes first, on its own, and leaves f as it was: the setup of the new run sees the compute's forces alone,
   // as after Verlet::setup
@@ -736,6 +738,7 @@ int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, dou
     with_final = false;
     mdp_heat_count_step(c);
   }
+  mdp_indent_count_step(c); // (the initial half below moves the atoms: a compute follows and overwrites f)
   const double *vscale = nullptr;
   bool lgv = false, masked = false;
   const bool baths = c->lgv.many();

@@ -914,6 +914,8 @@ int mdp_destroy(mdp_ctx *c)
   c->heat.st.release();
   c->heat.part.release();
   c->heat.count.release();
+  c->indent.st.release();
+  c->indent.part.release();
   c->fire.st.release();
   c->fire.part.release();
   c->fire.fsave.release();

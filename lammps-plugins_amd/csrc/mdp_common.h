@@ -352,6 +352,23 @@ struct MdpHeat {
 static constexpr int kHeatScale = 0, kHeatVcm = 1, kHeatKe = 4, kHeatM = 5, kHeatN = 6, kHeatErrStep = 7, kHeatS = 8, kHeatVsub = 9,
                      kHeatWords = 12, kHeatErr = MDP_HEAT_MAXSRC * kHeatWords, kHeatTotal = kHeatErr + 2;
 static constexpr int kHeatW = 5 * MDP_HEAT_MAXSRC; // per source: sum m v.v, m vx, m vy, m vz, m
+// Indenters (indent.hip): LAMMPS fix indent with a constant velocity, added into f by one pass in front of the kick that
+// first consumes a compute's forces.  The host keeps the configuration, the number of initial halves since mdp_indent_run
+// and whether the current forces have had their pass; the sums live on the device.  st: indenter k keeps its
+// MDP_INDENT_STATE_LEN state words (mdp_indent_state layout) at st + k * MDP_INDENT_STATE_LEN
+struct MdpIndent {
+  bool on = false;
+  bool applied = false;     // the forces the context holds have had their pass.  Cleared behind every initial half
+                            // (mdp_indent_count_step) and by mdp_indent_setup / _run (indent_restart), nowhere else
+  int n = 0;
+  mdp_indent_config cfg[MDP_INDENT_MAX];
+  int bit[MDP_INDENT_MAX] = {0, 0, 0, 0};
+  long long first = 0;      // the step of mdp_indent_run
+  long long nhalf = 0;      // initial halves since: the current forces are those of step first + nhalf
+  DevBuf<double> st;        // [MDP_INDENT_MAX * MDP_INDENT_STATE_LEN]
+  DevBuf<double> part;      // per-block partial sums, kIndW per block (fixed slots [block][indenter][5])
+};
+static constexpr int kIndW = 5 * MDP_INDENT_MAX; // per indenter: energy, the atoms' fx, fy, fz, atoms in contact
 // FIRE minimiser (fire.hip): the control block lives in st on the device; the host keeps the configuration and what it
 // has queued.  Control block, in doubles (flags and counters as whole numbers):
 enum MdpFireWord {
@@ -585,6 +602,31 @@ template <int W> __device__ __forceinline__ void mdp_block_sum_256(const double 
   if (k < W) part[W * (size_t) blockIdx.x + k] = (wsum[k][0] + wsum[k][1]) + (wsum[k][2] + wsum[k][3]);
 }
 __device__ __forceinline__ void mdp_block_sum_256(double e, double *part) { mdp_block_sum_256<1>(&e, part); }
+
+// ... for S groups of five sums each (the heat sources, the indenters), with one difference: a wave none of whose lanes
+// met an atom of group b leaves the five sums of b at the 0.0 they are, without shuffling zeros around -- the same bits,
+// and what the pass costs where the groups are strips of a large box (most waves see no atom of any, the others one).
+// seen: bit b set if this lane met an atom of group b; the branch is on a ballot, so a wave takes it as one.  Every lane
+// must call it.
+template <int S> __device__ __forceinline__ void mdp_block_sum_256_seen(const double *e, const int seen, double *part)
+{
+  constexpr int W = 5 * S;
+  __shared__ double wsum[W][4];
+#pragma unroll
+  for (int b = 0; b < S; b++) {
+    const bool any = __ballot((seen >> b) & 1) != 0;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+      double s = e[5 * b + j];
+      if (any)
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      if ((threadIdx.x & 63) == 0) wsum[5 * b + j][threadIdx.x >> 6] = s;
+    }
+  }
+  __syncthreads();
+  const int k = threadIdx.x;
+  if (k < W) part[W * (size_t) blockIdx.x + k] = (wsum[k][0] + wsum[k][1]) + (wsum[k][2] + wsum[k][3]);
+}
 
 // The slot sum: ONE 256-lane workgroup adds npart slots of W values, out[k] = sum over b of part[W * b + k] on every
 // lane -- slots strided by 256 per lane, then the tree 128..1 in shared memory; one pass over the slots for all W.
@@ -825,6 +867,7 @@ struct mdp_ctx {
   MdpLangevin lgv;                 // Langevin thermostat of the integrate calls (mdp_langevin_setup)
   MdpFire fire;                    // FIRE minimiser: mdp_md_advance launches its advance kernel while it is on (mdp_fire_setup)
   MdpHeat heat;                    // constant-flux heat sources behind every final half (mdp_heat_setup)
+  MdpIndent indent;                // indenters in front of the kicks (mdp_indent_setup)
   // groups (mdp_md_set_mask / mdp_hnve_set_mask, mdp_integrate_group, mdp_langevin_group)
   DevBuf<int> mask;                // [nlocal] atom->mask: device order (resident; permuted and migrated with the atoms) or the host's order
   bool mask_set = false;
@@ -1090,6 +1133,16 @@ inline void mdp_heat_count_step(mdp_ctx *c)
 }
 int mdp_heat_mask(mdp_ctx *c, const char *who);
 int mdp_heat_check(mdp_ctx *c);
+// indenters (indent.hip) when c->indent.on.  _pass: the force pass and the control workgroup for the forces the context
+// holds, which are those of step first + nhalf; sets `applied`.  md_final_half and md_launch_advance (md.hip) call it
+// first thing unless `applied`.  _count_step: behind an initial half -- the atoms have moved, a compute follows
+int mdp_indent_pass(mdp_ctx *c);
+inline void mdp_indent_count_step(mdp_ctx *c)
+{
+  if (!c->indent.on) return;
+  c->indent.nhalf++;
+  c->indent.applied = false;
+}
 void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
 void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds
 void mdp_profile_release(mdp_ctx *c); // frees what profile.hip holds

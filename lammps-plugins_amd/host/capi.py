@@ -64,6 +64,13 @@ class HeatConfig(C.Structure):
     """mirror of mdp_heat_config"""
     _fields_ = [("eflux", C.c_double), ("nevery", C.c_int), ("mvv2e", C.c_double)]
 HEAT_MAXSRC, HEAT_STATE_LEN = 4, 8   # MDP_HEAT_MAXSRC, MDP_HEAT_STATE_LEN of include/mdpair_hip.h
+class IndentConfig(C.Structure):
+    """mirror of mdp_indent_config"""
+    _fields_ = [("shape", C.c_int), ("dim", C.c_int), ("side", C.c_int), ("k", C.c_double), ("c", C.c_double * 3),
+                ("r", C.c_double), ("vel", C.c_double * 3)]
+INDENT_MAX, INDENT_STATE_LEN = 4, 10   # MDP_INDENT_MAX, MDP_INDENT_STATE_LEN of include/mdpair_hip.h
+INDENT_SHAPES = {"sphere": 0, "cylinder": 1, "plane": 2}
+INDENT_SIDES = {"out": 0, "in": 1, "lo": 0, "hi": 1}
 class FireConfig(C.Structure):
     _fields_ = [("etol", C.c_double), ("ftol", C.c_double), ("maxiter", C.c_longlong), ("maxeval", C.c_longlong),
                 ("dmax", C.c_double), ("tmax", C.c_double), ("tmin", C.c_double), ("delaystep", C.c_int),
@@ -113,6 +120,7 @@ EXPORTS = [
     "mdp_rebomos_centre_paths",
     "mdp_heatflux_sums", "mdp_md_download_vatom",
     "mdp_heat_setup", "mdp_heat_run", "mdp_heat_state", "mdp_heat_off",
+    "mdp_indent_setup", "mdp_indent_run", "mdp_indent_state", "mdp_indent_off",
 ]
 
 
@@ -618,6 +626,39 @@ class Context:
 
     def heat_off(self):
         self._ck(self.L.mdp_heat_off(self.h))
+
+    # ---------------- indenters in front of the kicks (fix indent/mdp)
+    def indent_setup(self, indenters):
+        """mdp_indent_setup: indenters is a list of dicts shape ("sphere", "cylinder", "plane" or 0, 1, 2), k, r (a plane
+        needs none), c (the centre at the run's first step, three numbers), and optionally dim (0, 1, 2: the cylinder's
+        axis, the plane's normal), side ("out" / "in", "lo" / "hi" or 0 / 1), vel (three numbers), bit (the group bit; 0:
+        every owned atom)"""
+        n = len(indenters)
+        cfgs = (IndentConfig * max(n, 1))()
+        bits = (C.c_int * max(n, 1))()
+        for k, q in enumerate(indenters):
+            cfgs[k].shape = INDENT_SHAPES.get(q["shape"], q["shape"])
+            cfgs[k].dim = int(q.get("dim", 0))
+            cfgs[k].side = INDENT_SIDES.get(q.get("side", 0), q.get("side", 0))
+            cfgs[k].k, cfgs[k].r = float(q["k"]), float(q.get("r", 0.0))
+            cfgs[k].c[:] = [float(a) for a in q["c"]]
+            cfgs[k].vel[:] = [float(a) for a in q.get("vel", (0.0, 0.0, 0.0))]
+            bits[k] = int(q.get("bit", 0))
+        self._ck(self.L.mdp_indent_setup(self.h, C.c_int(n), cfgs, bits))
+
+    def indent_run(self, first):
+        self._ck(self.L.mdp_indent_run(self.h, C.c_longlong(first)))
+
+    def indent_state(self, k):
+        """indenter k for the forces the context holds (blocking; runs their pass if no kick has yet): its energy, the
+        force on it, the atoms in contact, the step these belong to, the centre at that step, passes since setup"""
+        out = np.zeros(INDENT_STATE_LEN)
+        self._ck(self.L.mdp_indent_state(self.h, C.c_int(int(k)), _dp(out)))
+        return dict(energy=float(out[0]), force=out[1:4].copy(), contacts=int(out[4]), step=int(out[5]), centre=out[6:9].copy(),
+                    passes=int(out[9]))
+
+    def indent_off(self):
+        self._ck(self.L.mdp_indent_off(self.h))
 
     # ---------------- FIRE minimiser of a resident one-brick context (minimize/mdp)
     def fire_setup(self, etol, ftol, maxiter, maxeval, **modify):

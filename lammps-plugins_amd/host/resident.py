@@ -723,6 +723,33 @@ class DeviceDomain:
         self.ctx.heat_off()
         self._final_pending = False
 
+    def indent(self, indenters, first=0):
+        """Indenters (LAMMPS fix indent with `units box`) that push on the atoms of this domain: a list of up to four dicts
+        as capi.Context.indent_setup takes them -- shape, k, r, c, and optionally dim, side, vel, bit (the group bit in the
+        mask of set_group; 0: every atom).  The centre is c at step `first` and moves by vel dt per step.  The forces the
+        domain holds at the call are taken to be the pair style's alone (call it behind compute(), as a fix's setup runs
+        behind Verlet::setup).  One GPU; no Nose-Hoover chain, heat sources or minimiser next to them."""
+        if self.world > 1:
+            raise ValueError("indenters run on one GPU only (their sums would need an all-reduce per step)")
+        self.ctx.indent_setup(indenters)
+        self.indent_run(first)
+
+    def indent_run(self, first):
+        """A further run of the indenters set by indent(), from step `first`: the centres start again at c.  A pending
+        final half completes first, with its indenter forces; compute() again before the next step."""
+        self.ctx.indent_run(first)
+        self._final_pending = False
+
+    def indent_state(self, k):
+        """indenter k for the current forces (completes a deferred final half first): capi.Context.indent_state"""
+        self.flush()
+        return self.ctx.indent_state(k)
+
+    def indent_off(self):
+        """back to the pair style's forces alone; a deferred final half completes inside mdp_indent_off, with its pass"""
+        self.ctx.indent_off()
+        self._final_pending = False
+
     def minimize(self, etol, ftol, maxiter, maxeval, chunk=64, **modify):
         """FIRE minimisation (LAMMPS min_style fire with its defaults; **modify: capi.FIRE_DEFAULTS) of this domain on the
         device, one GPU only; returns the final state (capi.Context.fire_state).  The velocities are zero afterwards

@@ -345,6 +345,8 @@ class Fix : protected Pointers {
   virtual void reset_dt() {}
   virtual double compute_scalar() { return 0.0; } // thermo f_ID
   virtual void *extract(const char *, int &) { return nullptr; } // what a fix hands another one (Fix::extract)
+  int vector_flag = 0, size_vector = 0;                          // a global vector: thermo f_ID[k], k = 1 .. size_vector
+  virtual double compute_vector(int) { return 0.0; }             // its element k - 1
 };
 
 // the part of LAMMPS' Compute a global-vector or global-array compute style touches (compute.h of the 2 Aug 2023 release)

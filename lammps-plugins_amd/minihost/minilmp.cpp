@@ -1014,6 +1014,25 @@ struct Host {
     return cp;
   }
 
+  // A thermo column f_ID (the fix's scalar: k = 0) or f_ID[k] (element k of its global vector).  Refused: an unknown ID
+  // (must_exist; otherwise nullptr: the fix may be defined later), an index on a fix without a vector or out of bounds.
+  Fix *fix_ref(const std::string &c, bool must_exist, int &k)
+  {
+    const size_t lb = c.find('['), rb = c.find(']');
+    const std::string id = c.substr(2, lb == std::string::npos ? lb : lb - 2);
+    Fix *f = fix_by_id(id);
+    k = 0;
+    if (!f) {
+      if (must_exist) error.all(FLERR, "Could not find thermo custom fix ID: " + id);
+      return nullptr;
+    }
+    if (lb == std::string::npos) return f;
+    if (rb != std::string::npos && rb > lb + 1) k = atoi(c.substr(lb + 1, rb - lb - 1).c_str());
+    if (!f->vector_flag || k < 1 || k > f->size_vector)
+      error.all(FLERR, "Thermo custom fix " + std::string(f->id) + " is a vector of " + std::to_string(f->size_vector) + ": " + c + " is not one of its elements");
+    return f;
+  }
+
   void print_thermo()
   {
     const double ke = kinetic(), t = dof() > 0 ? 2.0 * ke / (dof() * BOLTZ) : 0.0;
@@ -1035,10 +1054,10 @@ struct Host {
         else if (c == "etotal") v = pe + ke;
         else if (c == "ecouple") v = ecouple();
         else if (c == "econserve") v = pe + ke + ecouple();
-        else if (c.compare(0, 2, "f_") == 0) {
-          Fix *f = fix_by_id(c.substr(2));
-          if (!f) error.all(FLERR, "Could not find thermo custom fix ID: " + c.substr(2));
-          v = f->compute_scalar();
+        else if (c.compare(0, 2, "f_") == 0) { // f_ID: the fix's scalar; f_ID[k]: element k of its global vector
+          int k = 0;
+          Fix *f = fix_ref(c, true, k);
+          v = k ? f->compute_vector(k - 1) : f->compute_scalar();
         }
         else if (c.compare(0, 2, "c_") == 0) { // c_ID[k] / c_ID[i][j]: evaluated once per step
           int i = 0, j = 0;
@@ -1980,6 +1999,9 @@ struct Script {
           if (col.compare(0, 2, "c_") == 0) {
             int i, j;
             H.compute_ref(col, false, i, j);
+          } else if (col.compare(0, 2, "f_") == 0) { // ... and an index on a fix defined by now
+            int k;
+            H.fix_ref(col, false, k);
           }
       }
       else if (w[1] == "one") H.thermo_cols = {"step", "temp", "epair", "emol", "etotal", "press"};

@@ -11,6 +11,7 @@
 #include "error.h"
 #include "force.h"
 #include "group.h"
+#include "modify.h"
 #include "neighbor.h"
 #include "output.h"
 #include "pair.h"
@@ -122,6 +123,9 @@ void MinimizeMDP::command(int narg, char **arg)
   if (comm->nprocs != 1)
     error->all(FLERR, "minimize/mdp runs on one MPI rank (its sums would need an all-reduce per iteration)");
   if (!domain->xperiodic || !domain->yperiodic || !domain->zperiodic) error->all(FLERR, "minimize/mdp needs a periodic box");
+  for (int i = 0; i < modify->nfix; i++) // (LAMMPS' minimiser would add the indenters' forces; this one sees the pair style's alone)
+    if (strcmp(modify->fix[i]->style, "indent/mdp") == 0)
+      error->all(FLERR, std::string("minimize/mdp: fix ") + modify->fix[i]->id + " (indent/mdp) is not applied by the minimiser; unfix it first");
   const int style_id = mdp_pair_style_id(force->pair);
   if (!style_id) error->all(FLERR, "minimize/mdp requires a pair style of this plugin (rebomos or aeam)");
   if (const char *e = getenv("MDP_REBOMOS_HOST_LIST"))

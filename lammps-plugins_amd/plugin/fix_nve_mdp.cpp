@@ -92,6 +92,7 @@ FixNVEMDP::FixNVEMDP(LAMMPS *lmp, int narg, char **arg)
 {
   memset(&baths, 0, sizeof baths);
   memset(&heat, 0, sizeof heat);
+  memset(&indent, 0, sizeof indent);
   if (narg < 3 || (narg - 3) % 2) error->all(FLERR, "Illegal fix nve/mdp command");
   if (igroup < 0)
     error->all(FLERR, std::string("Fix ") + arg[2] + " requires group all or a group defined by the group command: could not find fix group ID " + arg[1]);
@@ -226,6 +227,14 @@ void FixNVEMDP::setup(int vflag)
     if (mdp_heat_run(c, (long long) update->beginstep) != MDP_OK) fail(c);
     heat_ctx = c;
   }
+  // indenters (fix indent/mdp): the forces the context holds now are the setup's, the pair style's alone, and the first
+  // kick of the run adds the indenters' for step beginstep in front of itself -- FixIndent::setup's post_force
+  if (indent.count) {
+    if (heat.count) error->all(FLERR, "Fix nve/mdp: indenters (fix indent/mdp) and heat sources (fix heat/mdp) in one run");
+    if (mdp_indent_setup(c, indent.count, indent.cfg, indent.bit) != MDP_OK) fail(c);
+    if (mdp_indent_run(c, (long long) update->beginstep) != MDP_OK) fail(c);
+    indent_ctx = c;
+  }
   if (!baths.count) return;
   if (baths.count == 1) {
     if (mdp_langevin_setup(c, &baths.cfg[0]) != MDP_OK) fail(c);
@@ -243,9 +252,18 @@ void *FixNVEMDP::extract(const char *name, int &dim)
   if (strcmp(name, "mdp_run_ctx") == 0) return &lgv_ctx;
   if (strcmp(name, "mdp_heat_sources") == 0) return &heat;
   if (strcmp(name, "mdp_heat_ctx") == 0) return &heat_ctx;
+  if (strcmp(name, "mdp_indenters") == 0) return &indent;
+  if (strcmp(name, "mdp_indent_ctx") == 0) return &indent_ctx;
   if (strcmp(name, "mdp_steps_ctx") == 0) return &run_ctx;
   if (strcmp(name, "mdp_bricks") == 0) return &bricks;
   return nullptr;
+}
+
+bool FixNVEMDP::indent_masked() const
+{
+  for (int k = 0; k < indent.count; k++)
+    if (indent.bit[k]) return true;
+  return false;
 }
 
 double FixNVEMDP::group_count() { return grouped() ? (double) group->count(igroup) : (double) atom->natoms; }
@@ -375,6 +393,9 @@ void FixNVEMDP::post_run()
   if (heat_ctx && mdp_heat_off(heat_ctx) != MDP_OK) fail(heat_ctx); // (an unfix of the sources gives plain NVE next run)
   heat_ctx = nullptr;
   memset(&heat, 0, sizeof heat);
+  if (indent_ctx && mdp_indent_off(indent_ctx) != MDP_OK) fail(indent_ctx); // (an unfix of the indenters gives plain forces next run)
+  indent_ctx = nullptr;
+  memset(&indent, 0, sizeof indent);
   if (bricks) {
     long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (comm->nprocs > 1) (void) mdp_dd_comm_step_info(bctx, info);

@@ -31,6 +31,7 @@ FixStyle(nve/mdp,FixNVEMDP);
 
 #include "mdp_baths.h"
 #include "mdp_heat.h"
+#include "mdp_indent.h"
 #include "mdpair_hip.h"
 
 namespace LAMMPS_NS {
@@ -85,6 +86,12 @@ class FixNVEMDP : public Fix {
   // extract "mdp_heat_ctx"), off in post_run()
   MdpHeatSources heat;
   mdp_ctx *heat_ctx = nullptr;
+  // the indenters the `fix indent/mdp` fixes handed over (extract "mdp_indenters", mdp_indent.h): switched on in setup()
+  // behind the mask and the setup's forces (mdp_indent_setup, mdp_indent_run(beginstep)) on the context the steps run on
+  // (indent_ctx, extract "mdp_indent_ctx"), off in post_run()
+  MdpIndenters indent;
+  mdp_ctx *indent_ctx = nullptr;
+  bool indent_masked() const; // one of them acts on a group: the device needs atom->mask
   int brick_masked = 0; // this run's brick was set up with atom->mask (it comes back with the atoms)
   mdp_ctx *lgv_ctx = nullptr;
   // the context the steps of the run under way go through, thermostat or not, null between runs (extract "mdp_steps_ctx":
@@ -100,7 +107,7 @@ class FixNVEMDP : public Fix {
   int taken_delay() const;
   bool grouped() const { return igroup > 0; }                  // the fix acts on a group other than all
   bool lgv_masked() const { return baths.count > 1 || (baths.count == 1 && baths.bit[0]); }
-  bool masked() const { return grouped() || lgv_masked() || heat.count > 0; } // ... or a thermostat or a heat source does: the device needs atom->mask
+  bool masked() const { return grouped() || lgv_masked() || heat.count > 0 || indent_masked(); } // ... or a thermostat or a heat source does: the device needs atom->mask
   bool brick_mask() const;                                     // bricks: atom->mask travels with the atoms
   double group_count();                                        // atoms the fix integrates, over all ranks
   void apply_groups(mdp_ctx *c);                               // the group bits (and, host-linked, the mask) of this run on c
