@@ -254,8 +254,83 @@ struct CentreOut {
   double e_acc, v0, v1, v2, v3, v4, v5;
 };
 
+// The REBO pair parameters of one centre element, for either neighbour element ([0] Mo, [1] S).  The centre's element
+// is uniform over a launch, so the two candidates of every parameter are scalar loads at uniform indices and live in
+// scalar registers; the lane picks one by its neighbour's element.  Indexed by the lane's pair type instead, every
+// parameter was a vector load from the kernel-argument segment with a wait on vmcnt behind it -- and vmcnt counts the
+// slot stores as well.  What lj_select does for the tile kernel.
+struct PairPar {
+  double v_rc2[2], v_rmin[2], v_rinv[2], v_alpha[2], v_A[2], v_Q[2], v_B[2], v_beta[2];
+  __device__ __forceinline__ double rc2(const int tj) const { return tj ? v_rc2[1] : v_rc2[0]; }
+  __device__ __forceinline__ double rmin(const int tj) const { return tj ? v_rmin[1] : v_rmin[0]; }
+  __device__ __forceinline__ double rinv(const int tj) const { return tj ? v_rinv[1] : v_rinv[0]; }
+  __device__ __forceinline__ double alpha(const int tj) const { return tj ? v_alpha[1] : v_alpha[0]; }
+  __device__ __forceinline__ double A(const int tj) const { return tj ? v_A[1] : v_A[0]; }
+  __device__ __forceinline__ double Q(const int tj) const { return tj ? v_Q[1] : v_Q[0]; }
+  __device__ __forceinline__ double B(const int tj) const { return tj ? v_B[1] : v_B[0]; }
+  __device__ __forceinline__ double beta(const int tj) const { return tj ? v_beta[1] : v_beta[0]; }
+};
+
+__device__ __forceinline__ PairPar pair_par(const RebomosDev &P, const int tc)
+{
+  PairPar q;
+#pragma unroll
+  for (int t = 0; t < 2; t++) {
+    q.v_rc2[t] = P.rcmaxsq[tc * 2 + t];
+    q.v_rmin[t] = P.rcmin[tc * 2 + t];
+    q.v_rinv[t] = P.rcinv[tc * 2 + t];
+    q.v_alpha[t] = P.alpha[tc * 2 + t];
+    q.v_A[t] = P.A[tc * 2 + t];
+    q.v_Q[t] = P.Q[tc * 2 + t];
+    q.v_B[t] = P.B[tc * 2 + t];
+    q.v_beta[t] = P.beta[tc * 2 + t];
+  }
+  return q;
+}
+
+// The same from a point of the kernel on: the scalar loads index with a copy of tc that the compiler cannot see through,
+// so they are issued here and not at the head of the kernel, where their 32 registers would be held to the end.  A kernel
+// short of scalar registers fetches each stage's parameters a stretch of arithmetic ahead of their use.
+__device__ __forceinline__ PairPar pair_par_here(const RebomosDev &P, int tc)
+{
+  asm volatile("; pair parameters from here" : "+s"(tc));
+  return pair_par(P, tc);
+}
+
+// The general kernel's centres are of either element, lane group by lane group, and its registers are spoken for: a
+// table of all four pair types in LDS, filled once per block from scalar loads, read at the lane's pair type.  LDS
+// reads count on lgkmcnt, so no slot store is waited for either.
+constexpr int kPairTab = 8 * 4;
+struct PairTab {
+  const double *row; // table + 2 * (centre element)
+  __device__ __forceinline__ double rc2(const int tj) const { return row[0 * 4 + tj]; }
+  __device__ __forceinline__ double rmin(const int tj) const { return row[1 * 4 + tj]; }
+  __device__ __forceinline__ double rinv(const int tj) const { return row[2 * 4 + tj]; }
+  __device__ __forceinline__ double alpha(const int tj) const { return row[3 * 4 + tj]; }
+  __device__ __forceinline__ double A(const int tj) const { return row[4 * 4 + tj]; }
+  __device__ __forceinline__ double Q(const int tj) const { return row[5 * 4 + tj]; }
+  __device__ __forceinline__ double B(const int tj) const { return row[6 * 4 + tj]; }
+  __device__ __forceinline__ double beta(const int tj) const { return row[7 * 4 + tj]; }
+};
+
+__device__ __forceinline__ void pair_tab_fill(const RebomosDev &P, double *tab /* [kPairTab], by one thread */)
+{
+#pragma unroll
+  for (int pt = 0; pt < 4; pt++) {
+    tab[0 * 4 + pt] = P.rcmaxsq[pt];
+    tab[1 * 4 + pt] = P.rcmin[pt];
+    tab[2 * 4 + pt] = P.rcinv[pt];
+    tab[3 * 4 + pt] = P.alpha[pt];
+    tab[4 * 4 + pt] = P.A[pt];
+    tab[5 * 4 + pt] = P.Q[pt];
+    tab[6 * 4 + pt] = P.B[pt];
+    tab[7 * 4 + pt] = P.beta[pt];
+  }
+}
+
 // shared epilogue of a slot: radial terms (pair_rebomos.cpp:411-441, 683-725), store, tallies
-__device__ __forceinline__ void finish_slot(const RebomosDev &P, const int tc, const int je_m, const int off,
+template <class PP>
+__device__ __forceinline__ void finish_slot(const PP &pp, const int je_m, const int off,
                                             const double dp, const bool owned, const int eflag, const double mx,
                                             const double my, const double mz, const double mr, const double mw,
                                             const double mdw, const double mp, const double mrinv, const double mVA,
@@ -263,18 +338,19 @@ __device__ __forceinline__ void finish_slot(const RebomosDev &P, const int tc, c
                                             double *__restrict__ fnbr, double &eh, CentreOut &o)
 {
   const int tm = ((unsigned) je_m) >> 30;
-  const int pt = tc * 2 + tm;
+  const double alpha = pp.alpha(tm), A = pp.A(tm), Q = pp.Q(tm);
+  const double beta = pp.beta(tm);
   const double ux = mx * mrinv, uy = my * mrinv, uz = mz * mrinv;
   double radial = (acc1 + Csum * dp) * mdw; // dw_cm [ sum_q C_q G + P'(N) sum_j C_j ]
   double ehalf = 0.0;
   if (mw > kTol) {
-    const double ex = exp(-P.alpha[pt] * mr);
-    const double pre = mw * P.A[pt] * ex;
-    const double VR = pre * (1.0 + P.Q[pt] * mrinv);
-    double dVR = pre * (-P.alpha[pt] - P.Q[pt] * mrinv * mrinv - P.Q[pt] * P.alpha[pt] * mrinv);
+    const double ex = exp(-alpha * mr);
+    const double pre = mw * A * ex;
+    const double VR = pre * (1.0 + Q * mrinv);
+    double dVR = pre * (-alpha - Q * mrinv * mrinv - Q * alpha * mrinv);
     const double swl = fast_rcp(mw) * mdw; // (dw/dr)/w
     dVR += VR * swl;
-    double dVA = -P.beta[pt] * mVA;
+    double dVA = -beta * mVA;
     dVA += mVA * swl;
     radial += 0.5 * (dVR + mp * dVA);
     ehalf = 0.5 * (VR + mp * mVA);
@@ -332,8 +408,8 @@ __device__ __forceinline__ void centre_tally(const CentreOut &o, double *__restr
 // (rev_kernel: image centres are not computed at all), and decides with its own distance test, whose operands are
 // rounded differently: fl(x_a - fl(x_o + s)) against fl(x_o - fl(x_a - s)).  When the two tests disagree the pair
 // sits at rcmax to the last bits, where the switching function -- and with it every term of the record -- is zero.
-template <int G, int CAP, int REC>
-__device__ __forceinline__ void centre_take(const RebomosDev &P, const int tc, const double4 xc, const bool valid,
+template <int G, int CAP, int REC, class PP>
+__device__ __forceinline__ void centre_take(const PP &pp, const double4 xc, const bool valid,
                                             const int t, const double4 xj, const int s, const int glane0,
                                             const int base, double *rec, int *je, int &n,
                                             unsigned long long &active, double &nsum, double4 *__restrict__ slot4,
@@ -343,7 +419,7 @@ __device__ __forceinline__ void centre_take(const RebomosDev &P, const int tc, c
   const double dx = xc.x - xj.x, dy = xc.y - xj.y, dz = xc.z - xj.z;
   const double rsq = dx * dx + dy * dy + dz * dz;
   const int tj = (int) xj.w;
-  const double rc2 = P.rcmaxsq[tc * 2 + tj];
+  const double rc2 = pp.rc2(tj);
   const bool pred = valid && rsq < rc2;
   if (valid && !pred && rsq < rc2 * (1.0 + 1.0e-14)) { // (practically never taken)
     slot4[t] = make_double4(0.0, 0.0, 0.0, 0.0);
@@ -354,11 +430,10 @@ __device__ __forceinline__ void centre_take(const RebomosDev &P, const int tc, c
   const unsigned long long gb = (bal >> glane0) & gmask;
   const int pos = n + __popcll(gb & ((1ull << s) - 1ull));
   if (pred && pos < CAP) {
-    const int pt = tc * 2 + tj;
     const double rinv = rsqrt_nr(rsq); // r and 1/r from one reciprocal square root
     const double r = rsq * rinv;
     double dw;
-    const double w = sp_switch(r, P.rcmin[pt], P.rcinv[pt], dw);
+    const double w = sp_switch(r, pp.rmin(tj), pp.rinv(tj), dw);
     double *q = rec + pos * REC;
     q[0] = dx;
     q[1] = dy;
@@ -482,8 +557,8 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
     for (int u = 0; u < C::UA; u++) xj[u] = xq[jp[u] >= 0 ? jp[u] : c];
 #pragma unroll
     for (int u = 0; u < C::UA; u++)
-      centre_take<G, C::CAP, kRecF>(P, tc, xc, jp[u] >= 0, u * G + s, xj[u], s, glane0, u * G, rec, je, n, active, nsum,
-                                    reinterpret_cast<double4 *>(fnbr) + off, nullptr);
+      centre_take<G, C::CAP, kRecF>(pair_par(P, tc), xc, jp[u] >= 0, u * G + s, xj[u], s, glane0, u * G, rec, je, n,
+                                    active, nsum, reinterpret_cast<double4 *>(fnbr) + off, nullptr);
   }
   const int ncw = wave_max_int(nc);
   for (int base = W; base < ncw; base += W) { // rows longer than the packed part (rare)
@@ -499,8 +574,8 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
 #pragma unroll
     for (int u = 0; u < C::UA; u++) {
       const int t = base + u * G + s;
-      centre_take<G, C::CAP, kRecF>(P, tc, xc, t < nc, t, xj[u], s, glane0, base + u * G, rec, je, n, active, nsum,
-                                    reinterpret_cast<double4 *>(fnbr) + off, nullptr);
+      centre_take<G, C::CAP, kRecF>(pair_par(P, tc), xc, t < nc, t, xj[u], s, glane0, base + u * G, rec, je, n, active,
+                                    nsum, reinterpret_cast<double4 *>(fnbr) + off, nullptr);
     }
   }
   if (have && s == 0) amask[c] = active;
@@ -631,9 +706,12 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
   // -- phase B: p_cm, C_m (pair_rebomos.cpp:607-630)
   double mC = 0.0, mp = 0.0, mVA = 0.0;
   if (act) {
-    const int pt = tc * 2 + (((unsigned) je[m]) >> 30);
+    // (the pair parameters are fetched where they are used, here and in finish_slot: scalar loads, not kept through the
+    //  pair loops, which need every SGPR)
+    const PairPar pp = pair_par(P, tc);
+    const int tm = ((unsigned) je[m]) >> 30;
     mp = rsqrt_nr(1.0 + S + PS);
-    mVA = -mw * P.B[pt] * exp(-P.beta[pt] * mr);
+    mVA = -mw * pp.B(tm) * exp(-pp.beta(tm) * mr);
     mC = (mw > kTol) ? 0.5 * mVA * (-0.5 * mp * mp * mp) : 0.0;
     rec[m * kRecF + 6] = mC;
   }
@@ -721,8 +799,8 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
   }
   double eh = 0.0;
   if (act)
-    finish_slot(P, tc, je[m], off, dp, c_own >= 0, eflag, mx, my, mz, mr, mw, mdw, mp, mri, mVA, fx, fy, fz, acc1, Csum,
-                fnbr, eh, o);
+    finish_slot(pair_par(P, tc), je[m], off, dp, c_own >= 0, eflag, mx, my, mz, mr, mw, mdw, mp, mri, mVA, fx, fy, fz,
+                acc1, Csum, fnbr, eh, o);
   // the centre's own share: minus the sum of its slot forces, plus the centre halves of the pair energies.
   // Written once here so that the gather only has to follow the reverse slots.
   const double ox = group_sum_any<G>(act ? fx : 0.0, s, lane), oy = group_sum_any<G>(act ? fy : 0.0, s, lane), oz = group_sum_any<G>(act ? fz : 0.0, s, lane);
@@ -775,7 +853,9 @@ __global__ __launch_bounds__(kC3Block) void rebo_centre3_kernel(
     xc = xq[c];
   }
   double4 *__restrict__ slot4 = reinterpret_cast<double4 *>(fnbr) + off;
-  const double rc2_0 = P.rcmaxsq[tc * 2], rc2_1 = P.rcmaxsq[tc * 2 + 1];
+  // (the pair parameters in four stages -- rcmax^2 here; the switching interval, V_A's and V_R's each in front of the work
+  //  that comes before their use: the scalar registers do not hold all of them next to the polynomial coefficients)
+  const PairPar pp = pair_par(P, tc);
 
   // ---- phase A: which candidates are inside rcmax now (pair_rebomos.cpp:328-344); the first three are kept
   int n = 0, nj0 = 0, nj1 = 0, nj2 = 0, ts0 = 0, ts1 = 0, ts2 = 0;
@@ -783,7 +863,7 @@ __global__ __launch_bounds__(kC3Block) void rebo_centre3_kernel(
   auto take = [&](const int t, const int j, const bool valid, const double4 xj) {
     const double dx = xc.x - xj.x, dy = xc.y - xj.y, dz = xc.z - xj.z;
     const double rsq = dx * dx + dy * dy + dz * dz;
-    const double rc2 = ((int) xj.w) ? rc2_1 : rc2_0;
+    const double rc2 = pp.rc2((int) xj.w);
     const bool pred = valid && rsq < rc2;
     if (valid && !pred && rsq < rc2 * (1.0 + 1.0e-14)) slot4[t] = make_double4(0.0, 0.0, 0.0, 0.0); // (see centre_take)
     const bool s0 = pred && n == 0, s1 = pred && n == 1, s2 = pred && n == 2;
@@ -824,6 +904,7 @@ __global__ __launch_bounds__(kC3Block) void rebo_centre3_kernel(
   int tj[3];
   bool act[3];
   double Ntot = 0.0;
+  const PairPar pp_sw = pair_par_here(P, tc);
 #pragma unroll
   for (int k = 0; k < 3; k++) {
     act[k] = k < n;
@@ -831,11 +912,10 @@ __global__ __launch_bounds__(kC3Block) void rebo_centre3_kernel(
     tj[k] = act[k] ? (int) xj.w : 0;
     const double ex = xc.x - xj.x, ey = xc.y - xj.y, ez = xc.z - xj.z;
     const double rsq = act[k] ? ex * ex + ey * ey + ez * ez : 1.0;
-    const int pt = tc * 2 + tj[k];
     ri[k] = rsqrt_nr(rsq); // r and 1/r from one reciprocal square root
     r[k] = rsq * ri[k];
     double dwk = 0.0;
-    const double wk = sp_switch(r[k], P.rcmin[pt], P.rcinv[pt], dwk);
+    const double wk = sp_switch(r[k], pp_sw.rmin(tj[k]), pp_sw.rinv(tj[k]), dwk);
     w[k] = act[k] ? wk : 0.0;
     dw[k] = act[k] ? dwk : 0.0;
     dx[k] = act[k] ? ex : 0.0;
@@ -859,6 +939,7 @@ __global__ __launch_bounds__(kC3Block) void rebo_centre3_kernel(
 
   // ---- the three unordered pairs (0,1) (0,2) (1,2): cos, G, G' once each (pair_rebomos.cpp:607-630)
   double cs[3], g[3], dg[3], S[3] = {0.0, 0.0, 0.0};
+  const PairPar pp_va = pair_par_here(P, tc);
 #pragma unroll
   for (int e = 0; e < 3; e++) {
     const int m = e == 2 ? 1 : 0, q = e == 0 ? 1 : 2;
@@ -878,14 +959,14 @@ __global__ __launch_bounds__(kC3Block) void rebo_centre3_kernel(
   double p[3], VA[3], C[3], Csum = 0.0;
 #pragma unroll
   for (int k = 0; k < 3; k++) {
-    const int pt = tc * 2 + tj[k];
     p[k] = rsqrt_nr(1.0 + S[k] + PS);
-    VA[k] = -w[k] * P.B[pt] * exp(-P.beta[pt] * r[k]);
+    VA[k] = -w[k] * pp_va.B(tj[k]) * exp(-pp_va.beta(tj[k]) * r[k]);
     C[k] = (act[k] && w[k] > kTol) ? 0.5 * VA[k] * (-0.5 * p[k] * p[k] * p[k]) : 0.0;
     Csum += C[k];
   }
   // ---- forces on the slots (pair_rebomos.cpp:634-725)
   double fx[3] = {0, 0, 0}, fy[3] = {0, 0, 0}, fz[3] = {0, 0, 0}, a1[3] = {0, 0, 0};
+  const PairPar pp_vr = pair_par_here(P, tc);
 #pragma unroll
   for (int e = 0; e < 3; e++) {
     const int m = e == 2 ? 1 : 0, q = e == 0 ? 1 : 2;
@@ -909,7 +990,7 @@ __global__ __launch_bounds__(kC3Block) void rebo_centre3_kernel(
   for (int k = 0; k < 3; k++) {
     if (!act[k]) continue;
     double eh = 0.0;
-    finish_slot(P, tc, ts[k] | (tj[k] << 30), off, dp, owned, eflag, dx[k], dy[k], dz[k], r[k], w[k], dw[k], p[k], ri[k],
+    finish_slot(pp_vr, ts[k] | (tj[k] << 30), off, dp, owned, eflag, dx[k], dy[k], dz[k], r[k], w[k], dw[k], p[k], ri[k],
                 VA[k], fx[k], fy[k], fz[k], a1[k], Csum, fnbr, eh, o);
     ox += fx[k];
     oy += fy[k];
@@ -943,6 +1024,9 @@ __global__ __launch_bounds__(256) void rebo_centre_general_kernel(
   if (h_gen && list_count < 0 && blockIdx.x == 0 && threadIdx.x == 4) *h_gen = list[0];
   __shared__ double s_rec[8 * STRIDE];
   __shared__ int s_je[8 * CAP];
+  __shared__ double s_par[kPairTab];
+  if (threadIdx.x == 0) pair_tab_fill(P, s_par);
+  __syncthreads();
   // list_count < 0: overflow list of the fast kernels, {count, ids...}; else an explicit list of centres
   const int ncent = list_count < 0 ? list[0] : list_count;
   const int *ovf = list_count < 0 ? list : list - 1;
@@ -967,6 +1051,7 @@ __global__ __launch_bounds__(256) void rebo_centre_general_kernel(
       xc = xq[c];
       tc = (int) xc.w;
     }
+    const PairTab pp = {s_par + 2 * tc};
     int n = 0;
     double nsum = 0.0;
     unsigned long long active = 0ull;
@@ -975,7 +1060,7 @@ __global__ __launch_bounds__(256) void rebo_centre_general_kernel(
       const int t = base + s;
       const int j = t < nc ? cand[off + t] : c;
       const double4 xj = xq[j];
-      centre_take<G, CAP, kRec>(P, tc, xc, t < nc, t, xj, s, glane0, base, rec, je, n, active, nsum,
+      centre_take<G, CAP, kRec>(pp, xc, t < nc, t, xj, s, glane0, base, rec, je, n, active, nsum,
                                 reinterpret_cast<double4 *>(fnbr) + off, VATOM ? vslot + 6 * (size_t) off : nullptr);
     }
     if (n > CAP) {
@@ -1022,9 +1107,9 @@ __global__ __launch_bounds__(256) void rebo_centre_general_kernel(
         }
       }
       if (act) {
-        const int pt = tc * 2 + (((unsigned) je[m]) >> 30);
+        const int tm = ((unsigned) je[m]) >> 30;
         const double p = 1.0 / sqrt(1.0 + S + PS);
-        const double VA = -mw * P.B[pt] * exp(-P.beta[pt] * mr);
+        const double VA = -mw * pp.B(tm) * exp(-pp.beta(tm) * mr);
         const double Cm = (mw > kTol) ? 0.5 * VA * (-0.5 * p * p * p) : 0.0;
         double *q = rec + m * kRec;
         q[6] = Cm;
@@ -1101,8 +1186,8 @@ __global__ __launch_bounds__(256) void rebo_centre_general_kernel(
       }
       if (act) {
         double eh = 0.0;
-        finish_slot(P, tc, je[m], off, dp, owned, eflag, mx, my, mz, mr, mw, mdw, mp, mri, mVA, fx, fy, fz, acc1,
-                    Csum, fnbr, eh, o);
+        finish_slot(pp, je[m], off, dp, owned, eflag, mx, my, mz, mr, mw, mdw, mp, mri, mVA, fx, fy, fz, acc1, Csum,
+                    fnbr, eh, o);
         ox += fx;
         oy += fy;
         oz += fz;
@@ -1110,15 +1195,17 @@ __global__ __launch_bounds__(256) void rebo_centre_general_kernel(
         if (VATOM) {
           // v_tally2(i,j,tmp2,rij) with tmp2 = -C_m P' dw_m / r_m and ev_tally's pair part with this
           // centre's half of fpair: both give half to either end
-          const int pt = tc * 2 + (((unsigned) je[m]) >> 30);
+          const int tm = ((unsigned) je[m]) >> 30;
+          const double alpha = pp.alpha(tm), A = pp.A(tm), Q = pp.Q(tm);
+          const double beta = pp.beta(tm);
           double fh = -mC * dp * mdw * mri;
           if (mw > kTol) {
-            const double ex = exp(-P.alpha[pt] * mr);
-            const double pre = mw * P.A[pt] * ex;
-            const double VR = pre * (1.0 + P.Q[pt] * mri);
-            double dVR = pre * (-P.alpha[pt] - P.Q[pt] * mri * mri - P.Q[pt] * P.alpha[pt] * mri);
+            const double ex = exp(-alpha * mr);
+            const double pre = mw * A * ex;
+            const double VR = pre * (1.0 + Q * mri);
+            double dVR = pre * (-alpha - Q * mri * mri - Q * alpha * mri);
             dVR += VR / mw * mdw;
-            double dVA = -P.beta[pt] * mVA;
+            double dVA = -beta * mVA;
             dVA += mVA / mw * mdw;
             fh += -0.5 * (dVR + mp * dVA) * mri;
           }
