@@ -639,6 +639,50 @@ int mdp_indent_run(mdp_ctx *ctx, long long first);
 int mdp_indent_state(mdp_ctx *ctx, int k, double *out /* MDP_INDENT_STATE_LEN */);
 int mdp_indent_off(mdp_ctx *ctx);
 
+/* ---- Tether springs on a group's centre of mass (LAMMPS fix spring tether, with the constant-velocity tether point of
+ * fix smd; the plugin style `fix spring/mdp`) -----
+ * Up to MDP_SPRING_MAX springs, spring k on the owned atoms whose mask has groupbit[k]; a bit of 0 means every owned atom
+ * and needs no mask.  Springs may share atoms: their forces add.  For the forces of step n the tether point is
+ *     p = c + vel (n - first) dt                                                     (dt is the context's own)
+ * and a dimension d with use[d] == 0 (LAMMPS' NULL) takes no part: its component of d below is 0, its vel is ignored.
+ * With xu_i = x_i + h . image_i over the atoms of the group (the image flags of mdp_md_set_image, the box of mdp_dd_setup):
+ *     M = sum m_i,  xcm = (sum m_i xu_i) / M,  d = xcm - p,  r = max(|d|, 1e-10),  dr = r - R0
+ *     F = K d dr / r,  E = K dr^2 / 2,  f_i -= (F / M) m_i,  ftotal = (-Fx, -Fy, -Fz, sign(dr) |F|)
+ * The pass is three launches: per block and spring the sums in fixed slots; one workgroup that adds the slots in a fixed
+ * order, forms the above and leaves the state and F / M in device memory; one lane per owned atom that takes its share off
+ * f, spring after spring.  No float atomics and no host wait: a run is bitwise reproducible, and the same whether or not
+ * the host defers final halves.  M is summed in two parts that add exactly (up to 2^22 atoms with masses in [1, 2048)):
+ * the state's M is the correctly rounded sum of the masses, whatever order the device holds the atoms in.
+ * Every kick of v by f begins with the pass unless the forces the context holds have had theirs already -- behind the
+ * indenters' pass when both are on; that order is fixed and only affects the rounding of f.  The flag is cleared behind
+ * every initial half and by _setup / _run, under the rules of mdp_indent_* (above), call for call.
+ *   setup:  replaces the springs that are on.  A final half pending at the call completes first, without springs.
+ *           Refused (MDP_EINVAL / MDP_ESTATE, each with its cause, before anything on the context changes): n outside
+ *           1 .. MDP_SPRING_MAX, K or R0 negative or not finite, a tether point or velocity that is not finite, use all
+ *           zero, a group bit with no mask for the current atoms, no image flags (mdp_md_set_image), a host-linked
+ *           context (its host keeps the image flags), a brick of several ranks, the minimiser, the Nose-Hoover chain or
+ *           heat sources on the context -- those calls in turn refuse while springs are on -- and a spring whose group
+ *           holds no atom or no mass.  Langevin thermostats and indenters are welcome.
+ *   run:    a final half pending at the call completes first, with the pass of its step if that is still due; then the
+ *           tether point starts again at c: the forces the context holds count as those of step `first`, without a pass.
+ *   state:  blocking; completes a deferred final half, and runs the pass if the current forces have not had it.
+ *           out[0] E, [1..4) ftotal x, y, z, [4] sign(dr) |F|, [5] the step these belong to, [6..9) xcm (unwrapped),
+ *           [9..12) the tether point (0 in a dimension that takes no part), [12] M, [13] atoms, [14] passes since setup,
+ *           [15] 0.
+ *   off:    a pending final half completes first, with its pass; frees what was held. */
+#define MDP_SPRING_MAX 4
+#define MDP_SPRING_STATE_LEN 16
+typedef struct {
+  double k, r0;  /* force / length, length */
+  double c[3];   /* the tether point at step `first` */
+  int use[3];    /* 0: the dimension takes no part (LAMMPS' NULL) */
+  double vel[3]; /* length / time */
+} mdp_spring_config;
+int mdp_spring_setup(mdp_ctx *ctx, int n, const mdp_spring_config *cfg, const int *groupbit);
+int mdp_spring_run(mdp_ctx *ctx, long long first);
+int mdp_spring_state(mdp_ctx *ctx, int k, double *out /* MDP_SPRING_STATE_LEN */);
+int mdp_spring_off(mdp_ctx *ctx);
+
 /* ---- FIRE minimiser on the device (LAMMPS min_style fire, FIRE 2.0 with the eulerimplicit integrator and LAMMPS' defaults)
  * For a resident context on one rank, after mdp_md_setup + mdp_dd_setup (one brick) + mdp_dd_reneighbor.  An iteration
  * is two small launches next to the force compute: per-block partial sums of v.f, v.v, f.f and the largest |v_c| in

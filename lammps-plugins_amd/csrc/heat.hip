@@ -315,6 +315,7 @@ int mdp_heat_setup(mdp_ctx *c, int nsrc, const mdp_heat_config *cfg, const int *
   if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
   if (c->nhc.on) return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: the Nose-Hoover chain (mdp_nhc_setup) is on; heat sources run without a thermostat");
   if (c->indent.on) return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: indenters (mdp_indent_setup) are on; mdp_indent_off first");
+  if (c->spring.on) return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: springs (mdp_spring_setup) are on; mdp_spring_off first");
   if (c->lgv.on)
     return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: the Langevin thermostat (mdp_langevin_setup) is on; heat sources run without a thermostat");
   if (c->dd.on && c->dd.G.nranks > 1)

@@ -703,6 +703,7 @@ int lgv_final(mdp_ctx *c, bool writeback)
 int md_final_half(mdp_ctx *c, bool lgv_writeback = true)
 {
   if (c->indent.on && !c->indent.applied) MDP_TRY(mdp_indent_pass(c)); // (indenters: post_force of the step this half completes)
+  if (c->spring.on && !c->spring.applied) MDP_TRY(mdp_spring_pass(c)); // (springs: the same, behind the indenters)
   if (c->nhc.on) return mdp_nhc_final(c);
   if (c->lgv.on) return lgv_final(c, lgv_writeback);
   bool masked = false;
@@ -724,6 +725,7 @@ int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, dou
                       bool zero_f, double *dset, double *dclr)
 {
   if (c->indent.on && !c->indent.applied) MDP_TRY(mdp_indent_pass(c)); // (indenters: post_force of the forces this kernel kicks with first)
+  if (c->spring.on && !c->spring.applied) MDP_TRY(mdp_spring_pass(c)); // (springs: the same, behind the indenters)
   // a final half pending across a thermostat set-up (mdp_nhc_setup / _run, mdp_langevin_run by a host that does not
   // defer it) goes first, on its own, and leaves f as it was: the setup of the new run sees the compute's forces alone,
   // as after Verlet::setup
@@ -739,6 +741,7 @@ int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, dou
     mdp_heat_count_step(c);
   }
   mdp_indent_count_step(c); // (the initial half below moves the atoms: a compute follows and overwrites f)
+  mdp_spring_count_step(c);
   const double *vscale = nullptr;
   bool lgv = false, masked = false;
   const bool baths = c->lgv.many();

@@ -916,6 +916,10 @@ int mdp_destroy(mdp_ctx *c)
   c->heat.count.release();
   c->indent.st.release();
   c->indent.part.release();
+  c->spring.st.release();
+  c->spring.part.release();
+  c->spring.cpart.release();
+  c->spring.count.release();
   c->fire.st.release();
   c->fire.part.release();
   c->fire.fsave.release();

@@ -369,6 +369,27 @@ struct MdpIndent {
   DevBuf<double> part;      // per-block partial sums, kIndW per block (fixed slots [block][indenter][5])
 };
 static constexpr int kIndW = 5 * MDP_INDENT_MAX; // per indenter: energy, the atoms' fx, fy, fz, atoms in contact
+// Tether springs (spring.hip): LAMMPS fix spring tether with a tether point at constant velocity, taken off f by one pass in
+// front of the kick that first consumes a compute's forces, behind the indenters' pass.  The host keeps the configuration,
+// the number of initial halves since mdp_spring_run and whether the current forces have had their pass; the sums live on
+// the device.  st: spring k keeps its MDP_SPRING_STATE_LEN state words (mdp_spring_state layout) at st + k *
+// MDP_SPRING_STATE_LEN; behind the springs, F / M of the pass in flight (kSprF + 4 k: x, y, z and a spare word)
+struct MdpSpring {
+  bool on = false;
+  bool applied = false;     // the forces the context holds have had their pass.  Cleared behind every initial half
+                            // (mdp_spring_count_step) and by mdp_spring_setup / _run (spring_restart), nowhere else
+  int n = 0;
+  mdp_spring_config cfg[MDP_SPRING_MAX];
+  int bit[MDP_SPRING_MAX] = {0, 0, 0, 0};
+  long long first = 0;      // the step of mdp_spring_run
+  long long nhalf = 0;      // initial halves since: the current forces are those of step first + nhalf
+  DevBuf<double> st;        // [kSprTotal]
+  DevBuf<double> part;      // per-block partial sums, kSprW per block (fixed slots [block][spring][5])
+  DevBuf<int> cpart;        // per-block atom counts, MDP_SPRING_MAX per block
+  DevBuf<int> count;        // [2 MDP_SPRING_MAX] the counts of a set-up: atoms per spring, those with a mass
+};
+static constexpr int kSprW = 5 * MDP_SPRING_MAX; // per spring: sum m xu, m yu, m zu, m_hi, m_lo (m = m_hi + m_lo, spring.hip)
+static constexpr int kSprF = MDP_SPRING_MAX * MDP_SPRING_STATE_LEN, kSprTotal = kSprF + 4 * MDP_SPRING_MAX;
 // FIRE minimiser (fire.hip): the control block lives in st on the device; the host keeps the configuration and what it
 // has queued.  Control block, in doubles (flags and counters as whole numbers):
 enum MdpFireWord {
@@ -868,6 +889,7 @@ struct mdp_ctx {
   MdpFire fire;                    // FIRE minimiser: mdp_md_advance launches its advance kernel while it is on (mdp_fire_setup)
   MdpHeat heat;                    // constant-flux heat sources behind every final half (mdp_heat_setup)
   MdpIndent indent;                // indenters in front of the kicks (mdp_indent_setup)
+  MdpSpring spring;                // tether springs in front of the kicks, behind the indenters (mdp_spring_setup)
   // groups (mdp_md_set_mask / mdp_hnve_set_mask, mdp_integrate_group, mdp_langevin_group)
   DevBuf<int> mask;                // [nlocal] atom->mask: device order (resident; permuted and migrated with the atoms) or the host's order
   bool mask_set = false;
@@ -1142,6 +1164,15 @@ inline void mdp_indent_count_step(mdp_ctx *c)
   if (!c->indent.on) return;
   c->indent.nhalf++;
   c->indent.applied = false;
+}
+// tether springs (spring.hip) when c->spring.on, under the rules of the indenters: _pass at the same two sites, behind
+// the indenters' pass when both are on (the order only affects the rounding of f); _count_step behind an initial half
+int mdp_spring_pass(mdp_ctx *c);
+inline void mdp_spring_count_step(mdp_ctx *c)
+{
+  if (!c->spring.on) return;
+  c->spring.nhalf++;
+  c->spring.applied = false;
 }
 void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
 void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds

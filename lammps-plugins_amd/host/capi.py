@@ -71,6 +71,10 @@ class IndentConfig(C.Structure):
 INDENT_MAX, INDENT_STATE_LEN = 4, 10   # MDP_INDENT_MAX, MDP_INDENT_STATE_LEN of include/mdpair_hip.h
 INDENT_SHAPES = {"sphere": 0, "cylinder": 1, "plane": 2}
 INDENT_SIDES = {"out": 0, "in": 1, "lo": 0, "hi": 1}
+class SpringConfig(C.Structure):
+    """mirror of mdp_spring_config"""
+    _fields_ = [("k", C.c_double), ("r0", C.c_double), ("c", C.c_double * 3), ("use", C.c_int * 3), ("vel", C.c_double * 3)]
+SPRING_MAX, SPRING_STATE_LEN = 4, 16   # MDP_SPRING_MAX, MDP_SPRING_STATE_LEN of include/mdpair_hip.h
 class FireConfig(C.Structure):
     _fields_ = [("etol", C.c_double), ("ftol", C.c_double), ("maxiter", C.c_longlong), ("maxeval", C.c_longlong),
                 ("dmax", C.c_double), ("tmax", C.c_double), ("tmin", C.c_double), ("delaystep", C.c_int),
@@ -121,6 +125,7 @@ EXPORTS = [
     "mdp_heatflux_sums", "mdp_md_download_vatom",
     "mdp_heat_setup", "mdp_heat_run", "mdp_heat_state", "mdp_heat_off",
     "mdp_indent_setup", "mdp_indent_run", "mdp_indent_state", "mdp_indent_off",
+    "mdp_spring_setup", "mdp_spring_run", "mdp_spring_state", "mdp_spring_off",
 ]
 
 
@@ -659,6 +664,37 @@ class Context:
 
     def indent_off(self):
         self._ck(self.L.mdp_indent_off(self.h))
+
+    # ---------------- tether springs in front of the kicks (fix spring/mdp)
+    def spring_setup(self, springs):
+        """mdp_spring_setup: springs is a list of dicts k, r0 (default 0), c (the tether point at the run's first step:
+        three entries, None for a dimension that takes no part, LAMMPS' NULL), and optionally vel (three numbers), bit (the
+        group bit; 0: every owned atom)"""
+        n = len(springs)
+        cfgs = (SpringConfig * max(n, 1))()
+        bits = (C.c_int * max(n, 1))()
+        for k, q in enumerate(springs):
+            cfgs[k].k, cfgs[k].r0 = float(q["k"]), float(q.get("r0", 0.0))
+            cfgs[k].c[:] = [0.0 if a is None else float(a) for a in q["c"]]
+            cfgs[k].use[:] = [0 if a is None else 1 for a in q["c"]]
+            cfgs[k].vel[:] = [float(a) for a in q.get("vel", (0.0, 0.0, 0.0))]
+            bits[k] = int(q.get("bit", 0))
+        self._ck(self.L.mdp_spring_setup(self.h, C.c_int(n), cfgs, bits))
+
+    def spring_run(self, first):
+        self._ck(self.L.mdp_spring_run(self.h, C.c_longlong(first)))
+
+    def spring_state(self, k):
+        """spring k for the forces the context holds (blocking; runs their pass if no kick has yet): its energy, ftotal
+        (the force on the group, then sign(dr) |F|), the step these belong to, the unwrapped centre of mass, the tether
+        point at that step, the group's mass and atoms, passes since setup"""
+        out = np.zeros(SPRING_STATE_LEN)
+        self._ck(self.L.mdp_spring_state(self.h, C.c_int(int(k)), _dp(out)))
+        return dict(energy=float(out[0]), ftotal=out[1:5].copy(), step=int(out[5]), xcm=out[6:9].copy(), tether=out[9:12].copy(),
+                    mass=float(out[12]), atoms=int(out[13]), passes=int(out[14]))
+
+    def spring_off(self):
+        self._ck(self.L.mdp_spring_off(self.h))
 
     # ---------------- FIRE minimiser of a resident one-brick context (minimize/mdp)
     def fire_setup(self, etol, ftol, maxiter, maxeval, **modify):

@@ -750,6 +750,34 @@ class DeviceDomain:
         self.ctx.indent_off()
         self._final_pending = False
 
+    def spring(self, springs, first=0):
+        """Tether springs (LAMMPS fix spring tether) on the centres of mass of groups of this domain: a list of up to four
+        dicts as capi.Context.spring_setup takes them -- k, r0, c (None for a dimension that takes no part), and optionally
+        vel, bit (the group bit in the mask of set_group; 0: every atom).  The tether point is c at step `first` and moves by
+        vel dt per step.  The centre of mass is that of the unwrapped positions: the domain needs its image flags
+        (track_images).  Call it behind compute(), as indent().  One GPU; no Nose-Hoover chain, heat sources or minimiser next
+        to them; indenters and Langevin baths are welcome."""
+        if self.world > 1:
+            raise ValueError("springs run on one GPU only (their sums would need an all-reduce per step)")
+        self.ctx.spring_setup(springs)
+        self.spring_run(first)
+
+    def spring_run(self, first):
+        """A further run of the springs set by spring(), from step `first`: the tether points start again at c.  A pending
+        final half completes first, with its spring forces; compute() again before the next step."""
+        self.ctx.spring_run(first)
+        self._final_pending = False
+
+    def spring_state(self, k):
+        """spring k for the current forces (completes a deferred final half first): capi.Context.spring_state"""
+        self.flush()
+        return self.ctx.spring_state(k)
+
+    def spring_off(self):
+        """back to the pair style's forces alone; a deferred final half completes inside mdp_spring_off, with its pass"""
+        self.ctx.spring_off()
+        self._final_pending = False
+
     def minimize(self, etol, ftol, maxiter, maxeval, chunk=64, **modify):
         """FIRE minimisation (LAMMPS min_style fire with its defaults; **modify: capi.FIRE_DEFAULTS) of this domain on the
         device, one GPU only; returns the final state (capi.Context.fire_state).  The velocities are zero afterwards

@@ -126,6 +126,8 @@ void MinimizeMDP::command(int narg, char **arg)
   for (int i = 0; i < modify->nfix; i++) // (LAMMPS' minimiser would add the indenters' forces; this one sees the pair style's alone)
     if (strcmp(modify->fix[i]->style, "indent/mdp") == 0)
       error->all(FLERR, std::string("minimize/mdp: fix ") + modify->fix[i]->id + " (indent/mdp) is not applied by the minimiser; unfix it first");
+    else if (strcmp(modify->fix[i]->style, "spring/mdp") == 0)
+      error->all(FLERR, std::string("minimize/mdp: fix ") + modify->fix[i]->id + " (spring/mdp) is not applied by the minimiser; unfix it first");
   const int style_id = mdp_pair_style_id(force->pair);
   if (!style_id) error->all(FLERR, "minimize/mdp requires a pair style of this plugin (rebomos or aeam)");
   if (const char *e = getenv("MDP_REBOMOS_HOST_LIST"))

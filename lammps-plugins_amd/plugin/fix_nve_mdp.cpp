@@ -93,6 +93,7 @@ FixNVEMDP::FixNVEMDP(LAMMPS *lmp, int narg, char **arg)
   memset(&baths, 0, sizeof baths);
   memset(&heat, 0, sizeof heat);
   memset(&indent, 0, sizeof indent);
+  memset(&spring, 0, sizeof spring);
   if (narg < 3 || (narg - 3) % 2) error->all(FLERR, "Illegal fix nve/mdp command");
   if (igroup < 0)
     error->all(FLERR, std::string("Fix ") + arg[2] + " requires group all or a group defined by the group command: could not find fix group ID " + arg[1]);
@@ -235,6 +236,13 @@ void FixNVEMDP::setup(int vflag)
     if (mdp_indent_run(c, (long long) update->beginstep) != MDP_OK) fail(c);
     indent_ctx = c;
   }
+  // springs (fix spring/mdp): as the indenters, and behind them -- the order of the two passes in front of a kick
+  if (spring.count) {
+    if (heat.count) error->all(FLERR, "Fix nve/mdp: springs (fix spring/mdp) and heat sources (fix heat/mdp) in one run");
+    if (mdp_spring_setup(c, spring.count, spring.cfg, spring.bit) != MDP_OK) fail(c);
+    if (mdp_spring_run(c, (long long) update->beginstep) != MDP_OK) fail(c);
+    spring_ctx = c;
+  }
   if (!baths.count) return;
   if (baths.count == 1) {
     if (mdp_langevin_setup(c, &baths.cfg[0]) != MDP_OK) fail(c);
@@ -254,8 +262,14 @@ void *FixNVEMDP::extract(const char *name, int &dim)
   if (strcmp(name, "mdp_heat_ctx") == 0) return &heat_ctx;
   if (strcmp(name, "mdp_indenters") == 0) return &indent;
   if (strcmp(name, "mdp_indent_ctx") == 0) return &indent_ctx;
+  if (strcmp(name, "mdp_springs") == 0) return &spring;
+  if (strcmp(name, "mdp_spring_ctx") == 0) return &spring_ctx;
   if (strcmp(name, "mdp_steps_ctx") == 0) return &run_ctx;
   if (strcmp(name, "mdp_bricks") == 0) return &bricks;
+  if (strcmp(name, "mdp_bricks_want") == 0) {
+    bricks_want = comm->nprocs != 1 || bricks_kw;
+    return &bricks_want;
+  }
   return nullptr;
 }
 
@@ -263,6 +277,13 @@ bool FixNVEMDP::indent_masked() const
 {
   for (int k = 0; k < indent.count; k++)
     if (indent.bit[k]) return true;
+  return false;
+}
+
+bool FixNVEMDP::spring_masked() const
+{
+  for (int k = 0; k < spring.count; k++)
+    if (spring.bit[k]) return true;
   return false;
 }
 
@@ -396,6 +417,9 @@ void FixNVEMDP::post_run()
   if (indent_ctx && mdp_indent_off(indent_ctx) != MDP_OK) fail(indent_ctx); // (an unfix of the indenters gives plain forces next run)
   indent_ctx = nullptr;
   memset(&indent, 0, sizeof indent);
+  if (spring_ctx && mdp_spring_off(spring_ctx) != MDP_OK) fail(spring_ctx); // (an unfix of the springs gives plain forces next run)
+  spring_ctx = nullptr;
+  memset(&spring, 0, sizeof spring);
   if (bricks) {
     long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (comm->nprocs > 1) (void) mdp_dd_comm_step_info(bctx, info);

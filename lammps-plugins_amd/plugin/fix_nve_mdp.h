@@ -32,6 +32,7 @@ FixStyle(nve/mdp,FixNVEMDP);
 #include "mdp_baths.h"
 #include "mdp_heat.h"
 #include "mdp_indent.h"
+#include "mdp_spring.h"
 #include "mdpair_hip.h"
 
 namespace LAMMPS_NS {
@@ -63,6 +64,7 @@ class FixNVEMDP : public Fix {
   // several ranks ("bricks")
   int bricks;          // comm->nprocs > 1, or `bricks yes`: the steps run on bctx
   int bricks_kw;       // `bricks yes`
+  int bricks_want = 0; // what `bricks` will be once init() has run (extract "mdp_bricks_want": a fix whose init() runs first asks this)
   long one_rank_builds = 0;
   mdp_ctx *bctx;       // the fix's own context: this rank's brick
   mdp_ctx **bricks_slot;   // the pair style's pointer to it (set while a run is under way: its compute() ends the steps there)
@@ -92,6 +94,12 @@ class FixNVEMDP : public Fix {
   MdpIndenters indent;
   mdp_ctx *indent_ctx = nullptr;
   bool indent_masked() const; // one of them acts on a group: the device needs atom->mask
+  // the springs the `fix spring/mdp` fixes handed over (extract "mdp_springs", mdp_spring.h): switched on in setup() behind
+  // the indenters (mdp_spring_setup, mdp_spring_run(beginstep)) on the context the steps run on (spring_ctx, extract
+  // "mdp_spring_ctx"), off in post_run().  Bricks only: the fixes refuse the host-linked mode
+  MdpSprings spring;
+  mdp_ctx *spring_ctx = nullptr;
+  bool spring_masked() const; // one of them acts on a group: the device needs atom->mask
   int brick_masked = 0; // this run's brick was set up with atom->mask (it comes back with the atoms)
   mdp_ctx *lgv_ctx = nullptr;
   // the context the steps of the run under way go through, thermostat or not, null between runs (extract "mdp_steps_ctx":
@@ -107,7 +115,7 @@ class FixNVEMDP : public Fix {
   int taken_delay() const;
   bool grouped() const { return igroup > 0; }                  // the fix acts on a group other than all
   bool lgv_masked() const { return baths.count > 1 || (baths.count == 1 && baths.bit[0]); }
-  bool masked() const { return grouped() || lgv_masked() || heat.count > 0 || indent_masked(); } // ... or a thermostat or a heat source does: the device needs atom->mask
+  bool masked() const { return grouped() || lgv_masked() || heat.count > 0 || indent_masked() || spring_masked(); } // ... or a thermostat or a heat source does: the device needs atom->mask
   bool brick_mask() const;                                     // bricks: atom->mask travels with the atoms
   double group_count();                                        // atoms the fix integrates, over all ranks
   void apply_groups(mdp_ctx *c);                               // the group bits (and, host-linked, the mask) of this run on c
