@@ -1,7 +1,7 @@
 /* -*- c++ -*- -----------------------------------------------------------------------------------
    `fix heat/mdp`: LAMMPS `fix heat` with a constant flux on the device, for runs that integrate with `fix nve/mdp` on one
    MPI rank (host-linked or `bricks yes`).  Not a time integrator: at init() it hands a copy of its settings to the one
-   fix nve/mdp (its slot of Fix::extract "mdp_heat_sources", mdp_heat.h), which switches the library's heat sources
+   fix nve/mdp (its slot of Fix::extract "mdp_heat_sources", mdp_riders.h), which switches the library's heat sources
    (mdp_heat_*, csrc/heat.hip) on in the context its steps run on for the length of each run.
 
    fix ID GROUP heat/mdp N eflux
@@ -22,27 +22,19 @@ FixStyle(heat/mdp,FixHeatMDP);
 #ifndef MDP_FIX_HEAT_MDP_H
 #define MDP_FIX_HEAT_MDP_H
 
-#include "fix.h"
-
-#include "mdpair_hip.h"
+#include "fix_rider_mdp.h"
 
 namespace LAMMPS_NS {
 
-class FixHeatMDP : public Fix {
+class FixHeatMDP : public FixRiderMDP {
  public:
   FixHeatMDP(class LAMMPS *, int, char **);
-  int setmask() override;
   void init() override;
   double compute_scalar() override;
 
  private:
   mdp_heat_config cfg;
-  int src = 0;                   // this fix's position among the heat/mdp fixes of Modify's list, as of the last init()
   double scale = 1.0;            // of the last application read (kept between runs, as FixHeat keeps it)
-  class Fix *integrator() const; // the fix nve/mdp of this run (looked up anew: no pointer outlives either fix)
-  void inside(class Fix *nve);   // refuses a group with an atom the integrator does not move
-  void disjoint();               // refuses atoms shared with a heat/mdp fix earlier in Modify's list
-  void too_many(int n);          // refuses heat/mdp fix number n > MDP_HEAT_MAXSRC
 };
 
 }    // namespace LAMMPS_NS

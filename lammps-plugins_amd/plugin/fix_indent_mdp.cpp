@@ -4,24 +4,20 @@
                         anywhere, bad numbers, side on a plane, an unknown keyword, units other than box or none at all, a
                         cylinder that moves along its axis, a box with a non-periodic dimension, a fifth indent/mdp)
      init()             the one fix nve/mdp found through modify; a copy of the settings written into this fix's slot of its
-                        Fix::extract("mdp_indenters") block (mdp_indent.h).  Refused here: no fix nve/mdp, a host-side time
+                        Fix::extract("mdp_indenters") block (mdp_riders.h).  Refused here: no fix nve/mdp, a host-side time
                         integrator, a non-periodic dimension, fix nvt/mdp or fix heat/mdp in the same run, several ranks
      the steps          fix nve/mdp's: its setup() switches the indenters on (mdp_indent_setup, mdp_indent_run(beginstep))
                         in the context the steps run on, its post_run() switches them off
-     compute_scalar()   the indenter's energy, compute_vector(0..2) the force on it, read through the context fix nve/mdp
-                        exposes (Fix::extract("mdp_indent_ctx"))
+     compute_scalar()   the indenter's energy, compute_vector(0..2) the force on it, read from the context of the run under
+                        way, once per step
+   What it shares with the other fixes that ride on fix nve/mdp is FixRiderMDP's (fix_rider_mdp.h).
 -------------------------------------------------------------------------------------------------- */
 #include "fix_indent_mdp.h"
 #include "mdp_args.h"
-#include "mdp_indent.h"
 
-#include "atom.h"
 #include "comm.h"
 #include "domain.h"
 #include "error.h"
-#include "group.h"
-#include "modify.h"
-#include "update.h"
 
 #include <cstring>
 #include <string>
@@ -44,16 +40,13 @@ static int indent_dim(Error *error, const char *s)
   return 0;
 }
 
-FixIndentMDP::FixIndentMDP(LAMMPS *lmp, int narg, char **arg) : Fix(lmp, narg, arg)
+static const char *const usage = "Illegal fix indent/mdp command: fix ID group indent/mdp K sphere x y z R | cylinder dim c1 c2 R | plane dim pos lo|hi "
+                                 "[side in|out] [vel vx vy vz] units box";
+
+FixIndentMDP::FixIndentMDP(LAMMPS *lmp, int narg, char **arg)
+    : FixRiderMDP(lmp, narg, arg, "indent/mdp", MDP_INDENT_MAX, "mdp_indenters", 5, usage, "there is no atom to push on")
 {
   memset(&cfg, 0, sizeof cfg);
-  const char *usage = "Illegal fix indent/mdp command: fix ID group indent/mdp K sphere x y z R | cylinder dim c1 c2 R | plane dim pos lo|hi "
-                      "[side in|out] [vel vx vy vz] units box";
-  if (narg < 5) error->all(FLERR, usage);
-  if (igroup < 0)
-    error->all(FLERR, std::string("Fix indent/mdp requires group all or a group defined by the group command: could not find fix group ID ") + arg[1]);
-  if (igroup > 0 && group->count(igroup) == 0)
-    error->all(FLERR, std::string("Fix indent/mdp: group ") + arg[1] + " is empty: there is no atom to push on");
   for (int k = 3; k < narg; k++) // (a variable is named as such wherever it stands, before anything else is said)
     if (strncmp(arg[k], "v_", 2) == 0) number("an argument", arg[k]);
   cfg.k = number("K", arg[3]);
@@ -125,16 +118,7 @@ FixIndentMDP::FixIndentMDP(LAMMPS *lmp, int narg, char **arg) : Fix(lmp, narg, a
   extscalar = extvector = 1;
 #endif
   periodic_or_refuse();
-  int earlier = 0;
-  for (int i = 0; i < modify->nfix; i++) // (a fix with this ID is replaced by this one: it does not count)
-    if (strcmp(modify->fix[i]->style, "indent/mdp") == 0 && strcmp(modify->fix[i]->id, id) != 0) earlier++;
-  if (earlier + 1 > MDP_INDENT_MAX) too_many(earlier + 1);
-}
-
-void FixIndentMDP::too_many(int n)
-{
-  error->all(FLERR, std::string("Fix indent/mdp: ") + id + " is indent/mdp fix number " + std::to_string(n) + "; fix nve/mdp takes up to " +
-                        std::to_string(MDP_INDENT_MAX) + " of them");
+  census();
 }
 
 // The library takes the box of a host-linked context to be periodic in all three dimensions (mdp_set_box_host carries no
@@ -151,66 +135,25 @@ void FixIndentMDP::periodic_or_refuse()
                             "(use a periodic box with vacuum, as examples/in.rebomos-sheet.indent-mdp.mi355x does)");
 }
 
-int FixIndentMDP::setmask() { return 0; } // (the pass runs inside fix nve/mdp's device steps)
-
-Fix *FixIndentMDP::integrator() const
-{
-  for (int i = 0; i < modify->nfix; i++)
-    if (strcmp(modify->fix[i]->style, "nve/mdp") == 0) return modify->fix[i];
-  return nullptr;
-}
-
 void FixIndentMDP::init()
 {
   if (comm->nprocs > 1) error->all(FLERR, "Fix indent/mdp runs on one MPI rank only (its sums are taken on one device)");
   periodic_or_refuse(); // (a `boundary` or `change_box` command may stand behind the fix)
-  read_step = -1;       // (a new run: its setup state is not the last run's last)
-  Fix *nve = nullptr;
   int n = 0;
-  for (int i = 0; i < modify->nfix; i++) {
-    Fix *f = modify->fix[i];
-    if (strcmp(f->style, "indent/mdp") == 0) { // (this fix among them: its slot is its position in the list)
-      if (f == this) slot = n;
-      n++;
-      continue;
-    }
-    if (strcmp(f->style, "nvt/mdp") == 0 || strcmp(f->style, "heat/mdp") == 0)
-      error->all(FLERR, std::string("Fix indent/mdp: fix ") + id + " cannot run next to fix " + f->id + " (" + f->style +
-                            "): indenters run under fix nve/mdp, with or without fix langevin/mdp; unfix one of them");
-    if (strcmp(f->style, "nve/mdp") == 0) nve = f;
-    else if (f->time_integrate)
-      error->all(FLERR, std::string("Fix indent/mdp: fix ") + f->id + " (" + f->style +
-                            ") integrates on the host; the device's indenters need fix nve/mdp as the time integrator");
-  }
-  if (!nve) error->all(FLERR, "Fix indent/mdp requires fix nve/mdp as the time integrator");
-  if (n > MDP_INDENT_MAX) too_many(n);
-  int dim = 0;
-  MdpIndenters *block = static_cast<MdpIndenters *>(nve->extract("mdp_indenters", dim));
-  if (!block) error->all(FLERR, "Fix indent/mdp: this fix nve/mdp does not take indenters");
-  if ((igroup == 0 ? (double) atom->natoms : (double) group->count(igroup)) < 1.0)
-    error->all(FLERR, std::string("Fix indent/mdp: group ") + group->names[igroup] + " is empty: there is no atom to push on");
+  Fix *nve = walk({"nvt/mdp", "heat/mdp"}, std::string(id) + " cannot run next to fix ",
+                  "): indenters run under fix nve/mdp, with or without fix langevin/mdp; unfix one of them",
+                  "the device's indenters need fix nve/mdp as the time integrator", "Fix indent/mdp requires fix nve/mdp as the time integrator", n);
+  MdpIndenters *block = static_cast<MdpIndenters *>(handover(nve, "indenters"));
+  populated();
   block->count = n;
   block->cfg[slot] = cfg;
   block->bit[slot] = igroup == 0 ? 0 : groupbit; // (group all: every owned atom, no mask needed)
 }
 
-void FixIndentMDP::read()
-{
-  Fix *nve = integrator();
-  int dim = 0;
-  mdp_ctx **c = nve ? static_cast<mdp_ctx **>(nve->extract("mdp_indent_ctx", dim)) : nullptr;
-  if (!c || !*c) return; // (between runs: what the last read returned)
-  if (read_step == update->ntimestep) return; // (one blocking read per step serves f_ID and f_ID[1..3])
-  double st[MDP_INDENT_STATE_LEN];
-  if (mdp_indent_state(*c, slot, st) != MDP_OK) error->one(FLERR, std::string("Fix indent/mdp: ") + mdp_last_error(*c));
-  for (int k = 0; k < 4; k++) last[k] = st[k];
-  read_step = update->ntimestep;
-}
-
 // FixIndent::compute_scalar: the indenter's energy
 double FixIndentMDP::compute_scalar()
 {
-  read();
+  read(mdp_indent_state, last, true);
   return last[0];
 }
 
@@ -218,6 +161,6 @@ double FixIndentMDP::compute_scalar()
 double FixIndentMDP::compute_vector(int n)
 {
   if (n < 0 || n > 2) return 0.0;
-  read();
+  read(mdp_indent_state, last, true);
   return last[1 + n];
 }

@@ -1,7 +1,7 @@
 /* -*- c++ -*- -----------------------------------------------------------------------------------
    `fix indent/mdp`: LAMMPS `fix indent` on the device, for runs that integrate with `fix nve/mdp` on one MPI rank
    (host-linked or `bricks yes`), with or without `fix langevin/mdp` baths.  Not a time integrator: at init() it hands a
-   copy of its settings to the one fix nve/mdp (its slot of Fix::extract "mdp_indenters", mdp_indent.h), which switches the
+   copy of its settings to the one fix nve/mdp (its slot of Fix::extract "mdp_indenters", mdp_riders.h), which switches the
    library's indenters (mdp_indent_*, csrc/indent.hip) on in the context its steps run on for the length of each run.
 
    fix ID GROUP indent/mdp K sphere x y z R | cylinder dim c1 c2 R | plane dim pos lo|hi  [side in|out] [vel vx vy vz] units box
@@ -24,30 +24,22 @@ FixStyle(indent/mdp,FixIndentMDP);
 #ifndef MDP_FIX_INDENT_MDP_H
 #define MDP_FIX_INDENT_MDP_H
 
-#include "fix.h"
-
-#include "mdpair_hip.h"
+#include "fix_rider_mdp.h"
 
 namespace LAMMPS_NS {
 
-class FixIndentMDP : public Fix {
+class FixIndentMDP : public FixRiderMDP {
  public:
   FixIndentMDP(class LAMMPS *, int, char **);
-  int setmask() override;
   void init() override;
   double compute_scalar() override;
   double compute_vector(int) override;
 
  private:
   mdp_indent_config cfg;
-  int slot = 0;                  // this fix's position among the indent/mdp fixes of Modify's list, as of the last init()
-  double last[4] = {0.0, 0.0, 0.0, 0.0}; // energy and force of the last read (kept between runs)
-  bigint read_step = -1;         // the timestep `last` was read at in this run (-1: not yet)
+  double last[MDP_INDENT_STATE_LEN] = {}; // energy and force of the last read (kept between runs), and the words behind them
   void periodic_or_refuse();     // refuses a box with a non-periodic dimension
-  class Fix *integrator() const; // the fix nve/mdp of this run (looked up anew: no pointer outlives either fix)
-  void read();                   // mdp_indent_state of this fix's slot into `last`
   double number(const char *what, const char *s); // a finite number, or the refusal (a variable named as such)
-  void too_many(int n);          // refuses indent/mdp fix number n > MDP_INDENT_MAX
 };
 
 }    // namespace LAMMPS_NS

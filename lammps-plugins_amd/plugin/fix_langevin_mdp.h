@@ -1,7 +1,7 @@
 /* -*- c++ -*- -----------------------------------------------------------------------------------
    `fix langevin/mdp`: LAMMPS `fix langevin` on the device, for runs that integrate with `fix nve/mdp` (any of its modes:
    host-linked, `bricks yes`, several ranks).  Not a time integrator: at init() it hands a copy of its settings to the
-   one fix nve/mdp (its slot of Fix::extract "mdp_langevin_baths", mdp_baths.h), which switches the library's thermostat
+   one fix nve/mdp (its slot of Fix::extract "mdp_langevin_baths", mdp_riders.h), which switches the library's thermostat
    (mdp_langevin_*, csrc/langevin.hip) on in the context its steps run on for the length of each run.
 
    Up to MDP_LANGEVIN_MAXBATH (4) of these fixes may stand next to one fix nve/mdp -- a hot and a cold bath, say -- if no
@@ -25,26 +25,18 @@ FixStyle(langevin/mdp,FixLangevinMDP);
 #ifndef MDP_FIX_LANGEVIN_MDP_H
 #define MDP_FIX_LANGEVIN_MDP_H
 
-#include "fix.h"
-
-#include "mdpair_hip.h"
+#include "fix_rider_mdp.h"
 
 namespace LAMMPS_NS {
 
-class FixLangevinMDP : public Fix {
+class FixLangevinMDP : public FixRiderMDP {
  public:
   FixLangevinMDP(class LAMMPS *, int, char **);
-  int setmask() override;
   void init() override;
   double compute_scalar() override;
 
  private:
   mdp_langevin_config cfg;
-  int bath = 0;                  // this fix's position among the langevin/mdp fixes of Modify's list, as of the last init()
-  class Fix *integrator() const; // the fix nve/mdp of this run (looked up anew: no pointer outlives either fix)
-  void inside(class Fix *nve);   // refuses a group with an atom the integrator does not move
-  void disjoint();               // refuses atoms shared with a langevin/mdp fix earlier in Modify's list
-  void too_many(int n);          // refuses langevin/mdp fix number n > MDP_LANGEVIN_MAXBATH
 };
 
 }    // namespace LAMMPS_NS

@@ -56,7 +56,11 @@
    (PairMDP::upload_host, mdp_hnve_set_mask), with the atoms into the brick otherwise (mdp_brick.h, mdp_md_set_mask),
    from where it comes back with them.  A fix langevin/mdp on a sub-group hands its bit over the same way
    (mdp_langevin_group), several of them on disjoint sub-groups their bits and settings together (mdp_langevin_baths), and
-   the fix heat/mdp fixes of a run theirs (mdp_heat_setup, in setup() behind the mask).  Group all sets both bits to 0 and uploads no mask for the fix's sake.  Run in the mini-host
+   the fix heat/mdp, fix indent/mdp and fix spring/mdp fixes of a run theirs (mdp_heat_setup and its like, in setup() behind
+   the mask).  Group all sets both bits to 0 and uploads no mask for the fix's sake.  All four styles ride on this fix the
+   same way (fix_rider_mdp.h): one block per style (mdp_riders.h) that they fill at init(), one list of the blocks
+   (riders(), fix_nve_mdp.h) that setup(), post_run(), extract() and masked() walk, and one pointer, run_ctx, to the context
+   of the run under way, which they and the computes read through Fix::extract("mdp_steps_ctx").  Run in the mini-host
    on 2, 4 and 8 ranks (tests/test_gpu_minilmp_ranks.py: log.rebomos-bulk.4's rows, the one-rank thermo of hot runs with
    migration); against a real LAMMPS this mode is unverified.
 -------------------------------------------------------------------------------------------------- */
@@ -90,10 +94,6 @@ FixNVEMDP::FixNVEMDP(LAMMPS *lmp, int narg, char **arg)
     : Fix(lmp, narg, arg), ctxp(nullptr), pair_linked(nullptr), pair_mask(nullptr), downloads(0), hostcheck(0), took_delay(0), saved_delay(0),
       linked_to(nullptr), bricks(0), bricks_kw(0), bctx(nullptr), bricks_slot(nullptr), bricks_ev(nullptr), style_id(0), comm_up(0), pending_final(0), step_ev(0)
 {
-  memset(&baths, 0, sizeof baths);
-  memset(&heat, 0, sizeof heat);
-  memset(&indent, 0, sizeof indent);
-  memset(&spring, 0, sizeof spring);
   if (narg < 3 || (narg - 3) % 2) error->all(FLERR, "Illegal fix nve/mdp command");
   if (igroup < 0)
     error->all(FLERR, std::string("Fix ") + arg[2] + " requires group all or a group defined by the group command: could not find fix group ID " + arg[1]);
@@ -211,8 +211,33 @@ void FixNVEMDP::init_bricks()
   next_reneighbor = -1;
 }
 
-// Modify::setup, behind the host's own setup (exchange, borders, lists, forces of step 0 in host mode); then the
-// Langevin thermostat, if a fix langevin/mdp handed one over, on the context the steps of this run go through
+// how the library switches each kind on for a run that opens at step `first` and closes at `last`
+static int on(mdp_ctx *c, const MdpHeatSources &b, long long first, long long)
+{
+  const int rc = mdp_heat_setup(c, b.count, b.cfg, b.bit);
+  return rc != MDP_OK ? rc : mdp_heat_run(c, first); // (step `first` itself is not heated, as Verlet::setup does not call end_of_step)
+}
+// the forces the context holds now are the setup's, the pair style's alone, and the first kick of the run adds the
+// indenters' for step `first` in front of itself -- FixIndent::setup's post_force
+static int on(mdp_ctx *c, const MdpIndenters &b, long long first, long long)
+{
+  const int rc = mdp_indent_setup(c, b.count, b.cfg, b.bit);
+  return rc != MDP_OK ? rc : mdp_indent_run(c, first);
+}
+static int on(mdp_ctx *c, const MdpSprings &b, long long first, long long)
+{
+  const int rc = mdp_spring_setup(c, b.count, b.cfg, b.bit);
+  return rc != MDP_OK ? rc : mdp_spring_run(c, first);
+}
+static int on(mdp_ctx *c, const MdpLangevinBaths &b, long long first, long long last)
+{
+  // (several: counts the atoms in two baths, the mask is up)
+  const int rc = b.count == 1 ? mdp_langevin_setup(c, &b.cfg[0]) : mdp_langevin_baths(c, b.count, b.cfg, b.bit);
+  return rc != MDP_OK ? rc : mdp_langevin_run(c, first, last);
+}
+
+// Modify::setup, behind the host's own setup (exchange, borders, lists, forces of step 0 in host mode); then what the
+// riding fixes handed over, on the context the steps of this run go through
 void FixNVEMDP::setup(int vflag)
 {
   setup_steps(vflag);
@@ -220,50 +245,22 @@ void FixNVEMDP::setup(int vflag)
   if (!c) fail(nullptr);
   apply_groups(c);
   run_ctx = c;
-  // heat sources (fix heat/mdp): behind the groups and the mask, which mdp_heat_setup counts their atoms in; step
-  // beginstep itself is not heated, as Verlet::setup does not call end_of_step
-  if (heat.count) {
-    if (baths.count) error->all(FLERR, "Fix nve/mdp: heat sources (fix heat/mdp) and a thermostat (fix langevin/mdp) in one run");
-    if (mdp_heat_setup(c, heat.count, heat.cfg, heat.bit) != MDP_OK) fail(c);
-    if (mdp_heat_run(c, (long long) update->beginstep) != MDP_OK) fail(c);
-    heat_ctx = c;
-  }
-  // indenters (fix indent/mdp): the forces the context holds now are the setup's, the pair style's alone, and the first
-  // kick of the run adds the indenters' for step beginstep in front of itself -- FixIndent::setup's post_force
-  if (indent.count) {
-    if (heat.count) error->all(FLERR, "Fix nve/mdp: indenters (fix indent/mdp) and heat sources (fix heat/mdp) in one run");
-    if (mdp_indent_setup(c, indent.count, indent.cfg, indent.bit) != MDP_OK) fail(c);
-    if (mdp_indent_run(c, (long long) update->beginstep) != MDP_OK) fail(c);
-    indent_ctx = c;
-  }
-  // springs (fix spring/mdp): as the indenters, and behind them -- the order of the two passes in front of a kick
-  if (spring.count) {
-    if (heat.count) error->all(FLERR, "Fix nve/mdp: springs (fix spring/mdp) and heat sources (fix heat/mdp) in one run");
-    if (mdp_spring_setup(c, spring.count, spring.cfg, spring.bit) != MDP_OK) fail(c);
-    if (mdp_spring_run(c, (long long) update->beginstep) != MDP_OK) fail(c);
-    spring_ctx = c;
-  }
-  if (!baths.count) return;
-  if (baths.count == 1) {
-    if (mdp_langevin_setup(c, &baths.cfg[0]) != MDP_OK) fail(c);
-  } else if (mdp_langevin_baths(c, baths.count, baths.cfg, baths.bit) != MDP_OK) // (counts the atoms in two baths: the mask is up)
-    fail(c);
-  if (mdp_langevin_run(c, (long long) update->beginstep, (long long) update->endstep) != MDP_OK) fail(c);
-  lgv_ctx = c;
+  riders([&](auto &b, const char *, int (*)(mdp_ctx *), const int *against, const char *refusal) {
+    if (!b.count) return;
+    if (against && *against) error->all(FLERR, refusal);
+    if (on(c, b, (long long) update->beginstep, (long long) update->endstep) != MDP_OK) fail(c);
+  });
 }
 
-// the langevin/mdp fixes hand their thermostats over here (copies of their configs; no pointer to either fix is kept)
+// the riding fixes hand their settings over here (copies of their configs; no pointer to any of them is kept)
 void *FixNVEMDP::extract(const char *name, int &dim)
 {
   dim = 0;
-  if (strcmp(name, "mdp_langevin_baths") == 0) return &baths;
-  if (strcmp(name, "mdp_run_ctx") == 0) return &lgv_ctx;
-  if (strcmp(name, "mdp_heat_sources") == 0) return &heat;
-  if (strcmp(name, "mdp_heat_ctx") == 0) return &heat_ctx;
-  if (strcmp(name, "mdp_indenters") == 0) return &indent;
-  if (strcmp(name, "mdp_indent_ctx") == 0) return &indent_ctx;
-  if (strcmp(name, "mdp_springs") == 0) return &spring;
-  if (strcmp(name, "mdp_spring_ctx") == 0) return &spring_ctx;
+  void *block = nullptr;
+  riders([&](auto &b, const char *key, int (*)(mdp_ctx *), const int *, const char *) {
+    if (strcmp(name, key) == 0) block = &b;
+  });
+  if (block) return block;
   if (strcmp(name, "mdp_steps_ctx") == 0) return &run_ctx;
   if (strcmp(name, "mdp_bricks") == 0) return &bricks;
   if (strcmp(name, "mdp_bricks_want") == 0) {
@@ -273,23 +270,16 @@ void *FixNVEMDP::extract(const char *name, int &dim)
   return nullptr;
 }
 
-bool FixNVEMDP::indent_masked() const
+bool FixNVEMDP::masked()
 {
-  for (int k = 0; k < indent.count; k++)
-    if (indent.bit[k]) return true;
-  return false;
-}
-
-bool FixNVEMDP::spring_masked() const
-{
-  for (int k = 0; k < spring.count; k++)
-    if (spring.bit[k]) return true;
-  return false;
+  bool any = grouped();
+  riders([&](auto &b, const char *, int (*)(mdp_ctx *), const int *, const char *) { any = any || b.masked(); });
+  return any;
 }
 
 double FixNVEMDP::group_count() { return grouped() ? (double) group->count(igroup) : (double) atom->natoms; }
 
-bool FixNVEMDP::brick_mask() const { return masked() || mdp_host_has_groups(group); }
+bool FixNVEMDP::brick_mask() { return masked() || mdp_host_has_groups(group); }
 
 // The groups of this run on the context its steps go through.  Group all (and no thermostat on a group): both bits 0, the
 // kernels of a context without groups.  Host-linked: the setup compute that has just run uploaded the atoms of this step;
@@ -407,19 +397,11 @@ void FixNVEMDP::initial_integrate(int vflag)
 // MDP_FIX_STATS=1: one line per run on how often the host's x / v were brought up to date (bench.py reads it)
 void FixNVEMDP::post_run()
 {
-  if (lgv_ctx && mdp_langevin_off(lgv_ctx) != MDP_OK) fail(lgv_ctx); // (an unfix of the thermostat gives NVE next run)
-  lgv_ctx = nullptr;
+  riders([&](auto &b, const char *, int (*off)(mdp_ctx *), const int *, const char *) { // (an unfix of them gives plain NVE next run)
+    if (b.count && run_ctx && off(run_ctx) != MDP_OK) fail(run_ctx);
+    b = {};
+  });
   run_ctx = nullptr;
-  memset(&baths, 0, sizeof baths);
-  if (heat_ctx && mdp_heat_off(heat_ctx) != MDP_OK) fail(heat_ctx); // (an unfix of the sources gives plain NVE next run)
-  heat_ctx = nullptr;
-  memset(&heat, 0, sizeof heat);
-  if (indent_ctx && mdp_indent_off(indent_ctx) != MDP_OK) fail(indent_ctx); // (an unfix of the indenters gives plain forces next run)
-  indent_ctx = nullptr;
-  memset(&indent, 0, sizeof indent);
-  if (spring_ctx && mdp_spring_off(spring_ctx) != MDP_OK) fail(spring_ctx); // (an unfix of the springs gives plain forces next run)
-  spring_ctx = nullptr;
-  memset(&spring, 0, sizeof spring);
   if (bricks) {
     long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (comm->nprocs > 1) (void) mdp_dd_comm_step_info(bctx, info);

@@ -29,10 +29,7 @@ FixStyle(nve/mdp,FixNVEMDP);
 
 #include "fix.h"
 
-#include "mdp_baths.h"
-#include "mdp_heat.h"
-#include "mdp_indent.h"
-#include "mdp_spring.h"
+#include "mdp_riders.h"
 #include "mdpair_hip.h"
 
 namespace LAMMPS_NS {
@@ -79,31 +76,26 @@ class FixNVEMDP : public Fix {
   static constexpr int kVirialAtom = 4; // VIRIAL_ATOM of LAMMPS' force.h: the bit of the vflag Integrate::ev_set hands out
   bool atom_step(int vflag) const { return atom_ok && (vflag & kVirialAtom); }
 
-  // the Langevin thermostats the `fix langevin/mdp` fixes handed over (extract "mdp_langevin_baths", mdp_baths.h): switched
-  // on in setup() on the context the steps run on (lgv_ctx, extract "mdp_run_ctx"), off in post_run().  One: the calls of
-  // one thermostat (mdp_langevin_setup, mdp_langevin_group); several: mdp_langevin_baths
-  MdpLangevinBaths baths;
-  // the heat sources the `fix heat/mdp` fixes handed over (extract "mdp_heat_sources", mdp_heat.h): switched on in setup()
-  // behind the groups and the mask (mdp_heat_setup, mdp_heat_run(beginstep)) on the context the steps run on (heat_ctx,
-  // extract "mdp_heat_ctx"), off in post_run()
-  MdpHeatSources heat;
-  mdp_ctx *heat_ctx = nullptr;
-  // the indenters the `fix indent/mdp` fixes handed over (extract "mdp_indenters", mdp_indent.h): switched on in setup()
-  // behind the mask and the setup's forces (mdp_indent_setup, mdp_indent_run(beginstep)) on the context the steps run on
-  // (indent_ctx, extract "mdp_indent_ctx"), off in post_run()
-  MdpIndenters indent;
-  mdp_ctx *indent_ctx = nullptr;
-  bool indent_masked() const; // one of them acts on a group: the device needs atom->mask
-  // the springs the `fix spring/mdp` fixes handed over (extract "mdp_springs", mdp_spring.h): switched on in setup() behind
-  // the indenters (mdp_spring_setup, mdp_spring_run(beginstep)) on the context the steps run on (spring_ctx, extract
-  // "mdp_spring_ctx"), off in post_run().  Bricks only: the fixes refuse the host-linked mode
-  MdpSprings spring;
-  mdp_ctx *spring_ctx = nullptr;
-  bool spring_masked() const; // one of them acts on a group: the device needs atom->mask
+  // What the fixes that ride on this one handed over (fix_rider_mdp.h; one block per style, mdp_riders.h, under the
+  // Fix::extract key beside it): switched on in setup() on run_ctx, behind the groups and the mask, in the order they
+  // stand here -- heat sources (mdp_heat_setup, mdp_heat_run(beginstep)), indenters and behind them springs (the order
+  // of the two passes in front of a kick), Langevin thermostats (one: mdp_langevin_setup, mdp_langevin_group; several:
+  // mdp_langevin_baths) -- and off in post_run(), which clears the blocks.  A style takes part in a run if its count > 0
+  MdpHeatSources heat = {};      // "mdp_heat_sources"
+  MdpIndenters indent = {};      // "mdp_indenters"
+  MdpSprings spring = {};        // "mdp_springs": bricks only, the fixes refuse the host-linked mode
+  MdpLangevinBaths baths = {};   // "mdp_langevin_baths"
+  // f(block, key, off, against, refusal) for each of them; against: the count of the kind it cannot share a run with, or null
+  template <class F> void riders(F f)
+  {
+    f(heat, "mdp_heat_sources", mdp_heat_off, &baths.count, "Fix nve/mdp: heat sources (fix heat/mdp) and a thermostat (fix langevin/mdp) in one run");
+    f(indent, "mdp_indenters", mdp_indent_off, &heat.count, "Fix nve/mdp: indenters (fix indent/mdp) and heat sources (fix heat/mdp) in one run");
+    f(spring, "mdp_springs", mdp_spring_off, &heat.count, "Fix nve/mdp: springs (fix spring/mdp) and heat sources (fix heat/mdp) in one run");
+    f(baths, "mdp_langevin_baths", mdp_langevin_off, (const int *) nullptr, "");
+  }
   int brick_masked = 0; // this run's brick was set up with atom->mask (it comes back with the atoms)
-  mdp_ctx *lgv_ctx = nullptr;
-  // the context the steps of the run under way go through, thermostat or not, null between runs (extract "mdp_steps_ctx":
-  // compute msd/mdp reads its sums there); extract "mdp_bricks": whether that context is a brick of the library's own
+  // the context the steps of the run under way go through, null between runs (extract "mdp_steps_ctx": the computes read
+  // their sums there and the riding fixes their state); extract "mdp_bricks": whether that context is a brick of the library's own
   mdp_ctx *run_ctx = nullptr;
 
   mdp_ctx *ctx() const { return ctxp ? *ctxp : nullptr; }
@@ -114,9 +106,8 @@ class FixNVEMDP : public Fix {
   void fail(mdp_ctx *c);
   int taken_delay() const;
   bool grouped() const { return igroup > 0; }                  // the fix acts on a group other than all
-  bool lgv_masked() const { return baths.count > 1 || (baths.count == 1 && baths.bit[0]); }
-  bool masked() const { return grouped() || lgv_masked() || heat.count > 0 || indent_masked() || spring_masked(); } // ... or a thermostat or a heat source does: the device needs atom->mask
-  bool brick_mask() const;                                     // bricks: atom->mask travels with the atoms
+  bool masked();                                               // ... or a fix that rides on this one does: the device needs atom->mask
+  bool brick_mask();                                           // bricks: atom->mask travels with the atoms
   double group_count();                                        // atoms the fix integrates, over all ranks
   void apply_groups(mdp_ctx *c);                               // the group bits (and, host-linked, the mask) of this run on c
 };

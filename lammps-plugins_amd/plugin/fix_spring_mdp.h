@@ -1,7 +1,7 @@
 /* -*- c++ -*- -----------------------------------------------------------------------------------
    `fix spring/mdp`: LAMMPS `fix spring tether` on the device, for runs that integrate with `fix nve/mdp bricks yes` on one
    MPI rank, with or without `fix langevin/mdp` baths and `fix indent/mdp` indenters.  Not a time integrator: at init() it
-   hands a copy of its settings to the one fix nve/mdp (its slot of Fix::extract "mdp_springs", mdp_spring.h), which switches
+   hands a copy of its settings to the one fix nve/mdp (its slot of Fix::extract "mdp_springs", mdp_riders.h), which switches
    the library's springs (mdp_spring_*, csrc/spring.hip) on in the context its steps run on for the length of each run.
 
    fix ID GROUP spring/mdp tether K x y z R0 [vel vx vy vz]
@@ -23,30 +23,21 @@ FixStyle(spring/mdp,FixSpringMDP);
 #ifndef MDP_FIX_SPRING_MDP_H
 #define MDP_FIX_SPRING_MDP_H
 
-#include "fix.h"
-
-#include "mdpair_hip.h"
+#include "fix_rider_mdp.h"
 
 namespace LAMMPS_NS {
 
-class FixSpringMDP : public Fix {
+class FixSpringMDP : public FixRiderMDP {
  public:
   FixSpringMDP(class LAMMPS *, int, char **);
-  int setmask() override;
   void init() override;
   double compute_scalar() override;
   double compute_vector(int) override;
 
  private:
   mdp_spring_config cfg;
-  int slot = 0;                  // this fix's position among the spring/mdp fixes of Modify's list, as of the last init()
-  double last[5] = {0.0, 0.0, 0.0, 0.0, 0.0}; // energy and ftotal of the last read (kept between runs)
-  bigint read_step = -1;         // the timestep `last` was read at in this run (-1: not yet)
-  class Fix *integrator() const; // the fix nve/mdp of this run (looked up anew: no pointer outlives either fix)
-  void inside(class Fix *nve);   // refuses atoms of the group that the integrator does not move
-  void read();                   // mdp_spring_state of this fix's slot into `last`
+  double last[MDP_SPRING_STATE_LEN] = {}; // energy and ftotal of the last read (kept between runs), and the words behind them
   double number(const char *what, const char *s); // a finite number, or the refusal (a variable named as such)
-  void too_many(int n);          // refuses spring/mdp fix number n > MDP_SPRING_MAX
 };
 
 }    // namespace LAMMPS_NS
