@@ -247,7 +247,8 @@ __device__ __forceinline__ double gspline(const double *cb, const double *cg, do
 // ------------------------------------------------------------------------------------------------
 // per-slot LDS record of a centre's neighbour: dx dy dz r w dw C p 1/r V_A   (d = x_c - x_m)
 constexpr int kRec = 10;
-// the fast kernels need neither p nor V_A in LDS: dx dy dz r w dw C 1/r
+// the fast kernels need neither p nor V_A in LDS: dx dy dz r w dw C 1/r (phase A leaves rsq where r goes; after the
+// forces the first three doubles carry the slot force to the lanes that sum the centre's own share)
 constexpr int kRecF = 9, kInvF = 7; // stride 9 doubles: 16 lanes reading 16 records touch 16 distinct bank pairs
 
 struct CentreOut {
@@ -329,9 +330,12 @@ __device__ __forceinline__ void pair_tab_fill(const RebomosDev &P, double *tab /
 }
 
 // shared epilogue of a slot: radial terms (pair_rebomos.cpp:411-441, 683-725), store, tallies
+// tally: some energy or virial is asked for in this compute (a kernel argument, so a scalar branch).  On the other steps
+// the pair energy, its half in the slot record (zero then: the gather adds it to a sum that is stored only with the
+// per-atom energy) and the seven sums of the centre are not computed.
 template <class PP>
 __device__ __forceinline__ void finish_slot(const PP &pp, const int je_m, const int off,
-                                            const double dp, const bool owned, const int eflag, const double mx,
+                                            const double dp, const bool owned, const bool tally, const double mx,
                                             const double my, const double mz, const double mr, const double mw,
                                             const double mdw, const double mp, const double mrinv, const double mVA,
                                             double &fx, double &fy, double &fz, const double acc1, const double Csum,
@@ -353,7 +357,7 @@ __device__ __forceinline__ void finish_slot(const PP &pp, const int je_m, const 
     double dVA = -beta * mVA;
     dVA += mVA * swl;
     radial += 0.5 * (dVR + mp * dVA);
-    ehalf = 0.5 * (VR + mp * mVA);
+    if (tally) ehalf = 0.5 * (VR + mp * mVA);
   }
   fx += radial * ux;
   fy += radial * uy;
@@ -364,7 +368,7 @@ __device__ __forceinline__ void finish_slot(const PP &pp, const int je_m, const 
   const int tslot = je_m & 0x3FFFFFFF;
   eh = 0.5 * ehalf;
   reinterpret_cast<double4 *>(fnbr)[off + tslot] = make_double4(fx, fy, fz, eh);
-  if (owned) {
+  if (tally && owned) {
     o.e_acc += ehalf;
     // virial of the cluster: sum_m (x_m - x_c) (x) F_m = -sum_m d_m (x) F_m
     o.v0 -= mx * fx;
@@ -376,33 +380,55 @@ __device__ __forceinline__ void finish_slot(const PP &pp, const int je_m, const 
   }
 }
 
+// Energy and virial of the block's centres: seven sums over all its lanes, added to one of MDP_ACC_SLOTS slots (by
+// block) so that a million waves do not queue on seven addresses; acc_reduce_kernel folds the slots afterwards.
+// One reduction for the seven together instead of a 64-lane butterfly each: the lanes of a wave lay their values down in
+// wscr (kTallyScr doubles of LDS that belong to this wave alone and hold nothing it still reads), lane l adds the
+// values of eight lanes for sum number l % 8, three butterfly steps over the lane blocks finish the wave's sums in
+// lanes 0..6, and the first wave adds those of the NW waves and issues one atomic instruction for the block.
+// Every thread of the block has to arrive (one __syncthreads, on tallying steps only).
+constexpr int kTallyRow = 65; // 64 lanes + 1: the eight sums a wave reads at once start in different banks
+constexpr int kTallyScr = 7 * kTallyRow;
+template <int NW>
 __device__ __forceinline__ void centre_tally(const CentreOut &o, double *__restrict__ acc, const int eflag,
-                                             const int vflag)
+                                             const int vflag, double *wscr)
 {
-  // partial sums go to one of MDP_ACC_SLOTS slots (by block) so that a million waves do not queue
-  // on seven addresses; acc_reduce_kernel folds the slots afterwards
-  const int lane = threadIdx.x & 63;
-  double *slot = acc + MDP_ACC_STRIDE * (1 + (blockIdx.x & (MDP_ACC_SLOTS - 1)));
-  if (eflag & MDP_EFLAG_GLOBAL) {
-    const double e = group_sum<64>(o.e_acc);
-    if (lane == 0) atomicAdd(&slot[0], e);
+  const bool eg = (eflag & MDP_EFLAG_GLOBAL) != 0, vg = (vflag & MDP_VFLAG_GLOBAL) != 0;
+  if (!eg && !vg) return;
+  __shared__ double s_red[NW * 8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  wave_lds_fence();
+  wscr[0 * kTallyRow + lane] = o.e_acc;
+  wscr[1 * kTallyRow + lane] = o.v0;
+  wscr[2 * kTallyRow + lane] = o.v1;
+  wscr[3 * kTallyRow + lane] = o.v2;
+  wscr[4 * kTallyRow + lane] = o.v3;
+  wscr[5 * kTallyRow + lane] = o.v4;
+  wscr[6 * kTallyRow + lane] = o.v5;
+  wave_lds_fence();
+  const int k = lane & 7;
+  double v = 0.0;
+  if (k < 7) {
+    const double *p = wscr + k * kTallyRow + (lane & ~7);
+    v = p[0];
+#pragma unroll
+    for (int j = 1; j < 8; j++) v += p[j];
   }
-  if (vflag & MDP_VFLAG_GLOBAL) {
-    const double v0 = group_sum<64>(o.v0), v1 = group_sum<64>(o.v1), v2 = group_sum<64>(o.v2);
-    const double v3 = group_sum<64>(o.v3), v4 = group_sum<64>(o.v4), v5 = group_sum<64>(o.v5);
-    if (lane == 0) {
-      atomicAdd(&slot[1], v0);
-      atomicAdd(&slot[2], v1);
-      atomicAdd(&slot[3], v2);
-      atomicAdd(&slot[4], v3);
-      atomicAdd(&slot[5], v4);
-      atomicAdd(&slot[6], v5);
-    }
+#pragma unroll
+  for (int x = 8; x < 64; x <<= 1) v += __shfl_xor(v, x, 64);
+  if (lane < 8) s_red[wave * 8 + lane] = v;
+  __syncthreads();
+  if (wave == 0 && lane < 7) {
+    double t = s_red[lane];
+#pragma unroll
+    for (int w = 1; w < NW; w++) t += s_red[w * 8 + lane];
+    double *slot = acc + MDP_ACC_STRIDE * (1 + (blockIdx.x & (MDP_ACC_SLOTS - 1)));
+    if (lane == 0 ? eg : vg) atomicAdd(&slot[lane], t);
   }
 }
 
 // phase A for one candidate: distance test against rcmax (pair_rebomos.cpp:337), ballot compaction into
-// the centre's LDS slots in candidate order.  Returns nothing; updates n / active / nsum.
+// the centre's LDS slots in candidate order.  Returns nothing; updates n / active (and nsum, REC == kRec only).
 // A candidate a hair outside rcmax (rsq within 1e-14 relative) gets an explicit ZERO slot record.  The gather of an
 // owned atom next to a periodic image of a centre reads the slot the centre ITSELF keeps for the atom's image
 // (rev_kernel: image centres are not computed at all), and decides with its own distance test, whose operands are
@@ -429,7 +455,19 @@ __device__ __forceinline__ void centre_take(const PP &pp, const double4 xc, cons
   const unsigned long long bal = __ballot(pred);
   const unsigned long long gb = (bal >> glane0) & gmask;
   const int pos = n + __popcll(gb & ((1ull << s) - 1ull));
-  if (pred && pos < CAP) {
+  if constexpr (REC == kRecF) {
+    // The fast kernels: only dx dy dz rsq here, where about half the lanes of a chunk hold a neighbour and every chunk
+    // is a pass of its own.  1/r, r, w and dw follow once per neighbour, by the lane that owns it, with the whole group
+    // active (centre_slot_geometry); the number of neighbours N is summed there too.
+    if (pred && pos < CAP) {
+      double *q = rec + pos * REC;
+      q[0] = dx;
+      q[1] = dy;
+      q[2] = dz;
+      q[3] = rsq;
+      je[pos] = t | (tj << 30);
+    }
+  } else if (pred && pos < CAP) {
     const double rinv = rsqrt_nr(rsq); // r and 1/r from one reciprocal square root
     const double r = rsq * rinv;
     double dw;
@@ -589,38 +627,53 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
   // in SGPR pairs through both pair loops, which need every SGPR for the polynomial and series coefficients.)
   int c_own = (have && c < nlocal && !outgrown) ? c : -1;
   asm("" : "+v"(c_own));
-  const double Ntot = group_sum_any<G>(nsum, s, lane);
+  wave_lds_fence();
+  // -- every neighbour once, by the lane that owns its slot from here on: 1/r, r and the switching function from the
+  //    dx dy dz rsq that phase A left in the record; r, w, dw, 1/r go back into it for the partners of the pair loops.
+  //    N = nM + nS is the sum of w over the slots (pair_rebomos.cpp:339-342; only their sum is ever used, :628, h:175).
+  const int m = s;
+  const bool act = m < n;
+  double mx = 0, my = 0, mz = 0, mr = 1, mw = 0, mdw = 0, mri = 1;
+  if (act) {
+    double *q = rec + m * kRecF;
+    const PairPar pp = pair_par(P, tc);
+    const int tm = ((unsigned) je[m]) >> 30;
+    mx = q[0];
+    my = q[1];
+    mz = q[2];
+    const double rsq = q[3];
+    mri = rsqrt_nr(rsq); // r and 1/r from one reciprocal square root
+    mr = rsq * mri;
+    mw = sp_switch(mr, pp.rmin(tm), pp.rinv(tm), mdw);
+    q[3] = mr;
+    q[4] = mw;
+    q[5] = mdw;
+    q[kInvF] = mri;
+  }
+  const double Ntot = group_sum_any<G>(mw, s, lane);
   wave_lds_fence();
 
   // centre-element constants
   double cb[7], cg[7];
+  // (indexed with a copy of tc that the compiler cannot see through, as pair_par_here does: hoisted above the switching
+  //  function of the pass above, the coefficients lose their scalar registers there and ride through both pair loops in
+  //  40 VGPRs -- 166 instead of 128 for 12-lane groups)
+  int tcc = tc;
+  asm volatile("; centre constants from here" : "+s"(tcc));
 #pragma unroll
   for (int k = 0; k < 7; k++) {
-    cb[k] = P.b[tc][k];
-    cg[k] = P.bg[tc][k];
+    cb[k] = P.b[tcc][k];
+    cg[k] = P.bg[tcc][k];
   }
   // P(N) and dP/dN, pair_rebomos.h:173-179
-  const double ea = exp(-P.a[tc][2] * Ntot);
-  const double dp = -P.a[tc][0] + P.a[tc][1] * P.a[tc][2] * ea;
-  const double PS = -P.a[tc][0] * (Ntot - 1.0) - P.a[tc][1] * ea + P.a[tc][3];
+  const double ea = exp(-P.a[tcc][2] * Ntot);
+  const double dp = -P.a[tcc][0] + P.a[tcc][1] * P.a[tcc][2] * ea;
+  const double PS = -P.a[tcc][0] * (Ntot - 1.0) - P.a[tcc][1] * ea + P.a[tcc][3];
 
   const SeriesLead lead = series_lead();
   const int nw = wave_max_int(n);
   CentreOut o = {0, 0, 0, 0, 0, 0, 0};
 
-  const int m = s;
-  const bool act = m < n;
-  double mx = 0, my = 0, mz = 0, mr = 1, mw = 0, mdw = 0, mri = 1;
-  if (act) {
-    const double *q = rec + m * kRecF;
-    mx = q[0];
-    my = q[1];
-    mz = q[2];
-    mr = q[3];
-    mw = q[4];
-    mdw = q[5];
-    mri = q[kInvF];
-  }
   const double ux = mx * mri, uy = my * mri, uz = mz * mri;
   // -- every unordered pair (m,q) ONCE: circulant enumeration q = (m+d) mod n, d = 1..n/2 (for even n
   //    the distance-n/2 pairs are taken by the lower half of the lanes).  The lane of m evaluates G, G' and
@@ -798,15 +851,45 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
     }
   }
   double eh = 0.0;
+  const bool tally = (eflag | vflag) != 0;
   if (act)
-    finish_slot(pair_par(P, tc), je[m], off, dp, c_own >= 0, eflag, mx, my, mz, mr, mw, mdw, mp, mri, mVA, fx, fy, fz,
+    finish_slot(pair_par(P, tc), je[m], off, dp, c_own >= 0, tally, mx, my, mz, mr, mw, mdw, mp, mri, mVA, fx, fy, fz,
                 acc1, Csum, fnbr, eh, o);
   // the centre's own share: minus the sum of its slot forces, plus the centre halves of the pair energies.
   // Written once here so that the gather only has to follow the reverse slots.
-  const double ox = group_sum_any<G>(act ? fx : 0.0, s, lane), oy = group_sum_any<G>(act ? fy : 0.0, s, lane), oz = group_sum_any<G>(act ? fz : 0.0, s, lane);
+  // Nobody but the lane that stores a component reads its sum, so there is no shuffle tree and no broadcast: every lane
+  // lays its slot force down in the first three doubles of its own record (dead by now; zero for a lane without a
+  // neighbour), and lanes 0, 1, 2 of the group add the G values of x, y, z -- in the association of group_sum_any's
+  // tree (offsets 8, 4, 2, 1 towards lane 0, which is also what lane 0 of the xor butterfly of a power-of-two group
+  // holds), so the sums are bit for bit what the trees gave.  Lane 3 stores the energy share.
   const double oe = (eflag & MDP_EFLAG_ATOM) ? group_sum_any<G>(eh, s, lane) : 0.0;
-  if (c_own >= 0 && s == 0) reinterpret_cast<double4 *>(fown)[c_own] = make_double4(-ox, -oy, -oz, oe);
-  centre_tally(o, acc, eflag, vflag);
+  if constexpr (G <= 16) {
+    if (kAllLanes || lane_again < C::GPW * G) {
+      double *q = rec + m * kRecF;
+      q[0] = fx;
+      q[1] = fy;
+      q[2] = fz;
+    }
+    wave_lds_fence();
+    if (c_own >= 0 && s < 4) {
+      const double *q = rec + (s < 3 ? s : 0);
+      double t[G];
+#pragma unroll
+      for (int i = 0; i < G; i++) t[i] = q[i * kRecF];
+#pragma unroll
+      for (int o2 = 8; o2 > 0; o2 >>= 1) {
+#pragma unroll
+        for (int i = 0; i < o2; i++)
+          if (i + o2 < G) t[i] += t[i + o2];
+      }
+      fown[4 * (size_t) c_own + s] = s < 3 ? -t[0] : oe;
+    }
+  } else { // (32-lane groups, one wave per SIMD by their LDS: the butterflies as they were)
+    const double ox = group_sum<G>(fx), oy = group_sum<G>(fy), oz = group_sum<G>(fz);
+    if (c_own >= 0 && s == 0) reinterpret_cast<double4 *>(fown)[c_own] = make_double4(-ox, -oy, -oz, oe);
+  }
+  centre_tally<C::WPB>(o, acc, eflag, vflag, s_mat + (size_t) (tid >> 6) * (C::GPW * C::MSTRIDE));
+  static_assert(C::GPW * C::MSTRIDE >= kTallyScr, "centre_tally borrows the wave's part of the pair matrix");
 }
 
 // ---- centres with at most three neighbours: ONE LANE per centre ------------------------------------------
@@ -985,12 +1068,13 @@ __global__ __launch_bounds__(kC3Block) void rebo_centre3_kernel(
   }
   CentreOut o = {0, 0, 0, 0, 0, 0, 0};
   const bool owned = have && c < nlocal;
+  const bool tally = (eflag | vflag) != 0;
   double ox = 0.0, oy = 0.0, oz = 0.0, oe = 0.0;
 #pragma unroll
   for (int k = 0; k < 3; k++) {
     if (!act[k]) continue;
     double eh = 0.0;
-    finish_slot(pp_vr, ts[k] | (tj[k] << 30), off, dp, owned, eflag, dx[k], dy[k], dz[k], r[k], w[k], dw[k], p[k], ri[k],
+    finish_slot(pp_vr, ts[k] | (tj[k] << 30), off, dp, owned, tally, dx[k], dy[k], dz[k], r[k], w[k], dw[k], p[k], ri[k],
                 VA[k], fx[k], fy[k], fz[k], a1[k], Csum, fnbr, eh, o);
     ox += fx[k];
     oy += fy[k];
@@ -1000,7 +1084,8 @@ __global__ __launch_bounds__(kC3Block) void rebo_centre3_kernel(
   // the centre's own share: minus the sum of its slot forces, plus the centre halves of the pair energies
   if (owned && !outgrown)
     reinterpret_cast<double4 *>(fown)[c] = make_double4(-ox, -oy, -oz, (eflag & MDP_EFLAG_ATOM) ? oe : 0.0);
-  centre_tally(o, acc, eflag, vflag);
+  __shared__ double s_tally[(kC3Block / 64) * kTallyScr];
+  centre_tally<kC3Block / 64>(o, acc, eflag, vflag, s_tally + (threadIdx.x >> 6) * kTallyScr);
 }
 
 // ---- general centre kernel: 32 lanes per centre, up to 64 neighbours, no pair matrix ------------------
@@ -1038,6 +1123,7 @@ __global__ __launch_bounds__(256) void rebo_centre_general_kernel(
   double *rec = s_rec + (size_t) grp_in_block * STRIDE;
   int *je = s_je + grp_in_block * CAP;
   CentreOut o = {0, 0, 0, 0, 0, 0, 0};
+  const bool tally = (eflag | vflag) != 0;
   // wave-uniform trip count: both groups of a wave iterate together
   for (long long g0 = (long long) blockIdx.x * 8; g0 < ncent; g0 += (long long) gridDim.x * 8) {
     const long long gid = g0 + grp_in_block;
@@ -1186,7 +1272,7 @@ __global__ __launch_bounds__(256) void rebo_centre_general_kernel(
       }
       if (act) {
         double eh = 0.0;
-        finish_slot(pp, je[m], off, dp, owned, eflag, mx, my, mz, mr, mw, mdw, mp, mri, mVA, fx, fy, fz, acc1, Csum,
+        finish_slot(pp, je[m], off, dp, owned, tally, mx, my, mz, mr, mw, mdw, mp, mri, mVA, fx, fy, fz, acc1, Csum,
                     fnbr, eh, o);
         ox += fx;
         oy += fy;
@@ -1236,7 +1322,8 @@ __global__ __launch_bounds__(256) void rebo_centre_general_kernel(
     if (owned && s == 0) reinterpret_cast<double4 *>(fown)[c] = make_double4(-ox, -oy, -oz, oe);
     wave_lds_fence();
   }
-  centre_tally(o, acc, eflag, vflag);
+  static_assert(2 * STRIDE >= kTallyScr, "centre_tally borrows the records of the wave's two groups");
+  centre_tally<4>(o, acc, eflag, vflag, s_rec + (size_t) (tid >> 6) * (2 * STRIDE));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1427,16 +1514,23 @@ __device__ __forceinline__ unsigned long long lj_pair_fast(const LJPar &q, const
   fy += dy * fpair;
   fz += dz * fpair;
   if (EV) {
+    // Both directions of every pair are visited, so a pair counts half here: the caller halves e and v0..v5 ONCE, after
+    // its loops.  The six products share dx*fpair, dy*fpair, dz*fpair: three multiplies and six FMAs.
     const double v12 = r6inv * (q.c3 * r6inv - q.c4);
-    e += inwin ? 0.5 * v12 : 0.0;
+    e += inwin ? v12 : 0.0;
     if (vflag) {
-      const double h = 0.5 * fpair;
-      v0 += dx * dx * h;
-      v1 += dy * dy * h;
-      v2 += dz * dz * h;
-      v3 += dx * dy * h;
-      v4 += dx * dz * h;
-      v5 += dy * dz * h;
+      // (from a copy of fpair the compiler cannot see through: merged with the products of the three force FMAs above,
+      //  those would become a multiply and an add, and the forces of a tallying step would differ from a force-only
+      //  step's in the last bit)
+      double fp = fpair;
+      asm("" : "+v"(fp));
+      const double tx = dx * fp, ty = dy * fp, tz = dz * fp;
+      v0 += dx * tx;
+      v3 += dy * tx;
+      v4 += dz * tx;
+      v1 += dy * ty;
+      v5 += dz * ty;
+      v2 += dz * tz;
     }
   }
   return mcub; // the lanes of THIS call whose pair sits on the cubic inner spline (a wave-level value)
@@ -2105,6 +2199,16 @@ __global__ __launch_bounds__(256, WAVES) void rebo_lj_tile_kernel(
       if (qn[c]) cq_cnt[((size_t) t * MDP_TILE + tid / L) * CL + c] = qn[c];
   }
 
+  if (EV) { // the halves that lj_pair_fast leaves to its caller (exact: the sums are what sums of halves would be)
+#pragma unroll
+    for (int c = 0; c < CL; c++) ee[c] *= 0.5;
+    v0 *= 0.5;
+    v1 *= 0.5;
+    v2 *= 0.5;
+    v3 *= 0.5;
+    v4 *= 0.5;
+    v5 *= 0.5;
+  }
   double e_lj = 0.0;
 #pragma unroll
   for (int c = 0; c < CL; c++) e_lj += real[c] ? ee[c] : 0.0;
@@ -3341,6 +3445,8 @@ static int launch_lj(mdp_ctx *c, int klass, bool gather, int eflag, int vflag, b
         const bool small = !(klass & 1);
         const int capL = ((small ? c->tile_small : c->tile_maxu) + 1 + 7) & ~7;
         // the force-only variants fit 5 waves per SIMD (<= 102 VGPRs); with small unions LDS allows 5 workgroups too
+        // (the tallying variant of two-atom rows needs 118 VGPRs: under the 5-wave bound it keeps 96 and spills 34 to
+        //  124 B of scratch inside the segment loops, so it stays at 4 -- DESIGN.md section 4 item 41)
         constexpr int W = EV ? 4 : 5;
         // (the queue variant: decided once per compute, mdp_rebomos_run_end)
         const auto kernel = c->cluster == 1     ? rebo_lj_tile_kernel<EV, G, W, 1, false>
