@@ -12,100 +12,78 @@
 // wait: a run is bitwise reproducible.
 // Several baths (mdp_langevin_baths, nbath > 1): bath k acts on the atoms of its group bit with its own table, target,
 // seed, mean and tally.  The kernels read the mask once, pick the bath index by compare/select and take everything else
-// from that index; the block sums carry MDP_LANGEVIN_MAXBATH slots, one per bath.  One bath is the thermostat above.
+// from that index; the block sums carry one slot per bath.
+// One code path serves both: every kernel, the argument struct (MdpLgvArgs) and mdp_lgv_open / _close are templates on the
+// slot count NB, instantiated for 1 and for MDP_LANGEVIN_MAXBATH.  With NB = 1 the bath index is the constant 0, so the
+// mask is not read for it and the selects fold away: one bath costs what it cost before there were several.
 #include "mdp_common.h"
 
 #include <cmath>
 
 namespace {
 
-// zero yes: part[3 b + k] = the sum over block b of the random parts fran_k of the step (mdp_lgv_random)
-// MASK: of the Langevin group's atoms alone (MdpGroupArgs); the others add 0 and still reach the block sum
-template <bool MASK>
-__global__ __launch_bounds__(256) void lgv_zero_kernel(const int n, const MdpLgvArgs L, double *__restrict__ part,
+constexpr int kB = MDP_LANGEVIN_MAXBATH;
+
+// zero yes: part[3 (NB b + k) + j] = the sum over block b of the random parts fran_j of bath k's atoms (mdp_lgv_random)
+// MASK: of the baths' atoms alone (MdpGroupArgs); the others add 0 and still reach the block sum.  Several baths always
+// come with a mask
+template <int NB, bool MASK>
+__global__ __launch_bounds__(256) void lgv_zero_kernel(const int n, const MdpLgvArgs<NB> L, double *__restrict__ part,
                                                        const MdpGroupArgs M)
 {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  double r[3] = {0.0, 0.0, 0.0};
-  bool in = i < n;
-  if constexpr (MASK)
-    if (in) in = mdp_group_lgv(M, mdp_group_mask(M, i));
-  if (in) mdp_lgv_random(L, i, r[0], r[1], r[2]);
-  mdp_block_sum_256<3>(r, part);
-}
-
-// zero yes: st[kLgvMean + k] = (sum of the random parts) / natoms; the three components in one pass over the slots
-__global__ __launch_bounds__(256) void lgv_mean_kernel(const double *__restrict__ part, const int npart,
-                                                       const double natoms, double *__restrict__ st)
-{
-  double s[3];
-  mdp_slot_sum_256<3>(part, npart, s);
-  if (threadIdx.x < 3) st[kLgvMean + threadIdx.x] = (threadIdx.x == 0 ? s[0] : (threadIdx.x == 1 ? s[1] : s[2])) / natoms;
-}
-
-// tally yes: E = the fixed-order sum of the partials of f_L . v; the setup force starts the energy of the run at
-// 0.5 E dt (FixLangevin::compute_scalar at beginstep), a step adds E dt (end_of_step)
-__global__ __launch_bounds__(256) void lgv_tally_kernel(const double *__restrict__ part, const int npart, const double dt,
-                                                        const int setup, double *__restrict__ st)
-{
-  double e;
-  mdp_slot_sum_256<1>(part, npart, &e);
-  if (threadIdx.x == 0) {
-    st[kLgvE] = setup ? 0.5 * e * dt : st[kLgvE] + e * dt;
-    st[kLgvElast] = e;
-  }
-}
-
-// several baths, zero yes: part[3 (MAXBATH b + k) + j] = the sum over block b of the random parts fran_j of bath k's atoms
-constexpr int kB = MDP_LANGEVIN_MAXBATH;
-__global__ __launch_bounds__(256) void lgv_zero_baths_kernel(const int n, const MdpLgvBathArgs B, double *__restrict__ part,
-                                                             const MdpGroupArgs M)
-{
+  static_assert(MASK || NB == 1, "several baths are told apart by the mask");
   const int i = blockIdx.x * 256 + threadIdx.x;
   bool in = i < n;
   int k = 0;
-  if (in) {
-    const int m = mdp_group_mask(M, i);
-    in = mdp_group_lgv(M, m);
-    k = mdp_lgv_bath(B, m);
-  }
+  if constexpr (MASK)
+    if (in) {
+      const int m = mdp_group_mask(M, i);
+      in = mdp_group_lgv(M, m);
+      k = mdp_lgv_bath(L, m);
+    }
   double rx = 0.0, ry = 0.0, rz = 0.0;
-  if (in) mdp_lgv_random(B, i, k, rx, ry, rz);
-  double r[3 * kB];
+  if (in) mdp_lgv_random(L, i, k, rx, ry, rz);
+  double r[3 * NB];
 #pragma unroll
-  for (int b = 0; b < kB; b++) {
+  for (int b = 0; b < NB; b++) {
     r[3 * b] = k == b ? rx : 0.0;
     r[3 * b + 1] = k == b ? ry : 0.0;
     r[3 * b + 2] = k == b ? rz : 0.0;
   }
-  mdp_block_sum_256<3 * kB>(r, part);
+  mdp_block_sum_256<3 * NB>(r, part);
 }
 
+// what the two one-workgroup kernels below need of every bath (the slots beyond nbath have neither zero nor tally)
 struct LgvBathSums {
   double natoms[kB] = {1.0, 1.0, 1.0, 1.0};
   int zero[kB] = {0, 0, 0, 0}, tally[kB] = {0, 0, 0, 0};
 };
 
-// ... the mean of every zero yes bath over ITS natoms; the mean words of the other baths stay 0
-__global__ __launch_bounds__(256) void lgv_mean_baths_kernel(const double *__restrict__ part, const int npart, const LgvBathSums S,
-                                                             double *__restrict__ st)
+// zero yes: the mean of every zero yes bath, (the sum of its random parts) / ITS natoms, all components in one pass over
+// the slots; the mean words of the other baths stay 0
+template <int NB>
+__global__ __launch_bounds__(256) void lgv_mean_kernel(const double *__restrict__ part, const int npart, const LgvBathSums S,
+                                                       double *__restrict__ st)
 {
-  double s[3 * kB];
-  mdp_slot_sum_256<3 * kB>(part, npart, s);
+  double s[3 * NB];
+  mdp_slot_sum_256<3 * NB>(part, npart, s);
 #pragma unroll
-  for (int k = 0; k < 3 * kB; k++)
+  for (int k = 0; k < 3 * NB; k++)
     if ((int) threadIdx.x == k && S.zero[k / 3]) st[(k / 3) * kLgvWords + kLgvMean + k % 3] = s[k] / S.natoms[k / 3];
 }
 
-// ... tally yes: as lgv_tally_kernel for every bath that has a tally, from its slot of the partials
-__global__ __launch_bounds__(256) void lgv_tally_baths_kernel(const double *__restrict__ part, const int npart, const double dt,
-                                                              const int setup, const LgvBathSums S, double *__restrict__ st)
+// tally yes, for every bath that has a tally, from its slot of the partials: E = the fixed-order sum of the partials of
+// f_L . v; the setup force starts the energy of the run at 0.5 E dt (FixLangevin::compute_scalar at beginstep), a step
+// adds E dt (end_of_step)
+template <int NB>
+__global__ __launch_bounds__(256) void lgv_tally_kernel(const double *__restrict__ part, const int npart, const double dt,
+                                                        const int setup, const LgvBathSums S, double *__restrict__ st)
 {
-  double e[kB];
-  mdp_slot_sum_256<kB>(part, npart, e);
+  double e[NB];
+  mdp_slot_sum_256<NB>(part, npart, e);
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int k = 0; k < kB; k++)
+    for (int k = 0; k < NB; k++)
       if (S.tally[k]) {
         double *b = st + k * kLgvWords;
         b[kLgvE] = setup ? 0.5 * e[k] * dt : b[kLgvE] + e[k] * dt;
@@ -139,8 +117,8 @@ int lgv_tables(mdp_ctx *c)
   const MdpStep s = mdp_step(c);
   const double dt = s.dt, ftm2v = s.ftm2v, *mass = s.mass;
   if (h.tab_dt == dt && h.tab_ftm2v == ftm2v) return MDP_OK;
-  for (int k = 0; k < (h.nbath > 1 ? h.nbath : 1); k++) {
-    const mdp_langevin_config &g = h.nbath > 1 ? h.bcfg[k] : h.cfg;
+  for (int k = 0; k < h.nbath; k++) {
+    const mdp_langevin_config &g = h.cfg[k];
     double tab[2 * 16] = {};
     for (int t = 1; t < 16; t++) {
       const double m = mass[t] > 0.0 ? mass[t] : 0.0;
@@ -160,9 +138,9 @@ LgvBathSums lgv_bath_sums(const MdpLangevin &h)
 {
   LgvBathSums S;
   for (int k = 0; k < h.nbath; k++) {
-    S.natoms[k] = (double) h.bcfg[k].natoms;
-    S.zero[k] = h.bcfg[k].zero ? 1 : 0;
-    S.tally[k] = h.bcfg[k].tally ? 1 : 0;
+    S.natoms[k] = (double) h.cfg[k].natoms;
+    S.zero[k] = h.cfg[k].zero ? 1 : 0;
+    S.tally[k] = h.cfg[k].tally ? 1 : 0;
   }
   return S;
 }
@@ -198,6 +176,21 @@ int lgv_check_config(mdp_ctx *c, const char *who, const mdp_langevin_config *cfg
   return MDP_OK;
 }
 
+// the energy a bath has taken out of its atoms up to the last full step, from its two words (0 without tally yes)
+int lgv_read_tally(mdp_ctx *c, int bath, double *out)
+{
+  if (!c->lgv.cfg[bath].tally) {
+    *out = 0.0;
+    return MDP_OK;
+  }
+  MDP_HIP(c, hipSetDevice(c->device));
+  MDP_TRY(mdp_md_flush_final(c)); // (the energy of the finished step)
+  double e[2];
+  MDP_TRY(mdp_read_one(c, c->lgv.st.p + bath * kLgvWords + kLgvE, sizeof e, e));
+  *out = -(e[0] - 0.5 * e[1] * mdp_step(c).dt); // FixLangevin::compute_scalar: back from mid-step to the last full step
+  return MDP_OK;
+}
+
 } // namespace
 
 int mdp_lgv_check_disjoint(mdp_ctx *c, const char *who)
@@ -205,7 +198,7 @@ int mdp_lgv_check_disjoint(mdp_ctx *c, const char *who)
   MdpLangevin &h = c->lgv;
   if (h.disjoint_checked) return MDP_OK;
   int count = 0;
-  MDP_TRY(lgv_count_overlap(c, h.nbath, h.bbit, &count));
+  MDP_TRY(lgv_count_overlap(c, h.nbath, h.bit, &count));
   if (count)
     return mdp_fail(c, MDP_ESTATE, "%s: %d atoms are in more than one of the %d Langevin baths (mdp_langevin_baths); the groups of the baths must be disjoint",
                     who, count, h.nbath);
@@ -213,10 +206,7 @@ int mdp_lgv_check_disjoint(mdp_ctx *c, const char *who)
   return MDP_OK;
 }
 
-// mdp_lgv_open / mdp_lgv_close for several baths.  The bookkeeping -- which calls apply a force, the setup force and its
-// phase, the step counter, the layout of the partials -- is mdp_lgv_open's line for line and must stay so: a change to
-// either goes into both (the one-bath pair keeps its own copy so that its kernels receive what they always received).
-int mdp_lgv_open_baths(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvBathArgs *B)
+template <int NB> int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvArgs<NB> *L)
 {
   MdpLangevin &h = c->lgv;
   const int n = c->nlocal;
@@ -225,76 +215,30 @@ int mdp_lgv_open_baths(mdp_ctx *c, bool with_final, bool initial, bool *apply, M
   if (*apply) {
     MDP_TRY(lgv_tables(c));
     const int nb = nblk(n);
-    MDP_HIP(c, h.part.reserve((size_t) 4 * kB * nb + 4 * kB));
-    B->tag = c->tag.p;
-    B->type = c->type.p;
-    B->perm = !c->md && c->host_sort ? c->host_perm.p : nullptr; // host mode: tags and types are in the host's order
-    B->st = h.st.p;
-    for (int k = 0; k < h.nbath; k++) {
-      B->tsqrt[k] = sqrt(lgv_target(h, h.bcfg[k], h.step));
-      B->seed[k] = (unsigned) h.bcfg[k].seed;
-      B->bit[k] = h.bbit[k];
-    }
-    B->lo = (unsigned) (unsigned long long) h.step;
-    B->hi = (unsigned) ((unsigned long long) h.step >> 32);
-    B->phase = setup ? 1u : 0u;
-    B->zero = h.any_zero ? 1 : 0;
-    B->part = h.any_tally ? h.part.p + (size_t) 3 * kB * nb : nullptr;
-    if (h.any_zero) {
-      bool masked = false;
-      MdpGroupArgs M;
-      MDP_TRY(mdp_group_args(c, &masked, &M));
-      if (n) lgv_zero_baths_kernel<<<nb, 256, 0, c->stream>>>(n, *B, h.part.p, M);
-      lgv_mean_baths_kernel<<<1, 256, 0, c->stream>>>(h.part.p, n ? nb : 0, lgv_bath_sums(h), h.st.p);
-      MDP_HIP(c, hipGetLastError());
-    }
-  }
-  if (initial) {
-    h.need_setup = false;
-    h.step++;
-  }
-  return MDP_OK;
-}
-
-int mdp_lgv_close_baths(mdp_ctx *c, const MdpLgvBathArgs &B)
-{
-  if (!B.part) return MDP_OK;
-  lgv_tally_baths_kernel<<<1, 256, 0, c->stream>>>(B.part, c->nlocal ? nblk(c->nlocal) : 0, mdp_step(c).dt, B.phase == 1u ? 1 : 0,
-                                                   lgv_bath_sums(c->lgv), c->lgv.st.p);
-  MDP_HIP(c, hipGetLastError());
-  return MDP_OK;
-}
-
-int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvArgs *L)
-{
-  MdpLangevin &h = c->lgv;
-  const int n = c->nlocal;
-  const bool setup = initial && !with_final && h.need_setup;
-  *apply = !initial || with_final || setup;
-  if (*apply) {
-    MDP_TRY(lgv_tables(c));
-    const int nb = nblk(n);
-    MDP_HIP(c, h.part.reserve((size_t) 4 * nb + 4));
+    MDP_HIP(c, h.part.reserve((size_t) 4 * NB * nb + 4 * NB));
     L->tag = c->tag.p;
     L->type = c->type.p;
     L->perm = !c->md && c->host_sort ? c->host_perm.p : nullptr; // host mode: tags and types are in the host's order
     L->st = h.st.p;
-    L->tsqrt = sqrt(lgv_target(h, h.cfg, h.step));
-    L->seed = (unsigned) h.cfg.seed;
+    for (int k = 0; k < NB && k < h.nbath; k++) {
+      L->tsqrt[k] = sqrt(lgv_target(h, h.cfg[k], h.step));
+      L->seed[k] = (unsigned) h.cfg[k].seed;
+      if constexpr (NB > 1) L->bit[k] = h.bit[k];
+    }
     L->lo = (unsigned) (unsigned long long) h.step;
     L->hi = (unsigned) ((unsigned long long) h.step >> 32);
     L->phase = setup ? 1u : 0u;
-    L->mean = nullptr;
-    L->part = h.cfg.tally ? h.part.p + (size_t) 3 * nb : nullptr;
-    if (h.cfg.zero) {
+    L->mean = h.any_zero ? h.st.p + kLgvMean : nullptr;
+    L->part = h.any_tally ? h.part.p + (size_t) 3 * NB * nb : nullptr;
+    if (h.any_zero) {
       bool masked = false;
       MdpGroupArgs M;
       MDP_TRY(mdp_group_args(c, &masked, &M));
-      if (n && masked) lgv_zero_kernel<true><<<nb, 256, 0, c->stream>>>(n, *L, h.part.p, M);
-      else if (n) lgv_zero_kernel<false><<<nb, 256, 0, c->stream>>>(n, *L, h.part.p, M);
-      lgv_mean_kernel<<<1, 256, 0, c->stream>>>(h.part.p, n ? nb : 0, (double) h.cfg.natoms, h.st.p);
+      if (n && masked) lgv_zero_kernel<NB, true><<<nb, 256, 0, c->stream>>>(n, *L, h.part.p, M);
+      if constexpr (NB == 1) // (several baths always come with a mask: mdp_group_args)
+        if (n && !masked) lgv_zero_kernel<1, false><<<nb, 256, 0, c->stream>>>(n, *L, h.part.p, M);
+      lgv_mean_kernel<NB><<<1, 256, 0, c->stream>>>(h.part.p, n ? nb : 0, lgv_bath_sums(h), h.st.p);
       MDP_HIP(c, hipGetLastError());
-      L->mean = h.st.p + kLgvMean;
     }
   }
   if (initial) {
@@ -304,14 +248,19 @@ int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvA
   return MDP_OK;
 }
 
-int mdp_lgv_close(mdp_ctx *c, const MdpLgvArgs &L)
+template <int NB> int mdp_lgv_close(mdp_ctx *c, const MdpLgvArgs<NB> &L)
 {
   if (!L.part) return MDP_OK;
-  lgv_tally_kernel<<<1, 256, 0, c->stream>>>(L.part, c->nlocal ? nblk(c->nlocal) : 0, mdp_step(c).dt, L.phase == 1u ? 1 : 0,
-                                             c->lgv.st.p);
+  lgv_tally_kernel<NB><<<1, 256, 0, c->stream>>>(L.part, c->nlocal ? nblk(c->nlocal) : 0, mdp_step(c).dt, L.phase == 1u ? 1 : 0,
+                                                 lgv_bath_sums(c->lgv), c->lgv.st.p);
   MDP_HIP(c, hipGetLastError());
   return MDP_OK;
 }
+
+template int mdp_lgv_open<1>(mdp_ctx *, bool, bool, bool *, MdpLgvArgs<1> *);
+template int mdp_lgv_open<kB>(mdp_ctx *, bool, bool, bool *, MdpLgvArgs<kB> *);
+template int mdp_lgv_close<1>(mdp_ctx *, const MdpLgvArgs<1> &);
+template int mdp_lgv_close<kB>(mdp_ctx *, const MdpLgvArgs<kB> &);
 
 extern "C" {
 
@@ -328,8 +277,11 @@ int mdp_langevin_setup(mdp_ctx *c, const mdp_langevin_config *cfg)
   MDP_HIP(c, h.st.reserve(kLgvWords));
   double zero[kLgvWords] = {};
   MDP_TRY(mdp_write_small(c, h.st.p, zero, sizeof zero));
-  h.cfg = *cfg;
-  h.nbath = 0; // (one thermostat; mdp_langevin_baths sets what several need)
+  h.cfg[0] = *cfg; // one bath, on the group of mdp_langevin_group (mdp_langevin_baths sets what several need)
+  h.nbath = 1;
+  for (int k = 0; k < kB; k++) h.bit[k] = 0;
+  h.any_zero = cfg->zero;
+  h.any_tally = cfg->tally;
   h.tab_dt = h.tab_ftm2v = 0.0; // (the factors are computed by the first kernel that needs them)
   h.first = h.last = h.step = 0;
   h.need_setup = true;
@@ -378,9 +330,9 @@ int mdp_langevin_baths(mdp_ctx *c, int nbath, const mdp_langevin_config *cfg, co
   h.nbath = nbath;
   h.any_zero = h.any_tally = false;
   for (int k = 0; k < kB; k++) {
-    h.bbit[k] = k < nbath ? groupbit[k] : 0;
+    h.bit[k] = k < nbath ? groupbit[k] : 0;
     if (k < nbath) {
-      h.bcfg[k] = cfg[k];
+      h.cfg[k] = cfg[k];
       h.any_zero = h.any_zero || cfg[k].zero;
       h.any_tally = h.any_tally || cfg[k].tally;
     }
@@ -412,26 +364,16 @@ int mdp_langevin_run(mdp_ctx *c, long long first, long long last)
 int mdp_langevin_tally(mdp_ctx *c, double *out)
 {
   if (!c || !out) return MDP_EINVAL;
-  if (!c->lgv.on) return mdp_fail(c, MDP_ESTATE, "mdp_langevin_setup not called");
-  if (c->lgv.many()) { // the sum over the baths in bath order
-    double sum = 0.0;
-    for (int k = 0; k < c->lgv.nbath; k++) {
-      double e = 0.0;
-      MDP_TRY(mdp_langevin_tally_bath(c, k, &e));
-      sum += e;
-    }
-    *out = sum;
-    return MDP_OK;
+  const MdpLangevin &h = c->lgv;
+  if (!h.on) return mdp_fail(c, MDP_ESTATE, "mdp_langevin_setup not called");
+  if (h.nbath == 1) return lgv_read_tally(c, 0, out); // (as read: 0.0 + in front of it would lose the sign of a -0.0)
+  double sum = 0.0; // the sum over the baths in bath order
+  for (int k = 0; k < h.nbath; k++) {
+    double e = 0.0;
+    MDP_TRY(lgv_read_tally(c, k, &e));
+    sum += e;
   }
-  if (!c->lgv.cfg.tally) {
-    *out = 0.0;
-    return MDP_OK;
-  }
-  MDP_HIP(c, hipSetDevice(c->device));
-  MDP_TRY(mdp_md_flush_final(c)); // (the energy of the finished step)
-  double e[2];
-  MDP_TRY(mdp_read_one(c, c->lgv.st.p + kLgvE, sizeof e, e));
-  *out = -(e[0] - 0.5 * e[1] * mdp_step(c).dt); // FixLangevin::compute_scalar: back from mid-step to the last full step
+  *out = sum;
   return MDP_OK;
 }
 
@@ -440,19 +382,9 @@ int mdp_langevin_tally_bath(mdp_ctx *c, int bath, double *out)
   if (!c || !out) return MDP_EINVAL;
   const MdpLangevin &h = c->lgv;
   if (!h.on) return mdp_fail(c, MDP_ESTATE, "mdp_langevin_setup not called");
-  const int nbath = h.nbath > 1 ? h.nbath : 1;
-  if (bath < 0 || bath >= nbath) return mdp_fail(c, MDP_EINVAL, "mdp_langevin_tally_bath: bath index %d out of range (%d baths are on)", bath, nbath);
-  if (nbath == 1) return mdp_langevin_tally(c, out);
-  if (!h.bcfg[bath].tally) {
-    *out = 0.0;
-    return MDP_OK;
-  }
-  MDP_HIP(c, hipSetDevice(c->device));
-  MDP_TRY(mdp_md_flush_final(c)); // (the energy of the finished step)
-  double e[2];
-  MDP_TRY(mdp_read_one(c, h.st.p + bath * kLgvWords + kLgvE, sizeof e, e));
-  *out = -(e[0] - 0.5 * e[1] * mdp_step(c).dt);
-  return MDP_OK;
+  if (bath < 0 || bath >= h.nbath)
+    return mdp_fail(c, MDP_EINVAL, "mdp_langevin_tally_bath: bath index %d out of range (%d baths are on)", bath, h.nbath);
+  return lgv_read_tally(c, bath, out);
 }
 
 int mdp_langevin_off(mdp_ctx *c)

@@ -228,21 +228,21 @@ __global__ __launch_bounds__(256) void ang_select_kernel(const int nlocal, const
 // (SCALE = false) never read it, so their code is what it was without a thermostat.
 // LANGEVIN: this kernel is the first reader of the compute's forces and adds the Langevin force of the step (L,
 // langevin.hip) to them in registers, from the velocities it reads; L.part: the per-block sums of f_L . v for the tally
-// (v after the final half; with FINAL = false the setup force, and v as read).  LANGEVIN = 0 never reads L.
-// LANGEVIN = 2 (with MASK): several baths on disjoint groups (mdp_langevin_baths); L is then MdpLgvBathArgs, the bath of an
-// atom is picked from the mask word the kernel reads anyway, and the block sum carries one slot per bath.  The
-// instantiations with LANGEVIN 0 and 1 compile the code they had before there was a 2.
+// (v after the final half; with FINAL = false the setup force, and v as read).  LANGEVIN is the slot count of L: 0 never
+// reads L; 1 is one bath; MDP_LANGEVIN_MAXBATH (with MASK) is several baths on disjoint groups (mdp_langevin_baths): the
+// bath of an atom is picked from the mask word the kernel reads anyway, and the block sum carries one slot per bath.  With
+// one slot the bath is the constant 0 and the same lines compile to the code of one thermostat.
 template <bool FINAL, bool CHECK, bool SCALE, int LANGEVIN, bool MASK>
 __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const double *__restrict__ rmass,
                                    double *__restrict__ f, double *__restrict__ v, double4 *__restrict__ xq,
                                    const mdp_hold_t *__restrict__ xhold, const double trigsq, const double hardsq,
                                    int *__restrict__ flag, const MdpStyleCheck SC, const int zero_f,
                                    double *__restrict__ dflag_set, double *__restrict__ dflag_clear,
-                                   const double *__restrict__ vscale,
-                                   const std::conditional_t<LANGEVIN == 2, MdpLgvBathArgs, MdpLgvArgs> L, const MdpGroupArgs M)
+                                   const double *__restrict__ vscale, const MdpLgvArgs<LANGEVIN> L, const MdpGroupArgs M)
 {
+  static_assert(MASK || LANGEVIN <= 1, "several baths are told apart by the mask");
   double lgv_e = 0.0; // (LANGEVIN, tally: f_L . v of this atom)
-  [[maybe_unused]] int bath = 0; // (LANGEVIN == 2: the bath of this atom)
+  int bath = 0;       // (LANGEVIN: the bath of this atom; the constant 0 unless there are several)
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (CHECK && dflag_clear && i == 0) *dflag_clear = 0.0; // (the word of the next step; this step's was cleared a step ago)
   bool t = false, h = false;
@@ -267,7 +267,7 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
       const int m = mdp_group_mask(M, i);
       move = mdp_group_moves(M, m);
       lgv = LANGEVIN && mdp_group_lgv(M, m);
-      if constexpr (LANGEVIN == 2) bath = mdp_lgv_bath(L, m);
+      bath = mdp_lgv_bath(L, m);
     }
     double4 x;
     double two_steps = 0.0;
@@ -282,8 +282,7 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
       double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
       double lx = 0.0, ly = 0.0, lz = 0.0;
       if (lgv) { // post_force of step n (or the setup force): f += f_L, kept for both half-kicks
-        if constexpr (LANGEVIN == 2) mdp_lgv_force(L, i, bath, vx, vy, vz, lx, ly, lz);
-        else mdp_lgv_force(L, i, vx, vy, vz, lx, ly, lz);
+        mdp_lgv_force(L, i, bath, vx, vy, vz, lx, ly, lz);
         fx = fx + lx;
         fy = fy + ly;
         fz = fz + lz;
@@ -329,15 +328,13 @@ __global__ void nve_advance_kernel(int nlocal, double dtf, double dt, const doub
     }
     mdp_style_test(SC, (size_t) i, x, two_steps, w);
   }
-  if constexpr (LANGEVIN == 2) {
+  if constexpr (LANGEVIN > 0)
     if (L.part) { // one slot per bath; an atom adds to its own
-      double e[MDP_LANGEVIN_MAXBATH];
+      double e[LANGEVIN];
 #pragma unroll
-      for (int k = 0; k < MDP_LANGEVIN_MAXBATH; k++) e[k] = bath == k ? lgv_e : 0.0;
-      mdp_block_sum_256<MDP_LANGEVIN_MAXBATH>(e, L.part);
+      for (int k = 0; k < LANGEVIN; k++) e[k] = bath == k ? lgv_e : 0.0;
+      mdp_block_sum_256<LANGEVIN>(e, L.part);
     }
-  } else if constexpr (LANGEVIN == 1)
-    if (L.part) mdp_block_sum_256(lgv_e, L.part);
   if (CHECK) { // (pinned host words zeroed by the host before the launch: plain idempotent stores)
     if (__ballot(t) && (threadIdx.x & 63) == 0) {
       flag[0] = 1;
@@ -373,27 +370,31 @@ __global__ void nve_final_kernel(int nlocal, double dtf, const double *__restric
 
 // a final half on its own with the Langevin force (langevin.hip): f += f_L is written back (writeback), so that the
 // initial half of the next step kicks with the same modified forces (LAMMPS keeps them in atom->f); L.part: the
-// tally's partials.  MASK: an atom outside the integrate group is left alone, one outside the Langevin group gets the
-// plain half-kick; both add nothing to the tally and reach its block sum
-template <bool MASK>
+// tally's partials, one slot per bath.  MASK: an atom outside the integrate group is left alone, one outside the baths'
+// groups gets the plain half-kick; both add nothing to the tally and reach its block sum.  NB: the slot count of L, as
+// LANGEVIN of nve_advance_kernel
+template <int NB, bool MASK>
 __global__ __launch_bounds__(256) void lgv_final_kernel(int nlocal, double dtf, const double *__restrict__ rmass,
-                                                        double *__restrict__ f, double *__restrict__ v, const MdpLgvArgs L,
+                                                        double *__restrict__ f, double *__restrict__ v, const MdpLgvArgs<NB> L,
                                                         const int writeback, const MdpGroupArgs M)
 {
+  static_assert(MASK || NB == 1, "several baths are told apart by the mask");
   const int i = blockIdx.x * 256 + threadIdx.x;
   double e = 0.0;
+  int bath = 0;
   if (i < nlocal) {
     bool move = true, lgv = true;
     if constexpr (MASK) {
       const int m = mdp_group_mask(M, i);
       move = mdp_group_moves(M, m);
       lgv = mdp_group_lgv(M, m);
+      bath = mdp_lgv_bath(L, m);
     }
     if (lgv) {
       const double s = dtf / rmass[i];
       double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
       double lx, ly, lz;
-      mdp_lgv_force(L, i, vx, vy, vz, lx, ly, lz);
+      mdp_lgv_force(L, i, bath, vx, vy, vz, lx, ly, lz);
       const double fx = f[3 * (size_t) i] + lx, fy = f[3 * (size_t) i + 1] + ly, fz = f[3 * (size_t) i + 2] + lz;
       if (writeback) {
         f[3 * (size_t) i] = fx;
@@ -414,51 +415,11 @@ __global__ __launch_bounds__(256) void lgv_final_kernel(int nlocal, double dtf, 
       v[3 * (size_t) i + 2] += s * f[3 * (size_t) i + 2];
     }
   }
-  if (L.part) mdp_block_sum_256(e, L.part);
-}
-
-// ... with several baths (always with a mask): the same half, the bath's force, one slot of the block sum per bath
-__global__ __launch_bounds__(256) void lgv_final_baths_kernel(int nlocal, double dtf, const double *__restrict__ rmass,
-                                                              double *__restrict__ f, double *__restrict__ v,
-                                                              const MdpLgvBathArgs L, const int writeback, const MdpGroupArgs M)
-{
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  double e = 0.0;
-  int bath = 0;
-  if (i < nlocal) {
-    const int m = mdp_group_mask(M, i);
-    const bool move = mdp_group_moves(M, m), lgv = mdp_group_lgv(M, m);
-    bath = mdp_lgv_bath(L, m);
-    if (lgv) {
-      const double s = dtf / rmass[i];
-      double vx = v[3 * (size_t) i], vy = v[3 * (size_t) i + 1], vz = v[3 * (size_t) i + 2];
-      double lx, ly, lz;
-      mdp_lgv_force(L, i, bath, vx, vy, vz, lx, ly, lz);
-      const double fx = f[3 * (size_t) i] + lx, fy = f[3 * (size_t) i + 1] + ly, fz = f[3 * (size_t) i + 2] + lz;
-      if (writeback) {
-        f[3 * (size_t) i] = fx;
-        f[3 * (size_t) i + 1] = fy;
-        f[3 * (size_t) i + 2] = fz;
-      }
-      vx += s * fx;
-      vy += s * fy;
-      vz += s * fz;
-      v[3 * (size_t) i] = vx;
-      v[3 * (size_t) i + 1] = vy;
-      v[3 * (size_t) i + 2] = vz;
-      e = mdp_dot3(ly, vy, lx, vx, lz, vz); // (y first, as lgv_final_kernel)
-    } else if (move) {
-      const double s = dtf / rmass[i];
-      v[3 * (size_t) i] += s * f[3 * (size_t) i];
-      v[3 * (size_t) i + 1] += s * f[3 * (size_t) i + 1];
-      v[3 * (size_t) i + 2] += s * f[3 * (size_t) i + 2];
-    }
-  }
   if (L.part) {
-    double eb[MDP_LANGEVIN_MAXBATH];
+    double eb[NB];
 #pragma unroll
-    for (int k = 0; k < MDP_LANGEVIN_MAXBATH; k++) eb[k] = bath == k ? e : 0.0;
-    mdp_block_sum_256<MDP_LANGEVIN_MAXBATH>(eb, L.part);
+    for (int k = 0; k < NB; k++) eb[k] = bath == k ? e : 0.0;
+    mdp_block_sum_256<NB>(eb, L.part);
   }
 }
 
@@ -672,28 +633,20 @@ __global__ void x3_to_xq_kernel(int n, const double *__restrict__ x3, double4 *_
 
 // a final half on its own with the Langevin thermostat on (mdp_md_final_integrate, mdp_hnve_final).  writeback: the
 // initial half that follows kicks with these forces (false: the forces of a new run's setup come next instead)
-int lgv_final(mdp_ctx *c, bool writeback)
+template <int NB> int lgv_final(mdp_ctx *c, bool writeback)
 {
   bool apply = false, masked = false;
-  MdpLgvArgs L;
+  MdpLgvArgs<NB> L;
   MdpGroupArgs M;
   MDP_TRY(mdp_group_args(c, &masked, &M));
-  if (c->lgv.many()) {
-    MdpLgvBathArgs B;
-    MDP_TRY(mdp_lgv_open_baths(c, false, false, &apply, &B));
-    if (c->nlocal)
-      lgv_final_baths_kernel<<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, B,
-                                                                     writeback ? 1 : 0, M);
-    MDP_HIP(c, hipGetLastError());
-    return mdp_lgv_close_baths(c, B);
-  }
   MDP_TRY(mdp_lgv_open(c, false, false, &apply, &L));
   if (c->nlocal && masked)
-    lgv_final_kernel<true><<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, L,
-                                                                   writeback ? 1 : 0, M);
-  else if (c->nlocal)
-    lgv_final_kernel<false><<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, L,
-                                                                    writeback ? 1 : 0, M);
+    lgv_final_kernel<NB, true><<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, L,
+                                                                       writeback ? 1 : 0, M);
+  if constexpr (NB == 1) // (several baths always come with a mask: mdp_group_args)
+    if (c->nlocal && !masked)
+      lgv_final_kernel<1, false><<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, L,
+                                                                         writeback ? 1 : 0, M);
   MDP_HIP(c, hipGetLastError());
   return mdp_lgv_close(c, L);
 }
@@ -705,7 +658,7 @@ int md_final_half(mdp_ctx *c, bool lgv_writeback = true)
   if (c->indent.on && !c->indent.applied) MDP_TRY(mdp_indent_pass(c)); // (indenters: post_force of the step this half completes)
   if (c->spring.on && !c->spring.applied) MDP_TRY(mdp_spring_pass(c)); // (springs: the same, behind the indenters)
   if (c->nhc.on) return mdp_nhc_final(c);
-  if (c->lgv.on) return lgv_final(c, lgv_writeback);
+  if (c->lgv.on) return c->lgv.many() ? lgv_final<MDP_LANGEVIN_MAXBATH>(c, lgv_writeback) : lgv_final<1>(c, lgv_writeback);
   bool masked = false;
   MdpGroupArgs M;
   MDP_TRY(mdp_group_args(c, &masked, &M));
@@ -715,6 +668,55 @@ int md_final_half(mdp_ctx *c, bool lgv_writeback = true)
     nve_final_kernel<false><<<nblk(c->nlocal), 256, 0, c->stream>>>(c->nlocal, mdp_step(c).dtf, c->rmass.p, c->f.p, c->v.p, M);
   MDP_HIP(c, hipGetLastError());
   if (c->heat.on) return mdp_heat_pass(c); // (heat sources: FixHeat::end_of_step of the step this half completes)
+  return MDP_OK;
+}
+
+// The kernel of md_launch_advance between its thermostat's open and close.  NB: the slot count of the Langevin arguments,
+// MDP_LANGEVIN_MAXBATH while several baths are on and 1 otherwise (a thermostat off, or the chain, included)
+template <int NB>
+int md_launch_kernel(mdp_ctx *c, bool with_final, int *flag, double trigsq, double hardsq, const MdpStyleCheck &sc, bool zero_f,
+                     double *dset, double *dclr)
+{
+  const double *vscale = nullptr;
+  bool lgv = false, masked = false;
+  MdpLgvArgs<NB> L;
+  const MdpLgvArgs<0> none{}; // (what the instantiations without a Langevin force take and never read)
+  MdpGroupArgs M;
+  MDP_TRY(mdp_group_args(c, &masked, &M)); // (before a thermostat counts the step)
+  if (c->nhc.on) MDP_TRY(mdp_nhc_open(c, with_final, &vscale));
+  if (c->lgv.on) MDP_TRY(mdp_lgv_open(c, with_final, true, &lgv, &L));
+  const int n = c->nlocal;
+  if (!n) return MDP_OK;
+  const MdpStep s = mdp_step(c);
+  // FINAL x CHECK x {plain, SCALE, LANGEVIN = 1}: the twelve instantiations (one thermostat per context: never both), and
+  // their twelve MASK twins, which only a context with a group set ever launches; several baths: FINAL x CHECK more,
+  // LANGEVIN = MDP_LANGEVIN_MAXBATH, which exist with MASK alone (mdp_group_args: several baths always come with a mask)
+  auto launch = [&](auto fv, auto cv, auto sv, auto mv, const auto &la) {
+    constexpr int LV = std::decay_t<decltype(la)>::nb;
+    if constexpr (LV <= 1 || decltype(mv)::value)
+      nve_advance_kernel<decltype(fv)::value, decltype(cv)::value, decltype(sv)::value, LV, decltype(mv)::value>
+          <<<nblk(n), 256, 0, c->stream>>>(n, s.dtf, s.dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p, trigsq, hardsq, flag, sc,
+                                           zero_f ? 1 : 0, dset, dclr, vscale, la, M);
+  };
+  constexpr std::true_type T;
+  constexpr std::false_type F;
+  auto group = [&](auto fv, auto cv, auto sv, const auto &la) {
+    if (masked) launch(fv, cv, sv, T, la);
+    else launch(fv, cv, sv, F, la);
+  };
+  auto thermostat = [&](auto fv, auto cv) {
+    if (vscale) group(fv, cv, T, none);
+    else if (lgv) group(fv, cv, F, L);
+    else group(fv, cv, F, none);
+  };
+  auto check = [&](auto fv) {
+    if (flag) thermostat(fv, T);
+    else thermostat(fv, F);
+  };
+  if (with_final) check(T);
+  else check(F);
+  MDP_HIP(c, hipGetLastError());
+  if (lgv) MDP_TRY(mdp_lgv_close(c, L));
   return MDP_OK;
 }
 
@@ -742,58 +744,8 @@ int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, dou
   }
   mdp_indent_count_step(c); // (the initial half below moves the atoms: a compute follows and overwrites f)
   mdp_spring_count_step(c);
-  const double *vscale = nullptr;
-  bool lgv = false, masked = false;
-  const bool baths = c->lgv.many();
-  MdpLgvArgs L;
-  MdpLgvBathArgs B;
-  MdpGroupArgs M;
-  MDP_TRY(mdp_group_args(c, &masked, &M)); // (before a thermostat counts the step)
-  if (c->nhc.on) MDP_TRY(mdp_nhc_open(c, with_final, &vscale));
-  if (baths) MDP_TRY(mdp_lgv_open_baths(c, with_final, true, &lgv, &B));
-  else if (c->lgv.on) MDP_TRY(mdp_lgv_open(c, with_final, true, &lgv, &L));
-  const int n = c->nlocal;
-  if (!n) return MDP_OK;
-  const MdpStep s = mdp_step(c);
-  // FINAL x CHECK x {plain, SCALE, LANGEVIN}: the twelve instantiations (one thermostat per context: never both), and
-  // their twelve MASK twins, which only a context with a group set ever launches; several baths: FINAL x CHECK more,
-  // LANGEVIN = 2 with MASK
-  auto launch = [&](auto fv, auto cv, auto sv, auto lv, auto mv) {
-    constexpr int LV = decltype(lv)::value;
-    if constexpr (LV == 2)
-      nve_advance_kernel<decltype(fv)::value, decltype(cv)::value, false, 2, true>
-          <<<nblk(n), 256, 0, c->stream>>>(n, s.dtf, s.dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p, trigsq, hardsq, flag, sc,
-                                           zero_f ? 1 : 0, dset, dclr, vscale, B, M);
-    else
-      nve_advance_kernel<decltype(fv)::value, decltype(cv)::value, decltype(sv)::value, LV, decltype(mv)::value>
-          <<<nblk(n), 256, 0, c->stream>>>(n, s.dtf, s.dt, c->rmass.p, c->f.p, c->v.p, c->xq.p, c->xhold.p, trigsq, hardsq, flag, sc,
-                                           zero_f ? 1 : 0, dset, dclr, vscale, L, M);
-  };
-  constexpr std::true_type T;
-  constexpr std::false_type F;
-  constexpr std::integral_constant<int, 0> L0;
-  constexpr std::integral_constant<int, 1> L1;
-  constexpr std::integral_constant<int, 2> L2;
-  auto group = [&](auto fv, auto cv, auto sv, auto lv) {
-    if (masked) launch(fv, cv, sv, lv, T);
-    else launch(fv, cv, sv, lv, F);
-  };
-  auto thermostat = [&](auto fv, auto cv) {
-    if (vscale) group(fv, cv, T, L0);
-    else if (lgv && baths) launch(fv, cv, F, L2, T);
-    else if (lgv) group(fv, cv, F, L1);
-    else group(fv, cv, F, L0);
-  };
-  auto check = [&](auto fv) {
-    if (flag) thermostat(fv, T);
-    else thermostat(fv, F);
-  };
-  if (with_final) check(T);
-  else check(F);
-  MDP_HIP(c, hipGetLastError());
-  if (lgv && baths) MDP_TRY(mdp_lgv_close_baths(c, B));
-  else if (lgv) MDP_TRY(mdp_lgv_close(c, L));
-  return MDP_OK;
+  if (c->lgv.many()) return md_launch_kernel<MDP_LANGEVIN_MAXBATH>(c, with_final, flag, trigsq, hardsq, sc, zero_f, dset, dclr);
+  return md_launch_kernel<1>(c, with_final, flag, trigsq, hardsq, sc, zero_f, dset, dclr);
 }
 
 } // namespace
@@ -805,7 +757,7 @@ int mdp_group_args(mdp_ctx *c, bool *masked, MdpGroupArgs *M)
   int lbit = c->lgv.on ? c->lgv_bit : 0;
   if (baths) { // the baths' atoms: the OR of their bits
     lbit = 0;
-    for (int k = 0; k < c->lgv.nbath; k++) lbit |= c->lgv.bbit[k];
+    for (int k = 0; k < c->lgv.nbath; k++) lbit |= c->lgv.bit[k];
   }
   *masked = c->group_bit != 0 || lbit != 0;
   if (!*masked) return MDP_OK;

@@ -314,22 +314,21 @@ static constexpr int kNhcQ = MDP_NHC_STATE_LEN, kNhcS = MDP_NHC_STATE_LEN + MDP_
 struct MdpLangevin {
   bool on = false;
   bool need_setup = false;  // the next initial half applies the setup force of the run first (Fix::setup)
-  mdp_langevin_config cfg;
   long long first = 0, last = 0, step = 0; // step: the step of the forces the next post_force is applied to
   double tab_dt = 0.0, tab_ftm2v = 0.0;    // what the factors in st were computed for
-  DevBuf<double> st;        // [0..16) gfactor1, [16..32) gfactor2, [32..35) mean, [35] energy, [36] E of the last step
-  DevBuf<double> part;      // per-block partial sums (zero: 3 per block; tally: 1 per block)
-  // several baths on disjoint groups (mdp_langevin_baths with nbath > 1; 0 otherwise: the one thermostat above).  They
-  // share first / last / step / need_setup; bath k keeps its words at st + k * kLgvWords, the partials are
-  // 3 MDP_LANGEVIN_MAXBATH per block (zero), then MDP_LANGEVIN_MAXBATH per block (tally)
+  // nbath baths (>= 1 while on) share first / last / step / need_setup.  One bath (mdp_langevin_setup) acts on the group
+  // of mdp_langevin_group and its kernels are the NB = 1 instantiations; several (mdp_langevin_baths) act on disjoint
+  // groups, bath k on bit[k], in the NB = MDP_LANGEVIN_MAXBATH instantiations.  NB is the slot count of everything below.
   int nbath = 0;
-  mdp_langevin_config bcfg[MDP_LANGEVIN_MAXBATH];
-  int bbit[MDP_LANGEVIN_MAXBATH] = {0, 0, 0, 0};
+  mdp_langevin_config cfg[MDP_LANGEVIN_MAXBATH];
+  int bit[MDP_LANGEVIN_MAXBATH] = {0, 0, 0, 0};
   bool any_zero = false, any_tally = false;
+  DevBuf<double> st;        // bath k at st + k * kLgvWords: [0..16) gfactor1, [16..32) gfactor2, [32..35) mean, [35] energy, [36] E of the last step
+  DevBuf<double> part;      // per-block partial sums (zero: 3 NB per block, [bath][3]; then tally: NB per block)
   bool disjoint_checked = false; // the current mask has been counted for atoms in more than one bath
   DevBuf<int> overlap;           // [1] that count
   bool many() const { return on && nbath > 1; }
-  bool sums() const { return on && (nbath > 1 ? any_zero || any_tally : cfg.zero || cfg.tally); } // one rank only
+  bool sums() const { return on && (any_zero || any_tally); } // one rank only
 };
 static constexpr int kLgvG2 = 16, kLgvMean = 32, kLgvE = 35, kLgvElast = 36, kLgvWords = 37;
 // Constant-flux heat sources (heat.hip): the host keeps the step counter and which sources are due; the sums, the scale
@@ -470,28 +469,28 @@ static constexpr int kHfW = 8; // sum (ke + pe) v (3), sum W.v (3), count, sum (
 static constexpr int kMsdW = 9;// sum dx^2, dy^2, dz^2, count, sum m xu (3), sum m, atoms whose tag has no origin
 
 // what the integrate kernels need to add the Langevin force of one step (md.hip nve_advance_kernel / nve_final_kernel)
-struct MdpLgvArgs {
+// for NB slots: 1 (one bath) or MDP_LANGEVIN_MAXBATH (several, MdpLangevin::nbath > 1; a slot beyond nbath has bit 0 and
+// is never picked); 0 is what the kernels without a Langevin force take and never read, laid out as 1.  Everything a lane
+// takes from its bath is picked by unrolled selects on the bath index, never by indexing these arrays with it (no
+// scratch) and never by a branch (lanes of different baths run the same code); with one slot the index is the constant 0
+// and nothing is left to select.
+// bit: the group bit of every bath.  One bath has none to tell apart, so it carries none: its arguments keep the 72 bytes
+// that every instantiation of nve_advance_kernel finds the group arguments behind.
+template <int NB> struct MdpLgvBits { int bit[NB] = {}; };
+template <> struct MdpLgvBits<0> {};
+template <> struct MdpLgvBits<1> {};
+template <int NB> struct MdpLgvArgs : MdpLgvBits<NB> {
+  static constexpr int nb = NB, slots = NB ? NB : 1;
   const int *tag = nullptr, *type = nullptr, *perm = nullptr; // owned atom i: tag[perm ? perm[i] : i], same for type
-  const double *st = nullptr;   // MdpLangevin::st
-  const double *mean = nullptr; // zero yes: the mean of the random parts, [3]
-  double *part = nullptr;       // tally yes: per-block partial sums of f_L . v
-  double tsqrt = 0.0;           // sqrt(T(n))
-  unsigned seed = 0, lo = 0, hi = 0, phase = 0; // the Philox key and counter words of the step
+  const double *st = nullptr;   // MdpLangevin::st: bath k at st + k * kLgvWords
+  const double *mean = nullptr; // some bath has zero yes: st + kLgvMean, component j of bath k's mean at [k * kLgvWords + j]
+                                // (the mean of a bath without zero yes stays 0)
+  double *part = nullptr;       // some bath has tally yes: NB partial sums of f_L . v per block, [bath]
+  double tsqrt[slots] = {};     // sqrt(T(n)) of every bath
+  unsigned seed[slots] = {};    // the Philox key of every bath ...
+  unsigned lo = 0, hi = 0, phase = 0; // ... and the counter words of the step
 };
-
-// ... of several baths (MdpLangevin::nbath > 1).  Everything a lane takes from its bath is picked by unrolled selects on
-// the bath index, never by indexing these arrays (no scratch) and never by a branch (lanes of different baths run the
-// same code); a slot beyond nbath has bit 0 and is never picked.
-struct MdpLgvBathArgs {
-  const int *tag = nullptr, *type = nullptr, *perm = nullptr;
-  const double *st = nullptr; // bath k: st + k * kLgvWords; the mean of a bath without zero yes stays 0
-  double *part = nullptr;     // some bath has tally yes: MDP_LANGEVIN_MAXBATH partial sums of f_L . v per block, [bath]
-  double tsqrt[MDP_LANGEVIN_MAXBATH] = {0.0, 0.0, 0.0, 0.0};
-  unsigned seed[MDP_LANGEVIN_MAXBATH] = {0, 0, 0, 0};
-  int bit[MDP_LANGEVIN_MAXBATH] = {0, 0, 0, 0};
-  int zero = 0;               // some bath has zero yes: the means are read
-  unsigned lo = 0, hi = 0, phase = 0;
-};
+static_assert(sizeof(MdpLgvArgs<0>) == 72 && sizeof(MdpLgvArgs<1>) == 72, "the group arguments of nve_advance_kernel stay where they are");
 
 // what the MASK variants of the integrate kernels need to honour the groups (mdp_integrate_group, mdp_langevin_group);
 // the variants without MASK never read it
@@ -523,80 +522,53 @@ __device__ __forceinline__ void mdp_philox4x32_10(unsigned c[4], unsigned k0, un
   }
 }
 
-// owned atom i: the random part gamma2 (u - 0.5) of its Langevin force (FixLangevin::post_force, fran)
-__device__ __forceinline__ void mdp_lgv_random(const MdpLgvArgs &L, int i, double &rx, double &ry, double &rz)
+// the bath of an atom with mask m (the groups of the baths are disjoint: at most one bit matches); one bath: 0, unread
+template <int NB> __device__ __forceinline__ int mdp_lgv_bath(const MdpLgvArgs<NB> &L, int m)
+{
+  int k = 0;
+  if constexpr (NB > 1) {
+#pragma unroll
+    for (int b = 1; b < NB; b++) k = (m & L.bit[b]) ? b : k;
+  }
+  return k;
+}
+template <class T, int N> __device__ __forceinline__ T mdp_lgv_pick(const T (&a)[N], int k)
+{
+  T r = a[0];
+#pragma unroll
+  for (int b = 1; b < N; b++) r = k == b ? a[b] : r;
+  return r;
+}
+// owned atom i of bath k: the random part gamma2 (u - 0.5) of its Langevin force (FixLangevin::post_force, fran), with
+// the bath's table, T and seed
+template <int NB>
+__device__ __forceinline__ void mdp_lgv_random(const MdpLgvArgs<NB> &L, int i, int k, double &rx, double &ry, double &rz)
 {
   const int a = L.perm ? L.perm[i] : i;
   const int t = L.type[a] & 15;
   unsigned c[4] = {(unsigned) L.tag[a], L.lo, L.hi, L.phase};
-  mdp_philox4x32_10(c, L.seed, 0u);
-  const double g2 = L.st[kLgvG2 + t] * L.tsqrt;
+  mdp_philox4x32_10(c, mdp_lgv_pick(L.seed, k), 0u);
+  const double g2 = L.st[k * kLgvWords + kLgvG2 + t] * mdp_lgv_pick(L.tsqrt, k);
   rx = g2 * (((double) c[0] + 0.5) * 0x1p-32 - 0.5);
   ry = g2 * (((double) c[1] + 0.5) * 0x1p-32 - 0.5);
   rz = g2 * (((double) c[2] + 0.5) * 0x1p-32 - 0.5);
 }
-
-// owned atom i with velocity v: its Langevin force f_L = gamma1 v + fran (- the mean of fran with zero yes)
-__device__ __forceinline__ void mdp_lgv_force(const MdpLgvArgs &L, int i, double vx, double vy, double vz, double &lx,
-                                              double &ly, double &lz)
+// ... with velocity v: its Langevin force f_L = gamma1 v + fran (- the mean of fran where some bath has zero yes; a bath
+// without it next to one with it subtracts the 0 its mean holds: the same bits)
+template <int NB>
+__device__ __forceinline__ void mdp_lgv_force(const MdpLgvArgs<NB> &L, int i, int k, double vx, double vy, double vz,
+                                              double &lx, double &ly, double &lz)
 {
   double rx, ry, rz;
-  mdp_lgv_random(L, i, rx, ry, rz);
-  const double g1 = L.st[L.type[L.perm ? L.perm[i] : i] & 15];
+  mdp_lgv_random(L, i, k, rx, ry, rz);
+  const double g1 = L.st[k * kLgvWords + (L.type[L.perm ? L.perm[i] : i] & 15)];
   lx = g1 * vx + rx;
   ly = g1 * vy + ry;
   lz = g1 * vz + rz;
   if (L.mean) {
-    lx -= L.mean[0];
-    ly -= L.mean[1];
-    lz -= L.mean[2];
-  }
-}
-
-// several baths: the bath of an atom with mask m (its groups are disjoint: at most one bit matches)
-__device__ __forceinline__ int mdp_lgv_bath(const MdpLgvBathArgs &B, int m)
-{
-  int k = 0;
-  k = (m & B.bit[1]) ? 1 : k;
-  k = (m & B.bit[2]) ? 2 : k;
-  k = (m & B.bit[3]) ? 3 : k;
-  return k;
-}
-template <class T> __device__ __forceinline__ T mdp_lgv_pick(const T (&a)[MDP_LANGEVIN_MAXBATH], int k)
-{
-  T r = a[0];
-  r = k == 1 ? a[1] : r;
-  r = k == 2 ? a[2] : r;
-  r = k == 3 ? a[3] : r;
-  return r;
-}
-// owned atom i of bath k: the random part of its Langevin force, as mdp_lgv_random with the bath's table, T and seed
-__device__ __forceinline__ void mdp_lgv_random(const MdpLgvBathArgs &B, int i, int k, double &rx, double &ry, double &rz)
-{
-  const int a = B.perm ? B.perm[i] : i;
-  const int t = B.type[a] & 15;
-  unsigned c[4] = {(unsigned) B.tag[a], B.lo, B.hi, B.phase};
-  mdp_philox4x32_10(c, mdp_lgv_pick(B.seed, k), 0u);
-  const double g2 = B.st[k * kLgvWords + kLgvG2 + t] * mdp_lgv_pick(B.tsqrt, k);
-  rx = g2 * (((double) c[0] + 0.5) * 0x1p-32 - 0.5);
-  ry = g2 * (((double) c[1] + 0.5) * 0x1p-32 - 0.5);
-  rz = g2 * (((double) c[2] + 0.5) * 0x1p-32 - 0.5);
-}
-// ... and its Langevin force, as mdp_lgv_force (a bath without zero yes subtracts the 0 its mean holds: the same bits)
-__device__ __forceinline__ void mdp_lgv_force(const MdpLgvBathArgs &B, int i, int k, double vx, double vy, double vz,
-                                              double &lx, double &ly, double &lz)
-{
-  double rx, ry, rz;
-  mdp_lgv_random(B, i, k, rx, ry, rz);
-  const double *st = B.st + k * kLgvWords;
-  const double g1 = st[B.type[B.perm ? B.perm[i] : i] & 15];
-  lx = g1 * vx + rx;
-  ly = g1 * vy + ry;
-  lz = g1 * vz + rz;
-  if (B.zero) {
-    lx -= st[kLgvMean];
-    ly -= st[kLgvMean + 1];
-    lz -= st[kLgvMean + 2];
+    lx -= L.mean[k * kLgvWords];
+    ly -= L.mean[k * kLgvWords + 1];
+    lz -= L.mean[k * kLgvWords + 2];
   }
 }
 
@@ -1131,15 +1103,13 @@ int mdp_nhc_final(mdp_ctx *c);
 // Langevin thermostat (langevin.hip), around the integrate kernels when c->lgv.on.  _open: before a kernel that
 // first consumes a compute's forces (the fused final + initial, the setup step's initial half, a final half on its own):
 // *apply = whether this kernel adds the force; if so *L is filled (and the zero pre-pass queued).  Advances the step
-// counter when `initial`.  _close: behind that kernel (the tally of the step).
-int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvArgs *L);
+// counter when `initial`.  _close: behind that kernel (the tally of the step).  NB: 1 with one bath on,
+// MDP_LANGEVIN_MAXBATH with several (c->lgv.many()); langevin.hip instantiates these two.
+template <int NB> int mdp_lgv_open(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvArgs<NB> *L);
+template <int NB> int mdp_lgv_close(mdp_ctx *c, const MdpLgvArgs<NB> &L);
 // groups: *masked = whether the integrate calls take the MASK variants now (a group bit is set), *M filled if so; fails
 // with MDP_ESTATE when a group is set and no mask covers the current atoms
 int mdp_group_args(mdp_ctx *c, bool *masked, MdpGroupArgs *M);
-int mdp_lgv_close(mdp_ctx *c, const MdpLgvArgs &L);
-// ... with several baths on (c->lgv.many()): the same two calls around the bath instantiations
-int mdp_lgv_open_baths(mdp_ctx *c, bool with_final, bool initial, bool *apply, MdpLgvBathArgs *B);
-int mdp_lgv_close_baths(mdp_ctx *c, const MdpLgvBathArgs &B);
 // several baths and a mask: count the atoms in more than one bath, once per mask or bath set-up, and refuse any
 int mdp_lgv_check_disjoint(mdp_ctx *c, const char *who);
 // heat sources (heat.hip) when c->heat.on.  _pass: behind a plain final half that completes a step: the sums, the control

@@ -3,18 +3,17 @@ with the fused final half, as bench.py drives it) on
   * REBO-MoS bulk, in.rebomos-bulk's cell replicated 24x24x24 (3.98 M atoms) from 300 K
   * the AEAM alloy, fcc a = 4.045 A, 63^3 cells (1.0 M atoms, 0.75 % Si) at 863 K
 in one session on one MI355X.  Two questions:
-  1. Did the paths a context with one thermostat or none takes change?  They launch the kernels they launched (DESIGN.md
-     section 4 item 35), so the PARENT commit's library (--parent-lib PATH, loaded through MDP_LIB_PATH) is the yardstick:
+  1. Did any path change against the PARENT commit's library (--parent-lib PATH, loaded through MDP_LIB_PATH)?
        nve        all-atoms NVE
        lgv_all    one bath on all atoms (mdp_langevin_setup, no mask)
        lgv_third  one bath on the third of the box x < 1/3 (mdp_langevin_group: the MASK kernels)
-     each with the parent's library and with this build in alternating processes, REPS of each.  The spread of the parent's
-     own repetitions is reported next to the difference: a difference beyond it needs an explanation.
-  2. What do two baths cost against one bath over the same atoms?  From this build alone, alternating inside a process:
        union      one bath, `tally yes`, on two strips of a sixth of the box each (x < 1/6 and 1/2 <= x < 2/3)
        two_baths  a hot bath on the first strip and a cold bath on the second, `tally yes` both (mdp_langevin_baths:
-                  the LANGEVIN = 2 instantiations, four tally slots per block instead of one)
-     The ratio and the spread of its repetitions are reported; no bar is set for it.
+                  the LANGEVIN = MDP_LANGEVIN_MAXBATH instantiations, four tally slots per block instead of one)
+     each with the parent's library and with this build in alternating processes, REPS of each.  The spread of the parent's
+     own repetitions is reported next to the difference: a difference beyond it needs an explanation.
+  2. What do two baths cost against one bath over the same atoms?  union and two_baths of this build, which alternate inside
+     a process.  The ratio and the spread of its repetitions are reported; no bar is set for it.
 A process builds the system once and runs its modes one after the other, each on a fresh context; every process runs
 under `timeout -k 10`, and the parent stops at the first one that does not end cleanly.  All modes reneighbor on the same
 steps: the alloy at a fixed interval, REBO-MoS by the on-device check (the builds of each run are recorded).
@@ -132,7 +131,7 @@ def main():
             continue
         for rep in range(REPS):
             for lib in (("parent", "this") if parent else ("this",)):
-                modes = OLD_MODES if lib == "parent" else OLD_MODES + NEW_MODES
+                modes = OLD_MODES + NEW_MODES
                 cmd = ["timeout", "-k", "10", "900", sys.executable, os.path.abspath(__file__), "--child", wl, ",".join(modes),
                        str(steps), str(warmup)]
                 env = dict(os.environ)
@@ -156,7 +155,7 @@ def main():
         def ms(mode, lib):
             return [r["ms_per_step"] for r in results if r["workload"] == wl and r["mode"] == mode and r["library"] == lib]
         row = {"atoms": next(r["atoms"] for r in results if r["workload"] == wl)}
-        for mode in OLD_MODES:
+        for mode in OLD_MODES + NEW_MODES[:2]:
             new = ms(mode, "this build")
             row[mode] = {"this_ms": new, "this_best": min(new)}
             text = f"{wl} {mode}: this build {min(new):.3f} ms/step"

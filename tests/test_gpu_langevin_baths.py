@@ -1,6 +1,6 @@
-"""GPU: several Langevin baths on disjoint groups in one run (mdp_langevin_baths, mdp_langevin_tally_bath; the LANGEVIN = 2
-instantiations of nve_advance_kernel, lgv_final_baths_kernel and the bath forms of the zero / mean / tally kernels)
-against the masked host loop of tests/bathsref.py around the ORACLE forces.
+"""GPU: several Langevin baths on disjoint groups in one run (mdp_langevin_baths, mdp_langevin_tally_bath; the
+LANGEVIN = MDP_LANGEVIN_MAXBATH instantiations of nve_advance_kernel, lgv_final_kernel<4, true> and the four-slot
+instantiations of the zero / mean / tally kernels) against the masked host loop of tests/bathsref.py around the ORACLE forces.
 
 The two cells of the thermostat tests at 300 K, 200 steps of 0.001 ps with rebuild="auto" and the 0.5 A skin of the group
 tests.  The masks (bathsref.masks): bit 1 everywhere, integrate bit 2 as in the group tests, the baths on bits 4 / 8 / 16
@@ -366,15 +366,13 @@ def test_two_runs_of_the_three_baths_agree(style, capsys):
 
 
 # ---- 6. host-linked mode from shuffled atoms ----------------------------------------------------------------------------
-@pytest.mark.parametrize("style", ["aeam", "rebomos"])
-def test_hostlinked_baths_from_shuffled_atoms(oracle, style, capsys):
-    """mdp_hnve_* with mdp_hnve_set_mask and the three baths: the host's atom order is a shuffle of the tags, host
+def _hostlinked(oracle, style, s, v0, x_in, by_tag, g, baths, every, refused=None):
+    """mdp_hnve_* with mdp_hnve_set_mask and `baths` (dicts of _dev_bath): the host's atom order is a shuffle of the tags, host
     reneighborings every 50 steps re-upload atoms, velocities and mask (each upload counts the atoms in more than one
     bath again).  The alloy on the library's own lists, as under the plugin; REBO-MoS in the device's own order, so the mask,
-    tags and types are read through the host's permutation"""
+    tags and types are read through the host's permutation.  refused: what an initial half without a mask must answer.
+    {step: (x, [tally of bath k], v)} by tag at `every`, and the uploads"""
     import ctypes as C
-    s, v0, by_tag, g, groups, x_in = _case(style)
-    host = _reference(oracle, style)
     perm = np.random.default_rng(17).permutation(s.n)
     type_p, tag_p = s.type[perm].copy(), s.tag[perm].copy()
     mask_p = by_tag[tag_p]
@@ -410,16 +408,17 @@ def test_hostlinked_baths_from_shuffled_atoms(oracle, style, capsys):
         c.hnve_setup(0.001, S.FTM2V, s.mass)
         c.integrate_group(GBIT)
         cfgs = []
-        for k in range(3):
-            b = _dev_bath(BATHS[k], BITS[k], groups[k])
+        for b in baths:
+            b = dict(b)
             b["t_period"] = b.pop("damp")
             cfgs.append(b)
         c.langevin_baths(cfgs, boltz=S.BOLTZ, mvv2e=S.MVV2E)
         c.langevin_run(0, NSTEPS)
         upload(x_in[perm].copy(), v0[perm])
         assert c.host_ghosts_derived()
-        with pytest.raises(capi.MdpError, match="3 Langevin baths are on .* but no mask covers the current atoms"):
-            c.hnve_initial()
+        if refused:
+            with pytest.raises(capi.MdpError, match=refused):
+                c.hnve_initial()
         c.hnve_set_mask(mask_p)
         compute()
         dev, uploads = {}, 0
@@ -434,17 +433,133 @@ def test_hostlinked_baths_from_shuffled_atoms(oracle, style, capsys):
                 uploads += 1
             compute()
             c.hnve_final()
-            if step in EVERY20:
-                e = [c.langevin_tally(bath=k) for k in range(3)]
+            if step in every:
+                e = [c.langevin_tally(bath=k) for k in range(len(cfgs))]
                 got = c.hnve_download(s.n, want=("x", "v"))
                 xd, vd = np.zeros((s.n, 3)), np.zeros((s.n, 3))
                 xd[tag_p - 1], vd[tag_p - 1] = got["x"], got["v"]
                 dev[step] = (xd, e, vd)
     finally:
         c.close()
+    return dev, uploads
+
+
+@pytest.mark.parametrize("style", ["aeam", "rebomos"])
+def test_hostlinked_baths_from_shuffled_atoms(oracle, style, capsys):
+    """the three baths through _hostlinked against the host loop; before the mask is there an initial half is refused"""
+    s, v0, by_tag, g, groups, x_in = _case(style)
+    host = _reference(oracle, style)
+    dev, uploads = _hostlinked(oracle, style, s, v0, x_in, by_tag, g, [_dev_bath(BATHS[k], BITS[k], groups[k]) for k in range(3)],
+                               EVERY20, refused="3 Langevin baths are on .* but no mask covers the current atoms")
     assert uploads >= 3
     with capsys.disabled():
         _compare(s, host, dev, g, x_in, v0, f"three baths, host-linked {style}, shuffled host order ({uploads} uploads)", EVERY20)
+
+
+def test_hostlinked_split_bath_is_the_same_trajectory(oracle, capsys):
+    """test_a_split_bath_is_the_same_trajectory through mdp_hnve_initial / mdp_hnve_final from shuffled atoms: the one bath
+    runs the NB = 1 kernels with tags, types and mask read through the host's permutation, the two baths the NB = 4 kernels
+    -- both from the same templates.  x and v equal bit for bit at every read, the two tallies add up to the one (1e-9 eV)"""
+    s, v0, by_tag, g, groups, x_in = _case("rebomos")
+    L = groups[0] | groups[1]
+    b = dict(BATHS[1], t_start=300.0, t_stop=700.0)
+    even, odd = L & (s.tag % 2 == 0), L & (s.tag % 2 == 1)
+    m = np.zeros_like(by_tag)
+    m[s.tag] = 1 | np.where(g, GBIT, 0) | np.where(L, 4, 0) | np.where(even, 8, 0) | np.where(odd, 16, 0)
+    assert even.sum() > 50 and odd.sum() > 50
+    a, uploads = _hostlinked(oracle, "rebomos", s, v0, x_in, m, g, [_dev_bath(b, 4, L)], EVERY20)
+    c, _ = _hostlinked(oracle, "rebomos", s, v0, x_in, m, g, [_dev_bath(b, 8, even), _dev_bath(b, 16, odd)], EVERY20)
+    assert uploads >= 3
+    worst = 0.0
+    for step in EVERY20:
+        assert np.array_equal(a[step][0], c[step][0]) and np.array_equal(a[step][2], c[step][2]), step
+        worst = worse(worst, abs(c[step][1][0] + c[step][1][1] - a[step][1][0]))
+    with capsys.disabled():
+        print(f"host-linked split bath: tally {a[NSTEPS][1][0]:.6f} eV = {c[NSTEPS][1][0]:.6f} + {c[NSTEPS][1][1]:.6f}, "
+              f"worst difference {worst:.2e} eV")
+    assert abs(a[NSTEPS][1][0]) > 1e-3 and c[NSTEPS][1][0] != 0.0 and c[NSTEPS][1][1] != 0.0
+    assert worst < 1e-9, worst
+
+
+# ---- 6b. more than 256 per-block partials with two baths --------------------------------------------------------------------
+@pytest.mark.parametrize("style", ["aeam", "rebomos"])
+def test_two_baths_sum_every_partial(style, capsys):
+    """test_gpu_langevin_mdp.test_zero_and_tally_sum_every_partial with two baths, on the even and on the odd tags of the same
+    cell: more than 256 per-block partials, so mdp_slot_sum_256 makes a second trip with the 12 values per slot of the
+    means and the 4 of the tallies.  Both baths zero yes and tally yes, seeds, damping and ramps of their own, a ratio on
+    the first.  Per step the written-back force of every atom must be langevinref's for ITS bath, with that bath's mean of
+    the random parts taken by math.fsum over that bath's atoms, to 1e-12 eV/A; each bath's tally must be
+    -(e_0 / 2 + e_1 + ... + e_k / 2) dt with e = fsum(f_L . v) over its atoms, to 1e-12 of its scale (the bounds and their
+    reasons are that test's)"""
+    import math
+    import test_gpu_langevin_mdp as LM
+    import test_gpu_nvt_net as NN
+    s, v0 = NN._big(style)
+    assert s.n > 65536 and -(-s.n // 256) > 256
+    dt, nsteps, bits = 0.001, 3, (8, 16)
+    spec = (dict(t_start=300.0, t_stop=330.0, damp=0.05, seed=48271, ratio={1: 2.0, 2: 0.5}, zero=True, tally=True),
+            dict(t_start=250.0, t_stop=200.0, damp=0.02, seed=7919, ratio=None, zero=True, tally=True))
+    lgs = [_ref_bath(s, b) for b in spec]
+    for lg in lgs:
+        lg.setup(0, nsteps)
+    by_tag = np.zeros(int(s.tag.max()) + 1, dtype=np.int32)
+    by_tag[s.tag] = 1 | np.where(s.tag % 2 == 0, bits[0], bits[1])
+    count = [int((s.tag % 2 == 0).sum()), int((s.tag % 2 == 1).sum())]
+    dtf = 0.5 * dt * S.FTM2V
+    ctx, d = LM._domain(capi.STYLE_AEAM if style == "aeam" else capi.STYLE_REBOMOS, s, v0)
+
+    def f_l(step, tags, types, v, phase=0):
+        out = np.zeros_like(v)
+        for k, lg in enumerate(lgs):
+            sel = tags % 2 == k
+            fran = lg.random(step, tags[sel], types[sel], phase)
+            mean = np.array([math.fsum(fran[:, j]) for j in range(3)]) / count[k]
+            out[sel] = lg.g1[types[sel]][:, None] * v[sel] + fran - mean
+        return out
+
+    def dots(a, b, tags):
+        p = a * b
+        return [(math.fsum(p[tags % 2 == k].ravel()), math.fsum(np.abs(p[tags % 2 == k]).ravel())) for k in range(2)]
+    try:
+        d.set_group(by_tag, 0)
+        d.langevin_baths([dict(b, bit=bits[k], natoms=count[k]) for k, b in enumerate(spec)], first=0, last=nsteps)
+        d.compute(0, 0)
+        tags, types = d.tags_local.copy(), ctx.md_download_int("type", d.nlocal).copy()
+        assert (tags % 2 == 0).sum() == count[0]
+        m = s.mass[types][:, None]
+        worst_f, worst_e = 0.0, [0.0, 0.0]
+        # the setup force: in the first initial half
+        a = ctx.md_download(d.nlocal, want=("v", "f"))
+        ctx.md_initial_integrate()
+        b = ctx.md_download(d.nlocal, want=("v",))
+        want = f_l(0, tags, types, a["v"], phase=1)
+        assert np.abs(a["f"]).max() < 100.0
+        worst_f = worse(worst_f, float(np.abs((b["v"] - a["v"]) * m / dtf - a["f"] - want).max()))
+        acc = [dict(energy=0.5 * e * dt, e_last=e, scale=0.5 * sc * dt) for e, sc in dots(want, a["v"], tags)]
+        for step in range(1, nsteps + 1):
+            if step > 1:
+                ctx.md_initial_integrate()
+            ctx.md_compute(0, 0)
+            assert np.array_equal(d.tags_local, tags)            # (no reneighbouring in three steps: same slots)
+            a = ctx.md_download(d.nlocal, want=("v", "f"))
+            ctx.md_final_integrate()
+            b = ctx.md_download(d.nlocal, want=("v", "f"))
+            want = f_l(step, tags, types, a["v"])
+            assert np.abs(a["f"]).max() < 100.0
+            worst_f = worse(worst_f, float(np.abs(b["f"] - a["f"] - want).max()))
+            for k, (e, ea) in enumerate(dots(want, b["v"], tags)):
+                t = acc[k]
+                t.update(energy=t["energy"] + e * dt, e_last=e, scale=t["scale"] + ea * dt)
+                got = ctx.langevin_tally(bath=k)
+                worst_e[k] = worse(worst_e[k], abs(got + (t["energy"] - 0.5 * t["e_last"] * dt)) / t["scale"])
+            assert np.abs(b["v"] - a["v"] - dtf * b["f"] / m).max() < 1e-12   # and the final half used f + f_L
+    finally:
+        ctx.close()
+    with capsys.disabled():
+        print(f"{style} {s.n} atoms, two baths: worst |f_L - reference| {worst_f:.2e} eV/A, tallies {worst_e[0]:.2e} and {worst_e[1]:.2e} "
+              f"of their scales")
+    assert worst_f < 1e-12, worst_f
+    assert max(worst_e) < 1e-12, worst_e
 
 
 # ---- 7. bricks ----------------------------------------------------------------------------------------------------
