@@ -814,6 +814,47 @@ int mdp_rdf_counts(mdp_ctx *ctx, long long *hist, long long *icount, long long *
 int mdp_rdf_info(mdp_ctx *ctx, long long out[4]);
 int mdp_rdf_off(mdp_ctx *ctx);
 
+/* ---- bond-angle histograms: the angular distribution function (LAMMPS compute adf), in integers ------------------------------
+ * For a resident context with mdp_dd_setup (MDP_ESTATE otherwise), next to its one rdf measurement.  Nothing of a run is changed
+ * by a read: the binning is the measurement's own (the same stage as mdp_rdf_counts').
+ *   mdp_adf_setup:   starts a measurement of ntriple triples (1 .. MDP_ADF_MAXTRIPLE) of nbin bins.  Triple m has the centre
+ *                    types ilo[m] .. ihi[m], the j types jlo[m] .. jhi[m] inside the shell rjin[m] <= r < rjout[m] and the k
+ *                    types klo[m] .. khi[m] inside rkin[m] <= r < rkout[m] (LAMMPS types 1 .. ntypes, inclusive).  ordinate:
+ *                    MDP_ADF_DEGREE, _RADIAN or _COSINE.  member_by_tag as in mdp_rdf_setup.  A second call replaces the first.
+ *                    MDP_EINVAL: nbin < 1, an ordinate outside the three, ntriple outside 1 .. MDP_ADF_MAXTRIPLE (a neighbour's
+ *                    j- and k-qualifications are 32-bit masks), a type outside 1 .. ntypes, lo > hi, a radius < 0, inner >=
+ *                    outer, nbin * ntriple > MDP_ADF_MAXCOUNTERS (the workgroup's histogram in LDS), a member table with
+ *                    ntag < 1, and an outer radius + skin > the cutghost of mdp_dd_setup, for the reason given at mdp_rdf_setup.
+ *   mdp_adf_counts:  blocking.  A centre i of triple m is an owned member whose type lies in the i range; icount[m] counts
+ *                    them on this rank, with or without neighbours.  A neighbour is any other array entry, owned or ghost (a
+ *                    periodic image of an atom is a separate entry, the centre's own image included, as in mdp_rdf_counts).
+ *                    It is a j-neighbour of triple m when it is a member, its type lies in the j range and rjin^2 <= rsq <
+ *                    rjout^2, and a k-neighbour by the same rule with the k range and radii.  Every ORDERED pair (j, k), j != k
+ *                    as array entries, counts once -- a triple whose j and k selections coincide counts each angle twice, as
+ *                    LAMMPS does -- with c = clamp(d_ij . d_ik / (r_ij r_ik), -1, 1), the ordinate u = acos(c) 180 / pi,
+ *                    acos(c) or c over [lo, hi] = [0, 180], [0, pi] or [-1, 1], and the bin b = (int) ((u - lo) nbin /
+ *                    (hi - lo)), b >= nbin going into bin nbin - 1 (180 degrees and c = 1 land in the last bin).  All in double.
+ *                    hist[m][b] is this rank's number of them; the caller sums hist and icount over the ranks and normalises.
+ *                    All integers: two reads of one state agree exactly.  MDP_ESTATE without a setup; MDP_EINVAL if an owned
+ *                    or ghost atom has a tag outside the member table, if the largest outer radius has outgrown the ghost
+ *                    shell, and if a centre has more members inside the largest outer radius than MDP_ADF_MAXNEIGH (the
+ *                    short list a wave keeps in LDS): the message names the number of such centres and the cap, and no
+ *                    histogram is handed back -- no centre is ever truncated.  The cost is quadratic in the neighbours.
+ *   mdp_adf_info:    out = {a measurement is on, its nbin, its ntriple, its serial}; the serial as that of mdp_rdf_info.
+ *   mdp_adf_off:     releases the tables and the buffers of the binning. */
+#define MDP_ADF_MAXTRIPLE 32
+#define MDP_ADF_MAXCOUNTERS 8192
+#define MDP_ADF_MAXNEIGH 128
+#define MDP_ADF_DEGREE 0
+#define MDP_ADF_RADIAN 1
+#define MDP_ADF_COSINE 2
+int mdp_adf_setup(mdp_ctx *ctx, int nbin, int ordinate, int ntriple, const int *ilo, const int *ihi, const int *jlo,
+                  const int *jhi, const int *klo, const int *khi, const double *rjin, const double *rjout, const double *rkin,
+                  const double *rkout, int ntag, const unsigned char *member_by_tag);
+int mdp_adf_counts(mdp_ctx *ctx, long long *hist, long long *icount);
+int mdp_adf_info(mdp_ctx *ctx, long long out[4]);
+int mdp_adf_off(mdp_ctx *ctx);
+
 /* ---- binned mass, momentum and kinetic energy: temperature, density and flow profiles (LAMMPS compute chunk/atom bin/1d|2d|3d
  * with compute temp/chunk, vcm/chunk, fix ave/chunk), in integers ----------------------------------------------------------
  * For a resident context with mdp_dd_setup (MDP_ESTATE otherwise).  Nothing a step, a list build, msd or rdf reads is touched.

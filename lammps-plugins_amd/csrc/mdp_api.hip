@@ -927,6 +927,7 @@ int mdp_destroy(mdp_ctx *c)
   c->image.release();
   mdp_msd_release(c);
   mdp_rdf_release(c);
+  mdp_adf_release(c);
   mdp_profile_release(c);
   mdp_heatflux_release(c);
   if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);

@@ -125,6 +125,21 @@ struct MdpGrid {
   int range; // stencil half width in cells: range * cell width >= the cutoff the grid was made for
 };
 
+// The cell of a position on the grid of mdp_measure_bin.  It clamps: an atom that has drifted up to skin / 2 past the bounding
+// box of the last reneighbouring lands in an edge cell.  Cells are >= cutoff / 2 wide and the box is padded by more than
+// skin, so the atom is less than one cell outside and the 5-cell stencil around the edge cell still reaches every partner
+// within the cutoff.
+__device__ __forceinline__ int mdp_bin_cell_index(const MdpGrid &g, const double4 &x, int &cx, int &cy, int &cz)
+{
+  cx = (int) ((x.x - g.lo[0]) * g.inv[0]);
+  cy = (int) ((x.y - g.lo[1]) * g.inv[1]);
+  cz = (int) ((x.z - g.lo[2]) * g.inv[2]);
+  cx = cx < 0 ? 0 : (cx >= g.n[0] ? g.n[0] - 1 : cx);
+  cy = cy < 0 ? 0 : (cy >= g.n[1] ? g.n[1] - 1 : cy);
+  cz = cz < 0 ? 0 : (cz >= g.n[2] ? g.n[2] - 1 : cz);
+  return cx + g.n[0] * (cy + g.n[1] * cz);
+}
+
 // The reference sizes everything from the potential file (pair_aeam.cpp:752-872; the bundled AlSi.aeam has two
 // elements), and so does this library.  Up to MDP_AEAM_MAXT atom types the parameters of the type pairs also ride in
 // the kernel arguments (1.8 KB of the 4 KB a launch may carry), where the tile kernels and the templated CSR kernels read
@@ -439,19 +454,45 @@ struct MdpMsd : MdpMeasure {
   DevBuf<double> xu;   // [nlocal][3] unwrapped positions (mdp_md_download_unwrapped)
   DevBuf<double> part; // per-block partials, kMsdW per block, then the kMsdW sums
 };
-// pair-distance histograms (rdf.hip): a binning of its own and the counters of a read; nothing here is shared with the list
-// builders, so a read leaves the run's scratch alone
-struct MdpRdf : MdpMeasure {
-  int nbin = 0, npair = 0, ntypes = 0, ntag = 0; // ntag 0: every atom is a member
-  double cutoff = 0.0;
-  DevBuf<unsigned char> member;    // [ntag] membership of the atom with tag t at [t - 1], the WHOLE system on every rank
-  DevBuf<int> tab;                 // column masks per (type i, type j), then the i and j masks per type
+// The binning of a pair or angle measurement (measure_bin.hip): ALL atoms of the brick, owned and ghost, on a grid of its own.
+// Nothing here is shared with the list builders, so a read leaves the run's scratch alone.
+struct MdpBinning {
   DevBuf<unsigned> key_a, key_b;   // cell of every atom, before and after the sort
   DevBuf<int> val_a, perm, code;   // atom indices before / after the sort; type, membership and ownership per atom
   DevBuf<int> cell_start;          // [ncell + 1]
   DevBuf<double4> rec;             // [nall] {x, y, z, code} in cell order
   DevBuf<char> sort_tmp;
+  void release()
+  {
+    key_a.release();
+    key_b.release();
+    val_a.release();
+    perm.release();
+    code.release();
+    cell_start.release();
+    rec.release();
+    sort_tmp.release();
+  }
+};
+constexpr int kBinTypes = 16; // type codes 0 .. 15 of a record: 0 = not a member, t = LAMMPS type t
+constexpr int kBinOwned = 32; // code bit: an owned atom (a lane that counts)
+// pair-distance histograms (rdf.hip): the binning and the counters of a read
+struct MdpRdf : MdpMeasure {
+  int nbin = 0, npair = 0, ntypes = 0, ntag = 0; // ntag 0: every atom is a member
+  double cutoff = 0.0;
+  DevBuf<unsigned char> member;    // [ntag] membership of the atom with tag t at [t - 1], the WHOLE system on every rank
+  DevBuf<int> tab;                 // column masks per (type i, type j), then the i and j masks per type
+  MdpBinning bin;
   DevBuf<unsigned long long> out;  // [npair][nbin] histogram, then icount / jcount / dup [MDP_RDF_MAXPAIR] each, then the bad tags
+};
+// bond-angle histograms (adf.hip): the same, with the shells of every triple
+struct MdpAdf : MdpMeasure {
+  int nbin = 0, ntriple = 0, ntypes = 0, ntag = 0, ordinate = 0;
+  double rmax = 0.0;               // the largest outer radius: what the grid and the ghost shell have to cover
+  DevBuf<unsigned char> member;    // as MdpRdf::member
+  DevBuf<double> tab;              // squared shell radii [4][MDP_ADF_MAXTRIPLE], then the triple masks per type (adf.hip)
+  MdpBinning bin;
+  DevBuf<unsigned long long> out;  // [ntriple][nbin] histogram, icount [MDP_ADF_MAXTRIPLE], the centres over the cap, the bad tags
 };
 // binned sums of m, m v and m v^2 (profile.hip): the bins and the table of a read; nothing here is read by a step, a list build,
 // msd or rdf
@@ -872,6 +913,7 @@ struct mdp_ctx {
   bool image_set = false;
   MdpMsd msd;
   MdpRdf rdf;                      // pair-distance histograms of the current positions (mdp_rdf_setup)
+  MdpAdf adf;                      // bond-angle histograms of the current positions (mdp_adf_setup)
   MdpProfile profile;              // binned mass, momentum and kinetic energy of the current atoms (mdp_profile_setup)
   MdpHeatflux heatflux;            // partial sums of a heat-current read (mdp_heatflux_sums)
   // eflag / vflag of the last FINISHED compute while its per-atom tallies (eatom, vatom) still describe the owned atoms in
@@ -1146,6 +1188,15 @@ inline void mdp_spring_count_step(mdp_ctx *c)
 }
 void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
 void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds
+void mdp_adf_release(mdp_ctx *c); // frees what adf.hip holds
+// measure_bin.hip, queued on the stream: a grid with cells >= cutoff / 2 over the padded hull of the brick (stencil: 2 cells each
+// way), every owned and ghost atom sorted into it, b.cell_start and the cell-ordered records b.rec = {x, y, z, code} with
+// code = (member ? type : 0) | (owned ? kBinOwned : 0).  member: by tag - 1 over 1 .. ntag, or nullptr for every atom; an atom
+// whose tag has no entry counts in *d_bad and is no member.  Needs nall > 0.
+int mdp_measure_bin(mdp_ctx *c, MdpBinning &b, double cutoff, int ntypes, int ntag, const unsigned char *d_member,
+                    unsigned long long *d_bad, MdpGrid &g);
+// what a setup or a read of such a measurement needs: a resident context with mdp_dd_setup, on its device
+int mdp_measure_require(mdp_ctx *c, const char *who);
 void mdp_profile_release(mdp_ctx *c); // frees what profile.hip holds
 void mdp_heatflux_release(mdp_ctx *c); // frees what heatflux.hip holds
 // the end of an mdp_{msd,rdf,profile}_setup: the measurement is on, under a serial that is new in this process (one

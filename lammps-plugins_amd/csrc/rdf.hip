@@ -1,6 +1,7 @@
 // rdf.hip -- pair-distance histograms of a device-resident run (LAMMPS compute rdf), in integers.
 // A read bins ALL atoms of the brick (owned and ghost) on a grid of its own, at cell width >= cutoff / 2, into buffers that
-// belong to MdpRdf: the list builders' grid, permutation, cell starts and cell-ordered positions (mdp_bin_atoms) are
+// belong to MdpRdf (mdp_measure_bin, measure_bin.hip, which compute adf's read shares): the list builders' grid,
+// permutation, cell starts and cell-ordered positions (mdp_bin_atoms) are
 // neither read nor written, so a read changes nothing a later step or list build sees.  One lane per atom in cell order
 // (a wave shares its 5 x 5 x 5 stencil) sweeps the stencil as 25 runs of the cell-ordered records {x, y, z, code}; the
 // code word carries the type (0 for an atom outside the group), so one 32-byte load per candidate is all the inner loop
@@ -9,87 +10,16 @@
 // two reads of one state agree exactly, and the sum over the bricks of a decomposition is the one-brick histogram.
 #include "mdp_common.h"
 
-#include <rocprim/rocprim.hpp>
-
 namespace {
 
-constexpr int kRdfTypes = 16;          // type codes 0 .. 15: 0 = not a member, t = LAMMPS type t
-constexpr int kRdfOwned = 32;          // code bit: an owned atom (a lane that counts)
+constexpr int kRdfTypes = kBinTypes;   // type codes 0 .. 15: 0 = not a member, t = LAMMPS type t
+constexpr int kRdfOwned = kBinOwned;   // code bit: an owned atom (a lane that counts)
 constexpr int kRdfTabWords = kRdfTypes * kRdfTypes + 2 * kRdfTypes; // column masks per (ti, tj), then i masks, j masks per type
 constexpr int kRdfChunksPerFlush = 64; // a workgroup flushes its 32-bit counters after this many chunks of 256 atoms:
                                        // no counter overflows below 2^32 / (64 * 256) = 262 144 candidates per atom
 constexpr int kRdfCntWords = 3 * MDP_RDF_MAXPAIR + 1; // icount, jcount, dup per column, then the atoms whose tag has no entry
 
 using Grid = MdpGrid;
-
-// cell_index clamps: an atom that has drifted up to skin / 2 past the bounding box of the last reneighbouring lands in an
-// edge cell.  Cells are >= cutoff / 2 wide and the box is padded by more than skin, so the atom is less than one cell
-// outside and the 5-cell stencil around the edge cell still reaches every partner within the cutoff.
-__device__ __forceinline__ int rdf_cell_index(const Grid &g, const double4 &x, int &cx, int &cy, int &cz)
-{
-  cx = (int) ((x.x - g.lo[0]) * g.inv[0]);
-  cy = (int) ((x.y - g.lo[1]) * g.inv[1]);
-  cz = (int) ((x.z - g.lo[2]) * g.inv[2]);
-  cx = cx < 0 ? 0 : (cx >= g.n[0] ? g.n[0] - 1 : cx);
-  cy = cy < 0 ? 0 : (cy >= g.n[1] ? g.n[1] - 1 : cy);
-  cz = cz < 0 ? 0 : (cz >= g.n[2] ? g.n[2] - 1 : cz);
-  return cx + g.n[0] * (cy + g.n[1] * cz);
-}
-
-// key = cell, value = atom; code[i] = (member ? type : 0) | (owned ? kRdfOwned : 0).  An atom whose tag has no entry in the
-// member table is counted in *bad (mdp_rdf_counts refuses the read) and treated as outside the group.
-__global__ __launch_bounds__(256) void rdf_assign_kernel(const Grid g, const int nall, const int nlocal, const int ntypes,
-                                                         const double4 *__restrict__ xq, const int *__restrict__ type,
-                                                         const int *__restrict__ tag, const int ntag,
-                                                         const unsigned char *__restrict__ member,
-                                                         unsigned *__restrict__ key, int *__restrict__ val,
-                                                         int *__restrict__ code, unsigned long long *__restrict__ bad)
-{
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nall) return;
-  int cx, cy, cz;
-  key[i] = (unsigned) rdf_cell_index(g, xq[i], cx, cy, cz);
-  val[i] = i;
-  int t = type[i];
-  if (t < 1 || t > ntypes) t = 0; // (a type no column can name)
-  if (member) {
-    const int tg = tag[i];
-    if (tg < 1 || tg > ntag) {
-      atomicAdd(bad, 1ull);
-      t = 0;
-    } else if (!member[tg - 1])
-      t = 0;
-  }
-  code[i] = t | (i < nlocal ? kRdfOwned : 0);
-}
-
-// cell_start[c] .. cell_start[c + 1] delimit cell c in the sorted order, filled for every cell up to the last occupied
-// one (rdf_tail_kernel: the rest); rec[p] = {x, y, z, code} of the atom at place p, the code in the low word of w
-__global__ __launch_bounds__(256) void rdf_bounds_kernel(const int nall, const unsigned *__restrict__ key_sorted,
-                                                         const int *__restrict__ perm, const double4 *__restrict__ xq,
-                                                         const int *__restrict__ code, int *__restrict__ cell_start,
-                                                         double4 *__restrict__ rec)
-{
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= nall) return;
-  const int a = perm[p];
-  double4 r = xq[a];
-  r.w = __hiloint2double(0, code[a]);
-  rec[p] = r;
-  const unsigned k = key_sorted[p];
-  const unsigned kprev = p == 0 ? 0u : key_sorted[p - 1];
-  if (p == 0)
-    for (unsigned c = 0; c <= k; c++) cell_start[c] = 0;
-  else
-    for (unsigned c = kprev + 1; c <= k; c++) cell_start[c] = p;
-}
-
-__global__ void rdf_tail_kernel(const int nall, const int ncell, const unsigned *__restrict__ key_sorted,
-                                int *__restrict__ cell_start)
-{
-  const unsigned last = key_sorted[nall - 1];
-  for (int c = (int) last + 1 + threadIdx.x; c <= ncell; c += blockDim.x) cell_start[c] = nall;
-}
 
 // adds the workgroup's non-zero LDS counters to the global ones and clears them; every lane of the workgroup calls it
 __device__ __forceinline__ void rdf_flush(unsigned *lds, const int n, unsigned long long *__restrict__ glob)
@@ -139,7 +69,7 @@ __global__ __launch_bounds__(256) void rdf_hist_kernel(const Grid g, const int n
       if (im) {
         const int *row = tab + kRdfTypes * ti;
         int cx, cy, cz;
-        rdf_cell_index(g, xi, cx, cy, cz);
+        mdp_bin_cell_index(g, xi, cx, cy, cz);
         const int x0 = max(cx - 2, 0), x1 = min(cx + 2, g.n[0] - 1);
         for (int z = max(cz - 2, 0); z <= min(cz + 2, g.n[2] - 1); z++)
           for (int y = max(cy - 2, 0); y <= min(cy + 2, g.n[1] - 1); y++) {
@@ -171,39 +101,6 @@ __global__ __launch_bounds__(256) void rdf_hist_kernel(const Grid g, const int n
     if (lc[k]) atomicAdd(cnt + k, (unsigned long long) lc[k]);
 }
 
-int rdf_require(mdp_ctx *c, const char *who)
-{
-  if (!c) return MDP_EINVAL;
-  if (!c->md) return mdp_fail(c, MDP_ESTATE, "mdp_md_setup not called");
-  if (!c->dd.on) return mdp_fail(c, MDP_ESTATE, "%s: mdp_dd_setup not called (the ghost shell of the brick holds the partners)", who);
-  MDP_HIP(c, hipSetDevice(c->device));
-  return MDP_OK;
-}
-
-// the grid of a read: cells >= cutoff / 2 wide over the padded hull of the brick (mdp_dd_borders_end), and no more cells
-// than a few per atom -- wider cells are still correct with the 5-cell stencil
-void rdf_grid(const mdp_ctx *c, const double cutoff, Grid &g, long long &ncell)
-{
-  double binsize = 0.5 * cutoff;
-  const long long cap = 4ll * c->nall + 4096;
-  for (;;) {
-    ncell = 1;
-    for (int d = 0; d < 3; d++) {
-      const double len = c->cfg.bbox_hi[d] - c->cfg.bbox_lo[d];
-      int n = (int) floor(len / binsize);
-      if (n < 1) n = 1;
-      if (n > 1024) n = 1024;
-      g.n[d] = n;
-      g.lo[d] = c->cfg.bbox_lo[d];
-      g.inv[d] = n / len;
-      ncell *= n;
-    }
-    if (ncell <= cap) break;
-    binsize *= 1.26;
-  }
-  g.range = 2;
-}
-
 } // namespace
 
 void mdp_rdf_release(mdp_ctx *c)
@@ -211,14 +108,7 @@ void mdp_rdf_release(mdp_ctx *c)
   MdpRdf &h = c->rdf;
   h.member.release();
   h.tab.release();
-  h.key_a.release();
-  h.key_b.release();
-  h.val_a.release();
-  h.perm.release();
-  h.code.release();
-  h.cell_start.release();
-  h.rec.release();
-  h.sort_tmp.release();
+  h.bin.release();
   h.out.release();
   h.on = false;
 }
@@ -228,13 +118,13 @@ extern "C" {
 int mdp_rdf_setup(mdp_ctx *c, int nbin, double cutoff, int npair, const int *ilo, const int *ihi, const int *jlo,
                   const int *jhi, int ntag, const unsigned char *member_by_tag)
 {
-  MDP_TRY(rdf_require(c, "mdp_rdf_setup"));
+  MDP_TRY(mdp_measure_require(c, "mdp_rdf_setup"));
   if (nbin < 1) return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: nbin must be >= 1, not %d", nbin);
   if (npair < 1 || npair > MDP_RDF_MAXPAIR)
     return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: npair must be 1 .. %d, not %d", MDP_RDF_MAXPAIR, npair);
   if (!ilo || !ihi || !jlo || !jhi) return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: no type ranges");
   // mdp_md_setup admits 1 .. 15 atom types, which is what the 4-bit type code of a record and the 16 x 16 mask table hold:
-  // the check below cannot fire on a context that passed rdf_require, and stands for a later change of that limit
+  // the check below cannot fire on a context that passed mdp_measure_require, and stands for a later change of that limit
   const int ntypes = c->ntypes > 0 ? c->ntypes : c->cfg.ntypes;
   if (ntypes < 1 || ntypes >= kRdfTypes)
     return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: %d atom types (the type code of a record holds 1 .. %d)", ntypes, kRdfTypes - 1);
@@ -287,7 +177,7 @@ int mdp_rdf_setup(mdp_ctx *c, int nbin, double cutoff, int npair, const int *ilo
 
 int mdp_rdf_counts(mdp_ctx *c, long long *hist, long long *icount, long long *jcount, long long *dup)
 {
-  MDP_TRY(rdf_require(c, "mdp_rdf_counts"));
+  MDP_TRY(mdp_measure_require(c, "mdp_rdf_counts"));
   if (!hist || !icount || !jcount || !dup) return MDP_EINVAL;
   MdpRdf &h = c->rdf;
   if (!h.on) return mdp_fail(c, MDP_ESTATE, "mdp_rdf_setup not called");
@@ -304,28 +194,7 @@ int mdp_rdf_counts(mdp_ctx *c, long long *hist, long long *icount, long long *jc
   MDP_HIP(c, hipMemsetAsync(h.out.p, 0, sizeof(unsigned long long) * nout, st));
   if (nall > 0 && c->nlocal > 0) {
     Grid g;
-    long long ncell;
-    rdf_grid(c, h.cutoff, g, ncell);
-    MDP_HIP(c, h.key_a.reserve((size_t) nall + 1));
-    MDP_HIP(c, h.key_b.reserve((size_t) nall + 1));
-    MDP_HIP(c, h.val_a.reserve((size_t) nall + 1));
-    MDP_HIP(c, h.perm.reserve((size_t) nall + 1));
-    MDP_HIP(c, h.code.reserve((size_t) nall + 1));
-    MDP_HIP(c, h.rec.reserve((size_t) nall + 1));
-    MDP_HIP(c, h.cell_start.reserve((size_t) ncell + 2));
-    rdf_assign_kernel<<<nblk(nall), 256, 0, st>>>(g, nall, c->nlocal, h.ntypes, c->xq.p, c->type.p, c->tag.p, h.ntag,
-                                                  h.ntag ? h.member.p : nullptr, h.key_a.p, h.val_a.p, h.code.p,
-                                                  d_cnt + kRdfCntWords - 1);
-    MDP_HIP(c, hipGetLastError());
-    int bits = 1;
-    while ((1ll << bits) < ncell) bits++;
-    size_t tmp = 0;
-    MDP_HIP(c, rocprim::radix_sort_pairs(nullptr, tmp, h.key_a.p, h.key_b.p, h.val_a.p, h.perm.p, (size_t) nall, 0, bits, st));
-    MDP_HIP(c, h.sort_tmp.reserve(tmp + 16));
-    MDP_HIP(c, rocprim::radix_sort_pairs(h.sort_tmp.p, tmp, h.key_a.p, h.key_b.p, h.val_a.p, h.perm.p, (size_t) nall, 0, bits, st));
-    rdf_bounds_kernel<<<nblk(nall), 256, 0, st>>>(nall, h.key_b.p, h.perm.p, c->xq.p, h.code.p, h.cell_start.p, h.rec.p);
-    rdf_tail_kernel<<<1, 256, 0, st>>>(nall, (int) ncell, h.key_b.p, h.cell_start.p);
-    MDP_HIP(c, hipGetLastError());
+    MDP_TRY(mdp_measure_bin(c, h.bin, h.cutoff, h.ntypes, h.ntag, h.member.p, d_cnt + kRdfCntWords - 1, g));
     const int nchunk = nblk(nall);
     if (c->num_cu <= 0) {
       int n = 0;
@@ -338,8 +207,8 @@ int mdp_rdf_counts(mdp_ctx *c, long long *hist, long long *icount, long long *jc
     const int grid = nchunk < per_cu * cus ? nchunk : per_cu * cus;
     // every pair with (int) (r nbin / cutoff) < nbin has rsq below this; the bin index decides
     const double cutsq_hi = h.cutoff * h.cutoff * (1.0 + 1e-9);
-    rdf_hist_kernel<<<grid, 256, lds, st>>>(g, nall, nchunk, h.nbin, h.npair, (double) h.nbin / h.cutoff, cutsq_hi, h.rec.p,
-                                            h.cell_start.p, h.tab.p, d_hist, d_cnt);
+    rdf_hist_kernel<<<grid, 256, lds, st>>>(g, nall, nchunk, h.nbin, h.npair, (double) h.nbin / h.cutoff, cutsq_hi, h.bin.rec.p,
+                                            h.bin.cell_start.p, h.tab.p, d_hist, d_cnt);
     MDP_HIP(c, hipGetLastError());
   }
   std::vector<unsigned long long> host((size_t) nout);

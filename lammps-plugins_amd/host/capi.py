@@ -91,6 +91,8 @@ LANGEVIN_MAXBATH = 4         # MDP_LANGEVIN_MAXBATH of include/mdpair_hip.h
 STYLE_REBOMOS, STYLE_AEAM = 1, 2
 PROFILE_W = 5                # MDP_PROFILE_W of include/mdpair_hip.h
 PROFILE_MAXBINS = 1 << 20
+ADF_DEGREE, ADF_RADIAN, ADF_COSINE = 0, 1, 2     # MDP_ADF_* of include/mdpair_hip.h
+ADF_ORDINATES = dict(degree=ADF_DEGREE, radian=ADF_RADIAN, cosine=ADF_COSINE)
 
 EXPORTS = [
     "mdp_abi_version", "mdp_device_count", "mdp_create", "mdp_destroy", "mdp_last_error", "mdp_set_stream",
@@ -120,6 +122,7 @@ EXPORTS = [
     "mdp_md_set_mask", "mdp_hnve_set_mask", "mdp_integrate_group", "mdp_langevin_group",
     "mdp_md_set_image", "mdp_md_download_unwrapped", "mdp_msd_setup", "mdp_msd_sums", "mdp_msd_info", "mdp_msd_off",
     "mdp_rdf_setup", "mdp_rdf_counts", "mdp_rdf_info", "mdp_rdf_off",
+    "mdp_adf_setup", "mdp_adf_counts", "mdp_adf_info", "mdp_adf_off",
     "mdp_profile_setup", "mdp_profile_range", "mdp_profile_exponent", "mdp_profile_sums", "mdp_profile_info", "mdp_profile_off",
     "mdp_rebomos_centre_paths",
     "mdp_heatflux_sums", "mdp_md_download_vatom",
@@ -976,6 +979,38 @@ class Context:
 
     def rdf_off(self):
         self._ck(self.L.mdp_rdf_off(self.h))
+
+    # ---------------- bond-angle histograms: the angular distribution function (csrc/adf.hip)
+    def adf_setup(self, nbin, ordinate, triples, member_by_tag=None):
+        """starts a measurement: triples = [(ilo, ihi, jlo, jhi, klo, khi, rjin, rjout, rkin, rkout), ...] with inclusive ranges
+        of LAMMPS types and the two shells, one pair of columns each; ordinate ADF_DEGREE / _RADIAN / _COSINE or its name;
+        member_by_tag as in rdf_setup"""
+        tr = np.ascontiguousarray(triples, dtype=np.float64).reshape(-1, 10)
+        ty = [np.ascontiguousarray(tr[:, k], dtype=np.int32) for k in range(6)]
+        rr = [np.ascontiguousarray(tr[:, k]) for k in range(6, 10)]
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        mem = None if member_by_tag is None else np.ascontiguousarray(np.asarray(member_by_tag) != 0, dtype=np.uint8)
+        self._ck(self.L.mdp_adf_setup(self.h, C.c_int(int(nbin)), C.c_int(int(ADF_ORDINATES.get(ordinate, ordinate))), C.c_int(len(tr)),
+                                      *[_ip(a) for a in ty], *[dp(a) for a in rr], C.c_int(0 if mem is None else len(mem)),
+                                      None if mem is None else mem.ctypes.data_as(C.POINTER(C.c_ubyte))))
+
+    def adf_counts(self):
+        """this rank's (hist[ntriple][nbin], icount[ntriple]) as int64"""
+        info = self.adf_info()
+        hist = np.zeros((max(info["ntriple"], 1), max(info["nbin"], 1)), dtype=np.int64)
+        icount = np.zeros(len(hist), dtype=np.int64)
+        lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_longlong))
+        self._ck(self.L.mdp_adf_counts(self.h, lp(hist), lp(icount)))
+        return hist, icount
+
+    def adf_info(self):
+        """whether a measurement is on, its nbin and ntriple, and its serial (unique in the process per adf_setup)"""
+        out = (C.c_longlong * 4)()
+        self._ck(self.L.mdp_adf_info(self.h, out))
+        return dict(on=bool(out[0]), nbin=int(out[1]), ntriple=int(out[2]), serial=int(out[3]))
+
+    def adf_off(self):
+        self._ck(self.L.mdp_adf_off(self.h))
 
     # ---------------- binned mass, momentum and kinetic energy (csrc/profile.hip)
     def profile_setup(self, dims, nbins, group_bit=0):

@@ -141,6 +141,29 @@ def rdf_normalise(hist, icount, jcount, dup, cutoff, volume):
     return out
 
 
+ADF_RANGE = dict(degree=(0.0, 180.0), radian=(0.0, np.pi), cosine=(-1.0, 1.0))
+
+
+def adf_normalise(hist, icount, nbin, ordinate="degree", cumulative="fraction"):
+    """compute adf/mdp's array [nbin][1 + 2 ntriple] from rank-summed counts (DeviceDomain.adf_read): column 0 the bin
+    centres of the ordinate, then per triple hist / (count delta) with count = sum(hist) (it integrates to 1; 0 without a
+    count) and the running sum of hist over count (cumulative fraction) or over icount (cumulative centre: angles per
+    central atom)."""
+    hist = np.atleast_2d(np.asarray(hist, dtype=np.float64))
+    lo, hi = ADF_RANGE[ordinate]
+    delta = (hi - lo) / nbin
+    out = np.zeros((nbin, 1 + 2 * len(hist)))
+    out[:, 0] = lo + (np.arange(nbin) + 0.5) * delta
+    for m, h in enumerate(hist):
+        count = h.sum()
+        den = count if cumulative == "fraction" else float(icount[m])
+        if cumulative not in ("fraction", "centre"):
+            raise ValueError(f"adf_normalise: cumulative {cumulative!r}")
+        out[:, 1 + 2 * m] = h / (count * delta) if count > 0 else 0.0
+        out[:, 2 + 2 * m] = np.cumsum(h) / den if den > 0 else 0.0
+    return out
+
+
 def profile_split(q):
     """an int64 array as two float64 arrays (q >> 31, q & (2^31 - 1)): both halves, and their sums over up to 2^22 ranks, are
     whole numbers below 2^53, so a transport that adds doubles adds them exactly"""
@@ -582,6 +605,30 @@ class DeviceDomain:
 
     def rdf_off(self):
         self.ctx.rdf_off()
+
+    # ------------------------------------------------------------------ bond-angle distributions
+    def adf(self, nbin, triples, ordinate="degree", member_by_tag=None):
+        """starts a bond-angle histogram (LAMMPS compute adf) of nbin bins.  triples: one (itype, jtype, ktype, rjin, rjout,
+        rkin, rkout) per pair of columns, each type a LAMMPS type or an inclusive range (lo, hi), the outer radii at most
+        cutghost - skin.  ordinate: degree, radian or cosine.  member_by_tag as in rdf.  With several ranks every rank makes
+        the same call."""
+        rng = lambda t: (int(t), int(t)) if np.ndim(t) == 0 else (int(t[0]), int(t[1]))
+        rows = [rng(t[0]) + rng(t[1]) + rng(t[2]) + tuple(float(r) for r in t[3:7]) for t in triples]
+        self._adf = dict(nbin=int(nbin), ordinate=ordinate, triples=rows)
+        self.ctx.adf_setup(nbin, ordinate, rows, member_by_tag)
+
+    def adf_read(self):
+        """(hist[ntriple][nbin], icount[ntriple]) as int64, summed over the ranks through the domain's transport;
+        adf_normalise makes the compute's array of them"""
+        self.flush()
+        hist, ic = self.ctx.adf_counts()
+        flat = np.concatenate([hist.ravel(), ic])
+        assert int(flat.max(initial=0)) < 2 ** 53          # (the transports sum doubles: exact below 2^53)
+        tot = np.rint(self._group_sum(flat.astype(np.float64))).astype(np.int64)
+        return tot[:hist.size].reshape(hist.shape), tot[hist.size:]
+
+    def adf_off(self):
+        self.ctx.adf_off()
 
     # ------------------------------------------------------------------ temperature, density and flow profiles
     def profile(self, dims, nbins, group_bit=0):

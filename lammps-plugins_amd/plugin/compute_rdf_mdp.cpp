@@ -26,30 +26,6 @@
 
 using namespace LAMMPS_NS;
 
-namespace {
-// a LAMMPS type argument N, *, N*, *M or N*M over 1 .. ntypes (utils::bounds)
-bool type_bounds(const std::string &s, const int ntypes, int &lo, int &hi)
-{
-  const size_t star = s.find('*');
-  long long a = 0, b = 0;
-  if (star == std::string::npos) {
-    if (!mdp_whole(s.c_str(), a)) return false;
-    b = a;
-  } else {
-    const std::string l = s.substr(0, star), r = s.substr(star + 1);
-    if (r.find('*') != std::string::npos) return false;
-    a = 1;
-    b = ntypes;
-    if (!l.empty() && !mdp_whole(l.c_str(), a)) return false;
-    if (!r.empty() && !mdp_whole(r.c_str(), b)) return false;
-  }
-  if (a < 1 || b > ntypes || a > b) return false;
-  lo = (int) a;
-  hi = (int) b;
-  return true;
-}
-}    // namespace
-
 ComputeRDFMDP::ComputeRDFMDP(LAMMPS *lmp, int narg, char **arg)
     : ComputeMDP(lmp, narg, arg, "rdf/mdp", "there is no pair to count"), nbin(0), npairs(0), cutflag(0), cutoff_user(0.0), cutoff(0.0)
 {
@@ -79,7 +55,7 @@ ComputeRDFMDP::ComputeRDFMDP(LAMMPS *lmp, int narg, char **arg)
     for (int m = 0; m < npairs; m++)
       for (int s = 0; s < 2; s++) {
         const char *a = arg[4 + 2 * m + s];
-        if (!type_bounds(a, ntypes, s ? jlo[m] : ilo[m], s ? jhi[m] : ihi[m]))
+        if (!mdp_type_bounds(a, ntypes, s ? jlo[m] : ilo[m], s ? jhi[m] : ihi[m]))
           error->all(FLERR, head + "type " + a + " is not N, *, N*, *M or N*M within 1 .. " + std::to_string(ntypes));
       }
   }
