@@ -321,7 +321,7 @@ int mdp_adf_counts(mdp_ctx *c, long long *hist, long long *icount)
     const size_t lds = adf_lds_bytes(nhist);
     // as many resident workgroups as the LDS of a CU (160 KB) holds of them, 8 at the most (32 waves per CU)
     const int fit = (int) ((size_t) 144 * 1024 / lds), per_cu = fit < 1 ? 1 : (fit > 8 ? 8 : fit), cus = c->num_cu;
-    const int grid = nchunk < per_cu * cus ? nchunk : per_cu * cus;
+    const int grid = mdp_measure_grid(nchunk, per_cu * cus);
     const int cosine = h.ordinate == MDP_ADF_COSINE;
     adf_hist_kernel<<<grid, 256, lds, st>>>(g, nall, nchunk, h.nbin, h.ntriple, cosine, cosine ? 0.5 * h.nbin : h.nbin / M_PI,
                                             h.rmax * h.rmax, h.bin.rec.p, h.bin.cell_start.p, (const unsigned *) h.tab.p, d_hist, d_cnt);

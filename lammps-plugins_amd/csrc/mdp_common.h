@@ -1197,6 +1197,9 @@ int mdp_measure_bin(mdp_ctx *c, MdpBinning &b, double cutoff, int ntypes, int nt
                     unsigned long long *d_bad, MdpGrid &g);
 // what a setup or a read of such a measurement needs: a resident context with mdp_dd_setup, on its device
 int mdp_measure_require(mdp_ctx *c, const char *who);
+// the workgroups of a histogram kernel that strides over nchunk chunks: min(nchunk, resident), and no more than the test
+// hook MDP_MEASURE_GRID when that is a positive integer (read at every read; the sums are integers, so any value reads the same)
+int mdp_measure_grid(int nchunk, int resident);
 void mdp_profile_release(mdp_ctx *c); // frees what profile.hip holds
 void mdp_heatflux_release(mdp_ctx *c); // frees what heatflux.hip holds
 // the end of an mdp_{msd,rdf,profile}_setup: the measurement is on, under a serial that is new in this process (one

@@ -102,6 +102,15 @@ int mdp_measure_require(mdp_ctx *c, const char *who)
   return MDP_OK;
 }
 
+int mdp_measure_grid(const int nchunk, const int resident)
+{
+  int grid = nchunk < resident ? nchunk : resident;
+  const char *e = getenv("MDP_MEASURE_GRID");
+  const int knob = e ? atoi(e) : 0;
+  if (knob > 0 && knob < grid) grid = knob;
+  return grid;
+}
+
 int mdp_measure_bin(mdp_ctx *c, MdpBinning &b, const double cutoff, const int ntypes, const int ntag,
                     const unsigned char *d_member, unsigned long long *d_bad, MdpGrid &g)
 {

@@ -204,7 +204,7 @@ int mdp_rdf_counts(mdp_ctx *c, long long *hist, long long *icount, long long *jc
     const size_t lds = sizeof(unsigned) * ((size_t) nhist + kRdfCntWords + kRdfTabWords);
     // as many resident workgroups as the LDS of a CU (160 KB) holds histograms, 8 at the most (32 waves per CU)
     const int fit = (int) ((size_t) 144 * 1024 / lds), per_cu = fit < 1 ? 1 : (fit > 8 ? 8 : fit), cus = c->num_cu;
-    const int grid = nchunk < per_cu * cus ? nchunk : per_cu * cus;
+    const int grid = mdp_measure_grid(nchunk, per_cu * cus);
     // every pair with (int) (r nbin / cutoff) < nbin has rsq below this; the bin index decides
     const double cutsq_hi = h.cutoff * h.cutoff * (1.0 + 1e-9);
     rdf_hist_kernel<<<grid, 256, lds, st>>>(g, nall, nchunk, h.nbin, h.npair, (double) h.nbin / h.cutoff, cutsq_hi, h.bin.rec.p,

@@ -12,7 +12,7 @@ For each net NAME of NETS:
   line_NAME(spec, errors)     the report line of the case.
 
 spec["env"] holds the library's environment knobs of the case (MDP_INNER_SKIN, MDP_PRUNE, MDP_LJ_QUEUE,
-MDP_PRUNE_BUFFER).  A case runs with exactly these set and the others unset: the caller applies them (knobs() here,
+MDP_PRUNE_BUFFER, MDP_MEASURE_GRID).  A case runs with exactly these set and the others unset: the caller applies them (knobs() here,
 monkeypatch under pytest); run_NAME never writes os.environ.  spec["id"] is the short text of a test id."""
 from __future__ import annotations
 
@@ -26,7 +26,7 @@ import numpy as np
 
 from lammps_plugins_amd.host import system as S
 
-KNOBS = ("MDP_INNER_SKIN", "MDP_PRUNE", "MDP_LJ_QUEUE", "MDP_PRUNE_BUFFER")
+KNOBS = ("MDP_INNER_SKIN", "MDP_PRUNE", "MDP_LJ_QUEUE", "MDP_PRUNE_BUFFER", "MDP_MEASURE_GRID")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "lammps-plugins_amd")
 
@@ -45,6 +45,7 @@ SUITE = {
     "fire": [(4, 16)],
     "langevin": [(42, 14)],
     "heat": [(2, 12)],
+    "measure": [(4, 16)],
 }
 
 
@@ -1338,6 +1339,403 @@ def line_heat(spec, err):
             f"builds {err['builds']}")
 
 
+# ------------------------------------------------------------------------------------------------------------ measure
+# compute rdf/mdp and compute adf/mdp (csrc/rdf.hip, csrc/adf.hip behind csrc/measure_bin.hip), both set up on one context
+# per rank, against the brute-force references tests/rdfref.py and tests/adfref.py on positions merged by tag from the same
+# run: MoS2 replicas (1,1,1) - (2,2,2) or the alloy at 5 - 8 cells (sheared in some cases, relabelled to 3 - 12 types in
+# some), jittered and at 300 - 2 500 K, some with a drift; 1, 2, 3, 4 or 8 bricks of the thread transport, a free dimension
+# in some one-brick alloy cases; no group, a slab, a modulus class of the tags, 2 - 3 atoms or every atom of one type left
+# out; 1 - 32 columns and triples with random type ranges, 1 - 8192 / columns bins, cutoffs from just above the first
+# shell (where the cap of bin_grid widens the cells) to cutghost - skin, shells with random radii (no centre with more
+# than 100 neighbours at the start: the cap is 128), every ordinate; MDP_MEASURE_GRID unset or 1, 3, 64 (a workgroup
+# then walks several chunks and, at 1, flushes inside its loop).  Reads at step 0, in between and at the end, each taken
+# twice.  The references bracket in integers, so there is no tolerance: every error is a count that must be 0, except the
+# reference's own edge events (pairs and angles within 1e-9 of a bin edge, neighbours at a shell radius), which the fixed
+# tests cap at 2.  A case that is not about a tiny group holds at least 1e4 rdf entries and 1e4 angles at every read.
+MSR_NPAIR = (1, 2, 5, 17, 32)
+MSR_NTRIPLE = (1, 3, 8, 32)
+MSR_NBIN = (1, 2, 37, 50, 200, 1000, None)      # None: 8192 // columns, the whole LDS histogram
+MSR_COUNTERS = 8192
+MSR_GROUPS = ("none", "slab", "modulus", "tiny", "one type out")
+MSR_ORDINATES = ("degree", "radian", "cosine")
+MSR_GRID = ("1", "3", "64")
+MSR_FIRST = {"rebomos": 2.41, "aeam": 2.86}      # first shell: the Mo-S bond, fcc nearest neighbours
+MSR_LIMIT = {"rebomos": 11.4, "aeam": 6.5}       # cutghost - skin of the bundled potentials (run_measure asserts it)
+MSR_SKIN = {"rebomos": 2.0, "aeam": 1.0}
+MSR_NEIGH = 100                                  # neighbours of a centre inside the largest outer radius, at the start
+MSR_FLOOR, MSR_FLOOR_START = 10 ** 4, 3 * 10 ** 4   # entries and angles of a read; what the draw asks of the start positions
+MSR_EDGE_LIMIT = 3
+_MSR_DRAWN = {}
+
+
+def measure_bin_grid(lens, cutoff, nall):
+    """bin_grid of csrc/measure_bin.hip restated: (cells per dimension, how often the cell width grew by 1.26 from
+    cutoff / 2) over a bounding box with edge lengths lens for nall atoms"""
+    binsize, cap, grown = 0.5 * cutoff, 4 * nall + 4096, 0
+    while True:
+        n = [min(1024, max(1, int(np.floor(l / binsize)))) for l in lens]
+        if n[0] * n[1] * n[2] <= cap:
+            return n, grown
+        binsize *= 1.26
+        grown += 1
+
+
+def measure_domain_lens(box, cutghost):
+    """the edge lengths of the bounding box DeviceDomain sets: the box's corners, cutghost + 2 A further each way.  (On one
+    brick the hull the library sets at a reneighbouring holds this box, so a cell count over it is a lower bound.)"""
+    corners = box.lamda2x(np.array([[i, j, k] for i in (0, 1) for j in (0, 1) for k in (0, 1)], dtype=float))
+    return [float(corners[:, d].max() - corners[:, d].min() + 2.0 * (cutghost + 2.0)) for d in range(3)]
+
+
+def measure_nall_bound(box, n, cutghost, nonperiodic=(0, 0, 0)):
+    """an upper bound of nlocal + nghost on one brick from the density: the atoms of the box and its images inside the
+    ghost shell, lamda from -cutghost / width to 1 + cutghost / width in every periodic dimension, and 5 % more"""
+    hinv = np.linalg.inv(box.h)
+    f = 1.0
+    for d in range(3):
+        if not nonperiodic[d]:
+            f *= 1.0 + 2.0 * cutghost * float(np.linalg.norm(hinv[d]))
+    return int(np.ceil(1.05 * n * f))
+
+
+def measure_grid_grows(spec):
+    """no GPU: the first trial grid of the rdf read of a one-brick case, cells cutoff / 2 wide, exceeds bin_grid's cap"""
+    if spec["ranks"] != 1 or spec["cutoff"] is None:
+        return False
+    box = _msr_start(spec).box
+    cutghost = MSR_LIMIT[spec["style"]] + MSR_SKIN[spec["style"]]
+    nall = measure_nall_bound(box, spec["n"], cutghost, spec["nonperiodic"])
+    return measure_bin_grid(measure_domain_lens(box, cutghost), spec["cutoff"], nall)[1] > 0
+
+
+def _msr_range(rng, nt):
+    lo = rng.randint(1, nt)
+    return lo, rng.randint(lo, nt)
+
+
+def draw_measure(rng):
+    key = rng.getstate()
+    if key in _MSR_DRAWN:     # (the geometry below costs seconds; the draw is a function of the generator's state)
+        import copy
+        spec, after = _MSR_DRAWN[key]
+        rng.setstate(after)
+        return copy.deepcopy(spec)
+    import copy
+    spec = _msr_random(rng)
+    _msr_fit(spec)
+    _MSR_DRAWN[key] = (copy.deepcopy(spec), rng.getstate())
+    return spec
+
+
+def _msr_random(rng):
+    """the draws of a case; _msr_fit then bounds the radii and meets the floors on the start positions without drawing"""
+    style = rng.choice(["rebomos", "aeam"])
+    sd = rng.randrange(1, 10**6)
+    spec = dict(style=style, seed=sd, tilt=None, relabel=None, frac=None, nonperiodic=(0, 0, 0))
+    if style == "rebomos":
+        size = (rng.choice([1, 2]), rng.choice([1, 2]), rng.choice([1, 2]))
+        spec.update(size=size, n=_rebo_n(size), ntypes=2)
+    else:
+        size = rng.choice([5, 6, 7, 8])
+        spec.update(size=size, n=4 * size ** 3, ntypes=2, frac=rng.choice([0.05, 0.2, 0.5]))
+        if rng.random() < 0.4:   # a sheared (triclinic) box, as draw_force shears it
+            spec["tilt"] = [rng.uniform(-0.12, 0.12) * 4.045 * size for _ in range(3)]
+        if rng.random() < 0.5:   # relabelled to 3 - 12 types, as run_aeam_types relabels it
+            spec["relabel"] = rng.choice([(2, 1), (3, 2), (4, 2), (5, 3), (7, 5), (1, 3), (6, 2)])
+            spec["ntypes"] = sum(spec["relabel"])
+    nt = spec["ntypes"]
+    spec["amp"] = rng.choice([0.02, 0.05, 0.08])
+    spec["temp"] = rng.choice([300, 1200, 2500])
+    spec["drift"] = [rng.choice([-60, -30, 0, 25, 40, 70]) for _ in range(3)] if rng.random() < 0.4 else [0, 0, 0]
+    spec["nsteps"] = rng.randint(5, 40)
+    spec["ranks"] = 1 if rng.random() < 0.5 else rng.choice([2, 3, 4, 8])
+    auto, renb = rng.random() < 0.5, rng.choice([3, 5, 8])
+    spec["rebuild"] = "auto" if auto and spec["ranks"] == 1 else renb     # (the device's own check serves one brick only)
+    free = rng.random() < 0.4, rng.randrange(3)
+    if style == "aeam" and spec["ranks"] == 1 and spec["tilt"] is None and free[0]:
+        spec["nonperiodic"] = tuple(int(d == free[1]) for d in range(3))
+        spec["drift"] = [0, 0, 0]
+    spec["between"] = rng.randint(1, spec["nsteps"] - 1)
+    kind = rng.choice(MSR_GROUPS)
+    spec["group"] = dict(kind=kind, axis=rng.randrange(3), lo=rng.uniform(0.0, 0.5), width=rng.uniform(0.3, 0.5), m=rng.choice([2, 3, 5]),
+                         r=rng.randrange(2), count=rng.choice([2, 3]), pick=rng.randrange(10**6), type=rng.randint(1, nt))
+    first, limit = MSR_FIRST[style], MSR_LIMIT[style]
+    # ---- rdf
+    npair = rng.choice(MSR_NPAIR)
+    spec["pairs"] = [_msr_range(rng, nt) + _msr_range(rng, nt) for _ in range(npair)]
+    nbin = rng.choice(MSR_NBIN)
+    spec["nbin_rdf"] = MSR_COUNTERS // npair if nbin is None else min(nbin, MSR_COUNTERS // npair)     # (1000 x 17 is refused)
+    u, small, a, b = rng.random(), rng.random() < 0.4, rng.uniform(1.02, 1.15), rng.uniform(1.02 * first, 0.999 * limit)
+    spec["cutoff"] = None if u < 1.0 / 3.0 else (a * first if small else b)       # None: the limit cutghost - skin
+    spec["small"] = spec["cutoff"] is not None and small
+    # ---- adf; the outer radii are fractions here, of first .. the radius that holds MSR_NEIGH neighbours (_msr_fit)
+    ntriple = rng.choice(MSR_NTRIPLE)
+    spec["triples"] = []
+    for _ in range(ntriple):
+        row = _msr_range(rng, nt) + _msr_range(rng, nt) + _msr_range(rng, nt)
+        for _shell in range(2):
+            near, out = rng.random() < 0.7, rng.random()
+            inner = 0.0 if rng.random() < 0.6 else rng.uniform(0.0, 0.8)
+            row += (inner, (0.25 * out) if near else out)        # (inner as a fraction of the outer radius)
+        spec["triples"].append(row)
+    nbin = rng.choice(MSR_NBIN)
+    spec["nbin_adf"] = MSR_COUNTERS // ntriple if nbin is None else min(nbin, MSR_COUNTERS // ntriple)
+    spec["ordinate"] = rng.choice(MSR_ORDINATES)
+    spec["env"] = {"MDP_MEASURE_GRID": rng.choice(MSR_GRID)} if rng.random() < 0.5 else {}
+    return spec
+
+
+def _msr_start(spec):
+    """no GPU, no oracle: the start system of a case, jittered (placeholder masses; run_measure sets the potential's)"""
+    sd = spec["seed"]
+    if spec["style"] == "rebomos":
+        s = S.replicate(S.rebomos_bulk_cell(), spec["size"])
+    else:
+        s = S.fcc_cell(4.045, spec["size"], frac_type2=spec["frac"], seed=sd)
+        if spec["tilt"] is not None:
+            nb = S.Box(s.box.lo.copy(), s.box.prd.copy(), np.array(spec["tilt"]))
+            s = S.System(nb, nb.lamda2x(s.box.x2lamda(s.x)), s.type, s.tag, s.mass)
+        if spec["relabel"] is not None:
+            nmet, nang = spec["relabel"]
+            r = np.random.default_rng(sd)
+            ty = np.where(s.type == 1, r.integers(1, nmet + 1, s.n), r.integers(nmet + 1, nmet + nang + 1, s.n)).astype(np.int32)
+            s = S.System(s.box, s.x, ty, s.tag, np.array([0.0] + [27.0] * nmet + [28.0] * nang))
+    assert s.n == spec["n"] and np.array_equal(s.tag, np.arange(1, s.n + 1))
+    return S.jitter(s, spec["amp"], seed=sd + 1)
+
+
+def _msr_periodic(spec):
+    return tuple(0 if f else 1 for f in spec["nonperiodic"])
+
+
+def _msr_pairs(s, spec, rmax):
+    import rdfref
+    out = list(rdfref._pairs_in_range(np.ascontiguousarray(s.x), s.box.h, _msr_periodic(spec), rmax))
+    if not out:
+        return np.zeros(0, dtype=int), np.zeros(0, dtype=int), np.zeros(0)
+    return tuple(np.concatenate([o[k] for o in out]) for k in range(3))
+
+
+def measure_member(spec, s, pairs=None):
+    """the member table of the case by tag (row t - 1), or None; s: the start system.  A tiny group is an atom and one or
+    two of its nearest neighbours, so that it holds a pair"""
+    g = spec["group"]
+    if g["kind"] == "none":
+        return None
+    if g["kind"] == "slab":
+        a = s.box.x2lamda(s.x)[:, g["axis"]]
+        return (a >= g["lo"]) & (a < g["lo"] + g["width"])
+    if g["kind"] == "modulus":
+        return s.tag % g["m"] == g["r"]
+    if g["kind"] == "one type out":
+        return s.type != g["type"]
+    if "tags" not in g:
+        pi, pj, pr = _msr_pairs(s, spec, 1.25 * MSR_FIRST[spec["style"]]) if pairs is None else pairs
+        r = np.random.default_rng(g["pick"])
+        i = int(r.integers(0, s.n))
+        near = pj[(pi == i) & (pr < 1.25 * MSR_FIRST[spec["style"]])]
+        near = np.unique(near[near != i])
+        g["tags"] = sorted(int(t) for t in [i + 1] + (r.permutation(near)[:g["count"] - 1] + 1).tolist())
+    m = np.zeros(s.n, dtype=bool)
+    m[np.array(g["tags"]) - 1] = True
+    return m
+
+
+def _msr_in(t, lo, hi):
+    return (t >= lo) & (t <= hi)
+
+
+def measure_start_counts(spec, s, member, pairs):
+    """(rdf entries, angles) of the case on its start positions from the pair list (i, j, r): exact counts, summed over columns"""
+    pi, pj, pr = pairs
+    t = s.type
+    mem = np.ones(s.n, dtype=bool) if member is None else member
+    both = mem[pi] & mem[pj]
+    cutoff = MSR_LIMIT[spec["style"]] if spec["cutoff"] is None else spec["cutoff"]
+    entries = sum(int((both & (pr < cutoff) & _msr_in(t[pi], p[0], p[1]) & _msr_in(t[pj], p[2], p[3])).sum()) for p in spec["pairs"])
+    angles = 0
+    for tr in spec["triples"]:
+        c = both & _msr_in(t[pi], tr[0], tr[1])
+        jq = c & _msr_in(t[pj], tr[2], tr[3]) & (pr >= tr[6]) & (pr < tr[7])
+        kq = c & _msr_in(t[pj], tr[4], tr[5]) & (pr >= tr[8]) & (pr < tr[9])
+        nj, nk, njk = (np.bincount(pi[q], minlength=s.n) for q in (jq, kq, jq & kq))
+        angles += int((nj * nk - njk).sum())
+    return entries, angles
+
+
+def _msr_fit(spec):
+    """no draws: turns the triples' fractions into radii -- between the first shell and the radius inside which no centre
+    has more than MSR_NEIGH neighbours at the start (at most the limit) --, and, for a case that is not about a tiny group,
+    meets MSR_FLOOR_START entries and angles on the start positions: first column 1 / triple 1 over all types, then the
+    cutoff at the limit and triple 1 over the widest shell, then no group"""
+    style, nt = spec["style"], spec["ntypes"]
+    first, limit = MSR_FIRST[style], MSR_LIMIT[style]
+    s = _msr_start(spec)
+    pairs = _msr_pairs(s, spec, limit)
+    pi, pj, pr = pairs
+    # the distance of every centre's neighbour number MSR_NEIGH + 1, if it lies inside the limit
+    order = np.lexsort((pr, pi))
+    start = np.searchsorted(pi[order], np.arange(s.n + 1))
+    full = np.nonzero(np.diff(start) > MSR_NEIGH)[0]
+    rcap = 0.999 * limit
+    if len(full):
+        rcap = min(rcap, 0.999 * float(pr[order][start[full] + MSR_NEIGH].min()))
+    rows = []
+    for tr in spec["triples"]:
+        row = list(tr[:6])
+        for k in (6, 8):
+            rout = 1.05 * first + tr[k + 1] * (rcap - 1.05 * first)
+            row += [tr[k] * rout, rout]
+        rows.append(tuple(float(v) if k >= 6 else int(v) for k, v in enumerate(row)))
+    spec["triples"] = rows
+    spec["rcap"] = float(rcap)
+    member = measure_member(spec, s, pairs)
+    exempt = spec["group"]["kind"] in ("tiny", "one type out")
+    steps = ("all types", "widest", "no group")
+    spec["fitted"] = []
+    if exempt:      # column 1 and triple 1 over all types, so that the few members, or the columns without a centre, stand next to counts
+        spec["pairs"][0] = (1, nt, 1, nt)
+        spec["triples"][0] = (1, nt, 1, nt, 1, nt) + spec["triples"][0][6:]
+    while not exempt:
+        entries, angles = measure_start_counts(spec, s, member, pairs)
+        if (entries >= MSR_FLOOR_START and angles >= MSR_FLOOR_START) or len(spec["fitted"]) == len(steps):
+            break
+        step = steps[len(spec["fitted"])]
+        spec["fitted"].append(step)
+        if step == "all types":
+            spec["pairs"][0] = (1, nt, 1, nt)
+            spec["triples"][0] = (1, nt, 1, nt, 1, nt) + spec["triples"][0][6:]
+        elif step == "widest":
+            spec["cutoff"], spec["small"] = None, False
+            spec["triples"][0] = spec["triples"][0][:6] + (0.0, spec["rcap"], 0.0, spec["rcap"])
+        else:
+            spec["group"]["kind"], member = "none", None
+    g = spec["group"]["kind"].replace(" ", "")
+    spec["id"] = (f"{style}-n{spec['n']}-types{nt}-ranks{spec['ranks']}-{g}-rdf{len(spec['pairs'])}x{spec['nbin_rdf']}-"
+                  f"adf{len(spec['triples'])}x{spec['nbin_adf']}-{spec['ordinate']}-grid{spec['env'].get('MDP_MEASURE_GRID', 'unset')}")
+
+
+def _msr_velocities(spec, s):
+    """start velocities (with the drift) and the steps between forced list builds by the _lgv_system rule"""
+    v0 = S.gaussian_velocities(s, float(spec["temp"]), seed=spec["seed"] + 2) + np.array(spec["drift"], dtype=float)
+    vcap = float(np.sqrt((v0 ** 2).sum(axis=1)).max()) + 5.0 * np.sqrt(S.BOLTZ * spec["temp"] / (float(s.mass[1:].min()) * S.MVV2E))
+    return v0, max(1, int(0.3 * MSR_SKIN[spec["style"]] / (vcap * 0.001)))
+
+
+def measure_references(spec, x, types, h, member):
+    """rdfref.counts and adfref.counts of the case on positions and types by tag"""
+    import adfref
+    import rdfref
+    per = _msr_periodic(spec)
+    cutoff = spec.get("cutoff_used") or spec["cutoff"] or MSR_LIMIT[spec["style"]]
+    return (rdfref.counts(x, types, h, per, cutoff, spec["nbin_rdf"], spec["pairs"], member),
+            adfref.counts(x, types, h, per, spec["nbin_adf"], spec["ordinate"], spec["triples"], member))
+
+
+def _msr_outside(hist, ref):
+    low, high = ref["hist_sure"], ref["hist_sure"] + ref["edge_adjacent"]
+    return int(((hist < low) | (hist > high)).sum())
+
+
+def run_measure(spec):
+    import aeam_five
+    from lammps_plugins_amd.host import capi, resident
+    R = _res()
+    style, skin = spec["style"], MSR_SKIN[spec["style"]]
+    s = _msr_start(spec)
+    tabs = None
+    if style == "rebomos":
+        cutghost = 3.0 * R["rp"].rcmax[0][0] + skin
+    else:
+        af, tabs = R["af"], R["tabs"]
+        if spec["relabel"] is not None:
+            nmet, nang = spec["relabel"]
+            if "tmp" not in R:
+                R["tmp"] = tempfile.mkdtemp()
+            path = os.path.join(R["tmp"], f"p{nmet}_{nang}.aeam")
+            if not os.path.exists(path):
+                aeam_five.write_relabelled_file(path, R["pot_aeam"], [0] * nmet + [1] * nang, ["M%d" % i for i in range(nmet)] + ["X%d" % i for i in range(nang)])
+            af = capi.AeamFile(path)
+            tabs = af.build()
+        s.mass[1:] = af.mass[:spec["ntypes"]]
+        cutghost = float(af.cut_table(tabs).max()) + skin
+    limit = cutghost - skin
+    assert abs(limit - MSR_LIMIT[style]) < 1e-9, limit
+    cutoff = limit if spec["cutoff"] is None else spec["cutoff"]
+    member = measure_member(spec, s)
+    v0, safe = _msr_velocities(spec, s)
+    rebuild = spec["rebuild"] if spec["rebuild"] == "auto" else min(spec["rebuild"], safe)
+    reads = sorted({0, spec["between"], spec["nsteps"]})
+    pairs = [((p[0], p[1]), (p[2], p[3])) for p in spec["pairs"]]
+    triples = [((t[0], t[1]), (t[2], t[3]), (t[4], t[5])) + tuple(t[6:]) for t in spec["triples"]]
+    world = spec["ranks"]
+
+    def rank_fn(r, make_tr):
+        ctx = capi.Context(0)
+        try:
+            if style == "rebomos":
+                ctx.rebomos_set_params(R["rp"])
+                st, map_ = capi.STYLE_REBOMOS, [0, 0, 1]
+            else:
+                ctx.aeam_set_tables(tabs)
+                st, map_ = capi.STYLE_AEAM, None
+            d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0, transport=make_tr(ctx) if world > 1 else None,
+                                      nonperiodic=spec["nonperiodic"])
+            d.rdf(spec["nbin_rdf"], cutoff, pairs, member_by_tag=member)
+            d.adf(spec["nbin_adf"], triples, ordinate=spec["ordinate"], member_by_tag=member)
+            d.compute(0, 0)
+            out = {}
+            for step in range(0, spec["nsteps"] + 1):
+                if step:
+                    d.step(0, 0, rebuild="auto" if rebuild == "auto" else step % rebuild == 0)
+                if step in reads:   # rdf, adf, rdf, adf: the second pair re-reads the state of the first
+                    got = [d.rdf_read(), d.adf_read(), d.rdf_read(), d.adf_read()]
+                    out[step] = dict(tags=d.tags_local.copy(), x=ctx.md_download(d.nlocal, want=("x",))["x"], got=got)
+            return dict(out=out, builds=d.builds, late=d.dangerous)
+        finally:
+            ctx.close()
+
+    res = [rank_fn(0, None)] if world == 1 else resident.run_ranks(world, rank_fn)
+    types = s.type.copy()      # (by tag: the tags are 1 .. n in order)
+    err = dict(rdf_outside=0, adf_outside=0, counts=0, reread=0, ranks=0, edge=0, vacuous=0, not_owned_once=0, late=sum(r["late"] for r in res),
+               builds=res[0]["builds"], entries=None, angles=None, most=0)
+    exempt = spec["group"]["kind"] in ("tiny", "one type out")
+    same = lambda a, b: all(np.array_equal(u, v) for u, v in zip(a, b))
+    spec = dict(spec, cutoff_used=cutoff)
+    for step in reads:
+        x, seen = np.zeros((s.n, 3)), np.zeros(s.n, dtype=int)
+        for r in res:
+            o = r["out"][step]
+            x[o["tags"] - 1] = o["x"]
+            seen[o["tags"] - 1] += 1
+        err["not_owned_once"] += int(not np.all(seen == 1))
+        got = res[0]["out"][step]["got"]
+        for r in res[1:]:
+            err["ranks"] += int(not all(same(a, b) for a, b in zip(r["out"][step]["got"], got)))
+        err["reread"] += int(not (same(got[0], got[2]) and same(got[1], got[3])))
+        rref, aref = measure_references(spec, x, types, s.box.h, member)
+        (hist, ic, jc, du), (ahist, aic) = got[0], got[1]
+        err["rdf_outside"] += _msr_outside(hist, rref)
+        err["adf_outside"] += _msr_outside(ahist, aref)
+        err["counts"] += int(not (same((ic, jc, du), (rref["icount"], rref["jcount"], rref["dup"])) and np.array_equal(aic, aref["icount"])))
+        err["edge"] += rref["n_edge"] + aref["n_edge"] + aref["n_shell_edge"]
+        entries, angles = int(rref["hist"].sum()), int(aref["hist"].sum())
+        err["entries"] = entries if err["entries"] is None else min(err["entries"], entries)
+        err["angles"] = angles if err["angles"] is None else min(err["angles"], angles)
+        err["most"] = max(err["most"], aref["max_neighbours"])
+    err["vacuous"] = 0 if exempt or (err["entries"] >= MSR_FLOOR and err["angles"] >= MSR_FLOOR) else 1
+    return err, dict(rdf_outside=1, adf_outside=1, counts=1, reread=1, ranks=1, edge=MSR_EDGE_LIMIT, vacuous=1, not_owned_once=1, late=1)
+
+
+def line_measure(spec, err):
+    cut = "limit" if spec["cutoff"] is None else f"{spec['cutoff']:.3f}"
+    return (f"{spec['id']} size {spec['size']} tilt {spec['tilt'] is not None} relabel {spec['relabel']} free {spec['nonperiodic']} T {spec['temp']} "
+            f"drift {spec['drift']} steps {spec['nsteps']} rebuild {spec['rebuild']} read also at {spec['between']} cutoff {cut} "
+            f"rcap {spec['rcap']:.2f} fitted {spec['fitted']} seed {spec['seed']} rdf outside {err['rdf_outside']} adf outside {err['adf_outside']} "
+            f"counts {err['counts']} reread {err['reread']} ranks {err['ranks']} edge {err['edge']} entries {err['entries']} angles {err['angles']} "
+            f"most neighbours {err['most']} vacuous {err['vacuous']} owned once {not err['not_owned_once']} late {err['late']} builds {err['builds']}")
+
+
 # ---------------------------------------------------------------------------------------------------------------- nvt
 # The Nose-Hoover chain thermostat (tests/test_gpu_nvt_net.py): chains of 1-8, 1-3 loops, drag, flat or ramped targets,
 # both styles, the resident path and (REBO-MoS) the host-linked one, atom counts whose last 256-atom block varies.
@@ -1367,7 +1765,7 @@ def nvt_cases(seed, ncase):
 
 
 NETS = {name: (globals()["draw_" + name], globals()["run_" + name], globals()["line_" + name])
-        for name in ("force", "hostmode_walk", "aeam_types", "prune", "dd", "hnve", "minilmp", "trajectory", "block", "fire", "langevin", "heat")}
+        for name in ("force", "hostmode_walk", "aeam_types", "prune", "dd", "hnve", "minilmp", "trajectory", "block", "fire", "langevin", "heat", "measure")}
 
 
 def main(net, argv):

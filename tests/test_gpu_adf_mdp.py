@@ -14,9 +14,10 @@ import pytest
 
 from conftest import POT_AEAM, POT_REBOMOS  # noqa: F401  (the potentials _context reads)
 from lammps_plugins_amd.host import capi, resident, system as S
-from test_gpu_rdf_mdp import (MIG_READS, MIG_RENB, MIG_STEPS, PAIRS, _by_tag, _context, _mig_member, _mig_system, _system,
-                              _x_by_tag)
+from test_gpu_rdf_mdp import (MIG_READS, MIG_RENB, MIG_STEPS, PAIRS, SMALL_CUTOFF, TYPE_RANGES, _by_tag, _context, _five_context,
+                              _five_types, _mig_member, _mig_system, _nall, _system, _x_by_tag)
 import adfref
+import nets
 
 pytestmark = pytest.mark.gpu
 
@@ -103,6 +104,164 @@ def test_one_brick(style, temp, capsys):
             assert np.array_equal(hist2[free], hist[free])
         else:
             assert not np.array_equal(hist2, hist)
+    finally:
+        ctx.close()
+
+
+# ---- the slots test_one_brick leaves empty, as in tests/test_gpu_rdf_mdp.py
+def _triples32():
+    """32 triples over the 5 types of _five_types with pairwise different type ranges and shells: triple m takes every 97th
+    of the 15^3 range triples, j-shell 0 .. 3.0 + 0.1 m (3.0 - 6.1 A), k-shell 0.05 m .. 6.4 - 0.1 m (6.4 - 3.3 A)"""
+    all3 = [a + b + c for a in TYPE_RANGES for b in TYPE_RANGES for c in TYPE_RANGES][::97]
+    return [all3[m] + (0.0, 3.0 + 0.1 * m, 0.05 * m, 6.4 - 0.1 * m) for m in range(32)]
+
+
+def test_8192_counters_and_triple_32(capsys):
+    """32 triples x 256 bins, all the LDS histogram holds, on the alloy relabelled to 5 types; triple 32 (mask bit 31) is not
+    empty, and no two triples hold the same histogram"""
+    s, v0, af, tabs = _five_types()
+    rows = _triples32()
+    assert len({r[:6] for r in rows}) == 32 and len({r[6:] for r in rows}) == 32
+    ctx, st, skin, cutghost, map_ = _five_context()
+    try:
+        assert max(max(r[7], r[9]) for r in rows) < cutghost - skin
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        d.adf(256, [((r[0], r[1]), (r[2], r[3]), (r[4], r[5])) + r[6:] for r in rows])
+        d.compute(0, 0)
+        for _ in range(10):
+            d.step(0, 0, rebuild="auto")
+        hist, ic = d.adf_read()
+        assert hist.shape == (32, 256) and ctx.adf_info()["nbin"] * ctx.adf_info()["ntriple"] == 8192
+        ref = adfref.counts(_x_by_tag(d, s.n), s.type, s.box.h, PER, 256, "degree", rows)
+        with capsys.disabled():
+            print(f"{int(hist.sum())} angles, triple 32: {int(hist[31].sum())}, {ref['n_edge']} edge angles, at most {ref['max_neighbours']} neighbours")
+        adfref.check_bracket(hist, ref)
+        assert np.array_equal(ic, ref["icount"]) and ref["max_neighbours"] <= MAXNEIGH
+        assert ref["hist_sure"][31].sum() > 1000 and all(ref["hist_sure"][m].sum() > 0 for m in range(32))
+        assert len({ref["hist"][m].tobytes() for m in range(32)}) == 32
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("style", ["rebomos", "aeam"])
+def test_one_bin(style):
+    """nbin = 1: the one counter of a triple is the number of its angles -- the reference's, and the sum of the 45 bins read
+    on the same state (every angle lands in a bin: there is no cutoff on the ordinate)"""
+    s, v0 = _system(style, 300.0)
+    ctx, st, skin, cutghost, map_ = _context(style)
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        tr = _triples(style)
+        d.compute(0, 0)
+        for _ in range(5):
+            d.step(0, 0, rebuild="auto")
+        d.adf(1, tr, ordinate="cosine")
+        one = d.adf_read()
+        d.adf(NBIN, tr)
+        many = d.adf_read()
+        ref = adfref.counts(_x_by_tag(d, s.n), s.type, s.box.h, PER, 1, "cosine", _rows(tr))
+        adfref.check_bracket(one[0], ref)
+        assert ref["n_edge"] == 0                                     # (one bin has no interior edge)
+        assert one[0].shape == (len(tr), 1) and np.array_equal(one[0], ref["hist"]) and one[0][0, 0] > 1e4
+        assert np.array_equal(one[0][:, 0], many[0].sum(axis=1)) and np.array_equal(one[1], many[1])
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("style", ["rebomos", "aeam"])
+def test_a_small_outer_radius_widens_the_cells(style, capsys):
+    """the largest outer radius just above the first shell: the premise and the systems of test_a_small_cutoff_widens_the_cells
+    (tests/test_gpu_rdf_mdp.py).  A full first shell: 30 ordered pairs of S around every Mo, 6 of Mo around every S; 132 of
+    the 12 nearest neighbours around an alloy atom, less 2.5 % at the most (1 % of the neighbours: 11.88 x 10.88 = 129.3)."""
+    s, v0 = _system(style, 300.0 if style == "rebomos" else 10.0)
+    ctx, st, skin, cutghost, map_ = _context(style)
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        r = SMALL_CUTOFF[style]
+        tr = [(ALL, ALL, ALL, 0.0, r, 0.0, r), (1, 2, 2, 0.0, r, 0.0, r), (2, 1, 1, 0.0, r, 0.0, r), (1, ALL, ALL, 0.5 * r, r, 0.0, 0.9 * r)]
+        d.adf(NBIN, tr)
+        d.compute(0, 0)
+        for _ in range(25):
+            d.step(0, 0, rebuild="auto")
+        nall = _nall(ctx)
+        lens = nets.measure_domain_lens(s.box, cutghost)
+        cells, grown = nets.measure_bin_grid(lens, r, nall)
+        first = nets.measure_bin_grid(lens, r, 10 ** 9)[0]
+        assert grown >= 1 and first[0] * first[1] * first[2] > 4 * nall + 4096, (first, nall)
+        hist, ic = d.adf_read()
+        ref = adfref.counts(_x_by_tag(d, s.n), s.type, s.box.h, PER, NBIN, "degree", _rows(tr))
+        with capsys.disabled():
+            print(f"{style}: outer radius {r} A, nall {nall}, {first} cells against the cap {4 * nall + 4096}, grown {grown} times to {cells}; "
+                  f"{int(hist[0].sum())} angles, {ref['n_edge']} edge angles")
+        adfref.check_bracket(hist, ref)
+        assert np.array_equal(ic, ref["icount"])
+        n1, n2 = int((s.type == 1).sum()), int((s.type == 2).sum())
+        if style == "rebomos":
+            assert hist[1].sum() == 30 * n1 and hist[2].sum() == 6 * n2 and hist[0].sum() >= 30 * n1 + 6 * n2
+        else:
+            assert 0.975 * 132 * s.n <= hist[0].sum() <= 132 * s.n
+    finally:
+        ctx.close()
+
+
+def test_one_workgroup_walks_every_chunk(monkeypatch, capsys):
+    """MDP_MEASURE_GRID = 1 and 3 on the (3, 3, 2) MoS2 replica: the premise and the claim of the test of this name in
+    tests/test_gpu_rdf_mdp.py, for the angle kernel's chunk loop and the flush inside it"""
+    s = S.replicate(S.rebomos_bulk_cell(), (3, 3, 2))
+    v0 = S.gaussian_velocities(s, 300.0, seed=3)
+    ctx, st, skin, cutghost, map_ = _context("rebomos")
+    try:
+        monkeypatch.delenv("MDP_MEASURE_GRID", raising=False)
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        tr = _triples("rebomos")
+        d.adf(NBIN, tr)
+        d.compute(0, 0)
+        for _ in range(5):
+            d.step(0, 0, rebuild="auto")
+        nall = _nall(ctx)
+        assert nall > 16384 and s.n == 5184, nall
+        plain = d.adf_read()
+        ref = adfref.counts(_x_by_tag(d, s.n), s.type, s.box.h, PER, NBIN, "degree", _rows(tr))
+        adfref.check_bracket(plain[0], ref)
+        n1, n2 = int((s.type == 1).sum()), int((s.type == 2).sum())
+        assert plain[0].sum(axis=1)[1:3].tolist() == [30 * n1, 6 * n2]
+        for knob in ("1", "3", "0", ""):          # ("0" and "": the launch as it is)
+            monkeypatch.setenv("MDP_MEASURE_GRID", knob)
+            got = d.adf_read()
+            with capsys.disabled():
+                print(f"MDP_MEASURE_GRID={knob!r}: nall {nall}, {-(-nall // 256)} chunks, differs from the plain read in "
+                      f"{int((got[0] != plain[0]).sum())} counters")
+            adfref.check_bracket(got[0], ref)
+            assert np.array_equal(got[0], plain[0]) and np.array_equal(got[1], plain[1]), knob
+    finally:
+        ctx.close()
+
+
+def test_a_non_periodic_dimension(capsys):
+    """the alloy with free z at 2 500 K: atoms leave the box in z (asserted) and sit in clamped edge cells of the measurement
+    grid; the reference has no images in z.  The first-shell angles are fewer than with images in z: the atoms of the two
+    faces have lost neighbours."""
+    s, v0 = _system("aeam", 2500.0)
+    ctx, st, skin, cutghost, map_ = _context("aeam")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0, nonperiodic=(0, 0, 1))
+        tr = _triples("aeam")
+        d.adf(NBIN, tr)
+        d.compute(0, 0)
+        for _ in range(25):
+            d.step(0, 0, rebuild="auto")
+        hist, ic = d.adf_read()
+        x = _x_by_tag(d, s.n)
+        lamz = s.box.x2lamda(x)[:, 2]
+        below, above = int((lamz < 0.0).sum()), int((lamz >= 1.0).sum())
+        assert below > 5 and above >= 0 and below + above < s.n // 4, (below, above)
+        ref = adfref.counts(x, s.type, s.box.h, (1, 1, 0), NBIN, "degree", _rows(tr))
+        wrapped = adfref.counts(x, s.type, s.box.h, PER, NBIN, "degree", _rows(tr))
+        with capsys.disabled():
+            print(f"{below} atoms below and {above} above the box in z; {int(hist[0].sum())} angles, {int(wrapped['hist'][0].sum())} with images in z")
+        adfref.check_bracket(hist, ref)
+        assert np.array_equal(ic, ref["icount"])
+        assert 1e4 < hist[0].sum() < wrapped["hist"][0].sum()
     finally:
         ctx.close()
 

@@ -9,6 +9,7 @@ import pytest
 
 from conftest import POT_AEAM, POT_REBOMOS
 from lammps_plugins_amd.host import capi, resident, system as S
+import nets
 import rdfref
 
 pytestmark = pytest.mark.gpu
@@ -91,6 +92,201 @@ def test_one_brick(style, temp, capsys):
         assert hist[0][b0 - 1:b0 + 2].sum() > s.n and hist[0][:b0 // 2].sum() == 0
         arr = resident.rdf_normalise(hist, ic, jc, du, cutoff, s.box.volume)
         assert np.allclose(arr, rdfref.normalise(hist, ic, jc, du, cutoff, s.box.volume), rtol=1e-13, atol=1e-13)
+    finally:
+        ctx.close()
+
+
+# ---- the slots test_one_brick leaves empty: 8 192 counters and column 32, one bin, cells widened by bin_grid's cap, a
+# workgroup that walks many chunks (MDP_MEASURE_GRID), a free dimension
+FIVE = (3, 2)                  # the alloy relabelled to 3 metal and 2 angular types
+TYPE_RANGES = [(lo, hi) for lo in range(1, 6) for hi in range(lo, 6)]                    # the 15 inclusive ranges over 5 types
+# 32 of their 120 unordered pairs (a column and its transpose hold the same histogram)
+RANGES32 = [a + b for k, a in enumerate(TYPE_RANGES) for b in TYPE_RANGES[k:]][::3][:32]
+SMALL_CUTOFF = {"rebomos": 2.8, "aeam": 3.0}     # above the first shells (2.41, 2.86 A); test_a_small_cutoff asserts what they are for
+_FIVE = {}
+
+
+def _five_types(temp=300.0):
+    """the 864-atom alloy with 30 % Si relabelled to 5 types as nets.run_aeam_types relabels it: (s, v0, af, tabs)"""
+    import os
+    import tempfile
+    import aeam_five
+    if not _FIVE:
+        nmet, nang = FIVE
+        path = os.path.join(tempfile.mkdtemp(), "five.aeam")
+        aeam_five.write_relabelled_file(path, POT_AEAM, [0] * nmet + [1] * nang, ["M%d" % i for i in range(nmet)] + ["X%d" % i for i in range(nang)])
+        af = capi.AeamFile(path)
+        s2 = S.fcc_cell(4.045, 6, frac_type2=0.3, seed=92)
+        r = np.random.default_rng(5)
+        ty = np.where(s2.type == 1, r.integers(1, nmet + 1, s2.n), r.integers(nmet + 1, nmet + nang + 1, s2.n)).astype(np.int32)
+        _FIVE.update(af=af, tabs=af.build(), s=S.System(s2.box, s2.x.copy(), ty, s2.tag.copy(), np.array([0.0] + list(af.mass))))
+    s = _FIVE["s"]
+    return s, S.gaussian_velocities(s, temp, seed=3), _FIVE["af"], _FIVE["tabs"]
+
+
+def _five_context():
+    s, v0, af, tabs = _five_types()
+    ctx = capi.Context(0)
+    ctx.aeam_set_tables(tabs)
+    return ctx, capi.STYLE_AEAM, 1.0, float(af.cut_table(tabs).max()) + 1.0, None
+
+
+def _nall(ctx):
+    info = ctx.dd_info()
+    return info["nlocal"] + info["nself"] + info["nrecv"]
+
+
+def test_8192_counters_and_column_32(capsys):
+    """32 columns x 256 bins, all the LDS histogram holds, on the alloy relabelled to 5 types: 32 pairwise different pairs
+    of type ranges, so that no column can stand in for another; column 32 (mask bit 31) is not empty and is not column 31"""
+    s, v0, af, tabs = _five_types()
+    assert len(set(RANGES32)) == 32 and len(np.unique(s.type)) == 5
+    ctx, st, skin, cutghost, map_ = _five_context()
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        cutoff = cutghost - skin
+        d.rdf(256, cutoff, [((r[0], r[1]), (r[2], r[3])) for r in RANGES32])
+        d.compute(0, 0)
+        for _ in range(10):
+            d.step(0, 0, rebuild="auto")
+        hist, ic, jc, du = d.rdf_read()
+        assert hist.shape == (32, 256) and ctx.rdf_info()["nbin"] * ctx.rdf_info()["npair"] == 8192
+        ref = rdfref.counts(_x_by_tag(d, s.n), s.type, s.box.h, PER, cutoff, 256, RANGES32)
+        with capsys.disabled():
+            print(f"{int(hist.sum())} entries, column 32: {int(hist[31].sum())}, {ref['n_edge']} edge pairs")
+        rdfref.check_bracket(hist, ref)
+        assert np.array_equal(ic, ref["icount"]) and np.array_equal(jc, ref["jcount"]) and np.array_equal(du, ref["dup"])
+        assert ref["hist_sure"][31].sum() > 1000 and not np.array_equal(ref["hist"][31], ref["hist"][30])
+        assert all(ref["hist_sure"][m].sum() > 0 for m in range(32))
+        assert len({ref["hist"][m].tobytes() for m in range(32)}) == 32            # the columns are pairwise different in what they hold, too
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("style", ["rebomos", "aeam"])
+def test_one_bin(style):
+    """nbin = 1: the one counter of a column is the number of its pairs inside the cutoff -- the reference's, and the sum of
+    the 50 bins read on the same state"""
+    s, v0 = _system(style, 300.0)
+    ctx, st, skin, cutghost, map_ = _context(style)
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        cutoff = 0.8 * (cutghost - skin)
+        d.compute(0, 0)
+        for _ in range(5):
+            d.step(0, 0, rebuild="auto")
+        d.rdf(1, cutoff, PAIRS)
+        one = d.rdf_read()
+        d.rdf(NBIN, cutoff, PAIRS)
+        many = d.rdf_read()
+        ref = rdfref.counts(_x_by_tag(d, s.n), s.type, s.box.h, PER, cutoff, 1, RANGES)
+        rdfref.check_bracket(one[0], ref)
+        assert one[0].shape == (5, 1) and one[0][0, 0] > 1e4 and all(np.array_equal(a, b) for a, b in zip(one[1:], many[1:]))
+        if ref["n_edge"] == 0:      # (no pair within 1e-9 of the cutoff itself: the two reads then hold the same pairs)
+            assert np.array_equal(one[0][:, 0], many[0].sum(axis=1)) and np.array_equal(one[0], ref["hist"])
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("style", ["rebomos", "aeam"])
+def test_a_small_cutoff_widens_the_cells(style, capsys):
+    """A cutoff just above the first shell: cells of cutoff / 2 over the brick's bounding box would be more than bin_grid's
+    cap of 4 nall + 4096 (the premise, asserted from nets.measure_bin_grid over the box the domain sets -- the hull the
+    library sets at a reneighbouring holds that box -- and the domain's own nlocal + nghost), so the read bins on cells
+    1.26 or 1.26^2 times wider and the 5-cell stencil reaches further than it has to.  The histogram holds a full first
+    shell: at 300 K every Mo has its 6 S inside 2.8 A (tests/test_gpu_adf_mdp.py), 12 ordered pairs per Mo; the alloy runs
+    at 10 K: at 100 K its nearest-neighbour distances (2.86 A) spread by 0.07 A and 2 % of them lie beyond 3.0 A (the
+    reference's figure, on the device's positions); the spread goes with the root of the temperature, 0.02 A at 10 K, and
+    3.0 A is then six of them away: 12 per atom, less 1 % at the most."""
+    s, v0 = _system(style, 300.0 if style == "rebomos" else 10.0)
+    ctx, st, skin, cutghost, map_ = _context(style)
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        cutoff = SMALL_CUTOFF[style]
+        d.rdf(NBIN, cutoff, PAIRS)
+        d.compute(0, 0)
+        for _ in range(25):
+            d.step(0, 0, rebuild="auto")
+        nall = _nall(ctx)
+        cells, grown = nets.measure_bin_grid(nets.measure_domain_lens(s.box, cutghost), cutoff, nall)
+        first = nets.measure_bin_grid(nets.measure_domain_lens(s.box, cutghost), cutoff, 10 ** 9)[0]
+        assert grown >= 1 and first[0] * first[1] * first[2] > 4 * nall + 4096, (first, nall)
+        hist, ic, jc, du = d.rdf_read()
+        ref = rdfref.counts(_x_by_tag(d, s.n), s.type, s.box.h, PER, cutoff, NBIN, RANGES)
+        with capsys.disabled():
+            print(f"{style}: cutoff {cutoff} A, nall {nall}, {first} cells of cutoff / 2 against the cap {4 * nall + 4096}, grown {grown} times to "
+                  f"{cells}; {int(hist[0].sum())} pairs, {ref['n_edge']} edge pairs")
+        rdfref.check_bracket(hist, ref)
+        assert np.array_equal(ic, ref["icount"]) and np.array_equal(jc, ref["jcount"]) and np.array_equal(du, ref["dup"])
+        n1 = int((s.type == 1).sum())
+        if style == "rebomos":
+            assert hist[2].sum() == hist[3].sum() == 6 * n1 and hist[0].sum() >= 12 * n1
+        else:
+            assert 0.99 * 12 * s.n <= hist[0].sum() <= 12 * s.n
+    finally:
+        ctx.close()
+
+
+def test_one_workgroup_walks_every_chunk(monkeypatch, capsys):
+    """MDP_MEASURE_GRID = 1 and 3 on the (3, 3, 2) MoS2 replica, 5 184 atoms and more than 64 x 256 owned and ghost atoms (the
+    premise, from the domain): one workgroup takes more than 64 chunks, so it flushes its LDS counters inside its loop and
+    goes on counting, and three take a third each.  Either read is in the reference's bracket and equals the read without
+    the knob, integer for integer."""
+    s = S.replicate(S.rebomos_bulk_cell(), (3, 3, 2))
+    v0 = S.gaussian_velocities(s, 300.0, seed=3)
+    ctx, st, skin, cutghost, map_ = _context("rebomos")
+    try:
+        monkeypatch.delenv("MDP_MEASURE_GRID", raising=False)
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        cutoff = 6.0
+        d.rdf(NBIN, cutoff, PAIRS)
+        d.compute(0, 0)
+        for _ in range(5):
+            d.step(0, 0, rebuild="auto")
+        nall = _nall(ctx)
+        assert nall > 16384 and s.n == 5184, nall
+        plain = d.rdf_read()
+        ref = rdfref.counts(_x_by_tag(d, s.n), s.type, s.box.h, PER, cutoff, NBIN, RANGES)
+        rdfref.check_bracket(plain[0], ref)
+        assert plain[0].sum() > 1e5
+        for knob in ("1", "3", "0", ""):          # ("0" and "": the launch as it is)
+            monkeypatch.setenv("MDP_MEASURE_GRID", knob)
+            got = d.rdf_read()
+            with capsys.disabled():
+                print(f"MDP_MEASURE_GRID={knob!r}: nall {nall}, {-(-nall // 256)} chunks, differs from the plain read in "
+                      f"{int((got[0] != plain[0]).sum())} counters")
+            rdfref.check_bracket(got[0], ref)
+            assert all(np.array_equal(a, b) for a, b in zip(got, plain)), knob
+    finally:
+        ctx.close()
+
+
+def test_a_non_periodic_dimension(capsys):
+    """the alloy with free z at 2 500 K: atoms leave the box in z (asserted, as tests/test_gpu_profile_mdp.py asserts it) and
+    sit in clamped edge cells of the measurement grid; nobody has images in z, and the reference has none either"""
+    s, v0 = _system("aeam", 2500.0)
+    ctx, st, skin, cutghost, map_ = _context("aeam")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0, nonperiodic=(0, 0, 1))
+        cutoff = cutghost - skin
+        d.rdf(NBIN, cutoff, PAIRS)
+        d.compute(0, 0)
+        for _ in range(25):
+            d.step(0, 0, rebuild="auto")
+        hist, ic, jc, du = d.rdf_read()
+        x = _x_by_tag(d, s.n)
+        lamz = s.box.x2lamda(x)[:, 2]
+        below, above = int((lamz < 0.0).sum()), int((lamz >= 1.0).sum())
+        assert below > 5 and above >= 0 and below + above < s.n // 4, (below, above)
+        ref = rdfref.counts(x, s.type, s.box.h, (1, 1, 0), cutoff, NBIN, RANGES)
+        wrapped = rdfref.counts(x, s.type, s.box.h, PER, cutoff, NBIN, RANGES)
+        with capsys.disabled():
+            print(f"{below} atoms below and {above} above the box in z; {int(hist[0].sum())} pairs, {int(wrapped['hist'][0].sum())} with images in z")
+        rdfref.check_bracket(hist, ref)
+        assert np.array_equal(ic, ref["icount"]) and np.array_equal(jc, ref["jcount"]) and np.array_equal(du, ref["dup"])
+        # the two faces have lost their partners: an atom at depth z < R under a face loses the cap (2 R^3 - 3 R^2 z + z^3) / (4 R^3)
+        # of its sphere, 0.1875 R / L of all pairs per face in the mean: 10 % for R = 6.5 and L = 24.27 A
+        assert 0.8 < hist[0].sum() / wrapped["hist"][0].sum() < 0.95 and hist[0].sum() > 4e4
     finally:
         ctx.close()
 

@@ -108,6 +108,30 @@ CORNERS = {
         "slot k is not always the k-th lowest bit": lambda c: any(s["bits"] != sorted(s["bits"]) for s in c),
         "at most 16 cases": lambda c: len(c) <= 16,
     },
+    "measure": {   # (what the references make of these cases: test_measure_cases_meet_their_own_conditions)
+        "both styles": lambda c: {s["style"] for s in c} == {"rebomos", "aeam"},
+        "a sheared alloy box": lambda c: any(s["tilt"] is not None for s in c),
+        "more than 2 types": lambda c: any(s["ntypes"] > 2 for s in c),
+        "more than 8 types": lambda c: any(s["ntypes"] > 8 for s in c),
+        "a free dimension": lambda c: any(any(s["nonperiodic"]) for s in c),
+        "an odd rank count above 1": lambda c: any(s["ranks"] % 2 and s["ranks"] > 1 for s in c),
+        "8 ranks": lambda c: any(s["ranks"] == 8 for s in c),
+        "half of the cases on one rank, within 4": lambda c: abs(sum(s["ranks"] == 1 for s in c) - len(c) // 2) <= 4,
+        "npair = 32": lambda c: any(len(s["pairs"]) == 32 for s in c),
+        "ntriple = 32": lambda c: any(len(s["triples"]) == 32 for s in c),
+        "nbin = 1, both computes": lambda c: any(s["nbin_rdf"] == 1 for s in c) and any(s["nbin_adf"] == 1 for s in c),
+        "nbin x npair = 8192": lambda c: any(s["nbin_rdf"] * len(s["pairs"]) == 8192 for s in c),
+        "nbin x ntriple = 8192": lambda c: any(s["nbin_adf"] * len(s["triples"]) == 8192 for s in c),
+        "no histogram above 8192 counters": lambda c: all(s["nbin_rdf"] * len(s["pairs"]) <= 8192 and s["nbin_adf"] * len(s["triples"]) <= 8192 for s in c),
+        "the cutoff at its limit": lambda c: any(s["cutoff"] is None for s in c),
+        "a small cutoff that exceeds the cap of bin_grid at binsize = cutoff / 2": lambda c: any(s["small"] and nets.measure_grid_grows(s) for s in c),
+        "each group kind": lambda c: {s["group"]["kind"] for s in c} == set(nets.MSR_GROUPS),
+        "every ordinate": lambda c: {s["ordinate"] for s in c} == set(nets.MSR_ORDINATES),
+        "MDP_MEASURE_GRID set and unset": lambda c: {s["env"].get("MDP_MEASURE_GRID") for s in c} >= {None, "1"},
+        "the device's own check and forced rebuilds": lambda c: {s["rebuild"] == "auto" for s in c} == {True, False},
+        "a drift on several ranks": lambda c: any(any(s["drift"]) and s["ranks"] > 1 for s in c),
+        "at most 16 cases": lambda c: len(c) <= 16,
+    },
 }
 
 
@@ -231,3 +255,47 @@ def test_heat_cases_run_clean_and_the_limits_are_the_references(oracle):
         assert worst["i"][k] < 0.01 * lim, (k, worst["i"][k], lim)
     for k in ("dx", "dv", "dscale"):
         assert worst["ii"][k] < 0.25 * nets.HEAT_LIMITS[k], (k, worst["ii"][k])
+
+
+def test_measure_grid_restatement():
+    """nets.measure_bin_grid against bin_grid of csrc/measure_bin.hip worked by hand: a 43.27 A cube (the 6-cell alloy's box,
+    7.5 + 2 A further each way) with 3 700 atoms has the cap 4 x 3700 + 4096 = 18 896; cells of 1.5 A are 28^3 = 21 952, above
+    it, and cells of 1.5 x 1.26 = 1.89 A are 22^3 = 10 648; cells of 1.6 A are 27^3 = 19 683, still above; cells of 3.25 A
+    (the cutoff at its limit) are 13^3"""
+    lens = [4.045 * 6 + 2 * 9.5] * 3
+    assert nets.measure_bin_grid(lens, 3.0, 3700) == ([22, 22, 22], 1)
+    assert nets.measure_bin_grid(lens, 3.2, 3700) == ([21, 21, 21], 1)
+    assert nets.measure_bin_grid(lens, 6.5, 3700) == ([13, 13, 13], 0)
+    assert nets.measure_bin_grid([5000.0, 1.0, 1.0], 2.0, 10) == ([1024, 1, 1], 0)
+    s = nets.S.fcc_cell(4.045, 6)
+    assert np.allclose(nets.measure_domain_lens(s.box, 7.5), lens)
+    # 864 atoms, 1 + 2 x 7.5 / 24.27 = 1.618 per periodic dimension, 5 % more
+    assert nets.measure_nall_bound(s.box, 864, 7.5) == int(np.ceil(1.05 * 864 * (1 + 15 / 24.27) ** 3))
+    assert nets.measure_nall_bound(s.box, 864, 7.5, (0, 0, 1)) == int(np.ceil(1.05 * 864 * (1 + 15 / 24.27) ** 2))
+
+
+def test_measure_cases_meet_their_own_conditions():
+    """No GPU, no oracle.  On the start positions of every `measure` case of the suite the references meet the conditions
+    the case sets itself: at most 2 edge events (edge pairs, edge angles, neighbours at a shell radius), no centre with
+    more than 100 neighbours inside the largest outer radius (the device's list holds 128; the margin is for thermal
+    motion), and -- unless the case is about a tiny group or one type left out -- at least 3e4 rdf entries and 3e4 angles
+    (three times the floor of a read, for what thermal motion takes out of a first shell); the draw's own counts of entries
+    and angles are the references'."""
+    for spec in SPECS["measure"]:
+        s = nets._msr_start(spec)
+        member = nets.measure_member(spec, s)
+        rref, aref = nets.measure_references(spec, s.x, s.type, s.box.h, member)
+        entries, angles = int(rref["hist"].sum()), int(aref["hist"].sum())
+        print(spec["id"], f"{entries} entries, {angles} angles, at most {aref['max_neighbours']} neighbours, edge events "
+              f"{rref['n_edge']} + {aref['n_edge']} + {aref['n_shell_edge']}")
+        assert rref["n_edge"] + aref["n_edge"] + aref["n_shell_edge"] <= 2, spec["id"]
+        assert aref["max_neighbours"] <= nets.MSR_NEIGH, (spec["id"], aref["max_neighbours"])
+        limit = nets.MSR_LIMIT[spec["style"]]
+        assert all(0.0 <= t[k] < t[k + 1] <= limit for t in spec["triples"] for k in (6, 8)), spec["id"]
+        assert spec["cutoff"] is None or nets.MSR_FIRST[spec["style"]] < spec["cutoff"] < limit
+        pairs = nets._msr_pairs(s, spec, limit)
+        assert (entries, angles) == nets.measure_start_counts(spec, s, member, pairs), spec["id"]
+        if spec["group"]["kind"] == "tiny":
+            assert member.sum() in (2, 3)
+        elif spec["group"]["kind"] != "one type out":
+            assert entries >= nets.MSR_FLOOR_START and angles >= nets.MSR_FLOOR_START, (spec["id"], entries, angles)
