@@ -1197,8 +1197,9 @@ int mdp_measure_bin(mdp_ctx *c, MdpBinning &b, double cutoff, int ntypes, int nt
                     unsigned long long *d_bad, MdpGrid &g);
 // what a setup or a read of such a measurement needs: a resident context with mdp_dd_setup, on its device
 int mdp_measure_require(mdp_ctx *c, const char *who);
-// the workgroups of a histogram kernel that strides over nchunk chunks: min(nchunk, resident), and no more than the test
-// hook MDP_MEASURE_GRID when that is a positive integer (read at every read; the sums are integers, so any value reads the same)
+// the workgroups of a measurement kernel that strides over nchunk chunks (the histograms of rdf.hip and adf.hip, the range and
+// the sums of profile.hip): min(nchunk, resident), and no more than the test hook MDP_MEASURE_GRID when that is a positive
+// integer (read at every read; the sums are integers and the range is a maximum, so any value reads the same)
 int mdp_measure_grid(int nchunk, int resident);
 void mdp_profile_release(mdp_ctx *c); // frees what profile.hip holds
 void mdp_heatflux_release(mdp_ctx *c); // frees what heatflux.hip holds

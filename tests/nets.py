@@ -46,6 +46,7 @@ SUITE = {
     "langevin": [(42, 14)],
     "heat": [(2, 12)],
     "measure": [(4, 16)],
+    "peratom": [(27, 16)],
 }
 
 
@@ -1402,7 +1403,7 @@ def measure_grid_grows(spec):
     """no GPU: the first trial grid of the rdf read of a one-brick case, cells cutoff / 2 wide, exceeds bin_grid's cap"""
     if spec["ranks"] != 1 or spec["cutoff"] is None:
         return False
-    box = _msr_start(spec).box
+    box = _cell_start(spec).box
     cutghost = MSR_LIMIT[spec["style"]] + MSR_SKIN[spec["style"]]
     nall = measure_nall_bound(box, spec["n"], cutghost, spec["nonperiodic"])
     return measure_bin_grid(measure_domain_lens(box, cutghost), spec["cutoff"], nall)[1] > 0
@@ -1485,7 +1486,7 @@ def _msr_random(rng):
     return spec
 
 
-def _msr_start(spec):
+def _cell_start(spec):
     """no GPU, no oracle: the start system of a case, jittered (placeholder masses; run_measure sets the potential's)"""
     sd = spec["seed"]
     if spec["style"] == "rebomos":
@@ -1504,19 +1505,19 @@ def _msr_start(spec):
     return S.jitter(s, spec["amp"], seed=sd + 1)
 
 
-def _msr_periodic(spec):
+def _cell_periodic(spec):
     return tuple(0 if f else 1 for f in spec["nonperiodic"])
 
 
 def _msr_pairs(s, spec, rmax):
     import rdfref
-    out = list(rdfref._pairs_in_range(np.ascontiguousarray(s.x), s.box.h, _msr_periodic(spec), rmax))
+    out = list(rdfref._pairs_in_range(np.ascontiguousarray(s.x), s.box.h, _cell_periodic(spec), rmax))
     if not out:
         return np.zeros(0, dtype=int), np.zeros(0, dtype=int), np.zeros(0)
     return tuple(np.concatenate([o[k] for o in out]) for k in range(3))
 
 
-def measure_member(spec, s, pairs=None):
+def group_member(spec, s, pairs=None):
     """the member table of the case by tag (row t - 1), or None; s: the start system.  A tiny group is an atom and one or
     two of its nearest neighbours, so that it holds a pair"""
     g = spec["group"]
@@ -1570,7 +1571,7 @@ def _msr_fit(spec):
     cutoff at the limit and triple 1 over the widest shell, then no group"""
     style, nt = spec["style"], spec["ntypes"]
     first, limit = MSR_FIRST[style], MSR_LIMIT[style]
-    s = _msr_start(spec)
+    s = _cell_start(spec)
     pairs = _msr_pairs(s, spec, limit)
     pi, pj, pr = pairs
     # the distance of every centre's neighbour number MSR_NEIGH + 1, if it lies inside the limit
@@ -1589,7 +1590,7 @@ def _msr_fit(spec):
         rows.append(tuple(float(v) if k >= 6 else int(v) for k, v in enumerate(row)))
     spec["triples"] = rows
     spec["rcap"] = float(rcap)
-    member = measure_member(spec, s, pairs)
+    member = group_member(spec, s, pairs)
     exempt = spec["group"]["kind"] in ("tiny", "one type out")
     steps = ("all types", "widest", "no group")
     spec["fitted"] = []
@@ -1615,18 +1616,26 @@ def _msr_fit(spec):
                   f"adf{len(spec['triples'])}x{spec['nbin_adf']}-{spec['ordinate']}-grid{spec['env'].get('MDP_MEASURE_GRID', 'unset')}")
 
 
-def _msr_velocities(spec, s):
-    """start velocities (with the drift) and the steps between forced list builds by the _lgv_system rule"""
-    v0 = S.gaussian_velocities(s, float(spec["temp"]), seed=spec["seed"] + 2) + np.array(spec["drift"], dtype=float)
-    vcap = float(np.sqrt((v0 ** 2).sum(axis=1)).max()) + 5.0 * np.sqrt(S.BOLTZ * spec["temp"] / (float(s.mass[1:].min()) * S.MVV2E))
-    return v0, max(1, int(0.3 * MSR_SKIN[spec["style"]] / (vcap * 0.001)))
+def _cell_speed_cap(spec, s, v0):
+    """the speed no atom is expected to exceed during the run: the fastest atom of the start and five thermal standard
+    deviations of the lightest type more (of 300 K for a colder start, whose atoms the jitter's forces set moving)"""
+    return float(np.sqrt((v0 ** 2).sum(axis=1)).max()) + 5.0 * np.sqrt(S.BOLTZ * max(spec["temp"], 300) / (float(s.mass[1:].min()) * S.MVV2E))
+
+
+def _cell_velocities(spec, s):
+    """start velocities (with the drift; exactly zero at 0 K) and the steps between forced list builds by the _lgv_system rule"""
+    if spec["temp"] == 0:
+        v0 = np.zeros((s.n, 3))
+    else:
+        v0 = S.gaussian_velocities(s, float(spec["temp"]), seed=spec["seed"] + 2) + np.array(spec["drift"], dtype=float)
+    return v0, max(1, int(0.3 * MSR_SKIN[spec["style"]] / (_cell_speed_cap(spec, s, v0) * 0.001)))
 
 
 def measure_references(spec, x, types, h, member):
     """rdfref.counts and adfref.counts of the case on positions and types by tag"""
     import adfref
     import rdfref
-    per = _msr_periodic(spec)
+    per = _cell_periodic(spec)
     cutoff = spec.get("cutoff_used") or spec["cutoff"] or MSR_LIMIT[spec["style"]]
     return (rdfref.counts(x, types, h, per, cutoff, spec["nbin_rdf"], spec["pairs"], member),
             adfref.counts(x, types, h, per, spec["nbin_adf"], spec["ordinate"], spec["triples"], member))
@@ -1642,7 +1651,7 @@ def run_measure(spec):
     from lammps_plugins_amd.host import capi, resident
     R = _res()
     style, skin = spec["style"], MSR_SKIN[spec["style"]]
-    s = _msr_start(spec)
+    s = _cell_start(spec)
     tabs = None
     if style == "rebomos":
         cutghost = 3.0 * R["rp"].rcmax[0][0] + skin
@@ -1662,8 +1671,8 @@ def run_measure(spec):
     limit = cutghost - skin
     assert abs(limit - MSR_LIMIT[style]) < 1e-9, limit
     cutoff = limit if spec["cutoff"] is None else spec["cutoff"]
-    member = measure_member(spec, s)
-    v0, safe = _msr_velocities(spec, s)
+    member = group_member(spec, s)
+    v0, safe = _cell_velocities(spec, s)
     rebuild = spec["rebuild"] if spec["rebuild"] == "auto" else min(spec["rebuild"], safe)
     reads = sorted({0, spec["between"], spec["nsteps"]})
     pairs = [((p[0], p[1]), (p[2], p[3])) for p in spec["pairs"]]
@@ -1736,6 +1745,399 @@ def line_measure(spec, err):
             f"most neighbours {err['most']} vacuous {err['vacuous']} owned once {not err['not_owned_once']} late {err['late']} builds {err['builds']}")
 
 
+# ------------------------------------------------------------------------------------------------------------ peratom
+# compute profile/mdp, msd/mdp and heatflux/mdp (csrc/profile.hip, csrc/msd.hip, csrc/heatflux.hip) on one context per rank,
+# against tests/profileref.py, tests/msdref.py and tests/heatfluxref.py on the state gathered by tag from the same run, and
+# the heat current of the last read against the oracle's per-atom tallies.  The systems of the measure net (MoS2 replicas,
+# the alloy at 5 - 8 cells, all three tilts in some) at 0 K (velocities exactly zero), 300, 1 200 or 2 500 K, some with a
+# drift and some of those with 150 A/ps along one axis (atoms cross a face between two reads); 1 - 8 bricks, a free
+# dimension in some one-brick alloy cases; no group, a slab, a modulus class, one type left out, 1 - 3 atoms or nobody, on
+# group bit 1, 7, 30 or 31; two profile grids of 1 - 3 dimensions in any order, one that fits the workgroup's LDS copy
+# (rows * 5 <= 4 096) and, in half of the cases, one that does not (up to PROFILE_MAXBINS rows on one brick, 65 536 on
+# several); MDP_MEASURE_GRID unset or 1, 3, 64, and on one brick the
+# tables of a knob case once more with the knob unset; msd origins from the current positions or by tag, at step 0 or at
+# the read in between (images non-zero by then), read with and without the com shift; reads at step 0, in between and at
+# the end, each taken twice, the last step tallying and in half of the cases with its final half left to the first read.
+# Every error is a count that must be 0; the reference's own edge atoms (within 1e-9 of a bin edge) are capped at 2 a read.
+# The bounds (none measured):
+#   profile   counts exact, sums within count 2^-e + 2^-50 sum|t| (profileref.check_sums); rows an edge atom can fall in are
+#             bracketed instead (profileref.check_sums_with_edges)
+#   xu        |xu - (x + h . image)| <= 8 2^-53 (|x| + sum_k |h_dk image_k|) per component: three fused operations on the
+#             device, up to five roundings in msdref.unwrap
+#   msd       the sums within MSD_RTOL = 1e-12 (tests/test_gpu_msd_mdp.py) of the sums of their terms' magnitudes; for a
+#             read with the com shift the magnitude of a term ((xu - x0) - shift)^2 is (|xu - x0| + |shift|)^2, and the
+#             reference subtracts the very shift the device was handed (the shift itself is held to the centre of mass)
+#   images    between two reads no atom moves further than half the smallest perpendicular width of the box; the draw keeps
+#             1.5 x the speed cap x dt x the steps between two reads below that, so a miscounted image -- a whole box vector --
+#             fails whatever the forces did
+#   heatflux  the sums within 1e-12 of their terms' magnitudes (tests/test_gpu_heatflux_mdp.py), the count exact, out[7] of
+#             all atoms against thermo ke + fsum(eatom); at the last read J and sum W.v within
+#             sum|v|_1 (1e-9 + 3e-9 max(1, max|vatom|)) of the oracle's (test_physics_against_the_oracle)
+PA_TEMPS = (0, 300, 1200, 2500)
+PA_GROUPS = ("none", "slab", "modulus", "one type out", "few", "nobody")
+PA_BITS = (1 << 1, 1 << 7, 1 << 30, 1 << 31)
+PA_NBIN = (1, 2, 3, 5, 7, 11, 13, 37, 101, 819, 820, 1024)
+PA_LDS_ROWS = 819                 # rows * 5 <= 4 096: the largest grid a workgroup keeps in LDS
+PA_MAXBINS = 1048576              # PROFILE_MAXBINS of include/mdpair_hip.h (run_peratom asserts it)
+PA_BRICK_ROWS = 65536             # ... and the cap on several bricks: the transports carry a table as doubles, a million rows take seconds
+PA_FAST = 150                     # A/ps
+PA_DT = 0.001
+PA_EDGE_LIMIT = 3
+PA_RTOL = 1e-12
+PA_ORDER = ("profile", "heatflux", "msd")
+
+
+def _pa_grid(rng, cap, first=None):
+    ndim = rng.randint(1, 3)
+    dims = rng.sample(range(3), ndim)
+    nbins, rows = [], 1
+    for k in range(ndim):
+        n = rng.choice(first if first and k == 0 else PA_NBIN)
+        if rows * n > cap:
+            n = max(1, cap // rows)
+        nbins.append(n)
+        rows *= n
+    return tuple(dims), tuple(nbins)
+
+
+def draw_peratom(rng):
+    style = rng.choice(["rebomos", "aeam"])
+    sd = rng.randrange(1, 10**6)
+    spec = dict(style=style, seed=sd, tilt=None, relabel=None, frac=None, nonperiodic=(0, 0, 0), ntypes=2)
+    if style == "rebomos":
+        size = (rng.choice([1, 2]), rng.choice([1, 2]), rng.choice([1, 2]))
+        spec.update(size=size, n=_rebo_n(size))
+    else:
+        size = rng.choice([5, 6, 7, 8])
+        spec.update(size=size, n=4 * size ** 3, frac=rng.choice([0.05, 0.2, 0.5]))
+        if rng.random() < 0.4:   # all three tilts, as draw_measure shears it
+            spec["tilt"] = [rng.uniform(-0.12, 0.12) * 4.045 * size for _ in range(3)]
+    spec["amp"] = rng.choice([0.02, 0.05, 0.08])
+    spec["temp"] = rng.choice(PA_TEMPS)
+    spec["drift"] = [rng.choice([-60, -30, 0, 25, 40, 70]) for _ in range(3)] if rng.random() < 0.4 else [0, 0, 0]
+    spec["fast"] = (rng.random() < 0.5, rng.randrange(3), rng.choice([-1, 1]))
+    spec["nsteps"] = rng.randint(5, 40)
+    spec["ranks"] = 1 if rng.random() < 0.5 else rng.choice([2, 3, 4, 8])
+    auto, renb = rng.random() < 0.5, rng.choice([3, 5, 8])
+    spec["rebuild"] = "auto" if auto and spec["ranks"] == 1 else renb     # (the device's own check serves one brick only)
+    free = rng.random() < 0.4, rng.randrange(3)
+    if style == "aeam" and spec["ranks"] == 1 and spec["tilt"] is None and free[0]:
+        spec["nonperiodic"] = tuple(int(d == free[1]) for d in range(3))
+    spec["between"] = rng.randint(1, spec["nsteps"] - 1)
+    spec["group"] = dict(kind=rng.choice(PA_GROUPS), axis=rng.randrange(3), lo=rng.uniform(0.0, 0.5), width=rng.uniform(0.3, 0.5),
+                         m=rng.choice([2, 3, 5]), r=rng.randrange(2), count=rng.choice([1, 2, 3]), pick=rng.randrange(10**6),
+                         type=rng.randint(1, 2), bit=rng.choice(PA_BITS))
+    small = _pa_grid(rng, PA_LDS_ROWS)
+    cap = PA_MAXBINS if spec["ranks"] == 1 else PA_BRICK_ROWS
+    other = _pa_grid(rng, cap, first=(820, 1024)) if rng.random() < 0.5 else _pa_grid(rng, PA_LDS_ROWS)
+    spec["grids"] = [small, other] if rng.random() < 0.5 else [other, small]
+    spec["env"] = {"MDP_MEASURE_GRID": rng.choice(MSR_GRID)} if rng.random() < 0.5 else {}
+    spec["origin"] = dict(mode=rng.choice(["null", "tag"]), at=rng.choice(["start", "between"]))
+    if spec["ranks"] > 1:
+        spec["origin"]["mode"] = "tag"       # (origins from the current positions are for one rank)
+    spec["defer"] = rng.random() < 0.5
+    spec["first_read"] = rng.choice(PA_ORDER)
+    _pa_fit(spec)
+    return spec
+
+
+def peratom_half_width(box):
+    """half the smallest perpendicular width of the box"""
+    return 0.5 / float(np.linalg.norm(box.hinv, axis=1).max())
+
+
+def _pa_fit(spec):
+    """no draws: 0 K and a free dimension take the drift out; a drifting case takes PA_FAST along one axis where the rule of
+    _cell_velocities still allows a step between two list builds; the steps are cut to what keeps 1.5 x the speed cap x dt x
+    the steps between two reads below half the smallest perpendicular width (at least 5 fit every box here); a group of a
+    few atoms gets its tags"""
+    s = _cell_start(spec)
+    if spec["temp"] == 0 or any(spec["nonperiodic"]):
+        spec["drift"] = [0, 0, 0]
+    spec["fast_on"] = False
+    if any(spec["drift"]) and spec["fast"][0]:
+        fast = list(spec["drift"])
+        fast[spec["fast"][1]] = spec["fast"][2] * PA_FAST
+        trial = dict(spec, drift=fast)
+        if int(0.3 * MSR_SKIN[spec["style"]] / (_cell_speed_cap(trial, s, _cell_velocities(trial, s)[0]) * PA_DT)) >= 1:
+            spec["drift"], spec["fast_on"] = fast, True
+    vcap = _cell_speed_cap(spec, s, _cell_velocities(spec, s)[0])
+    half = peratom_half_width(s.box)
+    most = int(0.98 * half / (1.5 * vcap * PA_DT))      # (2 % for the potentials' masses in place of the placeholders')
+    assert most >= 5, (most, half, vcap)
+    spec["nsteps"] = min(spec["nsteps"], most)
+    spec["between"] = min(spec["between"], spec["nsteps"] - 1)
+    spec.update(vcap=vcap, half=half)
+    g = spec["group"]
+    if g["kind"] == "few":
+        g["tags"] = sorted(int(t) + 1 for t in np.random.default_rng(g["pick"]).choice(s.n, g["count"], replace=False))
+    spec["heatflux"] = spec["style"] == "rebomos" or spec["ranks"] == 1      # (alloy bricks are refused: tests/test_gpu_heatflux_mdp.py)
+    grids = "+".join(".".join(f"{'xyz'[d]}{n}" for d, n in zip(*gr)) for gr in spec["grids"])
+    bit = g["bit"].bit_length() - 1
+    spec["id"] = (f"{spec['style']}-n{spec['n']}-ranks{spec['ranks']}-T{spec['temp']}-{g['kind'].replace(' ', '')}-bit{bit}-{grids}-"
+                  f"grid{spec['env'].get('MDP_MEASURE_GRID', 'unset')}-origin{spec['origin']['mode']}at{spec['origin']['at']}")
+
+
+def peratom_member(spec, s):
+    """the member table of the case by tag (row t - 1), or None for no group; s: the start system"""
+    g = spec["group"]
+    if g["kind"] == "nobody":
+        return np.zeros(s.n, dtype=bool)
+    if g["kind"] == "few":
+        m = np.zeros(s.n, dtype=bool)
+        m[np.array(g["tags"]) - 1] = True
+        return m
+    return group_member(spec, s)
+
+
+def peratom_rows(grid):
+    return int(np.prod(grid[1]))
+
+
+def _pa_oracle_currents(spec, s, x, v, member):
+    """heatfluxref.sums with the ORACLE's per-atom tallies on positions by tag, and the scale of its vatom.  A free dimension:
+    the box grows by 30 A either way in it, so that no periodic image comes within reach"""
+    import dataclasses
+    import heatfluxref
+    import mdref
+    R = _res()
+    box = s.box
+    if any(spec["nonperiodic"]):
+        free = np.array(spec["nonperiodic"]) == 1
+        lam = box.x2lamda(x)
+        assert not box.tilt.any() and float((np.maximum(-lam, lam - 1.0) * box.prd)[:, free].max()) < 15.0    # no atom far outside
+        pad = 30.0 * free
+        box = S.Box(box.lo - pad, box.prd + 2.0 * pad, box.tilt.copy())
+    s2 = dataclasses.replace(s, box=box, x=S.wrap(box, x))
+    eng = mdref.RebomosCPU(R["orc"], R["P"], s2) if spec["style"] == "rebomos" else mdref.AeamCPU(R["orc"], R["T"], s2)
+    o = eng.compute(s2.x)
+    n = s.n
+    ea, va = o["eatom"][:n].copy(), o["vatom"][:n].copy()
+    np.add.at(ea, eng.owner, o["eatom"][n:])         # the oracle's ghost shares onto their owners
+    np.add.at(va, eng.owner, o["vatom"][n:])
+    return heatfluxref.sums(s.mass[s.type], v, ea, va, S.MVV2E, member=member), max(1.0, float(np.abs(va).max()))
+
+
+def run_peratom(spec):
+    import math
+    import heatfluxref
+    import msdref
+    import profileref
+    from lammps_plugins_amd.host import capi, resident
+    R = _res()
+    assert capi.PROFILE_MAXBINS == PA_MAXBINS and capi.PROFILE_W == profileref.W
+    style, skin = spec["style"], MSR_SKIN[spec["style"]]
+    s = _cell_start(spec)
+    tabs = None
+    if style == "rebomos":
+        cutghost = 3.0 * R["rp"].rcmax[0][0] + skin
+    else:
+        tabs = R["tabs"]
+        s.mass[1:] = R["af"].mass[:2]
+        cutghost = float(R["af"].cut_table(tabs).max()) + skin
+    n, world, nsteps, hf = s.n, spec["ranks"], spec["nsteps"], spec["heatflux"]
+    member = peratom_member(spec, s)
+    bit = spec["group"]["bit"] if member is not None else 0
+    gbit = bit - (1 << 32) if bit >= (1 << 31) else bit             # the C int with that bit
+    mask = np.ones(n + 1, dtype=np.uint32)
+    if member is not None:
+        mask[1:] |= np.where(member, np.uint32(bit), np.uint32(0))
+    mask = mask.view(np.int32)
+    sel = np.ones(n, dtype=bool) if member is None else member
+    mass = s.mass[s.type]
+    v0, safe = _cell_velocities(spec, s)
+    rebuild = spec["rebuild"] if spec["rebuild"] == "auto" else min(spec["rebuild"], safe)
+    reads = sorted({0, spec["between"], nsteps})
+    origin_at = 0 if spec["origin"]["at"] == "start" else spec["between"]
+    knob = "MDP_MEASURE_GRID" in spec["env"] and world == 1
+    plain_env = {k: v for k, v in spec["env"].items() if k != "MDP_MEASURE_GRID"}
+    k0 = PA_ORDER.index(spec["first_read"])
+    order = PA_ORDER[k0:] + PA_ORDER[:k0]
+    by_tag = lambda tags, a: _by_tag_rows(n, tags, a)
+
+    def rank_fn(r, make_tr):
+        ctx = capi.Context(0)
+        try:
+            if style == "rebomos":
+                ctx.rebomos_set_params(R["rp"])
+                st, map_ = capi.STYLE_REBOMOS, [0, 0, 1]
+            else:
+                ctx.aeam_set_tables(tabs)
+                st, map_ = capi.STYLE_AEAM, None
+            d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0, transport=make_tr(ctx) if world > 1 else None,
+                                      nonperiodic=spec["nonperiodic"])
+            if member is not None:
+                d.set_group(mask, 0)
+            d.track_images()
+            tally = (3, 5) if hf else (0, 0)
+            d.compute(*tally)
+            out, msd = {}, {}
+            for step in range(0, nsteps + 1):
+                if step:
+                    last = step == nsteps
+                    d.step(*((3, 5) if last or (hf and step in reads) else (0, 0)),
+                           rebuild="auto" if rebuild == "auto" else step % rebuild == 0, defer_final=last and spec["defer"])
+                    if last and spec["defer"]:
+                        d._final_pending = False      # the library holds the half: the first read that needs velocities completes it
+                if step not in reads:
+                    continue
+                o = dict(prof=[], plain=[])
+                for what in order:
+                    if what == "profile":
+                        for dims, nbins in spec["grids"]:
+                            d.profile(dims, nbins, group_bit=gbit)
+                            o["prof"].append((d.profile_read(), d.profile_read()))
+                            if knob:
+                                with knobs(plain_env):
+                                    o["plain"].append(d.profile_read())
+                    elif what == "heatflux" and hf:
+                        o["hf"] = [d._group_sum(ctx.heatflux_sums(gbit)) for _ in range(2)]
+                        o["hf_all"] = d._group_sum(ctx.heatflux_sums(0))
+                    elif what == "msd":
+                        tags, xu = d.tags_local, d.unwrapped_local()
+                        if step == origin_at:
+                            x0 = np.zeros((n, 3))
+                            x0[tags - 1] = xu
+                            if world > 1:
+                                x0 = d._group_sum(x0.ravel()).reshape(n, 3)
+                            ctx.msd_setup(n, None if spec["origin"]["mode"] == "null" else x0, gbit)
+                            msd.update(x0=x0, cm0=msdref.centre_of_mass(x0[sel], mass[sel]) if sel.any() else np.zeros(3))
+                        if msd:
+                            o["msd"] = [d._group_sum(ctx.msd_sums()) for _ in range(2)]
+                            o["x0"] = msd["x0"]
+                            if o["msd"][0][7] > 0.0:
+                                o["shift"] = o["msd"][0][4:7] / o["msd"][0][7] - msd["cm0"]
+                                o["msd_com"] = d._group_sum(ctx.msd_sums(o["shift"]))
+                tallied = hf
+                got = ctx.md_download(d.nlocal, want=("x", "v", "eatom") if tallied else ("x", "v"))
+                o.update(tags=d.tags_local.copy(), x=got["x"], v=got["v"], image=d.images_local(), xu=d.unwrapped_local())
+                if tallied:
+                    o.update(eatom=got["eatom"], vatom=ctx.md_download_vatom(d.nlocal), ke=d.thermo()["ke"])
+                out[step] = o
+            return dict(out=out, builds=d.builds, late=d.dangerous)
+        finally:
+            ctx.close()
+
+    res = [rank_fn(0, None)] if world == 1 else resident.run_ranks(world, rank_fn)
+    err = dict(reread=0, ranks=0, not_owned_once=0, exponents=0, profile=0, knob=0, edge=0, xu_outside=0, msd_outside=0, msd_count=0,
+               jumped=0, premise=0, hf_outside=0, hf_count=0, hf_energy=0, hf_physics=0, late=sum(r["late"] for r in res),
+               builds=res[0]["builds"], xu=0.0, msd=0.0, hf=0.0, prof=0.0, physics=0.0, failed=[])
+    same = lambda a, b: all(np.array_equal(u, w) for u, w in zip(a, b))
+    per = tuple(bool(p) for p in _cell_periodic(spec))
+    vcap = _cell_speed_cap(spec, s, v0)
+    half = peratom_half_width(s.box)
+    before = None
+    for step in reads:
+        g = dict(seen=np.zeros(n, dtype=int))
+        for r in res:
+            o = r["out"][step]
+            g["seen"][o["tags"] - 1] += 1
+            for key in ("x", "v", "image", "xu", "eatom", "vatom"):
+                if key in o:
+                    a = o[key] if o[key].ndim > 1 else o[key][:, None]
+                    g.setdefault(key, np.zeros((n, a.shape[1]), dtype=a.dtype))[o["tags"] - 1] = a
+        err["not_owned_once"] += int(not np.all(g["seen"] == 1))
+        o = res[0]["out"][step]
+        # ---- every compute: two reads of one state identical, every rank reads the same
+        err["reread"] += sum(int(not same(a, b)) for a, b in o["prof"])
+        for key in ("hf", "msd"):
+            if key in o:
+                err["reread"] += int(o[key][0].tobytes() != o[key][1].tobytes())
+        for r in res[1:]:
+            q = r["out"][step]
+            err["ranks"] += sum(int(not same(a[0], b[0])) for a, b in zip(q["prof"], o["prof"]))
+            err["ranks"] += sum(int(not np.array_equal(q[key], o[key])) for key in ("hf", "hf_all", "msd", "msd_com") if key in o)
+        # ---- profile
+        lam = s.box.x2lamda(g["x"])
+        for k, (dims, nbins) in enumerate(spec["grids"]):
+            count, sums, ex = o["prof"][k][0]
+            ref = profileref.table(lam, per, dims, nbins, mass, g["v"], exponents=ex, member=member, natoms_total=n)
+            err["exponents"] += int(ex.tolist() != [profileref.exponent(q, n) for q in ref["rng"]])
+            try:
+                worst, n_edge = profileref.check_sums_with_edges(count, sums, ex, ref, profileref.edges(lam, per, dims, nbins, member))
+                err["prof"], err["edge"] = max(err["prof"], worst), max(err["edge"], n_edge)
+            except AssertionError as e:
+                err["profile"] += 1
+                err["failed"].append(f"profile step {step} grid {k}: {str(e)[:200]}")
+            if knob:
+                err["knob"] += int(not same(o["plain"][k], o["prof"][k][0]))
+        # ---- msd: the unwrapped positions, the sums, the images
+        want = msdref.unwrap(s.box, g["x"], g["image"])
+        bound = 8.0 * 2.0 ** -53 * (np.abs(g["x"]) + S.mul_upper(np.abs(g["image"]).astype(np.float64), np.abs(s.box.h)))
+        dxu = np.abs(g["xu"] - want)
+        err["xu_outside"] += int((dxu > bound).sum())
+        err["xu"] = max(err["xu"], float(dxu.max()))
+        if "msd" in o:
+            got, x0, nsel = o["msd"][0], o["x0"], int(sel.sum())
+            err["msd_count"] += int(got[3] != nsel)
+            if nsel == 0:
+                err["msd_outside"] += int(np.any(got != 0.0))
+            else:
+                xs, os_, ms = g["xu"][sel], x0[sel], mass[sel]
+                means = msdref.msd_values(g["xu"], x0, sel=sel)[:3]          # (terms of one sign: the sum is its own magnitude)
+                pairs = list(zip(got[:3] / got[3], means, means))
+                cm, mtot = msdref.centre_of_mass(xs, ms), math.fsum(ms)
+                pairs += [(got[4 + c] / got[7], cm[c], math.fsum(np.abs(ms * xs[:, c])) / mtot) for c in range(3)]
+                pairs.append((got[7], mtot, mtot))
+                if "msd_com" in o:
+                    dd = (xs - os_) - o["shift"]
+                    mg = np.abs(xs - os_) + np.abs(o["shift"])
+                    pairs += [(o["msd_com"][c] / o["msd_com"][3], math.fsum(dd[:, c] * dd[:, c]) / nsel, math.fsum(mg[:, c] * mg[:, c]) / nsel)
+                              for c in range(3)]
+                    err["msd_count"] += int(o["msd_com"][3] != nsel)
+                for a, b, m in pairs:
+                    err["msd_outside"] += int(not abs(a - b) <= PA_RTOL * m)
+                    if m > 0.0:
+                        err["msd"] = max(err["msd"], abs(a - b) / m)
+        if before is not None:
+            gap = step - before[0]
+            err["premise"] += int(not 1.5 * vcap * PA_DT * gap < half)
+            err["jumped"] += int((np.sqrt(((g["xu"] - before[1]) ** 2).sum(axis=1)) > half).sum())
+        before = (step, g["xu"])
+        # ---- heatflux
+        if "hf" in o:
+            ref = heatfluxref.sums(mass, g["v"], g["eatom"][:, 0], g["vatom"], S.MVV2E, member=member)
+            got = o["hf"][0]
+            err["hf_count"] += int(got[6] != sel.sum())
+            err["hf_outside"] += int((~(np.abs(got - ref["sums"]) <= PA_RTOL * ref["mag"])).sum())
+            ok = ref["mag"] > 0.0
+            if ok.any():
+                err["hf"] = max(err["hf"], float((np.abs(got - ref["sums"])[ok] / ref["mag"][ok]).max()))
+            everyone = heatfluxref.sums(mass, g["v"], g["eatom"][:, 0], g["vatom"], S.MVV2E)
+            err["hf_energy"] += int(not abs(o["hf_all"][7] - (o["ke"] + math.fsum(g["eatom"][:, 0]))) <= PA_RTOL * everyone["mag"][7])
+            err["hf_energy"] += int(o["hf_all"][6] != n)
+            if step == nsteps:
+                oref, scale = _pa_oracle_currents(spec, s, g["x"], g["v"], member)
+                bound = float(np.abs(g["v"][sel]).sum()) * (1e-9 + 3e-9 * scale)
+                vec = np.concatenate([got[0:3] + got[3:6], got[0:3]])
+                diff = np.concatenate([np.abs(vec - oref["vector"]), np.abs(got[3:6] - oref["sums"][3:6])])
+                err["hf_physics"] += int((~(diff <= bound)).sum())
+                if bound > 0.0:
+                    err["physics"] = float(diff.max() / bound)
+    lim = dict.fromkeys(("reread", "ranks", "not_owned_once", "exponents", "profile", "knob", "xu_outside", "msd_outside", "msd_count", "jumped",
+                         "premise", "hf_outside", "hf_count", "hf_energy", "hf_physics", "late"), 1)
+    lim["edge"] = PA_EDGE_LIMIT
+    return err, lim
+
+
+def _by_tag_rows(n, tags, a):
+    out = np.zeros((n,) + a.shape[1:], dtype=a.dtype)
+    out[tags - 1] = a
+    return out
+
+
+def line_peratom(spec, err):
+    g = spec["group"]
+    return (f"{spec['id']} size {spec['size']} tilt {spec['tilt'] is not None} free {spec['nonperiodic']} drift {spec['drift']} steps {spec['nsteps']} "
+            f"rebuild {spec['rebuild']} read also at {spec['between']} defer {spec['defer']} first {spec['first_read']} heatflux {spec['heatflux']} "
+            f"seed {spec['seed']} reread {err['reread']} ranks {err['ranks']} exponents {err['exponents']} profile {err['profile']} knob {err['knob']} "
+            f"edge atoms {err['edge']} xu outside {err['xu_outside']} msd outside {err['msd_outside']} count {err['msd_count']} jumped {err['jumped']} "
+            f"premise {err['premise']} heatflux outside {err['hf_outside']} count {err['hf_count']} energy {err['hf_energy']} physics {err['hf_physics']} "
+            f"owned once {not err['not_owned_once']} late {err['late']} builds {err['builds']} worst: |xu - ref| {err['xu']:.2e} A, msd {err['msd']:.2e}, "
+            f"heatflux / mag {err['hf']:.2e}, profile / bound {err['prof']:.3f}, J / physics bound {err['physics']:.2e}"
+            + ("".join("  " + f for f in err["failed"])))
+
+
 # ---------------------------------------------------------------------------------------------------------------- nvt
 # The Nose-Hoover chain thermostat (tests/test_gpu_nvt_net.py): chains of 1-8, 1-3 loops, drag, flat or ramped targets,
 # both styles, the resident path and (REBO-MoS) the host-linked one, atom counts whose last 256-atom block varies.
@@ -1765,7 +2167,7 @@ def nvt_cases(seed, ncase):
 
 
 NETS = {name: (globals()["draw_" + name], globals()["run_" + name], globals()["line_" + name])
-        for name in ("force", "hostmode_walk", "aeam_types", "prune", "dd", "hnve", "minilmp", "trajectory", "block", "fire", "langevin", "heat", "measure")}
+        for name in ("force", "hostmode_walk", "aeam_types", "prune", "dd", "hnve", "minilmp", "trajectory", "block", "fire", "langevin", "heat", "measure", "peratom")}
 
 
 def main(net, argv):

@@ -1,7 +1,8 @@
 """NumPy reference of the binned sums behind compute profile/mdp (csrc/profile.hip): the binning of fractional coordinates,
 the terms t = (m, m vx, m vy, m vz, m v.v) of an atom, their quantised int64 sums, their exact sums (math.fsum) and the
 normalisation of the compute's array.  n_edge counts the atoms a rounding of the fractional coordinate could put into the
-neighbouring bin: the device forms it with fused multiply-adds, NumPy does not."""
+neighbouring bin: the device forms it with fused multiply-adds, NumPy does not.  check_sums asks for none; edges and
+check_sums_with_edges bracket the rows such an atom can fall in (the randomised net, which cannot choose its states)."""
 import math
 
 import numpy as np
@@ -63,7 +64,7 @@ def table(lam, periodic, dims, nbins, mass, v, exponents=None, member=None, nato
     exact, absum = np.zeros((rows, W)), np.zeros((rows, W))
     order = np.argsort(row, kind="stable")
     cuts = np.searchsorted(row[order], np.arange(rows + 1))
-    for b in range(rows):
+    for b in np.flatnonzero(np.diff(cuts)):          # (the occupied rows: a grid may hold a million empty ones)
         tb = t[order[cuts[b]:cuts[b + 1]]]
         for k in range(W):
             exact[b, k] = math.fsum(tb[:, k])
@@ -83,6 +84,56 @@ def check_sums(count, sums, exponents, ref):
     err = np.abs(got - ref["exact"])
     assert np.all(err <= bound), (err.max(), np.argwhere(err > bound)[:5])
     return float((err[bound > 0] / bound[bound > 0]).max()) if np.any(bound > 0) else 0.0
+
+
+def edges(lam, periodic, dims, nbins, member=None):
+    """the members within EDGE of a bin edge, for check_sums_with_edges: dict(n_edge, may[rows], placed[rows]) -- may[r] the
+    number of edge atoms that can fall into row r (in every dimension where the atom sits at an edge, the bin on either side
+    of that edge, wrapped or clamped as bins() does), placed[r] the number of them that bins() puts there"""
+    lam = np.asarray(lam, dtype=np.float64)
+    rows = int(np.prod(nbins))
+    keep = np.ones(len(lam), dtype=bool) if member is None else np.asarray(member, dtype=bool)
+    may, placed = np.zeros(rows, dtype=np.int64), np.zeros(rows, dtype=np.int64)
+    at = np.zeros(len(lam), dtype=bool)
+    for d, n in zip(dims, nbins):
+        u = lam[:, d] * n
+        at |= np.abs(u - np.rint(u)) < EDGE
+    at &= keep
+    row = bins(lam, periodic, dims, nbins)[0]
+    for i in np.flatnonzero(at):
+        cand = [0]
+        for d, n in zip(dims, nbins):
+            u = float(lam[i, d]) * n
+            k = int(np.rint(u))
+            bs = (k - 1, k) if abs(u - k) < EDGE else (int(np.floor(u)),)
+            bs = {((b % n) + n) % n if periodic[d] else min(max(b, 0), n - 1) for b in bs}
+            cand = [c * n + b for c in cand for b in sorted(bs)]
+        for r in set(cand):
+            may[r] += 1
+        assert row[i] in cand
+        placed[row[i]] += 1
+    return dict(n_edge=int(at.sum()), may=may, placed=placed)
+
+
+def check_sums_with_edges(count, sums, exponents, ref, edge):
+    """check_sums for a read that may hold atoms within EDGE of a bin edge (edge: edges() of the same read): in a row no edge
+    atom can fall into, the count is exact and the sums lie within check_sums' bound; in a row one can fall into, the sums are
+    skipped and the count lies between the reference's count without the edge atoms bins() put there and that plus the edge
+    atoms that can fall there; the counts of all rows add to the reference's.  Returns (worst ratio to the bound, n_edge)."""
+    count, rc = np.asarray(count, dtype=np.int64), np.asarray(ref["count"], dtype=np.int64)
+    assert ref["n_edge"] == edge["n_edge"], (ref["n_edge"], edge["n_edge"])
+    sure = edge["may"] == 0
+    assert np.array_equal(count[sure], rc[sure]), np.flatnonzero(sure & (count != rc))
+    low = rc - edge["placed"]
+    assert np.all((count >= low) & (count <= low + edge["may"])), np.flatnonzero((count < low) | (count > low + edge["may"]))
+    assert int(count.sum()) == int(rc.sum())
+    ex = np.asarray(exponents, dtype=np.int32)
+    got = np.ldexp(np.asarray(sums, dtype=np.float64), -ex)
+    bound = np.ldexp(count.astype(np.float64)[:, None] * np.ones(W), -ex) + 2.0 ** -50 * ref["absum"]
+    err = np.abs(got - ref["exact"])
+    assert np.all(err[sure] <= bound[sure]), (err[sure].max(), np.argwhere((err > bound) & sure[:, None])[:5])
+    ok = (bound > 0) & sure[:, None]
+    return (float((err[ok] / bound[ok]).max()) if np.any(ok) else 0.0), edge["n_edge"]
 
 
 def normalise(count, sums, exponents, nbins, volume, boltz, mvv2e, mv2d, com):

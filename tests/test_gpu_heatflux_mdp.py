@@ -270,3 +270,60 @@ def test_bricks_aeam_are_refused_where_angular_centres_reach_remote_ghosts():
             assert code == ENOTIMPL and "remote ghosts" in text and "2 ranks" in text, (code, text)
     one = rank_fn(0, None, world=1)
     assert [c for c, _ in one["got"]] == [0, 0] and not one["remote"]
+
+
+# ---- the slots the runs above leave empty: more than 256 slots for mdp_slot_total_kernel<8>, a group of nobody
+@pytest.fixture(scope="module")
+def big():
+    """70 304 aluminium atoms (fcc 26^3, as the indenter's second-trip test), jittered by 0.05 A, at 300 K: 275 blocks.  Built
+    once for this module."""
+    s = S.fcc_cell(4.045, 26)
+    s.mass[1:3] = capi.AeamFile(POT_AEAM).mass[:2]
+    s = S.jitter(s, 0.05, seed=71)
+    assert s.n == 70304 and -(-s.n // 256) == 275 and s.n % 256 == 160
+    return s, S.gaussian_velocities(s, 300.0, seed=72)
+
+
+def test_the_slot_sums_second_trip_against_fsum(big, capsys):
+    """275 slots: mdp_slot_sum_256<8> takes a second trip.  One tallying compute, no step; the sums over all atoms and over
+    the atoms with tag % 3 == 0 against heatfluxref.sums of the downloaded v, eatom, vatom and mass within 1e-12 of the
+    terms' magnitudes (any order of adding n terms stays within n 2^-53 = 7.8e-12; a fixed tree does far better)"""
+    s, v0 = big
+    member = s.tag % 3 == 0
+    ctx, st, skin, cutghost, map_ = _context("aeam")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        assert -(-d.nlocal // 256) > 256                                   # the premise: more slots than lanes
+        mask = np.ones(s.n + 1, dtype=np.int32)
+        mask[1:] |= 2 * member.astype(np.int32)
+        d.set_group(mask, 0)
+        d.compute(3, 5)
+        got = _download(d)
+        assert np.abs(got["vatom"]).max() > 1e-2 and np.abs(got["eatom"]).max() > 1.0
+        worst = []
+        for bit, mem in ((0, None), (2, member[got["tags"] - 1])):
+            out, again = ctx.heatflux_sums(group_bit=bit), ctx.heatflux_sums(group_bit=bit)
+            ref = heatfluxref.sums(got["mass"], got["v"], got["eatom"], got["vatom"], S.MVV2E, member=mem)
+            assert np.array_equal(out, again) and out[6] == (s.n if mem is None else member.sum())
+            assert np.all(np.abs(out - ref["sums"]) <= 1e-12 * ref["mag"]), np.abs(out - ref["sums"]) / ref["mag"]
+            assert np.all(ref["mag"][:6] > 1.0)
+            worst.append(float((np.abs(out - ref["sums"]) / ref["mag"]).max()))
+        with capsys.disabled():
+            print(f"70 304 atoms, heat current against fsum: worst |device - exact| / sum|term| {worst[0]:.2e} (all), {worst[1]:.2e} (a third)")
+    finally:
+        ctx.close()
+
+
+def test_a_group_of_nobody():
+    """a group bit carried by no atom: mdp_heatflux_sums gives eight zeros, the count among them"""
+    s, v0 = _system("rebomos", 300.0)
+    ctx, st, skin, cutghost, map_ = _context("rebomos")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        d.set_group(np.ones(s.n + 1, dtype=np.int32), 0)
+        d.compute(3, 5)
+        out = ctx.heatflux_sums(group_bit=4)
+        assert out.shape == (8,) and not out.any()
+        assert not d.heatflux(group_bit=4).any() and ctx.heatflux_sums()[6] == s.n
+    finally:
+        ctx.close()

@@ -356,3 +356,122 @@ def test_refusals():
 
     for msg in resident.run_ranks(2, rank_fn):
         assert "one rank only" in msg and "brick of 2 ranks" in msg, msg
+
+
+# ---- the slots the runs above leave empty: more than 256 slots for mdp_slot_total_kernel<9>, the xz and yz terms of the
+# unwrap in msd.hip's own kernels, a group of nobody
+@pytest.fixture(scope="module")
+def big():
+    """70 304 aluminium atoms (fcc 26^3, as the indenter's second-trip test): 275 blocks.  Built once for this module."""
+    s = S.fcc_cell(4.045, 26)
+    s.mass[1:3] = capi.AeamFile(POT_AEAM).mass[:2]
+    assert s.n == 70304 and -(-s.n // 256) == 275 and s.n % 256 == 160
+    return s
+
+
+def test_the_slot_sums_second_trip_against_fsum(big, capsys):
+    """275 slots: mdp_slot_sum_256<9> takes a second trip.  Random images of -2 .. 2, origins passed by tag and displaced from
+    the unwrapped positions by a known random vector per atom (about 2 A), no step taken.  The unwrapped positions against
+    msdref.unwrap; the eight sums against math.fsum over the terms of the downloaded state.  Any order of adding n terms
+    stays within n 2^-53 = 7.8e-12 of the sum of their magnitudes; asked here is the 1e-12 of the indenter's second-trip
+    test (STOL, tests/test_gpu_indent_mdp.py), which a fixed tree meets with room."""
+    s = big
+    rng = np.random.default_rng(88)
+    img = rng.integers(-2, 3, (s.n, 3))
+    disp = rng.normal(0.0, 2.0, (s.n, 3))
+    ctx, st, skin, cutghost, map_ = _context("aeam")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=np.zeros((s.n, 3)))
+        assert -(-d.nlocal // 256) > 256                                   # the premise: more slots than lanes
+        d.track_images(resident.image_pack(img))
+        got = _state(d, s.n)
+        assert np.array_equal(got["image"], img)
+        want = msdref.unwrap(s.box, got["x"], img)
+        assert np.abs(got["xu"] - want).max() <= 8 * 2.0 ** -53 * (np.abs(got["x"]).max() + 2 * s.box.prd.max())
+        x0 = got["xu"] - disp
+        shift = np.array([0.3, -0.2, 0.1])
+        sums = {}
+        for bit, sel in ((0, np.ones(s.n, dtype=bool)), (2, s.tag % 3 == 0)):
+            if bit:
+                mask = np.ones(s.n + 1, dtype=np.int32)
+                mask[1:] |= 2 * sel.astype(np.int32)
+                d.set_group(mask, 0)
+            ctx.msd_setup(s.n, x0, bit)
+            for sh in (None, shift):
+                out, again = ctx.msd_sums(sh), ctx.msd_sums(sh)
+                assert out.tobytes() == again.tobytes()
+                dd = (got["xu"][sel] - x0[sel]) - (0.0 if sh is None else sh)
+                m = s.mass[s.type][sel]
+                cols = [dd[:, 0] ** 2, dd[:, 1] ** 2, dd[:, 2] ** 2, np.ones(len(m)), m * got["xu"][sel][:, 0], m * got["xu"][sel][:, 1],
+                        m * got["xu"][sel][:, 2], m]
+                ref = np.array([math.fsum(c) for c in cols])
+                mag = np.array([math.fsum(np.abs(c)) for c in cols])
+                sums[(bit, sh is None)] = float((np.abs(out - ref) / mag).max())
+                assert out[3] == sel.sum() and np.all(np.abs(out - ref) <= 1e-12 * mag), (bit, np.abs(out - ref) / mag)
+                assert out[:3].min() > 2.0 * sel.sum()                     # (the displacements are there: about 4 A^2 each)
+        with capsys.disabled():
+            print("70 304 atoms, msd sums against fsum, worst relative to the terms' magnitudes: "
+                  + ", ".join(f"bit {b} shift {not p}: {w:.2e}" for (b, p), w in sums.items()))
+    finally:
+        ctx.close()
+
+
+def test_a_box_with_all_three_tilts(capsys):
+    """mdp_unwrap's xz and yz terms through msd.hip's own kernels: the 864-atom alloy sheared into the box of
+    test_the_centre_of_mass_in_a_cell_sheared_in_xz_and_yz (tests/test_gpu_spring_mdp.py), 300 K plus a drift that changes
+    images in x, y and z within 30 steps (lists rebuilt every step).  Origins from the current positions at the start
+    (msd_origin_kernel), unwrapped_local (msd_unwrap_kernel) and the sums (msd_partial_kernel) against msdref in that box.
+    Not vacuous: unwrapped with the box stripped of xz and yz, the positions are tenths of an A elsewhere."""
+    af = capi.AeamFile(POT_AEAM)
+    s0 = S.fcc_cell(4.045, 6, frac_type2=0.05, seed=92)
+    s0.mass[1:3] = af.mass[:2]
+    box = S.Box(s0.box.lo.copy(), s0.box.prd.copy(), np.array([0.35, -0.45, 0.25]))
+    s = S.System(box, np.ascontiguousarray(box.lamda2x(s0.box.x2lamda(s0.x))), s0.type, s0.tag, s0.mass)
+    flat = S.Box(box.lo, box.prd, np.array([0.35, 0.0, 0.0]))
+    v0 = S.gaussian_velocities(s, 300.0, seed=3) + np.array([500.0, -400.0, 300.0])
+    ctx, st, skin, cutghost, map_ = _context("aeam")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        d.track_images()
+        x0 = _by_tag(s.n, d.tags_local, d.unwrapped_local())
+        d.msd()                                                            # origins from the current positions
+        d.compute(0, 0)
+        for _ in range(30):
+            d.step(0, 0, rebuild=True)
+        got = _state(d, s.n)
+        assert all((got["image"][:, k] != 0).sum() > s.n // 4 for k in range(3))
+        want = msdref.unwrap(s.box, got["x"], got["image"])
+        bound = 8 * 2.0 ** -53 * (np.abs(got["x"]) + S.mul_upper(np.abs(got["image"]).astype(float), np.abs(s.box.h)))
+        assert np.all(np.abs(got["xu"] - want) <= bound)
+        moved = np.abs(msdref.unwrap(flat, got["x"], got["image"]) - want)
+        assert moved[:, 0].max() > 0.4 and moved[:, 1].max() > 0.2           # (xz and yz do matter to it)
+        m = s.mass[s.type]
+        for com in (False, True):
+            val = d.msd_read(com=com)
+            ref = msdref.msd_values(got["xu"], x0, mass_per_atom=m, com=com)
+            with capsys.disabled():
+                print(f"all three tilts, com {com}: msd {val[3]:.6f} A^2, relative to fsum {_rel(val, ref):.2e}")
+            assert _rel(val, ref) < MSD_RTOL, (com, val, ref)
+        assert d.msd_read()[3] > 100.0 > d.msd_read(com=True)[3]
+        wrong = msdref.msd_values(msdref.unwrap(flat, got["x"], got["image"]), x0)
+        assert _rel(d.msd_read(), wrong) > 1e-6
+    finally:
+        ctx.close()
+
+
+def test_a_group_of_nobody():
+    """a group bit carried by no atom: mdp_msd_sums gives eight zeros, the count among them"""
+    s = S.rebomos_bulk_cell()
+    ctx, st, skin, cutghost, map_ = _context("rebomos")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_)
+        d.set_group(np.ones(s.n + 1, dtype=np.int32), 0)
+        d.track_images()
+        ctx.msd_setup(s.n, np.zeros((s.n, 3)), groupbit=4)
+        for shift in (None, np.array([1.0, 2.0, 3.0])):
+            out = ctx.msd_sums(shift)
+            assert out.shape == (8,) and not out.any()
+        ctx.msd_setup(s.n, np.zeros((s.n, 3)))
+        assert ctx.msd_sums()[3] == s.n
+    finally:
+        ctx.close()

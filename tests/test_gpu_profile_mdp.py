@@ -7,6 +7,7 @@ the lattices, so no plane of atoms sits at an edge."""
 import numpy as np
 import pytest
 
+from conftest import POT_AEAM
 from lammps_plugins_amd.host import capi, resident, system as S
 import profileref
 from test_gpu_rdf_mdp import _by_tag, _context, _mig_system, _system, MIG_READS, MIG_RENB, MIG_STEPS
@@ -274,5 +275,176 @@ def test_refusals():
             with pytest.raises(capi.MdpError, match="mdp_dd_setup not called") as e:
                 call()
             assert e.value.code == ESTATE
+    finally:
+        ctx.close()
+
+
+# ---- the slots the small systems above leave empty: more than 256 blocks and a workgroup that walks many of them
+# (MDP_MEASURE_GRID), the two sides of the LDS / global switch, a box with all three tilts, a group of nobody, 0 K, bit 31
+BIG_GRIDS = [((2,), (7,)), ((0,), (819,)), ((0, 1, 2), (16, 16, 16))]
+
+
+@pytest.fixture(scope="module")
+def big():
+    """70 304 aluminium atoms (fcc 26^3, as the indenter's second-trip test), jittered by 0.05 A so that no lattice plane sits
+    at a bin edge, at 300 K; built once for this module"""
+    s = S.fcc_cell(4.045, 26)
+    s.mass[1:3] = capi.AeamFile(POT_AEAM).mass[:2]
+    s = S.jitter(s, 0.05, seed=61)
+    assert s.n == 70304 and -(-s.n // 256) == 275
+    return s, S.gaussian_velocities(s, 300.0, seed=62)
+
+
+def test_many_blocks_and_one_workgroup_read_the_same(big, monkeypatch, capsys):
+    """275 blocks: unset, profile_range_total_kernel strides over more than 256 slots; at MDP_MEASURE_GRID = 3 and 1 every
+    kernel's loop takes 92 and 275 trips and, at 1, one workgroup flushes everything.  The range, the exponents and the
+    tables of a 7-row, an 819-row (the largest LDS layout) and a 4 096-row grid (straight to global) are identical under the
+    three settings, and inside check_sums' bound of the reference.  No step is taken.  The atom the device keeps last (the
+    positions alone decide the order; a first set-up tells which it is) is given the largest velocity components of all, so
+    the maxima of the momentum and energy columns come from slot 274, beyond the first trip over the slots."""
+    s, v0 = big
+    ctx, st, skin, cutghost, map_ = _context("aeam")
+    try:
+        last = int(resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0).tags_local[-1])
+    finally:
+        ctx.close()
+    v0 = v0.copy()
+    v0[last - 1] = 1.5 * np.abs(v0).max(axis=0)
+    ctx, st, skin, cutghost, map_ = _context("aeam")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        assert d.nlocal == s.n and -(-d.nlocal // 256) > 256           # the premise: the slot loop takes a second trip
+        assert int(d.tags_local[-1]) == last
+        state = _state(d, s)
+        assert all(int(np.argmax(np.abs(profileref.terms(state[1], state[2])[:, k]))) == last - 1 for k in range(1, 5))
+        got = {}
+        for knob in (None, "3", "1"):
+            if knob is None:
+                monkeypatch.delenv("MDP_MEASURE_GRID", raising=False)
+            else:
+                monkeypatch.setenv("MDP_MEASURE_GRID", knob)
+            got[knob] = []
+            for dims, nbins in BIG_GRIDS:
+                d.profile(dims, nbins)
+                got[knob].append((ctx.profile_range(),) + d.profile_read())
+        monkeypatch.delenv("MDP_MEASURE_GRID", raising=False)
+        t = profileref.terms(state[1], state[2])
+        # a maximum, whatever the grid: m and m v are one product each, the same bits in NumPy; m v.v is formed with fused
+        # multiply-adds on the device, within 3 roundings of NumPy's
+        tmax = np.abs(t).max(axis=0)
+        rng = got[None][0][0]
+        assert np.array_equal(rng[:4], tmax[:4]) and abs(rng[4] - tmax[4]) <= 4 * 2.0 ** -53 * tmax[4]
+        worst = []
+        for k, (dims, nbins) in enumerate(BIG_GRIDS):
+            _, count, sums, ex = got[None][k]
+            for knob in ("3", "1"):
+                assert all(np.array_equal(a, b) for a, b in zip(got[knob][k], (rng, count, sums, ex))), (knob, nbins)
+            ref = profileref.table(state[0], PER, dims, nbins, state[1], state[2], exponents=ex)
+            assert ex.tolist() == [profileref.exponent(r, s.n) for r in ref["rng"]]
+            worst.append(profileref.check_sums(count, sums, ex, ref))
+            assert count.sum() == s.n and (count > 0).sum() >= min(count.size, 52)      # (52 lattice planes, 0.1 A thick, along x)
+        with capsys.disabled():
+            print("70 304 atoms, knob unset / 3 / 1 identical; worst error / bound per grid " + ", ".join(f"{w:.3f}" for w in worst))
+    finally:
+        ctx.close()
+
+
+def test_either_side_of_the_lds_switch():
+    """the 1 152-atom MoS2 state after 10 steps: 819 rows are the largest table a workgroup keeps in LDS (4 095 sums, then 819
+    counts from byte 32 760), 820 rows go straight to global.  1-d grids of 819 and 820 bins and 3-d grids of (9, 7, 13) and
+    (4, 5, 41) rows against the reference; the exponents depend on the range alone, so the 1-d pair summed over all rows
+    gives the same integers, column by column"""
+    s, v0 = _system("rebomos", 300.0)
+    ctx, st, skin, cutghost, map_ = _context("rebomos")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        d.compute(0, 0)
+        for _ in range(10):
+            d.step(0, 0, rebuild="auto")
+        state = _state(d, s)
+        got = {}
+        for dims, nbins in (((0,), (819,)), ((0,), (820,)), ((0, 1, 2), (9, 7, 13)), ((0, 1, 2), (4, 5, 41))):
+            rows = int(np.prod(nbins))
+            assert (rows * 5 <= 4096) == (rows == 819) and rows in (819, 820)
+            d.profile(dims, nbins)
+            count, sums, ex, ref, _ = _check(d, s, dims, nbins, state=state)
+            assert count.sum() == s.n
+            got[nbins] = (count, sums, ex)
+        a, b = got[(819,)], got[(820,)]
+        assert np.array_equal(a[2], b[2]) and a[0].sum() == b[0].sum() and np.array_equal(a[1].sum(axis=0), b[1].sum(axis=0))
+        assert np.array_equal(got[(9, 7, 13)][1].sum(axis=0), got[(4, 5, 41)][1].sum(axis=0))
+    finally:
+        ctx.close()
+
+
+def _sheared_alloy():
+    """the 864-atom alloy sheared homogeneously into the box with all three tilts of
+    test_the_centre_of_mass_in_a_cell_sheared_in_xz_and_yz (tests/test_gpu_spring_mdp.py), at 300 K with a drift that takes
+    atoms through the faces in x, y and z within 30 steps"""
+    s0, v0 = _system("aeam", 300.0)
+    box = S.Box(s0.box.lo.copy(), s0.box.prd.copy(), np.array([0.35, -0.45, 0.25]))
+    s = S.System(box, np.ascontiguousarray(box.lamda2x(s0.box.x2lamda(s0.x))), s0.type, s0.tag, s0.mass)
+    return s, v0 + np.array([500.0, -400.0, 300.0]), S.Box(box.lo, box.prd, np.array([0.35, 0.0, 0.0]))
+
+
+def test_a_box_with_all_three_tilts():
+    """dd_x2lamda's yz and xz terms: after 30 steps of the drift (the lists rebuilt every step, images changed in x, y and z)
+    a profile over (z, x) and one over (x, y, z) against the reference.  Not vacuous: the reference in the box stripped of xz
+    and yz counts differently"""
+    s, v0, flat = _sheared_alloy()
+    ctx, st, skin, cutghost, map_ = _context("aeam")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        d.track_images()
+        d.compute(0, 0)
+        for _ in range(30):
+            d.step(0, 0, rebuild=True)
+        assert all((d.images_local()[:, k] != 0).sum() > s.n // 4 for k in range(3))
+        got = d.ctx.md_download(d.nlocal, want=("x", "v"))
+        x, v = _by_tag(s.n, d.tags_local, got["x"]), _by_tag(s.n, d.tags_local, got["v"])
+        for dims, nbins in (((2, 0), (5, 7)), ((0, 1, 2), (6, 5, 7))):
+            d.profile(dims, nbins)
+            count, sums, ex, ref, _ = _check(d, s, dims, nbins, state=(s.box.x2lamda(x), s.mass[s.type], v))
+            other = profileref.table(flat.x2lamda(x), PER, dims, nbins, s.mass[s.type], v, exponents=ex)
+            assert count.sum() == s.n and (other["count"] != ref["count"]).sum() > 10, nbins
+    finally:
+        ctx.close()
+
+
+def test_nobody_zero_kelvin_and_bit_31():
+    """a group bit no atom carries: range, exponents and tables all 0.  Velocities exactly zero: the exponents of the momentum
+    and energy columns are 0 and their sums 0, the mass column and the counts exact.  A group on bit 31 (the sign bit of the
+    mask) against the reference"""
+    s, _ = _system("rebomos", 300.0)
+    member = s.tag % 3 == 0
+    mask = np.ones(s.n + 1, dtype=np.uint32)
+    mask[1:][member] |= 0x80000000
+    ctx, st, skin, cutghost, map_ = _context("rebomos")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=np.zeros((s.n, 3)))
+        d.set_group(mask.view(np.int32), 0)
+        for dims, nbins in (((2,), (7,)), ((0, 1), (41, 20))):                  # LDS, and straight to global
+            d.profile(dims, nbins, group_bit=4)
+            assert not ctx.profile_range().any()
+            count, sums, ex = d.profile_read()
+            assert not ex.any() and not count.any() and not sums.any() and count.size == int(np.prod(nbins))
+            d.profile(dims, nbins)                                              # everyone, at 0 K
+            count, sums, ex, ref, _ = _check(d, s, dims, nbins)
+            assert not ex[1:].any() and not sums[:, 1:].any() and ex[0] == profileref.exponent(s.mass[1:3].max(), s.n)
+            assert np.array_equal(sums[:, 0], ref["sums"][:, 0]) and count.sum() == s.n
+    finally:
+        ctx.close()
+    s, v0 = _system("rebomos", 300.0)
+    ctx, st, skin, cutghost, map_ = _context("rebomos")
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        d.set_group(mask.view(np.int32), 0)
+        d.compute(0, 0)
+        for _ in range(5):
+            d.step(0, 0, rebuild="auto")
+        for dims, nbins in (((2,), (7,)), ((0, 1), (41, 20))):
+            d.profile(dims, nbins, group_bit=-2 ** 31)
+            count, sums, ex, ref, _ = _check(d, s, dims, nbins, member=member)
+            assert count.sum() == member.sum() == s.n // 3
     finally:
         ctx.close()

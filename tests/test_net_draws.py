@@ -132,6 +132,35 @@ CORNERS = {
         "a drift on several ranks": lambda c: any(any(s["drift"]) and s["ranks"] > 1 for s in c),
         "at most 16 cases": lambda c: len(c) <= 16,
     },
+    "peratom": {   # (what the reference makes of these cases: test_peratom_cases_meet_their_own_conditions)
+        "both styles": lambda c: {s["style"] for s in c} == {"rebomos", "aeam"},
+        "a box with all three tilts": lambda c: any(s["tilt"] is not None and all(s["tilt"]) for s in c),
+        "a free dimension": lambda c: any(any(s["nonperiodic"]) for s in c),
+        "8 bricks": lambda c: any(s["ranks"] == 8 for s in c),
+        "each group kind": lambda c: {s["group"]["kind"] for s in c} == set(nets.PA_GROUPS),
+        "a group of one atom": lambda c: any(s["group"]["kind"] == "few" and len(s["group"]["tags"]) == 1 for s in c),
+        "bit 31 on a group with members": lambda c: any(s["group"]["bit"] == 1 << 31 and s["group"]["kind"] not in ("none", "nobody") for s in c),
+        "0 K": lambda c: any(s["temp"] == 0 for s in c),
+        "819 rows": lambda c: any(nets.peratom_rows(g) == 819 for s in c for g in s["grids"]),
+        "820 rows": lambda c: any(nets.peratom_rows(g) == 820 for s in c for g in s["grids"]),
+        "a 3-d grid": lambda c: any(len(g[0]) == 3 and min(g[1]) > 1 for s in c for g in s["grids"]),
+        "a grid above 4 096 words": lambda c: any(nets.peratom_rows(g) * 5 > 4096 for s in c for g in s["grids"]),
+        "every case has a grid in LDS": lambda c: all(min(nets.peratom_rows(g) for g in s["grids"]) * 5 <= 4096 for s in c),
+        "no grid above PROFILE_MAXBINS": lambda c: all(nets.peratom_rows(g) <= nets.PA_MAXBINS for s in c for g in s["grids"]),
+        "the knob at 1 on one brick": lambda c: any(s["env"].get("MDP_MEASURE_GRID") == "1" and s["ranks"] == 1 for s in c),
+        "the knob unset": lambda c: any(not s["env"] for s in c),
+        "origins taken mid-run": lambda c: any(s["origin"]["at"] == "between" for s in c),
+        "origins from the current positions and by tag": lambda c: {s["origin"]["mode"] for s in c} == {"null", "tag"},
+        "a com read of a group": lambda c: any(s["group"]["kind"] not in ("none", "nobody") for s in c),
+        "a deferred last half, and not": lambda c: {s["defer"] for s in c} == {True, False},
+        "each compute reads first after a deferred half": lambda c: {s["first_read"] for s in c if s["defer"] and (s["heatflux"] or s["first_read"] != "heatflux")} == set(nets.PA_ORDER),
+        "a fast drift": lambda c: any(s["fast_on"] for s in c),
+        "a drift on several bricks": lambda c: any(any(s["drift"]) and s["ranks"] > 1 for s in c),
+        "heatflux on a sheared alloy and on one with a free dimension": lambda c: any(s["heatflux"] and s["tilt"] is not None for s in c)
+        and any(s["heatflux"] and any(s["nonperiodic"]) for s in c),
+        "the device's own check and forced rebuilds": lambda c: {s["rebuild"] == "auto" for s in c} == {True, False},
+        "at most 16 cases": lambda c: len(c) <= 16,
+    },
 }
 
 
@@ -282,8 +311,8 @@ def test_measure_cases_meet_their_own_conditions():
     (three times the floor of a read, for what thermal motion takes out of a first shell); the draw's own counts of entries
     and angles are the references'."""
     for spec in SPECS["measure"]:
-        s = nets._msr_start(spec)
-        member = nets.measure_member(spec, s)
+        s = nets._cell_start(spec)
+        member = nets.group_member(spec, s)
         rref, aref = nets.measure_references(spec, s.x, s.type, s.box.h, member)
         entries, angles = int(rref["hist"].sum()), int(aref["hist"].sum())
         print(spec["id"], f"{entries} entries, {angles} angles, at most {aref['max_neighbours']} neighbours, edge events "
@@ -299,3 +328,40 @@ def test_measure_cases_meet_their_own_conditions():
             assert member.sum() in (2, 3)
         elif spec["group"]["kind"] != "one type out":
             assert entries >= nets.MSR_FLOOR_START and angles >= nets.MSR_FLOOR_START, (spec["id"], entries, angles)
+
+
+def test_peratom_cases_meet_their_own_conditions():
+    """No GPU, no oracle.  On the start state of every `peratom` case of the suite the reference alone meets the conditions the
+    case sets itself: at most 2 atoms within 1e-9 of a bin edge in either grid (expected n x sum(nbin) x 2e-9, below 1e-2),
+    the premise of the image check (1.5 x the speed cap x dt x the steps between two reads stays below half the smallest
+    perpendicular width), a step between two list builds under the rule of _cell_velocities where the drift is fast, the
+    group the case names (nobody: no member; a few: 1 - 3), zero velocities at 0 K, and the reference passes its own check"""
+    import profileref
+    for spec in SPECS["peratom"]:
+        s = nets._cell_start(spec)
+        v0, safe = nets._cell_velocities(spec, s)
+        member = nets.peratom_member(spec, s)
+        kind = spec["group"]["kind"]
+        assert (member is None) == (kind == "none")
+        if kind == "nobody":
+            assert not member.any()
+        elif kind == "few":
+            assert member.sum() == spec["group"]["count"] in (1, 2, 3)
+        elif kind != "none":
+            assert 0 < member.sum() < s.n
+        if spec["temp"] == 0:
+            assert not v0.any() and not any(spec["drift"])
+        if spec["fast_on"]:
+            assert nets.PA_FAST in np.abs(spec["drift"]) and int(0.3 * nets.MSR_SKIN[spec["style"]] / (spec["vcap"] * nets.PA_DT)) >= 1
+        reads = sorted({0, spec["between"], spec["nsteps"]})
+        assert 0 < spec["between"] < spec["nsteps"] and spec["nsteps"] >= 5
+        assert 1.5 * spec["vcap"] * nets.PA_DT * max(np.diff(reads)) < 0.98 * nets.peratom_half_width(s.box)
+        per = tuple(bool(p) for p in nets._cell_periodic(spec))
+        lam = s.box.x2lamda(s.x)
+        for dims, nbins in spec["grids"]:
+            assert s.n * sum(nbins) * 2e-9 < 1e-2, spec["id"]
+            ref = profileref.table(lam, per, dims, nbins, s.mass[s.type], v0, member=member, natoms_total=s.n)
+            edge = profileref.edges(lam, per, dims, nbins, member)
+            assert edge["n_edge"] <= 2, (spec["id"], edge["n_edge"])
+            profileref.check_sums_with_edges(ref["count"], ref["sums"], ref["exponents"], ref, edge)
+            assert ref["count"].sum() == (s.n if member is None else member.sum())

@@ -64,6 +64,45 @@ def test_edge_atoms_are_counted():
     assert profileref.bins(lam, (True,) * 3, (2, 1), (3, 4))[1] == 1
 
 
+def test_check_sums_with_edges_brackets_the_rows_of_an_edge_atom_and_no_other():
+    """three atoms planted at bin edges of a (4, 3) grid over (0, 2) -- one at an x edge, one at a z edge, one at a corner, a
+    periodic face among them --: the rows either side of each edge are bracketed, every other row stays exact; a table in
+    which the planted atoms sit on the other side passes, one with an atom moved between sure rows, or with a sum of a sure
+    row off by more than its bound, does not; without edge atoms the variant is check_sums"""
+    lam, mass, v = _atoms(seed=11)
+    lam[0], lam[1], lam[2] = (0.5 - 1e-12, 0.3, 0.2), (0.1, 0.3, 2.0 / 3.0 + 1e-12), (1.0 - 1e-12, 0.3, 1.0 / 3.0 - 1e-12)
+    per, dims, nbins = (True, True, True), (0, 2), (4, 3)
+    ref = profileref.table(lam, per, dims, nbins, mass, v)
+    edge = profileref.edges(lam, per, dims, nbins)
+    assert ref["n_edge"] == edge["n_edge"] == 3
+    want = np.zeros(12, dtype=int)
+    for r in (1 * 3 + 0, 2 * 3 + 0, 0 * 3 + 1, 0 * 3 + 2, 3 * 3 + 0, 3 * 3 + 1, 0 * 3 + 0, 0 * 3 + 1):     # (x 1|2, z 0), (x 0, z 1|2), (x 3|0, z 0|1)
+        want[r] += 1
+    assert edge["may"].tolist() == want.tolist() and edge["placed"].sum() == 3 and np.all(edge["placed"] <= edge["may"])
+    with pytest.raises(AssertionError):
+        profileref.check_sums(ref["count"], ref["sums"], ref["exponents"], ref)
+    worst, n_edge = profileref.check_sums_with_edges(ref["count"], ref["sums"], ref["exponents"], ref, edge)
+    assert n_edge == 3 and 0.0 < worst <= 0.5
+    other = profileref.table(np.vstack([[0.5 + 1e-12, 0.3, 0.2], lam[1:]]), per, dims, nbins, mass, v, exponents=ref["exponents"])
+    assert not np.array_equal(other["count"], ref["count"])
+    profileref.check_sums_with_edges(other["count"], other["sums"], ref["exponents"], ref, edge)
+    moved = ref["count"].copy()
+    moved[5] -= 1
+    moved[8] += 1                                     # rows (1, 2) and (2, 2): no planted atom can fall there
+    assert edge["may"][5] == edge["may"][8] == 0
+    with pytest.raises(AssertionError):
+        profileref.check_sums_with_edges(moved, ref["sums"], ref["exponents"], ref, edge)
+    off = ref["sums"].copy()
+    off[5, 4] += 4 * ref["count"][5]
+    with pytest.raises(AssertionError):
+        profileref.check_sums_with_edges(ref["count"], off, ref["exponents"], ref, edge)
+    lam2 = _atoms(seed=11)[0]
+    ref2, edge2 = profileref.table(lam2, per, dims, nbins, mass, v), profileref.edges(lam2, per, dims, nbins)
+    assert edge2["n_edge"] == 0 and not edge2["may"].any()
+    assert profileref.check_sums_with_edges(ref2["count"], ref2["sums"], ref2["exponents"], ref2, edge2)[0] == \
+        profileref.check_sums(ref2["count"], ref2["sums"], ref2["exponents"], ref2)
+
+
 @pytest.mark.parametrize("com", [False, True])
 def test_profile_normalise_against_the_reference(com):
     lam, mass, v = _atoms(seed=9)
