@@ -474,10 +474,7 @@ int mdp_dd_setup(mdp_ctx *c, const mdp_dd_config *cfg)
     return mdp_fail(c, MDP_ESTATE, "mdp_dd_setup: Langevin zero and tally (mdp_langevin_setup) run on one rank only, not on a brick of several ranks");
   if (c->heat.on && (long long) cfg->procgrid[0] * cfg->procgrid[1] * cfg->procgrid[2] > 1)
     return mdp_fail(c, MDP_ESTATE, "mdp_dd_setup: heat sources (mdp_heat_setup) run on one rank only, not on a brick of several ranks");
-  if (c->indent.on && (long long) cfg->procgrid[0] * cfg->procgrid[1] * cfg->procgrid[2] > 1)
-    return mdp_fail(c, MDP_ESTATE, "mdp_dd_setup: indenters (mdp_indent_setup) run on one rank only, not on a brick of several ranks");
-  if (c->spring.on && (long long) cfg->procgrid[0] * cfg->procgrid[1] * cfg->procgrid[2] > 1)
-    return mdp_fail(c, MDP_ESTATE, "mdp_dd_setup: springs (mdp_spring_setup) run on one rank only, not on a brick of several ranks");
+  if ((long long) cfg->procgrid[0] * cfg->procgrid[1] * cfg->procgrid[2] > 1) MDP_TRY(mdp_refuse_if_on(c, "mdp_dd_setup", kRefuseOneRank));
   if (c->fire.on && (long long) cfg->procgrid[0] * cfg->procgrid[1] * cfg->procgrid[2] > 1)
     return mdp_fail(c, MDP_ESTATE, "mdp_dd_setup: the minimiser (mdp_fire_setup) runs on one rank only, not on a brick of several ranks");
   MdpDomain &D = c->dd;

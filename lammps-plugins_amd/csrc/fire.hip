@@ -345,8 +345,7 @@ int mdp_fire_setup(mdp_ctx *c, const mdp_fire_config *cfg)
     return mdp_fail(c, MDP_ESTATE, "mdp_fire_setup: a thermostat (%s) is on; switch it off first",
                     c->nhc.on ? "mdp_nhc_setup" : "mdp_langevin_setup");
   if (c->heat.on) return mdp_fail(c, MDP_ESTATE, "mdp_fire_setup: heat sources (mdp_heat_setup) are on; mdp_heat_off first");
-  if (c->indent.on) return mdp_fail(c, MDP_ESTATE, "mdp_fire_setup: indenters (mdp_indent_setup) are on; mdp_indent_off first");
-  if (c->spring.on) return mdp_fail(c, MDP_ESTATE, "mdp_fire_setup: springs (mdp_spring_setup) are on; mdp_spring_off first");
+  MDP_TRY(mdp_refuse_if_on(c, "mdp_fire_setup", kRefuseOffFirst));
   if (!c->neigh_set) return mdp_fail(c, MDP_ESTATE, "mdp_fire_setup: neighbor list not built (mdp_dd_reneighbor)");
   if (!(cfg->etol >= 0.0) || !(cfg->ftol >= 0.0)) return mdp_fail(c, MDP_EINVAL, "mdp_fire_setup: etol and ftol must be >= 0");
   if (cfg->maxiter < 0 || cfg->maxeval < 0) return mdp_fail(c, MDP_EINVAL, "mdp_fire_setup: maxiter and maxeval must be >= 0");

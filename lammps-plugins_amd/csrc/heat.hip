@@ -196,8 +196,6 @@ HeatBits heat_bits(int nsrc, const int *bit)
   return B;
 }
 
-bool heat_mask_current(const mdp_ctx *c) { return c->mask_set && c->mask_n == c->nlocal; }
-
 // counts the current mask for `nsrc` sources and refuses what a source cannot have (who: the call)
 int heat_count(mdp_ctx *c, const char *who, int nsrc, const int *bit)
 {
@@ -221,14 +219,6 @@ int heat_count(mdp_ctx *c, const char *who, int nsrc, const int *bit)
   return MDP_OK;
 }
 
-MdpGroupArgs heat_mask_args(const mdp_ctx *c)
-{
-  MdpGroupArgs M;
-  M.mask = c->mask.p;
-  M.perm = !c->md && c->host_sort ? c->host_perm.p : nullptr; // host mode: the mask is in the host's order
-  return M;
-}
-
 } // namespace
 
 int mdp_heat_mask(mdp_ctx *c, const char *who)
@@ -237,7 +227,7 @@ int mdp_heat_mask(mdp_ctx *c, const char *who)
   if (!h.on) return MDP_OK;
   h.counted = false;
   h.mass_due = true;
-  if (!heat_mask_current(c)) return MDP_OK; // (the mask was withdrawn: the next pass says so)
+  if (!mdp_mask_current(c)) return MDP_OK; // (the mask was withdrawn: the next pass says so)
   MDP_TRY(heat_count(c, who, h.nsrc, h.bit));
   h.counted = true;
   return MDP_OK;
@@ -251,7 +241,7 @@ int mdp_heat_pass(mdp_ctx *c)
   for (int k = 0; k < h.nsrc; k++)
     if (h.step % h.cfg[k].nevery == 0) due |= 1 << k;
   if (!due) return MDP_OK;
-  if (!heat_mask_current(c))
+  if (!mdp_mask_current(c))
     return mdp_fail(c, MDP_ESTATE, "%d heat sources are on (mdp_heat_setup) but no mask covers the current atoms (%s)", h.nsrc,
                     c->md ? "mdp_md_set_mask" : "mdp_hnve_set_mask after mdp_set_atoms_host");
   if (!h.counted) { // (a group call after the mask: counted once, here)
@@ -264,7 +254,7 @@ int mdp_heat_pass(mdp_ctx *c)
   MDP_HIP(c, h.part.reserve((size_t) kHeatW * nbs));
   const MdpStep s = mdp_step(c);
   const HeatBits B = heat_bits(h.nsrc, h.bit);
-  const MdpGroupArgs M = heat_mask_args(c);
+  const MdpGroupArgs M = mdp_mask_args(c);
   HeatCtl a;
   for (int k = 0; k < h.nsrc; k++) {
     a.heat[k] = h.cfg[k].eflux * h.cfg[k].nevery * s.dt * s.ftm2v;
@@ -314,8 +304,7 @@ int mdp_heat_setup(mdp_ctx *c, int nsrc, const mdp_heat_config *cfg, const int *
   }
   if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
   if (c->nhc.on) return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: the Nose-Hoover chain (mdp_nhc_setup) is on; heat sources run without a thermostat");
-  if (c->indent.on) return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: indenters (mdp_indent_setup) are on; mdp_indent_off first");
-  if (c->spring.on) return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: springs (mdp_spring_setup) are on; mdp_spring_off first");
+  MDP_TRY(mdp_refuse_if_on(c, "mdp_heat_setup", kRefuseOffFirst));
   if (c->lgv.on)
     return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: the Langevin thermostat (mdp_langevin_setup) is on; heat sources run without a thermostat");
   if (c->dd.on && c->dd.G.nranks > 1)
@@ -327,7 +316,7 @@ int mdp_heat_setup(mdp_ctx *c, int nsrc, const mdp_heat_config *cfg, const int *
     h.on = false;
     MDP_TRY(mdp_md_flush_final(c));
   }
-  if (!heat_mask_current(c))
+  if (!mdp_mask_current(c))
     return mdp_fail(c, MDP_ESTATE, "mdp_heat_setup: no mask covers the current atoms (%s)",
                     c->md ? "mdp_md_set_mask" : "mdp_hnve_set_mask after mdp_set_atoms_host");
   MDP_TRY(heat_count(c, "mdp_heat_setup", nsrc, groupbit));

@@ -8,8 +8,8 @@
 // in two launches: one lane per owned atom that adds the forces of every indenter into f and leaves, per block and
 // indenter, energy, force and contact count in fixed slots (indent_force_kernel); one workgroup that adds the slots in a
 // fixed order and leaves the state of every indenter in device memory (indent_control_kernel).  No float atomics and no
-// host wait: a run is bitwise reproducible.  md.hip calls mdp_indent_pass at the top of md_final_half and
-// md_launch_advance unless the current forces have had their pass (MdpIndent::applied).
+// host wait: a run is bitwise reproducible.  The indenters are the first post-force stage of a context (kMdpStages,
+// mdp_common.h): mdp_postforce_apply calls mdp_indent_pass, and postforce.hip holds the life cycle they share with the springs.
 #include "mdp_common.h"
 
 #include <cmath>
@@ -139,15 +139,6 @@ __global__ __launch_bounds__(256) void indent_control_kernel(const double *__res
   }
 }
 
-bool indent_mask_current(const mdp_ctx *c) { return c->mask_set && c->mask_n == c->nlocal; }
-
-int indent_any_bit(int n, const int *bit)
-{
-  int any = 0;
-  for (int k = 0; k < n; k++) any |= bit[k];
-  return any;
-}
-
 // the context's own box and periodicity: a brick's (resident, or host-linked with bricks), else the box a host-linked
 // context was handed (one periodic rank)
 bool indent_box(const mdp_ctx *c, double h[6], int per[3])
@@ -171,21 +162,14 @@ int indent_no_mask(mdp_ctx *c, const char *who)
                   c->md ? "mdp_md_set_mask" : "mdp_hnve_set_mask after mdp_set_atoms_host");
 }
 
-// mdp_indent_setup / _run: the forces the context holds are taken to be the pair style's alone, those of step `first`
-void indent_restart(MdpIndent &h, long long first)
-{
-  h.first = first;
-  h.nhalf = 0;
-  h.applied = false;
-}
-
 } // namespace
 
 int mdp_indent_pass(mdp_ctx *c)
 {
   MdpIndent &h = c->indent;
   IndentArgs A;
-  if (indent_any_bit(h.n, h.bit) && !indent_mask_current(c)) return indent_no_mask(c, "integrate");
+  const int any = mdp_slot_bits(h.n, h.bit).any;
+  if (any && !mdp_mask_current(c)) return indent_no_mask(c, "integrate");
   if (!indent_box(c, A.h, A.per)) return mdp_fail(c, MDP_ESTATE, "indenters are on (mdp_indent_setup) but the context has no box any more");
   const int n = c->nlocal, nb = nblk(n);
   MDP_HIP(c, h.part.reserve((size_t) kIndW * (nb ? nb : 1)));
@@ -203,15 +187,10 @@ int mdp_indent_pass(mdp_ctx *c)
     A.r[k] = q.r;
     for (int d = 0; d < 3; d++) A.c[k][d] = a.c[k][d] = q.c[d] + q.vel[d] * t;
   }
-  MdpGroupArgs M;
-  if (indent_any_bit(h.n, h.bit)) {
-    M.mask = c->mask.p;
-    M.perm = !c->md && c->host_sort ? c->host_perm.p : nullptr; // host mode: the mask is in the host's order
-  }
+  const MdpGroupArgs M = any ? mdp_mask_args(c) : MdpGroupArgs();
   if (n) indent_force_kernel<<<nb, 256, 0, c->stream>>>(n, c->xq.p, c->f.p, A, h.part.p, M);
   indent_control_kernel<<<1, 256, 0, c->stream>>>(h.part.p, nb, a, h.st.p);
   MDP_HIP(c, hipGetLastError());
-  h.applied = true;
   return MDP_OK;
 }
 
@@ -235,75 +214,25 @@ int mdp_indent_setup(mdp_ctx *c, int n, const mdp_indent_config *cfg, const int 
     if (q.shape == MDP_INDENT_CYLINDER && q.vel[q.dim] != 0.0)
       return mdp_fail(c, MDP_EINVAL, "mdp_indent_setup: indenter %d: a cylinder cannot move along its axis (vel[%d] = %g)", k, q.dim, q.vel[q.dim]);
   }
-  if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_indent_setup: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
-  if (c->nhc.on) return mdp_fail(c, MDP_ESTATE, "mdp_indent_setup: the Nose-Hoover chain (mdp_nhc_setup) is on; indenters run under NVE and Langevin baths");
-  if (c->heat.on) return mdp_fail(c, MDP_ESTATE, "mdp_indent_setup: heat sources (mdp_heat_setup) are on; mdp_heat_off first");
-  if (c->dd.on && c->dd.G.nranks > 1)
-    return mdp_fail(c, MDP_ESTATE, "mdp_indent_setup: indenters run on one rank only (this context is a brick of %d ranks)", c->dd.G.nranks);
+  MDP_TRY(mdp_postforce_refuse_setup(c, kStageIndent));
   if (!c->md && !c->hn_on) return mdp_fail(c, MDP_ESTATE, "mdp_indent_setup: no integrator on the context (mdp_md_setup or mdp_hnve_setup)");
   double hbox[6];
   int per[3];
   if (!indent_box(c, hbox, per))
     return mdp_fail(c, MDP_ESTATE, "mdp_indent_setup: no box on the context (%s)", c->md ? "mdp_dd_setup" : "mdp_set_box_host");
-  if (indent_any_bit(n, groupbit) && !indent_mask_current(c)) return indent_no_mask(c, "mdp_indent_setup");
+  if (mdp_slot_bits(n, groupbit).any && !mdp_mask_current(c)) return indent_no_mask(c, "mdp_indent_setup");
   // (everything that can be refused has been: indenters that were on stay on, as they were, after a refusal above)
   MDP_HIP(c, hipSetDevice(c->device));
-  MdpIndent &h = c->indent;
-  if (c->md) { // a final half the host deferred belongs to the run before: it completes now, without indenters
-    const bool was_on = h.on;
-    h.on = false;
-    const int rc = mdp_md_flush_final(c);
-    if (rc != MDP_OK) {
-      h.on = was_on;
-      return rc;
-    }
-  }
-  MDP_HIP(c, h.st.reserve(kI * kLen));
-  const double st[kI * kLen] = {};
-  MDP_TRY(mdp_write_small(c, h.st.p, st, sizeof st));
-  h.n = n;
-  for (int k = 0; k < kI; k++) {
-    h.bit[k] = k < n ? groupbit[k] : 0;
-    if (k < n) h.cfg[k] = cfg[k];
-  }
-  indent_restart(h, 0);
-  h.on = true;
-  return MDP_OK;
+  return mdp_postforce_commit(c, kStageIndent, kI * kLen, n, groupbit, c->indent.cfg, cfg, sizeof *cfg);
 }
 
-int mdp_indent_run(mdp_ctx *c, long long first)
-{
-  if (!c) return MDP_EINVAL;
-  MdpIndent &h = c->indent;
-  if (!h.on) return mdp_fail(c, MDP_ESTATE, "mdp_indent_setup not called");
-  MDP_HIP(c, hipSetDevice(c->device));
-  if (c->md) MDP_TRY(mdp_md_flush_final(c)); // (the last kick of the run before, with the pass of its step if that is due)
-  indent_restart(h, first);
-  return MDP_OK;
-}
+int mdp_indent_run(mdp_ctx *c, long long first) { return c ? mdp_postforce_run(c, kStageIndent, first) : MDP_EINVAL; }
 
 int mdp_indent_state(mdp_ctx *c, int k, double *out)
 {
-  if (!c || !out) return MDP_EINVAL;
-  MdpIndent &h = c->indent;
-  if (!h.on) return mdp_fail(c, MDP_ESTATE, "mdp_indent_setup not called");
-  if (k < 0 || k >= h.n) return mdp_fail(c, MDP_EINVAL, "mdp_indent_state: indenter index %d out of range (%d indenters are on)", k, h.n);
-  MDP_HIP(c, hipSetDevice(c->device));
-  MDP_TRY(mdp_md_flush_final(c));
-  if (!h.applied) MDP_TRY(mdp_indent_pass(c)); // (the forces of a step no kick has consumed yet: step `first` before a run)
-  return mdp_read_one(c, h.st.p + k * kLen, sizeof(double) * kLen, out);
+  return c && out ? mdp_postforce_state(c, kStageIndent, k, kLen, out) : MDP_EINVAL;
 }
 
-int mdp_indent_off(mdp_ctx *c)
-{
-  if (!c) return MDP_EINVAL;
-  MdpIndent &h = c->indent;
-  // a deferred final half of the last step completes with its pass before the plain kicks take over
-  if (h.on && c->md) MDP_TRY(mdp_md_flush_final(c));
-  h.on = false;
-  h.st.release();
-  h.part.release();
-  return MDP_OK;
-}
+int mdp_indent_off(mdp_ctx *c) { return c ? mdp_postforce_off(c, kStageIndent) : MDP_EINVAL; }
 
 } // extern "C"

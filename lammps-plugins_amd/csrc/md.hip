@@ -655,8 +655,7 @@ template <int NB> int lgv_final(mdp_ctx *c, bool writeback)
 // plain.  lgv_writeback = false: the forces of a new run's setup come next, so f stays as the compute left it.
 int md_final_half(mdp_ctx *c, bool lgv_writeback = true)
 {
-  if (c->indent.on && !c->indent.applied) MDP_TRY(mdp_indent_pass(c)); // (indenters: post_force of the step this half completes)
-  if (c->spring.on && !c->spring.applied) MDP_TRY(mdp_spring_pass(c)); // (springs: the same, behind the indenters)
+  MDP_TRY(mdp_postforce_apply(c)); // (indenters, then springs: post_force of the step this half completes)
   if (c->nhc.on) return mdp_nhc_final(c);
   if (c->lgv.on) return c->lgv.many() ? lgv_final<MDP_LANGEVIN_MAXBATH>(c, lgv_writeback) : lgv_final<1>(c, lgv_writeback);
   bool masked = false;
@@ -726,8 +725,7 @@ int md_launch_kernel(mdp_ctx *c, bool with_final, int *flag, double trigsq, doub
 int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double hardsq, const MdpStyleCheck &sc,
                       bool zero_f, double *dset, double *dclr)
 {
-  if (c->indent.on && !c->indent.applied) MDP_TRY(mdp_indent_pass(c)); // (indenters: post_force of the forces this kernel kicks with first)
-  if (c->spring.on && !c->spring.applied) MDP_TRY(mdp_spring_pass(c)); // (springs: the same, behind the indenters)
+  MDP_TRY(mdp_postforce_apply(c)); // (indenters, then springs: post_force of the forces this kernel kicks with first)
   // a final half pending across a thermostat set-up (mdp_nhc_setup / _run, mdp_langevin_run by a host that does not
   // defer it) goes first, on its own, and leaves f as it was: the setup of the new run sees the compute's forces alone,
   // as after Verlet::setup
@@ -742,8 +740,7 @@ int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, dou
     with_final = false;
     mdp_heat_count_step(c);
   }
-  mdp_indent_count_step(c); // (the initial half below moves the atoms: a compute follows and overwrites f)
-  mdp_spring_count_step(c);
+  mdp_postforce_count_step(c); // (the initial half below moves the atoms: a compute follows and overwrites f)
   if (c->lgv.many()) return md_launch_kernel<MDP_LANGEVIN_MAXBATH>(c, with_final, flag, trigsq, hardsq, sc, zero_f, dset, dclr);
   return md_launch_kernel<1>(c, with_final, flag, trigsq, hardsq, sc, zero_f, dset, dclr);
 }

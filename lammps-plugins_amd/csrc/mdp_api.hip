@@ -914,12 +914,7 @@ int mdp_destroy(mdp_ctx *c)
   c->heat.st.release();
   c->heat.part.release();
   c->heat.count.release();
-  c->indent.st.release();
-  c->indent.part.release();
-  c->spring.st.release();
-  c->spring.part.release();
-  c->spring.cpart.release();
-  c->spring.count.release();
+  for (int s = 0; s < kStageCount; s++) mdp_postforce_release(c, s);
   c->fire.st.release();
   c->fire.part.release();
   c->fire.fsave.release();

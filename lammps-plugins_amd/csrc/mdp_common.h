@@ -366,39 +366,36 @@ struct MdpHeat {
 static constexpr int kHeatScale = 0, kHeatVcm = 1, kHeatKe = 4, kHeatM = 5, kHeatN = 6, kHeatErrStep = 7, kHeatS = 8, kHeatVsub = 9,
                      kHeatWords = 12, kHeatErr = MDP_HEAT_MAXSRC * kHeatWords, kHeatTotal = kHeatErr + 2;
 static constexpr int kHeatW = 5 * MDP_HEAT_MAXSRC; // per source: sum m v.v, m vx, m vy, m vz, m
-// Indenters (indent.hip): LAMMPS fix indent with a constant velocity, added into f by one pass in front of the kick that
-// first consumes a compute's forces.  The host keeps the configuration, the number of initial halves since mdp_indent_run
-// and whether the current forces have had their pass; the sums live on the device.  st: indenter k keeps its
-// MDP_INDENT_STATE_LEN state words (mdp_indent_state layout) at st + k * MDP_INDENT_STATE_LEN
-struct MdpIndent {
+// Post-force stages: the device fixes that add a force in front of every kick that first consumes a compute's forces
+// (the indenters, then the tether springs: kMdpStages below, postforce.hip).  The host keeps the configuration, the number
+// of initial halves since the stage's _run and whether the current forces have had the stage's pass; the sums live on the
+// device.  What every stage keeps:
+static constexpr int kStageSlots = 4; // indenters, springs of one context
+static_assert(MDP_INDENT_MAX == kStageSlots && MDP_SPRING_MAX == kStageSlots, "a stage has four slots");
+struct MdpPostForce {
   bool on = false;
-  bool applied = false;     // the forces the context holds have had their pass.  Cleared behind every initial half
-                            // (mdp_indent_count_step) and by mdp_indent_setup / _run (indent_restart), nowhere else
-  int n = 0;
-  mdp_indent_config cfg[MDP_INDENT_MAX];
-  int bit[MDP_INDENT_MAX] = {0, 0, 0, 0};
-  long long first = 0;      // the step of mdp_indent_run
+  bool applied = false;     // the forces the context holds have had this stage's pass.  Set by mdp_postforce_apply, cleared
+                            // behind every initial half (mdp_postforce_count_step) and by the stage's _setup / _run
+                            // (mdp_postforce_restart), nowhere else
+  int n = 0;                // slots that are on
+  int bit[kStageSlots] = {0, 0, 0, 0}; // their group bits (0: every owned atom)
+  long long first = 0;      // the step of the stage's _run
   long long nhalf = 0;      // initial halves since: the current forces are those of step first + nhalf
-  DevBuf<double> st;        // [MDP_INDENT_MAX * MDP_INDENT_STATE_LEN]
-  DevBuf<double> part;      // per-block partial sums, kIndW per block (fixed slots [block][indenter][5])
+  DevBuf<double> st;        // the state words of every slot (the stage's _state layout)
+  DevBuf<double> part;      // per-block partial sums (fixed slots [block][slot][5])
+};
+// Indenters (indent.hip): LAMMPS fix indent with a constant velocity, added into f by the stage's pass.  st: indenter k
+// keeps its MDP_INDENT_STATE_LEN state words (mdp_indent_state layout) at st + k * MDP_INDENT_STATE_LEN; part: kIndW per block
+struct MdpIndent : MdpPostForce {
+  mdp_indent_config cfg[MDP_INDENT_MAX];
 };
 static constexpr int kIndW = 5 * MDP_INDENT_MAX; // per indenter: energy, the atoms' fx, fy, fz, atoms in contact
-// Tether springs (spring.hip): LAMMPS fix spring tether with a tether point at constant velocity, taken off f by one pass in
-// front of the kick that first consumes a compute's forces, behind the indenters' pass.  The host keeps the configuration,
-// the number of initial halves since mdp_spring_run and whether the current forces have had their pass; the sums live on
-// the device.  st: spring k keeps its MDP_SPRING_STATE_LEN state words (mdp_spring_state layout) at st + k *
-// MDP_SPRING_STATE_LEN; behind the springs, F / M of the pass in flight (kSprF + 4 k: x, y, z and a spare word)
-struct MdpSpring {
-  bool on = false;
-  bool applied = false;     // the forces the context holds have had their pass.  Cleared behind every initial half
-                            // (mdp_spring_count_step) and by mdp_spring_setup / _run (spring_restart), nowhere else
-  int n = 0;
+// Tether springs (spring.hip): LAMMPS fix spring tether with a tether point at constant velocity, taken off f by the
+// stage's pass, behind the indenters'.  st ([kSprTotal]): spring k keeps its MDP_SPRING_STATE_LEN state words
+// (mdp_spring_state layout) at st + k * MDP_SPRING_STATE_LEN; behind the springs, F / M of the pass in flight (kSprF + 4 k:
+// x, y, z and a spare word); part: kSprW per block
+struct MdpSpring : MdpPostForce {
   mdp_spring_config cfg[MDP_SPRING_MAX];
-  int bit[MDP_SPRING_MAX] = {0, 0, 0, 0};
-  long long first = 0;      // the step of mdp_spring_run
-  long long nhalf = 0;      // initial halves since: the current forces are those of step first + nhalf
-  DevBuf<double> st;        // [kSprTotal]
-  DevBuf<double> part;      // per-block partial sums, kSprW per block (fixed slots [block][spring][5])
   DevBuf<int> cpart;        // per-block atom counts, MDP_SPRING_MAX per block
   DevBuf<int> count;        // [2 MDP_SPRING_MAX] the counts of a set-up: atoms per spring, those with a mass
 };
@@ -1167,24 +1164,84 @@ inline void mdp_heat_count_step(mdp_ctx *c)
 }
 int mdp_heat_mask(mdp_ctx *c, const char *who);
 int mdp_heat_check(mdp_ctx *c);
-// indenters (indent.hip) when c->indent.on.  _pass: the force pass and the control workgroup for the forces the context
-// holds, which are those of step first + nhalf; sets `applied`.  md_final_half and md_launch_advance (md.hip) call it
-// first thing unless `applied`.  _count_step: behind an initial half -- the atoms have moved, a compute follows
+// The post-force stages of a context, in the order their passes run (the order only affects the rounding of f).  base: the
+// stage's MdpPostForce; pass: its kernels for the forces the context holds, which are those of step first + nhalf
+// (indent.hip, spring.hip); api, many, one: the nouns of its messages.  The rule they share stands here and in
+// postforce.hip alone: a pass runs exactly once for the forces the context holds, in front of the kick that first consumes
+// them or of a state read, and a stage's pass never runs before the passes of the stages in front of it that are due.
 int mdp_indent_pass(mdp_ctx *c);
-inline void mdp_indent_count_step(mdp_ctx *c)
-{
-  if (!c->indent.on) return;
-  c->indent.nhalf++;
-  c->indent.applied = false;
-}
-// tether springs (spring.hip) when c->spring.on, under the rules of the indenters: _pass at the same two sites, behind
-// the indenters' pass when both are on (the order only affects the rounding of f); _count_step behind an initial half
 int mdp_spring_pass(mdp_ctx *c);
-inline void mdp_spring_count_step(mdp_ctx *c)
+enum MdpStageId { kStageIndent = 0, kStageSpring, kStageCount };
+struct MdpStage {
+  MdpPostForce &(*base)(mdp_ctx *);
+  int (*pass)(mdp_ctx *);
+  const char *api, *many, *one;
+};
+inline constexpr MdpStage kMdpStages[kStageCount] = {
+    {[](mdp_ctx *c) -> MdpPostForce & { return c->indent; }, mdp_indent_pass, "mdp_indent", "indenters", "indenter"},
+    {[](mdp_ctx *c) -> MdpPostForce & { return c->spring; }, mdp_spring_pass, "mdp_spring", "springs", "spring"},
+};
+// brings the forces the context holds up to date through stage `through`: the passes that are on and not `applied`, in
+// list order.  md_final_half and md_launch_advance (md.hip) call it first thing, for all stages
+inline int mdp_postforce_apply(mdp_ctx *c, int through = kStageCount - 1)
 {
-  if (!c->spring.on) return;
-  c->spring.nhalf++;
-  c->spring.applied = false;
+  for (int s = 0; s <= through; s++) {
+    MdpPostForce &h = kMdpStages[s].base(c);
+    if (!h.on || h.applied) continue;
+    MDP_TRY(kMdpStages[s].pass(c));
+    h.applied = true;
+  }
+  return MDP_OK;
+}
+// behind an initial half: the atoms have moved, a compute follows and overwrites f
+inline void mdp_postforce_count_step(mdp_ctx *c)
+{
+  for (const MdpStage &s : kMdpStages) {
+    MdpPostForce &h = s.base(c);
+    if (!h.on) continue;
+    h.nhalf++;
+    h.applied = false;
+  }
+}
+// the life cycle the stages share (postforce.hip); the four entry points of a kind bring their own argument checks.
+// _refuse_setup: what no stage's _setup goes with.  _commit: behind the last refusal of a _setup -- completes a deferred
+// final half with the stage off, zeroes st (`words` doubles), stores n, the bits and the n configurations (cfg_bytes each)
+// and restarts the stage at step 0, on.  _run, _state, _off: the entry points of those names behind their null checks.
+// _release: frees what stage s holds (_off, mdp_destroy).  mdp_refuse_if_on: the first stage that is on refuses `who`
+enum MdpRefuse { kRefuseOffFirst, kRefuseOneRank };
+int mdp_postforce_refuse_setup(mdp_ctx *c, int s);
+int mdp_postforce_commit(mdp_ctx *c, int s, int words, int n, const int *groupbit, void *cfg_dst, const void *cfg, size_t cfg_bytes);
+int mdp_postforce_run(mdp_ctx *c, int s, long long first);
+int mdp_postforce_state(mdp_ctx *c, int s, int k, int len, double *out);
+int mdp_postforce_off(mdp_ctx *c, int s);
+void mdp_postforce_release(mdp_ctx *c, int s);
+int mdp_refuse_if_on(mdp_ctx *c, const char *who, MdpRefuse how);
+// groups: whether the mask covers the current atoms, and the mask in the host's order (host mode) for a kernel that reads
+// it through mdp_group_mask alone (no group bits)
+inline bool mdp_mask_current(const mdp_ctx *c) { return c->mask_set && c->mask_n == c->nlocal; }
+inline MdpGroupArgs mdp_mask_args(const mdp_ctx *c)
+{
+  MdpGroupArgs M;
+  M.mask = c->mask.p;
+  M.perm = !c->md && c->host_sort ? c->host_perm.p : nullptr; // host mode: the mask is in the host's order
+  return M;
+}
+// the group bits of the n slots that are on (a bit of 0: every owned atom; a slot beyond n is never looked at) and
+// whether any is set: the mask is read.  Bits: MdpSlotBits, or a kernel's own argument type derived from it
+struct MdpSlotBits {
+  int n = 0;
+  int bit[kStageSlots] = {0, 0, 0, 0};
+  int any = 0;
+};
+template <class Bits = MdpSlotBits> Bits mdp_slot_bits(int n, const int *bit)
+{
+  Bits B;
+  B.n = n;
+  for (int k = 0; k < n; k++) {
+    B.bit[k] = bit[k];
+    B.any |= bit[k];
+  }
+  return B;
 }
 void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
 void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds

@@ -255,8 +255,7 @@ int mdp_nhc_setup(mdp_ctx *c, const mdp_nhc_config *cfg)
     return mdp_fail(c, MDP_ESTATE, "mdp_nhc_setup: the Langevin thermostat (mdp_langevin_setup) is on; one thermostat per context");
   if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_nhc_setup: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
   if (c->heat.on) return mdp_fail(c, MDP_ESTATE, "mdp_nhc_setup: heat sources (mdp_heat_setup) are on; mdp_heat_off first");
-  if (c->indent.on) return mdp_fail(c, MDP_ESTATE, "mdp_nhc_setup: indenters (mdp_indent_setup) are on; mdp_indent_off first");
-  if (c->spring.on) return mdp_fail(c, MDP_ESTATE, "mdp_nhc_setup: springs (mdp_spring_setup) are on; mdp_spring_off first");
+  MDP_TRY(mdp_refuse_if_on(c, "mdp_nhc_setup", kRefuseOffFirst));
   if (c->dd.on && c->dd.G.nranks > 1)
     return mdp_fail(c, MDP_ESTATE, "mdp_nhc_setup: the thermostat runs on one rank only (this context is a brick of %d ranks)",
                     c->dd.G.nranks);

@@ -7,9 +7,9 @@
 // in three launches: per block and spring sum m xu, sum m (in two exact parts) and the atom count in fixed slots
 // (spring_sums_kernel); one workgroup that adds the slots in a fixed order and leaves the state words and F / M of every
 // spring in device memory (spring_control_kernel); one lane per owned atom that takes (F / M) m off its f, spring after
-// spring (spring_apply_kernel).  No float atomics and no host wait: a run is bitwise reproducible.  md.hip calls mdp_spring_pass
-// at the top of md_final_half and md_launch_advance, behind the indenters' pass, unless the current forces have had
-// their pass (MdpSpring::applied).
+// spring (spring_apply_kernel).  No float atomics and no host wait: a run is bitwise reproducible.  The springs are the
+// second post-force stage of a context, behind the indenters (kMdpStages, mdp_common.h): mdp_postforce_apply calls
+// mdp_spring_pass, and postforce.hip holds the life cycle they share with the indenters.
 #include "mdp_common.h"
 
 #include <cmath>
@@ -19,12 +19,8 @@ namespace {
 constexpr int kN = MDP_SPRING_MAX;
 constexpr int kLen = MDP_SPRING_STATE_LEN;
 
-// the group bits of the springs that are on (a bit of 0: every owned atom); a slot beyond n is never looked at
-struct SpringBits {
-  int n = 0;
-  int bit[kN] = {0, 0, 0, 0};
-  int any = 0; // some spring acts on a group: the mask is read
-};
+// the group bits of the springs that are on, under the name the kernels take them by
+struct SpringBits : MdpSlotBits {};
 
 // part[kSprW b + 5 k + j]: the sums over block b of m xu, m yu, m zu, m_hi and m_lo of spring k's atoms; cnt[kN b + k]: their
 // number.  m = m_hi + m_lo with m_hi the multiple of 2^-20 nearest m: for up to 2^22 atoms with masses in [1, 2048) both
@@ -188,34 +184,13 @@ __global__ void spring_count_kernel(const int n, const int *__restrict__ mask, c
     }
 }
 
-SpringBits spring_bits(int n, const int *bit)
-{
-  SpringBits B;
-  B.n = n;
-  for (int k = 0; k < n; k++) {
-    B.bit[k] = bit[k];
-    B.any |= bit[k];
-  }
-  return B;
-}
-
-bool spring_mask_current(const mdp_ctx *c) { return c->mask_set && c->mask_n == c->nlocal; }
-
-// mdp_spring_setup / _run: the forces the context holds are taken to be the pair style's alone, those of step `first`
-void spring_restart(MdpSpring &h, long long first)
-{
-  h.first = first;
-  h.nhalf = 0;
-  h.applied = false;
-}
-
 } // namespace
 
 int mdp_spring_pass(mdp_ctx *c)
 {
   MdpSpring &h = c->spring;
-  const SpringBits B = spring_bits(h.n, h.bit);
-  if (B.any && !spring_mask_current(c))
+  const SpringBits B = mdp_slot_bits<SpringBits>(h.n, h.bit);
+  if (B.any && !mdp_mask_current(c))
     return mdp_fail(c, MDP_ESTATE, "integrate: a spring acts on a group but no mask covers the current atoms (mdp_md_set_mask)");
   if (!c->dd.on) return mdp_fail(c, MDP_ESTATE, "springs are on (mdp_spring_setup) but the context has no box any more");
   if (!c->image_set) return mdp_fail(c, MDP_ESTATE, "springs are on (mdp_spring_setup) but the image flags were withdrawn (mdp_md_set_image)");
@@ -240,7 +215,6 @@ int mdp_spring_pass(mdp_ctx *c)
   spring_control_kernel<<<1, 256, 0, c->stream>>>(h.part.p, h.cpart.p, nbs, a, h.st.p);
   if (n) spring_apply_kernel<<<nb, 256, 0, c->stream>>>(n, c->f.p, c->rmass.p, c->mask.p, B, h.st.p);
   MDP_HIP(c, hipGetLastError());
-  h.applied = true;
   return MDP_OK;
 }
 
@@ -260,17 +234,13 @@ int mdp_spring_setup(mdp_ctx *c, int n, const mdp_spring_config *cfg, const int 
     if (!q.use[0] && !q.use[1] && !q.use[2])
       return mdp_fail(c, MDP_EINVAL, "mdp_spring_setup: spring %d: no dimension takes part (use is all zero)", k);
   }
-  if (c->fire.on) return mdp_fail(c, MDP_ESTATE, "mdp_spring_setup: a minimisation (mdp_fire_setup) is on; mdp_fire_off first");
-  if (c->nhc.on) return mdp_fail(c, MDP_ESTATE, "mdp_spring_setup: the Nose-Hoover chain (mdp_nhc_setup) is on; springs run under NVE and Langevin baths");
-  if (c->heat.on) return mdp_fail(c, MDP_ESTATE, "mdp_spring_setup: heat sources (mdp_heat_setup) are on; mdp_heat_off first");
-  if (c->dd.on && c->dd.G.nranks > 1)
-    return mdp_fail(c, MDP_ESTATE, "mdp_spring_setup: springs run on one rank only (this context is a brick of %d ranks)", c->dd.G.nranks);
+  MDP_TRY(mdp_postforce_refuse_setup(c, kStageSpring));
   if (!c->md)
     return mdp_fail(c, MDP_ESTATE, "mdp_spring_setup: springs need a resident context (mdp_md_setup): on a host-linked one the host keeps the image flags");
   if (!c->dd.on) return mdp_fail(c, MDP_ESTATE, "mdp_spring_setup: mdp_dd_setup not called (the unwrapped positions need the box of the brick)");
   if (!c->image_set) return mdp_fail(c, MDP_ESTATE, "mdp_spring_setup: no image set (mdp_md_set_image)");
-  const SpringBits B = spring_bits(n, groupbit);
-  if (B.any && !spring_mask_current(c))
+  const SpringBits B = mdp_slot_bits<SpringBits>(n, groupbit);
+  if (B.any && !mdp_mask_current(c))
     return mdp_fail(c, MDP_ESTATE, "mdp_spring_setup: a spring acts on a group but no mask covers the current atoms (mdp_md_set_mask)");
   MDP_HIP(c, hipSetDevice(c->device));
   MdpSpring &h = c->spring;
@@ -290,66 +260,16 @@ int mdp_spring_setup(mdp_ctx *c, int n, const mdp_spring_config *cfg, const int 
     }
   }
   // (everything that can be refused has been: springs that were on stay on, as they were, after a refusal above)
-  { // a final half the host deferred belongs to the run before: it completes now, without springs
-    const bool was_on = h.on;
-    h.on = false;
-    const int rc = mdp_md_flush_final(c);
-    if (rc != MDP_OK) {
-      h.on = was_on;
-      return rc;
-    }
-  }
-  MDP_HIP(c, h.st.reserve(kSprTotal));
-  const double st[kSprTotal] = {};
-  MDP_TRY(mdp_write_small(c, h.st.p, st, sizeof st));
-  h.n = n;
-  for (int k = 0; k < kN; k++) {
-    h.bit[k] = k < n ? groupbit[k] : 0;
-    if (k < n) h.cfg[k] = cfg[k];
-  }
-  spring_restart(h, 0);
-  h.on = true;
-  return MDP_OK;
+  return mdp_postforce_commit(c, kStageSpring, kSprTotal, n, groupbit, h.cfg, cfg, sizeof *cfg);
 }
 
-int mdp_spring_run(mdp_ctx *c, long long first)
-{
-  if (!c) return MDP_EINVAL;
-  MdpSpring &h = c->spring;
-  if (!h.on) return mdp_fail(c, MDP_ESTATE, "mdp_spring_setup not called");
-  MDP_HIP(c, hipSetDevice(c->device));
-  MDP_TRY(mdp_md_flush_final(c)); // (the last kick of the run before, with the pass of its step if that is due)
-  spring_restart(h, first);
-  return MDP_OK;
-}
+int mdp_spring_run(mdp_ctx *c, long long first) { return c ? mdp_postforce_run(c, kStageSpring, first) : MDP_EINVAL; }
 
 int mdp_spring_state(mdp_ctx *c, int k, double *out)
 {
-  if (!c || !out) return MDP_EINVAL;
-  MdpSpring &h = c->spring;
-  if (!h.on) return mdp_fail(c, MDP_ESTATE, "mdp_spring_setup not called");
-  if (k < 0 || k >= h.n) return mdp_fail(c, MDP_EINVAL, "mdp_spring_state: spring index %d out of range (%d springs are on)", k, h.n);
-  MDP_HIP(c, hipSetDevice(c->device));
-  MDP_TRY(mdp_md_flush_final(c));
-  if (!h.applied) { // (the forces of a step no kick has consumed yet: step `first` before a run)
-    if (c->indent.on && !c->indent.applied) MDP_TRY(mdp_indent_pass(c)); // (the indenters' pass goes first, as in front of a kick)
-    MDP_TRY(mdp_spring_pass(c));
-  }
-  return mdp_read_one(c, h.st.p + k * kLen, sizeof(double) * kLen, out);
+  return c && out ? mdp_postforce_state(c, kStageSpring, k, kLen, out) : MDP_EINVAL;
 }
 
-int mdp_spring_off(mdp_ctx *c)
-{
-  if (!c) return MDP_EINVAL;
-  MdpSpring &h = c->spring;
-  // a deferred final half of the last step completes with its pass before the plain kicks take over
-  if (h.on && c->md) MDP_TRY(mdp_md_flush_final(c));
-  h.on = false;
-  h.st.release();
-  h.part.release();
-  h.cpart.release();
-  h.count.release();
-  return MDP_OK;
-}
+int mdp_spring_off(mdp_ctx *c) { return c ? mdp_postforce_off(c, kStageSpring) : MDP_EINVAL; }
 
 } // extern "C"

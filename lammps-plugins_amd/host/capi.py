@@ -175,6 +175,11 @@ def _ip(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
 
 
+def _slots(config, n):
+    """the arguments of a set-up that takes n slots: their configurations and group bits (never of length 0)"""
+    return (config * max(n, 1))(), (C.c_int * max(n, 1))()
+
+
 def comm_library():
     """(name of the RCCL object the library binds, True when it is the test double of tests/native)"""
     buf = C.create_string_buffer(256)
@@ -614,8 +619,7 @@ class Context:
     def heat_setup(self, sources, mvv2e=1.0364269e-4):
         """mdp_heat_setup: sources is a list of dicts eflux (energy / time, either sign), nevery, bit (the source's group bit)"""
         n = len(sources)
-        cfgs = (HeatConfig * max(n, 1))()
-        bits = (C.c_int * max(n, 1))()
+        cfgs, bits = _slots(HeatConfig, n)
         for k, s in enumerate(sources):
             cfgs[k].eflux, cfgs[k].nevery, cfgs[k].mvv2e = float(s["eflux"]), int(s["nevery"]), float(s.get("mvv2e", mvv2e))
             bits[k] = int(s["bit"])
@@ -642,8 +646,7 @@ class Context:
         axis, the plane's normal), side ("out" / "in", "lo" / "hi" or 0 / 1), vel (three numbers), bit (the group bit; 0:
         every owned atom)"""
         n = len(indenters)
-        cfgs = (IndentConfig * max(n, 1))()
-        bits = (C.c_int * max(n, 1))()
+        cfgs, bits = _slots(IndentConfig, n)
         for k, q in enumerate(indenters):
             cfgs[k].shape = INDENT_SHAPES.get(q["shape"], q["shape"])
             cfgs[k].dim = int(q.get("dim", 0))
@@ -674,8 +677,7 @@ class Context:
         three entries, None for a dimension that takes no part, LAMMPS' NULL), and optionally vel (three numbers), bit (the
         group bit; 0: every owned atom)"""
         n = len(springs)
-        cfgs = (SpringConfig * max(n, 1))()
-        bits = (C.c_int * max(n, 1))()
+        cfgs, bits = _slots(SpringConfig, n)
         for k, q in enumerate(springs):
             cfgs[k].k, cfgs[k].r0 = float(q["k"]), float(q.get("r0", 0.0))
             cfgs[k].c[:] = [0.0 if a is None else float(a) for a in q["c"]]

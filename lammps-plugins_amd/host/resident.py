@@ -742,14 +742,22 @@ class DeviceDomain:
         self.flush()
         return self.ctx.langevin_tally(bath)
 
+    def _one_gpu(self, what):
+        if self.world > 1:
+            raise ValueError(f"{what} run on one GPU only (their sums would need an all-reduce per step)")
+
+    def _run_from(self, kind, first):
+        """mdp_<kind>_run: a pending final half completes inside the call"""
+        getattr(self.ctx, kind + "_run")(first)
+        self._final_pending = False
+
     def heat(self, sources, first=0):
         """Constant-flux heat sources (LAMMPS fix heat) behind the final halves of this domain: sources is a list of up to
         four dicts eflux (energy / time; negative: a sink), nevery, bit -- the source's group bit in the mask of set_group.
         Source k's atoms gain eflux nevery dt of kinetic energy about their centre of mass every nevery steps and keep
         their momentum.  The groups must be disjoint and inside the integrate group; one GPU, no thermostat.  first: the
         step the run that follows starts from (it is never heated itself).  A pending final half completes first."""
-        if self.world > 1:
-            raise ValueError("heat sources run on one GPU only (their sums would need an all-reduce per step)")
+        self._one_gpu("heat sources")
         self.ctx.heat_setup(sources, mvv2e=S.MVV2E)
         self.heat_run(first)
 
@@ -757,8 +765,7 @@ class DeviceDomain:
         """A further run of the sources set by heat(), from step `first` (LAMMPS' second `run`): the phase of
         step % nevery starts over and step `first` itself is not heated again.  A pending final half completes first,
         WITHOUT the sources -- a host that wants the last step of the run before heated completes it first (flush)."""
-        self.ctx.heat_run(first)
-        self._final_pending = False
+        self._run_from("heat", first)
 
     def heat_state(self, src):
         """source src after the last full step (completes a deferred final half first): capi.Context.heat_state"""
@@ -776,16 +783,14 @@ class DeviceDomain:
         mask of set_group; 0: every atom).  The centre is c at step `first` and moves by vel dt per step.  The forces the
         domain holds at the call are taken to be the pair style's alone (call it behind compute(), as a fix's setup runs
         behind Verlet::setup).  One GPU; no Nose-Hoover chain, heat sources or minimiser next to them."""
-        if self.world > 1:
-            raise ValueError("indenters run on one GPU only (their sums would need an all-reduce per step)")
+        self._one_gpu("indenters")
         self.ctx.indent_setup(indenters)
         self.indent_run(first)
 
     def indent_run(self, first):
         """A further run of the indenters set by indent(), from step `first`: the centres start again at c.  A pending
         final half completes first, with its indenter forces; compute() again before the next step."""
-        self.ctx.indent_run(first)
-        self._final_pending = False
+        self._run_from("indent", first)
 
     def indent_state(self, k):
         """indenter k for the current forces (completes a deferred final half first): capi.Context.indent_state"""
@@ -804,16 +809,14 @@ class DeviceDomain:
         vel dt per step.  The centre of mass is that of the unwrapped positions: the domain needs its image flags
         (track_images).  Call it behind compute(), as indent().  One GPU; no Nose-Hoover chain, heat sources or minimiser next
         to them; indenters and Langevin baths are welcome."""
-        if self.world > 1:
-            raise ValueError("springs run on one GPU only (their sums would need an all-reduce per step)")
+        self._one_gpu("springs")
         self.ctx.spring_setup(springs)
         self.spring_run(first)
 
     def spring_run(self, first):
         """A further run of the springs set by spring(), from step `first`: the tether points start again at c.  A pending
         final half completes first, with its spring forces; compute() again before the next step."""
-        self.ctx.spring_run(first)
-        self._final_pending = False
+        self._run_from("spring", first)
 
     def spring_state(self, k):
         """spring k for the current forces (completes a deferred final half first): capi.Context.spring_state"""

@@ -25,7 +25,7 @@ from lammps_plugins_amd.host import capi, resident, system as S
 from firerig import BIG
 from refloops import worse
 from test_gpu_heat_mdp import _system, _oracle_engine, _context, _by_tag
-from test_gpu_indent_mdp import STATIC as INDENT_STATIC
+from test_gpu_indent_mdp import STATIC as INDENT_STATIC, MOVING as INDENT_MOVING
 import bathsref
 import indentref
 import langevinref
@@ -404,6 +404,63 @@ def test_a_spring_next_to_an_indenter(oracle, capsys):
     dev, _ = _resident(style, springs, inds=inds)
     with capsys.disabled():
         _compare(style, host, dev, "static tether next to a spherical indenter, aeam")
+
+
+def _read_both(defer, indenter_first):
+    """the run of test_a_spring_next_to_an_indenter on the MoS2 cell, whose forces are added in a fixed order (the alloy's
+    runs agree to rounding only), with a static and a moving sphere, and both kinds' states read at the setup and at every
+    read, the indenters' before the spring's or behind it: {step: (x, v, [indenter states], [spring state])}, step 0
+    without x and v"""
+    style, springs = _springs("static-rebomos")
+    inds = [INDENT_STATIC[style], INDENT_MOVING[style]]
+    s, v0, by_tag, g, x_in, img = _case(style)
+    ctx, st, cutghost, skin, map_ = _context(style)
+
+    def states(d):
+        if indenter_first:
+            i = [d.indent_state(k) for k in range(len(inds))]
+            return i, _dstate(d, 1)
+        p = _dstate(d, 1)
+        return [d.indent_state(k) for k in range(len(inds))], p
+
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        d.set_group(by_tag, GBIT)
+        d.track_images(resident.image_pack(img))
+        d.compute(1, 0)
+        d.indent(inds)
+        d.spring(springs)
+        out = {0: (None, None) + states(d)}
+        for step in range(1, NSTEPS + 1):
+            d.step(0, 0, rebuild="auto", defer_final=defer == "all")
+            if step in EVERY20:
+                i, p = states(d)
+                d.flush()
+                x, v = _by_tag(ctx, d, s)
+                out[step] = (x, v, i, p)
+        return out
+    finally:
+        ctx.close()
+
+
+@gpu
+@pytest.mark.parametrize("defer", ["all", "none"])
+def test_the_order_of_the_state_reads_of_a_spring_and_an_indenter_changes_nothing(defer):
+    """a pass runs once for the forces the context holds, the indenters' first, whichever state is asked for first and
+    whether the read finds the final half deferred (it completes it, passes included) or done: positions, velocities and
+    every state word bit for bit, and `passes` of both kinds = the computes whose forces were consumed or read, the
+    setup's and one per step"""
+    a, b = _read_both(defer, True), _read_both(defer, False)
+    for step in (0,) + EVERY20:
+        for what, p, q in zip(("x", "v"), a[step][:2], b[step][:2]):
+            assert step == 0 or np.array_equal(p, q), (defer, step, what)
+        for kind, p, q in [(kind, p, q) for kind, ps, qs in zip(("indenter", "spring"), a[step][2:], b[step][2:]) for p, q in zip(ps, qs)]:
+            assert p.keys() == q.keys()
+            for w in p:
+                assert np.array_equal(p[w], q[w]), (defer, step, kind, w, p[w], q[w])
+            assert p["passes"] == step + 1 and p["step"] == step, (defer, step, kind, p["passes"], p["step"])
+        assert len(a[step][2]) == len(b[step][2]) == 2 and len(a[step][3]) == len(b[step][3]) == 1
+    assert sum(q["contacts"] for q in a[NSTEPS][2]) >= 1 and a[NSTEPS][3][0]["ftotal"][3] != 0.0        # (both kinds push)
 
 
 _PLAIN = []
