@@ -855,6 +855,47 @@ int mdp_adf_counts(mdp_ctx *ctx, long long *hist, long long *icount);
 int mdp_adf_info(mdp_ctx *ctx, long long out[4]);
 int mdp_adf_off(mdp_ctx *ctx);
 
+/* ---- per-atom structure: coordination numbers and the centro-symmetry parameter (LAMMPS compute coord/atom cutoff and
+ * compute centro/atom without axes) ----------------------------------------------------------------------------------------
+ * For a resident context with mdp_dd_setup (MDP_ESTATE otherwise), one measurement of each kind next to the others.  Nothing of
+ * a run is changed by a read: the binning is the measurement's own (the stage of mdp_rdf_counts, without a member table:
+ * partners of any group count).  A centre is an owned atom with mask & groupbit (mdp_md_set_mask; groupbit 0: every owned
+ * atom); a partner is any other array entry, owned or ghost (a periodic image is a separate entry, the centre's own included),
+ * with rsq = dx^2 + dy^2 + dz^2 < cutoff^2 in double from the current positions.
+ *   mdp_coord_setup:   ncol columns (1 .. MDP_COORD_MAXCOL: a partner's columns are one mask word); column m counts the
+ *                      partners whose type lies in jlo[m] .. jhi[m] (LAMMPS types 1 .. ntypes, inclusive).  A second call
+ *                      replaces the first.  MDP_EINVAL: ncol outside 1 .. MDP_COORD_MAXCOL, a type outside 1 .. ntypes,
+ *                      lo > hi, cutoff <= 0, cutoff + skin > the cutghost of mdp_dd_setup (see mdp_rdf_setup).
+ *   mdp_coord_read:    blocking.  tag[i] and values[i][0 .. ncol) of this rank's nlocal owned atoms in the context's owned
+ *                      order (that of mdp_md_download): the counts as doubles, 0 in every column for an atom outside the
+ *                      group.  Integer counts: two reads of one state agree exactly.  MDP_ESTATE without a setup, or with a
+ *                      group bit and no mask that covers the current atoms; MDP_EINVAL if the cutoff has outgrown the shell.
+ *   mdp_coord_info:    out = {a measurement is on, its ncol, its groupbit, its serial}; the serial as that of mdp_rdf_info.
+ *   mdp_centro_setup:  nnn even, 2 .. MDP_CENTRO_MAXN (12 for fcc, 8 for bcc); cutoff <= 0 stands for the ghost shell's limit,
+ *                      cutghost - skin, as it is at the setup.  MDP_EINVAL: nnn odd or outside the range, cutoff beyond the
+ *                      limit.  A second call replaces the first.
+ *   mdp_centro_read:   blocking.  tag[i] and values[i] as above.  Of the partners of a centre the nnn nearest are taken --
+ *                      ordered by (rsq, place in the binning's cell order), so equal distances never depend on timing --,
+ *                      the nnn (nnn - 1) / 2 values |R_a + R_b|^2 are formed, and the nnn / 2 smallest (ordered by value,
+ *                      then pair index) are added in ascending order.  A centre with fewer than nnn partners gets 0, as
+ *                      in LAMMPS.  No atomics on doubles: two reads of one state agree bit for bit.  MDP_EINVAL if a centre
+ *                      has more than MDP_ADF_MAXNEIGH partners inside the cutoff (the short list a wave keeps in LDS): the
+ *                      message names their number and asks for a smaller cutoff; no values are handed back and no centre is
+ *                      ever truncated.  The context stays usable.  The other refusals as those of mdp_coord_read.
+ *   mdp_centro_info:   out = {a measurement is on, its nnn, the centres with fewer than nnn partners at the last read, its
+ *                      serial}.
+ *   mdp_*_off:         releases the buffers. */
+#define MDP_COORD_MAXCOL 32
+#define MDP_CENTRO_MAXN 64
+int mdp_coord_setup(mdp_ctx *ctx, double cutoff, int ncol, const int *jlo, const int *jhi, int groupbit);
+int mdp_coord_read(mdp_ctx *ctx, int *tag /* [nlocal] */, double *values /* [nlocal][ncol] */);
+int mdp_coord_info(mdp_ctx *ctx, long long out[4]);
+int mdp_coord_off(mdp_ctx *ctx);
+int mdp_centro_setup(mdp_ctx *ctx, int nnn, double cutoff, int groupbit);
+int mdp_centro_read(mdp_ctx *ctx, int *tag /* [nlocal] */, double *values /* [nlocal] */);
+int mdp_centro_info(mdp_ctx *ctx, long long out[4]);
+int mdp_centro_off(mdp_ctx *ctx);
+
 /* ---- binned mass, momentum and kinetic energy: temperature, density and flow profiles (LAMMPS compute chunk/atom bin/1d|2d|3d
  * with compute temp/chunk, vcm/chunk, fix ave/chunk), in integers ----------------------------------------------------------
  * For a resident context with mdp_dd_setup (MDP_ESTATE otherwise).  Nothing a step, a list build, msd or rdf reads is touched.

@@ -491,6 +491,23 @@ struct MdpAdf : MdpMeasure {
   MdpBinning bin;
   DevBuf<unsigned long long> out;  // [ntriple][nbin] histogram, icount [MDP_ADF_MAXTRIPLE], the centres over the cap, the bad tags
 };
+// per-atom coordination numbers (coord.hip): the binning of a read and the rows it writes, one per owned atom
+struct MdpCoord : MdpMeasure {
+  int ncol = 0, ntypes = 0, gbit = 0;
+  double cutoff = 0.0;
+  DevBuf<unsigned> tab;            // [kBinTypes] per type code the columns whose range holds it
+  MdpBinning bin;
+  DevBuf<double> val;              // [nlocal][ncol] in the context's owned order
+};
+// the per-atom centro-symmetry parameter (centro.hip): the same, with the counters of a read
+struct MdpCentro : MdpMeasure {
+  int nnn = 0, ntypes = 0, gbit = 0;
+  long long few = 0;               // centres with fewer than nnn partners at the last read
+  double cutoff = 0.0;
+  MdpBinning bin;
+  DevBuf<double> val;              // [nlocal]
+  DevBuf<unsigned long long> cnt;  // centres over the cap of the short list, centres with fewer than nnn partners, (unused) bad tags
+};
 // binned sums of m, m v and m v^2 (profile.hip): the bins and the table of a read; nothing here is read by a step, a list build,
 // msd or rdf
 struct MdpProfile : MdpMeasure {
@@ -911,6 +928,8 @@ struct mdp_ctx {
   MdpMsd msd;
   MdpRdf rdf;                      // pair-distance histograms of the current positions (mdp_rdf_setup)
   MdpAdf adf;                      // bond-angle histograms of the current positions (mdp_adf_setup)
+  MdpCoord coord;                  // per-atom coordination numbers of the current positions (mdp_coord_setup)
+  MdpCentro centro;                // per-atom centro-symmetry parameters of the current positions (mdp_centro_setup)
   MdpProfile profile;              // binned mass, momentum and kinetic energy of the current atoms (mdp_profile_setup)
   MdpHeatflux heatflux;            // partial sums of a heat-current read (mdp_heatflux_sums)
   // eflag / vflag of the last FINISHED compute while its per-atom tallies (eatom, vatom) still describe the owned atoms in
@@ -1246,6 +1265,8 @@ template <class Bits = MdpSlotBits> Bits mdp_slot_bits(int n, const int *bit)
 void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
 void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds
 void mdp_adf_release(mdp_ctx *c); // frees what adf.hip holds
+void mdp_coord_release(mdp_ctx *c); // frees what coord.hip holds
+void mdp_centro_release(mdp_ctx *c); // frees what centro.hip holds
 // measure_bin.hip, queued on the stream: a grid with cells >= cutoff / 2 over the padded hull of the brick (stencil: 2 cells each
 // way), every owned and ghost atom sorted into it, b.cell_start and the cell-ordered records b.rec = {x, y, z, code} with
 // code = (member ? type : 0) | (owned ? kBinOwned : 0).  member: by tag - 1 over 1 .. ntag, or nullptr for every atom; an atom
@@ -1290,6 +1311,27 @@ inline int mdp_require_group_mask(mdp_ctx *c, const char *who, const int gbit, c
 {
   if (gbit && (!c->mask_set || (need_current && c->mask_n != c->nlocal)))
     return mdp_fail(c, MDP_ESTATE, "%s: a group is set but no mask covers the current atoms (mdp_md_set_mask)", who);
+  return MDP_OK;
+}
+// What a per-atom read (coord.hip, centro.hip) checks before it bins: the cutoff of its setup still lies inside the ghost
+// shell, and the mask covers the atoms; then the final half a host deferred is completed, as before every blocking read.
+inline int mdp_peratom_open(mdp_ctx *c, const char *who, const double cutoff, const int gbit)
+{
+  const double limit = c->dd.cutghost - c->cfg.skin;
+  if (cutoff > limit * (1.0 + 1e-12))
+    return mdp_fail(c, MDP_EINVAL, "%s: the cutoff %.15g of the setup exceeds the current ghost shell less the skin, %.15g", who, cutoff, limit);
+  MDP_TRY(mdp_require_group_mask(c, who, gbit, true));
+  return mdp_md_flush_final(c);
+}
+// ... and what it hands over: the w values per owned atom and the owned atoms' tags, in the context's owned order
+inline int mdp_peratom_download(mdp_ctx *c, const double *d_val, const int w, int *tag, double *values)
+{
+  const size_t n = (size_t) c->nlocal;
+  if (n) {
+    MDP_HIP(c, hipMemcpyAsync(values, d_val, sizeof(double) * n * w, hipMemcpyDeviceToHost, c->stream));
+    MDP_HIP(c, hipMemcpyAsync(tag, c->tag.p, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+  }
+  MDP_HIP(c, hipStreamSynchronize(c->stream));
   return MDP_OK;
 }
 // the per-atom tallies are stale from here on (a compute starts, the atoms move, are re-ordered or replaced)

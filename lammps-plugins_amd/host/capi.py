@@ -93,6 +93,9 @@ PROFILE_W = 5                # MDP_PROFILE_W of include/mdpair_hip.h
 PROFILE_MAXBINS = 1 << 20
 ADF_DEGREE, ADF_RADIAN, ADF_COSINE = 0, 1, 2     # MDP_ADF_* of include/mdpair_hip.h
 ADF_ORDINATES = dict(degree=ADF_DEGREE, radian=ADF_RADIAN, cosine=ADF_COSINE)
+ADF_MAXNEIGH = 128           # MDP_ADF_MAXNEIGH: the short list of a wave, of adf.hip and centro.hip
+COORD_MAXCOL, CENTRO_MAXN = 32, 64               # MDP_COORD_MAXCOL, MDP_CENTRO_MAXN
+CENTRO_LATTICE = dict(fcc=12, bcc=8)
 
 EXPORTS = [
     "mdp_abi_version", "mdp_device_count", "mdp_create", "mdp_destroy", "mdp_last_error", "mdp_set_stream",
@@ -123,6 +126,8 @@ EXPORTS = [
     "mdp_md_set_image", "mdp_md_download_unwrapped", "mdp_msd_setup", "mdp_msd_sums", "mdp_msd_info", "mdp_msd_off",
     "mdp_rdf_setup", "mdp_rdf_counts", "mdp_rdf_info", "mdp_rdf_off",
     "mdp_adf_setup", "mdp_adf_counts", "mdp_adf_info", "mdp_adf_off",
+    "mdp_coord_setup", "mdp_coord_read", "mdp_coord_info", "mdp_coord_off",
+    "mdp_centro_setup", "mdp_centro_read", "mdp_centro_info", "mdp_centro_off",
     "mdp_profile_setup", "mdp_profile_range", "mdp_profile_exponent", "mdp_profile_sums", "mdp_profile_info", "mdp_profile_off",
     "mdp_rebomos_centre_paths",
     "mdp_heatflux_sums", "mdp_md_download_vatom",
@@ -1013,6 +1018,55 @@ class Context:
 
     def adf_off(self):
         self._ck(self.L.mdp_adf_off(self.h))
+
+    # ---------------- per-atom structure: coordination numbers and the centro-symmetry parameter (csrc/coord.hip, centro.hip)
+    def coord_setup(self, cutoff, ranges, group_bit=0):
+        """starts a measurement: ranges = [(jlo, jhi), ...] inclusive ranges of LAMMPS types, one column each; group_bit 0: every
+        owned atom is a centre, else the atoms whose mask has the bit (partners of any group count)"""
+        rg = np.ascontiguousarray(ranges, dtype=np.int32).reshape(-1, 2)
+        lo, hi = np.ascontiguousarray(rg[:, 0]), np.ascontiguousarray(rg[:, 1])
+        self._ck(self.L.mdp_coord_setup(self.h, C.c_double(float(cutoff)), C.c_int(len(rg)), _ip(lo), _ip(hi), C.c_int(int(group_bit))))
+
+    def coord_read(self, nlocal):
+        """this rank's (tags[nlocal], values[nlocal][ncol]) in the owned order of md_download; 0 outside the group"""
+        ncol = max(self.coord_info()["ncol"], 1)
+        tags = np.zeros(max(nlocal, 1), dtype=np.int32)
+        vals = np.zeros((max(nlocal, 1), ncol))
+        self._ck(self.L.mdp_coord_read(self.h, _ip(tags), _dp(vals)))
+        return tags[:nlocal], vals[:nlocal]
+
+    def coord_info(self):
+        """whether a measurement is on, its columns and group bit, and its serial (unique in the process per coord_setup)"""
+        out = (C.c_longlong * 4)()
+        self._ck(self.L.mdp_coord_info(self.h, out))
+        return dict(on=bool(out[0]), ncol=int(out[1]), groupbit=int(out[2]), serial=int(out[3]))
+
+    def coord_off(self):
+        self._ck(self.L.mdp_coord_off(self.h))
+
+    def centro_setup(self, nnn, cutoff=None, group_bit=0):
+        """starts a measurement over the nnn nearest neighbours (even; "fcc" = 12, "bcc" = 8) inside cutoff (None: the ghost
+        shell's limit, cutghost - skin); group_bit as in coord_setup"""
+        n = CENTRO_LATTICE.get(nnn, nnn)
+        self._ck(self.L.mdp_centro_setup(self.h, C.c_int(int(n)), C.c_double(0.0 if cutoff is None else float(cutoff)),
+                                         C.c_int(int(group_bit))))
+
+    def centro_read(self, nlocal):
+        """this rank's (tags[nlocal], values[nlocal]) in the owned order of md_download; 0 outside the group and for a centre with
+        fewer than nnn atoms inside the cutoff (centro_info()["few"] counts those)"""
+        tags = np.zeros(max(nlocal, 1), dtype=np.int32)
+        vals = np.zeros(max(nlocal, 1))
+        self._ck(self.L.mdp_centro_read(self.h, _ip(tags), _dp(vals)))
+        return tags[:nlocal], vals[:nlocal]
+
+    def centro_info(self):
+        """whether a measurement is on, its nnn, the centres with fewer than nnn partners at the last read, and its serial"""
+        out = (C.c_longlong * 4)()
+        self._ck(self.L.mdp_centro_info(self.h, out))
+        return dict(on=bool(out[0]), nnn=int(out[1]), few=int(out[2]), serial=int(out[3]))
+
+    def centro_off(self):
+        self._ck(self.L.mdp_centro_off(self.h))
 
     # ---------------- binned mass, momentum and kinetic energy (csrc/profile.hip)
     def profile_setup(self, dims, nbins, group_bit=0):

@@ -630,6 +630,38 @@ class DeviceDomain:
     def adf_off(self):
         self.ctx.adf_off()
 
+    # ------------------------------------------------------------------ per-atom structure
+    def coord(self, cutoff, jtypes=None, group_bit=0):
+        """starts per-atom coordination numbers (LAMMPS compute coord/atom cutoff): for every owned atom with mask & group_bit
+        (0: every atom; otherwise set_group must have given a mask) the atoms of any group inside cutoff (at most cutghost -
+        skin), one column per entry of jtypes, each a LAMMPS type or an inclusive range (lo, hi); None: one column over all
+        types.  With several ranks every rank makes the same call."""
+        rng = lambda t: (int(t), int(t)) if np.ndim(t) == 0 else (int(t[0]), int(t[1]))
+        cols = [(1, len(self._mass_by_type) - 1)] if jtypes is None else [rng(t) for t in jtypes]
+        self.ctx.coord_setup(cutoff, cols, group_bit)
+
+    def coord_read(self):
+        """(tags[nlocal], values[nlocal][ncol]) of this rank's owned atoms; 0 for an atom outside the group"""
+        self.flush()
+        return self.ctx.coord_read(self.nlocal)
+
+    def coord_off(self):
+        self.ctx.coord_off()
+
+    def centro(self, nnn, cutoff=None, group_bit=0):
+        """starts the per-atom centro-symmetry parameter (LAMMPS compute centro/atom): nnn "fcc" (12), "bcc" (8) or an even
+        number; for every owned atom of the group the nnn nearest atoms inside cutoff (None: cutghost - skin), the nnn / 2
+        smallest |R_a + R_b|^2 of their pairs added.  An atom with fewer than nnn atoms inside gets 0."""
+        self.ctx.centro_setup(nnn, cutoff, group_bit)
+
+    def centro_read(self):
+        """(tags[nlocal], values[nlocal]) of this rank's owned atoms; ctx.centro_info()["few"]: the atoms short of nnn neighbours"""
+        self.flush()
+        return self.ctx.centro_read(self.nlocal)
+
+    def centro_off(self):
+        self.ctx.centro_off()
+
     # ------------------------------------------------------------------ temperature, density and flow profiles
     def profile(self, dims, nbins, group_bit=0):
         """starts a binned measurement of mass, momentum and kinetic energy (LAMMPS compute chunk/atom bin/1d|2d|3d with

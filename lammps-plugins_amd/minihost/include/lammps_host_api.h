@@ -349,17 +349,27 @@ class Fix : protected Pointers {
   virtual double compute_vector(int) { return 0.0; }             // its element k - 1
 };
 
-// the part of LAMMPS' Compute a global-vector or global-array compute style touches (compute.h of the 2 Aug 2023 release)
+// the part of LAMMPS' Compute a global-scalar, global-vector, global-array or per-atom compute style touches (compute.h of the
+// 2 Aug 2023 release)
 class Compute : protected Pointers {
  public:
   char *id = nullptr, *style = nullptr;
   int igroup = 0, groupbit = 1;
+  double scalar = 0.0;          // the value compute_scalar() leaves (thermo c_ID reads it)
+  int scalar_flag = 0, extscalar = 0;
+  bigint invoked_scalar = -1;   // the step compute_scalar() ran last
   double *vector = nullptr;     // the values compute_vector() leaves (thermo c_ID[k] reads vector[k - 1])
   int vector_flag = 0, size_vector = 0, extvector = 0, create_attribute = 0;
   bigint invoked_vector = -1;   // the step compute_vector() ran last
   double **array = nullptr;     // the values compute_array() leaves (thermo c_ID[i][j] reads array[i - 1][j - 1])
   int array_flag = 0, size_array_rows = 0, size_array_cols = 0, extarray = 0;
   bigint invoked_array = -1;    // the step compute_array() ran last
+  // per-atom values of the owned atoms, in the order of atom->tag: vector_atom[i] when size_peratom_cols is 0, array_atom[i][k]
+  // otherwise (dump custom c_ID / c_ID[k] and compute reduce read them)
+  int peratom_flag = 0, size_peratom_cols = 0;
+  double *vector_atom = nullptr;
+  double **array_atom = nullptr;
+  bigint invoked_peratom = -1;  // the step compute_peratom() ran last
   // what Integrate::ev_set reads: the compute needs per-atom energy / per-atom virial tallied on the steps it is due,
   // and (timeflag) it is due only on the steps its readers -- thermo, fix ave/time -- announce
   int peatomflag = 0, pressatomflag = 0, timeflag = 0;
@@ -380,8 +390,10 @@ class Compute : protected Pointers {
     free(style);
   }
   virtual void init() = 0;
+  virtual double compute_scalar() { return 0.0; }
   virtual void compute_vector() {}
   virtual void compute_array() {}
+  virtual void compute_peratom() {}
 };
 
 // a command style (command.h of the 2 Aug 2023 release): one object per use of the input word, command() runs it

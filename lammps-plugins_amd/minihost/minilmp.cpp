@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <condition_variable>
 #include <mutex>
@@ -292,6 +293,15 @@ struct Host {
       if (id == c->id) return c;
     return nullptr;
   }
+  void add_compute(Compute *cp) // (a compute with the ID of an existing one replaces it)
+  {
+    if (Compute *old = compute_by_id(cp->id)) {
+      computes.erase(std::find(computes.begin(), computes.end(), old));
+      delete old;
+    }
+    computes.push_back(cp);
+    sync_modify();
+  }
   std::vector<void *> handles;
 
   // box: lo, prd, tilt (xy,xz,yz)
@@ -337,6 +347,21 @@ struct Host {
   double dt = 0.001;
   int thermo_every = 0;
   std::vector<std::string> thermo_cols = {"step", "temp", "epair", "emol", "etotal", "press"};
+  // `dump ID GROUP custom N FILE id type x y z c_ID c_ID[k] ...` with at least one c_ column: written every N steps of a run
+  // (not at its setup: the atoms are in the host's own order there), rows sorted by id, %.17g, rank 0 writes one file
+  struct DumpCol {
+    std::string name;  // id, type, x, y, z or c_ID / c_ID[k]
+    std::string cid;   // the compute's ID for a c_ column
+    int k = 0;         // ... and its column, 1-based; 0: the per-atom vector
+  };
+  struct Dump {
+    std::string id, file;
+    int bit = 1;
+    long every = 0;
+    std::vector<DumpCol> cols;
+    long written = 0;  // snapshots so far (a FILE without * is opened once and appended to)
+  };
+  std::vector<Dump> dumps;
   std::string fix_style = "";
   double nvt_t0 = 0, nvt_t1 = 0, nvt_damp = 0.1, nvt_eta_dot = 0.0;
   long step = 0;
@@ -986,8 +1011,8 @@ struct Host {
     return e;
   }
 
-  // A thermo column c_ID[k] (element k of a global vector compute) or c_ID[i][j] (element (i, j) of a global array
-  // compute): the compute and the indices, j = 0 for a vector.  Refused: an unknown ID (must_exist; otherwise nullptr:
+  // A thermo column c_ID (a global scalar compute: i = j = 0), c_ID[k] (element k of a global vector compute) or c_ID[i][j]
+  // (element (i, j) of a global array compute): the compute and the indices, j = 0 for a vector.  Refused: a per-atom compute, an unknown ID (must_exist; otherwise nullptr:
   // the compute may be defined later, and the column is looked at again when it is printed), a compute of the other
   // kind, an index out of bounds.
   Compute *compute_ref(const std::string &c, bool must_exist, int &i, int &j)
@@ -1000,6 +1025,10 @@ struct Host {
       if (must_exist) error.all(FLERR, "Could not find thermo custom compute ID: " + id);
       return nullptr;
     }
+    if (cp->peratom_flag && !cp->scalar_flag && !cp->vector_flag && !cp->array_flag)
+      error.all(FLERR, "Thermo custom compute " + std::string(cp->id) + " computes per-atom values: " + c + " is no global value (reduce it: compute ID GROUP " +
+                           "reduce sum|ave|min|max c_" + cp->id + (cp->size_peratom_cols ? "[k]" : "") + ")");
+    if (lb == std::string::npos && cp->scalar_flag) return cp; // c_ID: the compute's scalar, i = j = 0
     if (lb != std::string::npos && rb != std::string::npos && rb > lb + 1) i = atoi(c.substr(lb + 1, rb - lb - 1).c_str());
     const size_t lb2 = rb == std::string::npos ? rb : c.find('[', rb), rb2 = lb2 == std::string::npos ? lb2 : c.find(']', lb2);
     if (lb2 != std::string::npos) {
@@ -1065,6 +1094,9 @@ struct Host {
           if (j) {
             if (cp->invoked_array != (bigint) step) cp->compute_array();
             v = cp->array[i - 1][j - 1];
+          } else if (!i) {
+            if (cp->invoked_scalar != (bigint) step) cp->compute_scalar();
+            v = cp->scalar;
           } else {
             if (cp->invoked_vector != (bigint) step) cp->compute_vector();
             v = cp->vector[i - 1];
@@ -1088,6 +1120,22 @@ struct Host {
   // ---------------------------------------------------------------- Verlet
   void force_clear() { std::fill(fs.begin(), fs.end(), 0.0); }
   void write_dump(int bit, const std::string &path, bool with_image = false);
+  void define_dump(const std::vector<std::string> &w);
+  Compute *peratom_ref(const std::string &col, const std::string &who, std::string &cid, int &k);
+  void write_custom_dumps();
+  // the dumps due on this step, and the first step >= from on which one is (LONG_MAX without a dump)
+  bool dump_due() const
+  {
+    for (const Dump &d : dumps)
+      if (step % d.every == 0) return true;
+    return false;
+  }
+  long next_dump(long from) const
+  {
+    long nd = LONG_MAX;
+    for (const Dump &d : dumps) nd = std::min(nd, (from + d.every - 1) / d.every * d.every);
+    return nd;
+  }
 
   void sync_domain() // Domain::set_global_box
   {
@@ -1171,7 +1219,8 @@ struct Host {
       update.ntimestep = step;
       { // Output::next: the next thermo step, or the last step of the run
         long nt = every > 0 ? (step + every - 1) / every * every : first + nsteps;
-        output.next = output.next_thermo = std::min<long>(nt, first + nsteps);
+        output.next_thermo = std::min<long>(nt, first + nsteps);
+        output.next = std::min<long>(output.next_thermo, next_dump(step)); // (a dump step is an output step: the atoms come home)
       }
       if (fix) { // Verlet::run with a time-integration fix style from a plugin
         fix->initial_integrate((every > 0 && step % every == 0) || k == nsteps ? 2 | va : 0); // (ev_set: this step's vflag)
@@ -1198,6 +1247,7 @@ struct Host {
         }
         fix->final_integrate();
         if (out || last) print_thermo();
+        if (dump_due()) write_custom_dumps();
         continue;
       }
       const int n = atom.nlocal;
@@ -1243,6 +1293,7 @@ struct Host {
         for (auto &v : vs) v *= sc;
       }
       if (out || last) print_thermo();
+      if (dump_due()) write_custom_dumps();
     }
     const double loop = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     for (Fix *f : fixes) f->post_run(); // (Modify::post_run, behind Verlet::run in Run::command)
@@ -1321,6 +1372,171 @@ void Host::write_dump(int bit, const std::string &path, bool with_image)
   }
   if (multi()) world->barrier(); // (nobody moves its atoms while rank 0 reads them)
 }
+
+
+// A per-atom column c_ID or c_ID[k] of `who` ("Dump custom", "Compute reduce"): the compute, its ID and k (0: the per-atom
+// vector).  Refused: an unknown ID, a compute without per-atom values, an index on a vector, none on an array, one out of range.
+Compute *Host::peratom_ref(const std::string &col, const std::string &who, std::string &cid, int &k)
+{
+  const size_t lb = col.find('['), rb = col.find(']');
+  cid = col.substr(2, lb == std::string::npos ? lb : lb - 2);
+  k = 0;
+  Compute *cp = compute_by_id(cid);
+  if (!cp) error.all(FLERR, "Could not find " + who + " compute ID: " + cid);
+  if (!cp->peratom_flag) error.all(FLERR, who + " compute " + cid + " does not compute per-atom info");
+  if (lb == std::string::npos) {
+    if (cp->size_peratom_cols != 0)
+      error.all(FLERR, who + " compute " + cid + " does not calculate a per-atom vector: it has " + std::to_string(cp->size_peratom_cols) + " columns, " + col + "[k] names one");
+    return cp;
+  }
+  if (rb == std::string::npos || rb != col.size() - 1 || rb == lb + 1) error.all(FLERR, who + ": " + col + " is not c_ID or c_ID[k]");
+  k = atoi(col.substr(lb + 1, rb - lb - 1).c_str());
+  if (cp->size_peratom_cols == 0) error.all(FLERR, who + " compute " + cid + " does not calculate a per-atom array: " + col + " indexes a per-atom vector");
+  if (k < 1 || k > cp->size_peratom_cols)
+    error.all(FLERR, who + " compute " + cid + " has " + std::to_string(cp->size_peratom_cols) + " columns: " + col + " is accessed out-of-range");
+  return cp;
+}
+
+// dump ID GROUP custom N FILE col ... (called only when a column starts with c_; every other dump line is accepted and ignored)
+void Host::define_dump(const std::vector<std::string> &w)
+{
+  const std::string usage = "minilmp supports `dump ID GROUP custom N FILE id type x y z c_ID c_ID[k] ...` only";
+  if (w.size() < 7 || w[3] != "custom") error.all(FLERR, usage);
+  Dump d;
+  d.id = w[1];
+  const int ig = group.find(w[2]);
+  if (ig < 0) error.all(FLERR, "Could not find dump group ID " + w[2]);
+  d.bit = group_bits[ig];
+  char *end = nullptr;
+  d.every = strtol(w[4].c_str(), &end, 10);
+  if (end == w[4].c_str() || *end || d.every < 1) error.all(FLERR, "Illegal dump command: N must be a whole number >= 1, not " + w[4]);
+  d.file = w[5];
+  for (size_t k = 6; k < w.size(); k++) {
+    DumpCol c;
+    c.name = w[k];
+    if (w[k].compare(0, 2, "c_") == 0)
+      peratom_ref(w[k], "Dump custom", c.cid, c.k);
+    else if (w[k] != "id" && w[k] != "type" && w[k] != "x" && w[k] != "y" && w[k] != "z")
+      error.all(FLERR, usage + ", not the column " + w[k]);
+    d.cols.push_back(c);
+  }
+  for (size_t k = 0; k < dumps.size(); k++)
+    if (dumps[k].id == d.id) error.all(FLERR, "Reuse of dump ID '" + d.id + "'");
+  dumps.push_back(d);
+}
+
+// the dumps due on this step: every rank evaluates the computes they name, then rank 0 takes the group's atoms from every rank,
+// sorts them by id and writes "ITEM: ATOMS <cols>" with %.17g
+void Host::write_custom_dumps()
+{
+  for (Dump &d : dumps) {
+    if (step % d.every != 0) continue;
+    for (const DumpCol &c : d.cols) {
+      if (c.cid.empty()) continue;
+      std::string cid;
+      int k = 0;
+      Compute *cp = peratom_ref(c.name, "Dump custom", cid, k); // (the compute may have been replaced since the dump line)
+      if (cp->invoked_peratom != (bigint) step) cp->compute_peratom();
+    }
+    if (multi()) world->barrier(); // (every rank's values are where they are)
+    if (me == 0) {
+      struct Row {
+        int id;
+        std::vector<double> v;
+      };
+      std::vector<Row> rows;
+      for (int q = 0; q < (multi() ? np : 1); q++) {
+        Host *o = multi() ? world->host[q] : this;
+        for (int i = 0; i < o->atom.nlocal; i++) {
+          if (!(o->masks[i] & d.bit)) continue;
+          Row r;
+          r.id = o->tags[i];
+          for (const DumpCol &c : d.cols) {
+            if (c.name == "id") r.v.push_back(o->tags[i]);
+            else if (c.name == "type") r.v.push_back(o->types[i]);
+            else if (c.cid.empty()) r.v.push_back(o->xs[3 * (size_t) i + (c.name[0] - 'x')]);
+            else {
+              const Compute *cp = o->compute_by_id(c.cid);
+              r.v.push_back(c.k ? cp->array_atom[i][c.k - 1] : cp->vector_atom[i]);
+            }
+          }
+          rows.push_back(r);
+        }
+      }
+      std::sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) { return a.id < b.id; });
+      std::string path = d.file;
+      const size_t star = path.find('*');
+      if (star != std::string::npos) path.replace(star, 1, std::to_string(step));
+      FILE *fp = fopen(path.c_str(), star == std::string::npos && d.written ? "a" : "w");
+      if (!fp) error.one(FLERR, "Cannot open dump file " + path);
+      fprintf(fp, "ITEM: TIMESTEP\n%ld\nITEM: NUMBER OF ATOMS\n%zu\nITEM: ATOMS", step, rows.size());
+      for (const DumpCol &c : d.cols) fprintf(fp, " %s", c.name.c_str());
+      fprintf(fp, "\n");
+      for (const Row &r : rows) {
+        for (size_t k = 0; k < d.cols.size(); k++) {
+          const std::string &n = d.cols[k].name;
+          if (n == "id" || n == "type") fprintf(fp, k ? " %d" : "%d", (int) r.v[k]);
+          else fprintf(fp, k ? " %.17g" : "%.17g", r.v[k]);
+        }
+        fprintf(fp, "\n");
+      }
+      fclose(fp);
+    }
+    d.written++;
+    if (multi()) world->barrier(); // (nobody moves its atoms or its values while rank 0 reads them)
+  }
+}
+
+// The built-in `compute ID GROUP reduce sum|ave|min|max c_ID|c_ID[k]`: one per-atom input, reduced over the group's atoms of
+// every rank to a global scalar (thermo c_ID).  ave divides by the atoms of the group, as LAMMPS does; an empty group reads 0.
+class ComputeReduce : public Compute {
+ public:
+  ComputeReduce(LAMMPS *lmp, int narg, char **arg, Host *host) : Compute(lmp, narg, arg), h(host), mode(0), col(0)
+  {
+    const std::string usage = "minilmp supports `compute ID GROUP reduce sum|ave|min|max c_ID|c_ID[k]` over one per-atom compute only";
+    if (igroup < 0) error->all(FLERR, std::string("Could not find compute group ID ") + arg[1]);
+    if (narg != 5) error->all(FLERR, usage);
+    static const char *const modes[4] = {"sum", "ave", "min", "max"};
+    mode = -1;
+    for (int m = 0; m < 4; m++)
+      if (!strcmp(arg[3], modes[m])) mode = m;
+    if (mode < 0) error->all(FLERR, std::string("Illegal compute reduce command: the mode is sum, ave, min or max, not ") + arg[3]);
+    input = arg[4];
+    if (input.compare(0, 2, "c_") != 0) error->all(FLERR, usage + ", not the input " + input);
+    h->peratom_ref(input, "Compute reduce", source, col);
+    scalar_flag = 1;
+    extscalar = mode == 0;
+  }
+  void init() override { h->peratom_ref(input, "Compute reduce", source, col); }
+  double compute_scalar() override
+  {
+    invoked_scalar = update->ntimestep;
+    Compute *cp = h->peratom_ref(input, "Compute reduce", source, col);
+    if (cp->invoked_peratom != update->ntimestep) cp->compute_peratom();
+    double acc = mode == 2 ? 1e300 : (mode == 3 ? -1e300 : 0.0), n = 0.0;
+    for (int i = 0; i < atom->nlocal; i++) {
+      if (!(atom->mask[i] & groupbit)) continue;
+      const double v = col ? cp->array_atom[i][col - 1] : cp->vector_atom[i];
+      n += 1.0;
+      if (mode == 2) acc = std::min(acc, v);
+      else if (mode == 3) acc = std::max(acc, v);
+      else acc += v;
+    }
+    const std::vector<double> part = h->gather(acc), cnt = h->gather(n);
+    double tot = 0.0;
+    for (double c : cnt) tot += c;
+    acc = part[0];
+    for (size_t q = 1; q < part.size(); q++) acc = mode == 2 ? std::min(acc, part[q]) : (mode == 3 ? std::max(acc, part[q]) : acc + part[q]);
+    if (tot == 0.0) acc = 0.0;
+    else if (mode == 1) acc /= tot;
+    return scalar = acc;
+  }
+
+ private:
+  Host *h;
+  int mode, col; // mode: 0 sum, 1 ave, 2 min, 3 max
+  std::string input, source;
+};
 
 void PeriodicComm::forward_comm(Pair *pair)
 {
@@ -1637,6 +1853,8 @@ struct Script {
       H.domain.xperiodic = w[1] == "p";
       H.domain.yperiodic = w[2] == "p";
       H.domain.zperiodic = w[3] == "p";
+    } else if (c == "dump" && std::any_of(w.begin() + std::min<size_t>(w.size(), 6), w.end(), [](const std::string &col) { return col.compare(0, 2, "c_") == 0; })) {
+      H.define_dump(w); // (a dump with a c_ column is written; every other one is accepted and ignored, below)
     } else if (c == "atom_style" || c == "dimension" || c == "atom_modify" || c == "echo" ||
                c == "log" || c == "dump" || c == "dump_modify" || c == "restart" || c == "comm_modify") {
       // accepted, fixed behaviour: atomic, 3d
@@ -1726,6 +1944,32 @@ struct Script {
     } else if (c == "create_atoms") {
       need(3);
       create_atoms(w);
+    } else if (c == "delete_atoms") { // delete_atoms group ID: the group's atoms go, the IDs close up (compress yes, the default)
+      need(3);
+      if (w[1] != "group" || w.size() != 3) H.error.all(FLERR, "minilmp supports `delete_atoms group ID` only");
+      if (H.decomposed) H.error.all(FLERR, "minilmp -np N: delete_atoms after the first run is not supported");
+      const int ig = H.group.find(w[2]);
+      if (ig < 0) H.error.all(FLERR, "Could not find delete_atoms group ID " + w[2]);
+      const int n0 = H.atom.nlocal, bit = H.group_bits[ig];
+      int n = 0;
+      for (int i = 0; i < n0; i++) {
+        if (H.masks[i] & bit) continue;
+        for (int d = 0; d < 3; d++) {
+          H.xs[3 * (size_t) n + d] = H.xs[3 * (size_t) i + d];
+          H.vs[3 * (size_t) n + d] = H.vs[3 * (size_t) i + d];
+        }
+        H.types[n] = H.types[i];
+        H.masks[n] = H.masks[i];
+        H.images[n] = H.images[i];
+        H.tags[n] = n + 1;
+        n++;
+      }
+      H.atom.nlocal = n;
+      H.atom.nghost = 0;
+      H.atom.natoms = n;
+      H.set_views(n);
+      H.set_vviews();
+      printf("Deleted %d atoms, new total = %d\n", n0 - n, n);
     } else if (c == "replicate") {
       need(4);
       replicate(std::stoi(w[1]), std::stoi(w[2]), std::stoi(w[3]));
@@ -1972,19 +2216,18 @@ struct Script {
         H.sync_modify();
       } else
         H.error.all(FLERR, "minilmp supports fix nve|nvt and time-integration fix styles of loaded plugins only");
+    } else if (c == "compute" && w.size() > 3 && w[3] == "reduce") { // the built-in reduction of one per-atom compute to a scalar
+      H.update.ntimestep = H.step;
+      std::vector<char *> args;
+      for (size_t k = 1; k < w.size(); k++) args.push_back(const_cast<char *>(w[k].c_str()));
+      H.add_compute(new ComputeReduce(&H.lmp, (int) args.size(), args.data(), &H));
     } else if (c == "compute") { // compute ID group style args: a compute style from a plugin
       need(4);
       if (!H.compute_styles.count(w[3])) H.error.all(FLERR, "Unrecognized compute style '" + w[3] + "' (minilmp hosts the compute styles of loaded plugins only)");
       H.update.ntimestep = H.step;
       std::vector<char *> args;
       for (size_t k = 1; k < w.size(); k++) args.push_back(const_cast<char *>(w[k].c_str()));
-      Compute *cp = static_cast<Compute *>(H.compute_styles[w[3]](&H.lmp, (int) args.size(), args.data()));
-      if (Compute *old = H.compute_by_id(cp->id)) { // (a compute with the ID of an existing one replaces it)
-        H.computes.erase(std::find(H.computes.begin(), H.computes.end(), old));
-        delete old;
-      }
-      H.computes.push_back(cp);
-      H.sync_modify();
+      H.add_compute(static_cast<Compute *>(H.compute_styles[w[3]](&H.lmp, (int) args.size(), args.data())));
     } else if (c == "timestep") {
       need(2);
       H.dt = std::stod(w[1]);

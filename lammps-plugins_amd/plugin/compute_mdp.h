@@ -12,6 +12,14 @@
                       a context holds one measurement of a kind, and mdp_*_info names it by a serial: the setup goes up
                       once per context, and again when another compute's took its place
      global_array     the storage behind Compute::array
+     peratom_columns / read_peratom
+                      a per-atom compute: its flags, the storage behind vector_atom / array_atom for atom->nmax atoms, and
+                      the hand-over of a read that returns the brick's owned atoms' tags with their values.  On an output
+                      step mdp_brick_to_host has just put the brick's owned atoms into the host's arrays in the brick's order,
+                      so the tags a read returns are atom->tag[0 .. nlocal) in order; read_peratom checks that.  At the setup
+                      of a run (the thermo of step 0) the host still holds its own order: the rows then go to the host's atoms
+                      by ID, and an ID the host does not own, or owns twice, fails with a message -- it never hands out
+                      misattributed values
      sum_whole        whole numbers summed exactly over the ranks (mdp_whole_sum.h), in place
 -------------------------------------------------------------------------------------------------- */
 #ifndef MDP_COMPUTE_MDP_H
@@ -44,6 +52,9 @@ class ComputeMDP : public Compute {
   void record(mdp_ctx *c, info_fn info);          // ... behind a setup
   void forget() { sent_to = nullptr; }
   void global_array(long long nrows, int ncols);
+  typedef int (*peratom_fn)(mdp_ctx *, int *, double *);
+  void peratom_columns(int ncols);                // 1: a per-atom vector, more: a per-atom array
+  void read_peratom(mdp_ctx *c, peratom_fn read); // read(c, tags, values[nlocal][ncols]) into vector_atom / array_atom
 
   // v[k] = its sum over the ranks; every |sum| < 2^62.  In pieces: a megabyte of transient buffers whatever n
   template <typename T> void sum_whole(T *v, const size_t n)
@@ -63,6 +74,8 @@ class ComputeMDP : public Compute {
   long long sent_serial;
   std::vector<double> values;
   std::vector<double *> rows;
+  int peratom_ncols = 0;
+  std::vector<int> peratom_tags;
 };
 
 }    // namespace LAMMPS_NS
