@@ -316,6 +316,12 @@ int mdp_rebomos_list_info(mdp_ctx *ctx, long long out[8]);
  * and took the general loops (all of them with MDP_CENTRE_FULL=0).  reset != 0 clears both afterwards.  Waits for the
  * stream.  (No reference counterpart.) */
 int mdp_rebomos_centre_paths(mdp_ctx *ctx, long long out[2], int reset);
+/* ... and, over the same computes, *out = trips of the first pair loop of the waves on the full-group path that took the
+ * blend of the two G(cos) polynomials (some pair of the trip had cos >= 1/2); a wave of G-lane groups makes G/2 trips.
+ * The order of the candidate rows decides it (MDP_CAND_ORDER, read at each list build: 0 keeps the rows as the sweep
+ * emitted them).  A count of its own: reset != 0 clears it afterwards and leaves the two above alone.  Waits for the
+ * stream.  (No reference counterpart.) */
+int mdp_rebomos_centre_blend_trips(mdp_ctx *ctx, long long *out, int reset);
 /* how the work of the last compute was spread over the kernel classes (diagnostics of a bench line; no reference
  * counterpart -- the CPU style has one loop, pair_rebomos.cpp:358-447, pair_aeam.cpp:337-475):
  * rebomos: out[0..19] = centres per launch class at the last style-list build, class = 2 * (lane-group index: 0 one lane

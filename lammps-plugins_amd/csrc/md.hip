@@ -1816,6 +1816,18 @@ int mdp_rebomos_centre_paths(mdp_ctx *c, long long out[2], int reset)
   return MDP_OK;
 }
 
+int mdp_rebomos_centre_blend_trips(mdp_ctx *c, long long *out, int reset)
+{
+  if (!c || !out) return MDP_EINVAL;
+  *out = 0;
+  if (!c->centre_paths.p) return MDP_OK; // (no compute has counted yet)
+  unsigned long long h;
+  MDP_TRY(mdp_read_one(c, c->centre_paths.p + 2, sizeof h, &h));
+  *out = (long long) h;
+  if (reset) MDP_HIP(c, hipMemsetAsync(c->centre_paths.p + 2, 0, sizeof h, c->stream));
+  return MDP_OK;
+}
+
 int mdp_md_class_stats(mdp_ctx *c, long long out[32])
 {
   if (!c || !out) return MDP_EINVAL;

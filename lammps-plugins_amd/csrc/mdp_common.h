@@ -890,7 +890,7 @@ struct mdp_ctx {
   DevBuf<int> rev16;              // [nlocal][16] the first 16 of them at a fixed stride
   DevBuf<int> ovf;                // 5 x [1+nall+1]: centres handed on this step -- to the general kernel / by the lane-per-centre kernel
   int ovf_stride = 0;
-  DevBuf<unsigned long long> centre_paths; // [2] waves of rebo_centre_kernel on the full-group path / on the general loops (MDP_CENTRE_COUNT=1)
+  DevBuf<unsigned long long> centre_paths; // [3] waves of rebo_centre_kernel on the full-group path / on the general loops / blend trips of the former (MDP_CENTRE_COUNT=1)
   bool centre_full_now = true;    // this compute's lane-group kernels may take the full-group path (MDP_CENTRE_FULL)
   unsigned long long *centre_cnt_now = nullptr; // ... and count their waves here (null: no counting)
   int ovf3_hot[4] = {0, 0, 0, 0}; // computes left in list mode per (part, element) list of the lane-per-centre kernel

@@ -525,7 +525,11 @@ template <int G> struct CentreCfg {
 // centres that found a fourth neighbour: centres[-1] holds their number), the candidates from the rows themselves.
 // The host sizes the grid from the count it saw a step ago (h_count, a pinned word block 0 refreshes); entries beyond
 // what this grid covers are passed on to the general kernel's list, so no count is ever trusted.
-template <int G, bool LIST = false>
+// COUNT: the variant a compute under MDP_CENTRE_COUNT=1 launches, which also counts the trips of the full-group path's
+// first pair loop that took the blend.  The count is a scalar that lives through that loop, and the loop has no scalar
+// register to spare (with it: 12 SGPRs spilled, 129 VGPRs, three waves per SIMD instead of four for 12-lane groups), so
+// the kernel every other compute runs is compiled without it -- instruction for instruction what it was.
+template <int G, bool LIST = false, bool COUNT = false>
 __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
     const RebomosDev P, const int *__restrict__ centres, const int ncent_arg, const int nlocal,
     const double4 *__restrict__ xq, const int *__restrict__ cand_off, const int *__restrict__ cand,
@@ -533,7 +537,7 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
     double *__restrict__ fown, double *__restrict__ acc, int *__restrict__ ovf, const int eflag, const int vflag,
     const int tc /* element of every centre of this launch: a scalar, and with it all per-element constants */,
     const int full_on /* 0: every wave takes the general pair loops (MDP_CENTRE_FULL=0) */,
-    unsigned long long *__restrict__ path_cnt /* null, or {waves on the full-group path, other waves} (MDP_CENTRE_COUNT=1) */)
+    unsigned long long *__restrict__ path_cnt /* null, or {waves on the full-group path, other waves, trips of the former's first pair loop that took the blend} (MDP_CENTRE_COUNT=1) */)
 {
   using C = CentreCfg<G>;
   __shared__ double s_rec[C::WPB * C::GPW * C::STRIDE];
@@ -705,6 +709,7 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
       for (int d = 1; d <= G / 2; d++) from4[d - 1] = 4 * (lane - d + (m < d ? G : 0));
     }
   double S = 0.0;
+  int blend = 0; // COUNT: trips of the full-group path below that took the blend (wave-uniform)
   if (full) {
     if constexpr (kFullPath)
       if (kAllLanes || lane_again < C::GPW * G) {
@@ -718,8 +723,10 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
             cs = fmin(cs, 1.0);
             cs = fmax(cs, -1.0);
             double dg, g;
-            if (__any(cs >= 0.5)) g = gspline(cb, cg, cs, dg, lead);
-            else g = poly6(cb, cs, dg);
+            if (__any(cs >= 0.5)) {
+              g = gspline(cb, cg, cs, dg, lead);
+              if constexpr (COUNT) blend++;
+            } else g = poly6(cb, cs, dg);
             em[2 * (d - 1) * G] = g;
             em[2 * (d - 1) * G + 1] = dg;
             S += q[4] * g;
@@ -730,6 +737,8 @@ __global__ __launch_bounds__(64 * CentreCfg<G>::WPB) void rebo_centre_kernel(
           __builtin_amdgcn_sched_barrier(0); // (keeps a trip's loads out of the trips before it: 128 VGPRs hold)
         }
       }
+    if constexpr (COUNT)
+      if (path_cnt && blend && lane == 0) atomicAdd(&path_cnt[2], (unsigned long long) blend); // (one atomic per wave)
   } else
   for (int d = 1; d <= nw / 2; d++) {
     const bool mine = act && (2 * d < n || (2 * d == n && m < d));
@@ -2638,6 +2647,91 @@ __global__ __launch_bounds__(256) void cand_csr_kernel(const RebomosDev P, const
   if (have && s == 0) cnt[i] = n;
 }
 
+// ---- the order of a candidate row (MDP_CAND_ORDER, default on) -------------------------------------------------------
+// The neighbours of a centre take their slots in row order, and a trip d of the centre kernels' pair loops evaluates the
+// pairs (m, m + d mod n) of every centre of a wave: the blend of the two G(cos) polynomials runs for the whole wave when
+// any of them has cos >= 1/2.  A row as the bin sweep emits it (z, then y, then x) spreads the 15 or 16 such pairs of a Mo
+// centre of 2H-MoS2 (the Mo-Mo-S pairs of a shared Mo3S triangle at 0.65, the Mo-Mo-Mo pairs at 60 degrees) over all six
+// trips.  Here a row is put in the order of the azimuth about the lab axis along which the centre's neighbour cloud is
+// thinnest: neighbours close in angle are then close in the row, and those pairs fall into the trips 1, 2, 3 (DESIGN.md
+// section 4 item 45).  The axis is a LAB axis, so the centres of a wave agree on it and with it on the trips.
+//   axis     smallest sum of d_k^2 over the row's candidates inside rcmax (none: z; ties towards z, then y)
+//   key      atan2 in the plane of the other two axes, then the coordinate along the axis, then the place in the row
+//   rank     by counting: a permutation whatever the values, and the same one in every run of the same trajectory
+// One group of RP_L lanes per row, in place (the group has read the whole row before it writes).  Every reader of `cand`
+// follows the row index t (active mask, slot record, reverse slot, packed head) or searches the row (rev_kernel), so
+// no consumer assumes an order.  A row longer than the 64 entries the active mask addresses is left alone: rev_kernel
+// refuses the build.
+constexpr int kOrderRow = 64;
+__global__ __launch_bounds__(256) void cand_order_kernel(const RebomosDev P, const int nall,
+                                                         const double4 *__restrict__ xq,
+                                                         const int *__restrict__ cand_off, int *__restrict__ cand)
+{
+  constexpr int NG = 256 / RP_L, U = kOrderRow / RP_L;
+  __shared__ double s_az[NG][kOrderRow], s_h[NG][kOrderRow];
+  const int s = threadIdx.x % RP_L, grp = threadIdx.x / RP_L;
+  const long long i64 = (long long) blockIdx.x * NG + grp;
+  int off = 0, nc = 0;
+  if (i64 < nall) {
+    off = cand_off[i64];
+    nc = cand_off[i64 + 1] - off;
+  }
+  if (nc > kOrderRow) nc = 0;
+  const double4 xi = xq[nc ? (int) i64 : 0];
+  const int ti = (int) xi.w; // (>= 0 for an atom with a row: cand_build_kernel)
+  double dx[U], dy[U], dz[U], sxx = 0.0, syy = 0.0, szz = 0.0;
+  int jj[U];
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    const int t = u * RP_L + s;
+    jj[u] = -1;
+    dx[u] = dy[u] = dz[u] = 0.0;
+    if (t < nc) {
+      jj[u] = cand[off + t];
+      const double4 xj = xq[jj[u]];
+      dx[u] = xj.x - xi.x;
+      dy[u] = xj.y - xi.y;
+      dz[u] = xj.z - xi.z;
+      if (dx[u] * dx[u] + dy[u] * dy[u] + dz[u] * dz[u] < P.rcmaxsq[ti * 2 + (int) xj.w]) {
+        sxx += dx[u] * dx[u];
+        syy += dy[u] * dy[u];
+        szz += dz[u] * dz[u];
+      }
+    }
+  }
+#pragma unroll
+  for (int o = RP_L / 2; o > 0; o >>= 1) { // (xor butterfly: every lane of the group ends with the same bits)
+    sxx += __shfl_xor(sxx, o, 64);
+    syy += __shfl_xor(syy, o, 64);
+    szz += __shfl_xor(szz, o, 64);
+  }
+  const int axis = (szz <= sxx && szz <= syy) ? 2 : (syy <= sxx ? 1 : 0);
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    const int t = u * RP_L + s;
+    if (t < nc) {
+      const double a = axis == 2 ? dx[u] : (axis == 1 ? dz[u] : dy[u]); // (x,y) about z, (z,x) about y, (y,z) about x
+      const double b = axis == 2 ? dy[u] : (axis == 1 ? dx[u] : dz[u]);
+      s_az[grp][t] = atan2(b, a);
+      s_h[grp][t] = axis == 2 ? dz[u] : (axis == 1 ? dy[u] : dx[u]);
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    const int t = u * RP_L + s;
+    if (t < nc) {
+      const double az = s_az[grp][t], h = s_h[grp][t];
+      int rank = 0;
+      for (int k = 0; k < nc; k++) {
+        const double ak = s_az[grp][k], hk = s_h[grp][k];
+        rank += (ak < az || (ak == az && (hk < h || (hk == h && k < t)))) ? 1 : 0;
+      }
+      cand[off + rank] = jj[u];
+    }
+  }
+}
+
 // rev[slot of j in cand(a)] = absolute slot of a in cand(j), for owned a (static between list builds)
 // rev16: the first 16 reverse slots of every owned atom at a fixed stride (-1 beyond the row), so that the
 // gather reaches a slot record in two dependent loads instead of three (no row offset to fetch first)
@@ -3106,6 +3200,16 @@ static int repack_cand_fill(mdp_ctx *c, const Repack &R)
   return MDP_OK;
 }
 
+// the rows in the order that keeps the high-cosine pairs of a crystal's centres in the first trips of the pair loops
+// (cand_order_kernel), before anything has read them.  MDP_CAND_ORDER=0 keeps them as built (tests, A/B; read per build).
+static int repack_cand_order(mdp_ctx *c)
+{
+  const char *e = getenv("MDP_CAND_ORDER");
+  if ((e && atoi(e) == 0) || !c->nall || !c->cand_total) return MDP_OK;
+  return mdp_launch(c, cand_order_kernel, nblk(c->nall, kRpPerBlock), 256, 0, c->stream, c->rebomos, c->nall, c->xq.p,
+                    c->cand_off.p, c->cand.p);
+}
+
 // launch classes of the units (tiles, or clusters without tile lists): small/large union for the LDS allocation
 // of the tile kernel
 static int repack_launch_classes(mdp_ctx *c)
@@ -3221,6 +3325,7 @@ int mdp_rebomos_repack(mdp_ctx *c)
   MDP_TRY(repack_cand_count(c, R));
   MDP_TRY(repack_lj_rows(c, R));
   MDP_TRY(repack_cand_fill(c, R));
+  MDP_TRY(repack_cand_order(c));
   MDP_TRY(repack_launch_classes(c));
   MDP_TRY(repack_centres(c, R, &overflow));
   if (overflow) {
@@ -3310,8 +3415,10 @@ static int rebomos_lists_stale(mdp_ctx *c, bool &stale)
 
 // Which pair loops the lane-group kernels of this compute take, and whether their waves are counted (once per compute).
 // MDP_CENTRE_FULL=0 keeps every wave on the general loops (tests, A/B); MDP_CENTRE_COUNT=1 has every wave that holds a
-// centre add one to the context's pair of counts (mdp_rebomos_centre_paths) -- off by default: the kernels then get a null
-// pointer and the step pays one scalar test per wave.  (Read per compute: the tests switch both within one process.)
+// centre add one to the context's pair of counts (mdp_rebomos_centre_paths), and every wave on the full-group path the
+// trips of its first pair loop that took the blend to a third (mdp_rebomos_centre_blend_trips) -- off by default: the
+// kernels then get a null pointer and the step pays one scalar test per wave.  (Read per compute: the tests switch both
+// within one process.)
 static int centre_path_mode(mdp_ctx *c)
 {
   const char *fe = getenv("MDP_CENTRE_FULL");
@@ -3320,8 +3427,8 @@ static int centre_path_mode(mdp_ctx *c)
   c->centre_cnt_now = nullptr;
   if (ce && atoi(ce) != 0) {
     if (!c->centre_paths.p) {
-      MDP_HIP(c, c->centre_paths.reserve(2));
-      MDP_HIP(c, hipMemsetAsync(c->centre_paths.p, 0, sizeof(unsigned long long) * 2, c->stream));
+      MDP_HIP(c, c->centre_paths.reserve(3));
+      MDP_HIP(c, hipMemsetAsync(c->centre_paths.p, 0, sizeof(unsigned long long) * 3, c->stream));
     }
     c->centre_cnt_now = c->centre_paths.p;
   }
@@ -3340,10 +3447,11 @@ static void launch_centre(mdp_ctx *c, int kg, int eflag, int vflag, int part)
     const int *list = part == 2 ? c->class_merged.p + c->merged_base[k] : c->class_list.p + (size_t) k * c->nall;
     constexpr int per_block = CentreCfg<G>::WPB * CentreCfg<G>::GPW;
     const int grid = (n + per_block - 1) / per_block;
-    rebo_centre_kernel<G><<<grid, 64 * CentreCfg<G>::WPB, 0, c->stream>>>(c->rebomos, list, n, c->nlocal,
-                                                       c->xq.p, c->cand_off.p, c->cand.p, c->pk_cand.p + c->pk_base[k],
-                                                       c->amask.p, c->fnbr.p, c->fown.p, c->acc.p, c->ovf.p, eflag, vflag,
-                                                       elem, c->centre_full_now ? 1 : 0, c->centre_cnt_now);
+    const auto kernel = c->centre_cnt_now ? rebo_centre_kernel<G, false, true> : rebo_centre_kernel<G>;
+    kernel<<<grid, 64 * CentreCfg<G>::WPB, 0, c->stream>>>(c->rebomos, list, n, c->nlocal, c->xq.p, c->cand_off.p, c->cand.p,
+                                                           c->pk_cand.p + c->pk_base[k], c->amask.p, c->fnbr.p, c->fown.p,
+                                                           c->acc.p, c->ovf.p, eflag, vflag, elem,
+                                                           c->centre_full_now ? 1 : 0, c->centre_cnt_now);
   }
 }
 
@@ -3382,7 +3490,8 @@ static void launch_centre3(mdp_ctx *c, int eflag, int vflag, int part)
     long long est = 4 * (long long) *h_cnt + 2 * per_block;
     if (est > n) est = n;
     const int grid = (int) ((est + per_block - 1) / per_block);
-    rebo_centre_kernel<8, true><<<grid, 64 * CentreCfg<8>::WPB, 0, c->stream>>>(
+    const auto kernel8 = c->centre_cnt_now ? rebo_centre_kernel<8, true, true> : rebo_centre_kernel<8, true>;
+    kernel8<<<grid, 64 * CentreCfg<8>::WPB, 0, c->stream>>>(
         c->rebomos, list, 0, c->nlocal, c->xq.p, c->cand_off.p, c->cand.p, h_cnt, c->amask.p, c->fnbr.p, c->fown.p,
         c->acc.p, c->ovf.p, eflag, vflag, elem, c->centre_full_now ? 1 : 0, c->centre_cnt_now);
   }

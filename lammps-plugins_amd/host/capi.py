@@ -129,7 +129,7 @@ EXPORTS = [
     "mdp_coord_setup", "mdp_coord_read", "mdp_coord_info", "mdp_coord_off",
     "mdp_centro_setup", "mdp_centro_read", "mdp_centro_info", "mdp_centro_off",
     "mdp_profile_setup", "mdp_profile_range", "mdp_profile_exponent", "mdp_profile_sums", "mdp_profile_info", "mdp_profile_off",
-    "mdp_rebomos_centre_paths",
+    "mdp_rebomos_centre_paths", "mdp_rebomos_centre_blend_trips",
     "mdp_heatflux_sums", "mdp_md_download_vatom",
     "mdp_heat_setup", "mdp_heat_run", "mdp_heat_state", "mdp_heat_off",
     "mdp_indent_setup", "mdp_indent_run", "mdp_indent_state", "mdp_indent_off",
@@ -520,6 +520,13 @@ class Context:
         out = (C.c_longlong * 2)()
         self._ck(self.L.mdp_rebomos_centre_paths(self.h, out, C.c_int(1 if reset else 0)))
         return int(out[0]), int(out[1])
+
+    def rebomos_centre_blend_trips(self, reset=True):
+        """trips of the first pair loop that took the G(cos) blend, over the waves on the full-group path of the computes
+        run with MDP_CENTRE_COUNT=1 since its last reset (see mdpair_hip.h)"""
+        out = C.c_longlong(0)
+        self._ck(self.L.mdp_rebomos_centre_blend_trips(self.h, C.byref(out), C.c_int(1 if reset else 0)))
+        return int(out.value)
 
     def md_neighbor_stats(self):
         out = (C.c_longlong * 8)()
