@@ -2,7 +2,7 @@
 // A read bins ALL atoms of the brick (owned and ghost) as a read of rdf.hip does (mdp_measure_bin, measure_bin.hip) at cell
 // width >= half the largest outer radius, into buffers that belong to MdpAdf.  Then one WAVE per centre at a time, four
 // centres in flight per workgroup:
-//   phase A  the 64 lanes stride over the candidates of the centre's 5 x 5 stencil runs, laid end to end, test rsq against
+//   phase A  the 64 lanes stride over the candidates of the centre's 5 x 5 stencil runs, laid end to end (measure_walk.h), test rsq against
 //            the largest outer radius, form the candidate's j- and k-masks (the triples whose type range and shell it fits, among those the
 //            centre belongs to) and compact the hits by ballot and prefix count into the wave's short list in LDS
 //            {dx, dy, dz, 1 / r, jmask, kmask}, MDP_ADF_MAXNEIGH entries;
@@ -12,7 +12,7 @@
 // counters go to the global 64-bit histogram with device-scope integer atomics.  No floating-point atomic anywhere: two
 // reads of one state agree exactly, and the sum over the bricks of a decomposition is the one-brick histogram wherever
 // the last bit of an ordinate does not decide the bin.
-#include "mdp_common.h"
+#include "measure_walk.h"
 
 namespace {
 
@@ -34,33 +34,11 @@ constexpr int kAdfTabWords = (int) (sizeof(AdfTab) / sizeof(unsigned));
 struct AdfList {
   double dx[MDP_ADF_MAXNEIGH], dy[MDP_ADF_MAXNEIGH], dz[MDP_ADF_MAXNEIGH], inv[MDP_ADF_MAXNEIGH];
   unsigned jm[MDP_ADF_MAXNEIGH], km[MDP_ADF_MAXNEIGH];
-  int excl[32], base[32]; // the 25 runs of the centre's stencil: candidates in front of run k, and its first place
+  MdpWalkRuns runs; // the 25 runs of the centre's stencil
 };
 // LDS of a workgroup, in bytes: the table, four lists ((40 B x 128 + 256 B) x 4 = 21 KB), the histogram, the counters: 55.6 KB at
 // the most (8 192 counters), 23 KB with a small histogram
 size_t adf_lds_bytes(const int nhist) { return sizeof(AdfTab) + kAdfWaves * sizeof(AdfList) + sizeof(unsigned) * ((size_t) nhist + kAdfCntWords); }
-
-// adds the workgroup's non-zero LDS counters to the global ones and clears them; every lane of the workgroup calls it
-__device__ __forceinline__ void adf_flush(unsigned *lds, const int n, unsigned long long *__restrict__ glob)
-{
-  __syncthreads();
-  for (int k = threadIdx.x; k < n; k += 256) {
-    const unsigned v = lds[k];
-    if (v) {
-      atomicAdd(glob + k, (unsigned long long) v);
-      lds[k] = 0u;
-    }
-  }
-  __syncthreads();
-}
-
-// the lanes of one wave have written LDS that other lanes of the same wave read next (or the reverse)
-__device__ __forceinline__ void adf_wave_sync()
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Workgroups stride over the chunks of 256 places; within a chunk wave w takes the 64 places from 64 w, centre by centre.
 // cosine: the ordinate is c over [-1, 1], scale = nbin / 2; otherwise the angle over [0, pi] (degrees and radians share their
@@ -81,7 +59,6 @@ __global__ __launch_bounds__(256) void adf_hist_kernel(const Grid g, const int n
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   AdfList &L = lists[wave];
-  const unsigned long long below = (1ull << lane) - 1ull;
   int done = 0;
   for (int chunk = blockIdx.x; chunk < nchunk; chunk += gridDim.x) {
     const int pi = chunk * 256 + threadIdx.x;
@@ -95,80 +72,40 @@ __global__ __launch_bounds__(256) void adf_hist_kernel(const Grid g, const int n
     const unsigned cm = (ci & kBinOwned) && ti ? tab->imask[ti] : 0u; // the triples this owned member is a centre of
     for (unsigned m = cm; m; m &= m - 1) atomicAdd(lc + (__ffs(m) - 1), 1u);
     for (unsigned long long todo = __ballot(cm != 0u); todo; todo &= todo - 1) {
-      const int src = __ffsll((long long) todo) - 1, pc = chunk * 256 + wave * 64 + src;
-      double4 xc;
-      xc.x = __shfl(xi.x, src, 64);
-      xc.y = __shfl(xi.y, src, 64);
-      xc.z = __shfl(xi.z, src, 64);
-      const unsigned ccm = (unsigned) __shfl((int) cm, src, 64);
-      int cx, cy, cz;
-      mdp_bin_cell_index(g, xc, cx, cy, cz);
-      const int x0 = max(cx - 2, 0), x1 = min(cx + 2, g.n[0] - 1);
-      // the 25 runs of the stencil (cells along x are contiguous in the sort), one per lane: their bounds in one round trip
-      // and not in 25, then a prefix sum of their lengths, so that the lanes stride over the runs laid end to end
-      int len = 0, pb = 0;
-      if (lane < 25) {
-        const int z = cz - 2 + lane / 5, y = cy - 2 + lane % 5;
-        if (z >= 0 && z < g.n[2] && y >= 0 && y < g.n[1]) {
-          const int c0 = g.n[0] * (y + g.n[1] * z);
-          pb = cell_start[c0 + x0];
-          len = cell_start[c0 + x1 + 1] - pb;
-        }
-      }
-      int incl = len;
-#pragma unroll
-      for (int o = 1; o < 32; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-      }
-      if (lane < 32) {
-        L.excl[lane] = incl - len;
-        L.base[lane] = pb;
-      }
-      const int total = __shfl(incl, 31, 64); // (lanes 25 .. 31 add nothing)
-      adf_wave_sync();
+      const MdpWalkCentre ctr = mdp_walk_centre(todo, xi, (int) cm, chunk * 256 + wave * 64);
+      const unsigned ccm = (unsigned) ctr.v;
+      const int total = mdp_walk_runs(g, cell_start, ctr.x, lane, L.runs);
       int n = 0; // hits so far: the same in every lane
       for (int q0 = 0; q0 < total; q0 += 64) {
-        const int q = q0 + lane;
+        MdpWalkCand c;
+        const bool has = mdp_walk_cand(L.runs, q0 + lane, total, rec, ctr.x, c);
         bool hit = false;
-        double dx = 0.0, dy = 0.0, dz = 0.0, rsq = 1.0;
         unsigned jm = 0u, km = 0u;
-        if (q < total) {
-          int r = 0; // the last run that starts at or before q: the one that holds it (an empty run starts where the next does)
-#pragma unroll
-          for (int k = 1; k < 25; k++) r += q >= L.excl[k];
-          const int p = L.base[r] + (q - L.excl[r]);
-          const double4 xj = rec[p];
-          dx = xj.x - xc.x;
-          dy = xj.y - xc.y;
-          dz = xj.z - xc.z;
-          rsq = dx * dx + dy * dy + dz * dz;
-          const int tj = __double2loint(xj.w) & (kBinTypes - 1);
-          hit = tj && rsq < rmaxsq && p != pc;
+        if (has) {
+          const int tj = __double2loint(c.xj.w) & (kBinTypes - 1);
+          hit = tj && c.rsq < rmaxsq && c.p != ctr.p;
           if (hit) {
             for (unsigned m = tab->jmask[tj] & ccm; m; m &= m - 1) {
               const int k = __ffs(m) - 1;
-              if (rsq >= tab->rsq[0][k] && rsq < tab->rsq[1][k]) jm |= 1u << k;
+              if (c.rsq >= tab->rsq[0][k] && c.rsq < tab->rsq[1][k]) jm |= 1u << k;
             }
             for (unsigned m = tab->kmask[tj] & ccm; m; m &= m - 1) {
               const int k = __ffs(m) - 1;
-              if (rsq >= tab->rsq[2][k] && rsq < tab->rsq[3][k]) km |= 1u << k;
+              if (c.rsq >= tab->rsq[2][k] && c.rsq < tab->rsq[3][k]) km |= 1u << k;
             }
           }
         }
-        const unsigned long long bal = __ballot(hit);
-        const int at = n + __popcll(bal & below);
+        const int at = mdp_walk_slot(hit, lane, n);
         if (hit && at < MDP_ADF_MAXNEIGH) {
-          L.dx[at] = dx;
-          L.dy[at] = dy;
-          L.dz[at] = dz;
-          L.inv[at] = 1.0 / sqrt(rsq);
+          L.dx[at] = c.dx;
+          L.dy[at] = c.dy;
+          L.dz[at] = c.dz;
+          L.inv[at] = 1.0 / sqrt(c.rsq);
           L.jm[at] = jm;
           L.km[at] = km;
         }
-        n += __popcll(bal);
       }
-      adf_wave_sync();
+      mdp_wave_sync();
       if (n > MDP_ADF_MAXNEIGH) {
         if (lane == 0) atomicAdd(lc + MDP_ADF_MAXTRIPLE, 1u);
       } else if (n >= 2) {
@@ -192,14 +129,14 @@ __global__ __launch_bounds__(256) void adf_hist_kernel(const Grid g, const int n
           }
         }
       }
-      adf_wave_sync(); // the list is free for the wave's next centre
+      mdp_wave_sync(); // the list is free for the wave's next centre
     }
     if (++done == kAdfChunksPerFlush) {
-      adf_flush(lh, nhist, hist);
+      mdp_lds_flush(lh, nhist, hist);
       done = 0;
     }
   }
-  adf_flush(lh, nhist, hist);
+  mdp_lds_flush(lh, nhist, hist);
   for (int k = threadIdx.x; k < kAdfCntWords - 1; k += 256)
     if (lc[k]) atomicAdd(cnt + k, (unsigned long long) lc[k]);
 }
@@ -230,20 +167,12 @@ int mdp_adf_setup(mdp_ctx *c, int nbin, int ordinate, int ntriple, const int *il
     return mdp_fail(c, MDP_EINVAL, "mdp_adf_setup: ntriple must be 1 .. %d, not %d", MDP_ADF_MAXTRIPLE, ntriple);
   if (!ilo || !ihi || !jlo || !jhi || !klo || !khi) return mdp_fail(c, MDP_EINVAL, "mdp_adf_setup: no type ranges");
   if (!rjin || !rjout || !rkin || !rkout) return mdp_fail(c, MDP_EINVAL, "mdp_adf_setup: no shell radii");
-  // (1 .. 15 atom types: see mdp_rdf_setup)
-  const int ntypes = c->ntypes > 0 ? c->ntypes : c->cfg.ntypes;
-  if (ntypes < 1 || ntypes >= kBinTypes)
-    return mdp_fail(c, MDP_EINVAL, "mdp_adf_setup: %d atom types (the type code of a record holds 1 .. %d)", ntypes, kBinTypes - 1);
-  const double limit = c->dd.cutghost - c->cfg.skin;
+  int ntypes;
+  MDP_TRY(mdp_measure_ntypes(c, "mdp_adf_setup", ntypes));
   double rmax = 0.0;
   for (int m = 0; m < ntriple; m++) {
     const int r[6] = {ilo[m], ihi[m], jlo[m], jhi[m], klo[m], khi[m]};
-    for (int k = 0; k < 6; k++)
-      if (r[k] < 1 || r[k] > ntypes)
-        return mdp_fail(c, MDP_EINVAL, "mdp_adf_setup: triple %d: type %d outside 1 .. %d", m + 1, r[k], ntypes);
-    if (ilo[m] > ihi[m] || jlo[m] > jhi[m] || klo[m] > khi[m])
-      return mdp_fail(c, MDP_EINVAL, "mdp_adf_setup: triple %d: a type range with lo > hi (%d .. %d, %d .. %d, %d .. %d)", m + 1, ilo[m],
-                      ihi[m], jlo[m], jhi[m], klo[m], khi[m]);
+    MDP_TRY(mdp_measure_type_ranges(c, "mdp_adf_setup", "triple", m + 1, ntypes, 6, r));
     const double s[4] = {rjin[m], rjout[m], rkin[m], rkout[m]};
     for (int k = 0; k < 4; k++)
       if (!(s[k] >= 0.0) || !std::isfinite(s[k]))
@@ -251,20 +180,19 @@ int mdp_adf_setup(mdp_ctx *c, int nbin, int ordinate, int ntriple, const int *il
     for (int k = 0; k < 4; k += 2)
       if (!(s[k] < s[k + 1]))
         return mdp_fail(c, MDP_EINVAL, "mdp_adf_setup: triple %d: the inner radius %g is not below the outer radius %g", m + 1, s[k], s[k + 1]);
-    // the ghost shell and the skin: the argument of mdp_rdf_setup, for the outer radius of either shell
+    // the ghost shell and the skin, for the outer radius of either shell
+    char what[40];
+    snprintf(what, sizeof what, "triple %d: outer radius", m + 1);
     for (int k = 1; k < 4; k += 2) {
-      if (s[k] > limit * (1.0 + 1e-12))
-        return mdp_fail(c, MDP_EINVAL, "mdp_adf_setup: triple %d: outer radius %.15g + skin %g exceeds the ghost shell %.15g: only neighbours "
-                                       "within %.15g are guaranteed present between two reneighbourings",
-                        m + 1, s[k], c->cfg.skin, c->dd.cutghost, limit);
+      MDP_TRY(mdp_measure_shell_setup(c, "mdp_adf_setup", what, "neighbours", s[k]));
       if (s[k] > rmax) rmax = s[k];
     }
   }
   if ((long long) nbin * ntriple > MDP_ADF_MAXCOUNTERS)
     return mdp_fail(c, MDP_EINVAL, "mdp_adf_setup: nbin x ntriple = %lld counters, the histogram in LDS holds %d", (long long) nbin * ntriple,
                     MDP_ADF_MAXCOUNTERS);
-  if (member_by_tag && ntag < 1) return mdp_fail(c, MDP_EINVAL, "mdp_adf_setup: a member table with ntag = %d", ntag);
   MdpAdf &h = c->adf;
+  MDP_TRY(mdp_measure_member(c, "mdp_adf_setup", ntag, member_by_tag, h.member, h.ntag));
   AdfTab tab = {};
   for (int m = 0; m < ntriple; m++) {
     tab.rsq[0][m] = rjin[m] * rjin[m];
@@ -278,12 +206,6 @@ int mdp_adf_setup(mdp_ctx *c, int nbin, int ordinate, int ntriple, const int *il
   MDP_HIP(c, h.tab.reserve(sizeof(AdfTab) / sizeof(double)));
   MDP_HIP(c, h.out.reserve((size_t) nbin * ntriple + kAdfCntWords));
   MDP_TRY(mdp_write_small(c, h.tab.p, &tab, sizeof tab));
-  if (member_by_tag) {
-    MDP_HIP(c, h.member.reserve((size_t) ntag + 8));
-    MDP_TRY(mdp_host_upload(c, h.member.p, member_by_tag, (size_t) ntag));
-    MDP_HIP(c, hipStreamSynchronize(c->stream)); // the caller's array may change after return
-  }
-  h.ntag = member_by_tag ? ntag : 0;
   h.nbin = nbin;
   h.ntriple = ntriple;
   h.ntypes = ntypes;
@@ -299,40 +221,26 @@ int mdp_adf_counts(mdp_ctx *c, long long *hist, long long *icount)
   if (!hist || !icount) return MDP_EINVAL;
   MdpAdf &h = c->adf;
   if (!h.on) return mdp_fail(c, MDP_ESTATE, "mdp_adf_setup not called");
-  const double limit = c->dd.cutghost - c->cfg.skin;
-  if (h.rmax > limit * (1.0 + 1e-12))
-    return mdp_fail(c, MDP_EINVAL, "mdp_adf_counts: the largest outer radius %.15g of mdp_adf_setup exceeds the current ghost shell less the skin, %.15g",
-                    h.rmax, limit);
-  // positions are read; a deferred final half is completed as every blocking read completes it (mdp_rdf_counts)
-  MDP_TRY(mdp_md_flush_final(c));
   hipStream_t st = c->stream;
   const int nall = c->nall, nhist = h.nbin * h.ntriple, nout = nhist + kAdfCntWords;
   unsigned long long *d_hist = h.out.p, *d_cnt = h.out.p + nhist;
-  MDP_HIP(c, hipMemsetAsync(h.out.p, 0, sizeof(unsigned long long) * nout, st));
+  MDP_TRY(mdp_hist_open(c, "mdp_adf_counts", "largest outer radius", h.rmax, "mdp_adf_setup", h.out.p, nout));
   if (nall > 0 && c->nlocal > 0) {
     Grid g;
     MDP_TRY(mdp_measure_bin(c, h.bin, h.rmax, h.ntypes, h.ntag, h.member.p, d_cnt + kAdfCntWords - 1, g));
     const int nchunk = nblk(nall);
-    if (c->num_cu <= 0) {
-      int n = 0;
-      MDP_HIP(c, hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device));
-      c->num_cu = n > 0 ? n : 256;
-    }
     const size_t lds = adf_lds_bytes(nhist);
-    // as many resident workgroups as the LDS of a CU (160 KB) holds of them, 8 at the most (32 waves per CU)
-    const int fit = (int) ((size_t) 144 * 1024 / lds), per_cu = fit < 1 ? 1 : (fit > 8 ? 8 : fit), cus = c->num_cu;
-    const int grid = mdp_measure_grid(nchunk, per_cu * cus);
+    int resident;
+    MDP_TRY(mdp_measure_resident(c, lds, resident));
+    const int grid = mdp_measure_grid(nchunk, resident);
     const int cosine = h.ordinate == MDP_ADF_COSINE;
     adf_hist_kernel<<<grid, 256, lds, st>>>(g, nall, nchunk, h.nbin, h.ntriple, cosine, cosine ? 0.5 * h.nbin : h.nbin / M_PI,
                                             h.rmax * h.rmax, h.bin.rec.p, h.bin.cell_start.p, (const unsigned *) h.tab.p, d_hist, d_cnt);
     MDP_HIP(c, hipGetLastError());
   }
-  std::vector<unsigned long long> host((size_t) nout);
-  MDP_TRY(mdp_read_one(c, h.out.p, sizeof(unsigned long long) * nout, host.data()));
+  std::vector<unsigned long long> host;
+  MDP_TRY(mdp_hist_download(c, "mdp_adf_counts", "mdp_adf_setup", h.out.p, nout, h.ntag, host));
   const unsigned long long *cnt = host.data() + nhist;
-  if (cnt[kAdfCntWords - 1])
-    return mdp_fail(c, MDP_EINVAL, "mdp_adf_counts: %lld owned or ghost atoms have a tag outside 1 .. %d, the member table of mdp_adf_setup",
-                    (long long) cnt[kAdfCntWords - 1], h.ntag);
   if (cnt[MDP_ADF_MAXTRIPLE])
     return mdp_fail(c, MDP_EINVAL, "mdp_adf_counts: %lld centres have more than %d neighbours inside the largest outer radius %g, the short "
                                    "list of a wave: use smaller outer radii",

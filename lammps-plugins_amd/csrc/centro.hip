@@ -4,7 +4,7 @@
 // WAVE per centre at a time, four centres in flight per workgroup:
 //   gather  the 64 lanes stride over the candidates of the centre's 5 x 5 stencil runs, laid end to end, test rsq < cutoff^2 and
 //           compact the hits by ballot and prefix count into the wave's short list in LDS {dx, dy, dz, rsq}, MDP_ADF_MAXNEIGH
-//           entries, in the order of their places (a second copy of adf.hip's phase A; DESIGN.md 4.44 on giving them one);
+//           entries, in the order of their places (the walk of measure_walk.h, which adf.hip and coord.hip share);
 //   select  the rank of an entry is the number of entries with a smaller (rsq, list index) -- the list is in place order, so a tie
 //           breaks on the place and never on lane timing --; the entries of rank < N go to slot [rank] of a second list;
 //   sum     the lanes stride over the N (N - 1) / 2 pairs a < b of that list and write |R_a + R_b|^2 to LDS; the rank of a
@@ -12,7 +12,7 @@
 //           adds them in ascending order.
 // A centre with more hits than the short list holds is counted, not truncated, and the read is refused; one with fewer than N
 // gets 0 and is counted.  No floating-point atomic anywhere: two reads of one state agree bit for bit.
-#include "mdp_common.h"
+#include "measure_walk.h"
 
 namespace {
 
@@ -23,21 +23,13 @@ using Grid = MdpGrid;
 // the fixed part of a wave's LDS: the centre's neighbours inside the cutoff and the 25 runs of its stencil
 struct CentroList {
   double dx[MDP_ADF_MAXNEIGH], dy[MDP_ADF_MAXNEIGH], dz[MDP_ADF_MAXNEIGH], rsq[MDP_ADF_MAXNEIGH];
-  int excl[32], base[32];
+  MdpWalkRuns runs;
 };
 // ... and the part that grows with N, in doubles: the N nearest {x, y, z}, the pair values, the N / 2 smallest of them
 __host__ __device__ constexpr int centro_npair(const int nnn) { return nnn * (nnn - 1) / 2; }
 __host__ __device__ constexpr int centro_wave_doubles(const int nnn) { return 3 * nnn + centro_npair(nnn) + nnn / 2; }
 // LDS of a workgroup in bytes: 4.3 KB + 8 (3 N + N (N - 1) / 2 + N / 2) per wave: 20 KB at N = 12, 88 KB at N = 64
 size_t centro_lds_bytes(const int nnn) { return kCentroWaves * (sizeof(CentroList) + sizeof(double) * centro_wave_doubles(nnn)); }
-
-// the lanes of one wave have written LDS that other lanes of the same wave read next (or the reverse)
-__device__ __forceinline__ void centro_wave_sync()
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Workgroups stride over the chunks of 256 places; within a chunk wave w takes the 64 places from 64 w, centre by centre.
 // perm: place -> atom (an owned atom's index is its entry of val and of mask).  cnt[0]: centres over the cap, cnt[1]: centres
@@ -54,7 +46,6 @@ __global__ __launch_bounds__(256) void centro_kernel(const Grid g, const int nal
   CentroList &L = ((CentroList *) centro_lds)[wave];
   double *sx = (double *) (centro_lds + kCentroWaves * sizeof(CentroList)) + (size_t) wave * centro_wave_doubles(nnn);
   double *sy = sx + nnn, *sz = sy + nnn, *pv = sz + nnn, *sm = pv + npair;
-  const unsigned long long below = (1ull << lane) - 1ull;
   for (int chunk = blockIdx.x; chunk < nchunk; chunk += gridDim.x) {
     const int pi = chunk * 256 + threadIdx.x;
     int ai = -1; // the entry of a centre; -1: a ghost, an atom outside the group, a place past the end
@@ -67,66 +58,23 @@ __global__ __launch_bounds__(256) void centro_kernel(const Grid g, const int nal
       }
     }
     for (unsigned long long todo = __ballot(ai >= 0); todo; todo &= todo - 1) {
-      const int src = __ffsll((long long) todo) - 1, pc = chunk * 256 + wave * 64 + src;
-      double4 xc;
-      xc.x = __shfl(xi.x, src, 64);
-      xc.y = __shfl(xi.y, src, 64);
-      xc.z = __shfl(xi.z, src, 64);
-      const int ac = __shfl(ai, src, 64);
-      int cx, cy, cz;
-      mdp_bin_cell_index(g, xc, cx, cy, cz);
-      const int x0 = max(cx - 2, 0), x1 = min(cx + 2, g.n[0] - 1);
-      // ---- gather: the 25 runs of the stencil (cells along x are contiguous in the sort), one per lane, a prefix sum of their
-      // lengths, and the lanes stride over the runs laid end to end
-      int len = 0, pb = 0;
-      if (lane < 25) {
-        const int z = cz - 2 + lane / 5, y = cy - 2 + lane % 5;
-        if (z >= 0 && z < g.n[2] && y >= 0 && y < g.n[1]) {
-          const int c0 = g.n[0] * (y + g.n[1] * z);
-          pb = cell_start[c0 + x0];
-          len = cell_start[c0 + x1 + 1] - pb;
-        }
-      }
-      int incl = len;
-#pragma unroll
-      for (int o = 1; o < 32; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-      }
-      if (lane < 32) {
-        L.excl[lane] = incl - len;
-        L.base[lane] = pb;
-      }
-      const int total = __shfl(incl, 31, 64); // (lanes 25 .. 31 add nothing)
-      centro_wave_sync();
+      const MdpWalkCentre ctr = mdp_walk_centre(todo, xi, ai, chunk * 256 + wave * 64);
+      // ---- gather
+      const int total = mdp_walk_runs(g, cell_start, ctr.x, lane, L.runs);
       int n = 0; // hits so far: the same in every lane
       for (int q0 = 0; q0 < total; q0 += 64) {
-        const int q = q0 + lane;
-        bool hit = false;
-        double dx = 0.0, dy = 0.0, dz = 0.0, rsq = 0.0;
-        if (q < total) {
-          int r = 0; // the last run that starts at or before q: the one that holds it
-#pragma unroll
-          for (int k = 1; k < 25; k++) r += q >= L.excl[k];
-          const int p = L.base[r] + (q - L.excl[r]);
-          const double4 xj = rec[p];
-          dx = xj.x - xc.x;
-          dy = xj.y - xc.y;
-          dz = xj.z - xc.z;
-          rsq = dx * dx + dy * dy + dz * dz;
-          hit = rsq < cutsq && p != pc;
-        }
-        const unsigned long long bal = __ballot(hit);
-        const int at = n + __popcll(bal & below);
+        MdpWalkCand c;
+        const bool has = mdp_walk_cand(L.runs, q0 + lane, total, rec, ctr.x, c);
+        const bool hit = has && c.rsq < cutsq && c.p != ctr.p;
+        const int at = mdp_walk_slot(hit, lane, n);
         if (hit && at < MDP_ADF_MAXNEIGH) {
-          L.dx[at] = dx;
-          L.dy[at] = dy;
-          L.dz[at] = dz;
-          L.rsq[at] = rsq;
+          L.dx[at] = c.dx;
+          L.dy[at] = c.dy;
+          L.dz[at] = c.dz;
+          L.rsq[at] = c.rsq;
         }
-        n += __popcll(bal);
       }
-      centro_wave_sync();
+      mdp_wave_sync();
       if (n > MDP_ADF_MAXNEIGH) {
         if (lane == 0) atomicAdd(cnt, 1ull);
       } else if (n < nnn) {
@@ -146,7 +94,7 @@ __global__ __launch_bounds__(256) void centro_kernel(const Grid g, const int nal
             sz[rank] = L.dz[e];
           }
         }
-        centro_wave_sync();
+        mdp_wave_sync();
         // ---- sum: pair q is (a, b), a < b, row by row: q = a (nnn - 1) - a (a - 1) / 2 + (b - a - 1)
         for (int q = lane; q < npair; q += 64) {
           int a = 0, rem = q;
@@ -158,7 +106,7 @@ __global__ __launch_bounds__(256) void centro_kernel(const Grid g, const int nal
           const double ux = sx[a] + sx[b], uy = sy[a] + sy[b], uz = sz[a] + sz[b];
           pv[q] = ux * ux + uy * uy + uz * uz;
         }
-        centro_wave_sync();
+        mdp_wave_sync();
         for (int q = lane; q < npair; q += 64) {
           const double v = pv[q];
           int rank = 0;
@@ -168,14 +116,14 @@ __global__ __launch_bounds__(256) void centro_kernel(const Grid g, const int nal
           }
           if (rank < half) sm[rank] = v;
         }
-        centro_wave_sync();
+        mdp_wave_sync();
         if (lane == 0) {
           double s = 0.0;
           for (int k = 0; k < half; k++) s += sm[k];
-          val[ac] = s;
+          val[ctr.v] = s;
         }
       }
-      centro_wave_sync(); // the lists are free for the wave's next centre
+      mdp_wave_sync(); // the lists are free for the wave's next centre
     }
   }
 }
@@ -201,15 +149,12 @@ int mdp_centro_setup(mdp_ctx *c, int nnn, double cutoff, int groupbit)
     return mdp_fail(c, MDP_EINVAL, "mdp_centro_setup: the number of neighbours must be 2 .. %d (the pair values of a wave in LDS), not %d",
                     MDP_CENTRO_MAXN, nnn);
   if (nnn % 2) return mdp_fail(c, MDP_EINVAL, "mdp_centro_setup: the number of neighbours must be even, not %d", nnn);
-  const int ntypes = c->ntypes > 0 ? c->ntypes : c->cfg.ntypes;
-  const double limit = c->dd.cutghost - c->cfg.skin;
+  int ntypes;
+  MDP_TRY(mdp_measure_ntypes(c, "mdp_centro_setup", ntypes));
   if (!std::isfinite(cutoff)) return mdp_fail(c, MDP_EINVAL, "mdp_centro_setup: cutoff %g", cutoff);
-  if (!(cutoff > 0.0)) cutoff = limit; // the default: all that the ghost shell guarantees
+  if (!(cutoff > 0.0)) cutoff = mdp_measure_shell_limit(c); // the default: all that the ghost shell guarantees
   if (!(cutoff > 0.0)) return mdp_fail(c, MDP_EINVAL, "mdp_centro_setup: the ghost shell %.15g less the skin %g leaves no cutoff", c->dd.cutghost, c->cfg.skin);
-  if (cutoff > limit * (1.0 + 1e-12))
-    return mdp_fail(c, MDP_EINVAL, "mdp_centro_setup: cutoff %.15g + skin %g exceeds the ghost shell %.15g: only partners within %.15g are "
-                                   "guaranteed present between two reneighbourings",
-                    cutoff, c->cfg.skin, c->dd.cutghost, limit);
+  MDP_TRY(mdp_measure_shell_setup(c, "mdp_centro_setup", "cutoff", "partners", cutoff));
   MDP_TRY(mdp_require_group_mask(c, "mdp_centro_setup", groupbit, false));
   MdpCentro &h = c->centro;
   MDP_HIP(c, h.cnt.reserve(4));
@@ -238,15 +183,10 @@ int mdp_centro_read(mdp_ctx *c, int *tag, double *values)
     Grid g;
     MDP_TRY(mdp_measure_bin(c, h.bin, h.cutoff, h.ntypes, 0, nullptr, h.cnt.p + 2, g)); // (no member table: cnt[2] is never written)
     const int nchunk = nblk(nall);
-    if (c->num_cu <= 0) {
-      int n = 0;
-      MDP_HIP(c, hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device));
-      c->num_cu = n > 0 ? n : 256;
-    }
     const size_t lds = centro_lds_bytes(h.nnn);
-    // as many resident workgroups as the LDS of a CU (160 KB) holds of them, 8 at the most (32 waves per CU)
-    const int fit = (int) ((size_t) 144 * 1024 / lds), per_cu = fit < 1 ? 1 : (fit > 8 ? 8 : fit);
-    const int grid = mdp_measure_grid(nchunk, per_cu * c->num_cu);
+    int resident;
+    MDP_TRY(mdp_measure_resident(c, lds, resident));
+    const int grid = mdp_measure_grid(nchunk, resident);
     MDP_TRY(mdp_launch(c, centro_kernel, grid, 256, lds, st, g, nall, nchunk, h.nnn, h.gbit, h.cutoff * h.cutoff, h.bin.rec.p,
                        h.bin.cell_start.p, h.bin.perm.p, h.gbit ? c->mask.p : nullptr, h.val.p, h.cnt.p));
   }

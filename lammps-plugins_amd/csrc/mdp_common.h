@@ -1279,6 +1279,31 @@ int mdp_measure_require(mdp_ctx *c, const char *who);
 // the sums of profile.hip): min(nchunk, resident), and no more than the test hook MDP_MEASURE_GRID when that is a positive
 // integer (read at every read; the sums are integers and the range is a maximum, so any value reads the same)
 int mdp_measure_grid(int nchunk, int resident);
+// ... and `resident` for a kernel of 256 lanes with lds_bytes of LDS per workgroup: as many workgroups as the LDS of a CU (160 KB)
+// holds of them, 8 at the most (32 waves per CU), on every CU
+int mdp_measure_resident(mdp_ctx *c, size_t lds_bytes, int &resident);
+// What the setups of the neighbour measurements (rdf, adf, coord, centro) share.  The atom types of the run, 1 .. 15:
+int mdp_measure_ntypes(mdp_ctx *c, const char *who, int &ntypes);
+// the n type bounds lo, hi, lo, hi, ... of the index-th (from 1) `noun` (pair, triple, column) lie in 1 .. ntypes, and no lo > hi
+int mdp_measure_type_ranges(mdp_ctx *c, const char *who, const char *noun, int index, int ntypes, int n, const int *lohi);
+// The ghost shell is as of the last reneighbouring and cutghost wide; two atoms have since approached by up to half a skin
+// each, so only the partners within cutghost - skin are all present: mdp_measure_shell_limit (an allowance of 1e-12 for a
+// limit the caller formed as cutghost - skin is the checks').  At setup: `what` (a cutoff, an outer radius) of r reaches `whom`
+// (pairs, neighbours, partners) inside it; at a read: the `what` of `setup` (its name for the message) still does.
+inline double mdp_measure_shell_limit(const mdp_ctx *c) { return c->dd.cutghost - c->cfg.skin; }
+int mdp_measure_shell_setup(mdp_ctx *c, const char *who, const char *what, const char *whom, double r);
+int mdp_measure_shell_read(mdp_ctx *c, const char *who, const char *what, double r, const char *setup);
+// the member table of a histogram setup by tag - 1 (or nullptr: everyone) goes to the device, and the caller's array is free
+// on return; ntag_kept: ntag, or 0 without a table
+int mdp_measure_member(mdp_ctx *c, const char *who, int ntag, const unsigned char *member_by_tag, DevBuf<unsigned char> &d_member,
+                       int &ntag_kept);
+// A histogram read (rdf.hip, adf.hip) before it bins: `what` of the setup still lies inside the ghost shell, a final half the
+// host deferred is completed as every blocking read completes it (positions are read; the integrate kernel of the step is
+// ahead on the stream), and the nout words of out are zeroed ...
+int mdp_hist_open(mdp_ctx *c, const char *who, const char *what, double r, const char *setup, unsigned long long *d_out, int nout);
+// ... and after its kernel: the words on the host; the last one counts the atoms whose tag the member table does not hold
+int mdp_hist_download(mdp_ctx *c, const char *who, const char *setup, const unsigned long long *d_out, int nout, int ntag,
+                      std::vector<unsigned long long> &host);
 void mdp_profile_release(mdp_ctx *c); // frees what profile.hip holds
 void mdp_heatflux_release(mdp_ctx *c); // frees what heatflux.hip holds
 // the end of an mdp_{msd,rdf,profile}_setup: the measurement is on, under a serial that is new in this process (one
@@ -1317,9 +1342,7 @@ inline int mdp_require_group_mask(mdp_ctx *c, const char *who, const int gbit, c
 // shell, and the mask covers the atoms; then the final half a host deferred is completed, as before every blocking read.
 inline int mdp_peratom_open(mdp_ctx *c, const char *who, const double cutoff, const int gbit)
 {
-  const double limit = c->dd.cutghost - c->cfg.skin;
-  if (cutoff > limit * (1.0 + 1e-12))
-    return mdp_fail(c, MDP_EINVAL, "%s: the cutoff %.15g of the setup exceeds the current ghost shell less the skin, %.15g", who, cutoff, limit);
+  MDP_TRY(mdp_measure_shell_read(c, who, "cutoff", cutoff, "the setup"));
   MDP_TRY(mdp_require_group_mask(c, who, gbit, true));
   return mdp_md_flush_final(c);
 }

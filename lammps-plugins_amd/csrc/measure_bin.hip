@@ -1,4 +1,5 @@
-// measure_bin.hip -- the binning stage of the pair and angle measurements (rdf.hip, adf.hip): ALL atoms of the brick, owned and
+// measure_bin.hip -- the binning stage of the neighbour measurements (rdf.hip, adf.hip, coord.hip, centro.hip) and what their
+// setups and reads share on the host (mdp_measure_*, mdp_hist_*): ALL atoms of the brick, owned and
 // ghost, on a grid of the measurement's own at cell width >= cutoff / 2, into the buffers of an MdpBinning.  The list
 // builders' grid, permutation, cell starts and cell-ordered positions (mdp_bin_atoms) are neither read nor written, so a
 // read changes nothing a later step or list build sees.  What comes out: cell_start and the cell-ordered records
@@ -109,6 +110,90 @@ int mdp_measure_grid(const int nchunk, const int resident)
   const int knob = e ? atoi(e) : 0;
   if (knob > 0 && knob < grid) grid = knob;
   return grid;
+}
+
+int mdp_measure_resident(mdp_ctx *c, const size_t lds_bytes, int &resident)
+{
+  if (c->num_cu <= 0) {
+    int n = 0;
+    MDP_HIP(c, hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device));
+    c->num_cu = n > 0 ? n : 256;
+  }
+  const int fit = (int) ((size_t) 144 * 1024 / lds_bytes);
+  resident = (fit < 1 ? 1 : (fit > 8 ? 8 : fit)) * c->num_cu;
+  return MDP_OK;
+}
+
+int mdp_measure_ntypes(mdp_ctx *c, const char *who, int &ntypes)
+{
+  // mdp_md_setup admits 1 .. 15 atom types, which is what the 4-bit type code of a record and the 16-entry mask tables hold:
+  // the check below cannot fire on a context that passed mdp_measure_require, and stands for a later change of that limit
+  ntypes = c->ntypes > 0 ? c->ntypes : c->cfg.ntypes;
+  if (ntypes < 1 || ntypes >= kBinTypes)
+    return mdp_fail(c, MDP_EINVAL, "%s: %d atom types (the type code of a record holds 1 .. %d)", who, ntypes, kBinTypes - 1);
+  return MDP_OK;
+}
+
+int mdp_measure_type_ranges(mdp_ctx *c, const char *who, const char *noun, const int index, const int ntypes, const int n, const int *lohi)
+{
+  for (int k = 0; k < n; k++)
+    if (lohi[k] < 1 || lohi[k] > ntypes)
+      return mdp_fail(c, MDP_EINVAL, "%s: %s %d: type %d outside 1 .. %d", who, noun, index, lohi[k], ntypes);
+  for (int k = 0; k < n; k += 2)
+    if (lohi[k] > lohi[k + 1])
+      return mdp_fail(c, MDP_EINVAL, "%s: %s %d: a type range with lo > hi (%d .. %d)", who, noun, index, lohi[k], lohi[k + 1]);
+  return MDP_OK;
+}
+
+int mdp_measure_shell_setup(mdp_ctx *c, const char *who, const char *what, const char *whom, const double r)
+{
+  const double limit = mdp_measure_shell_limit(c);
+  if (r > limit * (1.0 + 1e-12))
+    return mdp_fail(c, MDP_EINVAL, "%s: %s %.15g + skin %g exceeds the ghost shell %.15g: only %s within %.15g are guaranteed present "
+                                   "between two reneighbourings",
+                    who, what, r, c->cfg.skin, c->dd.cutghost, whom, limit);
+  return MDP_OK;
+}
+
+int mdp_measure_shell_read(mdp_ctx *c, const char *who, const char *what, const double r, const char *setup)
+{
+  const double limit = mdp_measure_shell_limit(c);
+  if (r > limit * (1.0 + 1e-12))
+    return mdp_fail(c, MDP_EINVAL, "%s: the %s %.15g of %s exceeds the current ghost shell less the skin, %.15g", who, what, r, setup, limit);
+  return MDP_OK;
+}
+
+int mdp_measure_member(mdp_ctx *c, const char *who, const int ntag, const unsigned char *member_by_tag, DevBuf<unsigned char> &d_member,
+                       int &ntag_kept)
+{
+  if (member_by_tag) {
+    if (ntag < 1) return mdp_fail(c, MDP_EINVAL, "%s: a member table with ntag = %d", who, ntag);
+    MDP_HIP(c, d_member.reserve((size_t) ntag + 8));
+    MDP_TRY(mdp_host_upload(c, d_member.p, member_by_tag, (size_t) ntag));
+    MDP_HIP(c, hipStreamSynchronize(c->stream)); // the caller's array may change after return
+  }
+  ntag_kept = member_by_tag ? ntag : 0;
+  return MDP_OK;
+}
+
+int mdp_hist_open(mdp_ctx *c, const char *who, const char *what, const double r, const char *setup, unsigned long long *d_out,
+                  const int nout)
+{
+  MDP_TRY(mdp_measure_shell_read(c, who, what, r, setup));
+  MDP_TRY(mdp_md_flush_final(c));
+  MDP_HIP(c, hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * nout, c->stream));
+  return MDP_OK;
+}
+
+int mdp_hist_download(mdp_ctx *c, const char *who, const char *setup, const unsigned long long *d_out, const int nout, const int ntag,
+                      std::vector<unsigned long long> &host)
+{
+  host.resize((size_t) nout);
+  MDP_TRY(mdp_read_one(c, d_out, sizeof(unsigned long long) * nout, host.data()));
+  if (host[nout - 1])
+    return mdp_fail(c, MDP_EINVAL, "%s: %lld owned or ghost atoms have a tag outside 1 .. %d, the member table of %s", who,
+                    (long long) host[nout - 1], ntag, setup);
+  return MDP_OK;
 }
 
 int mdp_measure_bin(mdp_ctx *c, MdpBinning &b, const double cutoff, const int ntypes, const int ntag,

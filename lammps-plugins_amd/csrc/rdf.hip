@@ -8,7 +8,7 @@
 // reads.  Hits go into a per-workgroup LDS histogram of 32-bit counters (LDS integer atomics); its non-zero counters
 // are added to the global 64-bit histogram with device-scope integer atomics.  No floating-point atomic anywhere:
 // two reads of one state agree exactly, and the sum over the bricks of a decomposition is the one-brick histogram.
-#include "mdp_common.h"
+#include "measure_walk.h"
 
 namespace {
 
@@ -20,20 +20,6 @@ constexpr int kRdfChunksPerFlush = 64; // a workgroup flushes its 32-bit counter
 constexpr int kRdfCntWords = 3 * MDP_RDF_MAXPAIR + 1; // icount, jcount, dup per column, then the atoms whose tag has no entry
 
 using Grid = MdpGrid;
-
-// adds the workgroup's non-zero LDS counters to the global ones and clears them; every lane of the workgroup calls it
-__device__ __forceinline__ void rdf_flush(unsigned *lds, const int n, unsigned long long *__restrict__ glob)
-{
-  __syncthreads();
-  for (int k = threadIdx.x; k < n; k += 256) {
-    const unsigned v = lds[k];
-    if (v) {
-      atomicAdd(glob + k, (unsigned long long) v);
-      lds[k] = 0u;
-    }
-  }
-  __syncthreads();
-}
 
 // Dynamic LDS, in 32-bit words: [0, nhist) the histogram [column][bin], [nhist, nhist + kRdfCntWords) icount / jcount /
 // dup, then the kRdfTabWords mask table.  Workgroups stride over the chunks of 256 places, so that a workgroup's
@@ -92,11 +78,11 @@ __global__ __launch_bounds__(256) void rdf_hist_kernel(const Grid g, const int n
       }
     }
     if (++done == kRdfChunksPerFlush) {
-      rdf_flush(lh, nhist, hist);
+      mdp_lds_flush(lh, nhist, hist);
       done = 0;
     }
   }
-  rdf_flush(lh, nhist, hist);
+  mdp_lds_flush(lh, nhist, hist);
   for (int k = threadIdx.x; k < kRdfCntWords - 1; k += 256)
     if (lc[k]) atomicAdd(cnt + k, (unsigned long long) lc[k]);
 }
@@ -123,33 +109,19 @@ int mdp_rdf_setup(mdp_ctx *c, int nbin, double cutoff, int npair, const int *ilo
   if (npair < 1 || npair > MDP_RDF_MAXPAIR)
     return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: npair must be 1 .. %d, not %d", MDP_RDF_MAXPAIR, npair);
   if (!ilo || !ihi || !jlo || !jhi) return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: no type ranges");
-  // mdp_md_setup admits 1 .. 15 atom types, which is what the 4-bit type code of a record and the 16 x 16 mask table hold:
-  // the check below cannot fire on a context that passed mdp_measure_require, and stands for a later change of that limit
-  const int ntypes = c->ntypes > 0 ? c->ntypes : c->cfg.ntypes;
-  if (ntypes < 1 || ntypes >= kRdfTypes)
-    return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: %d atom types (the type code of a record holds 1 .. %d)", ntypes, kRdfTypes - 1);
+  int ntypes;
+  MDP_TRY(mdp_measure_ntypes(c, "mdp_rdf_setup", ntypes));
   for (int m = 0; m < npair; m++) {
     const int r[4] = {ilo[m], ihi[m], jlo[m], jhi[m]};
-    for (int k = 0; k < 4; k++)
-      if (r[k] < 1 || r[k] > ntypes)
-        return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: pair %d: type %d outside 1 .. %d", m + 1, r[k], ntypes);
-    if (ilo[m] > ihi[m] || jlo[m] > jhi[m])
-      return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: pair %d: a type range with lo > hi (%d .. %d, %d .. %d)", m + 1, ilo[m], ihi[m],
-                      jlo[m], jhi[m]);
+    MDP_TRY(mdp_measure_type_ranges(c, "mdp_rdf_setup", "pair", m + 1, ntypes, 4, r));
   }
   if (!(cutoff > 0.0)) return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: cutoff must be > 0, not %g", cutoff);
-  // The ghost shell is as of the last reneighbouring and cutghost wide; two atoms have since approached by up to half a
-  // skin each, so only the pairs within cutghost - skin are all present.  (1e-12: a limit the caller formed as cutghost - skin)
-  const double limit = c->dd.cutghost - c->cfg.skin;
-  if (cutoff > limit * (1.0 + 1e-12))
-    return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: cutoff %.15g + skin %g exceeds the ghost shell %.15g: only pairs within %.15g are "
-                                   "guaranteed present between two reneighbourings",
-                    cutoff, c->cfg.skin, c->dd.cutghost, limit);
+  MDP_TRY(mdp_measure_shell_setup(c, "mdp_rdf_setup", "cutoff", "pairs", cutoff));
   if ((long long) nbin * npair > MDP_RDF_MAXCOUNTERS)
     return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: nbin x npair = %lld counters, the histogram in LDS holds %d", (long long) nbin * npair,
                     MDP_RDF_MAXCOUNTERS);
-  if (member_by_tag && ntag < 1) return mdp_fail(c, MDP_EINVAL, "mdp_rdf_setup: a member table with ntag = %d", ntag);
   MdpRdf &h = c->rdf;
+  MDP_TRY(mdp_measure_member(c, "mdp_rdf_setup", ntag, member_by_tag, h.member, h.ntag));
   int tab[kRdfTabWords] = {};
   for (int m = 0; m < npair; m++) {
     for (int ti = ilo[m]; ti <= ihi[m]; ti++) {
@@ -161,12 +133,6 @@ int mdp_rdf_setup(mdp_ctx *c, int nbin, double cutoff, int npair, const int *ilo
   MDP_HIP(c, h.tab.reserve(kRdfTabWords));
   MDP_HIP(c, h.out.reserve((size_t) nbin * npair + kRdfCntWords));
   MDP_TRY(mdp_write_small(c, h.tab.p, tab, sizeof tab));
-  if (member_by_tag) {
-    MDP_HIP(c, h.member.reserve((size_t) ntag + 8));
-    MDP_TRY(mdp_host_upload(c, h.member.p, member_by_tag, (size_t) ntag));
-    MDP_HIP(c, hipStreamSynchronize(c->stream)); // the caller's array may change after return
-  }
-  h.ntag = member_by_tag ? ntag : 0;
   h.nbin = nbin;
   h.npair = npair;
   h.ntypes = ntypes;
@@ -181,42 +147,27 @@ int mdp_rdf_counts(mdp_ctx *c, long long *hist, long long *icount, long long *jc
   if (!hist || !icount || !jcount || !dup) return MDP_EINVAL;
   MdpRdf &h = c->rdf;
   if (!h.on) return mdp_fail(c, MDP_ESTATE, "mdp_rdf_setup not called");
-  const double limit = c->dd.cutghost - c->cfg.skin;
-  if (h.cutoff > limit * (1.0 + 1e-12))
-    return mdp_fail(c, MDP_EINVAL, "mdp_rdf_counts: the cutoff %.15g of mdp_rdf_setup exceeds the current ghost shell less the skin, %.15g",
-                    h.cutoff, limit);
-  // Positions are read: the integrate kernel of the step is ahead of this read on the stream.  A final half the host
-  // deferred touches v only; it is completed as every blocking read completes it, so that the host sees one state.
-  MDP_TRY(mdp_md_flush_final(c));
   hipStream_t st = c->stream;
   const int nall = c->nall, nhist = h.nbin * h.npair, nout = nhist + kRdfCntWords;
   unsigned long long *d_hist = h.out.p, *d_cnt = h.out.p + nhist;
-  MDP_HIP(c, hipMemsetAsync(h.out.p, 0, sizeof(unsigned long long) * nout, st));
+  MDP_TRY(mdp_hist_open(c, "mdp_rdf_counts", "cutoff", h.cutoff, "mdp_rdf_setup", h.out.p, nout));
   if (nall > 0 && c->nlocal > 0) {
     Grid g;
     MDP_TRY(mdp_measure_bin(c, h.bin, h.cutoff, h.ntypes, h.ntag, h.member.p, d_cnt + kRdfCntWords - 1, g));
     const int nchunk = nblk(nall);
-    if (c->num_cu <= 0) {
-      int n = 0;
-      MDP_HIP(c, hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device));
-      c->num_cu = n > 0 ? n : 256;
-    }
     const size_t lds = sizeof(unsigned) * ((size_t) nhist + kRdfCntWords + kRdfTabWords);
-    // as many resident workgroups as the LDS of a CU (160 KB) holds histograms, 8 at the most (32 waves per CU)
-    const int fit = (int) ((size_t) 144 * 1024 / lds), per_cu = fit < 1 ? 1 : (fit > 8 ? 8 : fit), cus = c->num_cu;
-    const int grid = mdp_measure_grid(nchunk, per_cu * cus);
+    int resident;
+    MDP_TRY(mdp_measure_resident(c, lds, resident));
+    const int grid = mdp_measure_grid(nchunk, resident);
     // every pair with (int) (r nbin / cutoff) < nbin has rsq below this; the bin index decides
     const double cutsq_hi = h.cutoff * h.cutoff * (1.0 + 1e-9);
     rdf_hist_kernel<<<grid, 256, lds, st>>>(g, nall, nchunk, h.nbin, h.npair, (double) h.nbin / h.cutoff, cutsq_hi, h.bin.rec.p,
                                             h.bin.cell_start.p, h.tab.p, d_hist, d_cnt);
     MDP_HIP(c, hipGetLastError());
   }
-  std::vector<unsigned long long> host((size_t) nout);
-  MDP_TRY(mdp_read_one(c, h.out.p, sizeof(unsigned long long) * nout, host.data()));
+  std::vector<unsigned long long> host;
+  MDP_TRY(mdp_hist_download(c, "mdp_rdf_counts", "mdp_rdf_setup", h.out.p, nout, h.ntag, host));
   const unsigned long long *cnt = host.data() + nhist;
-  if (cnt[kRdfCntWords - 1])
-    return mdp_fail(c, MDP_EINVAL, "mdp_rdf_counts: %lld owned or ghost atoms have a tag outside 1 .. %d, the member table of mdp_rdf_setup",
-                    (long long) cnt[kRdfCntWords - 1], h.ntag);
   for (int k = 0; k < nhist; k++) hist[k] = (long long) host[k];
   for (int m = 0; m < h.npair; m++) {
     icount[m] = (long long) cnt[m];

@@ -346,6 +346,40 @@ def test_a_non_periodic_dimension(capsys):
         ctx.close()
 
 
+@pytest.mark.parametrize("style,rc,nnn", [("aeam", None, 12), ("aeam", 3.5, 12), ("rebomos", 2.8, 6)])
+def test_three_reads_of_one_walk(style, rc, nnn):
+    """coord, adf and centro at one radius on one thermal state, no group and no member table: the three kernels walk the same
+    candidates (csrc/measure_walk.h) and test the same rsq against the same rc^2, so with c_i = coord's count of atom i over all
+    types, adf's `* * *` histogram over both shells [0, rc) holds sum_i c_i (c_i - 1) ordered angles of nlocal centres, and centro
+    counts exactly the atoms with c_i < N short, which read 0 -- all exact, in integers.  Only a pair within one rounding of rc
+    could tell the kernels apart, which a thermal state rules out (the module's docstring).  The alloy at the ghost shell's
+    limit (None) has 78 partners, two trips of the walk per centre, at 3.5 A one; MoS2 at 2.8 A has empty runs across the van
+    der Waals gap."""
+    s, v0 = _system(style, 300.0)
+    ctx, st, skin, cutghost, map_ = _context(style)
+    try:
+        d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0)
+        rc = cutghost - skin if rc is None else rc
+        ntypes = int(s.type.max())
+        d.coord(rc, [(1, ntypes)])
+        d.adf(45, [((1, ntypes), (1, ntypes), (1, ntypes), 0.0, rc, 0.0, rc)])
+        d.centro(nnn, rc)
+        d.compute(0, 0)
+        for _ in range(10):
+            d.step(0, 0, rebuild="auto")
+        tags, val = d.coord_read()
+        c = [int(v) for v in val[:, 0]]
+        assert np.array_equal(val[:, 0], c) and len(c) == d.nlocal == s.n and max(c) >= nnn
+        hist, icount = d.adf_read()
+        assert int(hist.sum()) == sum(k * (k - 1) for k in c) and icount.tolist() == [s.n]
+        ztags, z = d.centro_read()
+        short = val[:, 0] < nnn
+        assert np.array_equal(ztags, tags) and ctx.centro_info()["few"] == int(short.sum())
+        assert np.all(z[short] == 0.0) and np.all(z[~short] >= 0.0)
+    finally:
+        ctx.close()
+
+
 # ---- bricks: the drift case of tests/test_gpu_rdf_mdp.py, 2 304 MoS2 atoms, reneighbourings forced every 5 steps
 def _mig_run(s, v0, world, member):
     def rank_fn(r, make_tr):
