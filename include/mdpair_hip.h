@@ -902,6 +902,37 @@ int mdp_centro_read(mdp_ctx *ctx, int *tag /* [nlocal] */, double *values /* [nl
 int mdp_centro_info(mdp_ctx *ctx, long long out[4]);
 int mdp_centro_off(mdp_ctx *ctx);
 
+/* ---- per-atom structure: the common neighbour analysis (LAMMPS compute cna/atom Rc) ---------------------------------------
+ * For a resident context with mdp_dd_setup (MDP_ESTATE otherwise), next to the measurements above and with their centres,
+ * partners (here: neighbours) and binning.  For a centre with n neighbours inside the cutoff:
+ *   n not 12 and not 14       pattern 5 (other), whatever n is: a centre with more than MDP_CNA_MAXNEAR neighbours is never
+ *                             truncated into another pattern, and is counted (mdp_cna_info)
+ *   every neighbour j         common = the neighbours k of the centre with |r_k - r_j|^2 < cutoff^2, the difference formed from
+ *                             the two displacements from the centre; ncommon = |common|, nbonds = the pairs of common closer than
+ *                             the cutoff, maxbond / minbond = the most / fewest such bonds one member of common takes part in
+ *                             (0 / 8 for an empty set, as LAMMPS initialises them)
+ *   n = 12                    12 x (4,2,1,1): 1 (fcc); 6 x (4,2,1,1) and 6 x (4,2,2,0): 2 (hcp); 12 x (5,5,2,2): 4 (icosahedral);
+ *                             anything else 5
+ *   n = 14                    6 x (4,4,2,2) and 8 x (6,6,2,2): 3 (bcc); anything else 5
+ * Unlike LAMMPS the answer is formed from the current positions and not from a neighbour list of some age, it does not depend
+ * on whether a neighbour is owned or a ghost, and cutoff + skin <= cutghost suffices (LAMMPS asks 2 Rc <= cutforce + skin).
+ *   mdp_cna_setup:   MDP_EINVAL: cutoff <= 0 or not finite, cutoff + skin > the cutghost of mdp_dd_setup (see mdp_rdf_setup).
+ *                    A second call replaces the first.
+ *   mdp_cna_read:    blocking.  tag[i] and values[i] of this rank's nlocal owned atoms in the context's owned order: the pattern
+ *                    1 .. 5 as a double, 0 for an atom outside the group.  Integers throughout: two reads of one state agree
+ *                    bit for bit.  The refusals as those of mdp_coord_read.
+ *   mdp_cna_counts:  out[p] = this rank's group atoms with pattern p = 0 .. 5 at the last read (out[0] is always 0), counted on
+ *                    the device in 64-bit integers; all 0 before the first read.  MDP_ESTATE without a setup.
+ *   mdp_cna_info:    out = {a measurement is on, 0, the centres with more than MDP_CNA_MAXNEAR neighbours at the last read, its
+ *                    serial}.
+ *   mdp_cna_off:     releases the buffers. */
+#define MDP_CNA_MAXNEAR 16
+int mdp_cna_setup(mdp_ctx *ctx, double cutoff, int groupbit);
+int mdp_cna_read(mdp_ctx *ctx, int *tag /* [nlocal] */, double *values /* [nlocal] */);
+int mdp_cna_counts(mdp_ctx *ctx, long long out[6]);
+int mdp_cna_info(mdp_ctx *ctx, long long out[4]);
+int mdp_cna_off(mdp_ctx *ctx);
+
 /* ---- binned mass, momentum and kinetic energy: temperature, density and flow profiles (LAMMPS compute chunk/atom bin/1d|2d|3d
  * with compute temp/chunk, vcm/chunk, fix ave/chunk), in integers ----------------------------------------------------------
  * For a resident context with mdp_dd_setup (MDP_ESTATE otherwise).  Nothing a step, a list build, msd or rdf reads is touched.

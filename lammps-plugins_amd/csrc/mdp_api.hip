@@ -925,6 +925,7 @@ int mdp_destroy(mdp_ctx *c)
   mdp_adf_release(c);
   mdp_coord_release(c);
   mdp_centro_release(c);
+  mdp_cna_release(c);
   mdp_profile_release(c);
   mdp_heatflux_release(c);
   if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);

@@ -508,6 +508,16 @@ struct MdpCentro : MdpMeasure {
   DevBuf<double> val;              // [nlocal]
   DevBuf<unsigned long long> cnt;  // centres over the cap of the short list, centres with fewer than nnn partners, (unused) bad tags
 };
+// the per-atom common neighbour analysis (cna.hip): the same, with the census of a read
+struct MdpCna : MdpMeasure {
+  int ntypes = 0, gbit = 0;
+  long long counts[6] = {0, 0, 0, 0, 0, 0}; // group atoms of pattern 0 .. 5 at the last read
+  long long over = 0;              // centres with more than MDP_CNA_MAXNEAR neighbours at the last read
+  double cutoff = 0.0;
+  MdpBinning bin;
+  DevBuf<double> val;              // [nlocal]
+  DevBuf<unsigned long long> cnt;  // centres per pattern [6], centres over the cap of the short list, (unused) bad tags
+};
 // binned sums of m, m v and m v^2 (profile.hip): the bins and the table of a read; nothing here is read by a step, a list build,
 // msd or rdf
 struct MdpProfile : MdpMeasure {
@@ -930,6 +940,7 @@ struct mdp_ctx {
   MdpAdf adf;                      // bond-angle histograms of the current positions (mdp_adf_setup)
   MdpCoord coord;                  // per-atom coordination numbers of the current positions (mdp_coord_setup)
   MdpCentro centro;                // per-atom centro-symmetry parameters of the current positions (mdp_centro_setup)
+  MdpCna cna;                      // per-atom common neighbour analysis of the current positions (mdp_cna_setup)
   MdpProfile profile;              // binned mass, momentum and kinetic energy of the current atoms (mdp_profile_setup)
   MdpHeatflux heatflux;            // partial sums of a heat-current read (mdp_heatflux_sums)
   // eflag / vflag of the last FINISHED compute while its per-atom tallies (eatom, vatom) still describe the owned atoms in
@@ -1267,6 +1278,7 @@ void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds
 void mdp_adf_release(mdp_ctx *c); // frees what adf.hip holds
 void mdp_coord_release(mdp_ctx *c); // frees what coord.hip holds
 void mdp_centro_release(mdp_ctx *c); // frees what centro.hip holds
+void mdp_cna_release(mdp_ctx *c); // frees what cna.hip holds
 // measure_bin.hip, queued on the stream: a grid with cells >= cutoff / 2 over the padded hull of the brick (stencil: 2 cells each
 // way), every owned and ghost atom sorted into it, b.cell_start and the cell-ordered records b.rec = {x, y, z, code} with
 // code = (member ? type : 0) | (owned ? kBinOwned : 0).  member: by tag - 1 over 1 .. ntag, or nullptr for every atom; an atom

@@ -96,6 +96,8 @@ ADF_ORDINATES = dict(degree=ADF_DEGREE, radian=ADF_RADIAN, cosine=ADF_COSINE)
 ADF_MAXNEIGH = 128           # MDP_ADF_MAXNEIGH: the short list of a wave, of adf.hip and centro.hip
 COORD_MAXCOL, CENTRO_MAXN = 32, 64               # MDP_COORD_MAXCOL, MDP_CENTRO_MAXN
 CENTRO_LATTICE = dict(fcc=12, bcc=8)
+CNA_MAXNEAR = 16             # MDP_CNA_MAXNEAR: the short list of a wave of cna.hip
+CNA_FCC, CNA_HCP, CNA_BCC, CNA_ICO, CNA_OTHER = 1, 2, 3, 4, 5
 
 EXPORTS = [
     "mdp_abi_version", "mdp_device_count", "mdp_create", "mdp_destroy", "mdp_last_error", "mdp_set_stream",
@@ -128,6 +130,7 @@ EXPORTS = [
     "mdp_adf_setup", "mdp_adf_counts", "mdp_adf_info", "mdp_adf_off",
     "mdp_coord_setup", "mdp_coord_read", "mdp_coord_info", "mdp_coord_off",
     "mdp_centro_setup", "mdp_centro_read", "mdp_centro_info", "mdp_centro_off",
+    "mdp_cna_setup", "mdp_cna_read", "mdp_cna_counts", "mdp_cna_info", "mdp_cna_off",
     "mdp_profile_setup", "mdp_profile_range", "mdp_profile_exponent", "mdp_profile_sums", "mdp_profile_info", "mdp_profile_off",
     "mdp_rebomos_centre_paths", "mdp_rebomos_centre_blend_trips",
     "mdp_heatflux_sums", "mdp_md_download_vatom",
@@ -1074,6 +1077,35 @@ class Context:
 
     def centro_off(self):
         self._ck(self.L.mdp_centro_off(self.h))
+
+    # ---------------- per-atom structure: the common neighbour analysis (csrc/cna.hip)
+    def cna_setup(self, cutoff, group_bit=0):
+        """starts a measurement over the neighbours inside cutoff (0.8536 a for fcc and hcp, 1.207 a for bcc); group_bit as in
+        coord_setup"""
+        self._ck(self.L.mdp_cna_setup(self.h, C.c_double(float(cutoff)), C.c_int(int(group_bit))))
+
+    def cna_read(self, nlocal):
+        """this rank's (tags[nlocal], values[nlocal]) in the owned order of md_download: 1 fcc, 2 hcp, 3 bcc, 4 icosahedral,
+        5 other, 0 outside the group"""
+        tags = np.zeros(max(nlocal, 1), dtype=np.int32)
+        vals = np.zeros(max(nlocal, 1))
+        self._ck(self.L.mdp_cna_read(self.h, _ip(tags), _dp(vals)))
+        return tags[:nlocal], vals[:nlocal]
+
+    def cna_counts(self):
+        """int64[6]: this rank's group atoms with pattern 0 .. 5 at the last read, counted on the device"""
+        out = (C.c_longlong * 6)()
+        self._ck(self.L.mdp_cna_counts(self.h, out))
+        return np.array(list(out), dtype=np.int64)
+
+    def cna_info(self):
+        """whether a measurement is on, the centres with more than CNA_MAXNEAR neighbours at the last read, and its serial"""
+        out = (C.c_longlong * 4)()
+        self._ck(self.L.mdp_cna_info(self.h, out))
+        return dict(on=bool(out[0]), over=int(out[2]), serial=int(out[3]))
+
+    def cna_off(self):
+        self._ck(self.L.mdp_cna_off(self.h))
 
     # ---------------- binned mass, momentum and kinetic energy (csrc/profile.hip)
     def profile_setup(self, dims, nbins, group_bit=0):

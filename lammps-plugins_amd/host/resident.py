@@ -662,6 +662,20 @@ class DeviceDomain:
     def centro_off(self):
         self.ctx.centro_off()
 
+    def cna(self, cutoff, group_bit=0):
+        """starts the per-atom common neighbour analysis (LAMMPS compute cna/atom cutoff): for every owned atom of the group the
+        pattern of its neighbours inside cutoff (at most cutghost - skin): 1 fcc, 2 hcp, 3 bcc, 4 icosahedral, 5 other"""
+        self.ctx.cna_setup(cutoff, group_bit)
+
+    def cna_read(self):
+        """(tags[nlocal], values[nlocal]) of this rank's owned atoms; ctx.cna_counts(): this rank's census of the read,
+        ctx.cna_info()["over"]: the atoms with more than 16 neighbours"""
+        self.flush()
+        return self.ctx.cna_read(self.nlocal)
+
+    def cna_off(self):
+        self.ctx.cna_off()
+
     # ------------------------------------------------------------------ temperature, density and flow profiles
     def profile(self, dims, nbins, group_bit=0):
         """starts a binned measurement of mass, momentum and kinetic energy (LAMMPS compute chunk/atom bin/1d|2d|3d with
