@@ -47,6 +47,7 @@ SUITE = {
     "heat": [(2, 12)],
     "measure": [(4, 16)],
     "peratom": [(27, 16)],
+    "structure": [(1018, 16)],
 }
 
 
@@ -1399,14 +1400,16 @@ def measure_nall_bound(box, n, cutghost, nonperiodic=(0, 0, 0)):
     return int(np.ceil(1.05 * n * f))
 
 
-def measure_grid_grows(spec):
-    """no GPU: the first trial grid of the rdf read of a one-brick case, cells cutoff / 2 wide, exceeds bin_grid's cap"""
-    if spec["ranks"] != 1 or spec["cutoff"] is None:
+def measure_grid_grows(spec, cutoff=None):
+    """no GPU: the first trial grid of a read of a one-brick case (cutoff None: the rdf read of a `measure` case), cells
+    cutoff / 2 wide, exceeds bin_grid's cap"""
+    cutoff = spec["cutoff"] if cutoff is None else cutoff
+    if spec["ranks"] != 1 or cutoff is None:
         return False
     box = _cell_start(spec).box
     cutghost = MSR_LIMIT[spec["style"]] + MSR_SKIN[spec["style"]]
     nall = measure_nall_bound(box, spec["n"], cutghost, spec["nonperiodic"])
-    return measure_bin_grid(measure_domain_lens(box, cutghost), spec["cutoff"], nall)[1] > 0
+    return measure_bin_grid(measure_domain_lens(box, cutghost), cutoff, nall)[1] > 0
 
 
 def _msr_range(rng, nt):
@@ -1489,6 +1492,13 @@ def _msr_random(rng):
 def _cell_start(spec):
     """no GPU, no oracle: the start system of a case, jittered (placeholder masses; run_measure sets the potential's)"""
     sd = spec["seed"]
+    if spec.get("cell"):      # a constructed cell of tests/cnaref.py (the structure net): one type of the alloy's, its own jitter
+        import cnaref
+        x, h = {"stack": lambda: cnaref.stack_cell(spec["amp"], sd)[:2], "bcc": lambda: cnaref.bcc_cell(sigma=spec["amp"], seed=sd),
+                "icosahedron": lambda: cnaref.icosahedron_cell(spec["amp"], sd)}[spec["cell"]]()
+        box = S.Box(np.zeros(3), np.asarray(h).diagonal().copy(), np.zeros(3))
+        assert len(x) == spec["n"]
+        return S.System(box, S.wrap(box, x), np.ones(len(x), dtype=np.int32), np.arange(1, len(x) + 1, dtype=np.int32), np.array([0.0, 27.0, 28.0]))
     if spec["style"] == "rebomos":
         s = S.replicate(S.rebomos_bulk_cell(), spec["size"])
     else:
@@ -1564,6 +1574,19 @@ def measure_start_counts(spec, s, member, pairs):
     return entries, angles
 
 
+def _cell_rcap(s, pairs, limit):
+    """no draws: the radius inside which no centre has more than MSR_NEIGH neighbours at the start, at most the limit: from the
+    distance of every centre's neighbour number MSR_NEIGH + 1, if it lies inside the limit"""
+    pi, pj, pr = pairs
+    order = np.lexsort((pr, pi))
+    start = np.searchsorted(pi[order], np.arange(s.n + 1))
+    full = np.nonzero(np.diff(start) > MSR_NEIGH)[0]
+    rcap = 0.999 * limit
+    if len(full):
+        rcap = min(rcap, 0.999 * float(pr[order][start[full] + MSR_NEIGH].min()))
+    return rcap
+
+
 def _msr_fit(spec):
     """no draws: turns the triples' fractions into radii -- between the first shell and the radius inside which no centre
     has more than MSR_NEIGH neighbours at the start (at most the limit) --, and, for a case that is not about a tiny group,
@@ -1573,14 +1596,7 @@ def _msr_fit(spec):
     first, limit = MSR_FIRST[style], MSR_LIMIT[style]
     s = _cell_start(spec)
     pairs = _msr_pairs(s, spec, limit)
-    pi, pj, pr = pairs
-    # the distance of every centre's neighbour number MSR_NEIGH + 1, if it lies inside the limit
-    order = np.lexsort((pr, pi))
-    start = np.searchsorted(pi[order], np.arange(s.n + 1))
-    full = np.nonzero(np.diff(start) > MSR_NEIGH)[0]
-    rcap = 0.999 * limit
-    if len(full):
-        rcap = min(rcap, 0.999 * float(pr[order][start[full] + MSR_NEIGH].min()))
+    rcap = _cell_rcap(s, pairs, limit)
     rows = []
     for tr in spec["triples"]:
         row = list(tr[:6])
@@ -1631,6 +1647,52 @@ def _cell_velocities(spec, s):
     return v0, max(1, int(0.3 * MSR_SKIN[spec["style"]] / (_cell_speed_cap(spec, s, v0) * 0.001)))
 
 
+def _cell_potential(spec, s):
+    """the potential of a case: sets the masses of s; (the alloy's tables or None, cutghost).  cutghost - skin is MSR_LIMIT"""
+    import aeam_five
+    from lammps_plugins_amd.host import capi
+    R = _res()
+    style, skin = spec["style"], MSR_SKIN[spec["style"]]
+    tabs = None
+    if style == "rebomos":
+        cutghost = 3.0 * R["rp"].rcmax[0][0] + skin
+    else:
+        af, tabs = R["af"], R["tabs"]
+        if spec["relabel"] is not None:
+            nmet, nang = spec["relabel"]
+            if "tmp" not in R:
+                R["tmp"] = tempfile.mkdtemp()
+            path = os.path.join(R["tmp"], f"p{nmet}_{nang}.aeam")
+            if not os.path.exists(path):
+                aeam_five.write_relabelled_file(path, R["pot_aeam"], [0] * nmet + [1] * nang, ["M%d" % i for i in range(nmet)] + ["X%d" % i for i in range(nang)])
+            if path not in R:     # (kept for the process: the tables point into the file object, which frees them when it goes)
+                af = capi.AeamFile(path)
+                R[path] = (af, af.build())
+            af, tabs = R[path]
+        s.mass[1:] = af.mass[:spec["ntypes"]]
+        cutghost = float(af.cut_table(tabs).max()) + skin
+    assert abs(cutghost - skin - MSR_LIMIT[style]) < 1e-9, cutghost - skin
+    return tabs, cutghost
+
+
+def _cell_domain(spec, s, tabs, cutghost, v0, make_tr):
+    """(context, DeviceDomain) of one rank of a case; the caller closes the context"""
+    from lammps_plugins_amd.host import capi, resident
+    ctx = capi.Context(0)
+    try:
+        if spec["style"] == "rebomos":
+            ctx.rebomos_set_params(_res()["rp"])
+            st, map_ = capi.STYLE_REBOMOS, [0, 0, 1]
+        else:
+            ctx.aeam_set_tables(tabs)
+            st, map_ = capi.STYLE_AEAM, None
+        return ctx, resident.DeviceDomain(ctx, st, s, cutghost, MSR_SKIN[spec["style"]], map_, v0=v0,
+                                          transport=make_tr(ctx) if spec["ranks"] > 1 else None, nonperiodic=spec["nonperiodic"])
+    except BaseException:
+        ctx.close()
+        raise
+
+
 def measure_references(spec, x, types, h, member):
     """rdfref.counts and adfref.counts of the case on positions and types by tag"""
     import adfref
@@ -1647,29 +1709,11 @@ def _msr_outside(hist, ref):
 
 
 def run_measure(spec):
-    import aeam_five
-    from lammps_plugins_amd.host import capi, resident
-    R = _res()
-    style, skin = spec["style"], MSR_SKIN[spec["style"]]
+    from lammps_plugins_amd.host import resident
+    style = spec["style"]
     s = _cell_start(spec)
-    tabs = None
-    if style == "rebomos":
-        cutghost = 3.0 * R["rp"].rcmax[0][0] + skin
-    else:
-        af, tabs = R["af"], R["tabs"]
-        if spec["relabel"] is not None:
-            nmet, nang = spec["relabel"]
-            if "tmp" not in R:
-                R["tmp"] = tempfile.mkdtemp()
-            path = os.path.join(R["tmp"], f"p{nmet}_{nang}.aeam")
-            if not os.path.exists(path):
-                aeam_five.write_relabelled_file(path, R["pot_aeam"], [0] * nmet + [1] * nang, ["M%d" % i for i in range(nmet)] + ["X%d" % i for i in range(nang)])
-            af = capi.AeamFile(path)
-            tabs = af.build()
-        s.mass[1:] = af.mass[:spec["ntypes"]]
-        cutghost = float(af.cut_table(tabs).max()) + skin
-    limit = cutghost - skin
-    assert abs(limit - MSR_LIMIT[style]) < 1e-9, limit
+    tabs, cutghost = _cell_potential(spec, s)
+    limit = MSR_LIMIT[style]
     cutoff = limit if spec["cutoff"] is None else spec["cutoff"]
     member = group_member(spec, s)
     v0, safe = _cell_velocities(spec, s)
@@ -1680,16 +1724,8 @@ def run_measure(spec):
     world = spec["ranks"]
 
     def rank_fn(r, make_tr):
-        ctx = capi.Context(0)
+        ctx, d = _cell_domain(spec, s, tabs, cutghost, v0, make_tr)
         try:
-            if style == "rebomos":
-                ctx.rebomos_set_params(R["rp"])
-                st, map_ = capi.STYLE_REBOMOS, [0, 0, 1]
-            else:
-                ctx.aeam_set_tables(tabs)
-                st, map_ = capi.STYLE_AEAM, None
-            d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0, transport=make_tr(ctx) if world > 1 else None,
-                                      nonperiodic=spec["nonperiodic"])
             d.rdf(spec["nbin_rdf"], cutoff, pairs, member_by_tag=member)
             d.adf(spec["nbin_adf"], triples, ordinate=spec["ordinate"], member_by_tag=member)
             d.compute(0, 0)
@@ -1924,17 +1960,9 @@ def run_peratom(spec):
     import msdref
     import profileref
     from lammps_plugins_amd.host import capi, resident
-    R = _res()
     assert capi.PROFILE_MAXBINS == PA_MAXBINS and capi.PROFILE_W == profileref.W
-    style, skin = spec["style"], MSR_SKIN[spec["style"]]
     s = _cell_start(spec)
-    tabs = None
-    if style == "rebomos":
-        cutghost = 3.0 * R["rp"].rcmax[0][0] + skin
-    else:
-        tabs = R["tabs"]
-        s.mass[1:] = R["af"].mass[:2]
-        cutghost = float(R["af"].cut_table(tabs).max()) + skin
+    tabs, cutghost = _cell_potential(spec, s)
     n, world, nsteps, hf = s.n, spec["ranks"], spec["nsteps"], spec["heatflux"]
     member = peratom_member(spec, s)
     bit = spec["group"]["bit"] if member is not None else 0
@@ -1956,16 +1984,8 @@ def run_peratom(spec):
     by_tag = lambda tags, a: _by_tag_rows(n, tags, a)
 
     def rank_fn(r, make_tr):
-        ctx = capi.Context(0)
+        ctx, d = _cell_domain(spec, s, tabs, cutghost, v0, make_tr)
         try:
-            if style == "rebomos":
-                ctx.rebomos_set_params(R["rp"])
-                st, map_ = capi.STYLE_REBOMOS, [0, 0, 1]
-            else:
-                ctx.aeam_set_tables(tabs)
-                st, map_ = capi.STYLE_AEAM, None
-            d = resident.DeviceDomain(ctx, st, s, cutghost, skin, map_, v0=v0, transport=make_tr(ctx) if world > 1 else None,
-                                      nonperiodic=spec["nonperiodic"])
             if member is not None:
                 d.set_group(mask, 0)
             d.track_images()
@@ -2138,6 +2158,369 @@ def line_peratom(spec, err):
             + ("".join("  " + f for f in err["failed"])))
 
 
+# ---------------------------------------------------------------------------------------------------------- structure
+# compute coord/atom/mdp, centro/atom/mdp and cna/atom/mdp (csrc/coord.hip, csrc/centro.hip, csrc/cna.hip on the walk of
+# csrc/measure_walk.h behind csrc/measure_bin.hip), all three set up on one context per rank, against tests/structref.py and
+# tests/cnaref.py on positions merged by tag from the same state.  The thermal cells of the peratom net (MoS2 replicas, the
+# alloy at 5 - 8 cells, all three tilts in some, relabelled to 3 - 12 types in half: coord's columns), 0 - 2 500 K, some with
+# a drift, 1 - 8 bricks, a free dimension in some one-brick alloy cases; in a quarter of the cases a constructed cell of
+# cnaref in their place (the close-packed stack, bcc, the 13-atom icosahedron; jitter 0.02 - 0.05 A), read with no steps, on
+# 1, 2 or 4 bricks: the only hcp, bcc and icosahedral centres here.  One group for the three computes: none, a slab, a
+# modulus class, one type left out, 1 - 3 atoms or nobody, on bit 1, 7, 30 or 31.  coord: 1 - 32 columns of random type
+# ranges, the cutoff just above the first shell (where bin_grid widens its cells), anywhere up to the radius cap, or the cap;
+# centro: N of 2 - 64 (17 - 88 KB of LDS a workgroup), the cutoff the shell's limit or drawn; cna: the cutoff around the
+# canonical one of the lattice (0.80 - 0.92 a for fcc and hcp, which brackets 0.8536 a, and in 3 of 10 sets 0.96 - 1.04 a,
+# over the second shell: structure_cna_range; 1.15 - 1.26 a for bcc; 0.9 - 1.1 x 1.35 r for the icosahedron; 2.6 - 3.6 A
+# for MoS2).  The radius cap: no centre has more than 100 atoms
+# inside it at the start (the short list holds 128, and a centro read over it is refused by design); where the shell's limit
+# lies above it (MoS2), "the limit" is the cap (spec: centro_capped).  MDP_MEASURE_GRID unset or 1, 3, 64.  Reads at step 0,
+# in between and at the end, each taken twice (coord, centro, cna, and the three again); then either a second parameter set
+# on the same contexts (other cutoffs: other grids and bin buffers; other columns: val regrows; another N: another LDS
+# size) or *_off and the first set again, which must return the last read bit for bit.
+# Every error is a count that must be 0.  The bounds (none measured):
+#   coord    count_sure <= device <= count_sure + edge in every cell (structref.coord: equality but for pairs within 1e-9 of
+#            the cutoff), integers, rows outside the group exactly 0
+#   centro   |device - reference| <= structref.centro_bound(N, cutoff, Lmax) = 64 eps N cutoff Lmax (derived there from the
+#            roundings of x + shift and of the differences) for every atom that is not ambiguous; exactly 0 with fewer than N
+#            inside; the sum of centro_info()["few"] equal to the reference's count to within the ambiguous atoms; no refusal
+#   cna      the pattern equal for every atom that is not ambiguous; the census the histogram of the values handed out;
+#            cna_info()["over"] the reference's count of centres with more than 16 neighbours to within the ambiguous atoms
+# A condition of the case: the reference's own ambiguous atoms and edge pairs are at most 2 per read and compute, the fixed
+# tests' cap (tests/test_net_draws.py checks it on the start positions, with the floors: unless the case is about a group of
+# 0 - 3 atoms or the icosahedron, 100 centres have N inside and 100 a non-zero coordination number).
+# Measured on an MI355X, the 16 suite cases (seed 1018) and 200 cases at seed 7 through profiles/structure_fuzz.py: 16 of 16
+# and 200 of 200 inside every bound.  Worst centro error 0.001 and 0.002 of structref.centro_bound (as printed, to three
+# decimals); the largest `inside` of any atom 104 and 110 (the draw's cap is 100 at the start, the list holds 128; no read
+# was refused); the largest `few` of a read 0 and 1 918, the largest `over` 960 and 1 743; no edge pair or ambiguous atom in
+# any read (cap 2), no late check.  The suite's cases take 14.5 s of calls, the longest 2.4 s; of the 200 the longest took
+# 17.3 s (2 304 MoS2 atoms, N = 64, the knob at 1: one workgroup ranks 2 016 pair values for every centre), the next 4.7 s.
+# The net found no bug in the library.
+STR_CELLS = ("stack", "bcc", "icosahedron")
+STR_CELL_N = {"stack": 960, "bcc": 1024, "icosahedron": 13}
+STR_COLS = (1, 2, 3, 8, 17, 32)
+STR_N = (2, 4, 6, 8, 12, 14, 16, 32, 64)
+STR_CUTOFFS = ("shell", "uniform", "cap")
+STR_FLOOR = 100                   # centres with N inside, and with a non-zero coordination number, at the start
+STR_EDGE_LIMIT = 3                # the reference's ambiguous atoms and edge pairs of a read and compute: at most 2
+_STR_DRAWN = {}
+
+
+def structure_cna_range(spec, across=False):
+    """the interval the cna cutoff of a case is drawn from.  across (fcc-like cells only): over the second shell, 0.96 - 1.04 a,
+    where the jitter of the start positions alone leaves 12 - 18 neighbours -- below 0.92 a no start position has a thirteenth
+    (the second shell lies 0.32 A further out, the jitter moves a pair by 0.16 A at most, and a shear only lengthens the cube
+    axes), and tests/test_net_draws.py asks the start positions for 13, 15, 16 and 17"""
+    import cnaref
+    if spec["cell"] == "bcc":
+        return 1.15 * cnaref.A_BCC, 1.26 * cnaref.A_BCC
+    if spec["cell"] == "icosahedron":
+        return 0.9 * cnaref.RC_ICO, 1.1 * cnaref.RC_ICO
+    if spec["style"] == "rebomos":
+        return 2.6, 3.6
+    return (0.96 * cnaref.A_FCC, 1.04 * cnaref.A_FCC) if across else (0.80 * cnaref.A_FCC, 0.92 * cnaref.A_FCC)
+
+
+def _str_params(rng, nt):
+    """the draws of one parameter set; the radii are fractions here (_str_fit)"""
+    cols = [_msr_range(rng, nt) for _ in range(rng.choice(STR_COLS))]
+    return dict(cols=cols, coord_kind=rng.choice(STR_CUTOFFS), coord_shell=rng.uniform(1.02, 1.15), coord_u=rng.random(),
+                nnn=rng.choice(STR_N), centro_limit=rng.random() < 0.5, centro_u=rng.random(), cna_u=rng.random(), cna_across=rng.random() < 0.3)
+
+
+def draw_structure(rng):
+    import copy
+    key = rng.getstate()
+    if key in _STR_DRAWN:     # (the geometry of _str_fit costs seconds; the draw is a function of the generator's state)
+        spec, after = _STR_DRAWN[key]
+        rng.setstate(after)
+        return copy.deepcopy(spec)
+    spec = _str_random(rng)
+    _str_fit(spec)
+    _STR_DRAWN[key] = (copy.deepcopy(spec), rng.getstate())
+    return spec
+
+
+def _str_random(rng):
+    """the draws of a case; _str_fit then makes radii of the fractions and meets the floors on the start positions without drawing"""
+    sd = rng.randrange(1, 10**6)
+    spec = dict(seed=sd, cell=None, size=None, tilt=None, relabel=None, frac=None, nonperiodic=(0, 0, 0), ntypes=2, temp=0, drift=[0, 0, 0],
+                nsteps=0, between=0, rebuild="auto")
+    if rng.random() < 0.25:       # a constructed cell: one type of the alloy's, read after the setup compute
+        cell = rng.choice(STR_CELLS)
+        spec.update(style="aeam", cell=cell, n=STR_CELL_N[cell], amp=rng.uniform(0.02, 0.05))
+        ranks = rng.choice([1, 2, 4])
+        spec["ranks"] = 1 if cell == "icosahedron" else ranks
+    else:
+        style = rng.choice(["rebomos", "aeam"])
+        spec["style"] = style
+        if style == "rebomos":
+            size = (rng.choice([1, 2]), rng.choice([1, 2]), rng.choice([1, 2]))
+            spec.update(size=size, n=_rebo_n(size))
+        else:
+            size = rng.choice([5, 6, 7, 8])
+            spec.update(size=size, n=4 * size ** 3, frac=rng.choice([0.05, 0.2, 0.5]))
+            if rng.random() < 0.4:   # all three tilts, as draw_measure shears it
+                spec["tilt"] = [rng.uniform(-0.12, 0.12) * 4.045 * size for _ in range(3)]
+            if rng.random() < 0.5:   # relabelled to 3 - 12 types, as draw_measure relabels it
+                spec["relabel"] = rng.choice([(2, 1), (3, 2), (4, 2), (5, 3), (7, 5), (1, 3), (6, 2)])
+                spec["ntypes"] = sum(spec["relabel"])
+        spec["amp"] = rng.choice([0.02, 0.05, 0.08])
+        spec["temp"] = rng.choice(PA_TEMPS)
+        spec["drift"] = [rng.choice([-60, -30, 0, 25, 40, 70]) for _ in range(3)] if rng.random() < 0.4 else [0, 0, 0]
+        spec["nsteps"] = rng.randint(5, 40)
+        spec["ranks"] = 1 if rng.random() < 0.5 else rng.choice([2, 3, 4, 8])
+        auto, renb = rng.random() < 0.5, rng.choice([3, 5, 8])
+        spec["rebuild"] = "auto" if auto and spec["ranks"] == 1 else renb     # (the device's own check serves one brick only)
+        free = rng.random() < 0.4, rng.randrange(3)
+        if style == "aeam" and spec["ranks"] == 1 and spec["tilt"] is None and free[0]:
+            spec["nonperiodic"] = tuple(int(d == free[1]) for d in range(3))
+        spec["between"] = rng.randint(1, spec["nsteps"] - 1)
+    nt = spec["ntypes"]
+    spec["group"] = dict(kind=rng.choice(PA_GROUPS), axis=rng.randrange(3), lo=rng.uniform(0.0, 0.5), width=rng.uniform(0.3, 0.5),
+                         m=rng.choice([2, 3, 5]), r=rng.randrange(2), count=rng.choice([1, 2, 3]), pick=rng.randrange(10**6),
+                         type=rng.randint(1, nt), bit=rng.choice(PA_BITS))
+    spec["first"] = _str_params(rng, nt)
+    spec["second"] = _str_params(rng, nt) if rng.random() < 0.5 else None      # None: *_off and the first set again
+    spec["env"] = {"MDP_MEASURE_GRID": rng.choice(MSR_GRID)} if rng.random() < 0.5 else {}
+    return spec
+
+
+def structure_sets(spec):
+    """the parameter sets of a case: one or two"""
+    return [spec["first"]] + ([spec["second"]] if spec["second"] is not None else [])
+
+
+def structure_start_counts(spec, p, s, member, pairs):
+    """(centres with N inside the centro cutoff, centres with a non-zero coordination number in some column) of the set p on
+    the start positions, from the pair list (i, j, r): exact counts"""
+    pi, pj, pr = pairs
+    mem = np.ones(s.n, dtype=bool) if member is None else member
+    ccut = MSR_LIMIT[spec["style"]] if p["centro_cutoff"] is None else p["centro_cutoff"]
+    inside = np.bincount(pi[pr < ccut], minlength=s.n)
+    near, tj = pr < p["coord_cutoff"], s.type[pj]
+    some = np.zeros(s.n, dtype=bool)
+    for lo, hi in p["cols"]:
+        some |= np.bincount(pi[near & _msr_in(tj, lo, hi)], minlength=s.n) > 0
+    return int((mem & (inside >= p["nnn"])).sum()), int((mem & some).sum())
+
+
+def _str_fit(spec):
+    """no draws: 0 K and a free dimension take the drift out; a group of a few atoms gets its tags; the fractions of the sets
+    become radii -- between 1.02 first shells and the radius cap of _cell_rcap --; and a case that is not exempt (a group of
+    0 - 3 atoms, the icosahedron) meets STR_FLOOR on the start positions with each set: column 1 over all types; then centro's
+    cutoff at the limit (the cap); then N lowered; then no group (and N lowered once more)"""
+    style, nt = spec["style"], spec["ntypes"]
+    first, limit = MSR_FIRST[style], MSR_LIMIT[style]
+    if spec["temp"] == 0 or any(spec["nonperiodic"]):
+        spec["drift"] = [0, 0, 0]
+    s = _cell_start(spec)
+    pairs = _msr_pairs(s, spec, limit)
+    rcap = _cell_rcap(s, pairs, limit)
+    binds = bool(rcap < 0.999 * limit)           # some centre has more than MSR_NEIGH atoms inside the limit
+    spec["rcap"] = float(rcap)
+    g = spec["group"]
+    if g["kind"] == "few":
+        g["tags"] = sorted(int(t) + 1 for t in np.random.default_rng(g["pick"]).choice(s.n, g["count"], replace=False))
+    exempt = g["kind"] in ("few", "nobody") or spec["cell"] == "icosahedron"
+    for p in structure_sets(spec):
+        at_cap = lambda: (float(rcap), True) if binds else (None, False)
+        low = min(1.02 * first, rcap)
+        p["coord_cutoff"] = float({"shell": min(p["coord_shell"] * first, rcap), "uniform": low + p["coord_u"] * (rcap - low), "cap": rcap}[p["coord_kind"]])
+        p["centro_cutoff"], p["centro_capped"] = at_cap() if p["centro_limit"] else (float(low + p["centro_u"] * (rcap - low)), False)
+        lo, hi = structure_cna_range(spec, p["cna_across"])
+        p["cna_cutoff"] = float(lo + p["cna_u"] * (hi - lo))
+        p["fitted"] = []
+        if exempt:
+            continue
+        met = lambda: structure_start_counts(spec, p, s, peratom_member(spec, s), pairs)
+
+        def lower():      # (to the largest N that meets the floor; if none does, N stays)
+            drawn = p["nnn"]
+            for nnn in reversed([k for k in STR_N if k < drawn]):
+                p["nnn"] = nnn
+                if met()[0] >= STR_FLOOR:
+                    p["fitted"].append("N lowered")
+                    return
+            p["nnn"] = drawn
+        if met()[1] < STR_FLOOR:
+            p["cols"][0] = (1, nt)
+            p["fitted"].append("all types")
+        if met()[0] < STR_FLOOR and not p["centro_limit"]:
+            p["centro_cutoff"], p["centro_capped"] = at_cap()
+            p["centro_limit"] = True
+            p["fitted"].append("centro at the limit")
+        if met()[0] < STR_FLOOR:
+            lower()
+        if min(met()) < STR_FLOOR:
+            g["kind"] = "none"
+            p["fitted"].append("no group")
+            if met()[0] < STR_FLOOR:
+                lower()
+    p = spec["first"]
+    what = spec["cell"] or style
+    spec["id"] = (f"{what}-n{spec['n']}-types{nt}-ranks{spec['ranks']}-T{spec['temp']}-{g['kind'].replace(' ', '')}-bit{g['bit'].bit_length() - 1}-"
+                  f"col{len(p['cols'])}-N{p['nnn']}-grid{spec['env'].get('MDP_MEASURE_GRID', 'unset')}-{'second' if spec['second'] else 'again'}")
+
+
+def structure_references(spec, p, x, types, h, member):
+    """structref.coord, structref.centro and cnaref.cna of the set p on positions and types by tag, and centro's cutoff"""
+    import cnaref
+    import structref
+    per = _cell_periodic(spec)
+    ccut = MSR_LIMIT[spec["style"]] if p["centro_cutoff"] is None else p["centro_cutoff"]
+    return (structref.coord(x, types, h, per, p["coord_cutoff"], p["cols"], member), structref.centro(x, h, per, p["nnn"], ccut, member),
+            cnaref.cna(x, h, per, p["cna_cutoff"], member), ccut)
+
+
+def run_structure(spec):
+    import structref
+    from lammps_plugins_amd.host import capi, resident
+    s = _cell_start(spec)
+    tabs, cutghost = _cell_potential(spec, s)
+    n, world, nsteps = s.n, spec["ranks"], spec["nsteps"]
+    member = peratom_member(spec, s)
+    bit = spec["group"]["bit"] if member is not None else 0
+    gbit = bit - (1 << 32) if bit >= (1 << 31) else bit             # the C int with that bit
+    mask = np.ones(n + 1, dtype=np.uint32)
+    if member is not None:
+        mask[1:] |= np.where(member, np.uint32(bit), np.uint32(0))
+    mask = mask.view(np.int32)
+    sel = np.ones(n, dtype=bool) if member is None else member
+    v0, rebuild = None, "auto"
+    if spec["cell"] is None:
+        v0, safe = _cell_velocities(spec, s)
+        rebuild = spec["rebuild"] if spec["rebuild"] == "auto" else min(spec["rebuild"], safe)
+    reads = sorted({0, spec["between"], nsteps})
+    lmax = float(np.linalg.norm(s.box.h, axis=0).max())             # (test_gpu_struct_mdp._lmax)
+
+    def setup(d, p):
+        d.coord(p["coord_cutoff"], p["cols"], group_bit=gbit)
+        d.centro(p["nnn"], p["centro_cutoff"], group_bit=gbit)
+        d.cna(p["cna_cutoff"], group_bit=gbit)
+
+    def read(ctx, d):
+        """coord, centro, cna and the three again: the second round re-reads the state of the first"""
+        o = dict(tags=d.tags_local.copy(), x=ctx.md_download(d.nlocal, want=("x",))["x"], coord=[], centro=[], cna=[], refused="")
+        for _ in range(2):
+            o["coord"].append(d.coord_read())
+            try:
+                o["centro"].append(d.centro_read() + (np.array([ctx.centro_info()["few"]]),))
+            except capi.MdpError as e:
+                o["refused"] = str(e)[-200:]
+            o["cna"].append(d.cna_read() + (ctx.cna_counts(), np.array([ctx.cna_info()["over"]])))
+        return o
+
+    def rank_fn(r, make_tr):
+        ctx, d = _cell_domain(spec, s, tabs, cutghost, v0, make_tr)
+        try:
+            if member is not None:
+                d.set_group(mask, 0)
+            setup(d, spec["first"])
+            d.compute(0, 0)
+            out = {}
+            for step in range(0, nsteps + 1):
+                if step:
+                    d.step(0, 0, rebuild="auto" if rebuild == "auto" else step % rebuild == 0)
+                if step in reads:
+                    out[step] = read(ctx, d)
+            if spec["second"] is not None:
+                setup(d, spec["second"])
+            else:
+                d.coord_off(), d.centro_off(), d.cna_off()
+                setup(d, spec["first"])
+            out["again"] = read(ctx, d)
+            return dict(out=out, builds=d.builds, late=d.dangerous)
+        finally:
+            ctx.close()
+
+    res = [rank_fn(0, None)] if world == 1 else resident.run_ranks(world, rank_fn)
+    types = s.type.copy()      # (by tag: the tags are 1 .. n in order)
+    err = dict(reread=0, tags=0, not_owned_once=0, outside=0, coord=0, integers=0, centro=0, short=0, few=0, refused=0, cna=0, census=0, over=0,
+               fresh=0, edge=0, late=sum(r["late"] for r in res), builds=res[0]["builds"], worst=0.0, most=0, most_few=0, most_over=0,
+               centres=None, failed=[])
+    same = lambda a, b: len(a) == len(b) and all(u.tobytes() == w.tobytes() for u, w in zip(a, b))
+    last = None
+    for state in reads + ["again"]:
+        p = spec["second"] if state == "again" and spec["second"] is not None else spec["first"]
+        ncol = len(p["cols"])
+        x, seen = np.zeros((n, 3)), np.zeros(n, dtype=int)
+        co, ce, cn = np.zeros((n, ncol)), np.zeros(n), np.zeros(n)
+        few, over, census, refused = 0, 0, np.zeros(6, dtype=np.int64), False
+        for r in res:
+            o = r["out"][state]
+            tags = o["tags"]
+            x[tags - 1] = o["x"]
+            seen[tags - 1] += 1
+            refused |= bool(o["refused"]) or len(o["centro"]) != 2
+            if o["refused"]:
+                err["failed"].append(f"read {state}: {o['refused']}")
+            for key in ("coord", "centro", "cna"):
+                got = o[key]
+                if len(got) == 2:
+                    err["reread"] += int(not same(got[0], got[1]))
+                err["tags"] += sum(int(not np.array_equal(q[0], tags)) for q in got)
+            co[tags - 1] = o["coord"][0][1]
+            cn[tags - 1] = o["cna"][0][1]
+            census += o["cna"][0][2]
+            over += int(o["cna"][0][3][0])
+            if not refused:
+                ce[tags - 1] = o["centro"][0][1]
+                few += int(o["centro"][0][2][0])
+        err["not_owned_once"] += int(not np.all(seen == 1))
+        err["refused"] += int(refused)
+        now = (co, ce, cn, census, few, over)
+        if state == "again" and spec["second"] is None:     # the fresh setup of the same set on the same state: the last read again
+            err["fresh"] += int(not (same(now[:4], last[:4]) and now[4:] == last[4:]))
+            continue
+        last = now
+        cref, zref, aref, ccut = structure_references(spec, p, x, types, s.box.h, member)
+        err["outside"] += int((co[~sel] != 0.0).sum() + (ce[~sel] != 0.0).sum() + (cn[~sel] != 0.0).sum())
+        # ---- coord
+        err["integers"] += int((co != np.rint(co)).sum())
+        err["coord"] += int(((co < cref["count_sure"]) | (co > cref["count_sure"] + cref["edge"])).sum())
+        # ---- centro
+        amb = zref["ambiguous"]
+        namb = int(amb.sum())
+        short = sel & (zref["inside"] < p["nnn"])
+        if not refused:
+            bound = structref.centro_bound(p["nnn"], ccut, lmax)
+            dz = np.abs(ce - zref["value"])
+            err["centro"] += int((~(dz <= bound) & ~amb).sum())
+            err["short"] += int((short & ~amb & (ce != 0.0)).sum())
+            err["few"] += int(abs(few - int(short.sum())) > namb)
+            if (~amb).any():
+                err["worst"] = max(err["worst"], float(dz[~amb].max() / bound))
+        # ---- cna
+        camb = aref["ambiguous"]
+        err["cna"] += int(((cn != aref["pattern"]) & ~camb).sum())
+        err["census"] += int(not (np.array_equal(census, np.bincount(cn[sel].astype(np.int64), minlength=6)[:6]) and census[0] == 0))
+        many = int((sel & (aref["neighbours"] > 16)).sum())
+        err["over"] += int(abs(over - many) > int(camb.sum()))
+        err["edge"] = max(err["edge"], cref["n_edge"], namb, int(camb.sum()))
+        full = int((sel & (zref["inside"] >= p["nnn"])).sum())
+        err["centres"] = full if err["centres"] is None else min(err["centres"], full)
+        err.update(most=max(err["most"], int(zref["inside"].max(initial=0))), most_few=max(err["most_few"], few), most_over=max(err["most_over"], over))
+    lim = dict.fromkeys(("reread", "tags", "not_owned_once", "outside", "coord", "integers", "centro", "short", "few", "refused", "cna", "census",
+                         "over", "fresh", "late"), 1)
+    lim["edge"] = STR_EDGE_LIMIT
+    return err, lim
+
+
+def line_structure(spec, err):
+    def text(p):
+        cut = "limit" if p["centro_cutoff"] is None else f"{p['centro_cutoff']:.3f}" + (" (the limit, capped)" if p["centro_capped"] else "")
+        return (f"coord {len(p['cols'])} columns inside {p['coord_cutoff']:.3f} ({p['coord_kind']}), centro N {p['nnn']} inside {cut}, "
+                f"cna inside {p['cna_cutoff']:.3f}, fitted {p['fitted']}")
+    return (f"{spec['id']} size {spec['size']} tilt {spec['tilt'] is not None} relabel {spec['relabel']} free {spec['nonperiodic']} drift {spec['drift']} "
+            f"steps {spec['nsteps']} rebuild {spec['rebuild']} read also at {spec['between']} rcap {spec['rcap']:.2f} seed {spec['seed']} "
+            f"first: {text(spec['first'])}; " + (f"second: {text(spec['second'])}" if spec["second"] else "then off and the first again")
+            + f"; reread {err['reread']} tags {err['tags']} owned once {not err['not_owned_once']} outside {err['outside']} coord {err['coord']} "
+            f"integers {err['integers']} centro {err['centro']} short {err['short']} few {err['few']} refused {err['refused']} cna {err['cna']} "
+            f"census {err['census']} over {err['over']} fresh {err['fresh']} edge {err['edge']} late {err['late']} builds {err['builds']} "
+            f"worst centro error / bound {err['worst']:.3f}, most inside {err['most']}, most few {err['most_few']}, most over {err['most_over']}, "
+            f"fewest centres with N inside {err['centres']}" + "".join("  " + f for f in err["failed"]))
+
+
 # ---------------------------------------------------------------------------------------------------------------- nvt
 # The Nose-Hoover chain thermostat (tests/test_gpu_nvt_net.py): chains of 1-8, 1-3 loops, drag, flat or ramped targets,
 # both styles, the resident path and (REBO-MoS) the host-linked one, atom counts whose last 256-atom block varies.
@@ -2167,7 +2550,8 @@ def nvt_cases(seed, ncase):
 
 
 NETS = {name: (globals()["draw_" + name], globals()["run_" + name], globals()["line_" + name])
-        for name in ("force", "hostmode_walk", "aeam_types", "prune", "dd", "hnve", "minilmp", "trajectory", "block", "fire", "langevin", "heat", "measure", "peratom")}
+        for name in ("force", "hostmode_walk", "aeam_types", "prune", "dd", "hnve", "minilmp", "trajectory", "block", "fire", "langevin", "heat", "measure", "peratom",
+                     "structure")}
 
 
 def main(net, argv):

@@ -161,6 +161,38 @@ CORNERS = {
         "the device's own check and forced rebuilds": lambda c: {s["rebuild"] == "auto" for s in c} == {True, False},
         "at most 16 cases": lambda c: len(c) <= 16,
     },
+    "structure": {   # (what the references make of these cases: test_structure_cases_meet_their_own_conditions)
+        "both styles": lambda c: {s["style"] for s in c if s["cell"] is None} == {"rebomos", "aeam"},
+        "each constructed cell": lambda c: {s["cell"] for s in c if s["cell"]} == set(nets.STR_CELLS),
+        "a constructed cell on several bricks": lambda c: any(s["cell"] and s["ranks"] > 1 for s in c),
+        "an alloy with all three tilts on one brick": lambda c: any(s["tilt"] is not None and all(s["tilt"]) and s["ranks"] == 1 for s in c),
+        "an alloy with all three tilts on several bricks": lambda c: any(s["tilt"] is not None and all(s["tilt"]) and s["ranks"] > 1 for s in c),
+        "more than 2 types": lambda c: any(s["ntypes"] > 2 for s in c),
+        "a free dimension": lambda c: any(any(s["nonperiodic"]) for s in c),
+        "8 bricks": lambda c: any(s["ranks"] == 8 for s in c),
+        "an odd brick count above 1": lambda c: any(s["ranks"] % 2 and s["ranks"] > 1 for s in c),
+        "a drift on several bricks": lambda c: any(any(s["drift"]) and s["ranks"] > 1 for s in c),
+        "each group kind": lambda c: {s["group"]["kind"] for s in c} == set(nets.PA_GROUPS),
+        "a group of one atom": lambda c: any(s["group"]["kind"] == "few" and len(s["group"]["tags"]) == 1 for s in c),
+        "bit 31 on a group with members": lambda c: any(s["group"]["bit"] == 1 << 31 and s["group"]["kind"] not in ("none", "nobody") for s in c),
+        "1 column": lambda c: any(len(s["first"]["cols"]) == 1 for s in c),
+        "32 columns": lambda c: any(len(s["first"]["cols"]) == 32 for s in c),
+        "N = 2": lambda c: any(s["first"]["nnn"] == 2 for s in c),
+        "N = 64": lambda c: any(s["first"]["nnn"] == 64 for s in c),
+        "centro with the cutoff at the limit": lambda c: any(p["centro_cutoff"] is None for s in c for p in nets.structure_sets(s)),
+        "centro's limit capped (MoS2)": lambda c: any(p["centro_capped"] for s in c for p in nets.structure_sets(s)),
+        "a coord cutoff small enough that bin_grid widens its cells": lambda c: any(
+            p["coord_kind"] == "shell" and nets.measure_grid_grows(s, p["coord_cutoff"]) for s in c for p in nets.structure_sets(s)),
+        "every kind of coord cutoff": lambda c: {s["first"]["coord_kind"] for s in c} == set(nets.STR_CUTOFFS),
+        "the knob at 1 on one brick": lambda c: any(s["env"].get("MDP_MEASURE_GRID") == "1" and s["ranks"] == 1 for s in c),
+        "the knob unset": lambda c: any(not s["env"] for s in c),
+        "both kinds of second setup": lambda c: {s["second"] is None for s in c} == {True, False},
+        "a second setup with another N and other columns": lambda c: any(
+            s["second"] and s["second"]["nnn"] != s["first"]["nnn"] and len(s["second"]["cols"]) != len(s["first"]["cols"]) for s in c),
+        "0 K": lambda c: any(s["cell"] is None and s["temp"] == 0 for s in c),
+        "the device's own check and forced rebuilds": lambda c: {s["rebuild"] == "auto" for s in c if s["cell"] is None} == {True, False},
+        "at most 16 cases": lambda c: len(c) <= 16,
+    },
 }
 
 
@@ -365,3 +397,60 @@ def test_peratom_cases_meet_their_own_conditions():
             assert edge["n_edge"] <= 2, (spec["id"], edge["n_edge"])
             profileref.check_sums_with_edges(ref["count"], ref["sums"], ref["exponents"], ref, edge)
             assert ref["count"].sum() == (s.n if member is None else member.sum())
+
+
+def structure_conditions(specs):
+    """the references alone on the start positions of `structure` cases: asserts what every case promises and returns what the
+    cases reach together: the cna patterns, the neighbour counts of the centres, the centres with 12 or 14 neighbours that are
+    `other`"""
+    import cnaref
+    seen = dict(patterns=set(), neighbours=set(), other_at_12_or_14=0)
+    for spec in specs:
+        s = nets._cell_start(spec)
+        member = nets.peratom_member(spec, s)
+        sel = np.ones(s.n, dtype=bool) if member is None else member
+        kind, limit = spec["group"]["kind"], nets.MSR_LIMIT[spec["style"]]
+        assert (member is None) == (kind == "none")
+        if kind == "nobody":
+            assert not member.any()
+        elif kind == "few":
+            assert member.sum() == spec["group"]["count"] in (1, 2, 3)
+        pairs = nets._msr_pairs(s, spec, limit)
+        exempt = kind in ("few", "nobody") or spec["cell"] == "icosahedron"
+        for p in nets.structure_sets(spec):
+            cref, zref, aref, ccut = nets.structure_references(spec, p, s.x, s.type, s.box.h, member)
+            largest = max(p["coord_cutoff"], ccut, p["cna_cutoff"])
+            assert largest <= limit and min(p["coord_cutoff"], ccut, p["cna_cutoff"]) > 0.0, spec["id"]
+            assert (p["centro_cutoff"] is None) == (ccut == limit)
+            most = int(np.bincount(pairs[0][pairs[2] < largest], minlength=s.n).max())
+            edges = (cref["n_edge"], int(zref["ambiguous"].sum()), int(aref["ambiguous"].sum()))
+            full = int((sel & (zref["inside"] >= p["nnn"])).sum())
+            some = int((sel & (cref["count_sure"].sum(axis=1) > 0)).sum())
+            print(spec["id"], f"at most {most} inside {largest:.3f}, edge events {edges}, {full} centres with N = {p['nnn']} inside {ccut:.3f}, "
+                  f"{some} with a coordination number, cna {cnaref.histogram(aref['pattern']).tolist()}")
+            assert most <= nets.MSR_NEIGH, (spec["id"], most)
+            assert max(edges) <= 2, (spec["id"], edges)
+            assert 2 <= p["nnn"] <= 64 and 1 <= len(p["cols"]) <= 32
+            assert (full, some) == nets.structure_start_counts(spec, p, s, member, pairs) or cref["n_edge"] or zref["ambiguous"].any(), spec["id"]
+            if not exempt:
+                assert full >= nets.STR_FLOOR and some >= nets.STR_FLOOR, (spec["id"], full, some)
+            seen["patterns"] |= set(aref["pattern"][sel].tolist())
+            seen["neighbours"] |= set(aref["neighbours"][sel].tolist())
+            seen["other_at_12_or_14"] += int((sel & np.isin(aref["neighbours"], (12, 14)) & (aref["pattern"] == cnaref.OTHER)).sum())
+    return seen
+
+
+def test_structure_cases_meet_their_own_conditions():
+    """No GPU, no oracle.  On the start positions of every `structure` case of the suite, for each of its parameter sets, the
+    references alone meet the conditions the case sets itself: no centre has more than 100 atoms inside the largest cutoff
+    (the short list holds 128; the margin is for thermal motion); at most 2 edge pairs (coord) and 2 ambiguous atoms (centro,
+    cna); every cutoff at most the ghost shell's limit; unless the case is about a group of 0 - 3 atoms or the 13-atom
+    icosahedron, at least 100 centres have N atoms inside centro's cutoff and at least 100 a non-zero coordination number in
+    some column, and the draw's own counts of both are the references'.  Over the whole suite the reference's cna patterns
+    are fcc, hcp, bcc, icosahedral and other; centres with 13, 15, 16 and 17 neighbours occur (the edges of the list of 16
+    and of the n == 12 || n == 14 branch), and centres with 12 or 14 neighbours that are `other` all the same."""
+    import cnaref
+    seen = structure_conditions(SPECS["structure"])
+    print(seen)
+    assert seen["patterns"] >= {cnaref.FCC, cnaref.HCP, cnaref.BCC, cnaref.ICO, cnaref.OTHER}
+    assert seen["neighbours"] >= {13, 15, 16, 17} and seen["other_at_12_or_14"] >= 1
