@@ -21,9 +21,10 @@ def centre(ind, n, first, dt):
     return np.asarray(ind["c"], dtype=float) + np.asarray(ind.get("vel", (0.0, 0.0, 0.0)), dtype=float) * ((n - first) * dt)
 
 
-def minimum_image(box, d, periodic=(True, True, True)):
+def minimum_image(box, d, periodic=(True, True, True), taken=None):
     """Domain::minimum_image on the rows of d: one wrap per periodic dimension, z then y then x; a wrap in z carries
-    (xz, yz), a wrap in y carries xy"""
+    (xz, yz), a wrap in y carries xy.  taken: a dict that receives, per periodic dimension 0 | 1 | 2, the sign of the
+    wrap every row took there (0: none)"""
     d = np.array(d, dtype=float, copy=True).reshape(-1, 3)
     xprd, yprd, zprd = box.prd
     xy, xz, yz = box.tilt
@@ -32,18 +33,25 @@ def minimum_image(box, d, periodic=(True, True, True)):
         d[:, 2] += s * zprd
         d[:, 1] += s * yz
         d[:, 0] += s * xz
+        if taken is not None:
+            taken[2] = s
     if periodic[1]:
         s = np.where(np.abs(d[:, 1]) > 0.5 * yprd, np.where(d[:, 1] < 0.0, 1.0, -1.0), 0.0)
         d[:, 1] += s * yprd
         d[:, 0] += s * xy
+        if taken is not None:
+            taken[1] = s
     if periodic[0]:
         s = np.where(np.abs(d[:, 0]) > 0.5 * xprd, np.where(d[:, 0] < 0.0, 1.0, -1.0), 0.0)
         d[:, 0] += s * xprd
+        if taken is not None:
+            taken[0] = s
     return d
 
 
-def depth(ind, ctr, box, x, periodic=(True, True, True)):
-    """(dr, unit vector the force on a touching atom points along, r) of every atom for the indenter centred at ctr"""
+def depth(ind, ctr, box, x, periodic=(True, True, True), taken=None):
+    """(dr, unit vector the force on a touching atom points along, r) of every atom for the indenter centred at ctr;
+    taken: as minimum_image takes it (a plane takes no minimum image and leaves it empty)"""
     x = np.asarray(x, dtype=float).reshape(-1, 3)
     side = ind.get("side", "out")
     dim = int(ind.get("dim", 0))
@@ -59,7 +67,7 @@ def depth(ind, ctr, box, x, periodic=(True, True, True)):
     d = x - ctr
     if ind["shape"] == "cylinder":
         d[:, dim] = 0.0
-    d = minimum_image(box, d, periodic)
+    d = minimum_image(box, d, periodic, taken)
     r = np.sqrt((d * d).sum(axis=1))
     with np.errstate(invalid="ignore", divide="ignore"):
         u = np.where(r[:, None] > 0.0, d / r[:, None], 0.0)

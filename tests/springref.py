@@ -44,6 +44,9 @@ def spring_tether(sp, p, m, xu, order=None, exact=False):
     idx = np.arange(len(m)) if sp.get("group") is None else np.flatnonzero(np.asarray(sp["group"], dtype=bool))
     if order is not None:
         idx = idx[np.argsort(np.asarray(order)[idx], kind="stable")]
+    if len(idx) == 0:                           # (a group that lost its atoms to a new mask: no centre of mass, no force)
+        return dict(energy=0.0, ftotal=np.zeros(4), xcm=np.zeros(3), tether=np.asarray(p, dtype=float), mass=0.0, atoms=0,
+                    fm=np.zeros(3), dr=0.0)
     mi = np.asarray(m, dtype=float)[idx]
     mx = mi[:, None] * np.asarray(xu, dtype=float)[idx]
     M = math.fsum(mi)                           # (the sum of the masses is exact in every mode: it has one value)
@@ -100,7 +103,8 @@ def run(x, v, m, force, springs, first, last, dt, ftm2v, group, box, img=None, o
 
 
 def host_spring(make_engine, s, v0, img0, nsteps, every, rebuild_every, group, springs, dt=0.001, first=0, orders=None,
-                exact=False, cut=None, baths=None, inds=None):
+                exact=False, cut=None, baths=None, inds=None, ind_orders=None, dforce=0.0, regroup=None, skin=None, on_force=None,
+                periodic=(True, True, True), keep_held=False):
     """indentref.host_indent with the springs: velocity Verlet on `group` around the oracle, the lists built anew every
     rebuild_every steps -- where the atoms are wrapped and their image flags (img0 [n][3] counts, by the order of s, at the
     start) take up the box vectors -- and FixSpring::post_force after every force evaluation, behind the Langevin forces of
@@ -108,8 +112,18 @@ def host_spring(make_engine, s, v0, img0, nsteps, every, rebuild_every, group, s
     {step: (x by tag, [state of spring k], v by tag, xu by tag, [state of indenter k])} for the steps in `every` and for step
     0 (the setup), and dict(fmax: per spring the largest |F| over ALL steps, flagged: atoms of `group` whose image flag
     changed during the run).
-    cut = k: the host starts a second run behind step k (mdp_spring_run(first + k) and a new setup): the tether points
-    start again at c and the forces are computed anew, from the same positions."""
+    cut = k: the host starts a second run behind step k (mdp_spring_run(first + k), mdp_indent_run(first + k) and a new
+    setup): the tether points and the centres start again at c and the forces are computed anew, from the same positions.
+    The nets' extensions (tests/nets.py, the `postforce` net) -- `springs` may be empty, the indenters alone:
+    ind_orders: per indenter a permutation its touching atoms are summed in (indentref.post_force);
+    dforce: every component of the oracle's forces of every step gets an error drawn uniformly from +-dforce;
+    regroup = {step: (springs, inds)}: behind the read of that step the host sets a new mask -- from the forces of the next
+    step on these lists, with their groups, stand for the old ones (a spring whose group is empty reports zeros);
+    skin: assert that no atom has moved more than half of it since the last build (heatref.host_heat's rule);
+    on_force(step, x, img, spring states, indenter states): called behind every force evaluation of a step (0: the setup);
+    periodic: what the indenters' minimum image takes per dimension;
+    keep_held: a list build leaves the atoms outside `group` where they are, bit for bit, as a host that wraps only the atoms
+    that left the box does (S.wrap writes every atom anew, which moves an atom of a sheared box by an ulp)."""
     g = np.asarray(group, dtype=bool)
     m = s.mass[s.type]
     mg = m[g]
@@ -117,14 +131,18 @@ def host_spring(make_engine, s, v0, img0, nsteps, every, rebuild_every, group, s
     v = v0.copy()
     img = np.array(img0, dtype=np.int64, copy=True)
     eng = make_engine(S.System(s.box, x.copy(), s.type, s.tag, s.mass))
-    inds = inds or []
+    x_built = x.copy()
+    cur = dict(springs=springs, inds=inds or [])
+    noise = np.random.default_rng(20261) if dforce else None
 
-    def forces(step, n, phase=0):
+    def forces(step, n, phase=0, with_baths=True):
         f = eng.compute(x, eflag=1, vflag=0)["f_owned"].copy()
-        if baths:
+        if dforce:
+            f += noise.uniform(-dforce, dforce, f.shape)
+        if baths and with_baths:
             f += bathsref.baths_force(baths, step, s.tag, s.type, v, phase=phase)
-        ist = indentref.post_force(inds, n, first, dt, s.box, x, f) if inds else []
-        return f, post_force(springs, n, first, dt, s.box, x, img, m, f, orders=orders, exact=exact), ist
+        ist = indentref.post_force(cur["inds"], n, first, dt, s.box, x, f, periodic=periodic, orders=ind_orders) if cur["inds"] else []
+        return f, post_force(cur["springs"], n, first, dt, s.box, x, img, m, f, orders=orders, exact=exact), ist
     if baths:
         for lgv, _ in baths:
             lgv.setup(0, nsteps)
@@ -132,13 +150,15 @@ def host_spring(make_engine, s, v0, img0, nsteps, every, rebuild_every, group, s
     dtf = 0.5 * dt * S.FTM2V
     fmax = [0.0] * len(springs)
 
-    def note(st):
+    def note(step, st, ist):
         for k, q in enumerate(st):
             fmax[k] = max(fmax[k], abs(float(q["ftotal"][3])))
+        if on_force is not None:
+            on_force(step, x, img, st, ist)
 
     def read():
         return (x.copy(), st, v.copy(), unwrap(s.box, x, img), ist)
-    note(st)
+    note(0, st, ist)
     out = {0: read()}
     base = 0
     for step in range(1, nsteps + 1):
@@ -146,17 +166,25 @@ def host_spring(make_engine, s, v0, img0, nsteps, every, rebuild_every, group, s
         x[g] += dt * v[g]
         if step % rebuild_every == 0:
             img += np.floor(s.box.x2lamda(x)).astype(np.int64)
-            x = S.wrap(s.box, x)
+            xw = S.wrap(s.box, x)
+            if keep_held:
+                xw[~g] = x[~g]
+            x = xw
             eng = make_engine(S.System(s.box, x.copy(), s.type, s.tag, s.mass))
+            x_built = x.copy()
+        elif skin is not None:
+            far = float(np.sqrt(((x - x_built) ** 2).sum(axis=1)).max())
+            assert far <= 0.5 * skin, f"the reference's own list is stale at step {step}: an atom moved {far:.3f} A"
         f, st, ist = forces(step, first + step - base)
-        note(st)
+        note(step, st, ist)
         v[g] += dtf * f[g] / mg[:, None]
         if step in every:
             out[step] = read()
-        if cut is not None and step == cut:      # the second run's setup: same positions, the tether points at c again
+        if regroup is not None and step in regroup:
+            cur["springs"], cur["inds"] = regroup[step]
+        if cut is not None and step == cut:      # the second run's setup: same positions, tether points and centres at c again
             base = step
-            f = eng.compute(x, eflag=1, vflag=0)["f_owned"].copy()
-            st = post_force(springs, first, first, dt, s.box, x, img, m, f, orders=orders, exact=exact)
-            note(st)
+            f, st, ist = forces(step, first, with_baths=False)
+            note(step, st, ist)
     flagged = int(((img != np.asarray(img0)).any(axis=1) & g).sum())
     return out, dict(fmax=fmax, flagged=flagged)

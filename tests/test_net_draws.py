@@ -193,6 +193,45 @@ CORNERS = {
         "the device's own check and forced rebuilds": lambda c: {s["rebuild"] == "auto" for s in c if s["cell"] is None} == {True, False},
         "at most 16 cases": lambda c: len(c) <= 16,
     },
+    "postforce": {   # (what the reference makes of these cases: test_postforce_cases_meet_their_own_conditions)
+        "every shape x side x dim": lambda c: {(q["shape"], q["side"], q["dim"]) for s in c for q in s["inds"]} >= set(nets.PF_COMBOS),
+        "every path": lambda c: {s["path"] for s in c} == set(nets.HEAT_PATHS),
+        "both styles": lambda c: {s["style"] for s in c} == {"rebomos", "aeam"},
+        "a sheared cell with dynamics and an indenter": lambda c: any(s["tilt"] and s["nsteps"] and s["inds"] for s in c),
+        "a sheared cell with dynamics and a spring": lambda c: any(s["tilt"] and s["nsteps"] and s["springs"] for s in c),
+        "a sheared cell whose crystal travels along z under a spring": lambda c: any(
+            s["tilt"] and s["springs"] and s["springs"][s["drifting"]]["kind"] == "everything" and s["group"] == "all" for s in c),
+        "a static case with a free dimension": lambda c: any(s["free"] is not None and s["nsteps"] == 0 for s in c),
+        "an indenter with K = 0": lambda c: any(q["k"] == 0.0 for s in c for q in s["inds"]),
+        "a spring with K = 0": lambda c: any(q["k"] == 0.0 for s in c for q in s["springs"]),
+        "a bit-0 slot behind a slot with a bit": lambda c: any(q["bit"] == 0 and any(p["bit"] for p in s["inds"][:k])
+                                                                for s in c for k, q in enumerate(s["inds"])),
+        "slot k is not always the k-th lowest bit": lambda c: any([q["bit"] for q in s["inds"]] != sorted(q["bit"] for q in s["inds"]) for s in c),
+        "both stages on with 3 or more slots each": lambda c: any(len(s["inds"]) >= 3 and len(s["springs"]) >= 3 for s in c),
+        "a spring's group emptied by a new mask": lambda c: any(s["newmask"] for s in c),
+        "a second run over a pending final half": lambda c: any(s["cut"] and not s["cut"][1] for s in c),
+        "a second run, the first one completed": lambda c: any(s["cut"] and s["cut"][1] for s in c),
+        "a second run with both stages on": lambda c: any(s["cut"] and s["inds"] and s["springs"] for s in c),
+        "first = 2^32 + 7": lambda c: any(s["first"] == 2 ** 32 + 7 for s in c),
+        "256 atoms": lambda c: any(s["n"] == 256 for s in c),
+        "288 atoms": lambda c: any(s["n"] == 288 for s in c),
+        "more than 1024 atoms, the last 1024-atom block partial": lambda c: any(s["n"] > 1024 and s["n"] % 1024 for s in c),
+        "three fill levels of the last 256-atom block": lambda c: len({s["n"] % 256 for s in c}) >= 3,
+        "a plane with R = 0": lambda c: any(q["shape"] == "plane" and q["r_plane"] == 0.0 for s in c for q in s["inds"]),
+        "a sphere centred on a held atom (r == 0)": lambda c: any(q["site"] == "held" for s in c for q in s["inds"]),
+        "static and moving indenters": lambda c: {q["moving"] for s in c if s["nsteps"] for q in s["inds"]} == {True, False},
+        "a centre moved by a whole box vector, each dimension": lambda c: {q["shift"][0] for s in c for q in s["inds"]
+                                                                           if q["shift"] and q["shape"] != "plane"} == {0, 1, 2},
+        "every rest length": lambda c: {q["r0"] for s in c for q in s["springs"]} == {"zero", "below", "above"},
+        "static and moving tether points": lambda c: {q["moving"] for s in c for q in s["springs"]} == {True, False},
+        "six of the seven use patterns": lambda c: len({q["use"] for s in c for q in s["springs"]}) >= 6,
+        "a spring on bit 0": lambda c: any(q["bit"] == 0 for s in c for q in s["springs"]),
+        "a tiny group under a spring": lambda c: any(q["kind"] == "tiny" for s in c for q in s["springs"]),
+        "start image flags, and none": lambda c: {s["img"] for s in c if s["springs"]} == {True, False},
+        "integrate group all, and a part of the cell": lambda c: {s["group"] for s in c} == {"all", "slab"},
+        "reads that find the final half deferred, and not": lambda c: {d for s in c for _, d in s["reads"]} == {True, False},
+        "at most 16 cases": lambda c: len(c) <= 16,
+    },
 }
 
 
@@ -316,6 +355,101 @@ def test_heat_cases_run_clean_and_the_limits_are_the_references(oracle):
         assert worst["i"][k] < 0.01 * lim, (k, worst["i"][k], lim)
     for k in ("dx", "dv", "dscale"):
         assert worst["ii"][k] < 0.25 * nets.HEAT_LIMITS[k], (k, worst["ii"][k])
+
+
+_PF = {}
+
+
+def _postforce(spec):
+    """(the case as nets._pf_system fits it, its plain reference, what that run showed), once per case"""
+    if spec["id"] not in _PF:
+        P = nets._pf_system(spec)
+        _PF[spec["id"]] = (P,) + nets.postforce_reference(spec, P)
+    return _PF[spec["id"]]
+
+
+def postforce_conditions(specs):
+    """the reference alone over `postforce` cases: asserts what every case promises and returns what the cases reach together"""
+    reach = dict(wraps=set(), sheared_wraps=set(), rzero=False, zflag_sheared=False, emptied=False, decided=False)
+    for spec in specs:
+        P, ref, seen = _postforce(spec)
+        last = ref[spec["nsteps"]]
+        assert all(np.isfinite(w[0]).all() and np.isfinite(w[2]).all() for w in ref.values()), spec["id"]
+        print(spec["id"], {k: ([round(a, 3) for a in v] if isinstance(v, list) and v and isinstance(v[0], float) else v) for k, v in seen.items()})
+        for k, q in enumerate(P["inds"]):
+            if q["k"] > 0.0:
+                assert seen["contacts"][k] >= 2, (spec["id"], k, seen["contacts"])
+                assert seen["deepest"][k] < 0.8, (spec["id"], k, seen["deepest"])
+                assert seen["fmax"][k] >= 0.05, (spec["id"], k, seen["fmax"])
+            if q["shape"] == "plane":   # clear of the faces by skin + 1.5 A at every step: the remap never touches its atoms
+                assert seen["face"][k] >= spec["skin"] + nets.PF_FACE, (spec["id"], k, seen["face"])
+                assert q["bit"] != 0
+            else:
+                reach["wraps"] |= seen["wraps"][k]
+                if spec["tilt"]:
+                    reach["sheared_wraps"] |= seen["wraps"][k]
+            if q["shape"] == "cylinder":
+                assert q["vel"][q["dim"]] == 0.0
+        for k, (q, d) in enumerate(zip(P["springs"], spec["springs"])):
+            if d["moving"] and q["k"] > 0.0:
+                assert seen["sfmax"][k] >= 0.05, (spec["id"], k, seen["sfmax"])
+            if d["r0"] == "above":
+                assert ref[0][1][k]["dr"] < 0.0 and (q["k"] == 0.0 or ref[0][1][k]["ftotal"][3] < 0.0), (spec["id"], k)
+        reach["rzero"] = reach["rzero"] or seen["rzero"]
+        if spec["tilt"] and spec["springs"] and seen["zflag"]:
+            reach["zflag_sheared"] = True
+        if spec["newmask"] is not None:
+            at, e = spec["newmask"]
+            assert ref[at][1][e]["atoms"] > 0 and last[1][e]["atoms"] == 0 and last[1][e]["mass"] == 0.0 and not last[1][e]["ftotal"].any()
+            reach["emptied"] = True
+        if spec["free"] is not None:    # the free dimension decides: with the wrap taken there as well the energy is another
+            assert spec["nsteps"] == 0 and list(ref) == [0]
+            other = nets.postforce_reference(spec, P, periodic=(True, True, True))[0]
+            assert abs(other[0][4][0]["energy"] - ref[0][4][0]["energy"]) > 1e-6, (spec["id"], other[0][4][0]["energy"], ref[0][4][0]["energy"])
+            reach["decided"] = True
+    return reach
+
+
+def test_postforce_cases_meet_their_own_conditions(oracle):
+    """Needs the oracle, no GPU.  Every `postforce` case of the suite runs clean through the reference (no stale list, finite
+    throughout) and shows what its fit promises: every indenter with K > 0 touches at least 2 atoms at some read, never
+    reaches deeper than 0.8 A into an atom it pushes (the atom of the r == 0 case feels no force and is left out) and puts at
+    least 0.05 eV/A on one; every plane's atoms stay skin + 1.5 A clear of the faces whose remap would change their
+    coordinate along dim; every moving spring with K > 0 reaches |F| = 0.05 eV/A; a rest length above the distance pushes; a
+    case with a free dimension has another energy once the wrap is taken there as well.  Over the suite: in each of x, y and z
+    an atom in contact takes the wrap, in a sheared box in z and in y; an r == 0 contact is counted; in a sheared cell an
+    atom of a spring's group changes its z image flag in mid-run; a spring loses its group to a new mask."""
+    reach = postforce_conditions(SPECS["postforce"])
+    print(reach)
+    assert reach["wraps"] == {0, 1, 2} and reach["sheared_wraps"] >= {1, 2}, reach
+    assert reach["rzero"] and reach["zflag_sheared"] and reach["emptied"] and reach["decided"], reach
+
+
+def test_postforce_limits_are_the_references(oracle):
+    """Needs the oracle, no GPU.  The limits of the `postforce` net are the reference's own: over the suite's cases, against the
+    plain run,
+      (i)  every stage's atoms summed in a random order stays 100 times inside every limit, and
+      (ii) an error of +-1e-9 eV/A (uniform) on every force component at every step stays within a quarter of every limit;
+    a limit that differs from the project's bound for the quantity (nets.PF_START) is the larger of 100 x (i) and 4 x (ii),
+    rounded up in the second digit."""
+    worst = {"i": dict.fromkeys(nets.PF_START, 0.0), "ii": dict.fromkeys(nets.PF_START, 0.0)}
+    for spec in SPECS["postforce"]:
+        P, ref, _ = _postforce(spec)
+        for name, other in (("i", nets.postforce_reference(spec, P, permuted=True)[0]), ("ii", nets.postforce_reference(spec, P, dforce=1e-9)[0])):
+            w = nets.postforce_worst(spec, P, ref, other)
+            assert w["exact"] == 0, (spec["id"], name)
+            for k in worst[name]:
+                worst[name][k] = max(worst[name][k], w[k])
+            print(spec["id"], name, {k: f"{w[k]:.1e}" for k in worst[name]})
+    print("worst of (i):", {k: f"{v:.2e}" for k, v in worst["i"].items()})
+    print("worst of (ii):", {k: f"{v:.2e}" for k, v in worst["ii"].items()})
+    # after a change of the seed, the case count, the draw or the oracle's rounding, set nets.PF_LIMITS again from what is
+    # printed above -- never from what the device gives
+    for k, lim in nets.PF_LIMITS.items():
+        assert worst["i"][k] < 0.01 * lim, (k, worst["i"][k], lim)
+        assert worst["ii"][k] < 0.25 * lim, (k, worst["ii"][k], lim)
+        need = max(100.0 * worst["i"][k], 4.0 * worst["ii"][k])
+        assert lim == nets.PF_START[k] or lim < 1.2 * need, (k, lim, need, "a limit wider than the experiments ask for")
 
 
 def test_measure_grid_restatement():
