@@ -54,8 +54,10 @@ int mdp_device_count(void);
 int mdp_create(mdp_ctx **ctx, int device);
 int mdp_destroy(mdp_ctx *ctx);
 const char *mdp_last_error(const mdp_ctx *ctx);
-/* bytes of device memory THIS context holds (ctx = NULL: all contexts of the process): what Pair::memory_usage() should
- * add for the style's device-side lists and work arrays (the reference reports the lists it holds:
+/* bytes of device memory THIS context holds (ctx = NULL: all contexts of the process): EVERY device buffer of the context --
+ * lists, work arrays, tables, the domain's, the fixes' and the measurements' -- counted as it is reserved and released, so
+ * the contexts' figures add up to the process total and mdp_destroy takes the total back by exactly the context's.  What
+ * Pair::memory_usage() should add for the style's device side (the reference reports the lists it holds:
  * pair_rebomos.cpp:1113-1124) */
 double mdp_device_bytes(const mdp_ctx *ctx);
 /* host arrays are staged through pinned buffers of the context by default.  With MDP_HOST_REGISTER=1 large arrays

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void adf_hist_kernel(const Grid g, const int n
 
 } // namespace
 
-void mdp_adf_release(mdp_ctx *c)
+static void adf_release(mdp_ctx *c) // mdp_adf_off: the measurement's buffers go ahead of the context's end
 {
   MdpAdf &h = c->adf;
   h.member.release();
@@ -256,6 +256,6 @@ int mdp_adf_info(mdp_ctx *c, long long out[4])
   return mdp_measure_info(c->adf, c->adf.nbin, c->adf.ntriple, out);
 }
 
-int mdp_adf_off(mdp_ctx *c) { return mdp_measure_off(c, mdp_adf_release); }
+int mdp_adf_off(mdp_ctx *c) { return mdp_measure_off(c, adf_release); }
 
 } // extern "C"

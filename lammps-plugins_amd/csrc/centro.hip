@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void centro_kernel(const Grid g, const int nal
 
 } // namespace
 
-void mdp_centro_release(mdp_ctx *c)
+static void centro_release(mdp_ctx *c) // mdp_centro_off: the measurement's buffers go ahead of the context's end
 {
   MdpCentro &h = c->centro;
   h.bin.release();
@@ -206,6 +206,6 @@ int mdp_centro_info(mdp_ctx *c, long long out[4])
   return mdp_measure_info(c->centro, c->centro.nnn, c->centro.few, out);
 }
 
-int mdp_centro_off(mdp_ctx *c) { return mdp_measure_off(c, mdp_centro_release); }
+int mdp_centro_off(mdp_ctx *c) { return mdp_measure_off(c, centro_release); }
 
 } // extern "C"

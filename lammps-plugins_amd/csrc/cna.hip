@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void cna_kernel(const Grid g, const int nall, 
 
 } // namespace
 
-void mdp_cna_release(mdp_ctx *c)
+static void cna_release(mdp_ctx *c) // mdp_cna_off: the measurement's buffers go ahead of the context's end
 {
   MdpCna &h = c->cna;
   h.bin.release();
@@ -204,6 +204,6 @@ int mdp_cna_info(mdp_ctx *c, long long out[4])
   return mdp_measure_info(c->cna, 0, c->cna.over, out);
 }
 
-int mdp_cna_off(mdp_ctx *c) { return mdp_measure_off(c, mdp_cna_release); }
+int mdp_cna_off(mdp_ctx *c) { return mdp_measure_off(c, cna_release); }
 
 } // extern "C"

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void coord_count_kernel(const Grid g, const in
 
 } // namespace
 
-void mdp_coord_release(mdp_ctx *c)
+static void coord_release(mdp_ctx *c) // mdp_coord_off: the measurement's buffers go ahead of the context's end
 {
   MdpCoord &h = c->coord;
   h.tab.release();
@@ -132,6 +132,6 @@ int mdp_coord_info(mdp_ctx *c, long long out[4])
   return mdp_measure_info(c->coord, c->coord.ncol, c->coord.gbit, out);
 }
 
-int mdp_coord_off(mdp_ctx *c) { return mdp_measure_off(c, mdp_coord_release); }
+int mdp_coord_off(mdp_ctx *c) { return mdp_measure_off(c, coord_release); }
 
 } // extern "C"

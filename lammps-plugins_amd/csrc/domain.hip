@@ -380,16 +380,6 @@ __global__ __launch_bounds__(256) void dd_self_ghost_kernel(const int nself, con
   tag[nlocal + g] = tag[o];
 }
 
-template <typename T> void swap_buf(DevBuf<T> &a, DevBuf<T> &b)
-{
-  T *p = a.p;
-  a.p = b.p;
-  b.p = p;
-  const size_t c = a.cap;
-  a.cap = b.cap;
-  b.cap = c;
-}
-
 int sort_u64(mdp_ctx *c, const unsigned long long *kin, unsigned long long *kout, const int *vin, int *vout, size_t n,
              int bits)
 {
@@ -430,35 +420,6 @@ static int dd_require(mdp_ctx *c)
   if (!c->dd.on) return mdp_fail(c, MDP_ESTATE, "mdp_dd_setup not called");
   MDP_HIP(c, hipSetDevice(c->device));
   return MDP_OK;
-}
-
-extern "C" int mdp_dd_comm_destroy(mdp_ctx *c);
-
-void mdp_dd_release(mdp_ctx *c)
-{
-  MdpDomain &D = c->dd;
-  (void) mdp_dd_comm_destroy(c);
-  D.dest.release();
-  D.counters.release();
-  D.idx_a.release();
-  D.idx_b.release();
-  D.ent_atom.release();
-  D.ent_code.release();
-  D.ent_cnt.release();
-  D.ent_off.release();
-  D.sendlist.release();
-  D.type_tmp.release();
-  D.tag_tmp.release();
-  D.mask_tmp.release();
-  D.image_tmp.release();
-  D.key_a.release();
-  D.key_b.release();
-  D.sendshift.release();
-  D.v_tmp.release();
-  D.xq_tmp.release();
-  if (D.ev_moved) (void) hipEventDestroy(D.ev_moved);
-  D.ev_moved = nullptr;
-  D.on = false;
 }
 
 extern "C" {
@@ -623,7 +584,7 @@ int mdp_dd_migrate_end(mdp_ctx *c, int narrive, const double *d_buf)
     MDP_TRY(sort_u64(c, D.key_a.p, D.key_b.p, D.idx_a.p, D.idx_b.p, (size_t) ntot, 64));
     if (c->cfg.style == 1) { // rebomos: element-sorted runs of 32 atoms for the one-atom-row tile lists
       MDP_TRY(mdp_chunk_by_element(c, ntot, nnew, D.idx_b.p, D.idx_a.p, c->xq.p, nullptr, nullptr));
-      swap_buf(D.idx_a, D.idx_b);
+      D.idx_a.swap(D.idx_b);
     }
   }
   if (nnew) {
@@ -633,15 +594,15 @@ int mdp_dd_migrate_end(mdp_ctx *c, int narrive, const double *d_buf)
                                                   c->image_set ? c->image.p : nullptr, c->image_set ? D.image_tmp.p : nullptr);
     MDP_HIP(c, hipGetLastError());
   }
-  swap_buf(c->xq, D.xq_tmp);
-  swap_buf(c->v, D.v_tmp);
-  swap_buf(c->type, D.type_tmp);
-  swap_buf(c->tag, D.tag_tmp);
+  c->xq.swap(D.xq_tmp);
+  c->v.swap(D.v_tmp);
+  c->type.swap(D.type_tmp);
+  c->tag.swap(D.tag_tmp);
   if (c->mask_set) {
-    swap_buf(c->mask, D.mask_tmp);
+    c->mask.swap(D.mask_tmp);
     c->mask_n = nnew;
   }
-  if (c->image_set) swap_buf(c->image, D.image_tmp);
+  if (c->image_set) c->image.swap(D.image_tmp);
   c->nlocal = nnew;
   c->nghost = 0;
   c->nall = nnew;

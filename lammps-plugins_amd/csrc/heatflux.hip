@@ -61,8 +61,6 @@ int heatflux_require(mdp_ctx *c, const char *who)
 
 } // namespace
 
-void mdp_heatflux_release(mdp_ctx *c) { c->heatflux.part.release(); }
-
 extern "C" {
 
 int mdp_heatflux_sums(mdp_ctx *c, int groupbit, double out[8])

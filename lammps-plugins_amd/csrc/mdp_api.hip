@@ -794,111 +794,22 @@ int mdp_destroy(mdp_ctx *c)
   if (!c) return MDP_OK;
   (void) hipSetDevice(c->device);
   if (c->stream) (void) hipStreamSynchronize(c->stream);
-  mdp_dd_release(c);
-  c->aeam_frho.release();
-  c->aeam_rhor.release();
-  c->aeam_z2r.release();
-  c->aeam_rhor_v4.release();
-  c->aeam_rhor_d4.release();
-  c->aeam_z2r_v4.release();
-  c->aeam_z2r_d4.release();
-  c->aeam_pair_d8.release();
-  c->aeam_rhor_ys.release();
-  c->aeam_z2r_ys.release();
-  c->aeam_maps.release();
-  c->aeam_par_d.release();
-  c->aeam_par_i.release();
-  c->cut_tab.release();
-  c->xq.release();
-  c->xraw.release();
-  c->tag.release();
-  c->type.release();
-  c->f.release();
-  c->eatom.release();
-  c->vatom.release();
-  c->acc.release();
-  c->flags.release();
-  c->nb_off.release();
-  c->nb.release();
-  c->cand_cnt.release();
-  c->cand_off.release();
-  c->cand.release();
-  c->lj_off.release();
-  c->lj_cnt.release();
-  c->lj_split.release();
-  c->cl_flag.release();
-  c->cl_pos.release();
-  c->cl_order.release();
-  c->lj.release();
-  c->tu.release();
-  c->tmask.release();
-  c->lj16_in.release();
-  c->lj_len_in.release();
-  c->lj_split_in.release();
-  c->cand_stage.release();
-  c->lj_fixtab.release();
-  c->lj_fix_stamp.release();
-  c->xhold_prune.release();
-  c->tile_nu.release();
-  c->tile_flag.release();
-  c->lj16.release();
-  c->is_center.release();
-  c->class_list.release();
-  c->class_merged.release();
-  c->class_count.release();
-  c->pk_cand.release();
-  c->amask.release();
-  c->centre_paths.release();
-  c->xhold_all.release();
-  c->ovf.release();
-  c->rev.release();
-  c->rev16.release();
-  c->host_perm.release();
-  c->host_tagmap.release();
-  c->host_inv.release();
-  c->host_tag_dev.release();
-  c->host_img.release();
-  c->host_stage.release();
+  // what is no DevBuf: the communicator (before its buffers go), events, pinned host memory, the stream.  Every device
+  // buffer frees itself with the context
+  (void) mdp_dd_comm_destroy(c);
+  if (c->dd.ev_moved) (void) hipEventDestroy(c->dd.ev_moved);
   host_unregister_all(c);
   for (int k = 0; k < MDP_DOWN_CHUNKS; k++)
-    if (c->ev_down[k]) {
-      (void) hipEventDestroy(c->ev_down[k]);
-      c->ev_down[k] = nullptr;
-    }
+    if (c->ev_down[k]) (void) hipEventDestroy(c->ev_down[k]);
   for (int k = 0; k < MDP_UP_RING; k++) {
     if (c->h_up[k]) (void) hipHostFree(c->h_up[k]);
     if (c->ev_up[k]) (void) hipEventDestroy(c->ev_up[k]);
-    c->h_up[k] = nullptr;
-    c->ev_up[k] = nullptr;
   }
   if (c->h_down) (void) hipHostFree(c->h_down);
-  c->h_down = nullptr;
-  c->fnbr.release();
-  c->fown.release();
-  c->vslot.release();
-  c->scan_tmp.release();
-  c->rho.release();
-  c->fp.release();
-  c->ang_list.release();
-  c->ang_count.release();
-  c->v.release();
-  c->xhold.release();
-  c->rmass.release();
-  c->ghost_owner.release();
-  c->ghost_shift.release();
-  c->mass_type.release();
-  c->cell_of.release();
-  c->cell_perm.release();
-  c->cell_start.release();
-  c->sort_keys_a.release();
-  c->sort_keys_b.release();
-  c->sort_vals_b.release();
-  c->nb_cnt.release();
   for (int k = 0; k < 2; k++)
     if (c->ev_sflag[k]) (void) hipEventDestroy(c->ev_sflag[k]);
   if (c->h_pinned) (void) hipHostFree(c->h_pinned);
   if (c->h_small) (void) hipHostFree(c->h_small);
-  c->h_small = nullptr;
   if (c->ev_made)
     for (int i = 0; i < 8; i++) (void) hipEventDestroy(c->ev[i]);
   if (c->ev_sb[0])
@@ -906,28 +817,6 @@ int mdp_destroy(mdp_ctx *c)
       (void) hipEventDestroy(c->ev_sb[i]);
       (void) hipEventDestroy(c->ev_se[i]);
     }
-  c->nhc.st.release();
-  c->nhc.part.release();
-  c->lgv.st.release();
-  c->lgv.part.release();
-  c->lgv.overlap.release();
-  c->heat.st.release();
-  c->heat.part.release();
-  c->heat.count.release();
-  for (int s = 0; s < kStageCount; s++) mdp_postforce_release(c, s);
-  c->fire.st.release();
-  c->fire.part.release();
-  c->fire.fsave.release();
-  c->mask.release();
-  c->image.release();
-  mdp_msd_release(c);
-  mdp_rdf_release(c);
-  mdp_adf_release(c);
-  mdp_coord_release(c);
-  mdp_centro_release(c);
-  mdp_cna_release(c);
-  mdp_profile_release(c);
-  mdp_heatflux_release(c);
   if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
   delete c;
   return MDP_OK;
@@ -949,35 +838,8 @@ int mdp_set_stream(mdp_ctx *c, void *s)
 
 double mdp_device_bytes(const mdp_ctx *c)
 {
-  // this context's share: the capacities of ITS buffers (every DevBuf member of mdp_ctx and of its MdpDomain); the
-  // process-wide total of all contexts is mdp_device_bytes_counter()
-  if (!c) return (double) mdp_device_bytes_counter().load();
-  const MdpDomain &D = c->dd;
-  const size_t parts[] = {
-      c->aeam_frho.bytes(), c->aeam_rhor.bytes(), c->aeam_z2r.bytes(), c->aeam_rhor_v4.bytes(),
-      c->aeam_rhor_d4.bytes(), c->aeam_z2r_v4.bytes(), c->aeam_z2r_d4.bytes(), c->aeam_pair_d8.bytes(), c->cand_stage.bytes(),
-      c->aeam_rhor_ys.bytes(), c->aeam_z2r_ys.bytes(), c->aeam_maps.bytes(), c->xq.bytes(), c->xraw.bytes(),
-      c->host_perm.bytes(), c->host_tagmap.bytes(), c->host_inv.bytes(), c->host_tag_dev.bytes(), c->host_img.bytes(), c->host_stage.bytes(), c->tag.bytes(), c->type.bytes(), c->f.bytes(),
-      c->eatom.bytes(), c->vatom.bytes(), c->acc.bytes(), c->flags.bytes(), c->nb_off.bytes(), c->nb.bytes(),
-      c->cand_cnt.bytes(), c->cand_off.bytes(), c->cand.bytes(), c->lj_off.bytes(), c->lj_cnt.bytes(),
-      c->lj.bytes(), c->cl_flag.bytes(), c->cl_pos.bytes(), c->cl_order.bytes(), c->lj_split.bytes(),
-      c->tu.bytes(), c->tmask.bytes(), c->lj16_in.bytes(), c->lj_len_in.bytes(),
-      c->lj_split_in.bytes(), c->xhold_prune.bytes(), c->tile_nu.bytes(), c->tile_flag.bytes(),
-      c->lj16.bytes(), c->is_center.bytes(), c->class_list.bytes(), c->class_count.bytes(), c->pk_cand.bytes(),
-      c->amask.bytes(), c->rev.bytes(), c->rev16.bytes(), c->ovf.bytes(), c->xhold_all.bytes(),
-      c->fnbr.bytes(), c->fown.bytes(), c->vslot.bytes(), c->scan_tmp.bytes(), c->rho.bytes(), c->fp.bytes(),
-      c->ang_list.bytes(), c->ang_count.bytes(), c->v.bytes(), c->xhold.bytes(), c->rmass.bytes(),
-      c->ghost_owner.bytes(), c->ghost_shift.bytes(), c->mass_type.bytes(), c->cell_of.bytes(),
-      c->cell_perm.bytes(), c->cell_start.bytes(), c->sort_keys_a.bytes(), c->sort_keys_b.bytes(),
-      c->sort_vals_b.bytes(), c->nb_cnt.bytes(),
-      D.dest.bytes(), D.counters.bytes(), D.idx_a.bytes(), D.idx_b.bytes(), D.ent_atom.bytes(),
-      D.ent_code.bytes(), D.ent_cnt.bytes(), D.ent_off.bytes(), D.sendlist.bytes(), D.type_tmp.bytes(),
-      D.tag_tmp.bytes(), D.key_a.bytes(), D.key_b.bytes(), D.sendshift.bytes(), D.v_tmp.bytes(),
-      D.xq_tmp.bytes(), D.sbuf.bytes(), D.rbuf.bytes(), D.abuf.bytes(), D.cnt_dev.bytes(),
-  };
-  double sum = 0.0;
-  for (const size_t b : parts) sum += (double) b;
-  return sum;
+  // this context's share: every DevBuf inside mdp_ctx, as its ledger counts them; without a context, the process-wide total
+  return (double) (c ? c->ledger.bytes : mdp_device_bytes_counter().load());
 }
 
 int mdp_host_release(mdp_ctx *c, const void *ptr)

@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "devbuf.h"
 #include "mdpair_hip.h"
 
 #define MDP_NEIGHMASK 0x1FFFFFFF
@@ -31,45 +32,21 @@ static_assert(MDP_CLUSTER == 1 || MDP_CLUSTER == 2, "the Lennard-Jones kernels a
 #define MDP_NCLASS 20
 #define MDP_NCLASS_HALF 10
 
-// bytes of device memory currently held by the library's buffers in this process (memory_usage(), pair_rebomos.cpp:1113-1124)
-inline std::atomic<long long> &mdp_device_bytes_counter()
-{
-  static std::atomic<long long> bytes{0}; // several contexts (threads) allocate concurrently
-  return bytes;
-}
-
-// device buffer that only grows
-template <typename T> struct DevBuf {
-  T *p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t n, bool keep = false, hipStream_t s = nullptr)
+// every device allocation of the library: MdpBuf (devbuf.h) on the HIP allocator.  copy: the old contents into a grown
+// buffer, complete on return
+struct MdpHipMem {
+  using error = hipError_t;
+  using stream = hipStream_t;
+  static constexpr hipError_t ok = hipSuccess;
+  static hipError_t alloc(void **q, size_t bytes) { return hipMalloc(q, bytes); }
+  static void free(void *p) { (void) hipFree(p); }
+  static hipError_t copy(void *dst, const void *src, size_t bytes, hipStream_t s)
   {
-    if (n <= cap) return hipSuccess;
-    size_t ncap = n + n / 8 + 64;
-    T *q = nullptr;
-    hipError_t e = hipMalloc((void **) &q, ncap * sizeof(T));
-    if (e != hipSuccess) return e;
-    if (keep && p && cap) {
-      e = hipMemcpyAsync(q, p, cap * sizeof(T), hipMemcpyDeviceToDevice, s);
-      if (e != hipSuccess) return e;
-      e = hipStreamSynchronize(s);
-      if (e != hipSuccess) return e;
-    }
-    if (p) (void) hipFree(p);
-    mdp_device_bytes_counter() += (long long) ((ncap - cap) * sizeof(T));
-    p = q;
-    cap = ncap;
-    return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s);
+    return e != hipSuccess ? e : hipStreamSynchronize(s);
   }
-  void release()
-  {
-    if (p) (void) hipFree(p);
-    mdp_device_bytes_counter() -= (long long) (cap * sizeof(T));
-    p = nullptr;
-    cap = 0;
-  }
-  size_t bytes() const { return cap * sizeof(T); }
 };
+template <typename T> using DevBuf = MdpBuf<T, MdpHipMem>;
 
 // REBO-MoS parameters as the kernels see them: pair tables flattened [ti*2+tj]
 struct RebomosDev {
@@ -756,6 +733,8 @@ __device__ __forceinline__ void mdp_style_vote(const MdpStyleCheck &SC, const Md
 }
 
 struct mdp_ctx {
+  MdpLedger ledger;                       // bytes of every DevBuf between the two scopes: mdp_device_bytes(ctx)
+  MdpLedgerScope ledger_open{&ledger};    // (first and last members but for the ledger itself)
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
@@ -1002,6 +981,7 @@ struct mdp_ctx {
   bool ev_made = false;
   int ev_marks = 0;
   double t_ms[8] = {};
+  MdpLedgerScope ledger_close{nullptr};
 };
 
 int mdp_fail(mdp_ctx *c, int code, const char *fmt, ...);
@@ -1147,7 +1127,6 @@ int mdp_aeam_run_force_begin(mdp_ctx *c, int eflag, int vflag); // interior forc
 int mdp_aeam_run_force(mdp_ctx *c, int eflag, int vflag);
 int mdp_md_build_master_list(mdp_ctx *c);
 int mdp_md_build_neighbors_impl(mdp_ctx *c);
-void mdp_dd_release(mdp_ctx *c); // frees everything domain.hip / comm_rccl.hip hold
 int mdp_bin_atoms(mdp_ctx *c, double cutoff, const double lo[3], const double hi[3]); // fills c->grid, cell_perm, cell_start
 void mdp_time_mark(mdp_ctx *c, int k);
 void mdp_span_begin(mdp_ctx *c, int k); // per-phase device time as independent (begin, end) event pairs: aeam
@@ -1237,7 +1216,7 @@ inline void mdp_postforce_count_step(mdp_ctx *c)
 // _refuse_setup: what no stage's _setup goes with.  _commit: behind the last refusal of a _setup -- completes a deferred
 // final half with the stage off, zeroes st (`words` doubles), stores n, the bits and the n configurations (cfg_bytes each)
 // and restarts the stage at step 0, on.  _run, _state, _off: the entry points of those names behind their null checks.
-// _release: frees what stage s holds (_off, mdp_destroy).  mdp_refuse_if_on: the first stage that is on refuses `who`
+// _release: frees what stage s holds ahead of the context's end (_off).  mdp_refuse_if_on: the first stage that is on refuses `who`
 enum MdpRefuse { kRefuseOffFirst, kRefuseOneRank };
 int mdp_postforce_refuse_setup(mdp_ctx *c, int s);
 int mdp_postforce_commit(mdp_ctx *c, int s, int words, int n, const int *groupbit, void *cfg_dst, const void *cfg, size_t cfg_bytes);
@@ -1273,12 +1252,6 @@ template <class Bits = MdpSlotBits> Bits mdp_slot_bits(int n, const int *bit)
   }
   return B;
 }
-void mdp_msd_release(mdp_ctx *c); // frees what msd.hip holds
-void mdp_rdf_release(mdp_ctx *c); // frees what rdf.hip holds
-void mdp_adf_release(mdp_ctx *c); // frees what adf.hip holds
-void mdp_coord_release(mdp_ctx *c); // frees what coord.hip holds
-void mdp_centro_release(mdp_ctx *c); // frees what centro.hip holds
-void mdp_cna_release(mdp_ctx *c); // frees what cna.hip holds
 // measure_bin.hip, queued on the stream: a grid with cells >= cutoff / 2 over the padded hull of the brick (stencil: 2 cells each
 // way), every owned and ghost atom sorted into it, b.cell_start and the cell-ordered records b.rec = {x, y, z, code} with
 // code = (member ? type : 0) | (owned ? kBinOwned : 0).  member: by tag - 1 over 1 .. ntag, or nullptr for every atom; an atom
@@ -1316,8 +1289,6 @@ int mdp_hist_open(mdp_ctx *c, const char *who, const char *what, double r, const
 // ... and after its kernel: the words on the host; the last one counts the atoms whose tag the member table does not hold
 int mdp_hist_download(mdp_ctx *c, const char *who, const char *setup, const unsigned long long *d_out, int nout, int ntag,
                       std::vector<unsigned long long> &host);
-void mdp_profile_release(mdp_ctx *c); // frees what profile.hip holds
-void mdp_heatflux_release(mdp_ctx *c); // frees what heatflux.hip holds
 // the end of an mdp_{msd,rdf,profile}_setup: the measurement is on, under a serial that is new in this process (one
 // counter for all kinds and contexts: unique per setup, and growing)
 inline void mdp_measure_start(MdpMeasure &h)
@@ -1335,7 +1306,7 @@ inline int mdp_measure_info(const MdpMeasure &h, const long long a, const long l
   out[3] = h.on ? h.serial : 0;
   return MDP_OK;
 }
-// mdp_*_off
+// mdp_*_off: `release` is the kind's own (file-local): its buffers go now, not with the context
 inline int mdp_measure_off(mdp_ctx *c, void (*release)(mdp_ctx *))
 {
   if (!c) return MDP_EINVAL;

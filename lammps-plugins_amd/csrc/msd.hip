@@ -86,7 +86,7 @@ int msd_require(mdp_ctx *c, const char *who)
 
 } // namespace
 
-void mdp_msd_release(mdp_ctx *c)
+static void msd_release(mdp_ctx *c) // mdp_msd_off: the measurement's buffers go ahead of the context's end
 {
   c->msd.x0.release();
   c->msd.xu.release();
@@ -171,6 +171,6 @@ int mdp_msd_info(mdp_ctx *c, long long out[4])
   return mdp_measure_info(c->msd, c->msd.ntag, c->msd.gbit, out);
 }
 
-int mdp_msd_off(mdp_ctx *c) { return mdp_measure_off(c, mdp_msd_release); }
+int mdp_msd_off(mdp_ctx *c) { return mdp_measure_off(c, msd_release); }
 
 } // extern "C"

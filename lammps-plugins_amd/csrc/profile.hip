@@ -185,7 +185,7 @@ int profile_grid(const int n) { return mdp_measure_grid(nblk(n), kProfMaxGrid); 
 
 } // namespace
 
-void mdp_profile_release(mdp_ctx *c)
+static void profile_release(mdp_ctx *c) // mdp_profile_off: the measurement's buffers go ahead of the context's end
 {
   c->profile.part.release();
   c->profile.out.release();
@@ -300,6 +300,6 @@ int mdp_profile_info(mdp_ctx *c, long long out[4])
   return mdp_measure_info(c->profile, c->profile.rows, c->profile.ndim, out);
 }
 
-int mdp_profile_off(mdp_ctx *c) { return mdp_measure_off(c, mdp_profile_release); }
+int mdp_profile_off(mdp_ctx *c) { return mdp_measure_off(c, profile_release); }
 
 } // extern "C"

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void rdf_hist_kernel(const Grid g, const int n
 
 } // namespace
 
-void mdp_rdf_release(mdp_ctx *c)
+static void rdf_release(mdp_ctx *c) // mdp_rdf_off: the measurement's buffers go ahead of the context's end
 {
   MdpRdf &h = c->rdf;
   h.member.release();
@@ -183,6 +183,6 @@ int mdp_rdf_info(mdp_ctx *c, long long out[4])
   return mdp_measure_info(c->rdf, c->rdf.nbin, c->rdf.npair, out);
 }
 
-int mdp_rdf_off(mdp_ctx *c) { return mdp_measure_off(c, mdp_rdf_release); }
+int mdp_rdf_off(mdp_ctx *c) { return mdp_measure_off(c, rdf_release); }
 
 } // extern "C"

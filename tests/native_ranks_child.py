@@ -6,6 +6,7 @@ process, each with its own context -- what a C++ host driving several GPUs from 
 object for its lifetime, which is why these cases do not run inside the pytest process (its one-rank tests use RCCL).
 
 usage: native_ranks_child.py OUT.json [case ...]      prints nothing; writes {case: result | {"error": text}}"""
+import gc
 import json
 import os
 import sys
@@ -129,8 +130,12 @@ def case_steps(style, world, pure=False, langevin=None):
     aeam's fp / ghost-force exchange behind the interior tiles, prunings that send single ranks down the blocking order"""
     steps, thermo_at = (60, (20, 40)) if style == "rebomos" else (48, (16, 32))
     s, v0, one = _one_rank(style, pure, steps, thermo_at, langevin)
+    gc.collect()
+    bytes_before = float(capi.lib().mdp_device_bytes(None))     # no context is alive: every rank_fn closes its own
     many = _trajectory(world, style, s, v0, steps, True, thermo_at, langevin)
-    return _compare(s, one, many)
+    out = _compare(s, one, many)
+    out["device_bytes"] = [bytes_before, float(capi.lib().mdp_device_bytes(None))]   # before the first rank's context, after the last close
+    return out
 
 
 def case_fixed_policies():

@@ -70,6 +70,15 @@ def test_whole_steps_on_n_ranks_follow_the_one_rank_trajectory(results, style, w
         assert len(set(r["overlapped"])) > 1 or max(r["overlapped"]) < 48   # single ranks took the blocking order
 
 
+@pytest.mark.parametrize("style,world", [("rebomos", 2), ("aeam", 4)])
+def test_closing_every_rank_gives_all_device_memory_back(results, style, world):
+    """mdp_device_bytes(NULL) before the first rank's context of a step-mode case and after the last rank's close: equal to the
+    byte.  The ranks' transport buffers (send, receive, all-reduce, counts) and the words of the `check yes` decision that
+    step mode gathers are freed with the context like every other buffer"""
+    before, after = _case(results, f"{style}_{world}")["device_bytes"]
+    assert after == before
+
+
 @pytest.mark.parametrize("world", [2, 4])
 def test_pure_metal_bricks_skip_the_reverse_exchange_on_every_rank(results, world):
     r = _case(results, f"aeam_pure_{world}")

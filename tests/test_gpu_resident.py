@@ -1,5 +1,6 @@
 """GPU, resident mode: device neighbor build + device NVE + device thermo around the REBO-MoS hot
 path reproduce the reference log (config #2, in.rebomos-bulk) without x/f ever visiting the host."""
+import gc
 import json
 import os
 
@@ -8,6 +9,7 @@ import pytest
 
 from conftest import GOLDEN, POT_AEAM, POT_REBOMOS
 from lammps_plugins_amd.host import capi, resident, system as S
+import bathsref
 import hostplan
 import mdref
 
@@ -173,6 +175,117 @@ def test_device_bytes_are_reported_per_context():
     ctx1.close()
     assert ctx2.device_bytes() == b2
     ctx2.close()
+
+
+def _total_bytes():
+    return float(capi.lib().mdp_device_bytes(None))
+
+
+def _loaded_context(monkeypatch, s, v0, by_tag):
+    """a resident rebomos brick of 1 152 atoms (several tiles; the smallest bulk system the fix tests bin) that has reserved
+    what a context can hold next to each other: the lists of a build, the hot queues of the tile kernel (MDP_LJ_QUEUE=1), a
+    tallying compute, a group mask, image flags, a Langevin thermostat, an indenter, a tether spring, and all eight
+    measurements set up and read once.  The domain is resident.DeviceDomain, whose set-up ends in the device's
+    reneighbouring (bins, lists): the measurements need mdp_dd_setup, which hostplan's domain of _domain does without."""
+    monkeypatch.setenv("MDP_LJ_QUEUE", "1")
+    ctx = capi.Context(0)
+    p = capi.read_rebomos_file(POT_REBOMOS)
+    ctx.rebomos_set_params(p)
+    skin = 2.0
+    cutghost = 3.0 * p.rcmax[0][0] + skin
+    d = resident.DeviceDomain(ctx, capi.STYLE_REBOMOS, s, cutghost, skin, [0, 0, 1], v0=v0)
+    d.set_group(by_tag, bathsref.INTEGRATE_BIT)
+    d.track_images()
+    d.compute(3, 5)                                   # (per-atom energy and virial: what the heat current reads)
+    assert ctx.rebomos_list_info()["tiled"] == 1
+    d.langevin(300.0, 300.0, 0.1, 4711)
+    d.indent([dict(shape="plane", side="lo", dim=2, k=5.0, c=(0.0, 0.0, s.box.lo[2] - 5.0), bit=0)])   # (below every atom)
+    d.spring([dict(k=1.0, c=(0.0, 0.0, None), bit=bathsref.INTEGRATE_BIT)])
+    assert ctx.indent_state(0)["contacts"] >= 0 and ctx.spring_state(0)["atoms"] > 0
+    d.step(3, 5)                                      # the thermostat's and the stages' kernels in a step
+    assert ctx.heatflux_sums()[6] == s.n
+    before = ctx.device_bytes()
+    d.rdf(50, cutghost - skin, [(1, 1), (1, 2)])
+    assert ctx.device_bytes() > before                # a set-up that reserves shows in the context's figure
+    d.msd()
+    d.adf(45, [((1, 2), (1, 2), (1, 2), 0.0, 2.8, 0.0, 2.8)])
+    d.coord(3.0)
+    d.centro(6, 3.6)
+    d.cna(3.6)
+    d.profile([2], [5], group_bit=bathsref.INTEGRATE_BIT)
+    assert d.msd_read().shape == (4,)
+    assert d.rdf_read()[0].sum() > 0 and d.adf_read()[0].sum() > 0
+    assert d.coord_read()[1].max() > 0
+    d.centro_read()
+    d.cna_read()
+    assert d.profile_read()[0].sum() > 0
+    return ctx, d
+
+
+@pytest.fixture(scope="module")
+def loaded_case():
+    s = S.replicate(S.rebomos_bulk_cell(), (2, 2, 1))
+    return s, S.gaussian_velocities(s, 300.0, seed=91), bathsref.masks(s)[0]
+
+
+def test_destroying_contexts_leaves_no_device_memory_behind(monkeypatch, oracle, loaded_case):
+    """mdp_device_bytes(NULL) is back where it started, to the byte, once every context is closed: a resident context holding
+    everything _loaded_context lists, a second resident one with what refuses to stand next to that (heat sources, then a
+    Nose-Hoover chain) and a host-linked one with the device integrator (mdp_hnve_setup, one initial half).  Before the
+    buffers freed themselves mdp_destroy went by a hand-kept list that missed five of them, xq_cell (32 bytes per atom, reserved
+    whenever atoms are binned) among them."""
+    s, v0, by_tag = loaded_case
+    gc.collect()                                      # (contexts earlier tests let go of without closing them)
+    t0 = _total_bytes()
+    ctx, d = _loaded_context(monkeypatch, s, v0, by_tag)
+    p = capi.read_rebomos_file(POT_REBOMOS)
+    ctx2 = capi.Context(0)
+    ctx2.rebomos_set_params(p)
+    d2 = resident.DeviceDomain(ctx2, capi.STYLE_REBOMOS, s, 3.0 * p.rcmax[0][0] + 2.0, 2.0, [0, 0, 1], v0=v0)
+    d2.set_group(by_tag, bathsref.INTEGRATE_BIT)
+    d2.compute(0, 0)
+    d2.heat([dict(eflux=1e-3, nevery=1, bit=bathsref.BATH_BITS[0])])
+    d2.step(0, 0)
+    assert d2.heat_state(0)["applied"] >= 1
+    d2.heat_off()
+    d2.thermostat(300.0, 300.0, 0.1, nf=3.0 * int((by_tag & bathsref.INTEGRATE_BIT != 0).sum()) - 3.0, last=10)
+    d2.step(0, 0)
+    # host-linked: the host's atoms and ghosts, the integrator on the device
+    P = oracle.rebomos_params(POT_REBOMOS)
+    eng = mdref.RebomosCPU(oracle, P, s, skin=2.0)
+    ctx3 = capi.Context(0)
+    ctx3.rebomos_set_params(p)
+    ctx3.set_box_host(s.box)
+    ctx3.set_atoms_host(eng.nlocal, eng.all_positions(s.x), eng.type_all, eng.tag_all, 2, map_=[0, 0, 1])
+    ctx3.set_skin(2.0)
+    ctx3.hnve_setup(0.001, S.FTM2V, s.mass)
+    ctx3.hnve_upload_v(v0)
+    ctx3.rebomos_compute_host(eng.nlocal, eflag=0, vflag=0)
+    ctx3.hnve_initial()
+    held = [c.device_bytes() for c in (ctx, ctx2, ctx3)]
+    print(f"device bytes: {held} in three contexts, {_total_bytes() - t0:.0f} in the process since the start")
+    assert min(held) > 0 and sum(held) == _total_bytes() - t0
+    for c in (ctx, ctx2, ctx3):
+        c.close()
+    assert _total_bytes() == t0
+
+
+def test_a_context_reports_every_device_buffer_it_holds(monkeypatch, loaded_case):
+    """while one fully loaded context is alone, its figure IS what the process has taken since: every buffer of the context, at
+    any depth, counts in its ledger, so a buffer left out of the per-context figure (as the fixes', the measurements' and a dozen
+    others were while the figure was a hand-kept sum) shows here as a difference"""
+    s, v0, by_tag = loaded_case
+    gc.collect()
+    t0 = _total_bytes()
+    ctx, d = _loaded_context(monkeypatch, s, v0, by_tag)
+    try:
+        assert ctx.device_bytes() == _total_bytes() - t0
+        before = ctx.device_bytes()
+        ctx.rdf_off()                                 # an early release leaves both figures together
+        assert ctx.device_bytes() < before and ctx.device_bytes() == _total_bytes() - t0
+    finally:
+        ctx.close()
+    assert _total_bytes() == t0
 
 
 @pytest.mark.parametrize("style", ["rebomos", "aeam"])
