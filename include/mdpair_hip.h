@@ -691,6 +691,57 @@ int mdp_spring_run(mdp_ctx *ctx, long long first);
 int mdp_spring_state(mdp_ctx *ctx, int k, double *out /* MDP_SPRING_STATE_LEN */);
 int mdp_spring_off(mdp_ctx *ctx);
 
+/* ---- Prescribed forces on groups (LAMMPS fix setforce, fix addforce and fix aveforce with constant values; the plugin
+ * styles `fix setforce/mdp`, `fix addforce/mdp`, `fix aveforce/mdp`) -----
+ * Up to MDP_GFORCE_MAX slots, slot k on the owned atoms whose mask has groupbit[k]; a bit of 0 means every owned atom and
+ * needs no mask.  The slots act in order k = 0 .. n - 1 on one atom's force, as LAMMPS' fixes do in the order of their
+ * definition.  With g the atom's force as the slots before k left it, f the slot's values and use[d] == 0 LAMMPS' NULL:
+ *     SET:  F_k += g;                                  then g[d] = f[d] where use[d]
+ *     ADD:  F_k += g,  E_k -= f . xu  (xu = x + h . image);  then g += f
+ *     AVE:  F_k += g,  N_k += 1;  then g[d] = F_k[d] / N_k + f[d] where use[d], the sums over the whole group
+ * F_k is LAMMPS' f_ID[1..3] of all three styles (the group's total force before the fix acted), E_k the f_ID of addforce.
+ * Only an AVE slot needs a sum over the group before an atom's later force is known, so a slot must not share atoms with
+ * an AVE slot in front of it: then an atom's slots are local up to at most one AVE, the last of them, and the pass walks
+ * them in one go on a running force in registers.  Every other sharing is allowed.
+ * The pass: per block and slot the sums of F_k and E_k and the atom counts in fixed slots; one workgroup that adds the
+ * slots in a fixed order and leaves the state and, for AVE slots, the value to write in device memory; one lane per owned
+ * atom that writes the result into f.  With no AVE slot on the first kernel writes f itself and the pass is two launches.
+ * No float atomics and no host wait: a run is bitwise reproducible, and the same whether or not the host defers final
+ * halves.  An atom in no slot is neither read nor written.
+ * Every kick of v by f begins with the pass unless the forces the context holds have had theirs already -- behind the
+ * indenters' and the springs' passes when those are on, and in front of the Langevin force, which the kick itself adds:
+ * a bath atom under SET or AVE still feels its bath.  The flag is cleared behind every initial half and by _setup / _run,
+ * under the rules of mdp_indent_* (above), call for call.
+ *   setup:  replaces the slots that are on.  A final half pending at the call completes first, without them.
+ *           Refused (MDP_EINVAL / MDP_ESTATE, each with its cause, before anything on the context changes): n outside
+ *           1 .. MDP_GFORCE_MAX, an unknown kind, a value that is not finite, an ADD slot with a dimension off, a group bit
+ *           with no mask for the current atoms, a slot whose group holds no atom, a slot that shares atoms with an AVE
+ *           slot in front of it (the message gives the count and both slots), an ADD slot without image flags
+ *           (mdp_md_set_image) or on a host-linked context (its host keeps the image flags; SET and AVE do run there), a
+ *           brick of several ranks, the minimiser, the Nose-Hoover chain or heat sources on the context -- those calls in
+ *           turn refuse while the stage is on.  Langevin thermostats, indenters and springs are welcome.  A mask upload
+ *           while the stage is on counts the sharing again and fails with the same message (the mask stays; the next pass
+ *           refuses too), as a mask upload does under heat sources.
+ *   run:    a final half pending at the call completes first, with the pass of its step if that is still due; the forces
+ *           the context holds then count as those of step `first`, without a pass.
+ *   state:  blocking; completes a deferred final half, and runs the pass if the current forces have not had it.
+ *           out[0] E_k (0 unless ADD), [1..4) F_k, [4] the atoms of the slot's group, [5] the step these belong to,
+ *           [6..9) the value written or added per dimension (AVE: the average plus f; 0 where not used), [9] passes
+ *           since setup.
+ *   off:    a pending final half completes first, with its pass; frees what was held. */
+#define MDP_GFORCE_MAX 4
+#define MDP_GFORCE_STATE_LEN 10
+enum { MDP_GFORCE_SET = 0, MDP_GFORCE_ADD = 1, MDP_GFORCE_AVE = 2 };
+typedef struct {
+  int kind;      /* MDP_GFORCE_SET, _ADD, _AVE */
+  int use[3];    /* 0: the dimension is left alone (LAMMPS' NULL); an ADD slot has all three on */
+  double f[3];   /* force */
+} mdp_gforce_config;
+int mdp_gforce_setup(mdp_ctx *ctx, int n, const mdp_gforce_config *cfg, const int *groupbit);
+int mdp_gforce_run(mdp_ctx *ctx, long long first);
+int mdp_gforce_state(mdp_ctx *ctx, int k, double *out /* MDP_GFORCE_STATE_LEN */);
+int mdp_gforce_off(mdp_ctx *ctx);
+
 /* ---- FIRE minimiser on the device (LAMMPS min_style fire, FIRE 2.0 with the eulerimplicit integrator and LAMMPS' defaults)
  * For a resident context on one rank, after mdp_md_setup + mdp_dd_setup (one brick) + mdp_dd_reneighbor.  An iteration
  * is two small launches next to the force compute: per-block partial sums of v.f, v.v, f.f and the largest |v_c| in

@@ -655,7 +655,7 @@ template <int NB> int lgv_final(mdp_ctx *c, bool writeback)
 // plain.  lgv_writeback = false: the forces of a new run's setup come next, so f stays as the compute left it.
 int md_final_half(mdp_ctx *c, bool lgv_writeback = true)
 {
-  MDP_TRY(mdp_postforce_apply(c)); // (indenters, then springs: post_force of the step this half completes)
+  MDP_TRY(mdp_postforce_apply(c)); // (indenters, springs, group forces: post_force of the step this half completes)
   if (c->nhc.on) return mdp_nhc_final(c);
   if (c->lgv.on) return c->lgv.many() ? lgv_final<MDP_LANGEVIN_MAXBATH>(c, lgv_writeback) : lgv_final<1>(c, lgv_writeback);
   bool masked = false;
@@ -725,7 +725,7 @@ int md_launch_kernel(mdp_ctx *c, bool with_final, int *flag, double trigsq, doub
 int md_launch_advance(mdp_ctx *c, bool with_final, int *flag, double trigsq, double hardsq, const MdpStyleCheck &sc,
                       bool zero_f, double *dset, double *dclr)
 {
-  MDP_TRY(mdp_postforce_apply(c)); // (indenters, then springs: post_force of the forces this kernel kicks with first)
+  MDP_TRY(mdp_postforce_apply(c)); // (indenters, springs, group forces: post_force of the forces this kernel kicks with first)
   // a final half pending across a thermostat set-up (mdp_nhc_setup / _run, mdp_langevin_run by a host that does not
   // defer it) goes first, on its own, and leaves f as it was: the setup of the new run sees the compute's forces alone,
   // as after Verlet::setup
@@ -777,6 +777,7 @@ static int set_mask(mdp_ctx *c, const int *mask)
   if (!mask) {
     c->mask_set = false;
     c->mask_n = 0;
+    c->gforce.counted = false;
     return mdp_heat_mask(c, "");
   }
   MDP_HIP(c, hipSetDevice(c->device));
@@ -789,6 +790,7 @@ static int set_mask(mdp_ctx *c, const int *mask)
   c->lgv.disjoint_checked = false;
   if (c->lgv.many()) MDP_TRY(mdp_lgv_check_disjoint(c, c->md ? "mdp_md_set_mask" : "mdp_hnve_set_mask"));
   if (c->heat.on) MDP_TRY(mdp_heat_mask(c, c->md ? "mdp_md_set_mask" : "mdp_hnve_set_mask"));
+  if (c->gforce.on) MDP_TRY(mdp_gforce_mask(c, c->md ? "mdp_md_set_mask" : "mdp_hnve_set_mask"));
   return MDP_OK;
 }
 

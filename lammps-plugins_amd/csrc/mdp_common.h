@@ -344,11 +344,11 @@ static constexpr int kHeatScale = 0, kHeatVcm = 1, kHeatKe = 4, kHeatM = 5, kHea
                      kHeatWords = 12, kHeatErr = MDP_HEAT_MAXSRC * kHeatWords, kHeatTotal = kHeatErr + 2;
 static constexpr int kHeatW = 5 * MDP_HEAT_MAXSRC; // per source: sum m v.v, m vx, m vy, m vz, m
 // Post-force stages: the device fixes that add a force in front of every kick that first consumes a compute's forces
-// (the indenters, then the tether springs: kMdpStages below, postforce.hip).  The host keeps the configuration, the number
+// (the indenters, then the tether springs, then the prescribed group forces: kMdpStages below, postforce.hip).  The host keeps the configuration, the number
 // of initial halves since the stage's _run and whether the current forces have had the stage's pass; the sums live on the
 // device.  What every stage keeps:
-static constexpr int kStageSlots = 4; // indenters, springs of one context
-static_assert(MDP_INDENT_MAX == kStageSlots && MDP_SPRING_MAX == kStageSlots, "a stage has four slots");
+static constexpr int kStageSlots = 4; // indenters, springs, group-force slots of one context
+static_assert(MDP_INDENT_MAX == kStageSlots && MDP_SPRING_MAX == kStageSlots && MDP_GFORCE_MAX == kStageSlots, "a stage has four slots");
 struct MdpPostForce {
   bool on = false;
   bool applied = false;     // the forces the context holds have had this stage's pass.  Set by mdp_postforce_apply, cleared
@@ -378,6 +378,16 @@ struct MdpSpring : MdpPostForce {
 };
 static constexpr int kSprW = 5 * MDP_SPRING_MAX; // per spring: sum m xu, m yu, m zu, m_hi, m_lo (m = m_hi + m_lo, spring.hip)
 static constexpr int kSprF = MDP_SPRING_MAX * MDP_SPRING_STATE_LEN, kSprTotal = kSprF + 4 * MDP_SPRING_MAX;
+// Prescribed group forces (gforce.hip): LAMMPS fix setforce, addforce and aveforce with constant values, written into f by
+// the stage's pass, behind the springs'.  st: slot k keeps its MDP_GFORCE_STATE_LEN state words (mdp_gforce_state layout) at
+// st + k * MDP_GFORCE_STATE_LEN -- words [6..9) of an AVE slot are what the apply kernel writes; part: kGfW per block
+struct MdpGforce : MdpPostForce {
+  mdp_gforce_config cfg[MDP_GFORCE_MAX];
+  bool counted = false;     // the AVE sharing rule has been counted for the current mask (gforce.hip)
+  DevBuf<int> cpart;        // per-block atom counts, MDP_GFORCE_MAX per block
+  DevBuf<int> count;        // [MDP_GFORCE_MAX + MDP_GFORCE_MAX^2] the counts of a set-up or mask upload
+};
+static constexpr int kGfW = 5 * MDP_GFORCE_MAX; // per slot: the sums of fx, fy, fz before the slot acted, its energy, a spare word
 // FIRE minimiser (fire.hip): the control block lives in st on the device; the host keeps the configuration and what it
 // has queued.  Control block, in doubles (flags and counters as whole numbers):
 enum MdpFireWord {
@@ -906,6 +916,7 @@ struct mdp_ctx {
   MdpHeat heat;                    // constant-flux heat sources behind every final half (mdp_heat_setup)
   MdpIndent indent;                // indenters in front of the kicks (mdp_indent_setup)
   MdpSpring spring;                // tether springs in front of the kicks, behind the indenters (mdp_spring_setup)
+  MdpGforce gforce;                // prescribed group forces in front of the kicks, behind the springs (mdp_gforce_setup)
   // groups (mdp_md_set_mask / mdp_hnve_set_mask, mdp_integrate_group, mdp_langevin_group)
   DevBuf<int> mask;                // [nlocal] atom->mask: device order (resident; permuted and migrated with the atoms) or the host's order
   bool mask_set = false;
@@ -1173,14 +1184,18 @@ inline void mdp_heat_count_step(mdp_ctx *c)
 }
 int mdp_heat_mask(mdp_ctx *c, const char *who);
 int mdp_heat_check(mdp_ctx *c);
-// The post-force stages of a context, in the order their passes run (the order only affects the rounding of f).  base: the
+// prescribed group forces (gforce.hip) when c->gforce.on: a mask was uploaded (counts the AVE sharing rule again)
+int mdp_gforce_mask(mdp_ctx *c, const char *who);
+// The post-force stages of a context, in the order their passes run (between the first two the order only affects the
+// rounding of f; the group forces come last because setforce and aveforce overwrite what is there).  base: the
 // stage's MdpPostForce; pass: its kernels for the forces the context holds, which are those of step first + nhalf
-// (indent.hip, spring.hip); api, many, one: the nouns of its messages.  The rule they share stands here and in
+// (indent.hip, spring.hip, gforce.hip); api, many, one: the nouns of its messages.  The rule they share stands here and in
 // postforce.hip alone: a pass runs exactly once for the forces the context holds, in front of the kick that first consumes
 // them or of a state read, and a stage's pass never runs before the passes of the stages in front of it that are due.
 int mdp_indent_pass(mdp_ctx *c);
 int mdp_spring_pass(mdp_ctx *c);
-enum MdpStageId { kStageIndent = 0, kStageSpring, kStageCount };
+int mdp_gforce_pass(mdp_ctx *c);
+enum MdpStageId { kStageIndent = 0, kStageSpring, kStageGforce, kStageCount };
 struct MdpStage {
   MdpPostForce &(*base)(mdp_ctx *);
   int (*pass)(mdp_ctx *);
@@ -1189,6 +1204,7 @@ struct MdpStage {
 inline constexpr MdpStage kMdpStages[kStageCount] = {
     {[](mdp_ctx *c) -> MdpPostForce & { return c->indent; }, mdp_indent_pass, "mdp_indent", "indenters", "indenter"},
     {[](mdp_ctx *c) -> MdpPostForce & { return c->spring; }, mdp_spring_pass, "mdp_spring", "springs", "spring"},
+    {[](mdp_ctx *c) -> MdpPostForce & { return c->gforce; }, mdp_gforce_pass, "mdp_gforce", "group forces", "group force"},
 };
 // brings the forces the context holds up to date through stage `through`: the passes that are on and not `applied`, in
 // list order.  md_final_half and md_launch_advance (md.hip) call it first thing, for all stages

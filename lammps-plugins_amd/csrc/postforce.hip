@@ -1,7 +1,7 @@
-// The life cycle that the post-force stages share (kMdpStages, mdp_common.h: the indenters, then the tether springs):
+// The life cycle that the post-force stages share (kMdpStages, mdp_common.h: the indenters, the tether springs, the group forces):
 // what a _setup refuses and commits, _run, the common part of _state, _off, and the refusals of the modules that do not
 // go with a stage.  The per-step part (mdp_postforce_apply, mdp_postforce_count_step) is inline in mdp_common.h.  The
-// kernels, the passes and the argument checks of a kind stay in its own file (indent.hip, spring.hip).
+// kernels, the passes and the argument checks of a kind stay in its own file (indent.hip, spring.hip, gforce.hip).
 #include "mdp_common.h"
 
 #include <cstring>
@@ -44,7 +44,8 @@ int mdp_postforce_commit(mdp_ctx *c, int s, int words, int n, const int *groupbi
   }
   MDP_HIP(c, h.st.reserve(words));
   const double zero[kSprTotal] = {};
-  static_assert(kSprTotal >= MDP_INDENT_MAX * MDP_INDENT_STATE_LEN, "the state words of the largest stage");
+  static_assert(kSprTotal >= MDP_INDENT_MAX * MDP_INDENT_STATE_LEN && kSprTotal >= MDP_GFORCE_MAX * MDP_GFORCE_STATE_LEN,
+                "the state words of the largest stage");
   MDP_TRY(mdp_write_small(c, h.st.p, zero, sizeof(double) * words));
   h.n = n;
   for (int k = 0; k < kStageSlots; k++) h.bit[k] = k < n ? groupbit[k] : 0;
@@ -96,6 +97,10 @@ void mdp_postforce_release(mdp_ctx *c, int s)
   if (s == kStageSpring) {
     c->spring.cpart.release();
     c->spring.count.release();
+  }
+  if (s == kStageGforce) {
+    c->gforce.cpart.release();
+    c->gforce.count.release();
   }
 }
 

@@ -75,6 +75,11 @@ class SpringConfig(C.Structure):
     """mirror of mdp_spring_config"""
     _fields_ = [("k", C.c_double), ("r0", C.c_double), ("c", C.c_double * 3), ("use", C.c_int * 3), ("vel", C.c_double * 3)]
 SPRING_MAX, SPRING_STATE_LEN = 4, 16   # MDP_SPRING_MAX, MDP_SPRING_STATE_LEN of include/mdpair_hip.h
+class GforceConfig(C.Structure):
+    """mirror of mdp_gforce_config"""
+    _fields_ = [("kind", C.c_int), ("use", C.c_int * 3), ("f", C.c_double * 3)]
+GFORCE_MAX, GFORCE_STATE_LEN = 4, 10   # MDP_GFORCE_MAX, MDP_GFORCE_STATE_LEN of include/mdpair_hip.h
+GFORCE_KINDS = {"set": 0, "add": 1, "ave": 2}
 class FireConfig(C.Structure):
     _fields_ = [("etol", C.c_double), ("ftol", C.c_double), ("maxiter", C.c_longlong), ("maxeval", C.c_longlong),
                 ("dmax", C.c_double), ("tmax", C.c_double), ("tmin", C.c_double), ("delaystep", C.c_int),
@@ -137,6 +142,7 @@ EXPORTS = [
     "mdp_heat_setup", "mdp_heat_run", "mdp_heat_state", "mdp_heat_off",
     "mdp_indent_setup", "mdp_indent_run", "mdp_indent_state", "mdp_indent_off",
     "mdp_spring_setup", "mdp_spring_run", "mdp_spring_state", "mdp_spring_off",
+    "mdp_gforce_setup", "mdp_gforce_run", "mdp_gforce_state", "mdp_gforce_off",
 ]
 
 
@@ -715,6 +721,35 @@ class Context:
 
     def spring_off(self):
         self._ck(self.L.mdp_spring_off(self.h))
+
+    # ---------------- prescribed group forces in front of the kicks (fix setforce/mdp, addforce/mdp, aveforce/mdp)
+    def gforce_setup(self, slots):
+        """mdp_gforce_setup: slots is a list of dicts kind ("set", "add", "ave" or 0, 1, 2), f (three entries, None for a
+        dimension that is left alone, LAMMPS' NULL), and optionally bit (the group bit; 0: every owned atom).  They act in
+        list order on an atom's force"""
+        n = len(slots)
+        cfgs, bits = _slots(GforceConfig, n)
+        for k, q in enumerate(slots):
+            cfgs[k].kind = GFORCE_KINDS.get(q["kind"], q["kind"])
+            cfgs[k].f[:] = [0.0 if a is None else float(a) for a in q["f"]]
+            cfgs[k].use[:] = [0 if a is None else 1 for a in q["f"]]
+            bits[k] = int(q.get("bit", 0))
+        self._ck(self.L.mdp_gforce_setup(self.h, C.c_int(n), cfgs, bits))
+
+    def gforce_run(self, first):
+        self._ck(self.L.mdp_gforce_run(self.h, C.c_longlong(first)))
+
+    def gforce_state(self, k):
+        """slot k for the forces the context holds (blocking; runs their pass if no kick has yet): its energy (addforce),
+        the group's total force before the slot acted, the group's atoms, the step these belong to, the value written or
+        added per dimension, passes since setup"""
+        out = np.zeros(GFORCE_STATE_LEN)
+        self._ck(self.L.mdp_gforce_state(self.h, C.c_int(int(k)), _dp(out)))
+        return dict(energy=float(out[0]), ftotal=out[1:4].copy(), atoms=int(out[4]), step=int(out[5]), value=out[6:9].copy(),
+                    passes=int(out[9]))
+
+    def gforce_off(self):
+        self._ck(self.L.mdp_gforce_off(self.h))
 
     # ---------------- FIRE minimiser of a resident one-brick context (minimize/mdp)
     def fire_setup(self, etol, ftol, maxiter, maxeval, **modify):

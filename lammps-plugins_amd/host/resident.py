@@ -874,6 +874,32 @@ class DeviceDomain:
         self.ctx.spring_off()
         self._final_pending = False
 
+    def gforce(self, slots, first=0):
+        """Prescribed forces on groups of this domain (LAMMPS fix setforce, addforce and aveforce with constant values): a
+        list of up to four dicts as capi.Context.gforce_setup takes them -- kind ("set", "add", "ave"), f (None for a
+        dimension that is left alone), and optionally bit (the group bit in the mask of set_group; 0: every atom).  They
+        act in list order on an atom's force, behind the indenters and the springs; nothing may share atoms with an "ave"
+        in front of it.  An "add" needs the domain's image flags (track_images).  Call it behind compute(), as indent().
+        One GPU; no Nose-Hoover chain, heat sources or minimiser next to them."""
+        self._one_gpu("group forces")
+        self.ctx.gforce_setup(slots)
+        self.gforce_run(first)
+
+    def gforce_run(self, first):
+        """A further run of the slots set by gforce(), from step `first`.  A pending final half completes first, with its
+        pass; compute() again before the next step."""
+        self._run_from("gforce", first)
+
+    def gforce_state(self, k):
+        """slot k for the current forces (completes a deferred final half first): capi.Context.gforce_state"""
+        self.flush()
+        return self.ctx.gforce_state(k)
+
+    def gforce_off(self):
+        """back to the pair style's forces alone; a deferred final half completes inside mdp_gforce_off, with its pass"""
+        self.ctx.gforce_off()
+        self._final_pending = False
+
     def minimize(self, etol, ftol, maxiter, maxeval, chunk=64, **modify):
         """FIRE minimisation (LAMMPS min_style fire with its defaults; **modify: capi.FIRE_DEFAULTS) of this domain on the
         device, one GPU only; returns the final state (capi.Context.fire_state).  The velocities are zero afterwards

@@ -128,6 +128,10 @@ void MinimizeMDP::command(int narg, char **arg)
       error->all(FLERR, std::string("minimize/mdp: fix ") + modify->fix[i]->id + " (indent/mdp) is not applied by the minimiser; unfix it first");
     else if (strcmp(modify->fix[i]->style, "spring/mdp") == 0)
       error->all(FLERR, std::string("minimize/mdp: fix ") + modify->fix[i]->id + " (spring/mdp) is not applied by the minimiser; unfix it first");
+    else if (strcmp(modify->fix[i]->style, "setforce/mdp") == 0 || strcmp(modify->fix[i]->style, "addforce/mdp") == 0 ||
+             strcmp(modify->fix[i]->style, "aveforce/mdp") == 0)
+      error->all(FLERR, std::string("minimize/mdp: fix ") + modify->fix[i]->id + " (" + modify->fix[i]->style +
+                            ") is not applied by the minimiser; unfix it first");
   const int style_id = mdp_pair_style_id(force->pair);
   if (!style_id) error->all(FLERR, "minimize/mdp requires a pair style of this plugin (rebomos or aeam)");
   if (const char *e = getenv("MDP_REBOMOS_HOST_LIST"))

@@ -56,8 +56,8 @@
    (PairMDP::upload_host, mdp_hnve_set_mask), with the atoms into the brick otherwise (mdp_brick.h, mdp_md_set_mask),
    from where it comes back with them.  A fix langevin/mdp on a sub-group hands its bit over the same way
    (mdp_langevin_group), several of them on disjoint sub-groups their bits and settings together (mdp_langevin_baths), and
-   the fix heat/mdp, fix indent/mdp and fix spring/mdp fixes of a run theirs (mdp_heat_setup and its like, in setup() behind
-   the mask).  Group all sets both bits to 0 and uploads no mask for the fix's sake.  All four styles ride on this fix the
+   the fix heat/mdp, fix indent/mdp, fix spring/mdp and fix setforce/mdp, addforce/mdp, aveforce/mdp fixes of a run theirs (mdp_heat_setup and its like, in setup() behind
+   the mask).  Group all sets both bits to 0 and uploads no mask for the fix's sake.  All of these styles ride on this fix the
    same way (fix_rider_mdp.h): one block per style (mdp_riders.h) that they fill at init(), one list of the blocks
    (riders(), fix_nve_mdp.h) that setup(), post_run(), extract() and masked() walk, and one pointer, run_ctx, to the context
    of the run under way, which they and the computes read through Fix::extract("mdp_steps_ctx").  Run in the mini-host
@@ -228,6 +228,11 @@ static int on(mdp_ctx *c, const MdpSprings &b, long long first, long long)
 {
   const int rc = mdp_spring_setup(c, b.count, b.cfg, b.bit);
   return rc != MDP_OK ? rc : mdp_spring_run(c, first);
+}
+static int on(mdp_ctx *c, const MdpGforces &b, long long first, long long)
+{
+  const int rc = mdp_gforce_setup(c, b.count, b.cfg, b.bit);
+  return rc != MDP_OK ? rc : mdp_gforce_run(c, first);
 }
 static int on(mdp_ctx *c, const MdpLangevinBaths &b, long long first, long long last)
 {

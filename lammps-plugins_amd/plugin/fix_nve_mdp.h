@@ -78,12 +78,13 @@ class FixNVEMDP : public Fix {
 
   // What the fixes that ride on this one handed over (fix_rider_mdp.h; one block per style, mdp_riders.h, under the
   // Fix::extract key beside it): switched on in setup() on run_ctx, behind the groups and the mask, in the order they
-  // stand here -- heat sources (mdp_heat_setup, mdp_heat_run(beginstep)), indenters and behind them springs (the order
-  // of the two passes in front of a kick), Langevin thermostats (one: mdp_langevin_setup, mdp_langevin_group; several:
+  // stand here -- heat sources (mdp_heat_setup, mdp_heat_run(beginstep)), indenters, behind them springs and behind those the
+  // group forces (the order of the passes in front of a kick), Langevin thermostats (one: mdp_langevin_setup, mdp_langevin_group; several:
   // mdp_langevin_baths) -- and off in post_run(), which clears the blocks.  A style takes part in a run if its count > 0
   MdpHeatSources heat = {};      // "mdp_heat_sources"
   MdpIndenters indent = {};      // "mdp_indenters"
   MdpSprings spring = {};        // "mdp_springs": bricks only, the fixes refuse the host-linked mode
+  MdpGforces gforce = {};        // "mdp_gforces": fix setforce/mdp, addforce/mdp and aveforce/mdp share its slots
   MdpLangevinBaths baths = {};   // "mdp_langevin_baths"
   // f(block, key, off, against, refusal) for each of them; against: the count of the kind it cannot share a run with, or null
   template <class F> void riders(F f)
@@ -91,6 +92,8 @@ class FixNVEMDP : public Fix {
     f(heat, "mdp_heat_sources", mdp_heat_off, &baths.count, "Fix nve/mdp: heat sources (fix heat/mdp) and a thermostat (fix langevin/mdp) in one run");
     f(indent, "mdp_indenters", mdp_indent_off, &heat.count, "Fix nve/mdp: indenters (fix indent/mdp) and heat sources (fix heat/mdp) in one run");
     f(spring, "mdp_springs", mdp_spring_off, &heat.count, "Fix nve/mdp: springs (fix spring/mdp) and heat sources (fix heat/mdp) in one run");
+    f(gforce, "mdp_gforces", mdp_gforce_off, &heat.count,
+      "Fix nve/mdp: group forces (fix setforce/mdp, addforce/mdp, aveforce/mdp) and heat sources (fix heat/mdp) in one run");
     f(baths, "mdp_langevin_baths", mdp_langevin_off, (const int *) nullptr, "");
   }
   int brick_masked = 0; // this run's brick was set up with atom->mask (it comes back with the atoms)

@@ -14,8 +14,8 @@
 using namespace LAMMPS_NS;
 
 FixRiderMDP::FixRiderMDP(LAMMPS *lmp, int narg, char **arg, const char *name_, int max_, const char *key_, int min_narg,
-                         const char *usage, const char *empty_tail_)
-    : Fix(lmp, narg, arg), name(name_), max(max_), key(key_), empty_tail(empty_tail_)
+                         const char *usage, const char *empty_tail_, std::initializer_list<const char *> family_)
+    : Fix(lmp, narg, arg), name(name_), max(max_), key(key_), empty_tail(empty_tail_), family(family_.begin(), family_.end())
 {
   if (narg < min_narg) error->all(FLERR, usage);
   if (igroup < 0)
@@ -30,6 +30,22 @@ Fix *FixRiderMDP::integrator() const
   return nullptr;
 }
 
+bool FixRiderMDP::kin(const char *style) const
+{
+  if (name == style) return true;
+  for (const std::string &f : family)
+    if (f == style) return true;
+  return false;
+}
+
+std::string FixRiderMDP::kind() const
+{
+  if (family.empty()) return name;
+  std::string s;
+  for (size_t k = 0; k < family.size(); k++) s += (k == 0 ? "" : k + 1 == family.size() ? " or " : ", ") + family[k];
+  return s;
+}
+
 // From the constructor this fix is not in the list yet and is the one behind all it finds; from init() it is in the list,
 // and its slot is its position among them.  (LAMMPS constructs a fix before it removes the one whose ID it takes over.)
 int FixRiderMDP::census()
@@ -41,13 +57,13 @@ int FixRiderMDP::census()
     if (f == this) {
       listed = true;
       slot = n;
-    } else if (name != f->style || strcmp(f->id, id) == 0)
+    } else if (!kin(f->style) || strcmp(f->id, id) == 0)
       continue;
     n++;
   }
   if (!listed) n++;
   if (n > max)
-    error->all(FLERR, "Fix " + name + ": " + id + " is " + name + " fix number " + std::to_string(n) + "; fix nve/mdp takes up to " +
+    error->all(FLERR, "Fix " + name + ": " + id + " is " + kind() + " fix number " + std::to_string(n) + "; fix nve/mdp takes up to " +
                           std::to_string(max) + " of them");
   return n;
 }
@@ -91,7 +107,7 @@ Fix *FixRiderMDP::walk(std::initializer_list<const char *> refused, const std::s
   Fix *nve = nullptr;
   for (int i = 0; i < modify->nfix; i++) {
     Fix *f = modify->fix[i];
-    if (name == f->style) continue;
+    if (kin(f->style)) continue;
     for (const char *style : refused)
       if (strcmp(f->style, style) == 0) error->all(FLERR, "Fix " + name + ": fix " + before + f->id + " (" + f->style + after);
     if (strcmp(f->style, "nve/mdp") == 0) nve = f;
